@@ -35,6 +35,7 @@ PEAK_FP32_MFMA_TFLOPS = 157.3        # /opt/skills/guides/MI355X_MICROARCH.md "P
 PEAK_BF16_MFMA_TFLOPS = 2500.0       # same table, "Peak BF16/FP16 MFMA ~2.5 PF dense" (--dtype bf16 runs only)
 PMC_TRAFFIC_FILE = "r03_pmc_traffic.json"   # tools/pmc_traffic2.py: measured HBM bytes per launch, keyed by launch shape
 LAYERS = 2                            # hidden layers of the policy (test/policy.jl:9-19); 2 = the headline 2x256 MLP
+DUMP_MAX_TRANSITIONS = 1 << 20        # --dump-outputs: larger rollouts are dumped as a fixed seeded sample of transitions
 
 
 def flops_per_state(kind):
@@ -65,6 +66,30 @@ def split_backward_mfma_flops_per_state():
     to 96).  The identity-MFMA transposes and the two small fp32 MFMAs are not counted."""
     rows = 4 * QUADS
     return 2 * rows * (6 * HID * HID + 6 * HID * HID + 3 * HID * 96)
+
+
+def dump_outputs(out_dir, pol, opt, rollouts, histories):
+    """--dump-outputs DIR: what the timed path handed its caller in the last timed iteration, as DIR/<name>.npy (float32 /
+    float64) -- the trained parameters, the Adam moments, the per-epoch loss histories of ppo_train_ and the rollout's
+    [T,N] columns.  Above DUMP_MAX_TRANSITIONS transitions the columns are taken at fixed seeded flat indices t*N+n
+    (rollout_index.npy), which bounds a dump to ~31 MB.  The state rows are left out (T*N*32*F bytes); each dumped
+    probability is the policy evaluated on one."""
+    m, v, _ = opt._adam().get_state()
+    ppo_loss, entropy_loss, lr = histories
+    arrays = {"policy_params": pol.params, "adam_m": m, "adam_v": v,
+              "ppo_loss_history": np.asarray(ppo_loss, np.float64), "entropy_loss_history": np.asarray(entropy_loss, np.float64),
+              "lr_history": np.asarray(lr, np.float64)}
+    cols = {"selected_actions": rollouts.selected_actions, "selected_action_probabilities": rollouts.selected_action_probabilities,
+            "returns": rollouts.rewards, "raw_rewards": rollouts.raw_rewards, "terminal": rollouts.terminal}
+    T, N = rollouts.dims()
+    if T * N > DUMP_MAX_TRANSITIONS:
+        idx = np.sort(np.random.default_rng(0).choice(T * N, DUMP_MAX_TRANSITIONS, replace=False))
+        arrays["rollout_index"] = idx.astype(np.float64)
+        cols = {k: c.reshape(-1)[idx] for k, c in cols.items()}
+    arrays.update({k: c.astype(np.float32) for k, c in cols.items()})      # 1-based action ids <= 512: exact in float32
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline():
@@ -290,7 +315,11 @@ def main():
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak (default, BASELINE config 3): 4096 envs and a 4096-sample minibatch PER GPU; strong: the 4096 envs "
                          "and the 4096-sample global minibatch are split over the GPUs (flagged in the output)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     reduced = (args.t_steps != T_STEPS) or (args.epochs != EPOCHS)
     T_STEPS, EPOCHS = args.t_steps, args.epochs
     nonheadline = (args.dtype != "f32") or (args.envs != N_ENVS) or (args.scaling != "weak") or (args.quads != QUADS) or (args.hid != HID) or bool(args.stream) or (args.layers != LAYERS)
@@ -362,11 +391,13 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    def timed_run(n_envs, minibatch, seed_base):
-        """W warm-up + K timed PPO iterations on `n_envs` envs per rank; returns (max-over-ranks seconds, iteration fn)."""
+    def timed_run(n_envs, minibatch, seed_base, dump_dir=None):
+        """W warm-up + K timed PPO iterations on `n_envs` envs per rank; returns (max-over-ranks seconds, iteration fn).
+        dump_dir: the last timed iteration's outputs go there (dump_outputs), after the timing and before any other work."""
         env = PPO.HipVecEnv(num_envs=n_envs, Q=QUADS, max_actions=T_STEPS, seed=1234, global_offset=rank * n_envs)
         ro = PPO.BufferRollouts()
         stream_pending = []
+        last = {}
 
         def iteration(i):
             if args.stream:                              # a fresh DiskRollouts per iteration, as src/train.jl:185 does
@@ -377,7 +408,9 @@ def main():
             else:
                 PPO.collect_rollouts_steps_(ro, env, pol, T_STEPS, GAMMA)
                 ds = PPO.construct_dataset(ro)
-            PPO.ppo_train_(pol, opt, ds, EPS, minibatch, EPOCHS, ENT_W, seed=seed_base + i, parallel=dp, verbose=False)
+            hist = PPO.ppo_train_(pol, opt, ds, EPS, minibatch, EPOCHS, ENT_W, seed=seed_base + i, parallel=dp, verbose=False)
+            if dump_dir:                                 # (holds a streamed iteration's buffer until the next one replaces it)
+                last.update(rollouts=ds.rollouts, histories=hist)
             while stream_pending:                        # deferred finish (PPO_DISK_ASYNC=1): the file of THIS iteration is complete
                 PPO.disk_sync(stream_pending.pop())      # before the iteration counts as done (inside the timed region)
 
@@ -393,12 +426,14 @@ def main():
             tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
+        if dump_dir:
+            dump_outputs(dump_dir, pol, opt, last["rollouts"], last["histories"])
         return dt, iteration
 
     strong_requested = args.scaling == "strong"
     if strong_requested:                                 # the whole line is the strong-scaling figure
         N_ENVS = MINIBATCH = N_ENVS // world
-    dt, iteration = timed_run(N_ENVS, MINIBATCH, 1000)
+    dt, iteration = timed_run(N_ENVS, MINIBATCH, 1000, dump_dir=args.dump_outputs if rank == 0 else None)
 
     # ---- roofline leg: per-kernel HIP-event durations of one more iteration (outside the timed region)
     roof, kernels = None, {}

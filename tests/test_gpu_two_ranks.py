@@ -250,3 +250,47 @@ def test_bench_stream_flag(P, tmp_path):
     assert hdr[:4] == b"PPOR" and int.from_bytes(hdr[4:8], "little") == 2          # version 2: env snapshots
     assert int.from_bytes(hdr[8:16], "little") == 96                                 # N
     assert os.path.getsize(f) == 40 + 16 + 8 * 96 * (64 + 17) + 8 * 96 * 4          # header + template tag + T records + returns column
+
+
+_BENCH_REPLAY = """
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+import ppo_amd as P
+env = P.HipVecEnv(num_envs=96, Q=8, max_actions=8, seed=1234, global_offset=0)
+pol = P.HipPolicy(72, 128, 2, 4, seed=0)
+opt = P.Optimiser(P.Adam(1e-4))
+ro = P.BufferRollouts()
+for i in range(3):                                   # bench.py: warm-up iteration 0, timed iterations 1 and 2
+    P.collect_rollouts_steps_(ro, env, pol, 8, 1.0)
+    ph, eh, lr = P.ppo_train_(pol, opt, P.construct_dataset(ro), 0.05, 96, 2, 0.01, seed=1000 + i, verbose=False)
+np.savez(sys.argv[2], policy_params=pol.params, selected_actions=ro.selected_actions, returns=ro.rewards,
+         selected_action_probabilities=ro.selected_action_probabilities, ppo_loss_history=ph, entropy_loss_history=eh)
+"""
+
+
+def test_bench_dump_outputs(P, tmp_path):
+    """bench.py --dump-outputs DIR: the arrays of the LAST TIMED iteration (not of the profiling iterations after it), the
+    same from run to run, equal to the same loop replayed through the package in a fresh process."""
+    import subprocess
+    import sys
+    from test_host_logic import _run_bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for k in range(2):
+        d = str(tmp_path / ("dump%d" % k))
+        r, out = _run_bench({}, "--steps", "2", "--warmup", "1", "--envs", "96", "--t-steps", "8", "--epochs", "2", "--hid", "128",
+                            "--no-cpu-baseline", "--dump-outputs", d, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+    a, b = dumps
+    assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a), "same arguments, same outputs"
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    rep = str(tmp_path / "replay.npz")
+    r = subprocess.run([sys.executable, "-c", _BENCH_REPLAY, root, rep], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    want = np.load(rep)
+    for k in want.files:
+        assert np.array_equal(a[k], want[k]), k

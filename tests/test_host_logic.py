@@ -184,3 +184,60 @@ def test_julia_reference_driver_is_probed_not_assumed(monkeypatch):
     monkeypatch.setenv("PATH", "/nonexistent-bin")
     monkeypatch.setenv("PPO_JULIA_REFERENCE", ROOT)
     assert bench.cpu_baseline_julia() is None
+
+
+def test_bench_dump_outputs_files(monkeypatch, tmp_path):
+    """bench.dump_outputs without a GPU (stand-ins for the policy, optimiser and rollouts): every array lands as a
+    float32 / float64 .npy; above DUMP_MAX_TRANSITIONS the [T,N] columns are taken at the same seeded flat indices on
+    every call, listed in rollout_index.npy."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    T, N, n_params = 8, 12, 50
+    rng = np.random.default_rng(3)
+    actions = rng.integers(1, 129, size=(T, N))
+    probs = rng.random((T, N), dtype=np.float32)
+    returns = rng.normal(size=(T, N)).astype(np.float32)
+    raw = rng.normal(size=(T, N)).astype(np.float32)
+    done = rng.random((T, N)) < 0.1
+    params, m, v = (rng.normal(size=n_params).astype(np.float32) for _ in range(3))
+
+    class Adam:
+        def get_state(self):
+            return m, v, np.array([0.9, 0.999])
+
+    class Opt:
+        def _adam(self):
+            return Adam()
+
+    class Pol:
+        pass
+
+    class Rollouts:
+        selected_actions, selected_action_probabilities, rewards, raw_rewards, terminal = actions, probs, returns, raw, done
+
+        def dims(self):
+            return T, N
+
+    pol = Pol()
+    pol.params = params
+    hist = ([0.5, 0.25], [-4.8, -4.7], [1e-4, 1e-4])
+
+    def run(d, cap):
+        monkeypatch.setattr(bench, "DUMP_MAX_TRANSITIONS", cap)
+        bench.dump_outputs(str(d), pol, Opt(), Rollouts(), hist)
+        return {f[:-4]: np.load(os.path.join(str(d), f)) for f in os.listdir(str(d))}
+
+    full = run(tmp_path / "full", T * N)
+    assert "rollout_index" not in full
+    assert all(a.dtype in (np.float32, np.float64) for a in full.values())
+    assert np.array_equal(full["policy_params"], params) and np.array_equal(full["adam_m"], m) and np.array_equal(full["adam_v"], v)
+    assert np.array_equal(full["ppo_loss_history"], hist[0]) and np.array_equal(full["lr_history"], hist[2])
+    assert full["selected_actions"].shape == (T, N) and np.array_equal(full["selected_actions"], actions)
+    assert np.array_equal(full["returns"], returns) and np.array_equal(full["terminal"], done)
+
+    a, b = run(tmp_path / "a", 40), run(tmp_path / "b", 40)
+    idx = a["rollout_index"].astype(np.int64)
+    assert idx.size == 40 and np.unique(idx).size == 40 and np.array_equal(a["rollout_index"], b["rollout_index"])
+    assert np.array_equal(a["selected_action_probabilities"], probs.reshape(-1)[idx])
+    assert np.array_equal(a["raw_rewards"], raw.reshape(-1)[idx]) and np.array_equal(a["returns"], b["returns"])
