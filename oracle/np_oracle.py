@@ -1,7 +1,8 @@
 """Second, independent CPU restatement (numpy / torch-CPU autograd) -- TEST INFRASTRUCTURE ONLY.
 
 Written separately from oracle/ppo_oracle.c so the two can be cross-checked before anything is
-called golden.  Pure-Python loops: small cases only.
+called golden.  The scalar helpers are pure-Python loops (small cases only); the batched
+float64 gradients also serve bench-sized minibatches through step_batch_grad_chunked.
 """
 import numpy as np
 
@@ -103,8 +104,10 @@ def categorical_sample(p, u):
     return i
 
 
-def step_batch_grad_torch(params, F, HID, states, masks, actions0, p_old, adv, eps, entropy_weight, n_hidden=2):
-    """step_batch! loss (src/train.jl:35-46,54-84) differentiated by torch autograd in float64."""
+def step_batch_grad_torch(params, F, HID, states, masks, actions0, p_old, adv, eps, entropy_weight, n_hidden=2, B_global=None):
+    """step_batch! loss (src/train.jl:35-46,54-84) differentiated by torch autograd in float64.
+    B_global: divide the loss sums by this instead of the batch length (the device's forward_backward(..., B_global=)):
+    the gradient of a minibatch is then the sum of the gradients of its chunks."""
     import torch
     layers = unpack_params(params, F, HID, n_hidden)
     tl = [(torch.tensor(W, dtype=torch.float64, requires_grad=True),
@@ -124,10 +127,11 @@ def step_batch_grad_torch(params, F, HID, states, masks, actions0, p_old, adv, e
     pot = torch.tensor(np.asarray(p_old), dtype=torch.float64)
     gain = sel / pot * advt
     clip = torch.where(advt >= 0, (1.0 + eps) * advt, (1.0 - eps) * advt)
-    ppoloss = -torch.mean(torch.minimum(gain, clip))
+    mean = torch.mean if B_global is None else (lambda t: t.sum() / B_global)
+    ppoloss = -mean(torch.minimum(gain, clip))
     s = float(np.float32(1e-8))
     sp = (1.0 - s) * probs + s / A
-    ent = torch.mean(-(sp * torch.log(sp)).sum(dim=1))
+    ent = mean(-(sp * torch.log(sp)).sum(dim=1))
     entloss = -ent * entropy_weight
     (ppoloss + entloss).backward()
     g = []
@@ -186,9 +190,10 @@ def action_probabilities_bf16(params, F, HID, x, masks):
     return e / e.sum(axis=1, keepdims=True)
 
 
-def step_batch_grad_bf16(params, F, HID, states, masks, actions0, p_old, adv, eps, entropy_weight):
+def step_batch_grad_bf16(params, F, HID, states, masks, actions0, p_old, adv, eps, entropy_weight, B_global=None):
     """Gradient of the step_batch! loss (src/train.jl:35-46,54-84) in the bf16 compute mode.
-    Returns (flat grad in Flux order, ppoloss, entropy_weight*entropyloss)."""
+    Returns (flat grad in Flux order, ppoloss, entropy_weight*entropyloss).  B_global: like step_batch_grad_torch; the 1/B
+    inside dp is 1/B_global too, taken before dY is rounded to bf16 (what the device's forward kernel does)."""
     (W1, b1), (W2, b2), (W3, b3) = unpack_params(params, F, HID, 2)
     W2b, W3b = bf16_round(W2), bf16_round(W3)
     X = np.asarray(states, np.float64)
@@ -205,13 +210,15 @@ def step_batch_grad_bf16(params, F, HID, states, masks, actions0, p_old, adv, ep
     gain = psel / pod * advd
     clip = np.where(advd >= 0, (1.0 + eps) * advd, (1.0 - eps) * advd)
     unclipped = gain < clip
-    ppoloss = -np.mean(np.where(unclipped, gain, clip))
+    Bg = B if B_global is None else B_global
+    mean = np.mean if B_global is None else (lambda t: t.sum() / B_global)
+    ppoloss = -mean(np.where(unclipped, gain, clip))
     sA = float(np.float32(1e-8)) / A
     sp = p + sA
     lg = np.log(sp)
-    entloss = entropy_weight * np.mean((sp * lg).sum(axis=1))            # entropy_weight * (-H)
-    dp = (entropy_weight / B) * (lg + 1.0)
-    dp[np.arange(B), a0] += np.where(unclipped, -(advd / pod) / B, 0.0)
+    entloss = entropy_weight * mean((sp * lg).sum(axis=1))               # entropy_weight * (-H)
+    dp = (entropy_weight / Bg) * (lg + 1.0)
+    dp[np.arange(B), a0] += np.where(unclipped, -(advd / pod) / Bg, 0.0)
     dl = p * (dp - (p * dp).sum(axis=1, keepdims=True))                  # [B,A]
     dY = bf16_round(dl).reshape(B, H, 4)                                 # device: rounded once in the forward kernel
     dW3 = np.einsum("bho,bhf->of", dY, h2b)
@@ -224,3 +231,26 @@ def step_batch_grad_bf16(params, F, HID, states, masks, actions0, p_old, adv, ep
     db1 = dZ1.sum(axis=(0, 1))
     g = np.concatenate([dW1.ravel(order="F"), db1, dW2.ravel(order="F"), db2, dW3.ravel(order="F"), db3])
     return g, float(ppoloss), float(entloss)
+
+
+def batch_masks(active, Q):
+    """[B, 16 Q] action masks of a batch of active-quad bit sets (action_mask per state)."""
+    bits = (np.asarray(active, np.uint64)[:, None] >> np.arange(Q, dtype=np.uint64)) & 1
+    return np.where(np.repeat(bits, 16, axis=1) != 0, 0.0, -np.inf).astype(np.float32)
+
+
+def step_batch_grad_chunked(fn, params, F, HID, states, masks, actions0, p_old, adv, eps, entropy_weight, chunk=1024,
+                            B_global=None, **kw):
+    """Gradient of a large minibatch as the float64 sum of the gradients of its chunks, each taken with B_global = B
+    (fn: step_batch_grad_torch or step_batch_grad_bf16).  Keeps the reference's memory bounded at any minibatch size."""
+    B = len(states)
+    Bg = B if B_global is None else B_global
+    g, lp, le = None, 0.0, 0.0
+    for s in range(0, B, chunk):
+        c = slice(s, s + chunk)
+        gc, lpc, lec = fn(params, F, HID, states[c], masks[c], actions0[c], p_old[c], adv[c], eps, entropy_weight,
+                          B_global=Bg, **kw)
+        g = gc if g is None else g + gc
+        lp += lpc
+        le += lec
+    return g, lp, le

@@ -63,10 +63,11 @@ def _oracle_grad(orc, params, HID, ro, sel0, eps, ew):
 def test_split_backward_matches_fp32_kernel_and_f64(P, orc, HID, B, compact):
     """Same minibatch through both kernels: each within 2e-5 max|g| of the float64 gradient (the bar of every gradient
     test), the split form no further from float64 than a small multiple of the fp32 chain's own distance, the two within
-    fp32 rounding of each other, and the split form bitwise reproducible.  More tiles than workgroups (HID = 256: 1701 on
-    256) and fewer (70 on 512) both occur; from 1536 tiles on the HID = 256 train forward takes two tiles per workgroup pass,
-    below it one: the B = 401 case moves that switch to 200 tiles (PPO_FWD_SPLIT_T2_MIN_TILES, read per launch) -- an odd count,
-    the last pass has one tile."""
+    fp32 rounding of each other, and the split form bitwise reproducible.  More tiles than workgroups (HID = 256: 600 on 256,
+    HID = 128: 1100 on 512) and fewer (70 on 512) both occur; from 1536 tiles on the HID = 256 train forward takes two tiles per
+    workgroup pass, below it one: the B = 401 case moves that switch to 200 tiles (PPO_FWD_SPLIT_T2_MIN_TILES, read per launch)
+    -- an odd count, the last pass has one tile.  The default switch points and the minibatch sizes bench.py runs are tested in
+    tests/test_gpu_bench_shapes.py."""
     P.set_rollout_compact(compact)
     if B == 401:
         os.environ["PPO_FWD_SPLIT_T2_MIN_TILES"] = "200"

@@ -186,3 +186,77 @@ def test_rollout_ref_vs_dev_modes(orc):
             assert np.allclose(p_ref, p_dev, rtol=5e-6, atol=1e-9)
             assert ro["p_sel"][t, n] == p_dev[ro["actions"][t, n]]
     assert ro["done"].sum() >= 3
+
+
+def _grad_batch(rng, F, HID, L, Q, B):
+    """Random minibatch at H = 4 Q rows (Q = 8: 32 rows, the headline game; Q = 32: 128 rows, config 4) for the
+    float64 restatements: actions on active quads, p_old near 1/A, advantages of both signs."""
+    H = 4 * Q
+    n = HID * F + HID + (L - 1) * (HID * HID + HID) + 4 * HID + 4
+    params = (rng.normal(size=n) * 0.08).astype(np.float32)
+    states = rng.integers(-3, 7, size=(B, H, F)).astype(np.int8)
+    active = rng.integers(1, 2 ** Q, size=B, dtype=np.uint64).astype(np.uint32)
+    masks = np_oracle.batch_masks(active, Q)
+    actions0 = np.array([16 * rng.choice([q for q in range(Q) if (int(a) >> q) & 1]) + rng.integers(0, 16) for a in active])
+    p_old = rng.uniform(0.5, 2.0, B).astype(np.float32) / (16 * Q)
+    adv = (rng.normal(size=B) * 3).astype(np.float32)
+    return params, states, masks, actions0, p_old, adv
+
+
+def test_batch_masks_match_action_mask():
+    rng = np.random.default_rng(2)
+    for Q in (8, 32):
+        active = rng.integers(0, 2 ** Q, size=9, dtype=np.uint64).astype(np.uint32)
+        want = np.stack([np_oracle.action_mask([(int(a) >> q) & 1 for q in range(Q)]) for a in active])
+        assert np.array_equal(np_oracle.batch_masks(active, Q), want)
+
+
+@pytest.mark.parametrize("Q", [8, 32])
+@pytest.mark.parametrize("L", [1, 2, 3])
+def test_torch_grad_chunked_equals_unchunked(Q, L):
+    """The float64 gradient of a minibatch as the sum of its chunks' gradients (B_global = B) is the gradient of the whole
+    minibatch: the large GPU references (tests/test_gpu_bench_shapes.py) are built this way.  Ragged last chunk."""
+    rng = np.random.default_rng(10 * Q + L)
+    F, HID, B = 72, 64, 23
+    params, states, masks, a0, p_old, adv = _grad_batch(rng, F, HID, L, Q, B)
+    for eps in (0.05, 10.0):
+        g, lp, le = np_oracle.step_batch_grad_torch(params, F, HID, states, masks, a0, p_old, adv, eps, 0.01, n_hidden=L)
+        gc, lpc, lec = np_oracle.step_batch_grad_chunked(np_oracle.step_batch_grad_torch, params, F, HID, states, masks, a0,
+                                                         p_old, adv, eps, 0.01, chunk=5, n_hidden=L)
+        assert np.abs(g).max() > 0
+        assert np.abs(gc - g).max() <= 1e-12 * np.abs(g).max()
+        assert abs(lpc - lp) <= 1e-12 * (1 + abs(lp)) and abs(lec - le) <= 1e-12 * (1 + abs(le))
+        # one chunk with B_global = B is that chunk's share of the mean: B_global / B times its own-mean gradient
+        g5, lp5, _ = np_oracle.step_batch_grad_torch(params, F, HID, states[:5], masks[:5], a0[:5], p_old[:5], adv[:5], eps,
+                                                     0.01, n_hidden=L)
+        g5b, lp5b, _ = np_oracle.step_batch_grad_torch(params, F, HID, states[:5], masks[:5], a0[:5], p_old[:5], adv[:5], eps,
+                                                       0.01, n_hidden=L, B_global=B)
+        assert np.abs(g5b * B / 5 - g5).max() <= 1e-12 * np.abs(g5).max() and abs(lp5b * B / 5 - lp5) <= 1e-12 * (1 + abs(lp5))
+
+
+@pytest.mark.parametrize("Q", [8, 32])
+def test_bf16_grad_chunked_equals_unchunked(Q):
+    """bf16 restatement: with B_global the 1/B inside dp is the minibatch's before dY is rounded, so every per-sample
+    value is rounded exactly as in the whole-minibatch call and the chunk sum differs only in float64 summation order."""
+    rng = np.random.default_rng(Q)
+    F, HID, B = 72, 128, 21
+    params, states, masks, a0, p_old, adv = _grad_batch(rng, F, HID, 2, Q, B)
+    for eps in (0.05, 10.0):
+        g, lp, le = np_oracle.step_batch_grad_bf16(params, F, HID, states, masks, a0, p_old, adv, eps, 0.01)
+        gc, lpc, lec = np_oracle.step_batch_grad_chunked(np_oracle.step_batch_grad_bf16, params, F, HID, states, masks, a0,
+                                                         p_old, adv, eps, 0.01, chunk=4)
+        assert np.abs(g).max() > 0
+        assert np.abs(gc - g).max() <= 1e-12 * np.abs(g).max()
+        assert abs(lpc - lp) <= 1e-12 * (1 + abs(lp)) and abs(lec - le) <= 1e-12 * (1 + abs(le))
+
+
+def test_b_global_default_is_batch_length():
+    """B_global = None keeps the old results: bit for bit equal to B_global = len(batch) in both restatements (the
+    existing torch-vs-C and golden checks pin the None path itself)."""
+    rng = np.random.default_rng(4)
+    F, HID, B = 72, 64, 7
+    params, states, masks, a0, p_old, adv = _grad_batch(rng, F, HID, 2, 8, B)
+    for fn in (np_oracle.step_batch_grad_torch, np_oracle.step_batch_grad_bf16):
+        a = fn(params, F, HID, states, masks, a0, p_old, adv, 0.05, 0.01)
+        b = fn(params, F, HID, states, masks, a0, p_old, adv, 0.05, 0.01, B_global=B)
+        assert np.array_equal(a[0], b[0]) and a[1] == b[1] and a[2] == b[2]
