@@ -165,6 +165,41 @@ int32_t ppo_adam_set_state(ppo_adam_t opt, const float* m, const float* v, const
 int32_t ppo_adam_get_epoch_count(ppo_adam_t opt, int64_t* epochs);
 int32_t ppo_adam_set_epoch_count(ppo_adam_t opt, int64_t epochs);
 
+/* Flux.Optimiser chain (Flux 0.13 legacy Flux.Optimise) of 1..4 members, each kind at most once, in any order: the
+ * members whose `eta` get_optimizer_learning_rate multiplies (src/train.jl:155-158).  Flux.update! (src/train.jl:81)
+ * then does, per parameter: D = grad (f32); D = apply!(member, x, D) for each member in chain order; x -= D.
+ * Float64 hyper-parameters against Float32 arrays: each member's arithmetic is float64 where a float64 operand enters,
+ * and its output D (and every state array it stores) is rounded to float32:
+ *   Adam      exactly ppo_adam_create's update (m, v, float64 beta powers)
+ *   ExpDecay  D = f32(D * eta_n); at its n-th update! (n counts them, this one included) first
+ *             eta = max(eta * decay, clip) when n > start && n % decay_step == 0 && (decay_step > 1 || n == start + 1)
+ *             (Flux counts the arrays already at step n: with decay_step == 1 it decays exactly once)
+ *   Descent   D = f32(D * eta)
+ *   Momentum  v = f32(rho v - eta D); D = -v
+ *   Nesterov  d = rho*rho v - ((1 + rho) eta) D (old v, float64); v = f32(rho v - eta D); D = f32(-d)
+ *   RMSProp   acc = f32(rho acc + ((1 - rho) D) D); D = f32(D (eta / (sqrt_f32(acc) + epsilon)))
+ * hyper: n rows of 5 doubles, unused trailing entries ignored:
+ *   Adam (eta, beta1, beta2, epsilon)   ExpDecay (eta, decay, decay_step, clip, start)   Descent (eta)
+ *   Momentum (eta, rho)   Nesterov (eta, rho)   RMSProp (eta, rho, epsilon)
+ * The handle is a ppo_adam_t: ppo_train / ppo_step_batch / ppo_adam_apply take it unchanged; ppo_train's lr history is
+ * the left-to-right product of the members' etas after each epoch.  A chain of Adam alone runs ppo_adam_create's
+ * kernels.  ppo_adam_get_lr returns that product on a chain; ppo_adam_set_lr / _get_state / _set_state need a chain of
+ * Adam alone (use the member calls below).  Unknown kind: PPO_ERR_UNSUPPORTED; bad n, duplicate kind: PPO_ERR_ARG. */
+#define PPO_OPT_ADAM 1
+#define PPO_OPT_EXPDECAY 2
+#define PPO_OPT_DESCENT 3
+#define PPO_OPT_MOMENTUM 4
+#define PPO_OPT_NESTEROV 5
+#define PPO_OPT_RMSPROP 6
+int32_t ppo_optimiser_create(ppo_policy_t pol, int32_t n, const int32_t* kinds, const double* hyper, ppo_adam_t* out);
+int32_t ppo_optimiser_get_eta(ppo_adam_t opt, int32_t member, double* eta);   /* member: 0-based chain position */
+int32_t ppo_optimiser_set_eta(ppo_adam_t opt, int32_t member, double eta);
+/* member state, Flux layout (any argument may be NULL): Adam s0 = m, s1 = v, scalars = beta powers [2];
+ * Momentum / Nesterov s0 = velocity; RMSProp s0 = acc; ExpDecay count = update! calls seen (its eta: _get_eta). */
+int32_t ppo_optimiser_get_state(ppo_adam_t opt, int32_t member, float* s0, float* s1, double* scalars2, int64_t* count);
+int32_t ppo_optimiser_set_state(ppo_adam_t opt, int32_t member, const float* s0, const float* s1,
+                                const double* scalars2, const int64_t* count);
+
 /* ---------------------------------------------------------------- rollout buffer */
 /* BufferRollouts()                                          src/rollout_buffer.jl:1-22 */
 int32_t ppo_rollouts_create(ppo_env_t env, int64_t capacity_T, ppo_rollouts_t* out);

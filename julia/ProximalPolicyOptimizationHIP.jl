@@ -117,6 +117,59 @@ function HipAdam(p::HipPolicy, eta = 1e-3, beta = (0.9, 0.999), eps = 1e-8)
     HipAdam(r[], eta)
 end
 
+# Flux.Optimiser chain on the device (ppo_optimiser_create): 1 to 4 of Flux's legacy Adam, ExpDecay, Descent, Momentum,
+# Nesterov, RMSProp, each kind once, e.g. HipChain(policy, Flux.Optimiser(Flux.Adam(1e-4), Flux.ExpDecay(1.0, 0.5, 1000, 1e-6))).
+# Iterates the Flux members, so get_optimizer_learning_rate (src/train.jl:155-158) runs on it; their etas are pushed to the
+# device before each ppo_train! and the decayed ExpDecay eta is pulled back after it.
+struct HipChain; h::Ptr{Cvoid}; os::Vector{Any}; end
+Base.iterate(c::HipChain, s...) = iterate(c.os, s...)
+member_row(o::Flux.Adam) = (Int32(1), [o.eta, o.beta[1], o.beta[2], o.epsilon, 0.0])
+member_row(o::Flux.ExpDecay) = (Int32(2), [o.eta, o.decay, Float64(o.step), o.clip, Float64(o.start)])
+member_row(o::Flux.Descent) = (Int32(3), [o.eta, 0.0, 0.0, 0.0, 0.0])
+member_row(o::Flux.Momentum) = (Int32(4), [o.eta, o.rho, 0.0, 0.0, 0.0])
+member_row(o::Flux.Nesterov) = (Int32(5), [o.eta, o.rho, 0.0, 0.0, 0.0])
+member_row(o::Flux.RMSProp) = (Int32(6), [o.eta, o.rho, o.epsilon, 0.0, 0.0])
+member_row(o) = throw(ArgumentError("Optimiser member $(typeof(o)) is not supported on the device"))
+function HipChain(p::HipPolicy, opt::Flux.Optimiser)
+    1 <= length(opt.os) <= 4 || throw(ArgumentError("the device runs Optimiser chains of 1 to 4 members"))
+    rows = map(member_row, opt.os)
+    kinds, hyper = Int32[first(r) for r in rows], reduce(vcat, [last(r) for r in rows])
+    allunique(kinds) || throw(ArgumentError("each Optimiser member kind at most once on the device"))
+    r = Ref{Ptr{Cvoid}}()
+    check(ccall((:ppo_optimiser_create, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+                p.h, length(kinds), kinds, hyper, r))
+    HipChain(r[], collect(opt.os))
+end
+function push_etas!(c::HipChain)
+    for (j, o) in enumerate(c.os)
+        check(ccall((:ppo_optimiser_set_eta, LIB), Int32, (Ptr{Cvoid}, Int32, Float64), c.h, j - 1, o.eta))
+    end
+end
+function pull_etas!(c::HipChain)
+    e = Ref{Float64}()
+    for (j, o) in enumerate(c.os)
+        o isa Flux.ExpDecay || continue
+        check(ccall((:ppo_optimiser_get_eta, LIB), Int32, (Ptr{Cvoid}, Int32, Ref{Float64}), c.h, j - 1, e))
+        o.eta = e[]
+    end
+end
+# checkpoint / resume of member j (1-based): (s0, s1, scalars, count) -- Adam (m, v, beta powers), Momentum / Nesterov
+# velocity, RMSProp acc, ExpDecay its update count; n = the policy's parameter count
+function member_state(c::HipChain, j, n)
+    s0, s1, sc, cnt = zeros(Float32, n), zeros(Float32, n), zeros(2), Ref{Int64}(0)
+    check(ccall((:ppo_optimiser_get_state, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float64}, Ref{Int64}),
+                c.h, j - 1, s0, s1, sc, cnt))
+    s0, s1, sc, cnt[]
+end
+function member_state!(c::HipChain, j, s0::Vector{Float32}, s1::Vector{Float32}, sc::Vector{Float64}, cnt::Int64)
+    check(ccall((:ppo_optimiser_set_state, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float64}, Ref{Int64}),
+                c.h, j - 1, s0, s1, sc, Ref(cnt)))
+end
+opt_handle(o::HipChain) = (push_etas!(o); o.h)
+opt_handle(o) = (first(o)::HipAdam).h                  # (HipAdam(policy, eta),): the Adam-only form
+opt_done!(o::HipChain) = pull_etas!(o)
+opt_done!(o) = nothing
+
 # ---------------------------------------------------------------- env plugin methods  (:16-20)
 function PPO.state(env::HipVecEnv)
     obs = Array{Int8}(undef, env.F, env.H, env.N); act = Vector{UInt32}(undef, env.N)   # column-major [F,H,N]
@@ -219,13 +272,15 @@ end
 # rank / world / hook: data-parallel runs (one process per GPU; INTEGRATION.md section 5); single process: 0 / 1 / C_NULL
 function PPO.ppo_train!(p::HipPolicy, optimizer, r::HipRollouts, epsilon, batch_size, num_epochs, entropy_weight;
                         rank = 0, world = 1, hook = C_NULL)
-    adam = first(optimizer)::HipAdam
+    oh = opt_handle(optimizer)                         # a HipChain, or an iterable whose first member is a HipAdam
     ph, eh, lh = zeros(num_epochs), zeros(num_epochs), zeros(num_epochs)
-    check(ccall((:ppo_train, LIB), Int32,
-                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64, Int32, Float64, Int32, Ptr{Int64}, UInt64, Int32, Int32,
-                 Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
-                p.h, adam.h, r.h, epsilon, batch_size, num_epochs, entropy_weight, ADV_MODE[], C_NULL, SEED[], rank, world,
-                hook, C_NULL, ph, eh, lh))
+    status = ccall((:ppo_train, LIB), Int32,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Int64, Int32, Float64, Int32, Ptr{Int64}, UInt64, Int32, Int32,
+                    Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                   p.h, oh, r.h, epsilon, batch_size, num_epochs, entropy_weight, ADV_MODE[], C_NULL, SEED[], rank, world,
+                   hook, C_NULL, ph, eh, lh)
+    opt_done!(optimizer)                               # lr history == get_optimizer_learning_rate(optimizer) afterwards
+    check(status)
     for e in 1:num_epochs
         @printf "EPOCH : %d \t PPO LOSS : %1.4f\t ENTROPY LOSS : %1.4f \t LR : %1.1e\n" e ph[e] eh[e] lh[e]
     end

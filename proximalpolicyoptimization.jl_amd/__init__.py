@@ -19,6 +19,7 @@ Names, argument order and error behaviour follow the reference:
     PPO.ppo_train!(...)                     ppo_train_(...)
     PPO.ppo_iterate!(...)                   ppo_iterate_(...)
     Flux.Optimiser(Adam(1e-4))              Optimiser(Adam(1e-4))
+    Flux.Optimiser(Adam(), ExpDecay(...))   Optimiser(Adam(), ExpDecay(...))   (also Descent, Momentum, Nesterov, RMSProp)
 
 Plugin functions are generic: calling one on an object that does not overload it raises
 `PPOError("Function <name> needs to be overloaded")` like src/ProximalPolicyOptimization.jl:12-14.
@@ -42,7 +43,7 @@ from .disk import (DiskDataset, DiskRollouts, bson_decode_state, bson_encode_sta
                    update_, write_returns_to_disk)
 
 __all__ = [
-    "PPOError", "HipVecEnv", "HipPolicy", "Adam", "Optimiser", "StateData", "BufferRollouts", "BufferDataset",
+    "PPOError", "HipVecEnv", "HipPolicy", "Adam", "ExpDecay", "Descent", "Momentum", "Nesterov", "RMSProp", "Optimiser", "StateData", "BufferRollouts", "BufferDataset",
     "state", "reward", "is_terminal", "reset_", "step_", "action_probabilities", "batch_action_probabilities",
     "batch_state", "number_of_actions_per_state", "batch_advantage", "save_loss", "compute_returns",
     "compute_returns_tn", "gae_tn", "compute_gae_", "profile_gae", "collect_rollouts_", "collect_rollouts_steps_", "construct_dataset",
@@ -428,11 +429,63 @@ class Adam:
         return m, v, bp
 
 
+class ExpDecay:
+    """Flux legacy ExpDecay(eta, decay, decay_step, clip, start): eta = max(eta * decay, clip) every `decay_step`
+    update! calls past `start` (field `step` holds decay_step, as in Flux).  Only as a member of an Optimiser."""
+
+    def __init__(self, eta=1e-3, decay=0.1, decay_step=1000, clip=1e-4, start=0):
+        self.eta, self.decay, self.step, self.clip, self.start = float(eta), float(decay), int(decay_step), float(clip), int(start)
+
+
+class Descent:
+    """Flux legacy Descent(eta): plain gradient descent."""
+
+    def __init__(self, eta=0.1):
+        self.eta = float(eta)
+
+
+class Momentum:
+    """Flux legacy Momentum(eta, rho)."""
+
+    def __init__(self, eta=0.01, rho=0.9):
+        self.eta, self.rho = float(eta), float(rho)
+
+
+class Nesterov:
+    """Flux legacy Nesterov(eta, rho)."""
+
+    def __init__(self, eta=1e-3, rho=0.9):
+        self.eta, self.rho = float(eta), float(rho)
+
+
+class RMSProp:
+    """Flux legacy RMSProp(eta, rho, epsilon)."""
+
+    def __init__(self, eta=1e-3, rho=0.9, epsilon=1e-8):
+        self.eta, self.rho, self.epsilon = float(eta), float(rho), float(epsilon)
+
+
+# PPO_OPT_* kinds of include/ppo_hip.h and each member's hyper row (eta first)
+_CHAIN_KINDS = {
+    Adam: (1, lambda o: (o.eta, o.beta[0], o.beta[1], o.epsilon, 0.0)),
+    ExpDecay: (2, lambda o: (o.eta, o.decay, float(o.step), o.clip, float(o.start))),
+    Descent: (3, lambda o: (o.eta, 0.0, 0.0, 0.0, 0.0)),
+    Momentum: (4, lambda o: (o.eta, o.rho, 0.0, 0.0, 0.0)),
+    Nesterov: (5, lambda o: (o.eta, o.rho, 0.0, 0.0, 0.0)),
+    RMSProp: (6, lambda o: (o.eta, o.rho, o.epsilon, 0.0, 0.0)),
+}
+_STATE_KINDS = (Adam, Momentum, Nesterov, RMSProp)
+
+
 class Optimiser:
-    """Flux.Optimiser(...): iterable composite (get_optimizer_learning_rate iterates it, src/train.jl:155-158)."""
+    """Flux.Optimiser(...): iterable composite (get_optimizer_learning_rate iterates it, src/train.jl:155-158).
+    On the device: 1 to 4 members of Adam, ExpDecay, Descent, Momentum, Nesterov, RMSProp, each kind at most once, in
+    any order (include/ppo_hip.h, ppo_optimiser_create).  Optimiser(Adam(...)) keeps its Adam handle (members[0])."""
 
     def __init__(self, *members):
         self.members = list(members)
+        self._h = None
+        self._policy = None
 
     def __iter__(self):
         return iter(self.members)
@@ -442,6 +495,116 @@ class Optimiser:
         if len(adams) != 1 or len(self.members) != 1:
             raise PPOError(-4, "only Optimiser(Adam(...)) is implemented on the device")
         return adams[0]
+
+    def _adam_only(self):
+        return len(self.members) == 1 and type(self.members[0]) is Adam
+
+    def _check(self):
+        """The chain's (kinds, hyper) rows, or PPOError(PPO_ERR_UNSUPPORTED / PPO_ERR_ARG) before any device work."""
+        if not 1 <= len(self.members) <= 4:
+            raise PPOError(-4, "Optimiser: the device runs chains of 1 to 4 members, got %d" % len(self.members))
+        kinds, hyper = [], []
+        for m in self.members:
+            name = type(m).__name__
+            if not hasattr(m, "eta"):
+                raise PPOError(-4, "Optimiser member %s has no eta (get_optimizer_learning_rate cannot run it): "
+                                   "not supported on the device" % name)
+            if type(m) not in _CHAIN_KINDS:
+                raise PPOError(-4, "Optimiser member %s is not supported on the device (Adam, ExpDecay, Descent, Momentum, "
+                                   "Nesterov, RMSProp)" % name)
+            if type(m) in (type(x) for x in self.members[:len(kinds)]):
+                raise PPOError(-4, "Optimiser: member %s appears twice; each kind at most once on the device" % name)
+            if isinstance(m, ExpDecay) and m.step < 1:
+                raise PPOError(-1, "AssertionError: ExpDecay: decay_step >= 1")
+            k, row = _CHAIN_KINDS[type(m)]
+            kinds.append(k)
+            hyper.append(row(m))
+        return np.array(kinds, np.int32), np.ascontiguousarray(hyper, np.float64)
+
+    def _handle(self, policy):
+        """The ppo_adam_t of this chain for `policy`, created on first use; pushes every member's current eta."""
+        if self._adam_only():
+            return self._adam()._bind(policy)
+        kinds, hyper = self._check()
+        if self._h is None:
+            h = C.c_void_p()
+            call("ppo_optimiser_create", policy._h, len(kinds), _p(kinds, _lib.c_i32p), _p(hyper, _lib.c_f64p), C.byref(h))
+            self._h, self._policy = h, policy
+        elif self._policy is not policy:
+            raise PPOError(-1, "AssertionError: optimiser state belongs to another policy")
+        for j, m in enumerate(self.members):
+            call("ppo_optimiser_set_eta", self._h, j, float(m.eta))
+        return self._h
+
+    def _pull(self):
+        """After training: the etas ExpDecay decayed on the device back into the members."""
+        if self._h is None:
+            return
+        e = C.c_double(0)
+        for j, m in enumerate(self.members):
+            if isinstance(m, ExpDecay):
+                call("ppo_optimiser_get_eta", self._h, j, C.byref(e))
+                m.eta = e.value
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().ppo_adam_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def get_state(self):
+        """Checkpoint of a bound chain: {"epochs": epochs trained (keys the device permutation), "members": one dict per
+        member in chain order with its eta and state (Adam m, v, beta_pow; Momentum / Nesterov velocity; RMSProp acc;
+        ExpDecay its update count)}."""
+        h = self._adam()._h if self._adam_only() else self._h
+        if h is None:
+            raise PPOError(-1, "AssertionError: get_state: the optimiser has not been bound to a policy yet")
+        pol = self._adam()._policy if self._adam_only() else self._policy
+        n = pol.num_params
+        ep = C.c_int64(0)
+        call("ppo_adam_get_epoch_count", h, C.byref(ep))
+        out = []
+        for j, m in enumerate(self.members):
+            eta, cnt = C.c_double(0), C.c_int64(0)
+            s0, s1, sc = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(2, np.float64)
+            call("ppo_optimiser_get_eta", h, j, C.byref(eta))
+            call("ppo_optimiser_get_state", h, j, _p(s0, _lib.c_f32p), _p(s1, _lib.c_f32p), _p(sc, _lib.c_f64p), C.byref(cnt))
+            d = {"kind": type(m).__name__, "eta": eta.value}
+            if isinstance(m, Adam):
+                d.update(m=s0, v=s1, beta_pow=sc)
+            elif isinstance(m, (Momentum, Nesterov)):
+                d["velocity"] = s0
+            elif isinstance(m, RMSProp):
+                d["acc"] = s0
+            elif isinstance(m, ExpDecay):
+                d["count"] = int(cnt.value)
+            out.append(d)
+        return {"epochs": int(ep.value), "members": out}
+
+    def set_state(self, policy, state):
+        """Resume from get_state(): binds this chain (same member kinds, same order) to `policy` and restores it."""
+        ms = state["members"]
+        if [d["kind"] for d in ms] != [type(m).__name__ for m in self.members]:
+            raise PPOError(-1, "AssertionError: set_state: the checkpoint holds a chain of other members")
+        for m, d in zip(self.members, ms):
+            m.eta = float(d["eta"])
+        h = self._handle(policy)
+        keep = []                                          # the arrays handed over live until their call returns
+        for j, (m, d) in enumerate(zip(self.members, ms)):
+            s0 = s1 = sc = cnt = None
+            if isinstance(m, Adam):
+                keep += [np.ascontiguousarray(d["m"], np.float32), np.ascontiguousarray(d["v"], np.float32),
+                         np.ascontiguousarray(d["beta_pow"], np.float64)]
+                s0, s1, sc = _p(keep[-3], _lib.c_f32p), _p(keep[-2], _lib.c_f32p), _p(keep[-1], _lib.c_f64p)
+            elif isinstance(m, (Momentum, Nesterov, RMSProp)):
+                keep.append(np.ascontiguousarray(d["acc" if isinstance(m, RMSProp) else "velocity"], np.float32))
+                s0 = _p(keep[-1], _lib.c_f32p)
+            elif isinstance(m, ExpDecay):
+                cnt = C.byref(C.c_int64(int(d["count"])))
+            call("ppo_optimiser_set_state", h, j, s0, s1, sc, cnt)
+        call("ppo_adam_set_epoch_count", h, int(state["epochs"]))
 
 
 def get_optimizer_learning_rate(optimizer):
@@ -839,12 +1002,14 @@ def _adv_mode(advantage):
 def step_batch_(policy, optimizer, dataset, batch_indices, epsilon, entropy_weight, advantage="returns"):
     """One optimiser step on dataset[batch_indices] (1-based): gather + batch_advantage (=returns) +
     get_linear_action_index + step_batch! (src/train.jl:98-120, 54-84).  Returns (ppoloss, entropy_weight*entropyloss)."""
-    adam = optimizer._adam()
-    oh = adam._bind(policy)
+    oh = optimizer._handle(policy)
     ii = np.ascontiguousarray(np.asarray(batch_indices, np.int64) - 1)
     a, b = C.c_double(0), C.c_double(0)
-    call("ppo_step_batch", policy._h, oh, dataset.rollouts._h, _p(ii, _lib.c_i64p), ii.size, float(epsilon),
-         float(entropy_weight), _adv_mode(advantage), C.byref(a), C.byref(b))
+    try:
+        call("ppo_step_batch", policy._h, oh, dataset.rollouts._h, _p(ii, _lib.c_i64p), ii.size, float(epsilon),
+             float(entropy_weight), _adv_mode(advantage), C.byref(a), C.byref(b))
+    finally:
+        optimizer._pull()
     return a.value, b.value
 
 
@@ -863,8 +1028,7 @@ def ppo_train_(policy, optimizer, dataset, epsilon, batch_size, num_epochs, entr
     """PPO.ppo_train!(policy, optimizer, dataset, epsilon, batch_size, num_epochs, entropy_weight)
     (src/train.jl:130-153) -> (ppo_loss_history, entropy_loss_history, lr_history).
     perm: optional [num_epochs, len] 1-based permutations standing in for randperm (:93)."""
-    adam = optimizer._adam()
-    oh = adam._bind(policy)
+    oh = optimizer._handle(policy)
     n = len(dataset)
     pp = None
     if perm is not None:
@@ -879,10 +1043,13 @@ def ppo_train_(policy, optimizer, dataset, epsilon, batch_size, num_epochs, entr
     # shortest shard, identically on every rank (a local raise here would leave the other ranks in a collective)
     if world == 1 and not (1 <= batch_size <= n):
         raise PPOError(-1, "AssertionError: 1 <= batch_size <= num_data")                    # :88
-    call("ppo_train", policy._h, oh, dataset.rollouts._h, float(epsilon), int(batch_size), int(num_epochs),
-         float(entropy_weight), _adv_mode(advantage), _p(pp, _lib.c_i64p) if pp is not None else None, int(seed),
-         int(rank), int(world), fn, None,
-         _p(ph, _lib.c_f64p), _p(eh, _lib.c_f64p), _p(lh, _lib.c_f64p))
+    try:
+        call("ppo_train", policy._h, oh, dataset.rollouts._h, float(epsilon), int(batch_size), int(num_epochs),
+             float(entropy_weight), _adv_mode(advantage), _p(pp, _lib.c_i64p) if pp is not None else None, int(seed),
+             int(rank), int(world), fn, None,
+             _p(ph, _lib.c_f64p), _p(eh, _lib.c_f64p), _p(lh, _lib.c_f64p))
+    finally:
+        optimizer._pull()                                  # decayed ExpDecay etas: get_optimizer_learning_rate == lr_history
     if verbose:
         for e in range(num_epochs):                                                         # :146
             print("EPOCH : %d \t PPO LOSS : %1.4f\t ENTROPY LOSS : %1.4f \t LR : %1.1e" % (e + 1, ph[e], eh[e], lh[e]))

@@ -527,17 +527,21 @@ int32_t ppo_adam_create(ppo_policy_t pol, double eta, double beta1, double beta2
     return PPO_OK;
 }
 int32_t ppo_adam_destroy(ppo_adam_t opt) { if (opt) { (void)hipStreamSynchronize(g_stream); delete opt; } return PPO_OK; }
-int32_t ppo_adam_get_lr(ppo_adam_t opt, double* eta) { ARG_CHECK(opt && eta, "null"); *eta = opt->eta; return PPO_OK; }
-int32_t ppo_adam_set_lr(ppo_adam_t opt, double eta) { ARG_CHECK(opt, "null"); opt->eta = eta; return PPO_OK; }
+int32_t ppo_adam_get_lr(ppo_adam_t opt, double* eta) { ARG_CHECK(opt && eta, "null"); *eta = opt->lr(); return PPO_OK; }
+int32_t ppo_adam_set_lr(ppo_adam_t opt, double eta) {
+    ARG_CHECK(opt && opt->adam_only(), "adam_set_lr: null, or a chain (ppo_optimiser_set_eta)");
+    opt->eta = eta;
+    return PPO_OK;
+}
 int32_t ppo_adam_get_state(ppo_adam_t opt, float* m, float* v, double* bp) {
-    ARG_CHECK(opt, "null");
+    ARG_CHECK(opt && opt->adam_only(), "adam_get_state: null, or a chain (ppo_optimiser_get_state)");
     if (m) PPO_TRY(flat_to_host(opt->pol, m, opt->m.p));
     if (v) PPO_TRY(flat_to_host(opt->pol, v, opt->v.p));
     if (bp) { bp[0] = opt->beta_pow[0]; bp[1] = opt->beta_pow[1]; }
     return PPO_OK;
 }
 int32_t ppo_adam_set_state(ppo_adam_t opt, const float* m, const float* v, const double* bp) {
-    ARG_CHECK(opt, "null");
+    ARG_CHECK(opt && opt->adam_only(), "adam_set_state: null, or a chain (ppo_optimiser_set_state)");
     if (m) PPO_TRY(flat_to_device(opt->pol, m, opt->m.p));
     if (v) PPO_TRY(flat_to_device(opt->pol, v, opt->v.p));
     if (bp) { opt->beta_pow[0] = bp[0]; opt->beta_pow[1] = bp[1]; }
@@ -546,6 +550,103 @@ int32_t ppo_adam_set_state(ppo_adam_t opt, const float* m, const float* v, const
 
 int32_t ppo_adam_get_epoch_count(ppo_adam_t opt, int64_t* epochs) { ARG_CHECK(opt && epochs, "null"); *epochs = opt->epochs_done; return PPO_OK; }
 int32_t ppo_adam_set_epoch_count(ppo_adam_t opt, int64_t epochs) { ARG_CHECK(opt && epochs >= 0, "bad epoch count"); opt->epochs_done = epochs; return PPO_OK; }
+
+// Flux.Optimiser chain (include/ppo_hip.h): the Adam member keeps its hyper-parameters and state in the handle's own Adam
+// fields, so a chain of Adam alone is exactly a ppo_adam_create handle
+double ppo_adam_s::lr() const {
+    if (nmem == 0) return eta;
+    double p = 1.0;                                     // get_optimizer_learning_rate: prod(opt.eta for opt in optimizer)
+    for (int j = 0; j < nmem; ++j) p *= mem[j].kind == PPO_OPT_ADAM ? eta : mem[j].eta;
+    return p;
+}
+
+int32_t ppo_optimiser_create(ppo_policy_t pol, int32_t n, const int32_t* kinds, const double* hyper, ppo_adam_t* out) {
+    ARG_CHECK(pol && kinds && hyper && out, "optimiser_create: null");
+    ARG_CHECK(n >= 1 && n <= 4, "optimiser_create: a chain of 1 to 4 members");
+    for (int32_t j = 0; j < n; ++j) {
+        if (kinds[j] < PPO_OPT_ADAM || kinds[j] > PPO_OPT_RMSPROP) {
+            ppo_set_error("optimiser_create: member " + std::to_string(j) + " has an unknown kind " + std::to_string(kinds[j]));
+            return PPO_ERR_UNSUPPORTED;
+        }
+        for (int32_t k = 0; k < j; ++k) ARG_CHECK(kinds[k] != kinds[j], "optimiser_create: each member kind at most once");
+        if (kinds[j] == PPO_OPT_EXPDECAY) {
+            const double* h = hyper + 5 * (size_t)j;
+            ARG_CHECK(h[2] >= 1 && h[2] == std::floor(h[2]) && h[4] == std::floor(h[4]), "ExpDecay: integer decay_step >= 1 and start");
+        }
+    }
+    ppo_adam_s* o = new ppo_adam_s();
+    o->pol = pol; o->nmem = n;
+    o->eta = 0.0; o->beta1 = o->beta2 = o->eps = 0.0; o->beta_pow[0] = o->beta_pow[1] = 0.0;
+    int32_t s = PPO_OK;
+    for (int32_t j = 0; j < n && s == PPO_OK; ++j) {
+        const double* h = hyper + 5 * (size_t)j;
+        OptMember& e = o->mem[j];
+        e.kind = kinds[j];
+        if (e.kind == PPO_OPT_ADAM) {
+            o->eta = h[0]; o->beta1 = h[1]; o->beta2 = h[2]; o->eps = h[3];
+            o->beta_pow[0] = h[1]; o->beta_pow[1] = h[2];
+            if ((s = o->m.alloc(pol->np)) || (s = o->v.alloc(pol->np))) break;
+            (void)hipMemsetAsync(o->m.p, 0, pol->np * 4, g_stream);
+            (void)hipMemsetAsync(o->v.p, 0, pol->np * 4, g_stream);
+        } else {
+            e.eta = h[0]; e.h1 = h[1]; e.h2 = h[2]; e.h3 = h[3]; e.h4 = h[4];
+            if (e.kind == PPO_OPT_MOMENTUM || e.kind == PPO_OPT_NESTEROV || e.kind == PPO_OPT_RMSPROP) {
+                if ((s = e.s.alloc(pol->np))) break;
+                (void)hipMemsetAsync(e.s.p, 0, pol->np * 4, g_stream);
+            }
+        }
+    }
+    if (s != PPO_OK) { delete o; return s; }
+    *out = o;
+    return PPO_OK;
+}
+
+static int32_t chain_member(ppo_adam_t opt, int32_t member) {
+    ARG_CHECK(opt && member >= 0 && member < std::max(opt->nmem, 1), "optimiser: null handle or member out of range");
+    return PPO_OK;
+}
+static int32_t kind_of(ppo_adam_t opt, int32_t member) { return opt->nmem == 0 ? PPO_OPT_ADAM : opt->mem[member].kind; }
+
+int32_t ppo_optimiser_get_eta(ppo_adam_t opt, int32_t member, double* eta) {
+    PPO_TRY(chain_member(opt, member));
+    ARG_CHECK(eta, "null");
+    *eta = kind_of(opt, member) == PPO_OPT_ADAM ? opt->eta : opt->mem[member].eta;
+    return PPO_OK;
+}
+int32_t ppo_optimiser_set_eta(ppo_adam_t opt, int32_t member, double eta) {
+    PPO_TRY(chain_member(opt, member));
+    (kind_of(opt, member) == PPO_OPT_ADAM ? opt->eta : opt->mem[member].eta) = eta;
+    return PPO_OK;
+}
+int32_t ppo_optimiser_get_state(ppo_adam_t opt, int32_t member, float* s0, float* s1, double* scalars2, int64_t* count) {
+    PPO_TRY(chain_member(opt, member));
+    const int32_t k = kind_of(opt, member);
+    OptMember* e = opt->nmem ? &opt->mem[member] : nullptr;
+    if (k == PPO_OPT_ADAM) {
+        if (s0) PPO_TRY(flat_to_host(opt->pol, s0, opt->m.p));
+        if (s1) PPO_TRY(flat_to_host(opt->pol, s1, opt->v.p));
+        if (scalars2) { scalars2[0] = opt->beta_pow[0]; scalars2[1] = opt->beta_pow[1]; }
+    } else if (s0 && e->s.p) {
+        PPO_TRY(flat_to_host(opt->pol, s0, e->s.p));
+    }
+    if (count) *count = k == PPO_OPT_EXPDECAY ? e->count : 0;
+    return PPO_OK;
+}
+int32_t ppo_optimiser_set_state(ppo_adam_t opt, int32_t member, const float* s0, const float* s1, const double* scalars2,
+                                const int64_t* count) {
+    PPO_TRY(chain_member(opt, member));
+    const int32_t k = kind_of(opt, member);
+    OptMember* e = opt->nmem ? &opt->mem[member] : nullptr;
+    if (k == PPO_OPT_ADAM) {
+        if (s0) PPO_TRY(flat_to_device(opt->pol, s0, opt->m.p));
+        if (s1) PPO_TRY(flat_to_device(opt->pol, s1, opt->v.p));
+        if (scalars2) { opt->beta_pow[0] = scalars2[0]; opt->beta_pow[1] = scalars2[1]; }
+    } else if (s0 && e->s.p) {
+        PPO_TRY(flat_to_device(opt->pol, s0, e->s.p));
+    }
+    if (count && k == PPO_OPT_EXPDECAY) { ARG_CHECK(*count >= 0, "ExpDecay: negative update count"); e->count = *count; }
+    return PPO_OK;
+}
 
 // ================================================================ rollouts
 // capacity for T steps in the requested state-storage form (the other form's buffer is released: the two differ by
@@ -1157,7 +1258,7 @@ int32_t ppo_train(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, double ep
         for (int64_t i = 0; i < nb; ++i) { sp += hh[2 * i]; se += hh[2 * i + 1]; }
         if (ppo_hist) ppo_hist[ep] = sp / (double)nb;                               // unweighted mean over batches :127
         if (entropy_hist) entropy_hist[ep] = se / (double)nb;
-        if (lr_hist) lr_hist[ep] = opt->eta;                                        // :144,155-158
+        if (lr_hist) lr_hist[ep] = opt->lr();                                       // :144,155-158
     }
     int32_t f = 0;
     PPO_TRY(d2h(&f, pol->err.p, 1));

@@ -127,12 +127,27 @@ struct ppo_policy_s {
     double last_entropy_weight = 0.0;
 };
 
+// one member of a Flux.Optimiser chain (ppo_optimiser_create) other than Adam, whose hyper-parameters and state are the
+// handle's own eta / beta / m / v / beta_pow fields
+struct OptMember {
+    int32_t kind = 0;                  // PPO_OPT_*
+    double eta = 0.0, h1 = 0.0, h2 = 0.0, h3 = 0.0, h4 = 0.0;   // hyper rows of ppo_optimiser_create (eta in front)
+    int64_t count = 0;                 // ExpDecay: update! calls seen
+    DevBuf<float> s;                   // Momentum / Nesterov velocity, RMSProp acc
+};
+
 struct ppo_adam_s {
     ppo_policy_s* pol;
     double eta, beta1, beta2, eps;
     double beta_pow[2];
     int64_t epochs_done = 0;           // epochs trained through ppo_train: keys the minibatch permutation with the seed
     DevBuf<float> m, v;
+    // chain (ppo_optimiser_create): nmem members in chain order; 0 = a ppo_adam_create handle.  A chain of Adam alone
+    // runs the Adam kernels (k_reduce_adam / k_adam); every other chain the chain kernels (k_reduce_chain / k_chain_update)
+    int32_t nmem = 0;
+    OptMember mem[4];
+    bool adam_only() const { return nmem == 0 || (nmem == 1 && mem[0].kind == PPO_OPT_ADAM); }
+    double lr() const;                 // left-to-right product of the members' etas (get_optimizer_learning_rate)
 };
 
 struct DiskSink;   // ppo_disk.hip
@@ -254,9 +269,9 @@ int32_t launch_policy_fwd_bf16(ppo_policy_s* p, FwdArgs& args, int mode, int64_t
 int32_t launch_policy_rollout_persistent_bf16(ppo_policy_s* p, FwdArgs& args, int64_t N, int tps, int V);
 int32_t launch_policy_bwd_bf16(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B);
 static inline int bf16_ks1(int F) { return (F + 15) / 16; }     // layer-1 k-steps of 16 (zero padded)
-// fuse (optional): apply Adam + re-pack in the same launch (single-rank training); hist2: the per-batch loss pair of that step
+// fuse (optional): apply the optimiser (Adam, or a chain: k_reduce_chain) + re-pack in the same launch (single-rank training); hist2: the per-batch loss pair of that step
 int32_t launch_grad_reduce(ppo_policy_s* p, int64_t B, int64_t B_global, double entropy_weight, ppo_adam_s* fuse = nullptr, float* hist2 = nullptr);
-int32_t launch_adam(ppo_adam_s* o, float* hist2_or_null);
+int32_t launch_adam(ppo_adam_s* o, float* hist2_or_null);           // any handle: a chain other than Adam alone -> k_chain_update
 int32_t launch_categorical(const float* probs, const float* u, int64_t B, int64_t A, int32_t* actions, float* psel,
                            int32_t* err);
 int32_t launch_feistel_index(const int32_t* index_dev, int64_t len, uint64_t seed, uint32_t epoch, int32_t* out_dev);

@@ -1,8 +1,10 @@
 // ppo_optim.hip -- gradient slab reduction, K12 Adam (Flux legacy Adam + Flux.update!,
 // src/train.jl:81; semantics SURVEY.md Appendix A) and the re-packing of the updated parameters
-// into the MFMA A-operand fragment orders used by the forward/backward kernels.
+// into the MFMA A-operand fragment orders used by the forward/backward kernels; Flux.Optimiser chains (ExpDecay, Descent,
+// Momentum, Nesterov, RMSProp, Adam; include/ppo_hip.h) through the same reduction and re-pack.
 #include "ppo_internal.h"
 #include "ppo_device.h"
+#include <algorithm>
 
 // flat Flux-order parameter vector of Policy(F, HID, NL, 4) (test/policy.jl:9-19): W1, b1, then the NL - 1 hidden->hidden
 // layers (W, b) back to back -- layer l at offW2 + l * (HID*HID + HID) -- then W3, b3
@@ -39,13 +41,31 @@ struct AdamFuse { float* params; float* m; float* v; double eta, beta1, beta2, e
 __device__ __forceinline__ void pack_one(const ParamLayout& L, const PackPtrs& P, int64_t i, float x);
 __device__ __forceinline__ void adam_one(const AdamFuse& A, const ParamLayout& L, const PackPtrs& P, int64_t i, float g);
 
+// Flux.Optimiser chain of 1..4 members (ppo_optimiser_create; arithmetic in include/ppo_hip.h and DESIGN.md section 3):
+// passed by value, so the member loop below is unrolled over four constant slots and every branch is wave-uniform.
+// c[j]: the member's float64 scalars for this step -- Adam (eta, beta1, beta2, eps, beta1^t, beta2^t), ExpDecay (eta_n:
+// the host advanced its counter and decay), Descent (eta), Momentum / Nesterov (eta, rho), RMSProp (eta, rho, epsilon);
+// s0 / s1: its float32 state arrays at the kernels' width (Adam m / v, velocity, acc)
+struct ChainFuse {
+    float* params; float* hist2; int on; int n;
+    int kind[4];
+    double c[4][6];
+    float* s0[4]; float* s1[4];
+};
+__device__ __forceinline__ void chain_one(const ChainFuse& C, const ParamLayout& L, const PackPtrs& P, int64_t i, float g);
+__device__ __forceinline__ void fuse_one(const AdamFuse& A, const ParamLayout& L, const PackPtrs& P, int64_t i, float g) { adam_one(A, L, P, i, g); }
+__device__ __forceinline__ void fuse_one(const ChainFuse& C, const ParamLayout& L, const PackPtrs& P, int64_t i, float g) { chain_one(C, L, P, i, g); }
+
 // Block = 64 consecutive slab elements x 4 slab groups (wave g sums slabs g, g+4, g+8, ... with 8 loads in flight);
 // the four partial sums meet in LDS and are added in a fixed order.  4x the waves of a one-thread-per-element
 // layout: the 87 MB slab walk needs the memory-level parallelism (341 blocks of one wave per SIMD did 3.3 TB/s).
-// nwg_w slabs carry weight-gradient partials, nwg_s slabs the small-gradient tails (equal for the fused backward)
+// nwg_w slabs carry weight-gradient partials, nwg_s slabs the small-gradient tails (equal for the fused backward).
+// Fuse: AdamFuse (k_grad_reduce<AdamFuse>, timed as k_grad_reduce / k_reduce_adam) or ChainFuse (k_grad_reduce<ChainFuse>,
+// timed as k_reduce_chain); the Adam instantiation is the instruction stream of the former non-template kernel
+template <typename Fuse>
 __global__ __launch_bounds__(256) void k_grad_reduce(const float* __restrict__ slabs, size_t slab_stride, int nwg_w, int nwg_s, ParamLayout L,
                                                      float* __restrict__ grad, const double* __restrict__ terms, int64_t B,
-                                                     double inv_Bg, double entropy_weight, AdamFuse A, PackPtrs P) {
+                                                     double inv_Bg, double entropy_weight, Fuse A, PackPtrs P) {
     if (blockIdx.x == gridDim.x - 1) {          // the extra last block reduces the per-sample loss terms
         loss_reduce_block(terms, B, inv_Bg, entropy_weight, grad + L.np);
         if (A.on && A.hist2 && threadIdx.x == 0) { A.hist2[0] = grad[L.np]; A.hist2[1] = grad[L.np + 1]; }   // per-batch loss history (k_adam's job otherwise)
@@ -103,7 +123,7 @@ __global__ __launch_bounds__(256) void k_grad_reduce(const float* __restrict__ s
     }
     if (canon >= 0) {
         grad[canon] = s;
-        if (A.on) adam_one(A, L, P, canon, s);
+        if (A.on) fuse_one(A, L, P, canon, s);
     }
 }
 
@@ -272,6 +292,59 @@ __global__ void k_adam(float* __restrict__ params, const float* __restrict__ gra
     pack_one(L, P, i, x);
 }
 
+// Flux.update! through a chain on one parameter: D = g, D = apply!(member, x, D) in chain order, each member's D rounded
+// to float32; returns the final D (x -= D is the caller's)
+__device__ __forceinline__ float chain_delta(const ChainFuse& C, int64_t i, float g) {
+    float d = g;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (j >= C.n) break;
+        const double* c = C.c[j];
+        const double dd = (double)d;
+        const int kind = C.kind[j];
+        if (kind == PPO_OPT_ADAM) {                                        // the arithmetic of k_adam
+            float* m = C.s0[j];
+            float* v = C.s1[j];
+            const float mn = (float)(c[1] * (double)m[i] + (1.0 - c[1]) * dd);
+            const float vn = (float)(c[2] * (double)v[i] + ((1.0 - c[2]) * dd) * dd);
+            m[i] = mn; v[i] = vn;
+            d = (float)((double)mn / (1.0 - c[4]) / (sqrt((double)vn / (1.0 - c[5])) + c[3]) * c[0]);
+        } else if (kind == PPO_OPT_EXPDECAY || kind == PPO_OPT_DESCENT) {  // D .*= eta
+            d = (float)(dd * c[0]);
+        } else if (kind == PPO_OPT_MOMENTUM) {                             // v = rho v - eta D; D = -v
+            const float vn = (float)(c[1] * (double)C.s0[j][i] - c[0] * dd);
+            C.s0[j][i] = vn;
+            d = -vn;
+        } else if (kind == PPO_OPT_NESTEROV) {                             // d = rho^2 v - (1 + rho) eta D; v = rho v - eta D; D = -d
+            const double v0 = (double)C.s0[j][i];
+            const double dn = (c[1] * c[1]) * v0 - ((1.0 + c[1]) * c[0]) * dd;
+            C.s0[j][i] = (float)(c[1] * v0 - c[0] * dd);
+            d = (float)(-dn);
+        } else {                                                           // RMSProp: acc = rho acc + (1 - rho) D^2; D .*= eta / (sqrt(acc) + eps)
+            const float a = (float)(c[1] * (double)C.s0[j][i] + ((1.0 - c[1]) * dd) * dd);
+            C.s0[j][i] = a;
+            // sqrt of the Float32 array: the float64 root of a float rounds to the correctly rounded float root (53 >= 2*24 + 2)
+            const float ra = (float)sqrt((double)a);
+            d = (float)(dd * (c[0] / ((double)ra + c[2])));
+        }
+    }
+    return d;
+}
+
+__device__ __forceinline__ void chain_one(const ChainFuse& C, const ParamLayout& L, const PackPtrs& P, int64_t i, float g) {
+    const float x = C.params[i] - chain_delta(C, i, g);
+    C.params[i] = x;
+    pack_one(L, P, i, x);
+}
+
+// standalone chain update (all-reduce hook path, ppo_step_batch, ppo_adam_apply): k_adam with the chain
+__global__ void k_chain_update(const float* __restrict__ grad, ParamLayout L, PackPtrs P, ChainFuse C) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (C.hist2 && i < 2) C.hist2[i] = grad[L.np + i];   // per-batch loss history (after any all-reduce)
+    if (i >= L.np) return;
+    chain_one(C, L, P, i, grad[i]);
+}
+
 // dataset order -> minibatch order: out[i] = index[perm_epoch(i)]
 __global__ void k_feistel_index(const int32_t* __restrict__ index, int64_t len, uint64_t seed, uint32_t epoch,
                                 int32_t* __restrict__ out) {
@@ -299,17 +372,62 @@ int32_t launch_pack_params(ppo_policy_s* p) {
     return PPO_OK;
 }
 
+// one optimiser step of a chain: the members' scalars for this step (ExpDecay advances its counter and, on schedule, its eta
+// first: Flux's apply! does it before it scales the first array), then the Adam member's beta powers after the launch
+static ChainFuse chain_step(ppo_adam_s* o, float* hist2) {
+    ChainFuse C = {};
+    C.params = o->pol->params.p; C.hist2 = hist2; C.on = 1; C.n = o->nmem;
+    for (int j = 0; j < o->nmem; ++j) {
+        OptMember& e = o->mem[j];
+        double* c = C.c[j];
+        C.kind[j] = e.kind;
+        switch (e.kind) {
+        case PPO_OPT_ADAM:
+            c[0] = o->eta; c[1] = o->beta1; c[2] = o->beta2; c[3] = o->eps; c[4] = o->beta_pow[0]; c[5] = o->beta_pow[1];
+            C.s0[j] = o->m.p; C.s1[j] = o->v.p;
+            break;
+        case PPO_OPT_EXPDECAY: {   // h1 decay, h2 decay_step, h3 clip, h4 start
+            const int64_t n = ++e.count, st = (int64_t)e.h2, start = (int64_t)e.h4;
+            // Flux decays when exactly one array's counter is on schedule: once per step for decay_step > 1; with decay_step
+            // == 1 only at the first step past `start` (or at step 1, while the other arrays have no counter yet)
+            if (n > start && n % st == 0 && (st > 1 || n == start + 1 || n == 1)) e.eta = std::max(e.eta * e.h1, e.h3);
+            c[0] = e.eta;
+            break;
+        }
+        default:                   // Descent (eta), Momentum / Nesterov (eta, rho), RMSProp (eta, rho, epsilon)
+            c[0] = e.eta; c[1] = e.h1; c[2] = e.h2;
+            C.s0[j] = e.s.p;
+            break;
+        }
+    }
+    return C;
+}
+static void chain_done(ppo_adam_s* o) {
+    for (int j = 0; j < o->nmem; ++j)
+        if (o->mem[j].kind == PPO_OPT_ADAM) { o->beta_pow[0] *= o->beta1; o->beta_pow[1] *= o->beta2; }
+}
+
 // slab reduction + (one extra block) loss-term reduction in a single launch
 int32_t launch_grad_reduce(ppo_policy_s* p, int64_t B, int64_t B_global, double entropy_weight, ppo_adam_s* fuse, float* hist2) {
     ParamLayout L = layout_of(p);
     const size_t total = (size_t)L.NL2 * L.HID * L.HID + (size_t)L.HID * L.FP + (size_t)L.HID * (1 + L.NL2) + (size_t)L.HID * 4 + 4;
+    if (fuse && !fuse->adam_only()) {
+        const ChainFuse C = chain_step(fuse, hist2);
+        ProfScope ps("k_reduce_chain");
+        hipLaunchKernelGGL(k_grad_reduce<ChainFuse>, dim3((unsigned)((total + 63) / 64) + 1), dim3(256), 0, ppo_stream(), p->slabs.p,
+                           slab_floats(p->F, p->HID, p->L), p->nwg_bwd, p->nwg_small ? p->nwg_small : p->nwg_bwd, L, p->grad.p, p->loss_terms.p, B, 1.0 / (double)B_global,
+                           entropy_weight, C, packs_of(p));
+        HIP_TRY(hipGetLastError());
+        chain_done(fuse);
+        return PPO_OK;
+    }
     AdamFuse A = {};
     if (fuse) {
         A.params = p->params.p; A.m = fuse->m.p; A.v = fuse->v.p; A.eta = fuse->eta; A.beta1 = fuse->beta1; A.beta2 = fuse->beta2;
         A.eps = fuse->eps; A.bp1 = fuse->beta_pow[0]; A.bp2 = fuse->beta_pow[1]; A.hist2 = hist2; A.on = 1;
     }
     ProfScope ps(fuse ? "k_reduce_adam" : "k_grad_reduce");
-    hipLaunchKernelGGL(k_grad_reduce, dim3((unsigned)((total + 63) / 64) + 1), dim3(256), 0, ppo_stream(), p->slabs.p,
+    hipLaunchKernelGGL(k_grad_reduce<AdamFuse>, dim3((unsigned)((total + 63) / 64) + 1), dim3(256), 0, ppo_stream(), p->slabs.p,
                        slab_floats(p->F, p->HID, p->L), p->nwg_bwd, p->nwg_small ? p->nwg_small : p->nwg_bwd, L, p->grad.p, p->loss_terms.p, B, 1.0 / (double)B_global,
                        entropy_weight, A, packs_of(p));
     HIP_TRY(hipGetLastError());
@@ -320,6 +438,15 @@ int32_t launch_grad_reduce(ppo_policy_s* p, int64_t B, int64_t B_global, double 
 int32_t launch_adam(ppo_adam_s* o, float* hist2) {
     ppo_policy_s* p = o->pol;
     ParamLayout L = layout_of(p);
+    if (!o->adam_only()) {
+        const ChainFuse C = chain_step(o, hist2);
+        ProfScope ps("k_chain_update");
+        hipLaunchKernelGGL(k_chain_update, dim3((unsigned)((L.np + 255) / 256)), dim3(256), 0, ppo_stream(), p->grad.p, L,
+                           packs_of(p), C);
+        HIP_TRY(hipGetLastError());
+        chain_done(o);
+        return PPO_OK;
+    }
     ProfScope ps("k_adam");
     hipLaunchKernelGGL(k_adam, dim3((unsigned)((L.np + 255) / 256)), dim3(256), 0, ppo_stream(), p->params.p, p->grad.p,
                        o->m.p, o->v.p, L, packs_of(p), o->eta, o->beta1, o->beta2, o->eps, o->beta_pow[0],
