@@ -447,10 +447,11 @@ int32_t ppo_policy_create(int32_t F, int32_t hidden_user, int32_t num_hidden_lay
         (s = p->b2p.alloc((size_t)(NL2 > 0 ? NL2 : 1) * hidden)) ||
         (s = p->w3p.alloc((size_t)hidden * PPO_OUT)) || (s = p->b3.alloc(PPO_OUT)) || (s = p->grad.alloc(p->np + 2)) ||
         (s = p->err.alloc(1))) { delete p; return s; }
-    if (num_hidden_layers == 2 && F == 72) {             // + 16 KiB: the operand ring of the last k-steps reads ahead (up to 12 KiB)
-        if ((s = p->w2x.alloc((size_t)3 * hidden * hidden + 8192))) { delete p; return s; }
+    if (num_hidden_layers == 2 && F == 72) {             // zero padding: the operand rings of the last k-steps read ahead (bf16 elements here)
+        if ((s = p->w2x.alloc((size_t)3 * hidden * hidden + PPO_X6_W2_PAD_BYTES / 2))) { delete p; return s; }
         (void)hipMemsetAsync(p->w2x.p, 0, p->w2x.n * 2, g_stream);
-        if ((s = p->w2fx.alloc((size_t)3 * hidden * hidden + 8192)) || (s = p->w1x.alloc((size_t)(hidden / 32) * 5 * 3 * 512 + 4096))) { delete p; return s; }
+        if ((s = p->w2fx.alloc((size_t)3 * hidden * hidden + PPO_X6_W2_PAD_BYTES / 2)) ||
+            (s = p->w1x.alloc((size_t)(hidden / 32) * 5 * 3 * 512 + PPO_X6_W1_PAD_BYTES / 2))) { delete p; return s; }
         (void)hipMemsetAsync(p->w2fx.p, 0, p->w2fx.n * 2, g_stream);
         (void)hipMemsetAsync(p->w1x.p, 0, p->w1x.n * 2, g_stream);       // inputs 72 .. 79 of the last k-step stay zero
     }
@@ -1153,6 +1154,15 @@ int32_t ppo_last_losses(ppo_policy_t pol, double* ppoloss, double* entropyloss) 
     PPO_TRY(d2h(t, pol->grad.p + pol->np, 2));
     if (ppoloss) *ppoloss = t[0];
     if (entropyloss) *entropyloss = t[1];
+    return PPO_OK;
+}
+
+// diagnostic for the tests (not part of include/ppo_hip.h): what the last training forward left per tile of its minibatch, in
+// minibatch order -- the dL/dlogits rows [tiles][32][4] and the two loss terms [tiles][2]
+int32_t ppo_debug_train_outputs(ppo_policy_t pol, int64_t tiles, float* dY, double* loss_terms) {
+    ARG_CHECK(pol && tiles >= 1 && tiles <= pol->cap_tiles, "ppo_debug_train_outputs: tiles out of range");
+    if (dY) PPO_TRY(d2h(dY, pol->dY.p, (size_t)tiles * 128));
+    if (loss_terms) PPO_TRY(d2h(loss_terms, pol->loss_terms.p, (size_t)tiles * 2));
     return PPO_OK;
 }
 

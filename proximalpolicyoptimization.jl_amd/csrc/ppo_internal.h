@@ -10,6 +10,11 @@
 #define PPO_OUT 4   // actions per half-edge (test/quad_game_utilities.jl:39,95)
 #define PPO_TPL 36  // template rows; F = 72
 #define PPO_PACK_PAD (16 * 64 * 4)   // floats of zero tail padding behind each packed weight stream (prefetch over-read)
+// bytes of zero tail padding behind the split-fp32 (bf16x6) piece streams.  W2 (w2x: backward, w2fx: train forward): the last
+// round of an operand ring re-issues a ring's depth of 1 KiB pieces past the last wave's stream (static_asserts at the rings).
+// W1 (w1x): layer 1's ring stops at the stream's end; the padding is slack
+#define PPO_X6_W2_PAD_BYTES 16384
+#define PPO_X6_W1_PAD_BYTES 8192
 
 // ---------------------------------------------------------------- host-side error plumbing
 void ppo_set_error(const std::string& msg);

@@ -34,7 +34,6 @@
 #include "ppo_internal.h"
 #include "ppo_device.h"
 #include <cstdlib>
-#include <type_traits>
 
 #include "ppo_x6.h"
 typedef float pk2 __attribute__((ext_vector_type(2)));
@@ -76,19 +75,6 @@ struct XCfg {
 // it (0).  Off: the loads have to land before the barrier that ends the tile (see the loop), and the pieces issued last
 // would make that barrier wait for them.
 #define PPO_X6_DMA_SPREAD 0
-#endif
-// A/B knob (make -C csrc xprio): wave priority raised while a wave runs its MFMA loops (bit 0: the dH1 chain, bit 1: dW2), so that
-// the SIMD partner's vector phases (splits, small gradients) do not take issue slots from it.  Not measured yet: off.
-#ifndef PPO_X6_PRIO
-#define PPO_X6_PRIO 0
-#endif
-#ifndef PPO_X6_ZPIPE
-#define PPO_X6_ZPIPE 0
-#endif
-// A/B knob (make -C csrc xnodangle): the last ring round of the dH1 chain does not issue the reloads that run past the stream.
-// Not measured yet: off.
-#ifndef PPO_X6_NODANGLE
-#define PPO_X6_NODANGLE 0
 #endif
 #ifndef PPO_X6_RING
 #define PPO_X6_RING 6
@@ -342,9 +328,6 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_bwd_x6(BwdXArgs a) {
         if (grads_first) small_grads();
         XSTAMP(4);
         {
-#if PPO_X6_PRIO & 1
-            __builtin_amdgcn_s_setprio(2);
-#endif
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
@@ -364,79 +347,41 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_bwd_x6(BwdXArgs a) {
             // slots repeat (RD = 3: 1, RD = 6: 2, RD = 4: 4), so every slot index below is a compile-time constant
             constexpr int RU = (RD % 3 == 0) ? RD / 3 : RD;
             static_assert(KS % RU == 0 && (3 * RU) % RD == 0, "ring rounds");
+            static_assert(RD * 1024 <= PPO_X6_W2_PAD_BYTES, "the last ring round reads RD pieces past the end of the W2 stream");
             unsigned zo = (unsigned)lane * 16u;
             asm volatile("" : "+v"(zo));
             const char* zp = fragZ2 + zo;
             const unsigned lo16 = zo;
-#if PPO_X6_ZPIPE
-            // A/B knob: the dZ2 pieces of the next k-step are read in front of the current one's six MFMAs (12 more registers: only
-            // where the budget allows, i.e. HID = 128); the last read runs one k-step past the fragments (inside the LDS block)
-            constexpr bool ZP = HID <= 128;
-#else
-            constexpr bool ZP = false;
-#endif
-            uint4 zc[3] = {}, zn[3] = {};
-            if (ZP) {
-                zc[0] = *reinterpret_cast<const uint4*>(zp); zc[1] = *reinterpret_cast<const uint4*>(zp + 1024);
-                zc[2] = *reinterpret_cast<const uint4*>(zp + 2048);
-            }
-            // one ring round (RU k-steps).  LAST: the round whose reloads would run past the wave's stream -- with PPO_X6_NODANGLE those
-            // loads are not issued (their registers are reused right behind the loop, and overwriting a register with a load in
-            // flight costs a vmcnt wait: one exposed L2 latency per tile)
-            auto chain_round = [&](auto last_c) {
-                constexpr bool LAST = decltype(last_c)::value;
+            // one ring round (RU k-steps); the last round's reloads run RD KiB past the wave's stream (padding / next wave's stream)
+#pragma unroll 1
+            for (int k0 = 0; k0 < KS; k0 += RU) {
 #pragma unroll
                 for (int u = 0; u < RU; ++u) {
                     const int s0 = (3 * u + 0) % RD, s1 = (3 * u + 1) % RD, s2 = (3 * u + 2) % RD;
-                    // stream entry reloaded into slot s<pc>: 3 (k0 + u) + pc + RD, k0 = KS - RU in the last round
-                    const bool ld0 = !LAST || 3 * (KS - RU + u) + 0 + RD < 3 * KS;
-                    const bool ld1 = !LAST || 3 * (KS - RU + u) + 1 + RD < 3 * KS;
-                    const bool ld2 = !LAST || 3 * (KS - RU + u) + 2 + RD < 3 * KS;
-                    uint4 z_h, z_m, z_l;
-                    if (ZP) {
-                        zn[0] = *reinterpret_cast<const uint4*>(zp + ((u + 1) * 3 + 0) * 1024);
-                        zn[1] = *reinterpret_cast<const uint4*>(zp + ((u + 1) * 3 + 1) * 1024);
-                        zn[2] = *reinterpret_cast<const uint4*>(zp + ((u + 1) * 3 + 2) * 1024);
-                        __builtin_amdgcn_sched_barrier(0);
-                        z_h = zc[0]; z_m = zc[1]; z_l = zc[2];
-                    } else {
-                        z_h = *reinterpret_cast<const uint4*>(zp + (u * 3 + 0) * 1024);
-                        z_m = *reinterpret_cast<const uint4*>(zp + (u * 3 + 1) * 1024);
-                        z_l = *reinterpret_cast<const uint4*>(zp + (u * 3 + 2) * 1024);
-                    }
+                    const uint4 z_h = *reinterpret_cast<const uint4*>(zp + (u * 3 + 0) * 1024);
+                    const uint4 z_m = *reinterpret_cast<const uint4*>(zp + (u * 3 + 1) * 1024);
+                    const uint4 z_l = *reinterpret_cast<const uint4*>(zp + (u * 3 + 2) * 1024);
                     accs = x_mfma(z_h, ring[s0], accs);
                     __builtin_amdgcn_sched_barrier(0);
-                    if (ld0) ring[s0] = *reinterpret_cast<const uint4*>(wn + lo16);   // (without PPO_X6_NODANGLE the last round reads RD KiB ahead: padding / next wave's stream)
+                    ring[s0] = *reinterpret_cast<const uint4*>(wn + lo16);
                     __builtin_amdgcn_sched_barrier(0);
                     accs = x_mfma(z_m, ring[s1], accs);
                     accs = x_mfma(z_h, ring[s1], accs);
                     __builtin_amdgcn_sched_barrier(0);
-                    if (ld1) ring[s1] = *reinterpret_cast<const uint4*>(wn + 1024 + lo16);
+                    ring[s1] = *reinterpret_cast<const uint4*>(wn + 1024 + lo16);
                     __builtin_amdgcn_sched_barrier(0);
                     accs = x_mfma(z_l, ring[s2], accs);
                     accs = x_mfma(z_m, ring[s2], accs);
                     acc = x_mfma(z_h, ring[s2], acc);
                     __builtin_amdgcn_sched_barrier(0);
-                    if (ld2) ring[s2] = *reinterpret_cast<const uint4*>(wn + 2048 + lo16);
+                    ring[s2] = *reinterpret_cast<const uint4*>(wn + 2048 + lo16);
                     wn += 3 * 1024;
                     __builtin_amdgcn_sched_barrier(0);
-                    if (ZP) { zc[0] = zn[0]; zc[1] = zn[1]; zc[2] = zn[2]; }
                 }
                 zp += RU * 3 * 1024;
-            };
-#if PPO_X6_NODANGLE
-#pragma unroll 1
-            for (int k0 = 0; k0 < KS - RU; k0 += RU) chain_round(std::false_type{});
-            chain_round(std::true_type{});
-#else
-#pragma unroll 1
-            for (int k0 = 0; k0 < KS; k0 += RU) chain_round(std::false_type{});
-#endif
+            }
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = acc[r] + accs[r];
-#if PPO_X6_PRIO & 1
-            __builtin_amdgcn_s_setprio(0);
-#endif
             XSTAMP(5);
             // acc: dH1, lane = feature 32w + j, register r <-> tile row (r&3) + 8(r>>2) + 4h.  dZ1 = dH1 . lrelu'(H1): the sign
             // of H1 from the first piece of its image, read transposed (block rows 8g + 4h .. +3 = registers 4g .. 4g+3)
@@ -553,9 +498,6 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_bwd_x6(BwdXArgs a) {
                 b[2] = x_tr_frag(i0 + 2 * NT * 2048 + tb[s][0], i0 + 2 * NT * 2048 + tb[s][1]);
             };
             XSTAMP(9);
-#if PPO_X6_PRIO & 2
-            __builtin_amdgcn_s_setprio(2);
-#endif
             uint4 bc[3], bn[3];
             load_b(0, bc);
 #pragma unroll
@@ -581,9 +523,6 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_bwd_x6(BwdXArgs a) {
                 for (int p = 0; p < 3; ++p) bc[p] = bn[p];
             }
         }
-#if PPO_X6_PRIO & 2
-        __builtin_amdgcn_s_setprio(0);
-#endif
         XSTAMP(10);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // this wave's LDS-DMA (and register prefetch) of the next tile has landed ...
         __syncthreads();                                            // ... and only behind this barrier are its landing zones read

@@ -20,45 +20,10 @@
 // 0.211 -> 0.142 ms, 2048 0.110 -> 0.075, 1024 0.059 -> 0.039, 512 0.031 -> 0.023.  ppo_set_bwd_split_bf16(0) or
 // PPO_FWD_SPLIT_MAX_TILES=0 select the fp32-MFMA forward.
 #include "ppo_policy_tail.h"
-#include <type_traits>
 #include "ppo_x6.h"
 #include <cstdlib>
 
-#ifndef PPO_FX6_RING
-#define PPO_FX6_RING 6                // W2 piece fragments in flight ahead of layer 2 (3 per k-step)
-#endif
-#ifndef PPO_FX6_ACC3
-#define PPO_FX6_ACC3 1                // 1: one accumulator per term level (3); 0: leading + small (2)
-#endif
 #define X6F_LANE() unsigned ln = (unsigned)lane; asm volatile("" : "+v"(ln)); const int j = (int)(ln & 31u), h = (int)(ln >> 5); (void)j; (void)h
-
-// A/B knob (make -C csrc fsidx): the one- and two-tile train forwards read their transition ids (the two-tile one also the active word of its tail) through the
-// scalar cache instead of vector loads + readfirstlane, each of which waits for vmcnt(0) -- every store and load in flight.
-// Not measured yet: off.
-#ifndef PPO_FX6_SIDX
-#define PPO_FX6_SIDX 0
-#endif
-// A/B knob (make -C csrc fzpipe): layer 2 of the two-tile train forward reads the H1 pieces one (k-step, tile) ahead of their MFMAs
-// (today each set is read right in front of its six MFMAs: two LDS latencies per k-step that only the SIMD partner can hide).
-// Not measured yet: off.
-#ifndef PPO_FX6_ZPIPE
-#define PPO_FX6_ZPIPE 0
-#endif
-// A/B knob (make -C csrc fxearly; implies the scalar-cache ids): the next pass's state rows are requested right after this pass's are
-// converted, behind a W1 ring that holds all 15 pieces -- vmcnt counts in order, so where they are issued today (in front of barrier 1,
-// behind the W2 ring fill) the first MFMA of layer 2 waits for them: one HBM latency per pass on all eight waves.  Not measured yet: off.
-#ifndef PPO_FX6_XEARLY
-#define PPO_FX6_XEARLY 0
-#endif
-#if PPO_FX6_XEARLY
-#undef PPO_FX6_SIDX
-#define PPO_FX6_SIDX 1
-#endif
-// A/B knob (make -C csrc fnodangle): the last ring round of layer 2 of the two-tile train forward does not issue the reloads that run
-// past the stream.  Not measured yet: off.
-#ifndef PPO_FX6_NODANGLE
-#define PPO_FX6_NODANGLE 0
-#endif
 
 template <int HID>
 struct FXCfg {
@@ -173,8 +138,9 @@ __global__ __launch_bounds__(HID * 2, 4) void k_policy_fwd_train_x6(FwdArgs a, c
             }
         }
         // the W2 piece ring of layer 2 is in flight across the barrier; so are the next tile's state rows
-        constexpr int RD = PPO_FX6_RING;
+        constexpr int RD = 6;                                           // W2 piece fragments in flight ahead of layer 2 (3 per k-step)
         static_assert(RD % 3 == 0 && KS % (RD / 3) == 0, "ring rounds");
+        static_assert(RD * 1024 <= PPO_X6_W2_PAD_BYTES, "the last ring round reads RD pieces past the end of the W2 stream");
         uint4 ring[RD];
         {
             unsigned lo = (unsigned)lane * 16u;
@@ -186,14 +152,7 @@ __global__ __launch_bounds__(HID * 2, 4) void k_policy_fwd_train_x6(FwdArgs a, c
         {
             unsigned ln2 = (unsigned)lane;
             asm volatile("" : "+v"(ln2));
-#if PPO_FX6_SIDX
-            {
-                const int32_t* const ip = a.idx + ntile;
-                asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(sid) : "s"(ip) : "memory");
-            }
-#else
             sid = __builtin_amdgcn_readfirstlane(a.idx[ntile]);
-#endif
             load_x(x_by_tile ? ntile : (int64_t)sid, ln2);
         }
         __syncthreads();                                                // (1) every layer-1 tile is in LDS
@@ -210,10 +169,9 @@ __global__ __launch_bounds__(HID * 2, 4) void k_policy_fwd_train_x6(FwdArgs a, c
             // themselves and meet the leading sum in two fp32 additions at the end.  Inside one MFMA the 16 products and the
             // accumulator are aligned to the largest of them before they are added (tools/microbench/mfma_bf16_accumulate.hip):
             // small terms fed into the leading accumulator would lose their low bits 96 times per output
-            f32x16 accm, accl_;
+            f32x16 accm, accl;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { accm[r] = 0.0f; accl_[r] = 0.0f; }
-            f32x16& accl = PPO_FX6_ACC3 ? accl_ : accm;
+            for (int r = 0; r < 16; ++r) { accm[r] = 0.0f; accl[r] = 0.0f; }
             const unsigned lo16 = ln * 16u;
             const char* zp = frag + lo16;
             const char* wn = w2s + (size_t)RD * 1024;
@@ -244,7 +202,7 @@ __global__ __launch_bounds__(HID * 2, 4) void k_policy_fwd_train_x6(FwdArgs a, c
                 zp += (RD / 3) * 3 * 1024;
             }
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = acc[r] + (PPO_FX6_ACC3 ? accm[r] + accl_[r] : accm[r]);
+            for (int r = 0; r < 16; ++r) acc[r] = acc[r] + (accm[r] + accl[r]);
             asm volatile("" : "+v"(acc));
             lrelu16(acc);
             float4* dst = a.act2 + ((size_t)tile * NT + w) * 4 * 64;
@@ -301,6 +259,7 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
     using C = FXTCfg<HID, T>;
     constexpr int F = C::F, NT = C::NT, KS = C::KS, K1 = C::K1;
     static_assert(T <= NT, "one tail wave per tile");
+    static_assert(T == 2, "two scalar id loads per pass; waves 0 and 1 run the tails");
     extern __shared__ __attribute__((aligned(16))) char smem_c[];
     char* const frag = smem_c + C::oFr;                                    // [T][feature tile][k-step 2][piece 3][64 lanes][16 B]
     float4* const sP = reinterpret_cast<float4*>(smem_c + C::oP);          // [T][NT][64] layer-3 partial dots
@@ -315,6 +274,8 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
 #else
 #define FXSTAMP(i) do { } while (0)
 #endif
+    // b3 once per kernel (the loss tail adds it to every tile's logits)
+    const float b3_0 = a.b3[0], b3_1 = a.b3[1], b3_2 = a.b3[2], b3_3 = a.b3[3];
     for (int i = tid; i < 2 * NT * 16; i += NT * 64) sW3p[i] = a.w3p[i];
     for (int i = tid; i < NT * 8; i += NT * 64) { sB1[i] = a.b1p[i]; sB2[i] = a.b2p[i]; }
     __syncthreads();
@@ -324,35 +285,17 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
     uint2 xr[T][K1];
     auto load_x = [&](int i, int64_t rec, unsigned ln) {
         const char* row = reinterpret_cast<const char*>(a.states) + (size_t)rec * 32 * F + (ln & 31u) * (unsigned)F + (ln >> 5) * 8u;
-#if PPO_FX6_XEARLY
-        // every load unconditional (the padding lanes of the last k-step re-read the row's first bytes and mask them with a value
-        // the compiler cannot see through): a load under an exec mask counts as "maybe not issued" in the compiler's vmcnt
-        // arithmetic, and the waits of layer 1 would then include the first state-row loads
-        unsigned keep = (ln >> 5) ? 0u : 0xFFFFFFFFu;
-        asm volatile("" : "+v"(keep));
-#pragma unroll
-        for (int s = 0; s < K1; ++s) {
-            const bool last = (s == K1 - 1);
-            unsigned off = (last && (ln >> 5)) ? 0u : (unsigned)(16 * s);
-            if (last) asm volatile("" : "+v"(off));
-            const uint2 v = *reinterpret_cast<const uint2*>(row + off);
-            xr[i][s] = last ? make_uint2(v.x & keep, v.y & keep) : v;
-        }
-#else
 #pragma unroll
         for (int s = 0; s < K1; ++s) {
             const bool pad = (s == K1 - 1) && (ln >> 5);
             const uint2 v = *reinterpret_cast<const uint2*>(row + (pad ? 0 : 16 * s));
             xr[i][s] = pad ? make_uint2(0u, 0u) : v;
         }
-#endif
     };
     // tile i of group g is g*T + i; a group that runs past the minibatch re-does the last tile and discards it
     auto tile_of = [&](int64_t g, int i) { const int64_t t = g * T + i; return t < a.B ? t : a.B - 1; };
-#if PPO_FX6_SIDX
     // transition ids of a pass through the scalar cache, both in one wait (a vector load + readfirstlane waits on vmcnt(0), i.e.
-    // on every activation store and operand load the wave has in flight, twice per pass)
-    static_assert(T == 2, "two scalar loads per pass");
+    // on every activation store and operand load the wave has in flight)
     int cid[T] = {0, 0}, nid[T] = {0, 0};
     auto sload_ids = [&](int64_t g, int (&id)[T]) {
         const int32_t* const ip0 = a.idx + tile_of(g, 0);
@@ -360,26 +303,29 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
         asm volatile("s_load_dword %0, %2, 0x0\n\ts_load_dword %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
                      : "=&s"(id[0]), "=&s"(id[1]) : "s"(ip0), "s"(ip1) : "memory");
     };
+    // what the loss tail of a pass reads -- the active word, action, old probability and advantage of the tile of wave w (waves
+    // >= T fetch tile 0's and never use them) -- requested one pass ahead, right behind that pass's state rows: vector loads, so
+    // they land with the rows, whose wait layer 2 pays anyway (scalar loads would share lgkmcnt with the LDS traffic: the next
+    // LDS wait behind them would wait for their memory round trip).  The tail then has no memory round trip left: before, it
+    // waited on idx (vmcnt(0), behind the H2 stores), then active, then actions / p_old / adv, then b3, one after another
+    uint32_t tact = 0u, nact = 0u;
+    TailPre tpre = {0, 0.0f, 0.0f}, npre = {0, 0.0f, 0.0f};
+    auto load_tail_in = [&](const int (&id)[T], uint32_t& act, TailPre& pre) {
+        const int32_t s = w == 1 ? id[1] : id[0];
+        act = a.active[s]; pre.ab = a.actions[s]; pre.po = a.p_old[s]; pre.adv = a.adv[s];
+    };
     if ((int64_t)blockIdx.x * T < a.B) {
         sload_ids(blockIdx.x, cid);
 #pragma unroll
         for (int i = 0; i < T; ++i) load_x(i, x_by_tile ? tile_of(blockIdx.x, i) : (int64_t)cid[i], (unsigned)lane);
+        load_tail_in(cid, tact, tpre);
     }
-#else
-    if ((int64_t)blockIdx.x * T < a.B) {
-#pragma unroll
-        for (int i = 0; i < T; ++i) {
-            const int64_t t = tile_of(blockIdx.x, i);
-            load_x(i, x_by_tile ? t : (int64_t)__builtin_amdgcn_readfirstlane(a.idx[t]), (unsigned)lane);
-        }
-    }
-#endif
     for (int64_t g = blockIdx.x; g * T < a.B; g += gridDim.x) {
         // ================= layer 1: H1 tile w of the T states
         {
             X6F_LANE();
             unsigned lo16 = ln * 16u;
-            constexpr int R1 = PPO_FX6_XEARLY ? 3 * K1 : 8;          // XEARLY: every W1 piece up front, no reload younger than the X loads below
+            constexpr int R1 = 8;
             uint4 ring[R1];
 #pragma unroll
             for (int q = 0; q < R1; ++q) ring[q] = *reinterpret_cast<const uint4*>(w1s + (lo16 + (unsigned)q * 1024u));
@@ -402,20 +348,6 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
                     xb[i][s] = make_uint4(x_perm(v[0], v[1]), x_perm(v[2], v[3]), x_perm(v[4], v[5]), x_perm(v[6], v[7]));
                 }
             }
-#if PPO_FX6_XEARLY
-            // the next pass's state rows leave for HBM here, as soon as this pass's are converted: they are younger than every W1
-            // piece (all loaded above), so no wait in layer 1 includes them, and layer 1 + the H1 epilogue (3-4 k clocks) pass before
-            // the first wait that does (the W2 ring in layer 2).  Issued in front of barrier 1, as before, that wait came
-            // a few hundred clocks after them.
-            {
-                __builtin_amdgcn_sched_barrier(0);
-                const int64_t gn = ((g + gridDim.x) * T < a.B) ? g + gridDim.x : g;
-                sload_ids(gn, nid);
-#pragma unroll
-                for (int i = 0; i < T; ++i) load_x(i, x_by_tile ? tile_of(gn, i) : (int64_t)nid[i], ln);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-#endif
 #pragma unroll
             for (int st = 0; st < 3 * K1; ++st) {
 #pragma unroll
@@ -463,6 +395,7 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
         FXSTAMP(1);
         constexpr int RD = 6;
         static_assert(KS % (RD / 3) == 0, "ring rounds");
+        static_assert(RD * 1024 <= PPO_X6_W2_PAD_BYTES, "the last ring round reads RD pieces past the end of the W2 stream");
         uint4 ring[RD];
         {
             unsigned lo = (unsigned)lane * 16u;
@@ -470,24 +403,15 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
 #pragma unroll
             for (int q = 0; q < RD; ++q) ring[q] = *reinterpret_cast<const uint4*>(w2s + (lo + (unsigned)q * 1024u));
         }
-#if !PPO_FX6_XEARLY
         {
             const int64_t gn = ((g + gridDim.x) * T < a.B) ? g + gridDim.x : g;
             unsigned ln2 = (unsigned)lane;
             asm volatile("" : "+v"(ln2));
-#if PPO_FX6_SIDX
             sload_ids(gn, nid);
 #pragma unroll
             for (int i = 0; i < T; ++i) load_x(i, x_by_tile ? tile_of(gn, i) : (int64_t)nid[i], ln2);
-#else
-#pragma unroll
-            for (int i = 0; i < T; ++i) {
-                const int64_t t = tile_of(gn, i);
-                load_x(i, x_by_tile ? t : (int64_t)__builtin_amdgcn_readfirstlane(a.idx[t]), ln2);
-            }
-#endif
+            load_tail_in(nid, nact, npre);
         }
-#endif
         FXSTAMP(2);
         __syncthreads();                                                // (1) every layer-1 tile of the T states is in LDS
         FXSTAMP(3);
@@ -508,66 +432,6 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
             const unsigned lo16 = ln * 16u;
             const char* zp = frag + lo16;
             const char* wn = w2s + (size_t)RD * 1024;
-#if PPO_FX6_ZPIPE
-            // the H1 pieces of the NEXT (k-step, tile) are read from the LDS in front of the six MFMAs of the current one (one
-            // set of lookahead, pinned), instead of right in front of the MFMAs that use them; the last set reads one k-step
-            // past this tile's fragments (the next tile's, or the partial-dot buffer: inside the LDS block, never used)
-            uint4 zc[3], zn[3];
-            auto load_z = [&](const char* zb, uint4 (&z)[3]) {
-                z[0] = *reinterpret_cast<const uint4*>(zb);
-                z[1] = *reinterpret_cast<const uint4*>(zb + 1024);
-                z[2] = *reinterpret_cast<const uint4*>(zb + 2048);
-            };
-            load_z(zp, zc);
-#endif
-#if PPO_FX6_NODANGLE
-            // one ring round (RD / 3 k-steps).  LAST (PPO_FX6_NODANGLE): the round whose reloads would run past the wave's stream does
-            // not issue them -- the ring registers are reused right behind the loop, and overwriting a register with a load in flight
-            // costs a vmcnt(0) wait there, which then also waits for the H2 stores of the first tile
-            auto l2_round = [&](auto last_c) {
-                constexpr bool LAST = decltype(last_c)::value;
-#pragma unroll
-                for (int u = 0; u < RD / 3; ++u) {
-                    const uint4 wl = ring[3 * u + 0], wm = ring[3 * u + 1], wh = ring[3 * u + 2];
-#pragma unroll
-                    for (int i = 0; i < T; ++i) {
-#if PPO_FX6_ZPIPE
-                        load_z(i + 1 < T ? zp + (size_t)(i + 1) * NT * 6 * 1024 + u * 3 * 1024 : zp + (u + 1) * 3 * 1024, zn);
-                        __builtin_amdgcn_sched_barrier(0);
-                        const uint4 z_h = zc[0], z_m = zc[1], z_l = zc[2];
-#else
-                        const char* zi = zp + (size_t)i * NT * 6 * 1024;
-                        const uint4 z_h = *reinterpret_cast<const uint4*>(zi + (u * 3 + 0) * 1024);
-                        const uint4 z_m = *reinterpret_cast<const uint4*>(zi + (u * 3 + 1) * 1024);
-                        const uint4 z_l = *reinterpret_cast<const uint4*>(zi + (u * 3 + 2) * 1024);
-#endif
-                        accs[i] = x_mfma(wl, z_h, accs[i]);
-                        accs[i] = x_mfma(wm, z_m, accs[i]);
-                        accs[i] = x_mfma(wm, z_h, accs[i]);
-                        accs[i] = x_mfma(wh, z_l, accs[i]);
-                        accs[i] = x_mfma(wh, z_m, accs[i]);
-                        acc[i] = x_mfma(wh, z_h, acc[i]);
-#if PPO_FX6_ZPIPE
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int q = 0; q < 3; ++q) zc[q] = zn[q];
-#endif
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (!LAST) {
-                        ring[3 * u + 0] = *reinterpret_cast<const uint4*>(wn + lo16);          // (without PPO_FX6_NODANGLE the last round reads RD KiB ahead: padding / next wave's stream)
-                        ring[3 * u + 1] = *reinterpret_cast<const uint4*>(wn + 1024 + lo16);
-                        ring[3 * u + 2] = *reinterpret_cast<const uint4*>(wn + 2048 + lo16);
-                        wn += 3 * 1024;
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                zp += (RD / 3) * 3 * 1024;
-            };
-#pragma unroll 1
-            for (int k0 = 0; k0 < KS - RD / 3; k0 += RD / 3) l2_round(std::false_type{});
-            l2_round(std::true_type{});
-#else
 #pragma unroll 1
             for (int k0 = 0; k0 < KS; k0 += RD / 3) {
 #pragma unroll
@@ -575,27 +439,16 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
                     const uint4 wl = ring[3 * u + 0], wm = ring[3 * u + 1], wh = ring[3 * u + 2];
 #pragma unroll
                     for (int i = 0; i < T; ++i) {
-#if PPO_FX6_ZPIPE
-                        load_z(i + 1 < T ? zp + (size_t)(i + 1) * NT * 6 * 1024 + u * 3 * 1024 : zp + (u + 1) * 3 * 1024, zn);
-                        __builtin_amdgcn_sched_barrier(0);
-                        const uint4 z_h = zc[0], z_m = zc[1], z_l = zc[2];
-#else
                         const char* zi = zp + (size_t)i * NT * 6 * 1024;
                         const uint4 z_h = *reinterpret_cast<const uint4*>(zi + (u * 3 + 0) * 1024);
                         const uint4 z_m = *reinterpret_cast<const uint4*>(zi + (u * 3 + 1) * 1024);
                         const uint4 z_l = *reinterpret_cast<const uint4*>(zi + (u * 3 + 2) * 1024);
-#endif
                         accs[i] = x_mfma(wl, z_h, accs[i]);
                         accs[i] = x_mfma(wm, z_m, accs[i]);
                         accs[i] = x_mfma(wm, z_h, accs[i]);
                         accs[i] = x_mfma(wh, z_l, accs[i]);
                         accs[i] = x_mfma(wh, z_m, accs[i]);
                         acc[i] = x_mfma(wh, z_h, acc[i]);
-#if PPO_FX6_ZPIPE
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int q = 0; q < 3; ++q) zc[q] = zn[q];
-#endif
                     }
                     __builtin_amdgcn_sched_barrier(0);
                     ring[3 * u + 0] = *reinterpret_cast<const uint4*>(wn + lo16);          // the last round reads RD KiB ahead (padding / next wave's stream)
@@ -606,7 +459,6 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
                 }
                 zp += (RD / 3) * 3 * 1024;
             }
-#endif
             FXSTAMP(4);
 #pragma unroll
             for (int i = 0; i < T; ++i) {
@@ -641,32 +493,21 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
         if (w < T && g * T + w < a.B) {                                 // wave i runs the loss tail of tile i
             X6F_LANE();
             const int64_t tile = g * T + w;
-#if PPO_FX6_SIDX
             const int32_t sidw = w == 0 ? cid[0] : cid[1];
-            uint32_t act;
-            {
-                const uint32_t* const ap = a.active + sidw;
-                asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(act) : "s"(ap) : "memory");
-            }
-#else
-            const int32_t sidw = __builtin_amdgcn_readfirstlane(a.idx[tile]);
-            const uint32_t act = a.active[sidw];
-#endif
             const float4* sPi = sP + (size_t)w * NT * 64;
             float4 s = sPi[ln];
 #pragma unroll
             for (int u = 1; u < NT; ++u) { const float4 q4 = sPi[u * 64 + ln]; s.x += q4.x; s.y += q4.y; s.z += q4.z; s.w += q4.w; }
             float l[1][4];
-            l[0][0] = (s.x + __shfl_xor(s.x, 32)) + a.b3[0];
-            l[0][1] = (s.y + __shfl_xor(s.y, 32)) + a.b3[1];
-            l[0][2] = (s.z + __shfl_xor(s.z, 32)) + a.b3[2];
-            l[0][3] = (s.w + __shfl_xor(s.w, 32)) + a.b3[3];
-            policy_tail<2, 1, false>(a, tile, sidw, act, l, (int)ln, j, h);
+            l[0][0] = (s.x + __shfl_xor(s.x, 32)) + b3_0;
+            l[0][1] = (s.y + __shfl_xor(s.y, 32)) + b3_1;
+            l[0][2] = (s.z + __shfl_xor(s.z, 32)) + b3_2;
+            l[0][3] = (s.w + __shfl_xor(s.w, 32)) + b3_3;
+            policy_tail<2, 1, false>(a, tile, sidw, tact, l, (int)ln, j, h, 0u, 0, &tpre);
         }
         FXSTAMP(7);
-#if PPO_FX6_SIDX
         cid[0] = nid[0]; cid[1] = nid[1];
-#endif
+        tact = nact; tpre = npre;
     }
 #ifdef PPO_FX6_STAMP
     if (a.stamps && lane == 0 && (w == 0 || w == NT - 1))
