@@ -23,7 +23,8 @@
  *  - one engine per HOST THREAD: the device (ppo_device_init), the stream (ppo_set_stream), the kernel timers, the RCCL
  *    communicator and the error text are thread-local, so a process may run several engines side by side (one thread per
  *    GPU); a handle belongs to the thread that created it and is not re-entrant.  The ppo_set_* tuning knobs are
- *    process-wide.
+ *    process-wide.  Each starts at its PPO_* environment variable, read once at load, else at its built-in default;
+ *    passing -1 to its setter restores that starting value.
  */
 #ifndef PPO_HIP_H
 #define PPO_HIP_H
@@ -61,16 +62,17 @@ int32_t ppo_device_synchronize(void);
 int32_t ppo_device_count(int32_t* out);
 /* rollout execution: 0 = three launches per step (observe, policy forward + sample, step!), 1 = ONE launch for the
  * whole T-step rollout wherever the shape is covered (envs are independent: each wavefront walks its envs through all
- * steps with the env state in LDS), -1 (default) = automatic: one launch for Q = 8 envs, per-step launches otherwise.
- * Same results bit for bit; per-step launches are always used while a disk sink is attached. */
+ * steps with the env state in LDS), -1 = the value at load (PPO_ROLLOUT_PERSISTENT, else automatic: one launch for
+ * Q = 8 envs, per-step launches otherwise).  Same results bit for bit; per-step launches are always used while a disk
+ * sink is attached. */
 int32_t ppo_set_rollout_persistent(int32_t mode);
 /* state storage of engine-collected rollouts (R4, src/rollout_buffer.jl:1-22: the reference boxes every state):
  * 0 = expanded observation rows [H][F] int8 per transition (2304 B for Q = 8), 1 = compact: the env snapshot the rows
  * are derived from (score[V] + degree[V] int8 = 64 B for Q = 8, plus the active-quad word) -- the train forward
- * re-derives the rows exactly as state(env) does, the getters expand on demand; -1 (default) = automatic: compact when
- * the expanded rollout would exceed 32 GiB (PPO_COMPACT_AUTO_BYTES; below that the rows are kept because re-deriving
- * them costs the train forward 3 % in fp32 and 17 % in bf16 mode) or while a disk sink is attached (the streamed record
- * shrinks 28x).  Same results bit for bit.  Host-supplied rollouts (ppo_rollouts_set) are always expanded. */
+ * re-derives the rows exactly as state(env) does, the getters expand on demand; -1 = the value at load
+ * (PPO_ROLLOUT_COMPACT, else automatic: compact when the expanded rollout would exceed 32 GiB (PPO_COMPACT_AUTO_BYTES;
+ * below that the rows are kept because re-deriving them costs the train forward 3 % in fp32 and 17 % in bf16 mode) or
+ * while a disk sink is attached (the streamed record shrinks 28x)).  Same results bit for bit.  Host-supplied rollouts (ppo_rollouts_set) are always expanded. */
 int32_t ppo_set_rollout_compact(int32_t mode);
 
 /* ---------------------------------------------------------------- standalone ops (parity entry points) */
@@ -258,7 +260,8 @@ int32_t ppo_forward_backward(ppo_policy_t pol, ppo_rollouts_t ro, const int64_t*
 /* Which backward kernel a minibatch takes (same gradient, different reduction tree: results agree to fp32 rounding):
  * up to `tiles` 32-row tiles the three-product form (dZ kernel + output-stationary split-K weight-gradient kernel: no
  * per-workgroup gradient slabs, the fixed cost that dominates a small optimiser step), above it the fused kernel that
- * keeps every weight gradient resident in MFMA accumulators.  Default 384 (-1 restores it), 0 = always fused.  While the
+ * keeps every weight gradient resident in MFMA accumulators.  Default PPO_BWD_SMALL_MAX_TILES, else 384 (-1 restores
+ * it), 0 = always fused.  While the
  * split-fp32 training pass is on (ppo_set_bwd_split_bf16, the default) its fused backward is faster at every size and the
  * threshold that applies is PPO_BWD_SMALL_MAX_TILES_SPLIT (default 0). */
 int32_t ppo_set_bwd_small_max_tiles(int64_t tiles);
@@ -266,22 +269,27 @@ int32_t ppo_set_bwd_small_max_tiles(int64_t tiles);
  * dW1 += dZ1^T X) run on the bf16 matrix pipe as SPLIT-fp32 products -- every fp32 operand is the exact sum of three
  * bfloat16 pieces, six piece products (fp32 accumulation) carry a product to one fp32 rounding -- instead of on the 16x
  * slower fp32 matrix instructions; 0 = the pure fp32-MFMA kernel; -1 = the default (environment PPO_BWD_SPLIT_BF16, else
- * on).  Same inputs, same gradient slab; gradients agree with the other form to fp32 rounding and meet the same 2e-5 max|g|
+ * on).  The same switch selects the split-fp32 train forward for minibatches up to PPO_FWD_SPLIT_MAX_TILES states.  Same inputs, same gradient slab; gradients agree with the other form to fp32 rounding and meet the same 2e-5 max|g|
  * bar against the float64 restatement. */
 int32_t ppo_set_bwd_split_bf16(int32_t mode);
 /* Small minibatches (the per-GPU shard of a strong-scaling run): up to `tiles` 32-row tiles the train forward, the loss and
  * the backward-data pass of a tile run in ONE workgroup (k_policy_train_tile: nothing but the operands of the weight-
  * gradient products leaves the CU) followed by the split-K weight-gradient kernel, instead of the separate forward and
  * backward launches.  Same gradient to fp32 rounding (the layer-3 partial sums are added in another order), bitwise
- * reproducible.  -1 restores the default, 0 = never. */
+ * reproducible.  Default PPO_TRAIN_TILE_MAX_TILES, else 0 (-1 restores it), 0 = never. */
 int32_t ppo_set_train_tile_max_tiles(int64_t tiles);
 /* Likewise for the train forward: minibatches of up to `states` states (H = 32) give every state to 2 or 4 waves instead
  * of one, so a minibatch smaller than the chip's 1024 SIMDs still fills it (logits agree with the one-wave kernel to
- * fp32 rounding: the layer-3 partial sums are added in a different order).  Default 512 (-1 restores it), 0 = never. */
+ * fp32 rounding: the layer-3 partial sums are added in a different order).  Default PPO_FWD_SPLIT_MAX_STATES, else 512
+ * (-1 restores it), 0 = never. */
 int32_t ppo_set_fwd_split_max_states(int64_t states);
+/* The split-fp32 train forward (ppo_set_bwd_split_bf16) of an H = 32 minibatch at kernel width `hid` (128 or 256) takes
+ * its two-tiles-per-pass form from `tiles` 32-row tiles on.  Default PPO_FWD_SPLIT_T2_MIN_TILES_128 / PPO_FWD_SPLIT_T2_MIN_TILES,
+ * else 1024 / 1536 (-1 restores it), 0 = never.  Same results bit for bit. */
+int32_t ppo_set_fwd_split_t2_min_tiles(int32_t hid, int64_t tiles);
 /* And for the one-launch rollout: up to `envs` resident envs (Q = 8, fp32) every env is walked by 2 or 4 waves instead of
  * one.  Unlike the train forward this split is BIT-EXACT (the layer-3 fmaf chain is handed from wave to wave in tile
- * order), so it changes nothing but the time.  Default 512 (-1 restores it), 0 = never. */
+ * order), so it changes nothing but the time.  Default PPO_ROLLOUT_SPLIT_MAX_ENVS, else 512 (-1 restores it), 0 = never. */
 int32_t ppo_set_rollout_split_max_envs(int64_t envs);
 /* Flux.update!(optimizer, weights, grad)                    src/train.jl:81 */
 int32_t ppo_adam_apply(ppo_adam_t opt, ppo_policy_t pol);

@@ -94,45 +94,54 @@ def device_count():
 
 def set_rollout_persistent(on=None):
     """Rollout execution: True = one launch per rollout (each wavefront walks its envs through all T steps) wherever
-    covered, False = three launches per step, None = automatic (default: one launch for Q = 8 envs).  Bit-identical
-    results either way."""
+    covered, False = three launches per step, None = the value at load (PPO_ROLLOUT_PERSISTENT, else automatic: one launch
+    for Q = 8 envs).  Bit-identical results either way."""
     call("ppo_set_rollout_persistent", -1 if on is None else int(bool(on)))
 
 
 def set_rollout_compact(on=None):
     """State storage of engine-collected rollouts: True = compact env snapshots (64 B per transition for Q = 8; the train
-    forward re-derives the observation rows), False = expanded observations (2304 B), None = automatic (compact above
-    32 GiB of expanded states or while streaming to disk).  Bit-identical results either way."""
+    forward re-derives the observation rows), False = expanded observations (2304 B), None = the value at load
+    (PPO_ROLLOUT_COMPACT, else automatic: compact above 32 GiB of expanded states or while streaming to disk).
+    Bit-identical results either way."""
     call("ppo_set_rollout_compact", -1 if on is None else int(bool(on)))
 
 
 def set_bwd_small_max_tiles(tiles=None):
     """Minibatches of up to `tiles` 32-row tiles use the three-product backward (no per-workgroup gradient slabs), larger
-    ones the fused kernel.  None = default (384), 0 = always the fused kernel."""
+    ones the fused kernel.  None = the value at load (PPO_BWD_SMALL_MAX_TILES, else 384), 0 = always the fused kernel."""
     call("ppo_set_bwd_small_max_tiles", -1 if tiles is None else int(tiles))
 
 
 def set_bwd_split_bf16(mode=None):
     """fp32 policies: True = the fused backward's three big products as split-fp32 ("bf16x6") products on the bf16 matrix
-    pipe, False = the pure fp32-MFMA kernel, None = default (PPO_BWD_SPLIT_BF16, else on)."""
+    pipe, False = the pure fp32-MFMA kernel, None = the value at load (PPO_BWD_SPLIT_BF16, else on)."""
     call("ppo_set_bwd_split_bf16", -1 if mode is None else int(bool(mode)))
 
 
 def set_train_tile_max_tiles(tiles=None):
     """Minibatches of up to `tiles` 32-row tiles run forward + loss + backward-data of each tile in one workgroup
-    (k_policy_train_tile) followed by the split-K weight-gradient kernel.  None = default, 0 = never."""
+    (k_policy_train_tile) followed by the split-K weight-gradient kernel.  None = the value at load
+    (PPO_TRAIN_TILE_MAX_TILES, else 0), 0 = never."""
     call("ppo_set_train_tile_max_tiles", -1 if tiles is None else int(tiles))
 
 
 def set_fwd_split_max_states(states=None):
-    """Minibatches of up to `states` states use the train forward that gives each state to 2 or 4 waves.  None = default
-    (512), 0 = always one wave per state."""
+    """Minibatches of up to `states` states use the train forward that gives each state to 2 or 4 waves.  None = the value
+    at load (PPO_FWD_SPLIT_MAX_STATES, else 512), 0 = always one wave per state."""
     call("ppo_set_fwd_split_max_states", -1 if states is None else int(states))
 
 
+def set_fwd_split_t2_min_tiles(hid, tiles=None):
+    """Split-fp32 train forward at kernel width `hid` (128 or 256): minibatches of at least `tiles` 32-row tiles take its
+    two-tiles-per-pass form.  None = the value at load (PPO_FWD_SPLIT_T2_MIN_TILES_128 / PPO_FWD_SPLIT_T2_MIN_TILES, else
+    1024 / 1536), 0 = never."""
+    call("ppo_set_fwd_split_t2_min_tiles", int(hid), -1 if tiles is None else int(tiles))
+
+
 def set_rollout_split_max_envs(envs=None):
-    """One-launch rollouts of up to `envs` envs give every env to 2 or 4 waves (bit-identical results).  None = default
-    (512), 0 = always one wave per env."""
+    """One-launch rollouts of up to `envs` envs give every env to 2 or 4 waves (bit-identical results).  None = the value at
+    load (PPO_ROLLOUT_SPLIT_MAX_ENVS, else 512), 0 = always one wave per env."""
     call("ppo_set_rollout_split_max_envs", -1 if envs is None else int(envs))
 
 

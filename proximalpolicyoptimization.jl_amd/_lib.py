@@ -94,6 +94,7 @@ SIGNATURES = {
     "ppo_set_bwd_split_bf16": [C.c_int32],
     "ppo_set_train_tile_max_tiles": [C.c_int64],
     "ppo_set_fwd_split_max_states": [C.c_int64],
+    "ppo_set_fwd_split_t2_min_tiles": [C.c_int32, C.c_int64],
     "ppo_set_rollout_split_max_envs": [C.c_int64],
     "ppo_adam_apply": [H, H],
     "ppo_last_losses": [H, c_f64p, c_f64p],

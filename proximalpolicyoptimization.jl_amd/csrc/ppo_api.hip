@@ -295,23 +295,16 @@ int32_t ppo_env_dims(ppo_env_t env, int64_t* N, int32_t* H, int32_t* F, int32_t*
     return PPO_OK;
 }
 
-// -1 = auto (persistent where it is the faster form: Q = 8, wavefront-parallel env update), 0 = off, 1 = on wherever covered
-static int g_rollout_persistent = [] { const char* v = std::getenv("PPO_ROLLOUT_PERSISTENT"); return (v && (v[0] == '0' || v[0] == '1')) ? v[0] - '0' : -1; }();
-int32_t ppo_set_rollout_persistent(int32_t mode) { g_rollout_persistent = mode < 0 ? -1 : (mode != 0); return PPO_OK; }
-
-// state storage of engine-collected rollouts: -1 = automatic (compact env snapshots when the expanded observations of
-// the requested rollout would exceed PPO_COMPACT_AUTO_BYTES -- default 32 GiB: re-deriving the rows costs the train
-// forward 3 % in fp32 and 17 % in bf16 mode, so below that the 288 GB of HBM are spent on speed -- or when a disk sink is
-// attached: the stream then carries 64 + 4 instead of 2304 + 4 state bytes per env-step for Q = 8), 0 = always
-// expanded, 1 = always compact
-static int g_rollout_compact = [] { const char* v = std::getenv("PPO_ROLLOUT_COMPACT"); return (v && (v[0] == '0' || v[0] == '1')) ? v[0] - '0' : -1; }();
-int32_t ppo_set_rollout_compact(int32_t mode) { g_rollout_compact = mode < 0 ? -1 : (mode != 0); return PPO_OK; }
+// state storage of engine-collected rollouts: automatic (rollout_compact = -1): compact env snapshots when the expanded
+// observations of the requested rollout would exceed PPO_COMPACT_AUTO_BYTES -- default 32 GiB: re-deriving the rows costs
+// the train forward 3 % in fp32 and 17 % in bf16 mode, so below that the 288 GB of HBM are spent on speed -- or when a disk
+// sink is attached: the stream then carries 64 + 4 instead of 2304 + 4 state bytes per env-step for Q = 8
 static bool want_compact(const ppo_rollouts_s* ro, int64_t T) {
+    const PpoKnobs& k = ppo_knobs();
     if (ro->V == 0) return false;                             // created by shape: no env snapshot form
-    if (g_rollout_compact >= 0) return g_rollout_compact == 1;
+    if (k.rollout_compact >= 0) return k.rollout_compact == 1;
     if (ro->sink) return true;
-    static const double limit = [] { const char* v = std::getenv("PPO_COMPACT_AUTO_BYTES"); return v ? atof(v) : 32.0 * 1024 * 1024 * 1024; }();
-    return (double)T * (double)ro->N * ro->H * ro->F > limit;
+    return (double)T * (double)ro->N * ro->H * ro->F > k.compact_auto_bytes;
 }
 
 int32_t ppo_env_set_strict_sampling(ppo_env_t env, int32_t strict) { ARG_CHECK(env, "null env"); env->strict_sampling = strict ? 1 : 0; return PPO_OK; }
@@ -738,7 +731,8 @@ int32_t ppo_collect_rollouts(ppo_rollouts_t ro, ppo_env_t env, ppo_policy_t pol,
     // Q = 32, whose update still runs on one lane.  ppo_set_rollout_persistent / PPO_ROLLOUT_PERSISTENT=0|1 override.
     // With a disk sink attached the rollout is a CHAIN of such launches, a few steps each: the finished steps of launch k
     // are copied device -> pinned host on the copy stream while launch k + 1 runs.
-    const bool persistent_ok = g_rollout_persistent == 1 || (g_rollout_persistent < 0 && env->Q == 8);
+    const int32_t persistent = ppo_knobs().rollout_persistent;
+    const bool persistent_ok = persistent == 1 || (persistent < 0 && env->Q == 8);
     int32_t ps = PPO_ERR_UNSUPPORTED;
     PPO_TRY(disk_sink_begin(ro, T));
     if (persistent_ok && !ro->sink) ps = launch_policy_rollout_persistent(pol, env, ro, T, record_probs);
@@ -1019,30 +1013,6 @@ int32_t ppo_rollouts_compute_gae(ppo_rollouts_t ro, const float* values, double 
     return PPO_OK;
 }
 
-// minibatches up to this many 32-row tiles take the three-product backward (ppo_policy_bwd_small.hip).  Measured on
-// MI355X (HID = 256): 7.6 % faster per PPO iteration at 256 tiles, level with the fused kernel at
-// 512, 6 % slower at 1024 -- so the default switches between the two at 384.  PPO_BWD_SMALL_MAX_TILES overrides (0 = never).
-static int64_t g_bwd_small_max_tiles = [] { const char* v = std::getenv("PPO_BWD_SMALL_MAX_TILES"); return v ? (int64_t)atoll(v) : (int64_t)384; }();
-
-int32_t ppo_set_bwd_small_max_tiles(int64_t tiles) { g_bwd_small_max_tiles = tiles < 0 ? 384 : tiles; return PPO_OK; }
-
-// minibatches up to this many tiles run forward + loss + backward-data of each tile in one workgroup (k_policy_train_tile)
-// and the weight gradients as a split-K product on operand-layout tiles.  PPO_TRAIN_TILE_MAX_TILES overrides (0 = never).
-#ifndef PPO_TRAIN_TILE_DEFAULT
-#define PPO_TRAIN_TILE_DEFAULT 0
-#endif
-static int64_t g_train_tile_max_tiles = [] { const char* v = std::getenv("PPO_TRAIN_TILE_MAX_TILES"); return v ? (int64_t)atoll(v) : (int64_t)PPO_TRAIN_TILE_DEFAULT; }();
-int32_t ppo_set_train_tile_max_tiles(int64_t tiles) { g_train_tile_max_tiles = tiles < 0 ? PPO_TRAIN_TILE_DEFAULT : tiles; return PPO_OK; }
-
-// fused backward: weight-gradient products as split-fp32 ("bf16x6") MFMAs (ppo_policy_bwd_x6.hip).  PPO_BWD_SPLIT_BF16 overrides.
-#ifndef PPO_BWD_SPLIT_DEFAULT
-#define PPO_BWD_SPLIT_DEFAULT 1
-#endif
-static int bwd_split_default() { const char* v = std::getenv("PPO_BWD_SPLIT_BF16"); return v ? (atoi(v) != 0) : PPO_BWD_SPLIT_DEFAULT; }
-static int g_bwd_split = bwd_split_default();
-int ppo_bwd_split_enabled() { return g_bwd_split; }
-int32_t ppo_set_bwd_split_bf16(int32_t mode) { g_bwd_split = mode < 0 ? bwd_split_default() : (mode != 0); return PPO_OK; }
-
 // ================================================================ training
 // B = number of 32-row tiles of the minibatch (states * H/32)
 static int32_t train_reserve(ppo_policy_s* p, int64_t B, bool compact = false) {
@@ -1075,40 +1045,23 @@ static int32_t forward_backward_dev(ppo_policy_s* pol, ppo_rollouts_s* ro, const
         PPO_TRY(launch_adv_normalise(adv, idx_dev, B, pol->adv_col.p));
         adv = pol->adv_col.p;
     }
-    // small minibatches: the whole training pass of a tile on one CU (ppo_policy_train_tile.hip), then the weight gradients
-    if (B * (ro->H / 32) <= g_train_tile_max_tiles && pol->L == 2 && pol->dtype == PPO_DTYPE_F32) {
-        const size_t frag = (size_t)pol->cap_tiles * (pol->HID / 32) * 1024;
-        PPO_TRY(pol->dz1f.alloc(frag)); PPO_TRY(pol->dz2f.alloc(frag));
-        const int32_t ts = launch_policy_train_tile(pol, ro, idx_dev, B, B_global, eps, ew, adv);
-        if (ts != PPO_ERR_UNSUPPORTED) {
-            if (ts != PPO_OK) return ts;
-            PPO_TRY(launch_grad_reduce(pol, B, B_global, ew, fuse_opt, fuse_hist2));
-            pol->last_B = B; pol->last_entropy_weight = ew;
-            return PPO_OK;
-        }
-    }
-    PPO_TRY(launch_policy_train_fwd(pol, ro, idx_dev, B, B_global, eps, ew, adv));
-    // small minibatches: three-product backward (no per-workgroup gradient slabs); otherwise the fused kernel
-    int32_t bs = PPO_ERR_UNSUPPORTED;
-    // the fused kernel is the num_hidden_layers == 2 shape with all its weight gradients resident (and F = 216 at HID = 256
-    // does not fit its LDS): every other policy takes the layer-looped three-product form at any minibatch size
-    const bool fused_ok = pol->L == 2 && !(pol->F == 216 && pol->HID == 256);
-    // with the split-fp32 fused backward (ppo_policy_bwd_x6.hip) the three-product form no longer wins at any size (measured,
-    // gpurun_out/small1: 128 / 256 / 384 tiles 30.3 / 35.6 / 49.4 ms per iteration against 28.4 / 35.5 / 43.8): it is taken only
-    // below PPO_BWD_SMALL_MAX_TILES_SPLIT (default 0) while the split form is on and covers the policy
-    static const int64_t small_max_split = [] { const char* v = std::getenv("PPO_BWD_SMALL_MAX_TILES_SPLIT"); return v ? (int64_t)atoll(v) : (int64_t)0; }();
-    const bool split_covers = ppo_bwd_split_enabled() && fused_ok && pol->F == 72 && pol->w2x.p != nullptr;
-    const int64_t small_max = split_covers ? small_max_split : g_bwd_small_max_tiles;
-    if ((B * (ro->H / 32) <= small_max || !fused_ok) && pol->dtype == PPO_DTYPE_F32) {
+    const TrainRoute r = train_route(pol->dtype, pol->F, pol->HID, pol->L, ro->H, ro->compact, B, ppo_knobs());
+    if (r.fwd == TrainFwd::None) { ppo_set_error(r.err); return PPO_ERR_UNSUPPORTED; }
+    if (r.bwd == TrainBwd::Wgrad || r.bwd == TrainBwd::Small) {
         const size_t frag = (size_t)pol->cap_tiles * (pol->HID / 32) * 1024;     // dZ in fragment order, like act1 / act2
         PPO_TRY(pol->dz1f.alloc(frag));
         if (pol->L >= 2) PPO_TRY(pol->dz2f.alloc(frag));
         if (pol->L > 2) PPO_TRY(pol->dzm.alloc((size_t)(pol->L - 2) * frag));
-        bs = launch_policy_bwd_small(pol, ro, idx_dev, B);
-        if (bs == PPO_ERR_UNSUPPORTED && !fused_ok) { ppo_set_error("step_batch!: no backward kernel for this policy / state shape"); return bs; }
     }
-    if (bs != PPO_OK && bs != PPO_ERR_UNSUPPORTED) return bs;
-    if (bs == PPO_ERR_UNSUPPORTED) PPO_TRY(launch_policy_bwd(pol, ro, idx_dev, B));
+    if (r.fwd == TrainFwd::TrainTile) PPO_TRY(launch_policy_train_tile(pol, ro, idx_dev, B, B_global, eps, ew, adv));
+    else PPO_TRY(launch_policy_train_fwd(pol, ro, idx_dev, B, B_global, eps, ew, adv, r.fwd));
+    switch (r.bwd) {
+    case TrainBwd::Small: PPO_TRY(launch_policy_bwd_small(pol, ro, idx_dev, B)); break;
+    case TrainBwd::X6: PPO_TRY(launch_policy_bwd_x6(pol, ro, idx_dev, B)); break;
+    case TrainBwd::Fused: PPO_TRY(launch_policy_bwd(pol, ro, idx_dev, B)); break;
+    case TrainBwd::Bf16: PPO_TRY(launch_policy_bwd_bf16(pol, ro, idx_dev, B)); break;
+    default: break;                                         // Wgrad: launched by launch_policy_train_tile
+    }
     PPO_TRY(launch_grad_reduce(pol, B, B_global, ew, fuse_opt, fuse_hist2));
     pol->last_B = B; pol->last_entropy_weight = ew;
     return PPO_OK;
@@ -1251,8 +1204,7 @@ int32_t ppo_train(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, double ep
             int64_t Bg = 0;
             for (int64_t l : lens) Bg += std::max<int64_t>(0, std::min(batch_size, l - start));
             // single-rank training: Adam and the re-pack ride in the slab-reduction launch (PPO_FUSE_REDUCE_ADAM=0: separate launches)
-            static const bool fuse_ok = [] { const char* v = std::getenv("PPO_FUSE_REDUCE_ADAM"); return v ? atoi(v) != 0 : true; }();
-            const bool fused = fuse_ok && !allreduce && B > 0;
+            const bool fused = ppo_knobs().fuse_reduce_adam && !allreduce && B > 0;
             if (B > 0) PPO_TRY(forward_backward_dev(pol, ro, order.p + start, B, Bg, epsilon, entropy_weight, adv_mode, fused ? opt : nullptr, hist.p + 2 * b));
             else HIP_TRY(hipMemsetAsync(pol->grad.p, 0, (size_t)(pol->np + 2) * sizeof(float), g_stream));   // shard exhausted
             if (allreduce) {                     // every rank of a data-parallel run; a world of 1 may pass it too

@@ -248,18 +248,51 @@ int32_t launch_policy_rollout(ppo_policy_s* p, ppo_env_s* e, const int8_t* state
 // adv_col: the advantage column indexed by transition id (ro->returns for PPO_ADV_RETURNS)
 int32_t launch_policy_rollout_persistent(ppo_policy_s* p, ppo_env_s* e, ppo_rollouts_s* ro, int64_t T, int record_probs,
                                          int64_t t0 = 0);
-int32_t launch_policy_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B,
-                                int64_t B_global, double eps, double entropy_weight, const float* adv_col);
 int32_t launch_adv_normalise(const float* returns, const int32_t* idx_dev, int64_t B, float* adv_col);
+
+// ---------------------------------------------------------------- kernel selection (ppo_route.hip)
+// Every kernel-selection knob of the policy, process-wide (include/ppo_hip.h): read from its environment variable once at
+// load, changed by the ppo_set_* setters; a setter's -1 restores the value read at load.
+struct PpoKnobs {
+    // training pass                          environment variable
+    int32_t bwd_split = 1;                    // PPO_BWD_SPLIT_BF16: split-fp32 train forward and fused backward
+    int64_t train_tile_max_tiles = 0;         // PPO_TRAIN_TILE_MAX_TILES: one-tile training pass up to this many tiles
+    int64_t bwd_small_max_tiles = 384;        // PPO_BWD_SMALL_MAX_TILES: three-product backward up to this many tiles,
+    int64_t bwd_small_max_tiles_split = 0;    // PPO_BWD_SMALL_MAX_TILES_SPLIT: ... or this many while the split backward covers
+    int64_t fwd_split_max_states = 512;       // PPO_FWD_SPLIT_MAX_STATES: 2 or 4 waves per state up to this many states
+    int64_t fwd_x6_max_states = 1 << 30;      // PPO_FWD_SPLIT_MAX_TILES: split-fp32 train forward up to this many STATES
+    // its two-tile form from this many tiles on (0 = never): [0] HID = 128, PPO_FWD_SPLIT_T2_MIN_TILES_128 (measured: train
+    // forward 0.0570 -> 0.0548 ms at 4096 states); [1] HID = 256, PPO_FWD_SPLIT_T2_MIN_TILES
+    int64_t fwd_x6_t2_min_tiles[2] = {1024, 1536};
+    int32_t fuse_reduce_adam = 1;             // PPO_FUSE_REDUCE_ADAM: single-rank Adam in the slab-reduction launch
+    // rollout
+    int32_t rollout_persistent = -1;          // PPO_ROLLOUT_PERSISTENT: 0 / 1, -1 = one launch for Q = 8
+    int32_t rollout_compact = -1;             // PPO_ROLLOUT_COMPACT: 0 / 1, -1 = compact above compact_auto_bytes or with a sink
+    double compact_auto_bytes = 32.0 * 1024 * 1024 * 1024;   // PPO_COMPACT_AUTO_BYTES
+    int64_t rollout_split_max_envs = 512;     // PPO_ROLLOUT_SPLIT_MAX_ENVS: 2 or 4 waves per env up to this many envs
+};
+const PpoKnobs& ppo_knobs();
+
+// The kernels that run one training minibatch.  TrainTile runs forward, loss and backward-data in one launch and is
+// always followed by Wgrad (k_policy_wgrad<TR = true>).
+enum class TrainFwd { None, TrainTile, X6S, X6T, X6, Split, Fwd, Bf16 };
+enum class TrainBwd { None, Wgrad, Small, X6, Fused, Bf16 };
+struct TrainRoute { TrainFwd fwd; TrainBwd bwd; const char* err; };      // err: why fwd is None
+// dtype: PPO_DTYPE_*; HID: kernel width (128 / 256); H: rows per state (32 / 128); states: minibatch size
+TrainRoute train_route(int32_t dtype, int F, int HID, int L, int H, bool compact, int64_t states, const PpoKnobs& k);
+
+// train-pass launchers: each launches what train_route chose and checks nothing else
+int32_t launch_policy_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B,
+                                int64_t B_global, double eps, double entropy_weight, const float* adv_col, TrainFwd form);
 int32_t launch_policy_bwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B);
 // the same fused backward with its row contractions (dW2, dW1) as split-fp32 products on the bf16 matrix pipe
-// (ppo_policy_bwd_x6.hip); PPO_ERR_UNSUPPORTED: shape not covered
+// (ppo_policy_bwd_x6.hip)
 int32_t launch_policy_bwd_x6(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B);
-extern "C" int ppo_bwd_split_enabled();
-// three-product backward for small minibatches (ppo_policy_bwd_small.hip); PPO_ERR_UNSUPPORTED: not covered
-int32_t launch_policy_bwd_small(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B);
-// small minibatches: forward + loss + backward-data of a tile in one workgroup, then the weight-gradient kernel
-// (ppo_policy_train_tile.hip); PPO_ERR_UNSUPPORTED: not covered
+// three-product backward of an fp32 policy (ppo_policy_bwd_small.hip); dz1f (dz2f, dzm where the layers exist) allocated.
+// tr_tail_wg > 0: only its weight-gradient kernel, on the operand-layout tiles k_policy_train_tile left in act1 / dz2f /
+// dz1f from that many workgroups (the slabs holding the small-gradient tails)
+int32_t launch_policy_bwd_small(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int tr_tail_wg = 0);
+// forward + loss + backward-data of a tile in one workgroup, then the weight-gradient kernel (ppo_policy_train_tile.hip)
 int32_t launch_policy_train_tile(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
                                  double eps, double entropy_weight, const float* adv_col);
 // bf16 compute mode (ppo_policy_bf16.hip); MODE as in k_policy_fwd: 0 probs, 1 rollout, 2 train
@@ -267,9 +300,9 @@ struct FwdArgs;
 // one-launch rollout with 2 or 4 waves per env for few envs, bit-identical results (ppo_policy_rollout_split.hip)
 int32_t launch_rollout_split(ppo_policy_s* p, FwdArgs& a, int64_t N, int tps, int V, int env);
 // train forward with 2 or 4 waves per state for small minibatches (ppo_policy_fwd_split.hip)
-int32_t launch_policy_train_fwd_split(ppo_policy_s* p, FwdArgs& a, int64_t B, int tps, bool compact);
-// train forward with its Dense products as split-fp32 MFMAs (ppo_policy_fwd_x6.hip); PPO_ERR_UNSUPPORTED: not covered / switched off
-int32_t launch_policy_train_fwd_x6(ppo_policy_s* p, FwdArgs& a, int64_t B, int tps, bool compact);
+int32_t launch_policy_train_fwd_split(ppo_policy_s* p, FwdArgs& a, int64_t B, bool compact);
+// train forward with its Dense products as split-fp32 MFMAs (ppo_policy_fwd_x6.hip); form: X6S, X6T or X6
+int32_t launch_policy_train_fwd_x6(ppo_policy_s* p, FwdArgs& a, int64_t B, TrainFwd form, bool compact);
 int32_t launch_policy_fwd_bf16(ppo_policy_s* p, FwdArgs& args, int mode, int64_t B, int tps);
 int32_t launch_policy_rollout_persistent_bf16(ppo_policy_s* p, FwdArgs& args, int64_t N, int tps, int V);
 int32_t launch_policy_bwd_bf16(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B);

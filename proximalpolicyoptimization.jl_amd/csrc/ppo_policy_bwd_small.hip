@@ -684,20 +684,7 @@ static int32_t launch_small(ppo_policy_s* p, BwdSmallArgs& a, int tr_tail_wg = 0
     return PPO_OK;
 }
 
-static int32_t bwd_small_impl(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int tr_tail_wg);
-
-// PPO_ERR_UNSUPPORTED (no error text): shape or size not covered -> the caller runs the fused kernel
-int32_t launch_policy_bwd_small(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B) {
-    return bwd_small_impl(p, ro, idx_dev, B, 0);
-}
-// weight gradients from the operand-layout tiles k_policy_train_tile left in act1 / dz2f / dz1f; nwg_tail = its workgroups
-// (the slabs holding the small-gradient tails)
-int32_t launch_policy_wgrad_tr(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int nwg_tail) {
-    return bwd_small_impl(p, ro, idx_dev, B, nwg_tail);
-}
-
-static int32_t bwd_small_impl(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int tr_tail_wg) {
-    if (p->dtype != PPO_DTYPE_F32 || !p->dz1f.p || (p->L >= 2 && !p->dz2f.p) || (p->L > 2 && !p->dzm.p)) return PPO_ERR_UNSUPPORTED;
+int32_t launch_policy_bwd_small(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int tr_tail_wg) {
     BwdSmallArgs a;
     a.tps = ro->H / 32;
     a.states = ro->compact ? p->xs.p : ro->states.p; a.x_by_tile = ro->compact ? 1 : 0;
@@ -716,9 +703,7 @@ static int32_t bwd_small_impl(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t
         a.dzl[l] = first ? (float4*)p->dz1f.p : (last ? (float4*)p->dz2f.p : (float4*)p->dzm.p + (size_t)(l - 1) * lstride);
     }
     if (p->F == 72 && p->HID == 256) return launch_small<72, 256>(p, a, tr_tail_wg);
-    if (p->F == 72 && p->HID == 128) return launch_small<72, 128>(p, a, tr_tail_wg);
-    if (tr_tail_wg) return PPO_ERR_UNSUPPORTED;
-    if (p->F == 216 && p->HID == 256) return launch_small<216, 256>(p, a);
-    if (p->F == 216 && p->HID == 128) return launch_small<216, 128>(p, a);
-    return PPO_ERR_UNSUPPORTED;
+    if (p->F == 72) return launch_small<72, 128>(p, a, tr_tail_wg);
+    if (p->HID == 256) return launch_small<216, 256>(p, a);
+    return launch_small<216, 128>(p, a);
 }

@@ -584,6 +584,7 @@ extern "C" int32_t ppo_debug_x6_stamps(unsigned long long* out) {
 }
 #endif
 
+// fp32 Policy(72, h, 2, 4) (train_route)
 int32_t launch_policy_bwd_x6(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B) {
     BwdXArgs a;
     a.stamps = nullptr;
@@ -594,7 +595,6 @@ int32_t launch_policy_bwd_x6(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t*
     a.states = ro->compact ? p->xs.p : ro->states.p; a.x_by_tile = ro->compact ? 1 : 0;
     a.idx = idx_dev; a.B = B * a.tps;
     a.act1 = (const float4*)p->act1.p; a.act2 = (const float4*)p->act2.p; a.dY = (const float4*)p->dY.p;
-    if (p->L != 2 || !p->w2x.p) return PPO_ERR_UNSUPPORTED;
     a.w2x = (const uint4*)p->w2x.p; a.w3p = (const float4*)p->w3p.p;
     a.slabs = p->slabs.p; a.slab_stride = slab_floats(p->F, p->HID);
     int nwg = 0;
@@ -613,9 +613,8 @@ int32_t launch_policy_bwd_x6(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t*
         }                                                                                                     \
         hipLaunchKernelGGL((k_policy_bwd_x6<FF, HH>), dim3(nwg), dim3(HH * 2), lds, ppo_stream(), a);          \
     } while (0)
-    if (p->F == 72 && p->HID == 256) LAUNCH(72, 256);
-    else if (p->F == 72 && p->HID == 128) LAUNCH(72, 128);
-    else return PPO_ERR_UNSUPPORTED;
+    if (p->HID == 256) LAUNCH(72, 256);
+    else LAUNCH(72, 128);
 #undef LAUNCH
     HIP_TRY(hipGetLastError());
     return PPO_OK;

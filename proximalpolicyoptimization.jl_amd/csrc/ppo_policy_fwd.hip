@@ -592,10 +592,6 @@ int32_t launch_policy_probs(ppo_policy_s* p, const int8_t* states_dev, const uin
     return dispatch_fwd<0>(p, a, B, H / 32);
 }
 
-// rollouts of up to this many envs give every env to 2 or 4 waves; ppo_set_rollout_split_max_envs / PPO_ROLLOUT_SPLIT_MAX_ENVS
-static int64_t g_rollout_split_max_envs = [] { const char* v = std::getenv("PPO_ROLLOUT_SPLIT_MAX_ENVS"); return v ? (int64_t)atoll(v) : (int64_t)512; }();
-extern "C" int32_t ppo_set_rollout_split_max_envs(int64_t envs) { g_rollout_split_max_envs = envs < 0 ? 512 : envs; return PPO_OK; }
-
 int32_t launch_policy_rollout(ppo_policy_s* p, ppo_env_s* e, const int8_t* states_dev, const uint32_t* active_dev,
                               int32_t* actions_out, float* psel_out, float* full_probs_or_null) {
     FwdArgs a = {};
@@ -605,7 +601,7 @@ int32_t launch_policy_rollout(ppo_policy_s* p, ppo_env_s* e, const int8_t* state
     a.actions_out = actions_out; a.psel_out = psel_out; a.full_probs = full_probs_or_null; a.err = e->err.p;
     ProfScope ps("k_policy_fwd_rollout");
     if (p->dtype == PPO_DTYPE_BF16) return launch_policy_fwd_bf16(p, a, 1, e->N, e->H / 32);
-    if (e->N <= g_rollout_split_max_envs) {   // few envs: 2 or 4 waves per env, same bits
+    if (e->N <= ppo_knobs().rollout_split_max_envs) {   // few envs: 2 or 4 waves per env, same bits
         const int32_t rs = launch_rollout_split(p, a, e->N, e->H / 32, e->V, 0);
         if (rs != PPO_ERR_UNSUPPORTED) return rs;
     }
@@ -643,7 +639,7 @@ int32_t launch_policy_rollout_persistent(ppo_policy_s* p, ppo_env_s* e, ppo_roll
     a.full_probs = record_probs ? ro->full_probs.p + r0 * e->A : nullptr;
     ProfScope ps("k_rollout_persistent");
     if (p->dtype == PPO_DTYPE_BF16) return launch_policy_rollout_persistent_bf16(p, a, N, tps, e->V);
-    if (N <= g_rollout_split_max_envs) {      // few envs: 2 or 4 waves per env, same bits (ppo_policy_rollout_split.hip)
+    if (N <= ppo_knobs().rollout_split_max_envs) {      // few envs: 2 or 4 waves per env, same bits (ppo_policy_rollout_split.hip)
         const int32_t rs = launch_rollout_split(p, a, N, tps, e->V, 1);
         if (rs != PPO_ERR_UNSUPPORTED) return rs;
         a.env_slots = slots;
@@ -668,12 +664,9 @@ int32_t launch_policy_rollout_persistent(ppo_policy_s* p, ppo_env_s* e, ppo_roll
     return PPO_OK;
 }
 
-// minibatches of up to this many states take the split train forward; ppo_set_fwd_split_max_states / PPO_FWD_SPLIT_MAX_STATES
-static int64_t g_fwd_split_max_states = [] { const char* v = std::getenv("PPO_FWD_SPLIT_MAX_STATES"); return v ? (int64_t)atoll(v) : (int64_t)512; }();
-extern "C" int32_t ppo_set_fwd_split_max_states(int64_t states) { g_fwd_split_max_states = states < 0 ? 512 : states; return PPO_OK; }
-
+// form: any TrainFwd but None and TrainTile (train_route)
 int32_t launch_policy_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B,
-                                int64_t B_global, double eps, double entropy_weight, const float* adv_col) {
+                                int64_t B_global, double eps, double entropy_weight, const float* adv_col, TrainFwd form) {
     FwdArgs a = {};
     fill_weights(p, a);
     a.states = ro->states.p; a.active = ro->active.p; a.idx = idx_dev; a.B = B;
@@ -687,20 +680,13 @@ int32_t launch_policy_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32
         a.states = nullptr; a.cstate = ro->cstate.p; a.xs_out = p->xs.p;
         a.env_tmpl = ro->tmpl.p; a.envV = ro->V; a.envQ = ro->V / 4; a.env_slots = 1;
     }
-    {   // Dense products as split-fp32 MFMAs on the bf16 pipe (ppo_policy_fwd_x6.hip: fp32 Policy(72, h, 2, 4), expanded states)
-        const int32_t rx = launch_policy_train_fwd_x6(p, a, B, ro->H / 32, ro->compact);
-        if (rx != PPO_ERR_UNSUPPORTED) return rx;
+    switch (form) {
+    case TrainFwd::Split: return launch_policy_train_fwd_split(p, a, B, ro->compact);     // ppo_policy_fwd_split.hip
+    // compact: the rows are re-derived from the env snapshots and left in p->xs (minibatch order) for the backward
+    case TrainFwd::Bf16: return launch_policy_fwd_bf16(p, a, ro->compact ? 4 : 2, B, ro->H / 32);
+    case TrainFwd::Fwd: return ro->compact ? dispatch_fwd<4>(p, a, B, ro->H / 32) : dispatch_fwd<2>(p, a, B, ro->H / 32);
+    default: return launch_policy_train_fwd_x6(p, a, B, form, ro->compact);               // ppo_policy_fwd_x6.hip
     }
-    if (B <= g_fwd_split_max_states) {        // small minibatch: 2 or 4 waves per state (ppo_policy_fwd_split.hip)
-        const int32_t rs = launch_policy_train_fwd_split(p, a, B, ro->H / 32, ro->compact);
-        if (rs != PPO_ERR_UNSUPPORTED) return rs;
-    }
-    if (ro->compact) {      // rows are re-derived from the env snapshots and left in p->xs (minibatch order) for the backward
-        if (p->dtype == PPO_DTYPE_BF16) return launch_policy_fwd_bf16(p, a, 4, B, ro->H / 32);
-        return dispatch_fwd<4>(p, a, B, ro->H / 32);
-    }
-    if (p->dtype == PPO_DTYPE_BF16) return launch_policy_fwd_bf16(p, a, 2, B, ro->H / 32);
-    return dispatch_fwd<2>(p, a, B, ro->H / 32);
 }
 
 int32_t launch_categorical(const float* probs, const float* u, int64_t B, int64_t A, int32_t* actions, float* psel,

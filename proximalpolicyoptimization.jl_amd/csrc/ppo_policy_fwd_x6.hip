@@ -754,22 +754,6 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6s(FwdArgs a, 
     }
 }
 
-// minibatches of up to this many 32-row tiles take the split-fp32 train forward (when ppo_set_bwd_split_bf16 is on);
-// PPO_FWD_SPLIT_MAX_TILES overrides (0 = never)
-#ifndef PPO_FWD_X6_DEFAULT_MAX_TILES
-#define PPO_FWD_X6_DEFAULT_MAX_TILES (1 << 30)
-#endif
-// HID = 256 minibatches of at least this many tiles take the two-tiles-per-pass form (PPO_FWD_SPLIT_T2_MIN_TILES; 0 = never)
-#ifndef PPO_FWD_X6_T2_DEFAULT_MIN_TILES
-#define PPO_FWD_X6_T2_DEFAULT_MIN_TILES 1536
-#endif
-// (read at every launch: the tests move the switch point to sizes their float64 checker finishes in seconds)
-static int64_t fwd_x6_t2_min_tiles() { const char* v = std::getenv("PPO_FWD_SPLIT_T2_MIN_TILES"); return v ? (int64_t)atoll(v) : (int64_t)PPO_FWD_X6_T2_DEFAULT_MIN_TILES; }
-// the same switch for HID = 128 (PPO_FWD_SPLIT_T2_MIN_TILES_128; 0 = never).  Measured (gpurun_out/h128_t2, alternating): train forward
-// 0.0570 -> 0.0548 ms at 4096 states, 6.00 -> 6.09 M env-steps/s
-static int64_t fwd_x6_t2_min_tiles_128() { const char* v = std::getenv("PPO_FWD_SPLIT_T2_MIN_TILES_128"); return v ? (int64_t)atoll(v) : (int64_t)1024; }
-static int64_t g_fwd_x6_max_tiles = [] { const char* v = std::getenv("PPO_FWD_SPLIT_MAX_TILES"); return v ? (int64_t)atoll(v) : (int64_t)PPO_FWD_X6_DEFAULT_MAX_TILES; }();
-
 #ifdef PPO_FX6_STAMP
 // diagnostic build (make -C csrc fxstamp, tools/fx6_stamps.py): per-phase clocks of k_policy_fwd_train_x6t, [workgroup][wave 0 / last][8]
 static unsigned long long* g_fx6_stamps = nullptr;
@@ -780,13 +764,12 @@ extern "C" int32_t ppo_debug_fx6_stamps(unsigned long long* out) {
 }
 #endif
 
-int32_t launch_policy_train_fwd_x6(ppo_policy_s* p, FwdArgs& a, int64_t B, int tps, bool compact) {
-    if (!ppo_bwd_split_enabled() || B > g_fwd_x6_max_tiles) return PPO_ERR_UNSUPPORTED;
+// fp32 Policy(72, h, 2, 4); form X6S: Q = 32 states at HID = 256, X6T / X6: Q = 8 states (train_route)
+int32_t launch_policy_train_fwd_x6(ppo_policy_s* p, FwdArgs& a, int64_t B, TrainFwd form, bool compact) {
 #ifdef PPO_FX6_STAMP
     if (!g_fx6_stamps) { (void)hipMalloc((void**)&g_fx6_stamps, 512 * 2 * 8 * 8); (void)hipMemset(g_fx6_stamps, 0, 512 * 2 * 8 * 8); }
     a.stamps = g_fx6_stamps;
 #endif
-    if (p->dtype != PPO_DTYPE_F32 || p->L != 2 || p->F != 72 || !(tps == 1 || (tps == 4 && p->HID == 256)) || !p->w1x.p || !p->w2fx.p) return PPO_ERR_UNSUPPORTED;
     if (compact) {
         // env snapshots: the minibatch's observation rows are re-derived first (the arithmetic of state(env), ppo_env.hip) into
         // the scratch the backward reads in this storage form anyway; both kernels then see the rows the expanded form holds,
@@ -794,60 +777,26 @@ int32_t launch_policy_train_fwd_x6(ppo_policy_s* p, FwdArgs& a, int64_t B, int t
         PPO_TRY(launch_expand_states(a.cstate, a.active, a.env_tmpl, B, a.envQ, a.xs_out, a.idx));
         a.states = a.xs_out;
     }
-#define LAUNCH(HH)                                                                                           \
+    // K: the kernel, LDS: its dynamic LDS bytes, one workgroup per GROUPS item up to CAP workgroups of THREADS threads
+#define LAUNCH(K, LDS, GROUPS, CAP, THREADS)                                                                 \
     do {                                                                                                     \
-        const int64_t cap = 256 * FXCfg<HH>::WG_PER_CU;                                                      \
-        const int nwg = (int)(B < cap ? B : cap);                                                            \
-        const size_t lds = FXCfg<HH>::total;                                                                 \
+        const int64_t groups = GROUPS, cap = CAP;                                                            \
+        const int nwg = (int)(groups < cap ? groups : cap);                                                  \
         static thread_local bool attr_set = false;                                                           \
         if (!attr_set) {                                                                                     \
-            HIP_TRY(hipFuncSetAttribute((const void*)k_policy_fwd_train_x6<HH>,                              \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));              \
+            HIP_TRY(hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS)); \
             attr_set = true;                                                                                 \
         }                                                                                                    \
-        hipLaunchKernelGGL((k_policy_fwd_train_x6<HH>), dim3(nwg), dim3(HH * 2), lds, ppo_stream(), a,       \
-                           (const uint4*)p->w1x.p, (const uint4*)p->w2fx.p, compact ? 1 : 0);                                 \
+        hipLaunchKernelGGL(K, dim3(nwg), dim3(THREADS), LDS, ppo_stream(), a,                                \
+                           (const uint4*)p->w1x.p, (const uint4*)p->w2fx.p, compact ? 1 : 0);                 \
     } while (0)
-    if (tps == 4) {                                               // Q = 32 states: one workgroup per state, its four tiles in two passes
-        const int nwg = (int)(B < 256 ? B : 256);
-        const size_t lds = FXSCfg<256, 4>::total;
-        static thread_local bool attr_set4 = false;
-        if (!attr_set4) {
-            HIP_TRY(hipFuncSetAttribute((const void*)k_policy_fwd_train_x6s<256, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_set4 = true;
-        }
-        hipLaunchKernelGGL((k_policy_fwd_train_x6s<256, 4>), dim3(nwg), dim3(512), lds, ppo_stream(), a,
-                           (const uint4*)p->w1x.p, (const uint4*)p->w2fx.p, compact ? 1 : 0);
-    }
-    else if (p->HID == 256 && fwd_x6_t2_min_tiles() > 0 && B >= fwd_x6_t2_min_tiles()) {
-        constexpr int T = 2;
-        const int64_t groups = (B + T - 1) / T;
-        const int nwg = (int)(groups < 256 ? groups : 256);
-        const size_t lds = FXTCfg<256, T>::total;
-        static thread_local bool attr_set2 = false;
-        if (!attr_set2) {
-            HIP_TRY(hipFuncSetAttribute((const void*)k_policy_fwd_train_x6t<256, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_set2 = true;
-        }
-        hipLaunchKernelGGL((k_policy_fwd_train_x6t<256, T>), dim3(nwg), dim3(512), lds, ppo_stream(), a,
-                           (const uint4*)p->w1x.p, (const uint4*)p->w2fx.p, compact ? 1 : 0);
-    }
-    else if (p->HID == 128 && fwd_x6_t2_min_tiles_128() > 0 && B >= fwd_x6_t2_min_tiles_128()) {
-        constexpr int T = 2;                                       // 54 KB of LDS per workgroup: two (four-wave) workgroups per CU
-        const int64_t groups = (B + T - 1) / T;
-        const int nwg = (int)(groups < 512 ? groups : 512);
-        const size_t lds = FXTCfg<128, T>::total;
-        static thread_local bool attr_set3 = false;
-        if (!attr_set3) {
-            HIP_TRY(hipFuncSetAttribute((const void*)k_policy_fwd_train_x6t<128, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_set3 = true;
-        }
-        hipLaunchKernelGGL((k_policy_fwd_train_x6t<128, T>), dim3(nwg), dim3(256), lds, ppo_stream(), a,
-                           (const uint4*)p->w1x.p, (const uint4*)p->w2fx.p, compact ? 1 : 0);
-    }
-    else if (p->HID == 256) LAUNCH(256);
-    else if (p->HID == 128) LAUNCH(128);
-    else return PPO_ERR_UNSUPPORTED;
+    // Q = 32 states: one workgroup per state, its four tiles in two passes
+    if (form == TrainFwd::X6S) LAUNCH((k_policy_fwd_train_x6s<256, 4>), (FXSCfg<256, 4>::total), B, 256, 512);
+    // two tiles per pass; HID = 128: 54 KB of LDS per workgroup, two (four-wave) workgroups per CU
+    else if (form == TrainFwd::X6T && p->HID == 256) LAUNCH((k_policy_fwd_train_x6t<256, 2>), (FXTCfg<256, 2>::total), (B + 1) / 2, 256, 512);
+    else if (form == TrainFwd::X6T) LAUNCH((k_policy_fwd_train_x6t<128, 2>), (FXTCfg<128, 2>::total), (B + 1) / 2, 512, 256);
+    else if (p->HID == 256) LAUNCH(k_policy_fwd_train_x6<256>, FXCfg<256>::total, B, 256 * FXCfg<256>::WG_PER_CU, 512);
+    else LAUNCH(k_policy_fwd_train_x6<128>, FXCfg<128>::total, B, 256 * FXCfg<128>::WG_PER_CU, 256);
 #undef LAUNCH
     HIP_TRY(hipGetLastError());
     return PPO_OK;

@@ -313,9 +313,6 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_train_tile(TrainTileArgs 
     if (tid < 4) sb3[tid] = db3;
 }
 
-// weight-gradient half of the pass (ppo_policy_bwd_small.hip)
-int32_t launch_policy_wgrad_tr(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int nwg_tail);
-
 template <int F, int HID>
 static int32_t launch_tt(ppo_policy_s* p, TrainTileArgs& ta, int64_t B, int* nwg_out) {
     constexpr int NT = HID / 32;
@@ -335,12 +332,10 @@ static int32_t launch_tt(ppo_policy_s* p, TrainTileArgs& ta, int64_t B, int* nwg
     return PPO_OK;
 }
 
-// PPO_ERR_UNSUPPORTED (no error text): shape not covered -> the caller runs the separate forward / backward kernels.
-// On success the flat-gradient inputs of k_grad_reduce (slabs, loss terms) are complete.
+// fp32 Policy(72, h, 2, 4), H = 32, expanded states, dz1f / dz2f allocated (train_route).  On success the flat-gradient
+// inputs of k_grad_reduce (slabs, loss terms) are complete.
 int32_t launch_policy_train_tile(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
                                  double eps, double entropy_weight, const float* adv_col) {
-    if (p->dtype != PPO_DTYPE_F32 || p->F != 72 || p->L != 2 || ro->H != 32 || ro->compact) return PPO_ERR_UNSUPPORTED;
-    if (!p->dz1f.p || !p->dz2f.p) return PPO_ERR_UNSUPPORTED;
     TrainTileArgs ta = {};
     FwdArgs& a = ta.f;
     a.w1p = (const float4*)p->w1p.p; a.w2p = (const float4*)p->w2p.p; a.b1p = (const float4*)p->b1p.p;
@@ -353,10 +348,6 @@ int32_t launch_policy_train_tile(ppo_policy_s* p, ppo_rollouts_s* ro, const int3
     ta.h1t = (float4*)p->act1.p; ta.dz2t = (float4*)p->dz2f.p; ta.dz1t = (float4*)p->dz1f.p;   // operand layout, not fragment order
     ta.slabs = p->slabs.p; ta.slab_stride = slab_floats(p->F, p->HID, p->L);
     int nwg = 0;
-    int32_t s;
-    if (p->HID == 256) s = launch_tt<72, 256>(p, ta, B, &nwg);
-    else if (p->HID == 128) s = launch_tt<72, 128>(p, ta, B, &nwg);
-    else return PPO_ERR_UNSUPPORTED;
-    if (s != PPO_OK) return s;
-    return launch_policy_wgrad_tr(p, ro, idx_dev, B, nwg);
+    PPO_TRY((p->HID == 256 ? launch_tt<72, 256>(p, ta, B, &nwg) : launch_tt<72, 128>(p, ta, B, &nwg)));
+    return launch_policy_bwd_small(p, ro, idx_dev, B, nwg);          // the weight-gradient half of the pass
 }

@@ -14,6 +14,7 @@ the split train forward (1536 tiles at HID = 256, 1024 at HID = 128) and one sta
     the slab-reduction launch at world 1): parameters, Adam moments and loss history bit for bit against the oracle's Adam on
     forward_backward's gradient, on the fused and on the unfused (all-reduce hook) path; then a fresh policy given the trained
     parameters through set_params must compute the same probabilities and gradients bit for bit (pins the re-pack).
+Every launch also asserts the kernels the library picks for it (ppo_debug_train_route, see tests/test_train_route.py).
 
 TEST_RECORD_DIR=<dir>: append the measured errors / tolerances of every case to <dir>/bench_shapes.jsonl."""
 import json
@@ -23,6 +24,7 @@ import numpy as np
 import pytest
 
 from oracle import np_oracle
+from test_train_route import DEFAULT, expected, route
 
 pytestmark = pytest.mark.gpu
 
@@ -44,6 +46,13 @@ def knobs(P):
     yield P
     P.set_bwd_split_bf16(None)
     P.set_rollout_compact(None)
+
+
+def _assert_route(P, dtype, split, Q, hid, L, B, compact=False, want=None):
+    """The library's route for this launch is the restated table's (and `want`, where the case names its kernels)."""
+    got = route(P, dtype, F, hid, L, 4 * Q, compact, B)
+    assert got == expected(dtype, F, hid, L, 4 * Q, compact, B, dict(DEFAULT, split=split)), got
+    assert want is None or got == want, (got, want)
 
 
 def _record(rec):
@@ -165,6 +174,17 @@ PARITY = [
     (8, 256, 3, 4096, "shape"),      # --layers 3: layer-looped kernels
     (8, 256, 1, 4096, "shape"),      # --layers 1
 ]
+# the kernels each case of PARITY runs with the default knobs (split-fp32 on)
+X6T, X6, X6S, BX6 = "k_policy_fwd_train_x6t<%d,2>", "k_policy_fwd_train_x6<%d>", "k_policy_fwd_train_x6s<256,4>", "k_policy_bwd_x6<72,%d>"
+PARITY_ROUTE = {
+    (8, 256, 2, 4096): (X6T % 256, BX6 % 256), (8, 128, 2, 4096): (X6T % 128, BX6 % 128),
+    (8, 256, 2, 1535): (X6 % 256, BX6 % 256), (8, 256, 2, 1536): (X6T % 256, BX6 % 256), (8, 256, 2, 1537): (X6T % 256, BX6 % 256),
+    (8, 128, 2, 1023): (X6 % 128, BX6 % 128), (8, 128, 2, 1024): (X6T % 128, BX6 % 128), (8, 128, 2, 1025): (X6T % 128, BX6 % 128),
+    (32, 256, 2, 1024): (X6S, BX6 % 256), (32, 256, 2, 8192): (X6S, BX6 % 256),
+    (32, 128, 2, 1024): ("k_policy_fwd<72,128,2,4,0>", BX6 % 128),
+    (8, 256, 3, 4096): ("k_policy_fwd<72,256,2,1,1>", "k_policy_bwd_data_deep<72,256>"),
+    (8, 256, 1, 4096): ("k_policy_fwd<72,256,2,1,1>", "k_policy_bwd_data_deep<72,256>"),
+}
 
 
 @pytest.mark.parametrize("Q,hid,L,B,source", PARITY, ids=["Q%d-h%d-L%d-%d-%s" % c for c in PARITY])
@@ -192,6 +212,8 @@ def test_bench_shape_gradient_vs_f64(P, knobs, Q, hid, L, B, source):
     for mode in modes:
         if mode is not None:
             P.set_bwd_split_bf16(mode)
+        _assert_route(P, "f32", 1 if mode is None else mode, Q, hid, L, B, source == "compact",
+                      PARITY_ROUTE[(Q, hid, L, B)] if mode != 0 else None)
         lp, le = P.forward_backward(pol, ds, sel0 + 1, EPS, ENT)
         g = pol.grad()
         err = np.abs(g - g64).max() / scale
@@ -281,6 +303,9 @@ def test_bench_shape_additivity(P, knobs, mode, Q, hid, L, B, chunkings):
         pol = _policy(P, hid, L, rng, seed=3)
         ds, allc = _by_shape(P, pol, rng, B, Q, kink=False, ratio=(1, 1))      # device against device: the kink does not matter
         sel0 = rng.permutation(B)
+    dtype, compact = ("bf16" if mode == "bf16" else "f32"), mode == "compact"
+    for n in {B, 1} | {n for c in chunkings for n in c}:
+        _assert_route(P, dtype, 1, Q, hid, L, n, compact)
     lp, le = P.forward_backward(pol, ds, sel0 + 1, EPS, ENT)
     g_full = pol.grad().astype(np.float64)
     M = np.abs(g_full).max()
@@ -350,7 +375,7 @@ def world1(P):
 STEP = [(256, "f32", 1), (128, "f32", 1), (256, "f32", 0), (256, "bf16", None)]
 
 
-def _bench_step(P, orc, hid, dtype, parallel):
+def _bench_step(P, orc, hid, dtype, parallel, split):
     rng = np.random.default_rng(hid + (dtype == "bf16"))
     B = 4096
     pol = _policy(P, hid, 2, rng, dtype=dtype, seed=5)
@@ -358,6 +383,7 @@ def _bench_step(P, orc, hid, dtype, parallel):
     ds, c = _by_shape(P, pol, rng, B, 8, kink=False)
     assert len(ds) == B
     perm = (rng.permutation(B) + 1)[None]
+    _assert_route(P, dtype, 1 if split is None else split, 8, hid, 2, B)
     # the reference: forward_backward on an identical copy of the pre-step policy, the oracle's Adam on its gradient
     ref = P.HipPolicy(F, hid, 2, 4, dtype=dtype)
     ref.params = p0
@@ -396,7 +422,7 @@ def test_bench_optimiser_step_fused(P, orc, knobs, hid, dtype, split):
     gradient it steps with is forward_backward's bit for bit."""
     if split is not None:
         P.set_bwd_split_bf16(split)
-    _bench_step(P, orc, hid, dtype, None)
+    _bench_step(P, orc, hid, dtype, None, split)
 
 
 @pytest.mark.parametrize("hid,dtype,split", STEP, ids=["h%d-%s-split%s" % s for s in STEP])
@@ -404,4 +430,4 @@ def test_bench_optimiser_step_unfused(P, orc, knobs, world1, hid, dtype, split):
     """The same step through the all-reduce hook (one rank: the sum is the identity), then a separate k_adam launch."""
     if split is not None:
         P.set_bwd_split_bf16(split)
-    _bench_step(P, orc, hid, dtype, world1())
+    _bench_step(P, orc, hid, dtype, world1(), split)

@@ -595,10 +595,17 @@ def test_gradient_at_the_kernel_switch_points(P, orc, B, split):
     """Default kernel selection by minibatch size.  fp32-MFMA training pass (ppo_set_bwd_split_bf16(0)): 4 waves per state up
     to 256 states, 2 up to 512, one above; the three-product backward up to 384 tiles, the fused kernel above.  Split-fp32
     pass (the default): one workgroup per state and the fused backward at every size.  Every size around the switch points
-    gives the float64 oracle's gradient (same tolerance)."""
+    gives the float64 oracle's gradient (same tolerance), and the route named here is the one the library picks."""
     if split and B in (257, 384, 512):
         pytest.skip("the split pass has no switch points of its own: three of the six sizes (suite time)")
+    from test_train_route import route
     P.set_bwd_split_bf16(split)
+    if split:
+        want = ("k_policy_fwd_train_x6<256>", "k_policy_bwd_x6<72,256>")
+    else:
+        want = ("k_policy_fwd_train_split<72,256,%d,0>" % (4 if B <= 256 else 2) if B <= 512 else "k_policy_fwd<72,256,2,1,0>",
+                "k_policy_bwd_data<72,256>" if B <= 384 else "k_policy_bwd<72,256>")
+    got = route(P, "f32", 72, 256, 2, 32, False, B)
     env, pol, ro, ds = _make_dataset(P, orc, 48, 12, 256, seed=91)
     assert len(ds) == 576
     sel = np.random.default_rng(B).permutation(len(ds))[:B] + 1
@@ -611,6 +618,7 @@ def test_gradient_at_the_kernel_switch_points(P, orc, B, split):
     same = np.array_equal(g, pol.grad())
     P.set_bwd_split_bf16(None)
     assert same, "bitwise reproducible run to run"
+    assert got == want
 
 
 def test_gradient_clipped_branch(P, orc):

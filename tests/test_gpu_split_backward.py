@@ -22,8 +22,8 @@ def P(ppo):
     ppo.set_train_tile_max_tiles(None)
     ppo.set_bwd_split_bf16(None)
     ppo.set_rollout_compact(None)
-    os.environ.pop("PPO_FWD_SPLIT_T2_MIN_TILES", None)
-    os.environ.pop("PPO_FWD_SPLIT_T2_MIN_TILES_128", None)
+    ppo.set_fwd_split_t2_min_tiles(256, None)
+    ppo.set_fwd_split_t2_min_tiles(128, None)
 
 
 def _dataset(P, N, T, HID, seed):
@@ -65,14 +65,14 @@ def test_split_backward_matches_fp32_kernel_and_f64(P, orc, HID, B, compact):
     test), the split form no further from float64 than a small multiple of the fp32 chain's own distance, the two within
     fp32 rounding of each other, and the split form bitwise reproducible.  More tiles than workgroups (HID = 256: 600 on 256,
     HID = 128: 1100 on 512) and fewer (70 on 512) both occur; from 1536 tiles on the HID = 256 train forward takes two tiles per
-    workgroup pass, below it one: the B = 401 case moves that switch to 200 tiles (PPO_FWD_SPLIT_T2_MIN_TILES, read per launch)
+    workgroup pass, below it one: the B = 401 case moves that switch to 200 tiles (set_fwd_split_t2_min_tiles)
     -- an odd count, the last pass has one tile.  The default switch points and the minibatch sizes bench.py runs are tested in
     tests/test_gpu_bench_shapes.py."""
     P.set_rollout_compact(compact)
     if B == 401:
-        os.environ["PPO_FWD_SPLIT_T2_MIN_TILES"] = "200"
+        P.set_fwd_split_t2_min_tiles(256, 200)
     if (HID, B) == (128, 70):
-        os.environ["PPO_FWD_SPLIT_T2_MIN_TILES_128"] = "32"       # (HID = 128 switches at 1024 tiles; B = 1100 takes it by itself)
+        P.set_fwd_split_t2_min_tiles(128, 32)           # (HID = 128 switches at 1024 tiles; B = 1100 takes it by itself)
     env, pol, ro, ds = _dataset(P, 48, 40 if B > 1152 else 24, HID, seed=B)
     pool = np.flatnonzero(_off_the_kink(pol.params, HID, ro.state_data[0].reshape(-1, 32, 72)))
     assert len(pool) >= 64                                           # (a minibatch may repeat samples)
