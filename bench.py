@@ -10,8 +10,12 @@ fp32, T=128, E=4 epochs, minibatch 4096 per GPU, gamma=1.0, eps=0.05, entropy we
 Multi-GPU (one process per GPU): `python bench.py --gpus N` starts its N rank processes ITSELF (before anything touches
 the GPU) unless a launcher (torchrun) already did.  Headline = weak scaling (BASELINE config 3): 4096 envs and a
 4096-sample minibatch PER GPU, one RCCL all-reduce of the flat gradient per optimiser step (issued by the library
-itself, ppo_rccl_*), no other exchange.  For N > 1 the same JSON line also carries a "strong" object: 4096 envs and a
-4096-sample global minibatch split over the N GPUs, timed the same way.
+itself, ppo_rccl_*), no other exchange.  With --full and N > 1 the same JSON line also carries a "strong" object: 4096 envs
+and a 4096-sample global minibatch split over the N GPUs, timed the same way.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line.  Everything else --
+the per-kernel / roofline leg (more iterations after the timed ones), the strong-scaling leg and the CPU baselines --
+runs only under --full.
 
 Prints ONE JSON line on rank 0.
 """
@@ -295,7 +299,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel / roofline leg, the strong-scaling leg (N > 1) and the "
+                         "CPU baselines; off by default: a plain run reports the headline figure only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--t-steps", type=int, default=T_STEPS, help="profiling only: shorter rollout (flagged in the output)")
     ap.add_argument("--epochs", type=int, default=EPOCHS, help="profiling only: fewer epochs (flagged in the output)")
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
@@ -435,10 +442,10 @@ def main():
         N_ENVS = MINIBATCH = N_ENVS // world
     dt, iteration = timed_run(N_ENVS, MINIBATCH, 1000, dump_dir=args.dump_outputs if rank == 0 else None)
 
-    # ---- roofline leg: per-kernel HIP-event durations of one more iteration (outside the timed region)
+    # ---- roofline leg (--full): per-kernel HIP-event durations of one more iteration (outside the timed region)
     roof, kernels = None, {}
     peak = PEAK_FP32_MFMA_TFLOPS if args.dtype == "f32" else PEAK_BF16_MFMA_TFLOPS
-    if rank == 0:
+    if args.full and rank == 0:
         PPO.profile_enable(True)
         iteration(args.warmup + args.steps)
         PPO.synchronize()
@@ -580,13 +587,13 @@ def main():
                     "design_hbm_bytes_per_launch": dict(
                         {"gradient_slabs_written": min(256 if (HID == 256 or args.dtype == "bf16") else 512, tiles) * 4 * (HID * HID + HID * 96 + HID * 6 + 4)},
                         **({"dz1_fragments_written": tiles * HID * 32 * 2} if args.dtype == "bf16" and HID > 128 else {}))}
-    elif use_dist:
+    elif args.full and use_dist:
         iteration(args.warmup + args.steps)          # keep the collectives of the extra iteration matched
         PPO.synchronize()
 
-    # ---- strong-scaling leg (N > 1): the 4096 envs and the 4096-sample global minibatch split over the ranks
+    # ---- strong-scaling leg (--full, N > 1): the 4096 envs and the 4096-sample global minibatch split over the ranks
     strong = None
-    if world > 1 and not strong_requested:
+    if args.full and world > 1 and not strong_requested:
         sdt, _ = timed_run(N_ENVS // world, MINIBATCH // world, 5000)
         strong = {"value": N_ENVS * T_STEPS * args.steps / sdt, "unit": "env-steps/s", "ms_per_step": sdt / args.steps * 1e3,
                   "envs_total": N_ENVS, "envs_per_gpu": N_ENVS // world, "minibatch_global": MINIBATCH,
@@ -620,9 +627,9 @@ def main():
             "allreduce": (dp.hook_kind if use_dist else None), "rccl_ranks": (comm[1] if comm else None),
             "strong": strong,
             "roofline": roof, "kernels": kernels, "reduced_profiling_run": reduced, "headline_config": not nonheadline,
-            "target_frac_of_1e6": value / 1e6,
+            "target_frac_of_1e6": value / 1e6, "full": args.full,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             for key, fn in (("cpu_baseline", cpu_baseline), ("cpu_baseline_blas", cpu_baseline_blas),
                             ("cpu_baseline_blas_1core", lambda: cpu_baseline_blas(threads=1)),
                             ("cpu_baseline_all_cores", cpu_baseline_all_cores), ("cpu_baseline_julia", cpu_baseline_julia)):

@@ -223,12 +223,12 @@ def test_two_ranks_with_unequal_shards(ppo, orc, tmp_path):
 
 
 def test_bench_two_ranks_rehearsal_on_one_gpu(P):
-    """bench.py --gpus 2 exactly as the driver calls it (no launcher environment): two rank processes, here sharing the
-    one GPU with the exchange over gloo; the line must report two ranks and carry the strong-scaling leg."""
+    """bench.py --gpus 2 --full exactly as the driver calls it (no launcher environment): two rank processes, here sharing
+    the one GPU with the exchange over gloo; the line must report two ranks and carry the strong-scaling leg."""
     from test_host_logic import _run_bench
     r, out = _run_bench({"PPO_BENCH_BACKEND": "gloo", "PPO_BENCH_SHARE_GPU": "1"}, "--gpus", "2", "--steps", "1",
                         "--warmup", "1", "--envs", "64", "--t-steps", "8", "--epochs", "1", "--hid", "128",
-                        "--no-cpu-baseline", timeout=900)
+                        "--full", "--no-cpu-baseline", timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     assert out["n_gpus"] == 2 and out["config"]["parallelism"] == "dp2" and out["value"] > 0
     assert out["allreduce"] == "torch.distributed/gloo"
@@ -270,22 +270,24 @@ np.savez(sys.argv[2], policy_params=pol.params, selected_actions=ro.selected_act
 
 
 def test_bench_dump_outputs(P, tmp_path):
-    """bench.py --dump-outputs DIR: the arrays of the LAST TIMED iteration (not of the profiling iterations after it), the
-    same from run to run, equal to the same loop replayed through the package in a fresh process."""
+    """bench.py --dump-outputs DIR: the arrays of the LAST TIMED iteration (not of the profiling iterations that --full
+    runs after it), the same from run to run and with or without --full, equal to the same loop replayed through the
+    package in a fresh process."""
     import subprocess
     import sys
     from test_host_logic import _run_bench
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     dumps = []
-    for k in range(2):
-        d = str(tmp_path / ("dump%d" % k))
+    for extra in ([], [], ["--full"]):
+        d = str(tmp_path / ("dump%d" % len(dumps)))
         r, out = _run_bench({}, "--steps", "2", "--warmup", "1", "--envs", "96", "--t-steps", "8", "--epochs", "2", "--hid", "128",
-                            "--no-cpu-baseline", "--dump-outputs", d, timeout=600)
+                            "--no-cpu-baseline", "--dump-outputs", d, *extra, timeout=600)
         assert r.returncode == 0, r.stderr[-3000:]
-        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["full"] == bool(extra)
         dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
-    a, b = dumps
+    a, b, c = dumps
     assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a), "same arguments, same outputs"
+    assert sorted(a) == sorted(c) and all(np.array_equal(a[k], c[k]) for k in a), "--full changes nothing the timed steps hand back"
     assert all(x.dtype in (np.float32, np.float64) for x in a.values())
     assert sum(x.nbytes for x in a.values()) <= 64 << 20
     rep = str(tmp_path / "replay.npz")
@@ -294,3 +296,19 @@ def test_bench_dump_outputs(P, tmp_path):
     want = np.load(rep)
     for k in want.files:
         assert np.array_equal(a[k], want[k]), k
+
+
+def test_bench_plain_run_and_full(P):
+    """A plain bench.py run times the steps and reports the headline only; --full adds the per-kernel / roofline leg and
+    the CPU baselines after the timed steps (left out here with --no-cpu-baseline, as a plain run leaves them out)."""
+    from test_host_logic import _run_bench
+    argv = ("--steps", "1", "--warmup", "1", "--envs", "96", "--t-steps", "8", "--epochs", "1", "--hid", "128")
+    r, plain = _run_bench({}, *argv, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert plain["full"] is False and plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert plain["kernels"] == {} and plain["roofline"] is None and plain["strong"] is None and plain["cpu_baseline"] is None
+    assert not any(k.startswith("cpu_baseline_") for k in plain)
+    r, full = _run_bench({}, *argv, "--full", "--no-cpu-baseline", timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert full["full"] is True and full["value"] > 0 and full["cpu_baseline"] is None
+    assert any(v.get("launches", 0) > 0 for v in full["kernels"].values()) and "k_returns_tn@65536x128" in full["kernels"]

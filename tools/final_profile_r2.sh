@@ -4,10 +4,10 @@
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 F=gpurun_out/final2; mkdir -p $F
-B="python3 bench.py --no-cpu-baseline"
+B="python3 bench.py --full --no-cpu-baseline"
 if [ "${1:-a}" = "a" ]; then
   rm -rf $F/trace $F/pmc
-  timeout -k 10 500 python3 bench.py --steps 5 --warmup 2 > $F/bench.json 2> $F/bench.err || { tail -5 $F/bench.err; exit 1; }
+  timeout -k 10 500 python3 bench.py --full --steps 5 --warmup 2 > $F/bench.json 2> $F/bench.err || { tail -5 $F/bench.err; exit 1; }
   cut -c1-200 $F/bench.json
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $F/trace -- $B --steps 3 --warmup 1 > $F/trace.log 2>&1 || { tail -5 $F/trace.log; exit 1; }
   rm -f $F/trace/*/*kernel_trace.csv

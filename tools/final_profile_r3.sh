@@ -8,7 +8,7 @@
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 F=gpurun_out/final3; mkdir -p $F
-B="python3 bench.py --no-cpu-baseline"
+B="python3 bench.py --full --no-cpu-baseline"
 if [ "${1:-a}" = "a" ]; then
   export PPO_PMC_TRAFFIC_FILE=$GRAFT_REPO_ROOT/$F/pmc_traffic.json
   rm -rf $F/trace $F/pmc
@@ -28,7 +28,7 @@ if [ "${1:-a}" = "a" ]; then
   python3 tools/pmc_traffic2.py $F/pmc_traffic.json "f32|envs=4096|quads=8|hid=256=$F/pmc/f32_4096" "f32|envs=8192|quads=32|hid=256=$F/pmc/f32_q32_8192" \
       "bf16|envs=4096|quads=8|hid=256=$F/pmc/bf16_4096" "bf16|envs=65536|quads=8|hid=256=$F/pmc/bf16_65536" "f32|envs=4096|quads=8|hid=128=$F/pmc/f32_h128_4096" \
       "f32|envs=4096|quads=8|hid=256|layers=3=$F/pmc/f32_l3_4096"
-  timeout -k 10 500 python3 bench.py --steps 5 --warmup 2 > $F/bench.json 2> $F/bench.err || { tail -5 $F/bench.err; exit 1; }
+  timeout -k 10 500 python3 bench.py --full --steps 5 --warmup 2 > $F/bench.json 2> $F/bench.err || { tail -5 $F/bench.err; exit 1; }
   cut -c1-200 $F/bench.json
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $F/trace -- $B --steps 3 --warmup 1 > $F/trace.log 2>&1 || { tail -5 $F/trace.log; exit 1; }
   rm -f $F/trace/*/*kernel_trace.csv

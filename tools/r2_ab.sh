@@ -14,7 +14,7 @@ fi
 for rep in 1 2; do for v in $2; do
   if [ "$v" = default ]; then unset PPO_HIP_LIB; else export PPO_HIP_LIB=$PWD/proximalpolicyoptimization.jl_amd/libppo_hip_$v.so; fi
   for h in $3; do
-    timeout -k 10 200 python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --hid $h $5 > $O/ab_${v}_$h.json 2> $O/ab_${v}_$h.err || { tail -5 $O/ab_${v}_$h.err; exit 1; }
+    timeout -k 10 200 python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --hid $h $5 > $O/ab_${v}_$h.json 2> $O/ab_${v}_$h.err || { tail -5 $O/ab_${v}_$h.err; exit 1; }
     python3 - $O/ab_${v}_$h.json $v $h <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -13,7 +13,7 @@ for rep in 1 2; do for v in $2; do
   if [ "$v" = default ]; then unset PPO_HIP_LIB; else export PPO_HIP_LIB=$PWD/proximalpolicyoptimization.jl_amd/libppo_hip_$v.so; fi
   for e in 4096 65536; do
     S=4; [ $e = 65536 ] && S=2
-    timeout -k 10 300 python3 bench.py --steps $S --warmup 1 --no-cpu-baseline --dtype bf16 --envs $e > $O/ab_${v}_$e.json 2> $O/ab_${v}_$e.err || { tail -5 $O/ab_${v}_$e.err; exit 1; }
+    timeout -k 10 300 python3 bench.py --full --steps $S --warmup 1 --no-cpu-baseline --dtype bf16 --envs $e > $O/ab_${v}_$e.json 2> $O/ab_${v}_$e.err || { tail -5 $O/ab_${v}_$e.err; exit 1; }
     python3 - $O/ab_${v}_$e.json $v $e <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -11,7 +11,7 @@ for rep in 1 2; do for v in $2; do
   for cfg in "c5s:--dtype bf16 --envs 65536 --steps 1 --warmup 1 --stream /tmp/ppo_ab_stream" "f32c:--steps 3 --warmup 1" "f32:--steps 3 --warmup 1"; do
     name=${cfg%%:*}; extra=${cfg#*:}
     if [ $name = f32c ]; then export PPO_ROLLOUT_COMPACT=1; else unset PPO_ROLLOUT_COMPACT; fi
-    timeout -k 10 300 python3 bench.py --no-cpu-baseline $extra > $O/ab_${v}_$name.json 2> $O/ab_${v}_$name.err || { tail -5 $O/ab_${v}_$name.err; exit 1; }
+    timeout -k 10 300 python3 bench.py --full --no-cpu-baseline $extra > $O/ab_${v}_$name.json 2> $O/ab_${v}_$name.err || { tail -5 $O/ab_${v}_$name.err; exit 1; }
     python3 - $O/ab_${v}_$name.json $v $name <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

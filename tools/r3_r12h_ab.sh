@@ -8,6 +8,6 @@ timeout -k 10 90 python3 -m pytest tests/test_gpu_split_backward.py -x -q > $O/t
 R=$GRAFT_REPO_ROOT/proximalpolicyoptimization.jl_amd/libppo_hip_r12h.so
 for r in 1 2; do for v in default r12h; do
   L=""; [ $v = r12h ] && L=$R
-  PPO_HIP_LIB=$L timeout -k 10 60 python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 --hid 128 > $O/h_${v}_$r.json 2> $O/h_${v}_$r.err && python3 tools/show_bench.py $O/h_${v}_$r.json $v | cut -c1-170
+  PPO_HIP_LIB=$L timeout -k 10 60 python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 --hid 128 > $O/h_${v}_$r.json 2> $O/h_${v}_$r.err && python3 tools/show_bench.py $O/h_${v}_$r.json $v | cut -c1-170
 done; done
 PPO_HIP_LIB=$R timeout -k 10 60 python3 -m pytest tests/test_gpu_split_backward.py -x -q -k "128" > $O/tests_r12h.log 2>&1; echo tests_r12h rc=$?; tail -2 $O/tests_r12h.log

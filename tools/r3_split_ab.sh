@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/${1:-split_ab}; mkdir -p $O
 timeout -k 10 400 python3 -m pytest tests/test_gpu_split_backward.py -x -q -m gpu > $O/tests.log 2>&1; rc=$?; echo "tests rc=$rc"; tail -4 $O/tests.log
 [ $rc -eq 0 ] || exit 1
-B="python3 bench.py --no-cpu-baseline --steps 5 --warmup 2"
+B="python3 bench.py --full --no-cpu-baseline --steps 5 --warmup 2"
 for r in 1 2; do for v in 0 1; do
   PPO_BWD_SPLIT_BF16=$v timeout -k 10 200 $B > $O/bench_${v}_$r.json 2> $O/bench_${v}_$r.err && python3 tools/show_bench.py $O/bench_${v}_$r.json split=$v
 done; done

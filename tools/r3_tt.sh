@@ -8,6 +8,6 @@ echo "tests rc=$rc"; tail -5 $O/tests.log
 [ $rc -ne 0 ] && exit $rc
 for e in 512 1024 256 2048; do
   for tt in 0 100000; do
-    PPO_TRAIN_TILE_MAX_TILES=$tt PPO_BENCH_FORCE_DIST=1 timeout -k 10 200 python3 bench.py --no-cpu-baseline --steps 5 --warmup 2 --envs $e > $O/shard_${e}_tt$tt.json 2> $O/shard_${e}_tt$tt.err && python3 tools/show_bench.py $O/shard_${e}_tt$tt.json "envs=$e tt=$tt" || { tail -5 $O/shard_${e}_tt$tt.err; exit 1; }
+    PPO_TRAIN_TILE_MAX_TILES=$tt PPO_BENCH_FORCE_DIST=1 timeout -k 10 200 python3 bench.py --full --no-cpu-baseline --steps 5 --warmup 2 --envs $e > $O/shard_${e}_tt$tt.json 2> $O/shard_${e}_tt$tt.err && python3 tools/show_bench.py $O/shard_${e}_tt$tt.json "envs=$e tt=$tt" || { tail -5 $O/shard_${e}_tt$tt.err; exit 1; }
   done
 done
