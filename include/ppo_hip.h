@@ -180,24 +180,47 @@ int32_t ppo_adam_set_epoch_count(ppo_adam_t opt, int64_t epochs);
  *   Momentum  v = f32(rho v - eta D); D = -v
  *   Nesterov  d = rho*rho v - ((1 + rho) eta) D (old v, float64); v = f32(rho v - eta D); D = f32(-d)
  *   RMSProp   acc = f32(rho acc + ((1 - rho) D) D); D = f32(D (eta / (sqrt_f32(acc) + epsilon)))
+ * Members without an eta (x: the float32 parameter before this step's update; "array": one of the 2L + 2 arrays of
+ * Flux.params, in order W1, b1, (W, b) per hidden->hidden layer, W3, b3):
+ *   ClipValue    D = f32(clamp(D, -thresh, thresh)); NaN stays NaN
+ *   ClipNorm     per array: S = the float64 sum of D_i^2 over the array, rounded once from the exact sum (the squares of
+ *                float32 values are exact in float64); nrm = f32(sqrt(S)); if nrm > thresh: D_i = f32(D_i (thresh / nrm)).
+ *                Julia takes norm() of a Vector{Float32} through BLAS snrm2, which is not correctly rounded: this is the
+ *                deterministic, correctly rounded definition (a fixed-order double-double sum on the device)
+ *   WeightDecay  D = f32(D + wd x)
+ *   InvDecay     at its n-th update! (n counts them, this one included): D = f32(D (1 / (1 + gamma n)))
+ * Flux.AdamW(eta, beta, decay) is Optimiser(Adam(1, beta), WeightDecay(decay), Descent(eta)).
  * hyper: n rows of 5 doubles, unused trailing entries ignored:
  *   Adam (eta, beta1, beta2, epsilon)   ExpDecay (eta, decay, decay_step, clip, start)   Descent (eta)
  *   Momentum (eta, rho)   Nesterov (eta, rho)   RMSProp (eta, rho, epsilon)
+ *   ClipValue (thresh)   ClipNorm (thresh)   WeightDecay (wd)   InvDecay (gamma)
  * The handle is a ppo_adam_t: ppo_train / ppo_step_batch / ppo_adam_apply take it unchanged; ppo_train's lr history is
- * the left-to-right product of the members' etas after each epoch.  A chain of Adam alone runs ppo_adam_create's
+ * the left-to-right product of the etas of the members that have one, after each epoch (the reference's ppo_train!
+ * fails on a member without eta; the engine goes beyond it here).  A chain of Adam alone runs ppo_adam_create's
  * kernels.  ppo_adam_get_lr returns that product on a chain; ppo_adam_set_lr / _get_state / _set_state need a chain of
- * Adam alone (use the member calls below).  Unknown kind: PPO_ERR_UNSUPPORTED; bad n, duplicate kind: PPO_ERR_ARG. */
+ * Adam alone (use the member calls below).  Unknown kind: PPO_ERR_UNSUPPORTED; bad n, duplicate kind, a NaN or
+ * negative thresh: PPO_ERR_ARG. */
 #define PPO_OPT_ADAM 1
 #define PPO_OPT_EXPDECAY 2
 #define PPO_OPT_DESCENT 3
 #define PPO_OPT_MOMENTUM 4
 #define PPO_OPT_NESTEROV 5
 #define PPO_OPT_RMSPROP 6
+#define PPO_OPT_CLIPVALUE 7
+#define PPO_OPT_CLIPNORM 8
+#define PPO_OPT_WEIGHTDECAY 9
+#define PPO_OPT_INVDECAY 10
 int32_t ppo_optimiser_create(ppo_policy_t pol, int32_t n, const int32_t* kinds, const double* hyper, ppo_adam_t* out);
-int32_t ppo_optimiser_get_eta(ppo_adam_t opt, int32_t member, double* eta);   /* member: 0-based chain position */
+/* member: 0-based chain position; a member without eta (ClipValue .. InvDecay): PPO_ERR_ARG */
+int32_t ppo_optimiser_get_eta(ppo_adam_t opt, int32_t member, double* eta);
 int32_t ppo_optimiser_set_eta(ppo_adam_t opt, int32_t member, double eta);
+/* the member's hyper row (5 doubles, as in ppo_optimiser_create): a caller may change thresh / wd / gamma (or any other
+ * hyper-parameter) between calls, as Flux allows; set_hyper validates like ppo_optimiser_create */
+int32_t ppo_optimiser_get_hyper(ppo_adam_t opt, int32_t member, double* hyper5);
+int32_t ppo_optimiser_set_hyper(ppo_adam_t opt, int32_t member, const double* hyper5);
 /* member state, Flux layout (any argument may be NULL): Adam s0 = m, s1 = v, scalars = beta powers [2];
- * Momentum / Nesterov s0 = velocity; RMSProp s0 = acc; ExpDecay count = update! calls seen (its eta: _get_eta). */
+ * Momentum / Nesterov s0 = velocity; RMSProp s0 = acc; ExpDecay / InvDecay count = update! calls seen (ExpDecay's eta:
+ * _get_eta). */
 int32_t ppo_optimiser_get_state(ppo_adam_t opt, int32_t member, float* s0, float* s1, double* scalars2, int64_t* count);
 int32_t ppo_optimiser_set_state(ppo_adam_t opt, int32_t member, const float* s0, const float* s1,
                                 const double* scalars2, const int64_t* count);

@@ -118,9 +118,11 @@ function HipAdam(p::HipPolicy, eta = 1e-3, beta = (0.9, 0.999), eps = 1e-8)
 end
 
 # Flux.Optimiser chain on the device (ppo_optimiser_create): 1 to 4 of Flux's legacy Adam, ExpDecay, Descent, Momentum,
-# Nesterov, RMSProp, each kind once, e.g. HipChain(policy, Flux.Optimiser(Flux.Adam(1e-4), Flux.ExpDecay(1.0, 0.5, 1000, 1e-6))).
-# Iterates the Flux members, so get_optimizer_learning_rate (src/train.jl:155-158) runs on it; their etas are pushed to the
-# device before each ppo_train! and the decayed ExpDecay eta is pulled back after it.
+# Nesterov, RMSProp, ClipValue, ClipNorm, WeightDecay, InvDecay, each kind once, e.g.
+# HipChain(policy, Flux.Optimiser(Flux.Adam(1e-4), Flux.ExpDecay(1.0, 0.5, 1000, 1e-6))) or HipChain(policy, Flux.AdamW(3e-4)).
+# Iterates the Flux members, so get_optimizer_learning_rate (src/train.jl:155-158) runs on it when every member has an eta;
+# their etas (thresh / wd / gamma for the members without) are pushed to the device before each ppo_train! and the decayed
+# ExpDecay eta is pulled back after it.
 struct HipChain; h::Ptr{Cvoid}; os::Vector{Any}; end
 Base.iterate(c::HipChain, s...) = iterate(c.os, s...)
 member_row(o::Flux.Adam) = (Int32(1), [o.eta, o.beta[1], o.beta[2], o.epsilon, 0.0])
@@ -129,6 +131,10 @@ member_row(o::Flux.Descent) = (Int32(3), [o.eta, 0.0, 0.0, 0.0, 0.0])
 member_row(o::Flux.Momentum) = (Int32(4), [o.eta, o.rho, 0.0, 0.0, 0.0])
 member_row(o::Flux.Nesterov) = (Int32(5), [o.eta, o.rho, 0.0, 0.0, 0.0])
 member_row(o::Flux.RMSProp) = (Int32(6), [o.eta, o.rho, o.epsilon, 0.0, 0.0])
+member_row(o::Flux.ClipValue) = (Int32(7), [Float64(o.thresh), 0.0, 0.0, 0.0, 0.0])
+member_row(o::Flux.ClipNorm) = (Int32(8), [Float64(o.thresh), 0.0, 0.0, 0.0, 0.0])
+member_row(o::Flux.WeightDecay) = (Int32(9), [Float64(o.wd), 0.0, 0.0, 0.0, 0.0])
+member_row(o::Flux.InvDecay) = (Int32(10), [Float64(o.gamma), 0.0, 0.0, 0.0, 0.0])
 member_row(o) = throw(ArgumentError("Optimiser member $(typeof(o)) is not supported on the device"))
 function HipChain(p::HipPolicy, opt::Flux.Optimiser)
     1 <= length(opt.os) <= 4 || throw(ArgumentError("the device runs Optimiser chains of 1 to 4 members"))
@@ -142,19 +148,23 @@ function HipChain(p::HipPolicy, opt::Flux.Optimiser)
 end
 function push_etas!(c::HipChain)
     for (j, o) in enumerate(c.os)
-        check(ccall((:ppo_optimiser_set_eta, LIB), Int32, (Ptr{Cvoid}, Int32, Float64), c.h, j - 1, o.eta))
+        if hasproperty(o, :eta)
+            check(ccall((:ppo_optimiser_set_eta, LIB), Int32, (Ptr{Cvoid}, Int32, Float64), c.h, j - 1, o.eta))
+        else                                          # ClipValue / ClipNorm / WeightDecay / InvDecay: the whole hyper row
+            check(ccall((:ppo_optimiser_set_hyper, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}), c.h, j - 1, last(member_row(o))))
+        end
     end
 end
 function pull_etas!(c::HipChain)
     e = Ref{Float64}()
     for (j, o) in enumerate(c.os)
-        o isa Flux.ExpDecay || continue
+        o isa Flux.ExpDecay || continue                # (members without eta have nothing the device changes)
         check(ccall((:ppo_optimiser_get_eta, LIB), Int32, (Ptr{Cvoid}, Int32, Ref{Float64}), c.h, j - 1, e))
         o.eta = e[]
     end
 end
 # checkpoint / resume of member j (1-based): (s0, s1, scalars, count) -- Adam (m, v, beta powers), Momentum / Nesterov
-# velocity, RMSProp acc, ExpDecay its update count; n = the policy's parameter count
+# velocity, RMSProp acc, ExpDecay / InvDecay its update count; n = the policy's parameter count
 function member_state(c::HipChain, j, n)
     s0, s1, sc, cnt = zeros(Float32, n), zeros(Float32, n), zeros(2), Ref{Int64}(0)
     check(ccall((:ppo_optimiser_get_state, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float32}, Ptr{Float32}, Ptr{Float64}, Ref{Int64}),

@@ -43,7 +43,7 @@ from .disk import (DiskDataset, DiskRollouts, bson_decode_state, bson_encode_sta
                    update_, write_returns_to_disk)
 
 __all__ = [
-    "PPOError", "HipVecEnv", "HipPolicy", "Adam", "ExpDecay", "Descent", "Momentum", "Nesterov", "RMSProp", "Optimiser", "StateData", "BufferRollouts", "BufferDataset",
+    "PPOError", "HipVecEnv", "HipPolicy", "Adam", "ExpDecay", "Descent", "Momentum", "Nesterov", "RMSProp", "ClipValue", "ClipNorm", "WeightDecay", "InvDecay", "AdamW", "Optimiser", "StateData", "BufferRollouts", "BufferDataset",
     "state", "reward", "is_terminal", "reset_", "step_", "action_probabilities", "batch_action_probabilities",
     "batch_state", "number_of_actions_per_state", "batch_advantage", "save_loss", "compute_returns",
     "compute_returns_tn", "gae_tn", "compute_gae_", "profile_gae", "collect_rollouts_", "collect_rollouts_steps_", "construct_dataset",
@@ -474,7 +474,42 @@ class RMSProp:
         self.eta, self.rho, self.epsilon = float(eta), float(rho), float(epsilon)
 
 
-# PPO_OPT_* kinds of include/ppo_hip.h and each member's hyper row (eta first)
+class ClipValue:
+    """Flux legacy ClipValue(thresh): D = clamp(D, -thresh, thresh).  No eta: get_optimizer_learning_rate fails on a chain
+    that holds it, as in the reference."""
+
+    def __init__(self, thresh):
+        self.thresh = float(thresh)
+
+
+class ClipNorm:
+    """Flux legacy ClipNorm(thresh): each parameter array's D scaled by thresh / norm(D) when its 2-norm exceeds thresh
+    (the norm: float64 sum of the squares, rounded once; include/ppo_hip.h)."""
+
+    def __init__(self, thresh):
+        self.thresh = float(thresh)
+
+
+class WeightDecay:
+    """Flux legacy WeightDecay(wd): D += wd * x."""
+
+    def __init__(self, wd=0.0):
+        self.wd = float(wd)
+
+
+class InvDecay:
+    """Flux legacy InvDecay(gamma): D *= 1 / (1 + gamma * n) at its n-th update! call."""
+
+    def __init__(self, gamma=0.001):
+        self.gamma = float(gamma)
+
+
+def AdamW(eta=0.001, beta=(0.9, 0.999), decay=0.0):
+    """Flux 0.13 AdamW: Optimiser(Adam(1, beta), WeightDecay(decay), Descent(eta))."""
+    return Optimiser(Adam(1.0, beta), WeightDecay(decay), Descent(eta))
+
+
+# PPO_OPT_* kinds of include/ppo_hip.h and each member's hyper row (eta first; thresh / wd / gamma for the members without)
 _CHAIN_KINDS = {
     Adam: (1, lambda o: (o.eta, o.beta[0], o.beta[1], o.epsilon, 0.0)),
     ExpDecay: (2, lambda o: (o.eta, o.decay, float(o.step), o.clip, float(o.start))),
@@ -482,14 +517,21 @@ _CHAIN_KINDS = {
     Momentum: (4, lambda o: (o.eta, o.rho, 0.0, 0.0, 0.0)),
     Nesterov: (5, lambda o: (o.eta, o.rho, 0.0, 0.0, 0.0)),
     RMSProp: (6, lambda o: (o.eta, o.rho, o.epsilon, 0.0, 0.0)),
+    ClipValue: (7, lambda o: (o.thresh, 0.0, 0.0, 0.0, 0.0)),
+    ClipNorm: (8, lambda o: (o.thresh, 0.0, 0.0, 0.0, 0.0)),
+    WeightDecay: (9, lambda o: (o.wd, 0.0, 0.0, 0.0, 0.0)),
+    InvDecay: (10, lambda o: (o.gamma, 0.0, 0.0, 0.0, 0.0)),
 }
 _STATE_KINDS = (Adam, Momentum, Nesterov, RMSProp)
+_NO_ETA = (ClipValue, ClipNorm, WeightDecay, InvDecay)
+_HYPER_FIELD = {ClipValue: "thresh", ClipNorm: "thresh", WeightDecay: "wd", InvDecay: "gamma"}
 
 
 class Optimiser:
     """Flux.Optimiser(...): iterable composite (get_optimizer_learning_rate iterates it, src/train.jl:155-158).
-    On the device: 1 to 4 members of Adam, ExpDecay, Descent, Momentum, Nesterov, RMSProp, each kind at most once, in
-    any order (include/ppo_hip.h, ppo_optimiser_create).  Optimiser(Adam(...)) keeps its Adam handle (members[0])."""
+    On the device: 1 to 4 members of Adam, ExpDecay, Descent, Momentum, Nesterov, RMSProp, ClipValue, ClipNorm,
+    WeightDecay, InvDecay, each kind at most once, in any order (include/ppo_hip.h, ppo_optimiser_create); AdamW(...) is
+    such a chain.  Optimiser(Adam(...)) keeps its Adam handle (members[0])."""
 
     def __init__(self, *members):
         self.members = list(members)
@@ -515,7 +557,11 @@ class Optimiser:
         kinds, hyper = [], []
         for m in self.members:
             name = type(m).__name__
-            if not hasattr(m, "eta"):
+            if type(m) in _NO_ETA:
+                t = getattr(m, "thresh", 0.0)
+                if not t >= 0:
+                    raise PPOError(-1, "AssertionError: %s: thresh must be >= 0 (and not NaN), got %r" % (name, t))
+            elif not hasattr(m, "eta"):
                 raise PPOError(-4, "Optimiser member %s has no eta (get_optimizer_learning_rate cannot run it): "
                                    "not supported on the device" % name)
             if type(m) not in _CHAIN_KINDS:
@@ -542,7 +588,10 @@ class Optimiser:
         elif self._policy is not policy:
             raise PPOError(-1, "AssertionError: optimiser state belongs to another policy")
         for j, m in enumerate(self.members):
-            call("ppo_optimiser_set_eta", self._h, j, float(m.eta))
+            if type(m) in _NO_ETA:                          # thresh / wd / gamma may change between calls, as in Flux
+                call("ppo_optimiser_set_hyper", self._h, j, _p(np.ascontiguousarray(hyper[j]), _lib.c_f64p))
+            else:
+                call("ppo_optimiser_set_eta", self._h, j, float(m.eta))
         return self._h
 
     def _pull(self):
@@ -565,8 +614,8 @@ class Optimiser:
 
     def get_state(self):
         """Checkpoint of a bound chain: {"epochs": epochs trained (keys the device permutation), "members": one dict per
-        member in chain order with its eta and state (Adam m, v, beta_pow; Momentum / Nesterov velocity; RMSProp acc;
-        ExpDecay its update count)}."""
+        member in chain order with its eta (or thresh / wd / gamma) and state (Adam m, v, beta_pow; Momentum / Nesterov
+        velocity; RMSProp acc; ExpDecay / InvDecay its update count)}."""
         h = self._adam()._h if self._adam_only() else self._h
         if h is None:
             raise PPOError(-1, "AssertionError: get_state: the optimiser has not been bound to a policy yet")
@@ -578,8 +627,16 @@ class Optimiser:
         for j, m in enumerate(self.members):
             eta, cnt = C.c_double(0), C.c_int64(0)
             s0, s1, sc = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(2, np.float64)
-            call("ppo_optimiser_get_eta", h, j, C.byref(eta))
             call("ppo_optimiser_get_state", h, j, _p(s0, _lib.c_f32p), _p(s1, _lib.c_f32p), _p(sc, _lib.c_f64p), C.byref(cnt))
+            if type(m) in _NO_ETA:
+                hy = np.zeros(5, np.float64)
+                call("ppo_optimiser_get_hyper", h, j, _p(hy, _lib.c_f64p))
+                d = {"kind": type(m).__name__, _HYPER_FIELD[type(m)]: float(hy[0])}
+                if isinstance(m, InvDecay):
+                    d["count"] = int(cnt.value)
+                out.append(d)
+                continue
+            call("ppo_optimiser_get_eta", h, j, C.byref(eta))
             d = {"kind": type(m).__name__, "eta": eta.value}
             if isinstance(m, Adam):
                 d.update(m=s0, v=s1, beta_pow=sc)
@@ -598,7 +655,10 @@ class Optimiser:
         if [d["kind"] for d in ms] != [type(m).__name__ for m in self.members]:
             raise PPOError(-1, "AssertionError: set_state: the checkpoint holds a chain of other members")
         for m, d in zip(self.members, ms):
-            m.eta = float(d["eta"])
+            if type(m) in _NO_ETA:
+                setattr(m, _HYPER_FIELD[type(m)], float(d[_HYPER_FIELD[type(m)]]))
+            else:
+                m.eta = float(d["eta"])
         h = self._handle(policy)
         keep = []                                          # the arrays handed over live until their call returns
         for j, (m, d) in enumerate(zip(self.members, ms)):
@@ -610,7 +670,7 @@ class Optimiser:
             elif isinstance(m, (Momentum, Nesterov, RMSProp)):
                 keep.append(np.ascontiguousarray(d["acc" if isinstance(m, RMSProp) else "velocity"], np.float32))
                 s0 = _p(keep[-1], _lib.c_f32p)
-            elif isinstance(m, ExpDecay):
+            elif isinstance(m, (ExpDecay, InvDecay)):
                 cnt = C.byref(C.c_int64(int(d["count"])))
             call("ppo_optimiser_set_state", h, j, s0, s1, sc, cnt)
         call("ppo_adam_set_epoch_count", h, int(state["epochs"]))

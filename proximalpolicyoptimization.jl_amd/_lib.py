@@ -70,6 +70,8 @@ SIGNATURES = {
     "ppo_optimiser_create": [H, C.c_int32, c_i32p, c_f64p, HP],
     "ppo_optimiser_get_eta": [H, C.c_int32, c_f64p],
     "ppo_optimiser_set_eta": [H, C.c_int32, C.c_double],
+    "ppo_optimiser_get_hyper": [H, C.c_int32, c_f64p],
+    "ppo_optimiser_set_hyper": [H, C.c_int32, c_f64p],
     "ppo_optimiser_get_state": [H, C.c_int32, c_f32p, c_f32p, c_f64p, c_i64p],
     "ppo_optimiser_set_state": [H, C.c_int32, c_f32p, c_f32p, c_f64p, c_i64p],
     "ppo_rollouts_create": [H, C.c_int64, HP],

@@ -550,23 +550,30 @@ int32_t ppo_adam_set_epoch_count(ppo_adam_t opt, int64_t epochs) { ARG_CHECK(opt
 double ppo_adam_s::lr() const {
     if (nmem == 0) return eta;
     double p = 1.0;                                     // get_optimizer_learning_rate: prod(opt.eta for opt in optimizer)
-    for (int j = 0; j < nmem; ++j) p *= mem[j].kind == PPO_OPT_ADAM ? eta : mem[j].eta;
+    for (int j = 0; j < nmem; ++j)                      // the members without eta are skipped (the reference would fail)
+        if (has_eta(mem[j].kind)) p *= mem[j].kind == PPO_OPT_ADAM ? eta : mem[j].eta;
     return p;
+}
+
+// a member's hyper row (include/ppo_hip.h): PPO_OK, or PPO_ERR_ARG with the reason
+static int32_t check_hyper(int32_t kind, const double* h) {
+    if (kind == PPO_OPT_EXPDECAY)
+        ARG_CHECK(h[2] >= 1 && h[2] == std::floor(h[2]) && h[4] == std::floor(h[4]), "ExpDecay: integer decay_step >= 1 and start");
+    if (kind == PPO_OPT_CLIPVALUE || kind == PPO_OPT_CLIPNORM)
+        ARG_CHECK(h[0] >= 0, std::string(kind == PPO_OPT_CLIPNORM ? "ClipNorm" : "ClipValue") + ": thresh must be >= 0 (and not NaN)");
+    return PPO_OK;
 }
 
 int32_t ppo_optimiser_create(ppo_policy_t pol, int32_t n, const int32_t* kinds, const double* hyper, ppo_adam_t* out) {
     ARG_CHECK(pol && kinds && hyper && out, "optimiser_create: null");
     ARG_CHECK(n >= 1 && n <= 4, "optimiser_create: a chain of 1 to 4 members");
     for (int32_t j = 0; j < n; ++j) {
-        if (kinds[j] < PPO_OPT_ADAM || kinds[j] > PPO_OPT_RMSPROP) {
+        if (kinds[j] < PPO_OPT_ADAM || kinds[j] > PPO_OPT_INVDECAY) {
             ppo_set_error("optimiser_create: member " + std::to_string(j) + " has an unknown kind " + std::to_string(kinds[j]));
             return PPO_ERR_UNSUPPORTED;
         }
         for (int32_t k = 0; k < j; ++k) ARG_CHECK(kinds[k] != kinds[j], "optimiser_create: each member kind at most once");
-        if (kinds[j] == PPO_OPT_EXPDECAY) {
-            const double* h = hyper + 5 * (size_t)j;
-            ARG_CHECK(h[2] >= 1 && h[2] == std::floor(h[2]) && h[4] == std::floor(h[4]), "ExpDecay: integer decay_step >= 1 and start");
-        }
+        PPO_TRY(check_hyper(kinds[j], hyper + 5 * (size_t)j));
     }
     ppo_adam_s* o = new ppo_adam_s();
     o->pol = pol; o->nmem = n;
@@ -588,6 +595,10 @@ int32_t ppo_optimiser_create(ppo_policy_t pol, int32_t n, const int32_t* kinds, 
                 if ((s = e.s.alloc(pol->np))) break;
                 (void)hipMemsetAsync(e.s.p, 0, pol->np * 4, g_stream);
             }
+            if (e.kind == PPO_OPT_CLIPNORM) {
+                o->clip_slots = clip_slot_count(pol);
+                if ((s = o->clip_d.alloc(pol->np)) || (s = o->clip_part.alloc(2 * (size_t)o->clip_slots))) break;
+            }
         }
     }
     if (s != PPO_OK) { delete o; return s; }
@@ -604,12 +615,30 @@ static int32_t kind_of(ppo_adam_t opt, int32_t member) { return opt->nmem == 0 ?
 int32_t ppo_optimiser_get_eta(ppo_adam_t opt, int32_t member, double* eta) {
     PPO_TRY(chain_member(opt, member));
     ARG_CHECK(eta, "null");
+    ARG_CHECK(has_eta(kind_of(opt, member)), "optimiser_get_eta: the member has no eta (ppo_optimiser_get_hyper)");
     *eta = kind_of(opt, member) == PPO_OPT_ADAM ? opt->eta : opt->mem[member].eta;
     return PPO_OK;
 }
 int32_t ppo_optimiser_set_eta(ppo_adam_t opt, int32_t member, double eta) {
     PPO_TRY(chain_member(opt, member));
+    ARG_CHECK(has_eta(kind_of(opt, member)), "optimiser_set_eta: the member has no eta (ppo_optimiser_set_hyper)");
     (kind_of(opt, member) == PPO_OPT_ADAM ? opt->eta : opt->mem[member].eta) = eta;
+    return PPO_OK;
+}
+int32_t ppo_optimiser_get_hyper(ppo_adam_t opt, int32_t member, double* h) {
+    PPO_TRY(chain_member(opt, member));
+    ARG_CHECK(h, "null");
+    if (kind_of(opt, member) == PPO_OPT_ADAM) { h[0] = opt->eta; h[1] = opt->beta1; h[2] = opt->beta2; h[3] = opt->eps; h[4] = 0.0; }
+    else { const OptMember& e = opt->mem[member]; h[0] = e.eta; h[1] = e.h1; h[2] = e.h2; h[3] = e.h3; h[4] = e.h4; }
+    return PPO_OK;
+}
+int32_t ppo_optimiser_set_hyper(ppo_adam_t opt, int32_t member, const double* h) {
+    PPO_TRY(chain_member(opt, member));
+    ARG_CHECK(h, "null");
+    const int32_t k = kind_of(opt, member);
+    PPO_TRY(check_hyper(k, h));
+    if (k == PPO_OPT_ADAM) { opt->eta = h[0]; opt->beta1 = h[1]; opt->beta2 = h[2]; opt->eps = h[3]; }   // beta powers stay
+    else { OptMember& e = opt->mem[member]; e.eta = h[0]; e.h1 = h[1]; e.h2 = h[2]; e.h3 = h[3]; e.h4 = h[4]; }
     return PPO_OK;
 }
 int32_t ppo_optimiser_get_state(ppo_adam_t opt, int32_t member, float* s0, float* s1, double* scalars2, int64_t* count) {
@@ -623,7 +652,7 @@ int32_t ppo_optimiser_get_state(ppo_adam_t opt, int32_t member, float* s0, float
     } else if (s0 && e->s.p) {
         PPO_TRY(flat_to_host(opt->pol, s0, e->s.p));
     }
-    if (count) *count = k == PPO_OPT_EXPDECAY ? e->count : 0;
+    if (count) *count = (k == PPO_OPT_EXPDECAY || k == PPO_OPT_INVDECAY) ? e->count : 0;
     return PPO_OK;
 }
 int32_t ppo_optimiser_set_state(ppo_adam_t opt, int32_t member, const float* s0, const float* s1, const double* scalars2,
@@ -638,7 +667,7 @@ int32_t ppo_optimiser_set_state(ppo_adam_t opt, int32_t member, const float* s0,
     } else if (s0 && e->s.p) {
         PPO_TRY(flat_to_device(opt->pol, s0, e->s.p));
     }
-    if (count && k == PPO_OPT_EXPDECAY) { ARG_CHECK(*count >= 0, "ExpDecay: negative update count"); e->count = *count; }
+    if (count && (k == PPO_OPT_EXPDECAY || k == PPO_OPT_INVDECAY)) { ARG_CHECK(*count >= 0, "negative update count"); e->count = *count; }
     return PPO_OK;
 }
 

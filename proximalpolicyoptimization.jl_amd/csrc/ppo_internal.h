@@ -136,10 +136,13 @@ struct ppo_policy_s {
 // handle's own eta / beta / m / v / beta_pow fields
 struct OptMember {
     int32_t kind = 0;                  // PPO_OPT_*
-    double eta = 0.0, h1 = 0.0, h2 = 0.0, h3 = 0.0, h4 = 0.0;   // hyper rows of ppo_optimiser_create (eta in front)
-    int64_t count = 0;                 // ExpDecay: update! calls seen
+    double eta = 0.0, h1 = 0.0, h2 = 0.0, h3 = 0.0, h4 = 0.0;   // hyper rows of ppo_optimiser_create (eta in front; the
+                                       // members without eta keep thresh / wd / gamma in its place)
+    int64_t count = 0;                 // ExpDecay / InvDecay: update! calls seen
     DevBuf<float> s;                   // Momentum / Nesterov velocity, RMSProp acc
 };
+
+inline bool has_eta(int32_t kind) { return kind >= PPO_OPT_ADAM && kind <= PPO_OPT_RMSPROP; }   // ClipValue .. InvDecay have none
 
 struct ppo_adam_s {
     ppo_policy_s* pol;
@@ -151,6 +154,11 @@ struct ppo_adam_s {
     // runs the Adam kernels (k_reduce_adam / k_adam); every other chain the chain kernels (k_reduce_chain / k_chain_update)
     int32_t nmem = 0;
     OptMember mem[4];
+    // ClipNorm member: the update splits in two launches around it (ppo_optim.hip): D of the members before it, and
+    // double-double partial sums of D^2, one per 32 consecutive elements of the first launch
+    DevBuf<float> clip_d;              // [np]
+    DevBuf<double> clip_part;          // [clip_slots][2]
+    int64_t clip_slots = 0;
     bool adam_only() const { return nmem == 0 || (nmem == 1 && mem[0].kind == PPO_OPT_ADAM); }
     double lr() const;                 // left-to-right product of the members' etas (get_optimizer_learning_rate)
 };
@@ -309,6 +317,7 @@ int32_t launch_policy_bwd_bf16(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_
 static inline int bf16_ks1(int F) { return (F + 15) / 16; }     // layer-1 k-steps of 16 (zero padded)
 // fuse (optional): apply the optimiser (Adam, or a chain: k_reduce_chain) + re-pack in the same launch (single-rank training); hist2: the per-batch loss pair of that step
 int32_t launch_grad_reduce(ppo_policy_s* p, int64_t B, int64_t B_global, double entropy_weight, ppo_adam_s* fuse = nullptr, float* hist2 = nullptr);
+int64_t clip_slot_count(const ppo_policy_s* p);                     // ClipNorm partial-sum slots either launch pair writes
 int32_t launch_adam(ppo_adam_s* o, float* hist2_or_null);           // any handle: a chain other than Adam alone -> k_chain_update
 int32_t launch_categorical(const float* probs, const float* u, int64_t B, int64_t A, int32_t* actions, float* psel,
                            int32_t* err);

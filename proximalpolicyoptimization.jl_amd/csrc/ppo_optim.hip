@@ -1,10 +1,13 @@
 // ppo_optim.hip -- gradient slab reduction, K12 Adam (Flux legacy Adam + Flux.update!,
 // src/train.jl:81; semantics SURVEY.md Appendix A) and the re-packing of the updated parameters
 // into the MFMA A-operand fragment orders used by the forward/backward kernels; Flux.Optimiser chains (ExpDecay, Descent,
-// Momentum, Nesterov, RMSProp, Adam; include/ppo_hip.h) through the same reduction and re-pack.
+// Momentum, Nesterov, RMSProp, Adam, ClipValue, ClipNorm, WeightDecay, InvDecay; include/ppo_hip.h) through the same
+// reduction and re-pack.
 #include "ppo_internal.h"
 #include "ppo_device.h"
 #include <algorithm>
+#include <cstring>
+#include <type_traits>
 
 // flat Flux-order parameter vector of Policy(F, HID, NL, 4) (test/policy.jl:9-19): W1, b1, then the NL - 1 hidden->hidden
 // layers (W, b) back to back -- layer l at offW2 + l * (HID*HID + HID) -- then W3, b3
@@ -56,6 +59,24 @@ __device__ __forceinline__ void chain_one(const ChainFuse& C, const ParamLayout&
 __device__ __forceinline__ void fuse_one(const AdamFuse& A, const ParamLayout& L, const PackPtrs& P, int64_t i, float g) { adam_one(A, L, P, i, g); }
 __device__ __forceinline__ void fuse_one(const ChainFuse& C, const ParamLayout& L, const PackPtrs& P, int64_t i, float g) { chain_one(C, L, P, i, g); }
 
+// A chain with a ClipNorm member at position c updates in two launches, because ClipNorm's per-array norm is a reduction
+// across workgroups between the gradient and the update.  Phase 1 (k_grad_reduce<ClipFuse> fused with the slab reduction,
+// or k_chain_clip1 behind an all-reduce) applies members [0, c), stores their state and D into dbuf, and writes one
+// double-double partial sum of D^2 per 32 consecutive elements it walks (a half-wave: every array starts at a multiple of
+// 32 in both the slab order and the Flux order, so a half-wave never straddles two arrays).  Phase 2 (k_clip_apply)
+// finishes each array's norm from its slot range in a fixed order, scales D, applies members (c, n) and does x -= D.
+// No float atomics: a second run repeats the first bit for bit.
+struct ClipFuse {
+    float* hist2; int on;
+    ChainFuse C;                                // members [0, c): C.n = c
+    float* dbuf;                                // [np] D after them, Flux order
+    double* part;                               // [slots][2] (hi, lo)
+};
+__device__ __forceinline__ float chain_delta(const ChainFuse& C, int64_t i, float g);
+__device__ __forceinline__ void clip_partial(double* __restrict__ part, size_t e, float d);
+
+__device__ __forceinline__ void fuse_one(const ClipFuse&, const ParamLayout&, const PackPtrs&, int64_t, float) {}   // (phase 1 returns earlier)
+
 // Block = 64 consecutive slab elements x 4 slab groups (wave g sums slabs g, g+4, g+8, ... with 8 loads in flight);
 // the four partial sums meet in LDS and are added in a fixed order.  4x the waves of a one-thread-per-element
 // layout: the 87 MB slab walk needs the memory-level parallelism (341 blocks of one wave per SIMD did 3.3 TB/s).
@@ -97,7 +118,8 @@ __global__ __launch_bounds__(256) void k_grad_reduce(const float* __restrict__ s
     }
     part[grp][el] = ((ps[0] + ps[1]) + (ps[2] + ps[3])) + ((ps[4] + ps[5]) + (ps[6] + ps[7]));
     __syncthreads();
-    if (grp != 0 || e >= total) return;
+    constexpr bool clip = std::is_same<Fuse, ClipFuse>::value;   // ClipNorm phase 1: every lane of wave 0 joins its half-wave's sum
+    if (grp != 0 || (e >= total && !clip)) return;
     const float s = (part[0][el] + part[1][el]) + (part[2][el] + part[3][el]);
     int64_t canon = -1;
     if (e < nW2) {
@@ -120,6 +142,16 @@ __global__ __launch_bounds__(256) void k_grad_reduce(const float* __restrict__ s
             canon = L.offW2 + (int64_t)(e2 / L.HID) * ((int64_t)nW2l + L.HID) + (int64_t)nW2l + (int64_t)(e2 % L.HID);
         else if ((e2 -= (size_t)L.HID * L.NL2) < (size_t)L.HID * 4) canon = L.offW3 + (int64_t)(e2 & 3) + 4 * (int64_t)(e2 >> 2);
         else canon = L.offb3 + (int64_t)(e2 - (size_t)L.HID * 4);
+    }
+    if constexpr (clip) {
+        float d = 0.f;                          // beyond the end and in dead columns: adds nothing to any norm
+        if (e < total && canon >= 0) {
+            grad[canon] = s;
+            d = chain_delta(A.C, canon, s);
+            A.dbuf[canon] = d;
+        }
+        clip_partial(A.part, e, d);
+        return;
     }
     if (canon >= 0) {
         grad[canon] = s;
@@ -320,15 +352,44 @@ __device__ __forceinline__ float chain_delta(const ChainFuse& C, int64_t i, floa
             const double dn = (c[1] * c[1]) * v0 - ((1.0 + c[1]) * c[0]) * dd;
             C.s0[j][i] = (float)(c[1] * v0 - c[0] * dd);
             d = (float)(-dn);
-        } else {                                                           // RMSProp: acc = rho acc + (1 - rho) D^2; D .*= eta / (sqrt(acc) + eps)
+        } else if (kind == PPO_OPT_RMSPROP) {                              // acc = rho acc + (1 - rho) D^2; D .*= eta / (sqrt(acc) + eps)
             const float a = (float)(c[1] * (double)C.s0[j][i] + ((1.0 - c[1]) * dd) * dd);
             C.s0[j][i] = a;
             // sqrt of the Float32 array: the float64 root of a float rounds to the correctly rounded float root (53 >= 2*24 + 2)
             const float ra = (float)sqrt((double)a);
             d = (float)(dd * (c[0] / ((double)ra + c[2])));
+        } else if (kind == PPO_OPT_CLIPVALUE) {                            // clamp(D, -thresh, thresh); NaN stays NaN
+            d = (float)(dd > c[0] ? c[0] : (dd < -c[0] ? -c[0] : dd));
+        } else if (kind == PPO_OPT_WEIGHTDECAY) {                          // D += wd x (x before this step's update)
+            d = (float)(dd + c[0] * (double)C.params[i]);
+        } else {                                                           // InvDecay: D .*= 1 / (1 + gamma n), host-side
+            d = (float)(dd * c[0]);
         }
     }
     return d;
+}
+
+// (h, l) += (bh, bl) in double-double: the exact error of the leading sum is kept; an infinite or NaN sum stays one
+__device__ __forceinline__ void dd_add(double& h, double& l, double bh, double bl) {
+    const double s = h + bh;
+    if (!isfinite(s)) { h = s; l = 0.0; return; }
+    const double v = s - h;
+    double e = (h - (s - v)) + (bh - v);
+    e += l + bl;
+    h = s + e;
+    l = e - (h - s);
+}
+
+// one double-double sum of D^2 (exact squares) per 32 consecutive elements e, in a fixed shuffle tree; lane 0 of the
+// half-wave stores it in slot e / 32.  All 64 lanes of the wave must call it.
+__device__ __forceinline__ void clip_partial(double* __restrict__ part, size_t e, float d) {
+    double h = (double)d * (double)d, l = 0.0;
+#pragma unroll
+    for (int off = 16; off >= 1; off >>= 1) {
+        const double bh = __shfl_down(h, off, 32), bl = __shfl_down(l, off, 32);
+        dd_add(h, l, bh, bl);
+    }
+    if ((e & 31) == 0) { part[2 * (e >> 5)] = h; part[2 * (e >> 5) + 1] = l; }
 }
 
 __device__ __forceinline__ void chain_one(const ChainFuse& C, const ParamLayout& L, const PackPtrs& P, int64_t i, float g) {
@@ -343,6 +404,81 @@ __global__ void k_chain_update(const float* __restrict__ grad, ParamLayout L, Pa
     if (C.hist2 && i < 2) C.hist2[i] = grad[L.np + i];   // per-batch loss history (after any all-reduce)
     if (i >= L.np) return;
     chain_one(C, L, P, i, grad[i]);
+}
+
+// ClipNorm phase 1 behind an all-reduce (hook path, ppo_step_batch, ppo_adam_apply): slot = Flux-order index / 32
+__global__ __launch_bounds__(256) void k_chain_clip1(const float* __restrict__ grad, ParamLayout L, ClipFuse A) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (A.hist2 && i < 2) A.hist2[i] = grad[L.np + i];   // per-batch loss history (after any all-reduce)
+    float d = 0.f;
+    if (i < L.np) {
+        d = chain_delta(A.C, i, grad[i]);
+        A.dbuf[i] = d;
+    }
+    clip_partial(A.part, (size_t)i, d);
+}
+
+// the 2L + 2 arrays of Flux.params: Flux-order start of each (start[na] = np) and the range of partial-sum slots phase 1
+// wrote for it
+#define PPO_CLIP_MAX_ARRAYS 10
+struct ClipMap {
+    const float* dbuf; const double* part;
+    double thresh;
+    int na;
+    int64_t start[PPO_CLIP_MAX_ARRAYS + 1];
+    int32_t s0[PPO_CLIP_MAX_ARRAYS], s1[PPO_CLIP_MAX_ARRAYS];
+};
+__device__ __forceinline__ int clip_array(const ClipMap& M, int64_t i) {
+    int a = 0;
+    while (a + 1 < M.na && i >= M.start[a + 1]) ++a;
+    return a;
+}
+
+// ClipNorm phase 2: one parameter per thread, 256 per block (many blocks: the re-pack's scattered stores want the CUs).
+// The block first finishes the norm of every array its range touches -- each thread a strided double-double sum over the
+// array's slots (8 loads in flight), the wave's shuffle tree, the 4 waves in order -- the same fixed order in every block;
+// then D = dbuf (scaled when nrm > thresh), members (c, n) of the chain (C), x -= D, re-pack
+#define PPO_CLIP_BLOCK 256
+__global__ __launch_bounds__(PPO_CLIP_BLOCK) void k_clip_apply(ParamLayout L, PackPtrs P, ChainFuse C, ClipMap M) {
+    __shared__ double wsum[PPO_CLIP_BLOCK / 64][2];
+    __shared__ float nrm[PPO_CLIP_MAX_ARRAYS];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int64_t i0 = (int64_t)blockIdx.x * PPO_CLIP_BLOCK, i = i0 + t;
+    const int a0 = clip_array(M, i0), a1 = clip_array(M, std::min<int64_t>(i0 + PPO_CLIP_BLOCK, L.np) - 1);
+    for (int a = a0; a <= a1; ++a) {
+        double h = 0.0, l = 0.0;
+        for (int s = M.s0[a] + t; s < M.s1[a]; s += 8 * PPO_CLIP_BLOCK) {
+            double v[8][2];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int su = s + u * PPO_CLIP_BLOCK;
+                v[u][0] = su < M.s1[a] ? M.part[2 * (size_t)su] : 0.0;
+                v[u][1] = su < M.s1[a] ? M.part[2 * (size_t)su + 1] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) dd_add(h, l, v[u][0], v[u][1]);
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const double bh = __shfl_down(h, off, 64), bl = __shfl_down(l, off, 64);
+            dd_add(h, l, bh, bl);
+        }
+        if (lane == 0) { wsum[w][0] = h; wsum[w][1] = l; }
+        __syncthreads();
+        if (t == 0) {
+            double H = wsum[0][0], Lo = wsum[0][1];
+            for (int k = 1; k < PPO_CLIP_BLOCK / 64; ++k) dd_add(H, Lo, wsum[k][0], wsum[k][1]);
+            nrm[a] = (float)sqrt(H + Lo);                   // S rounded once; nrm = f32(sqrt(S))
+        }
+        __syncthreads();
+    }
+    if (i >= L.np) return;
+    float d = M.dbuf[i];
+    const double nr = (double)nrm[clip_array(M, i)];
+    if (nr > M.thresh) d = (float)((double)d * (M.thresh / nr));
+    const float x = C.params[i] - chain_delta(C, i, d);
+    C.params[i] = x;
+    pack_one(L, P, i, x);
 }
 
 // dataset order -> minibatch order: out[i] = index[perm_epoch(i)]
@@ -394,13 +530,87 @@ static ChainFuse chain_step(ppo_adam_s* o, float* hist2) {
             c[0] = e.eta;
             break;
         }
-        default:                   // Descent (eta), Momentum / Nesterov (eta, rho), RMSProp (eta, rho, epsilon)
-            c[0] = e.eta; c[1] = e.h1; c[2] = e.h2;
+        case PPO_OPT_INVDECAY: {   // h0 gamma: n counts its update! calls, this one included
+            const int64_t n = ++e.count;
+            c[0] = 1.0 / (1.0 + e.eta * (double)n);
+            break;
+        }
+        case PPO_OPT_CLIPNORM:     // not a chain_delta member: split_at_clip takes it out (thresh: ClipMap)
+            break;
+        default:                   // Descent (eta), Momentum / Nesterov (eta, rho), RMSProp (eta, rho, epsilon), ClipValue
+            c[0] = e.eta; c[1] = e.h1; c[2] = e.h2;   // (thresh), WeightDecay (wd)
             C.s0[j] = e.s.p;
             break;
         }
     }
     return C;
+}
+
+// ---------------------------------------------------------------- ClipNorm: the two-launch update
+static int clip_position(const ppo_adam_s* o) {
+    for (int j = 0; j < o->nmem; ++j)
+        if (o->mem[j].kind == PPO_OPT_CLIPNORM) return j;
+    return -1;
+}
+
+static size_t slab_total(const ParamLayout& L) {
+    return (size_t)L.NL2 * L.HID * L.HID + (size_t)L.HID * L.FP + (size_t)L.HID * (1 + L.NL2) + (size_t)L.HID * 4 + 4;
+}
+
+// slots: k_grad_reduce<ClipFuse> writes two per 64-element block, k_chain_clip1 eight per 256-thread block
+int64_t clip_slot_count(const ppo_policy_s* p) {
+    const ParamLayout L = layout_of(p);
+    return std::max<int64_t>(2 * (int64_t)((slab_total(L) + 63) / 64), 8 * ((L.np + 255) / 256));
+}
+
+// the chain of this step (chain_step) split around its ClipNorm at position c: members [0, c) for phase 1, (c, n) for phase 2
+static void split_at_clip(const ChainFuse& C, int c, ChainFuse& before, ChainFuse& after) {
+    before = C;
+    before.n = c;
+    after = C;
+    after.hist2 = nullptr;
+    after.n = C.n - c - 1;
+    for (int j = 0; j < after.n; ++j) {
+        after.kind[j] = C.kind[c + 1 + j];
+        std::memcpy(after.c[j], C.c[c + 1 + j], sizeof(after.c[j]));
+        after.s0[j] = C.s0[c + 1 + j]; after.s1[j] = C.s1[c + 1 + j];
+    }
+}
+
+// Flux.params arrays in order (W1, b1, (W, b) per hidden->hidden layer, W3, b3) with the slots phase 1 wrote for each:
+// in the slab order of k_grad_reduce (slab_order) or in the Flux order of k_chain_clip1
+static ClipMap clip_map(const ppo_adam_s* o, const ParamLayout& L, bool slab_order) {
+    ClipMap M = {};
+    M.dbuf = o->clip_d.p; M.part = o->clip_part.p; M.thresh = o->mem[clip_position(o)].eta;
+    const int64_t H = L.HID, nW2l = H * H, nW2 = (int64_t)L.NL2 * nW2l, nW1 = H * L.FP, tail = nW2 + nW1;
+    auto add = [&](int64_t canon_lo, int64_t canon_hi, int64_t slab_lo, int64_t slab_hi) {
+        const int64_t lo = slab_order ? slab_lo : canon_lo, hi = slab_order ? slab_hi : canon_hi;
+        M.start[M.na] = canon_lo; M.s0[M.na] = (int32_t)(lo / 32); M.s1[M.na] = (int32_t)((hi + 31) / 32);
+        ++M.na;
+    };
+    add(L.offW1, L.offb1, nW2, nW2 + nW1);                                  // W1 (the slab block also holds the dead columns)
+    add(L.offb1, L.offW2, tail, tail + H);                                  // b1
+    for (int l = 0; l < L.NL2; ++l) {
+        const int64_t w = L.offW2 + l * (nW2l + H);
+        add(w, w + nW2l, l * nW2l, (l + 1) * nW2l);                         // W of hidden->hidden layer l
+        add(w + nW2l, w + nW2l + H, tail + H * (1 + l), tail + H * (2 + l)); // its b
+    }
+    const int64_t t3 = tail + H * (1 + L.NL2);
+    add(L.offW3, L.offb3, t3, t3 + 4 * H);                                  // W3
+    add(L.offb3, L.np, t3 + 4 * H, t3 + 4 * H + 4);                         // b3
+    M.start[M.na] = L.np;
+    return M;
+}
+
+// phase 1 is launched by the caller; this is phase 2
+static int32_t launch_clip_apply(ppo_adam_s* o, const ParamLayout& L, const ChainFuse& after, bool slab_order) {
+    ppo_policy_s* p = o->pol;
+    const ClipMap M = clip_map(o, L, slab_order);
+    ProfScope ps("k_clip_apply");
+    hipLaunchKernelGGL(k_clip_apply, dim3((unsigned)((L.np + PPO_CLIP_BLOCK - 1) / PPO_CLIP_BLOCK)), dim3(PPO_CLIP_BLOCK), 0,
+                       ppo_stream(), L, packs_of(p), after, M);
+    HIP_TRY(hipGetLastError());
+    return PPO_OK;
 }
 static void chain_done(ppo_adam_s* o) {
     for (int j = 0; j < o->nmem; ++j)
@@ -411,6 +621,22 @@ static void chain_done(ppo_adam_s* o) {
 int32_t launch_grad_reduce(ppo_policy_s* p, int64_t B, int64_t B_global, double entropy_weight, ppo_adam_s* fuse, float* hist2) {
     ParamLayout L = layout_of(p);
     const size_t total = (size_t)L.NL2 * L.HID * L.HID + (size_t)L.HID * L.FP + (size_t)L.HID * (1 + L.NL2) + (size_t)L.HID * 4 + 4;
+    if (fuse && clip_position(fuse) >= 0) {
+        ClipFuse A = {};
+        ChainFuse after;
+        split_at_clip(chain_step(fuse, hist2), clip_position(fuse), A.C, after);
+        A.hist2 = hist2; A.on = 1; A.dbuf = fuse->clip_d.p; A.part = fuse->clip_part.p;
+        {
+            ProfScope ps("k_reduce_clip");
+            hipLaunchKernelGGL(k_grad_reduce<ClipFuse>, dim3((unsigned)((total + 63) / 64) + 1), dim3(256), 0, ppo_stream(), p->slabs.p,
+                               slab_floats(p->F, p->HID, p->L), p->nwg_bwd, p->nwg_small ? p->nwg_small : p->nwg_bwd, L, p->grad.p, p->loss_terms.p, B,
+                               1.0 / (double)B_global, entropy_weight, A, packs_of(p));
+            HIP_TRY(hipGetLastError());
+        }
+        PPO_TRY(launch_clip_apply(fuse, L, after, true));
+        chain_done(fuse);
+        return PPO_OK;
+    }
     if (fuse && !fuse->adam_only()) {
         const ChainFuse C = chain_step(fuse, hist2);
         ProfScope ps("k_reduce_chain");
@@ -438,6 +664,20 @@ int32_t launch_grad_reduce(ppo_policy_s* p, int64_t B, int64_t B_global, double 
 int32_t launch_adam(ppo_adam_s* o, float* hist2) {
     ppo_policy_s* p = o->pol;
     ParamLayout L = layout_of(p);
+    if (clip_position(o) >= 0) {
+        ClipFuse A = {};
+        ChainFuse after;
+        split_at_clip(chain_step(o, hist2), clip_position(o), A.C, after);
+        A.hist2 = hist2; A.on = 1; A.dbuf = o->clip_d.p; A.part = o->clip_part.p;
+        {
+            ProfScope ps("k_chain_clip1");
+            hipLaunchKernelGGL(k_chain_clip1, dim3((unsigned)((L.np + 255) / 256)), dim3(256), 0, ppo_stream(), p->grad.p, L, A);
+            HIP_TRY(hipGetLastError());
+        }
+        PPO_TRY(launch_clip_apply(o, L, after, false));
+        chain_done(o);
+        return PPO_OK;
+    }
     if (!o->adam_only()) {
         const ChainFuse C = chain_step(o, hist2);
         ProfScope ps("k_chain_update");
