@@ -45,6 +45,46 @@ def philox4x32_10(ctr, key):
     return np.array(c, np.uint32)
 
 
+def _feistel_round(x, k):
+    x = x * np.uint32(0x9E3779B1) + np.uint32(k)
+    x ^= x >> np.uint32(15)
+    x *= np.uint32(0x85EBCA77)
+    x ^= x >> np.uint32(13)
+    x *= np.uint32(0xC2B2AE3D)
+    x ^= x >> np.uint32(16)
+    return x
+
+
+def feistel_perm(n, seed, epoch):
+    """Minibatch order of ppo_train! without an explicit permutation (stands in for randperm, src/train.jl:93): entry i
+    is the dataset position drawn i-th.  Six Feistel rounds on the smallest even number of bits that covers n, round r
+    keyed by the low (even r) or high (odd r) word of the 64-bit seed, the epoch and r; values >= n walk the cycle
+    again.  Vectorised over i (oracle/ppo_oracle.c orc_feistel_perm takes one i at a time)."""
+    n = int(n)
+    if n <= 1:
+        return np.zeros(max(n, 0), np.int64)
+    seed, epoch = int(seed) % 2 ** 64, int(epoch) % 2 ** 32
+    bits = 2
+    while (1 << bits) < n:
+        bits += 2
+    hb = bits // 2
+    hmask = np.uint32((1 << hb) - 1)
+    keys = [((seed >> (32 if r & 1 else 0)) ^ (epoch * 0x9E3779B9) ^ (r * 0x7F4A7C15)) & 0xFFFFFFFF for r in range(6)]
+    out = np.empty(n, np.int64)
+    pos = np.arange(n, dtype=np.int64)
+    x = pos.astype(np.uint64)
+    while pos.size:
+        L = (x >> np.uint64(hb)).astype(np.uint32) & hmask
+        R = x.astype(np.uint32) & hmask
+        for k in keys:
+            L, R = R, L ^ (_feistel_round(R, k) & hmask)
+        x = (L.astype(np.uint64) << np.uint64(hb)) | R.astype(np.uint64)
+        inside = x < np.uint64(n)
+        out[pos[inside]] = x[inside].astype(np.int64)
+        pos, x = pos[~inside], x[~inside]
+    return out
+
+
 def index_to_action(index, actions_per_edge=4, edges=4):
     """test/quad_game_utilities.jl:95-105 (1-based); edges=3 is the tutorial notebook's triangle variant."""
     apq = edges * actions_per_edge

@@ -52,6 +52,7 @@ def lib():
         L.orc_u01.argtypes = [C.c_uint32]
         L.orc_feistel_perm.restype = C.c_int64
         L.orc_feistel_perm.argtypes = [C.c_int64, C.c_int64, C.c_uint64, C.c_uint32]
+        L.orc_feistel_perm_all.argtypes = [C.c_int64, C.c_uint64, C.c_uint32, c_i64p]
         L.orc_env_create.restype = C.POINTER(_Env)
         L.orc_env_create.argtypes = [C.c_int32, C.c_int32, C.c_float, C.c_int64, C.c_int64, C.c_uint64]
         L.orc_env_destroy.argtypes = [C.POINTER(_Env)]
@@ -59,6 +60,8 @@ def lib():
         L.orc_env_reset_one.argtypes = [C.POINTER(_Env), C.c_int64]
         L.orc_env_step_one.argtypes = [C.POINTER(_Env), C.c_int64, C.c_int32]
         L.orc_env_observe_one.argtypes = [C.POINTER(_Env), C.c_int64, c_i8p]
+        L.orc_env_step_all.argtypes = [C.POINTER(_Env), c_i32p]
+        L.orc_env_observe_all.argtypes = [C.POINTER(_Env), c_i8p]
         L.orc_env_template.restype = C.c_int32
         L.orc_env_template.argtypes = [C.c_int32, C.c_int32, C.c_int32]
         L.orc_mlp_num_params.restype = C.c_int64
@@ -139,8 +142,9 @@ def u01(w):
 
 
 def feistel_perm(n, seed, epoch):
-    L = lib()
-    return np.array([L.orc_feistel_perm(i, n, seed, epoch) for i in range(n)], np.int64)
+    out = np.empty(n, np.int64)
+    lib().orc_feistel_perm_all(n, seed, epoch, _p(out, c_i64p))
+    return out
 
 
 def index_to_action(index1, actions_per_edge=4, edges=4):
@@ -230,6 +234,12 @@ class Env:
         for n, a in enumerate(actions):
             self.step_one(n, a)
 
+    def step_all(self, actions):
+        """step(actions) in one call into the oracle (envs in order 0..N-1)."""
+        a = np.ascontiguousarray(actions, np.int32)
+        assert a.shape == (self.N,)
+        self.L.orc_env_step_all(self.e, _p(a, c_i32p))
+
     def observe_one(self, n):
         obs = np.empty((self.H, self.F), np.int8)
         self.L.orc_env_observe_one(self.e, n, _p(obs, c_i8p))
@@ -237,6 +247,12 @@ class Env:
 
     def observe(self):
         return np.stack([self.observe_one(n) for n in range(self.N)])
+
+    def observe_all(self):
+        """observe() in one call into the oracle."""
+        obs = np.empty((self.N, self.H, self.F), np.int8)
+        self.L.orc_env_observe_all(self.e, _p(obs, c_i8p))
+        return obs
 
     def _arr(self, name, dtype, per=1):
         c = self.e.contents

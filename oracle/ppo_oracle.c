@@ -137,6 +137,10 @@ int64_t orc_feistel_perm(int64_t i, int64_t n, uint64_t seed, uint32_t epoch) {
     return (int64_t)x;
 }
 
+void orc_feistel_perm_all(int64_t n, uint64_t seed, uint32_t epoch, int64_t* out) {
+    for (int64_t i = 0; i < n; ++i) out[i] = orc_feistel_perm(i, n, seed, epoch);
+}
+
 /* ===================================================================== synthetic env */
 
 orc_env* orc_env_create(int32_t Q, int32_t max_actions, float no_action_reward, int64_t N,
@@ -218,6 +222,10 @@ void orc_env_observe_one(const orc_env* e, int64_t n, int8_t* obs) {
     }
 }
 
+void orc_env_observe_all(const orc_env* e, int8_t* obs) {
+    for (int64_t n = 0; n < e->N; ++n) orc_env_observe_one(e, n, obs + (size_t)n * e->H * e->F);
+}
+
 static int total_abs(const int8_t* sc, uint32_t act, int Q) {
     int s = 0;
     for (int q = 0; q < Q; ++q) if ((act >> q) & 1u)
@@ -286,6 +294,10 @@ void orc_env_step_one(orc_env* e, int64_t n, int32_t a) {
     int sum = total_sum(sc, act, Q);
     int opt = sum < 0 ? -sum : sum;
     e->done[n] = (uint8_t)((new_total == opt) || (e->steps[n] >= e->max_actions));
+}
+
+void orc_env_step_all(orc_env* e, const int32_t* actions) {
+    for (int64_t n = 0; n < e->N; ++n) orc_env_step_one(e, n, actions[n]);
 }
 
 /* index_to_action for elements with `edges` edges (4: the quad game, test/quad_game_utilities.jl:95-105;

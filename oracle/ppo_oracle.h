@@ -45,6 +45,7 @@ float orc_u01(uint32_t w); /* (w>>8) * 2^-24  in [0,1) */
 /* Feistel bijection on [0,n): minibatch permutation used when no explicit permutation
  * is supplied (stands in for randperm, src/train.jl:93) */
 int64_t orc_feistel_perm(int64_t i, int64_t n, uint64_t seed, uint32_t epoch);
+void orc_feistel_perm_all(int64_t n, uint64_t seed, uint32_t epoch, int64_t* out /*[n]*/);
 
 /* ---------------- synthetic rand-poly-shaped env (plugin contract:
  *   src/ProximalPolicyOptimization.jl:16-20; shapes test/quad_game_utilities.jl:39-59,95-110) */
@@ -73,6 +74,9 @@ void orc_env_reset_one(orc_env* e, int64_t n);
 void orc_env_reset(orc_env* e);
 void orc_env_step_one(orc_env* e, int64_t n, int32_t action); /* 0-based action */
 void orc_env_observe_one(const orc_env* e, int64_t n, int8_t* obs /*[H][F]*/);
+/* every env in order: orc_env_step_one / orc_env_observe_one for n = 0..N-1 */
+void orc_env_step_all(orc_env* e, const int32_t* actions /*[N], 0-based*/);
+void orc_env_observe_all(const orc_env* e, int8_t* obs /*[N][H][F]*/);
 int32_t orc_env_template(int32_t Q, int32_t h, int32_t t); /* vertex id or -1 */
 /* (quad,edge,type) 1-based decode of a 1-based index: test/quad_game_utilities.jl:95-105 */
 void orc_index_to_action(int32_t index1, int32_t actions_per_edge, int32_t* quad, int32_t* edge, int32_t* type);

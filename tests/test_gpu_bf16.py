@@ -230,13 +230,22 @@ def test_bf16_learning_signal(P):
     assert np.mean(means[-3:]) > np.mean(means[:3]) + 0.05, means
 
 
-def test_bf16_config5_size_properties(P):
-    """BASELINE config 5 shapes: 65536 envs, 2x256 bf16 MLP, fp32 returns.  Size-independent properties only."""
+def test_bf16_config5_size_properties(P, orc, npo):
+    """BASELINE config 5 shapes: 65536 envs, 2x256 bf16 MLP, fp32 returns (the 64 x 16 return-scan tiles).  The whole
+    rollout is replayed on the oracle env teacher-forced with the device's own probabilities (test_gpu_parity.replay_rollout:
+    states, masks, actions, p_sel, rewards, done flags, returns bit for bit); probabilities at wave / workgroup edges
+    against the bf16 oracle."""
+    from test_gpu_parity import collect_twice, edge_env_ids, replay_rollout
     N, T = 65536, 4
-    env = P.HipVecEnv(num_envs=N, Q=8, max_actions=16, seed=5)
-    pol = P.HipPolicy(72, 256, 2, 4, seed=1, dtype="bf16")
-    ro = P.BufferRollouts()
-    P.collect_rollouts_steps_(ro, env, pol, T, 1.0)
+    kw = dict(num_envs=N, Q=8, max_actions=16, seed=5)
+    p0 = P.HipPolicy(72, 256, 2, 4, seed=1, dtype="bf16").params
+
+    def policy():
+        pol = P.HipPolicy(72, 256, 2, 4, seed=1, dtype="bf16")
+        pol.params = p0
+        return pol
+
+    env, pol, ro, probs, _ = collect_twice(P, kw, policy, T, 1.0)
     assert len(ro) == N * T
     a = ro.selected_actions - 1
     st, act = ro.state_data
@@ -244,6 +253,17 @@ def test_bf16_config5_size_properties(P):
     assert np.all((act.reshape(-1) >> (a.reshape(-1) // 16)) & 1 == 1), "only unmasked actions are ever sampled"
     ps = ro.selected_action_probabilities
     assert np.all(ps > 0) and np.all(ps <= 1.0)
+    ids = np.array(edge_env_ids(N))
+    for t in (0, 1, T // 2, T - 1):
+        want = npo.action_probabilities_bf16(p0, 72, 256, st[t, ids], npo.batch_masks(act[t, ids], 8))
+        got = probs[t, ids]
+        # tolerance of test_bf16_forward_vs_oracle: 5e-3 relative + 1e-6 absolute per probability
+        assert np.all(np.abs(got - want) <= 5e-3 * want + 1e-6), (t, float(np.abs(got - want).max()))
+    del st
+    counts, _ = replay_rollout(orc, env, ro, kw, 1.0, probs)
+    del probs
+    print("config-5 replay counters:", counts)
+    assert counts["transitions"] == N * T and counts["early"] > 0, counts      # episodes that reach the optimum early
     ds = P.construct_dataset(ro)
     opt = P.Optimiser(P.Adam(1e-4))
     h = P.ppo_train_(pol, opt, ds, 0.05, 65536, 1, 0.01, seed=0, verbose=False)

@@ -22,13 +22,36 @@ def P(ppo):
 
 
 # ---------------------------------------------------------------- K6 returns / GAE
+def _plant_done(d):
+    """Done flags where the return scans' passes and workgroups meet: rows 0 and T-1 and both rows of every 16-row pass
+    boundary (T-16k, T-16k-1; the 32-row passes' boundaries are among them) on the first and last column of the array
+    and of one workgroup of every tile width (64, 128, 256 columns); one column done on every row, one never done."""
+    T, N = d.shape
+    rows = sorted({0, T - 1} | {r for k in range(1, T // 16 + 1) for r in (T - 16 * k, T - 16 * k - 1) if r >= 0})
+    cols = {0, N - 1}
+    for C in (64, 128, 256):
+        w = (N // 2) // C
+        cols |= {c for c in (w * C, w * C + C - 1) if c < N}
+    for c in cols:
+        d[rows, c] = 1
+    if N >= 4:
+        d[:, 1] = 1
+        d[:, N - 2] = 0
+
+
 @pytest.mark.parametrize("T,N", [(1, 1), (6, 1), (128, 1), (129, 65), (127, 64), (300, 200), (128, 4096),
-                                 (130, 16384), (33, 16388)])
+                                 (130, 16384), (33, 16388),
+                                 (1, 32768), (17, 65540), (128, 131068),          # 64 x 16 tiles
+                                 (15, 131072), (129, 131076), (16, 262144),       # 128 x 16 tiles
+                                 (17, 65537)])                                    # one lane per column, wide grid
 @pytest.mark.parametrize("gamma", [1.0, 0.99, np.float32(0.99)])
 def test_returns_tn_bitexact(P, orc, T, N, gamma):
+    """Every tile shape of launch_returns_tn (128 x 32, 64 x 16 and 128 x 16 columns x rows above 16384 columns, one lane
+    per column otherwise) in both discount types: full and partly filled last workgroups, ragged last passes."""
     rng = np.random.default_rng(T * 1000 + N)
     r = (rng.normal(size=(T, N)) * 3).astype(np.float32)
     d = (rng.random((T, N)) < 0.03).astype(np.uint8)
+    _plant_done(d)
     got = P.compute_returns_tn(r, d, gamma)
     want = orc.compute_returns_tn(r, d, float(gamma), isinstance(gamma, np.float32))
     assert np.array_equal(got, want)
@@ -62,7 +85,8 @@ def test_returns_rel_tolerance_vs_pure_f32(P):
     assert np.allclose(a, b, rtol=1e-5, atol=1e-5)
 
 
-@pytest.mark.parametrize("T,N", [(77, 130), (1, 1), (128, 16384), (45, 16388), (33, 65536), (16, 262144)])
+@pytest.mark.parametrize("T,N", [(77, 130), (1, 1), (128, 16384), (45, 16388), (33, 65536), (16, 262144),
+                                 (17, 262148)])
 def test_gae(P, orc, T, N):
     """GAE(gamma, lambda) scan, both kernels (one lane per column below 16384 columns, the LDS-tiled wide form above:
     128- and 256-column workgroups, ragged last pass, partly filled last workgroup): bit-exact against the fp64 oracle;
@@ -716,13 +740,42 @@ def test_ppo_train_epochs_with_explicit_perm(P, orc):
         P.ppo_train_(pol, opt, ds, 0.05, n + 1, 1, 0.01, verbose=False)     # @assert 1 <= batch_size <= num_data
 
 
+FEISTEL_SEEDS = (0, 7, 2 ** 32 + 7, 2 ** 64 - 1)
+
+
 def test_feistel_minibatch_order_is_a_permutation(P, orc):
+    """ppo_train! without `perm` draws its minibatches in the oracle's Feistel order keyed by (seed, epochs the optimiser
+    has trained): the same training as with perm = orc.feistel_perm bit for bit, at dataset lengths that cycle-walk, batch
+    sizes that leave a short last minibatch, three epochs, and seeds that set either 32-bit word or both."""
     env, pol, ro, ds = _make_dataset(P, orc, 10, 10, 128, seed=5)
     opt = P.Optimiser(P.Adam(1e-4))
     before = pol.params.copy()
     ph, eh, lh = P.ppo_train_(pol, opt, ds, 0.05, 32, 1, 0.01, seed=77, verbose=False)
     assert np.isfinite(ph).all() and np.isfinite(eh).all()
     assert not np.array_equal(before, pol.params)
+    rng = np.random.default_rng(11)
+    p0 = (before + (rng.normal(size=before.size) * 0.02).astype(np.float32)).astype(np.float32)
+    for n, batch in ((1, 1), (2, 1), (3, 2), (5, 2), (17, 5), (300, 64), (1025, 256), (4097, 1000)):
+        states = rng.integers(-3, 7, size=(1, n, 32, 72)).astype(np.int8)
+        active = rng.integers(1, 256, size=(1, n)).astype(np.uint32)
+        quads = [np.flatnonzero((int(x) >> np.arange(8)) & 1) for x in active[0]]
+        actions1 = np.array([[16 * rng.choice(q) + rng.integers(0, 16) + 1 for q in quads]], np.int64)
+        p_sel = rng.uniform(0.01, 0.5, size=(1, n)).astype(np.float32)
+        returns = rng.normal(size=(1, n)).astype(np.float32)
+        rnd = P.BufferRollouts()
+        rnd.set_columns(None, states, active, actions1, p_sel, returns)
+        dsn = P.construct_dataset(rnd)
+        assert len(dsn) == n
+        for seed in FEISTEL_SEEDS:
+            seeded_order_matches_oracle(P, orc, p0, 128, dsn, batch, [(seed, 3)], eta=1e-3)
+    # a dataset of whole episodes, whose dataset order (ro.index()) is not the transition order
+    env = P.HipVecEnv(num_envs=6, Q=8, max_actions=9, seed=21)
+    epi = P.BufferRollouts()
+    P.collect_rollouts_(epi, env, P.HipPolicy(72, 128, 2, 4, seed=4), 10, 1.0)
+    assert not np.array_equal(epi.index(), np.arange(len(epi)))
+    dse = P.construct_dataset(epi)
+    for seed in FEISTEL_SEEDS:
+        seeded_order_matches_oracle(P, orc, p0, 128, dse, 7, [(seed, 3)], eta=1e-3)
 
 
 def test_learning_signal(P):
@@ -740,14 +793,162 @@ def test_learning_signal(P):
     assert np.mean(means[-3:]) > np.mean(means[:3]) + 0.05, means
 
 
+# ---------------------------------------------------------------- teacher-forced replay of benchmark-size rollouts
+def oracle_env(orc, env_kw):
+    """The oracle twin of HipVecEnv(**env_kw), reset like a freshly created device env."""
+    oenv = orc.Env(Q=env_kw["Q"], max_actions=env_kw["max_actions"], N=env_kw["num_envs"], seed=env_kw["seed"],
+                   global_offset=env_kw.get("global_offset", 0))
+    oenv.reset()
+    return oenv
+
+
+def cdf_walk(probs, u):
+    """rand(Categorical(p)) as the engine draws it (ppo_policy_tail.h): the sequential fp32 inverse-CDF walk, vectorised
+    over rows ([B, A] probabilities, [B] uniforms); a walk that ends on p = 0 (the fp32 sum fell short of u) hands the
+    residue to the last action with p > 0.  Returns (0-based actions, mask of the rows that took the residue rule)."""
+    cdf = np.cumsum(probs, axis=1, dtype=np.float32)            # add.accumulate: left to right, one fp32 rounding per step
+    a = (cdf[:, :-1] <= u[:, None]).sum(axis=1)                 # cdf is non-decreasing: the walk stops at the first cdf > u
+    short = ~(probs[np.arange(len(probs)), a] > 0)
+    last = probs.shape[1] - 1 - np.argmax(probs[:, ::-1] > 0, axis=1)
+    return np.where(short, last, a), short
+
+
+def replay_rollout(orc, env, ro, env_kw, gamma, probs, oenv=None):
+    """Replay a collected rollout on the oracle env, teacher-forced with the device's actions, and assert bit for bit at
+    every step t: the recorded state and active quads are what the oracle env shows; the action is the sequential fp32
+    CDF walk over the recorded probabilities with the uniform of Philox4x32-10 at counter (global_offset + n, tick[n]) and
+    key (seed low word, seed high word); p_sel = probs[a]; reward and done are what the oracle env returns for that
+    action (it is reset on done).  Then the returns column (discount type kept) and the device's error flags.
+    probs: [T, N, A] from ro.full_probs().  oenv: the oracle env of an earlier call on the same device env (its ticks and
+    episodes continue), None for a fresh one.  Returns (counters, oenv)."""
+    from test_gpu_sampler_agreement import _philox_u01
+    T, N = ro.dims()
+    if oenv is None:
+        oenv = oracle_env(orc, env_kw)
+    assert probs.shape == (T, N, oenv.A)
+    seed, goff = int(env_kw["seed"]), int(env_kw.get("global_offset", 0))
+    gid = (goff + np.arange(N, dtype=np.int64)).astype(np.uint32)
+    st, act = ro.state_data
+    acts = ro.selected_actions - 1
+    p_sel = ro.selected_action_probabilities
+    raw, term = ro.raw_rewards, ro.terminal
+    rows = np.arange(N)
+    rng = np.random.default_rng(T * N)
+    # carried: envs in the middle of an episode when the call starts; spanning: episodes begun in an earlier call that end
+    counts = dict(transitions=0, early=0, max_actions=0, residue=0, carried=int((oenv.steps > 0).sum()), spanning=0)
+    for t in range(T):
+        assert np.array_equal(oenv.observe_all(), st[t]), "recorded states differ from the oracle env at t = %d" % t
+        assert np.array_equal(oenv.active, act[t]), "active quads at t = %d" % t
+        u = _philox_u01(gid, oenv.tick.copy(), seed & 0xFFFFFFFF, seed >> 32)
+        want, short = cdf_walk(probs[t], u)
+        for n in set(rng.integers(0, N, 4).tolist()) | set(np.flatnonzero(short).tolist()):   # the walk, restated
+            oa, oerr = orc.categorical_sample(probs[t, n], u[n])
+            if oerr:
+                oa = int(np.flatnonzero(probs[t, n] > 0)[-1])
+            assert oa == want[n] and bool(oerr) == bool(short[n]), (t, n)
+        bad = np.flatnonzero(acts[t] != want)
+        assert bad.size == 0, "sampled actions at t = %d, envs %s" % (t, bad[:8])
+        assert np.array_equal(p_sel[t], probs[t][rows, acts[t]]), "p_sel != probs[a] at t = %d" % t
+        oenv.step_all(acts[t])
+        done = oenv.done.astype(bool)
+        assert np.array_equal(oenv.reward, raw[t]), "rewards at t = %d" % t
+        assert np.array_equal(done, term[t]), "done flags at t = %d" % t
+        steps = oenv.steps
+        counts["transitions"] += N
+        counts["early"] += int((done & (steps < env_kw["max_actions"])).sum())
+        counts["max_actions"] += int((done & (steps >= env_kw["max_actions"])).sum())
+        counts["spanning"] += int((done & (steps > t + 1)).sum())
+        counts["residue"] += int(short.sum())
+        for n in np.flatnonzero(done):
+            oenv.reset_one(int(n))
+    del st
+    assert np.all(oenv.err == 0)
+    assert np.array_equal(ro.rewards, orc.compute_returns_tn(raw, term, float(gamma), isinstance(gamma, np.float32)))
+    flags = env.error_flags()
+    assert flags & ~32 == 0 and (counts["residue"] == 0 or flags & 32)
+    return counts, oenv
+
+
+def rollout_columns(ro):
+    """Every column of a collected rollout; the [T, N, H, F] states as a digest (a benchmark-size array is 1.2 GB)."""
+    import hashlib
+    st, act = ro.state_data
+    cols = dict(states=hashlib.blake2b(st, digest_size=32).hexdigest(), active=act,
+                actions=ro.selected_actions, p_sel=ro.selected_action_probabilities, raw_rewards=ro.raw_rewards,
+                terminal=ro.terminal, returns=ro.rewards, valid=ro.valid, index=ro.index())
+    del st
+    return cols
+
+
+def assert_same_columns(a, b, what):
+    for k in a:
+        assert np.array_equal(a[k], b[k]), "%s: column %s differs" % (what, k)
+
+
+def collect_twice(P, env_kw, policy_of, T, gamma):
+    """The same rollout from fresh, identical env and policy: once as bench.py collects it (record_probs=False), once
+    with the full probabilities recorded; every column must be bit for bit equal.  Returns the second (env, policy,
+    rollouts, probabilities) and the first one's columns."""
+    env, pol = P.HipVecEnv(**env_kw), policy_of()
+    ro = P.BufferRollouts()
+    P.collect_rollouts_steps_(ro, env, pol, T, gamma)
+    plain = rollout_columns(ro)
+    del ro, env, pol
+    env, pol = P.HipVecEnv(**env_kw), policy_of()
+    ro = P.BufferRollouts()
+    P.collect_rollouts_steps_(ro, env, pol, T, gamma, record_probs=True)
+    assert_same_columns(plain, rollout_columns(ro), "record_probs=True")
+    return env, pol, ro, ro.full_probs(), plain
+
+
+def edge_env_ids(N):
+    """Env ids at wave (64) and workgroup (256 .. 2048) edges, and the last two."""
+    return sorted({n for n in (0, 1, 63, 64, 255, 256, 511, 512, 2047, 2048) if n < N} | {N - 2, N - 1})
+
+
+def seeded_order_matches_oracle(P, orc, p0, HID, ds, batch, calls, eta=1e-4, eps=0.05, ew=0.01):
+    """ppo_train! without `perm`, once per (seed, epochs) of `calls` on one optimiser, against a second policy and
+    optimiser from the same start given perm = the oracle's Feistel orders for the (seed, epoch key) pairs those calls
+    use (the key counts the epochs the optimiser has trained).  After every call: parameters, Adam m / v / beta powers and
+    the loss, entropy and lr histories bit for bit.  Returns the per-call snapshots."""
+    n = len(ds)
+    runs = []
+    for explicit in (False, True):
+        pol = P.HipPolicy(72, HID, 2, 4, seed=0)
+        pol.params = p0
+        opt = P.Optimiser(P.Adam(eta))
+        key, snaps = 0, []
+        for seed, epochs in calls:
+            if explicit:
+                perm = np.stack([orc.feistel_perm(n, seed, key + e) + 1 for e in range(epochs)])
+                h = P.ppo_train_(pol, opt, ds, eps, batch, epochs, ew, perm=perm, verbose=False)
+            else:
+                h = P.ppo_train_(pol, opt, ds, eps, batch, epochs, ew, seed=seed, verbose=False)
+            key += epochs
+            snaps.append((pol.params,) + tuple(opt.members[0].get_state()) + tuple(np.asarray(x) for x in h))
+        runs.append(snaps)
+    for c, (a, b) in enumerate(zip(*runs)):
+        for name, x, y in zip(("params", "adam m", "adam v", "beta powers", "ppo loss", "entropy loss", "lr"), a, b):
+            assert np.array_equal(x, y), "n = %d, call %d %s: seeded order != oracle order" % (n, c, name)
+    return runs[0]
+
+
 # ---------------------------------------------------------------- BASELINE-size properties (config 2)
 def test_full_size_properties(P, orc):
-    """4096 envs x 128 steps, 2x256 MLP: size-independent properties + teacher-forced oracle spot checks."""
+    """The headline: 4096 envs x 128 steps in one launch, 2x256 MLP.  The whole rollout and two 16-step collects that
+    continue the same envs are replayed on the oracle (replay_rollout); per-step launches and the compact storage
+    form give the same columns; full probability vectors at wave / workgroup edges and random spot checks against the
+    device-order oracle; ppo_train! with the benchmark's settings draws its minibatches in the oracle's seeded order."""
     N, T = 4096, 128
-    env = P.HipVecEnv(num_envs=N, Q=8, max_actions=128, seed=1234)
-    pol = P.HipPolicy(72, 256, 2, 4, seed=0)
-    ro = P.BufferRollouts()
-    P.collect_rollouts_steps_(ro, env, pol, T, 1.0)
+    kw = dict(num_envs=N, Q=8, max_actions=128, seed=1234)
+    p0 = P.HipPolicy(72, 256, 2, 4, seed=0).params
+
+    def policy():
+        pol = P.HipPolicy(72, 256, 2, 4, seed=0)
+        pol.params = p0
+        return pol
+
+    env, pol, ro, probs, plain = collect_twice(P, kw, policy, T, 1.0)
     assert len(ro) == N * T
     a = ro.selected_actions
     p = ro.selected_action_probabilities
@@ -757,16 +958,64 @@ def test_full_size_properties(P, orc):
     assert np.all((act >> quad.astype(np.uint32)) & 1), "sampled action on an inactive quad"
     assert np.array_equal(ro.rewards, orc.compute_returns_tn(ro.raw_rewards, ro.terminal, 1.0))
     rng = np.random.default_rng(0)
-    params = pol.params
     for _ in range(40):                     # teacher-forced: recorded state -> oracle probs -> same sample
         t, n = int(rng.integers(0, T)), int(rng.integers(0, N))
-        pr = orc.action_probabilities(params, 72, 256, st[t, n], act[t, n], "dev")
+        pr = orc.action_probabilities(p0, 72, 256, st[t, n], act[t, n], "dev")
         assert p[t, n] == pr[a[t, n] - 1]
+    for t in (0, 1, T // 2, T - 1):
+        for n in edge_env_ids(N):
+            assert np.array_equal(probs[t, n], orc.action_probabilities(p0, 72, 256, st[t, n], act[t, n], "dev")), (t, n)
+    del st
+    counts, oenv = replay_rollout(orc, env, ro, kw, 1.0, probs)
+    del probs
+    counts = [counts]
+    for _ in range(2):             # two more 16-step collects on the same envs: ticks, episodes and env state carry on
+        more = P.BufferRollouts()
+        P.collect_rollouts_steps_(more, env, pol, 16, 1.0, record_probs=True)
+        c, oenv = replay_rollout(orc, env, more, kw, 1.0, more.full_probs(), oenv)
+        counts.append(c)
+        del more
+    del oenv
+    print("headline replay counters:", json.dumps(counts))
+    assert [c["transitions"] for c in counts] == [N * T, N * 16, N * 16]
+    # This policy does not reach an optimum within 128 steps, so every episode of the headline rollout ends at
+    # max_actions = T: the first 16-step collect starts fresh episodes, the second carries them on mid-episode.
+    # (Early terminations at benchmark size: test_gpu_bf16.py::test_bf16_config5_size_properties.)
+    assert counts[0]["max_actions"] > 0 and counts[0]["carried"] == 0, counts
+    assert counts[2]["carried"] > 0, counts
+    # the other executions of the same rollout: per-step launches, and env snapshots instead of observation rows
+    for knob in (P.set_rollout_persistent, P.set_rollout_compact):
+        knob(knob is P.set_rollout_compact)
+        try:
+            other, other_env, other_pol = P.BufferRollouts(), P.HipVecEnv(**kw), policy()
+            P.collect_rollouts_steps_(other, other_env, other_pol, T, 1.0)
+        finally:
+            knob(None)
+        assert_same_columns(plain, rollout_columns(other), knob.__name__)
+        del other, other_env, other_pol
+    # ppo_train! as bench.py runs it (minibatch 4096, Adam 1e-4, eps 0.05, entropy 0.01, a seed per iteration, no perm):
+    # epoch keys 0-1, then 2-3 on the same optimiser
     ds = P.construct_dataset(ro)
-    opt = P.Optimiser(P.Adam(1e-4))
-    ph, eh, _ = P.ppo_train_(pol, opt, ds, 0.05, 4096, 1, 0.01, seed=1, verbose=False)
+    nb = len(ds) // 4096
+    snaps = seeded_order_matches_oracle(P, orc, p0, 256, ds, 4096, [(1000, 2), (1001, 2)])
+    ph, eh, _ = snaps[0][4:]
     assert np.isfinite(ph[0]) and np.isfinite(eh[0])
-    assert np.isfinite(pol.params).all()
+    assert np.isfinite(snaps[1][0]).all()
+    # the first call replayed on the host in the oracle order: forward_backward -> oracle Adam -> parameters
+    host = policy()
+    hp, hm, hv, hbp = p0.copy(), np.zeros_like(p0), np.zeros_like(p0), np.array([0.9, 0.999])
+    for e in range(2):
+        order = orc.feistel_perm(len(ds), 1000, e) + 1
+        sp = se = 0.0
+        for b in range(nb):
+            lp, le = P.forward_backward(host, ds, order[b * 4096:(b + 1) * 4096], 0.05, 0.01)
+            orc.adam_step(hp, host.grad(), hm, hv, hbp, 1e-4)
+            host.params = hp
+            sp += lp                                                  # in order, float64, like ppo_train's history
+            se += le
+        assert ph[e] == sp / nb and eh[e] == se / nb, (e, ph[e], sp / nb, eh[e], se / nb)
+    for name, x, y in zip(("params", "adam m", "adam v", "beta powers"), snaps[0][:4], (hp, hm, hv, hbp)):
+        assert np.array_equal(x, y), "host replay of the first ppo_train! call: " + name
 
 
 # ---------------------------------------------------------------- BASELINE config 4 shape: Q=32 -> H=128, A=512
@@ -827,14 +1076,21 @@ def test_rollout_and_gradient_q32(P, orc, HID, rollout_mode2, storage_mode):
     assert np.isfinite(ph[0]) and np.isfinite(eh[0])
 
 
-def test_config4_size_properties(P, orc, rollout_mode2):
+@pytest.mark.parametrize("HID", [128, 256])
+def test_config4_size_properties(P, orc, HID, rollout_mode2):
     """BASELINE config 4 size: 8192 envs, Q=32 (A=512), masked actions, variable-length episodes; both rollout
-    executions (per-step launches and the one-launch persistent rollout)."""
+    executions (per-step launches and the one-launch persistent rollout).  Global env ids 8192..16383, as on the second
+    rank of a two-GPU weak-scaling run; the whole rollout is replayed on the oracle (replay_rollout)."""
     N, T = 8192, 16
-    env = P.HipVecEnv(num_envs=N, Q=32, max_actions=12, seed=4)
-    pol = P.HipPolicy(72, 128, 2, 4, seed=0)
-    ro = P.BufferRollouts()
-    P.collect_rollouts_steps_(ro, env, pol, T, 0.99)
+    kw = dict(num_envs=N, Q=32, max_actions=12, seed=4, global_offset=8192)
+    p0 = P.HipPolicy(72, HID, 2, 4, seed=0).params
+
+    def policy():
+        pol = P.HipPolicy(72, HID, 2, 4, seed=0)
+        pol.params = p0
+        return pol
+
+    env, pol, ro, probs, _ = collect_twice(P, kw, policy, T, 0.99)
     a, p = ro.selected_actions, ro.selected_action_probabilities
     st, act = ro.state_data
     assert a.min() >= 1 and a.max() <= 512 and np.all(p > 0)
@@ -844,8 +1100,15 @@ def test_config4_size_properties(P, orc, rollout_mode2):
     rng = np.random.default_rng(0)
     for _ in range(10):
         t, n = int(rng.integers(0, T)), int(rng.integers(0, N))
-        pr = orc.action_probabilities(pol.params, 72, 128, st[t, n], act[t, n], "dev")
+        pr = orc.action_probabilities(p0, 72, HID, st[t, n], act[t, n], "dev")
         assert p[t, n] == pr[a[t, n] - 1]
+    for t in (0, 1, T // 2, T - 1):
+        for n in edge_env_ids(N):
+            assert np.array_equal(probs[t, n], orc.action_probabilities(p0, 72, HID, st[t, n], act[t, n], "dev")), (t, n)
+    del st
+    counts, _ = replay_rollout(orc, env, ro, kw, 0.99, probs)
+    print("config-4 replay counters:", json.dumps(counts))
+    assert counts["transitions"] == N * T and counts["max_actions"] > 0, counts
 
 
 # ---------------------------------------------------------------- data-parallel plumbing on one GPU

@@ -134,12 +134,34 @@ def test_adam_c_vs_numpy(orc):
     assert np.all(np.abs(p - p2) == 0)
 
 
+FEISTEL_SEEDS = (0, 7, 2 ** 32 + 7, 2 ** 64 - 1)
+
+
 def test_feistel_is_permutation(orc):
     for n in (1, 2, 7, 100, 1000, 4096):
         for epoch in (0, 1):
             p = orc.feistel_perm(n, 1234, epoch)
             assert np.array_equal(np.sort(p), np.arange(n))
     assert not np.array_equal(orc.feistel_perm(1000, 1234, 0), orc.feistel_perm(1000, 1234, 1))
+    # the vectorised restatement (np_oracle.feistel_perm) is the C oracle's order, at lengths that cycle-walk (n just
+    # above a power of 4 and far below the next one) and at seeds that set either 32-bit word or both
+    for n in (1, 2, 3, 5, 17, 300, 1025, 4097, 524288):
+        for seed in FEISTEL_SEEDS:
+            orders = [np_oracle.feistel_perm(n, seed, e) for e in range(4)]
+            flipped = [np_oracle.feistel_perm(n, seed ^ 2 ** 32, e) for e in range(4)]
+            for e in range(4):
+                assert np.array_equal(orders[e], orc.feistel_perm(n, seed, e)), (n, seed, e)
+                assert np.array_equal(np.sort(orders[e]), np.arange(n))
+            if n < 3:
+                continue
+            same_epoch = [np.array_equal(orders[e], orders[e + 1]) for e in range(3)]
+            same_seed = [np.array_equal(orders[e], flipped[e]) for e in range(4)]
+            if n == 3:
+                # three samples have six orders: two keys coincide one time in six, so here the epoch and the high seed
+                # word must change the order somewhere in the first epochs
+                assert not all(same_epoch) and not all(same_seed), (seed, same_epoch, same_seed)
+            else:
+                assert not any(same_epoch) and not any(same_seed), (n, seed, same_epoch, same_seed)
 
 
 def test_env_invariants(orc):
