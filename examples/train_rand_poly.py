@@ -52,6 +52,7 @@ def main():
     ap.add_argument("--iterations", type=int, default=20)
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32")
+    ap.add_argument("--critic", action="store_true", help="train a device critic of the policy's shape and use its GAE(0.95) advantage")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "best_policy.bson"))
     args = ap.parse_args()
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
@@ -65,8 +66,11 @@ def main():
     policy = PPO.HipPolicy(72, 128, 2, 4, seed=0, dtype=args.dtype)
     optimizer = PPO.Optimiser(PPO.Adam(3e-4))                # an iterable composite, like Flux.Optimiser(Adam(...))
     evaluator = SaveBestModel(args.out)
+    extra = {}
+    if args.critic:                                          # fp32 critic; its own optimiser (keyword-only arguments of ppo_iterate_)
+        extra = dict(critic=PPO.HipCritic(72, 128, 2, seed=1), critic_optimizer=PPO.Optimiser(PPO.Adam(1e-3)), gae_lambda=0.95)
     PPO.ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size, args.iterations, evaluator,
-                     epochs_per_iteration, discount, epsilon, entropy_weight, verbose=False)
+                     epochs_per_iteration, discount, epsilon, entropy_weight, verbose=False, **extra)
     evaluator(policy, env, optimizer)
     best = PPO.load_policy(args.out)                          # BSON.@load path policy
     print("best average return %.3f (first %.3f); checkpoint holds Policy(%d, %d, %d, %d)"

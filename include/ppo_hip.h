@@ -50,7 +50,7 @@ typedef struct ppo_rollouts_s* ppo_rollouts_t;
  * implementation exists in the reference, old scripts use raw returns) */
 #define PPO_ADV_RETURNS 0            /* advantage = returns (what the reference's old scripts do)            */
 #define PPO_ADV_RETURNS_NORMALISED 1 /* (R - mean) / (std + 1e-8) over the minibatch (population std, fp64 stats) */
-#define PPO_ADV_GAE 2                /* the GAE(gamma, lambda) column of ppo_rollouts_compute_gae (host-supplied state values) */
+#define PPO_ADV_GAE 2                /* the GAE(gamma, lambda) column of ppo_rollouts_compute_gae (host-supplied state values) or _gae_critic */
 #define PPO_ADV_GAE_NORMALISED 3     /* the same, normalised over the minibatch like mode 1 */
 
 /* ---------------------------------------------------------------- library / device */
@@ -346,6 +346,35 @@ int32_t ppo_train(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, double ep
                   int32_t num_epochs, double entropy_weight, int32_t adv_mode, const int64_t* perm, uint64_t seed,
                   int32_t rank, int32_t world, ppo_allreduce_fn allreduce, void* allreduce_ctx, double* ppo_hist,
                   double* entropy_hist, double* lr_hist);
+
+/* ---------------------------------------------------------------- critic (device state values)
+ * A critic is an ordinary ppo_policy_t made by ppo_policy_create(F, hidden, L, 4) and read as a state value: the mean of
+ * the 4 outputs of every half-edge row that belongs to an ACTIVE quad,
+ *     V(s) = (sum over active rows r, outputs i of y[r][i]) / (4 * number of active rows),   0 when no quad is active,
+ * trained with Flux.mse(V, target).  Parameters, gradient, optimiser chains and checkpoints are the policy's.  fp32 dtype
+ * only (PPO_ERR_UNSUPPORTED for a bf16 critic, and for one whose F differs from the buffer's); single rank. */
+#define PPO_VTARGET_RETURNS 0         /* regress on the buffer's returns column                                     */
+#define PPO_VTARGET_LAMBDA_RETURNS 1  /* ... on the lambda-returns adv + V of the latest GAE call on these rollouts */
+/* values[b] = V(states[b]): host arrays in and out like ppo_policy_forward */
+int32_t ppo_value_forward(ppo_policy_t critic, const int8_t* states, const uint32_t* active, int64_t B, int32_t H,
+                          float* values);
+/* fills the buffer's device values [T+1][N]: rows 0 .. T-1 are the stored states, row T the state every env is in now
+ * (behind the last step).  env may be NULL -- e.g. for a buffer made by ppo_rollouts_create_shape -- and row T is then
+ * all zeros: the caller bootstraps from 0.  Optional host copy. */
+int32_t ppo_rollouts_compute_values(ppo_rollouts_t ro, ppo_env_t env_or_null, ppo_policy_t critic, float* values_out_or_null);
+/* ppo_rollouts_compute_values + the scan of ppo_rollouts_compute_gae, nothing crossing to the host unless an output is
+ * asked for; ppo_train(..., PPO_ADV_GAE*) works after it */
+int32_t ppo_rollouts_compute_gae_critic(ppo_rollouts_t ro, ppo_env_t env_or_null, ppo_policy_t critic, double gamma,
+                                        double lambda, float* adv_out_or_null, float* lambda_returns_out_or_null);
+/* forward + mse + backward of one minibatch (sample_idx as in ppo_forward_backward): the flat gradient of
+ * sum_b (V(s_b) - target_b)^2 / B_global goes to the critic's gradient buffer (ppo_policy_get_grad), that loss to
+ * loss_out (optional).  target: PPO_VTARGET_*; lambda-returns need a GAE call on these rollouts first (PPO_ERR_ARG). */
+int32_t ppo_value_forward_backward(ppo_policy_t critic, ppo_rollouts_t ro, const int64_t* sample_idx, int64_t B,
+                                   int64_t B_global, int32_t target, double* loss_out_or_null);
+/* the epoch loop of ppo_train for the critic: perm / seed, slices of batch_size with a short last one, mse_hist[ep] =
+ * unweighted mean of the per-batch losses, lr_hist from the chain.  opt: any optimiser made for `critic`. */
+int32_t ppo_value_train(ppo_policy_t critic, ppo_adam_t opt, ppo_rollouts_t ro, int64_t batch_size, int32_t num_epochs,
+                        int32_t target, const int64_t* perm, uint64_t seed, double* mse_hist, double* lr_hist);
 
 /* Native hook (the default of bench.py and DataParallel): the same all-reduce as ONE RCCL call made by the library
  * itself on the engine's stream -- no host-language callback per optimiser step.  RCCL is resolved with dlopen at first

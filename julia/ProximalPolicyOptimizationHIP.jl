@@ -296,6 +296,42 @@ function PPO.ppo_train!(p::HipPolicy, optimizer, r::HipRollouts, epsilon, batch_
     end
     ph, eh, lh
 end
+# ---- device critic: a HipPolicy(F, hidden, L, 4) read as a state value (mean of the outputs of the active quads' rows),
+# trained with Flux.mse; its state values feed GAE without leaving the device (include/ppo_hip.h "critic")
+const VTARGET = Dict(:returns => Int32(0), :lambda_returns => Int32(1))
+function batch_state_values(c::HipPolicy, s::StateData)
+    vs = s.vertex_score; B = size(vs, 3)                               # [F, H, B] column-major == [B][H][F]
+    v = Vector{Float32}(undef, B)
+    check(ccall((:ppo_value_forward, LIB), Int32, (Ptr{Cvoid}, Ptr{Int8}, Ptr{UInt32}, Int64, Int32, Ptr{Float32}),
+                c.h, vs, UInt32.(s.action_mask), B, size(vs, 2), v))
+    v
+end
+function compute_values!(r::HipRollouts, env::Union{Nothing,HipVecEnv}, c::HipPolicy)
+    check(ccall((:ppo_rollouts_compute_values, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32}),
+                r.h, env === nothing ? C_NULL : env.h, c.h, C_NULL))
+end
+function compute_gae_critic!(r::HipRollouts, env::Union{Nothing,HipVecEnv}, c::HipPolicy, gamma, lambda)
+    check(ccall((:ppo_rollouts_compute_gae_critic, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Ptr{Float32}, Ptr{Float32}),
+                r.h, env === nothing ? C_NULL : env.h, c.h, Float64(gamma), Float64(lambda), C_NULL, C_NULL))
+end
+function value_forward_backward(c::HipPolicy, r::HipRollouts, idx::Vector{Int64}; target = :returns, B_global = length(idx))
+    loss = Ref{Float64}()
+    check(ccall((:ppo_value_forward_backward, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Int64, Int64, Int32, Ref{Float64}),
+                c.h, r.h, idx .- 1, length(idx), B_global, VTARGET[target], loss))
+    loss[]
+end
+function value_train!(c::HipPolicy, optimizer, r::HipRollouts, batch_size, num_epochs; target = :returns)
+    oh = opt_handle(optimizer)
+    mh, lh = zeros(num_epochs), zeros(num_epochs)
+    status = ccall((:ppo_value_train, LIB), Int32,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Int64}, UInt64, Ptr{Float64}, Ptr{Float64}),
+                   c.h, oh, r.h, batch_size, num_epochs, VTARGET[target], C_NULL, SEED[], mh, lh)
+    opt_done!(optimizer)
+    check(status)
+    mh, lh
+end
+
 # ppo_iterate!(policy, env, optimizer, ...) (src/train.jl:210-249) then works unchanged once
 # `BufferRollouts()` on its line 230 is replaced by `HipRollouts()` (or dispatched on the env type).
 

@@ -55,6 +55,8 @@ __all__ = [
     "HostRollouts", "HostDataset", "update_rollouts_", "compute_state_value_", "collect_step_data_", "collect_episode_data_",
     "permute_", "shuffle_", "single_trajectory_return", "smoothed_entropy", "clamped_entropy", "ppo_loss", "step_epoch_",
     "save_policy", "load_policy", "forward_backward",
+    "HipCritic", "state_values", "batch_state_values", "compute_values_", "compute_gae_critic_", "value_forward_backward",
+    "value_train_", "pooled_state_value", "value_loss",
 ]
 
 
@@ -402,6 +404,57 @@ def _(policy, s):
 def _(policy, s):
     """test/quad_game_utilities.jl:73-79 -> [A,B] (returned as the transposed view of the C-order [B,A])."""
     return _forward(policy, s.vertex_score, s.action_mask).T
+
+
+# ------------------------------------------------------------------ critic
+class HipCritic(HipPolicy):
+    """A state-value network of the policy's own shape, Policy(in_channels, hidden_channels, num_hidden_layers, 4), read as
+    V(s) = mean of the 4 outputs of every half-edge row of an ACTIVE quad (0 when no quad is active) and trained with
+    Flux.mse.  Being a HipPolicy, `params`, `grad`, save_policy / load_policy and every Optimiser chain work unchanged.
+    fp32 only."""
+
+    def __init__(self, in_channels, hidden_channels, num_hidden_layers, seed=0):
+        super().__init__(in_channels, hidden_channels, num_hidden_layers, 4, seed=seed)
+
+
+def _value_forward(critic, vs, bits):
+    vs = np.ascontiguousarray(vs, np.int8)
+    bits = np.ascontiguousarray(bits, np.uint32)
+    B, Hh, F = vs.shape
+    out = np.empty(B, np.float32)
+    call("ppo_value_forward", critic._h, _p(vs, _lib.c_i8p), _p(bits, _lib.c_u32p), B, Hh, _p(out, _lib.c_f32p))
+    return out
+
+
+def state_values(critic, s):
+    """V(s) of one StateData -> float."""
+    return float(_value_forward(critic, np.asarray(s.vertex_score)[None], np.atleast_1d(np.uint32(s.action_mask)))[0])
+
+
+def batch_state_values(critic, s):
+    """V of a batched StateData ([B,H,F] rows, [B] active-quad masks) -> float32 [B]."""
+    return _value_forward(critic, s.vertex_score, s.action_mask)
+
+
+def pooled_state_value(logits, active):
+    """The critic's pooling on given per-half-edge outputs (plain numpy, for users of the generic path): logits [B,H,4]
+    (or [H,4]), active = active-quad bit mask(s) -> float32 [B]: mean over the rows of active quads and their 4 outputs,
+    0 where no quad is active."""
+    y = np.asarray(logits, np.float32)
+    single = y.ndim == 2
+    y = y[None] if single else y
+    bits = np.atleast_1d(np.asarray(active, np.uint32))
+    on = ((bits[:, None] >> (np.arange(y.shape[1]) // 4).astype(np.uint32)[None, :]) & 1).astype(bool)     # [B,H]
+    n = 4 * on.sum(axis=1)
+    tot = np.where(on[:, :, None], y, np.float32(0)).sum(axis=(1, 2), dtype=np.float32)
+    v = np.where(n > 0, tot / np.maximum(n, 1).astype(np.float32), np.float32(0)).astype(np.float32)
+    return v[0] if single else v
+
+
+def value_loss(values, targets):
+    """Flux.mse(values, targets) in float32 arithmetic -> float."""
+    d = np.asarray(values, np.float32) - np.asarray(targets, np.float32)
+    return float(np.mean(d * d, dtype=np.float32))
 
 
 # ------------------------------------------------------------------ optimiser
@@ -954,6 +1007,28 @@ def compute_gae_(rollouts, values, gamma, lam):
     return adv, ret
 
 
+def compute_values_(rollouts, env, critic):
+    """State values of the buffer from a device critic -> float32 [T+1, N]: rows 0..T-1 are the stored states, row T the
+    state every env is in now (zeros when env is None).  They stay on the device for compute_gae_critic_."""
+    T, N = rollouts.dims()
+    v = np.empty((T + 1, N), np.float32)
+    call("ppo_rollouts_compute_values", rollouts._h, env._h if env is not None else None, critic._h, _p(v, _lib.c_f32p))
+    return v
+
+
+def compute_gae_critic_(rollouts, env, critic, gamma, lam, fetch=True):
+    """compute_values_ + the GAE(gamma, lambda) scan without a host trip; the advantage column stays on the device for
+    ppo_train_(..., advantage="gae"), the lambda-returns for value_train_(..., target="lambda_returns").
+    fetch=True returns (advantages, lambda_returns) [T,N]; fetch=False copies nothing back and returns None."""
+    T, N = rollouts.dims()
+    adv = ret = None
+    if fetch:
+        adv, ret = np.empty((T, N), np.float32), np.empty((T, N), np.float32)
+    call("ppo_rollouts_compute_gae_critic", rollouts._h, env._h if env is not None else None, critic._h, float(gamma),
+         float(lam), _p(adv, _lib.c_f32p) if fetch else None, _p(ret, _lib.c_f32p) if fetch else None)
+    return (adv, ret) if fetch else None
+
+
 class BufferDataset:
     """src/rollout_buffer.jl:95-147.  Non-owning view; indices are 1-based like the reference."""
 
@@ -1125,12 +1200,65 @@ def ppo_train_(policy, optimizer, dataset, epsilon, batch_size, num_epochs, entr
     return list(ph), list(eh), list(lh)                     # lr = get_optimizer_learning_rate per epoch (:144)
 
 
+VALUE_TARGETS = {"returns": 0, "lambda_returns": 1}
+
+
+def _value_target(target):
+    if target not in VALUE_TARGETS:
+        raise PPOError(-4, "value target must be one of %s" % sorted(VALUE_TARGETS))
+    return VALUE_TARGETS[target]
+
+
+def value_forward_backward(critic, dataset, batch_indices, target="returns", B_global=None):
+    """Gradient of Flux.mse(V(dataset[batch_indices]), target) (no update): leaves it in critic.grad(); returns the loss.
+    target: "returns" (the buffer's returns) or "lambda_returns" (adv + V of the latest GAE call on these rollouts)."""
+    t = _value_target(target)
+    ii = np.ascontiguousarray(np.asarray(batch_indices, np.int64) - 1)
+    out = C.c_double(0)
+    call("ppo_value_forward_backward", critic._h, dataset.rollouts._h, _p(ii, _lib.c_i64p), ii.size,
+         int(B_global or ii.size), t, C.byref(out))
+    return out.value
+
+
+def value_train_(critic, optimizer, dataset, batch_size, num_epochs, target="returns", perm=None, seed=0, verbose=True):
+    """ppo_train_'s epoch loop for the critic -> (mse_history, lr_history).  optimizer: any Optimiser chain, bound to the
+    critic (not the one that trains the policy).  Single rank."""
+    t = _value_target(target)
+    oh = optimizer._handle(critic)
+    n = len(dataset)
+    pp = None
+    if perm is not None:
+        pp = np.ascontiguousarray(np.asarray(perm, np.int64).reshape(num_epochs, n) - 1)
+    if not (1 <= batch_size <= n):
+        raise PPOError(-1, "AssertionError: 1 <= batch_size <= num_data")
+    mh, lh = np.zeros(num_epochs, np.float64), np.zeros(num_epochs, np.float64)
+    try:
+        call("ppo_value_train", critic._h, oh, dataset.rollouts._h, int(batch_size), int(num_epochs), t,
+             _p(pp, _lib.c_i64p) if pp is not None else None, int(seed), _p(mh, _lib.c_f64p), _p(lh, _lib.c_f64p))
+    finally:
+        optimizer._pull()
+    if verbose:
+        for e in range(num_epochs):
+            print("EPOCH : %d \t VALUE LOSS : %1.4f \t LR : %1.1e" % (e + 1, mh[e], lh[e]))
+    return list(mh), list(lh)
+
+
 def ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size, num_ppo_iterations, evaluator,
-                 epochs_per_iteration, discount, epsilon, entropy_weight, state_data_path=None, verbose=True):
+                 epochs_per_iteration, discount, epsilon, entropy_weight, state_data_path=None, verbose=True, *,
+                 critic=None, critic_optimizer=None, gae_lambda=0.95, value_epochs=None):
     """PPO.ppo_iterate! (src/train.jl:164-249), positional argument order preserved: 11 arguments = in-memory
     method, a 12th `state_data_path` = the disk method (rollouts through DiskRollouts, directory removed at
-    the end, :198-201)."""
+    the end, :198-201).
+    critic (keyword only; None = the reference's loop, advantage = returns): a HipCritic with its own critic_optimizer.
+    Each iteration then is collect, GAE(discount, gae_lambda) from the critic as it stands, ppo_train_ on that advantage,
+    value_train_ on the lambda-returns for value_epochs (default epochs_per_iteration) epochs; loss gains "value"."""
     loss = {"ppo": [], "entropy": [], "lr": []}
+    if critic is not None:
+        if critic_optimizer is None:
+            raise PPOError(-1, "AssertionError: a critic needs its own critic_optimizer")
+        if state_data_path is not None:
+            raise PPOError(-4, "a critic with disk-backed rollouts is not supported")
+        loss["value"] = []
     for it in range(1, num_ppo_iterations + 1):
         evaluator(policy, env, optimizer)                                                    # :181,226
         if verbose:
@@ -1138,8 +1266,17 @@ def ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size,
         rollouts = BufferRollouts() if state_data_path is None else DiskRollouts(state_data_path)   # :185,230
         collect_rollouts_(rollouts, env, policy, episodes_per_iteration, discount)
         dataset = construct_dataset(rollouts)
-        p, e, lr = ppo_train_(policy, optimizer, dataset, epsilon, minibatch_size, epochs_per_iteration,
-                              entropy_weight, verbose=verbose)
+        if critic is None:
+            p, e, lr = ppo_train_(policy, optimizer, dataset, epsilon, minibatch_size, epochs_per_iteration,
+                                  entropy_weight, verbose=verbose)
+        else:
+            compute_gae_critic_(dataset.rollouts, env, critic, discount, gae_lambda, fetch=False)
+            p, e, lr = ppo_train_(policy, optimizer, dataset, epsilon, minibatch_size, epochs_per_iteration,
+                                  entropy_weight, verbose=verbose, advantage="gae")
+            v, _ = value_train_(critic, critic_optimizer, dataset, minibatch_size,
+                                epochs_per_iteration if value_epochs is None else value_epochs,
+                                target="lambda_returns", verbose=verbose)
+            loss["value"] += v
         loss["ppo"] += p
         loss["entropy"] += e
         loss["lr"] += lr

@@ -115,6 +115,11 @@ SIGNATURES = {
     "ppo_profile_returns": [C.c_int64, C.c_int64, C.c_double, C.c_int32, c_f64p],
     "ppo_profile_gae": [C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int32, c_f64p],
     "ppo_rollouts_compute_gae": [H, c_f32p, C.c_double, C.c_double, c_f32p, c_f32p],
+    "ppo_value_forward": [H, c_i8p, c_u32p, C.c_int64, C.c_int32, c_f32p],
+    "ppo_rollouts_compute_values": [H, H, H, c_f32p],
+    "ppo_rollouts_compute_gae_critic": [H, H, H, C.c_double, C.c_double, c_f32p, c_f32p],
+    "ppo_value_forward_backward": [H, H, c_i64p, C.c_int64, C.c_int64, C.c_int32, c_f64p],
+    "ppo_value_train": [H, H, H, C.c_int64, C.c_int32, C.c_int32, c_i64p, C.c_uint64, c_f64p, c_f64p],
     "ppo_rccl_probe": [],
     "ppo_rccl_unique_id": [C.c_void_p],
     "ppo_rccl_init": [C.c_int32, C.c_int32, C.c_void_p],

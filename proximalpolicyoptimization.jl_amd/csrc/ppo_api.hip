@@ -1257,4 +1257,182 @@ int32_t ppo_train(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, double ep
     return PPO_OK;
 }
 
+
+// ================================================================ critic
+// A critic is a ppo_policy_t read as a state value (include/ppo_hip.h): the refusals every value entry point shares
+static int32_t value_checks(const char* who, ppo_policy_s* critic, int32_t F) {
+    if (critic->dtype != PPO_DTYPE_F32) {
+        ppo_set_error(std::string(who) + ": a bf16-dtype critic is not supported (the value modes exist in the fp32-MFMA forward only)");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    if (critic->F != F) {
+        ppo_set_error(std::string(who) + ": the critic's input width F = " + std::to_string(critic->F) + " differs from the buffer's F = " + std::to_string(F));
+        return PPO_ERR_UNSUPPORTED;
+    }
+    return PPO_OK;
+}
+
+int32_t ppo_value_forward(ppo_policy_t critic, const int8_t* states, const uint32_t* active, int64_t B, int32_t H, float* values) {
+    ARG_CHECK(critic && states && active && values, "state_values: null argument");
+    ARG_CHECK(B >= 1, "state_values: empty batch");
+    if (H != 32 && H != 128) { ppo_set_error("value_forward: H must be 32 (Q=8) or 128 (Q=32) half-edges in this build"); return PPO_ERR_UNSUPPORTED; }
+    PPO_TRY(value_checks("value_forward", critic, critic->F));
+    DevBuf<int8_t> s; DevBuf<uint32_t> a; DevBuf<float> v;
+    const size_t ns = (size_t)B * H * critic->F;
+    PPO_TRY(s.alloc(ns)); PPO_TRY(a.alloc(B)); PPO_TRY(v.alloc(B));
+    PPO_TRY(h2d(s.p, states, ns)); PPO_TRY(h2d(a.p, active, (size_t)B));
+    PPO_TRY(launch_value_predict(critic, s.p, nullptr, a.p, nullptr, 0, B, H, v.p));
+    return d2h(values, v.p, (size_t)B);
+}
+
+// ro->values [T+1][N] on the device: rows 0 .. T-1 from the stored states (one launch, either storage form), row T from the
+// envs' current observation (zeros without an env)
+static int32_t compute_values_dev(const char* who, ppo_rollouts_s* ro, ppo_env_s* env, ppo_policy_s* critic) {
+    ARG_CHECK(ro->T >= 1, "compute_values: empty rollout buffer");
+    ARG_CHECK(ro->H == 32 || ro->H == 128, "compute_values: shape mismatch");
+    PPO_TRY(value_checks(who, critic, ro->F));
+    if (env) ARG_CHECK(ro->N == env->N && ro->H == env->H && ro->F == env->F, "compute_values: rollouts were created for another env shape");
+    const size_t n = (size_t)ro->T * ro->N;
+    PPO_TRY(ro->values.alloc((size_t)(ro->capT + 1) * ro->N));
+    PPO_TRY(launch_value_predict(critic, ro->compact ? nullptr : ro->states.p, ro->compact ? ro->cstate.p : nullptr, ro->active.p,
+                                 ro->tmpl.p, ro->V, (int64_t)n, ro->H, ro->values.p));
+    if (env) {
+        PPO_TRY(env->obs_tmp.alloc((size_t)env->N * env->H * env->F));
+        PPO_TRY(launch_env_observe(env, env->obs_tmp.p, nullptr));
+        PPO_TRY(launch_value_predict(critic, env->obs_tmp.p, nullptr, env->active.p, nullptr, 0, env->N, env->H, ro->values.p + n));
+    } else {
+        HIP_TRY(hipMemsetAsync(ro->values.p + n, 0, (size_t)ro->N * sizeof(float), g_stream));
+    }
+    return PPO_OK;
+}
+
+int32_t ppo_rollouts_compute_values(ppo_rollouts_t ro, ppo_env_t env, ppo_policy_t critic, float* values_out) {
+    ARG_CHECK(ro && critic, "compute_values: null argument");
+    PPO_TRY(compute_values_dev("compute_values", ro, env, critic));
+    if (values_out) return d2h(values_out, ro->values.p, (size_t)(ro->T + 1) * ro->N);
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    return PPO_OK;
+}
+
+int32_t ppo_rollouts_compute_gae_critic(ppo_rollouts_t ro, ppo_env_t env, ppo_policy_t critic, double gamma, double lambda,
+                                        float* adv_out, float* lambda_returns_out) {
+    ARG_CHECK(ro && critic, "compute_gae_critic: null argument");
+    PPO_TRY(compute_values_dev("compute_gae_critic", ro, env, critic));
+    const size_t n = (size_t)ro->T * ro->N;
+    PPO_TRY(ro->adv.alloc((size_t)ro->capT * ro->N)); PPO_TRY(ro->lam_ret.alloc((size_t)ro->capT * ro->N));
+    PPO_TRY(launch_gae_tn(ro->rewards.p, ro->done.p, ro->values.p, ro->adv.p, ro->lam_ret.p, ro->T, ro->N, gamma, lambda));
+    ro->adv_T = ro->T;
+    if (adv_out) PPO_TRY(d2h(adv_out, ro->adv.p, n));
+    if (lambda_returns_out) PPO_TRY(d2h(lambda_returns_out, ro->lam_ret.p, n));
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    return PPO_OK;
+}
+
+// the regression target column [T][N] of a value-training call
+static int32_t value_target(ppo_rollouts_s* ro, int32_t target, const float** col) {
+    if (target != PPO_VTARGET_RETURNS && target != PPO_VTARGET_LAMBDA_RETURNS) { ppo_set_error("value target: unknown target"); return PPO_ERR_UNSUPPORTED; }
+    if (target == PPO_VTARGET_LAMBDA_RETURNS)
+        ARG_CHECK(ro->lam_ret.p && ro->adv_T == ro->T, "value target: lambda-returns mode needs ppo_rollouts_compute_gae on these rollouts first");
+    *col = target == PPO_VTARGET_RETURNS ? ro->returns.p : ro->lam_ret.p;
+    return PPO_OK;
+}
+
+// idx_dev: transition ids (already resolved through the dataset index)
+static int32_t value_forward_backward_dev(ppo_policy_s* critic, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B,
+                                          int64_t B_global, const float* target_col, ppo_adam_s* fuse_opt = nullptr,
+                                          float* fuse_hist2 = nullptr) {
+    PPO_TRY(train_reserve(critic, B * (ro->H / 32), ro->compact));
+    const ValueRoute r = value_route(critic->dtype, critic->F, critic->HID, critic->L, ro->H, ro->compact, B, ppo_knobs());
+    if (r.bwd == TrainBwd::None) { ppo_set_error(r.err); return PPO_ERR_UNSUPPORTED; }
+    if (r.bwd == TrainBwd::Small) {
+        const size_t frag = (size_t)critic->cap_tiles * (critic->HID / 32) * 1024;     // dZ in fragment order, like act1 / act2
+        PPO_TRY(critic->dz1f.alloc(frag));
+        if (critic->L >= 2) PPO_TRY(critic->dz2f.alloc(frag));
+        if (critic->L > 2) PPO_TRY(critic->dzm.alloc((size_t)(critic->L - 2) * frag));
+    }
+    PPO_TRY(launch_value_train_fwd(critic, ro, idx_dev, B, B_global, target_col));
+    switch (r.bwd) {
+    case TrainBwd::Small: PPO_TRY(launch_policy_bwd_small(critic, ro, idx_dev, B)); break;
+    case TrainBwd::X6: PPO_TRY(launch_policy_bwd_x6(critic, ro, idx_dev, B)); break;
+    default: PPO_TRY(launch_policy_bwd(critic, ro, idx_dev, B)); break;     // Fused
+    }
+    PPO_TRY(launch_grad_reduce(critic, B, B_global, 0.0, fuse_opt, fuse_hist2));
+    critic->last_B = B; critic->last_entropy_weight = 0.0;
+    return PPO_OK;
+}
+
+int32_t ppo_value_forward_backward(ppo_policy_t critic, ppo_rollouts_t ro, const int64_t* sample_idx, int64_t B,
+                                   int64_t B_global, int32_t target, double* loss_out) {
+    ARG_CHECK(critic && ro && sample_idx, "value_forward_backward: null argument");
+    ARG_CHECK(B >= 1 && B <= ro->len, "value_forward_backward: 1 <= batch_size <= num_data");
+    ARG_CHECK(B_global >= B, "value_forward_backward: B_global < B");
+    ARG_CHECK(ro->H == 32 || ro->H == 128, "value_forward_backward: shape mismatch");
+    PPO_TRY(value_checks("value_forward_backward", critic, ro->F));
+    const float* col = nullptr;
+    PPO_TRY(value_target(ro, target, &col));
+    for (int64_t i = 0; i < B; ++i) ARG_CHECK(sample_idx[i] >= 0 && sample_idx[i] < ro->len, "dataset index out of range (src/rollout_buffer.jl:105-106)");
+    PPO_TRY(train_reserve(critic, B * (ro->H / 32)));
+    DevBuf<int64_t> pos;
+    PPO_TRY(pos.alloc(B));
+    PPO_TRY(h2d(pos.p, sample_idx, (size_t)B));
+    hipLaunchKernelGGL(k_gather_index, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, g_stream, ro->index.p, pos.p, B,
+                       ro->len, critic->idx.p, critic->err.p);
+    HIP_TRY(hipGetLastError());
+    PPO_TRY(value_forward_backward_dev(critic, ro, critic->idx.p, B, B_global, col));
+    if (loss_out) {
+        float t = 0.0f;
+        PPO_TRY(d2h(&t, critic->grad.p + critic->np, 1));
+        *loss_out = t;
+    }
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    return PPO_OK;
+}
+
+// ppo_train's epoch loop for the critic (single rank): same permutation keying, slices and histories
+int32_t ppo_value_train(ppo_policy_t critic, ppo_adam_t opt, ppo_rollouts_t ro, int64_t batch_size, int32_t num_epochs,
+                        int32_t target, const int64_t* perm, uint64_t seed, double* mse_hist, double* lr_hist) {
+    ARG_CHECK(critic && opt && ro && opt->pol == critic, "value_train: null/mismatched argument");
+    const int64_t len = ro->len;
+    ARG_CHECK(num_epochs >= 0, "value_train: bad epochs");
+    ARG_CHECK(ro->H == 32 || ro->H == 128, "value_train: shape mismatch");
+    PPO_TRY(value_checks("value_train", critic, ro->F));
+    const float* col = nullptr;
+    PPO_TRY(value_target(ro, target, &col));
+    ARG_CHECK(batch_size >= 1 && batch_size <= len, "1 <= batch_size <= num_data (src/train.jl:88)");
+    const int64_t nb = (len + batch_size - 1) / batch_size;
+    PPO_TRY(train_reserve(critic, batch_size * (ro->H / 32)));
+    DevBuf<int32_t> order; DevBuf<int64_t> permd; DevBuf<float> hist;
+    PPO_TRY(order.alloc(len));
+    if (perm) PPO_TRY(permd.alloc(len));
+    PPO_TRY(hist.alloc((size_t)nb * 2));
+    std::vector<float> hh((size_t)nb * 2);
+    for (int32_t ep = 0; ep < num_epochs; ++ep) {
+        if (perm) {
+            PPO_TRY(h2d(permd.p, perm + (size_t)ep * len, (size_t)len));
+            hipLaunchKernelGGL(k_perm_index, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, g_stream, ro->index.p,
+                               permd.p, len, order.p, critic->err.p);
+            HIP_TRY(hipGetLastError());
+        } else {
+            PPO_TRY(launch_feistel_index(ro->index.p, len, seed, (uint32_t)opt->epochs_done, order.p));
+        }
+        for (int64_t b = 0; b < nb; ++b) {                                          // last batch may be short
+            const int64_t start = b * batch_size;
+            const int64_t B = std::min(batch_size, len - start);
+            const bool fused = ppo_knobs().fuse_reduce_adam != 0;
+            PPO_TRY(value_forward_backward_dev(critic, ro, order.p + start, B, B, col, fused ? opt : nullptr, hist.p + 2 * b));
+            if (!fused) PPO_TRY(launch_adam(opt, hist.p + 2 * b));
+        }
+        opt->epochs_done += 1;
+        PPO_TRY(d2h(hh.data(), hist.p, (size_t)nb * 2));
+        double sm = 0.0;
+        for (int64_t i = 0; i < nb; ++i) sm += hh[2 * i];
+        if (mse_hist) mse_hist[ep] = sm / (double)nb;                               // unweighted mean over batches
+        if (lr_hist) lr_hist[ep] = opt->lr();
+    }
+    int32_t f = 0;
+    PPO_TRY(d2h(&f, critic->err.p, 1));
+    if (f) { ppo_set_error("AssertionError (device flag): permutation / dataset index out of range"); return PPO_ERR_DEVICE_FLAG; }
+    return PPO_OK;
+}
+
 }  // extern "C"

@@ -188,7 +188,7 @@ struct ppo_rollouts_s {
     DevBuf<uint8_t> valid;     // [T][N]
     DevBuf<int32_t> index;     // [len] transition ids in dataset order
     DevBuf<float> full_probs;  // [T][N][A] optional
-    DevBuf<float> values;      // [T+1][N] host-supplied state values (ppo_rollouts_compute_gae)
+    DevBuf<float> values;      // [T+1][N] state values: host-supplied (ppo_rollouts_compute_gae) or a device critic's (ppo_rollouts_compute_values)
     DevBuf<float> adv;         // [T][N] GAE(gamma, lambda) advantages (PPO_ADV_GAE*)
     DevBuf<float> lam_ret;     // [T][N] lambda-returns adv + V
     int64_t adv_T = -1;        // T the adv column was computed for (-1: none)
@@ -289,10 +289,22 @@ struct TrainRoute { TrainFwd fwd; TrainBwd bwd; const char* err; };      // err:
 // dtype: PPO_DTYPE_*; HID: kernel width (128 / 256); H: rows per state (32 / 128); states: minibatch size
 TrainRoute train_route(int32_t dtype, int F, int HID, int L, int H, bool compact, int64_t states, const PpoKnobs& k);
 
+// The critic's training pass (ppo_value_train): its forward is always k_policy_fwd in a value-train mode -- the only forward
+// with one -- followed by the backward train_route picks for the shape and size; where that is the one-tile pass, whose
+// weight-gradient kernel only runs from inside it, the three-product Small backward.  bwd == None: err says why.
+struct ValueRoute { TrainBwd bwd; const char* err; };
+ValueRoute value_route(int32_t dtype, int F, int HID, int L, int H, bool compact, int64_t states, const PpoKnobs& k);
+
 // train-pass launchers: each launches what train_route chose and checks nothing else
 int32_t launch_policy_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B,
                                 int64_t B_global, double eps, double entropy_weight, const float* adv_col, TrainFwd form);
 int32_t launch_policy_bwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B);
+// critic (ppo_policy_fwd.hip value modes): state values of B stored states (rows, or snapshots when cstate_dev is given), and
+// the value-train forward of a minibatch against target_col (indexed by transition id)
+int32_t launch_value_predict(ppo_policy_s* p, const int8_t* states_dev, const int8_t* cstate_dev, const uint32_t* active_dev,
+                             const int8_t* tmpl_dev, int32_t V, int64_t B, int32_t H, float* values_dev);
+int32_t launch_value_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
+                               const float* target_col);
 // the same fused backward with its row contractions (dW2, dW1) as split-fp32 products on the bf16 matrix pipe
 // (ppo_policy_bwd_x6.hip)
 int32_t launch_policy_bwd_x6(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B);

@@ -50,6 +50,15 @@ static __device__ __forceinline__ void act_store_nt(float4* p, float4 v) {
 #ifndef PPO_FWD_PF_SMALL_TRAIN
 #define PPO_FWD_PF_SMALL_TRAIN PPO_FWD_PF   // their train-forward ring depth
 #endif
+// k_policy_fwd's MODE: 0 probabilities, 1 one rollout step, 2 train forward (rows gathered through idx), 3 persistent
+// rollout, 4 train forward from compact env snapshots (through idx); and the critic's (value_tail instead of policy_tail):
+// 5 value-predict on rows [B][H][F], 6 value-train (= 2), 7 value-predict on snapshots [B][2V], 8 value-train (= 4)
+constexpr bool fwd_mode_value(int m) { return m >= 5 && m <= 8; }
+constexpr bool fwd_mode_train(int m) { return m == 2 || m == 4 || m == 6 || m == 8; }    // saves activations, writes dY
+constexpr bool fwd_mode_gather(int m) { return m == 2 || m == 6; }                       // expanded rows through idx
+constexpr bool fwd_mode_snap(int m) { return m == 4 || m == 7 || m == 8; }               // one env snapshot per state in LDS
+constexpr bool fwd_mode_snap_idx(int m) { return m == 4 || m == 8; }                     // ... fetched through idx, rows -> xs_out
+
 template <int F, int HID>
 struct FwdCfg { static constexpr int WPS = (HID >= 256 || F > 128) ? 1 : PPO_FWD_WPS_SMALL; };
 
@@ -81,9 +90,15 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
     // two waves per SIMD (HID = 128, F = 72): 4 groups cover the L2 latency; the train forward, whose activation stores
     // sit in the same vmcnt queue, wants the deep ring here too (0.072 -> 0.069 ms), the rollout does not (8.3 -> 8.7 ms)
     constexpr int PFT = (PPO_FWD_PF_SMALL_TRAIN < HID / 8) ? PPO_FWD_PF_SMALL_TRAIN : HID / 8;
-    constexpr int PF = (FwdCfg<F, HID>::WPS == 1) ? PFW : ((MODE == 2 || MODE == 4) ? PFT : 4);   // weight-fragment groups kept in flight per wave
-    constexpr bool TRAIN = (MODE == 2 || MODE == 4);    // train forward: saves activations, loss tail
-    constexpr bool OBS = (MODE == 3 || MODE == 4);      // the state rows are re-derived from an env snapshot in LDS
+    constexpr bool TRAIN = fwd_mode_train(MODE);        // train forward: saves activations, loss tail
+    constexpr bool VALUE = fwd_mode_value(MODE);        // critic: value_tail
+    constexpr bool GATHER = fwd_mode_gather(MODE);
+    constexpr bool SNAP = fwd_mode_snap(MODE), SNAPX = fwd_mode_snap_idx(MODE);
+    // (value-train from snapshots keeps half the train ring at two waves per SIMD: with 16 groups next to the row
+    // re-derivation it does not fit the 256 registers)
+    constexpr int PFV = (PFT < 8) ? PFT : 8;
+    constexpr int PF = (FwdCfg<F, HID>::WPS == 1) ? PFW : (TRAIN ? ((VALUE && SNAP) ? PFV : PFT) : 4);   // weight-fragment groups kept in flight per wave
+    constexpr bool OBS = (MODE == 3 || SNAP);           // the state rows are re-derived from an env snapshot in LDS
     constexpr int TMODE = TRAIN ? 2 : MODE;             // policy_tail's mode
     static_assert(F % 8 == 0 && HID % 32 == 0, "shape");
     static_assert(PF * 64 * 4 <= PPO_PACK_PAD, "the ring reads PF groups past the end of a packed weight stream: padding must cover it");
@@ -111,7 +126,7 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
                                                                   // MODE 3 / 4 compute the rows themselves (no fetch)
     uint32_t xw[XW];
     auto fetch_rows = [&](int64_t state, int ts) {
-        const int64_t sidn = (MODE == 2) ? (int64_t)a.idx[state] : state;
+        const int64_t sidn = GATHER ? (int64_t)a.idx[state] : state;
         const uint32_t* xr = reinterpret_cast<const uint32_t*>(a.states + ((size_t)sidn * TPS + ts) * 32 * F +
                                                                (size_t)j * F + (size_t)h * XB);
 #pragma unroll
@@ -166,27 +181,30 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
     uint32_t cs_next = 0u, act_next = 0u;
     int32_t sid_next = 0;
     auto fetch_snapshot = [&](int64_t state) {
-        sid_next = a.idx[state];
+        sid_next = SNAPX ? a.idx[state] : (int32_t)state;
         act_next = a.active[sid_next];
         const int nd = a.envV >> 1;                              // dwords of one snapshot
         cs_next = (lane < nd) ? reinterpret_cast<const uint32_t*>(a.cstate)[(size_t)sid_next * nd + lane] : 0u;
     };
-    if (MODE == 4 && wave < a.B) fetch_snapshot(wave);
+    if (SNAP && wave < a.B) fetch_snapshot(wave);
     const int64_t t_steps = (MODE == 3) ? a.T : 1;
     for (int64_t tt = 0; tt < t_steps; ++tt) {
     int slot = 0;
     for (int64_t state = wave; state < a.B; state += nwaves, ++slot) {
-        const int64_t sid = (MODE == 2) ? (int64_t)a.idx[state] : ((MODE == 4) ? (int64_t)sid_next : state);
+        const int64_t sid = GATHER ? (int64_t)a.idx[state] : (SNAP ? (int64_t)sid_next : state);
         EnvRefLds er = {};
         if (MODE == 3) er = slot_ref(slot);
-        if (MODE == 4) {
+        if (SNAP) {
             er = slot_ref(0);
             if (lane < (a.envV >> 1)) reinterpret_cast<PPO_LDS uint32_t*>(er.sc)[lane] = cs_next;
             if (lane == 0) *er.active = act_next;
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // wave-private slot: program order + in-order LDS suffice
         }
-        const uint32_t act = (MODE == 3) ? *er.active : ((MODE == 4) ? act_next : a.active[sid]);
-        if (MODE == 4) fetch_snapshot(state + nwaves < a.B ? state + nwaves : state);      // lands under this state's MFMAs
+        const uint32_t act = (MODE == 3) ? *er.active : (SNAP ? act_next : a.active[sid]);
+        // value-train: the target is fetched here, ahead of the activation stores it would otherwise queue behind (vmcnt)
+        float vtarget = 0.0f;
+        if (VALUE && TRAIN) vtarget = a.vtarget[sid];
+        if (SNAP) fetch_snapshot(state + nwaves < a.B ? state + nwaves : state);      // lands under this state's MFMAs
         const uint32_t tick_val = (MODE == 3) ? *er.tick : ((MODE == 1) ? a.tick[state] : 0u);
         const int64_t out_index = (MODE == 3) ? tt * a.B + state : state;
         float l[TPS][4];
@@ -218,9 +236,9 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
                 env_observe_lane(er, tid, 32 * ts + j, h, ob);
 #pragma unroll
                 for (int k = 0; k < XW; ++k) xw[k] = ob[k < 9 ? k : 0];
-                int8_t* const rows_out = (MODE == 4) ? a.xs_out : a.states_out;
+                int8_t* const rows_out = SNAPX ? a.xs_out : ((MODE == 3) ? a.states_out : nullptr);
                 if (rows_out) {                                  // wave-uniform
-                    uint32_t* so = reinterpret_cast<uint32_t*>(rows_out + ((size_t)(MODE == 4 ? state : out_index) * TPS + ts) * 32 * F +
+                    uint32_t* so = reinterpret_cast<uint32_t*>(rows_out + ((size_t)(SNAPX ? state : out_index) * TPS + ts) * 32 * F +
                                                                (size_t)j * F + (size_t)h * XB);
 #pragma unroll
                     for (int k = 0; k < XW; ++k) so[k] = xw[k];
@@ -429,7 +447,9 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
         }
 
         FSTAMP(4);
-        const int sampled = policy_tail<TMODE, TPS, false>(a, state, sid, act, l, lane, j, h, tick_val, out_index);
+        int sampled = 0;
+        if constexpr (VALUE) value_tail<TRAIN ? 1 : 0, TPS>(a, state, act, l, lane, j, h, out_index, vtarget);
+        else sampled = policy_tail<TMODE, TPS, false>(a, state, sid, act, l, lane, j, h, tick_val, out_index);
         if (MODE == 3) {
             // update!: the observed mask, then step!(env, a), reward, is_terminal (src/collect_rollouts.jl:9-14) and the
             // reset! before the next episode (src/rollout_buffer.jl:75) -- one lane, on the LDS slot
@@ -494,21 +514,21 @@ __global__ void k_categorical(const float* __restrict__ probs, const float* __re
     err[b] = !(p[i] > 0.0f);
 }
 
-// num_hidden_layers != 2: the layer-looped instantiations (DEEP = 1).  Dynamic LDS = [MODE 4: one env-snapshot slot per
+// num_hidden_layers != 2: the layer-looped instantiations (DEEP = 1).  Dynamic LDS = [MODE 4 / 7 / 8: one env-snapshot slot per
 // wave][park: 4 waves x HID/32 tiles x 4 KiB].
 template <int MODE>
 static int32_t dispatch_fwd_deep(ppo_policy_s* p, const FwdArgs& args, int64_t B, int tps) {
     const int64_t need = (B + 3) / 4;
     FwdArgs a = args;
     a.nl2 = p->L - 1;
-    const size_t snap = (MODE == 4) ? (((size_t)4 * (2 * a.envV + 32) + 15) & ~(size_t)15) : 0;
+    const size_t snap = fwd_mode_snap(MODE) ? (((size_t)4 * (2 * a.envV + 32) + 15) & ~(size_t)15) : 0;
     a.park_off = (uint32_t)snap;
 #define LAUNCHD(FF, HH, TT)                                                                              \
     do {                                                                                                 \
         const int64_t cap = 256 * FwdCfg<FF, HH>::WPS;                                                   \
         const unsigned grid = (unsigned)(need < cap ? need : cap);                                       \
         a.wg_sync = 0;                                                                                   \
-        if constexpr (MODE == 4 && FF != 72) {                                                           \
+        if constexpr (fwd_mode_snap(MODE) && FF != 72) {                                                 \
             ppo_set_error("compact rollouts need the built-in env's F = 72"); return PPO_ERR_UNSUPPORTED; \
         } else {                                                                                         \
             const size_t dlds = snap + (size_t)4 * (HH / 32) * 4096;                                     \
@@ -543,10 +563,10 @@ static int32_t dispatch_fwd(ppo_policy_s* p, const FwdArgs& args, int64_t B, int
         const int64_t cap = 256 * FwdCfg<FF, HH>::WPS;                                                   \
         const unsigned grid = (unsigned)(need < cap ? need : cap);                                       \
         const_cast<FwdArgs&>(args).wg_sync = (B % ((int64_t)grid * 4) == 0) ? 1 : 0;                     \
-        if constexpr (MODE == 4 && FF != 72) {                                                             \
+        if constexpr (fwd_mode_snap(MODE) && FF != 72) {                                                   \
             ppo_set_error("compact rollouts need the built-in env's F = 72"); return PPO_ERR_UNSUPPORTED;    \
         } else {                                                                                             \
-            const size_t dlds = (MODE == 4) ? (size_t)4 * (2 * args.envV + 32) : 0;   /* one snapshot slot per wave */ \
+            const size_t dlds = fwd_mode_snap(MODE) ? (size_t)4 * (2 * args.envV + 32) : 0;   /* one snapshot slot per wave */ \
             hipLaunchKernelGGL((k_policy_fwd<FF, HH, MODE, TT>), dim3(grid), dim3(256), dlds, ppo_stream(), args); \
         }                                                                                                    \
     } while (0)
@@ -687,6 +707,39 @@ int32_t launch_policy_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32
     case TrainFwd::Fwd: return ro->compact ? dispatch_fwd<4>(p, a, B, ro->H / 32) : dispatch_fwd<2>(p, a, B, ro->H / 32);
     default: return launch_policy_train_fwd_x6(p, a, B, form, ro->compact);               // ppo_policy_fwd_x6.hip
     }
+}
+
+// ---- critic (value modes 5 .. 8): only this fp32-MFMA forward has them
+// values_dev[b] = V(state b) for B states in storage order: observation rows [B][H][F] (cstate_dev == nullptr), or env
+// snapshots [B][2V] with the buffer's template (compact rollouts; F = 72)
+int32_t launch_value_predict(ppo_policy_s* p, const int8_t* states_dev, const int8_t* cstate_dev, const uint32_t* active_dev,
+                             const int8_t* tmpl_dev, int32_t V, int64_t B, int32_t H, float* values_dev) {
+    if (B <= 0) return PPO_OK;
+    FwdArgs a = {};
+    fill_weights(p, a);
+    a.states = states_dev; a.active = active_dev; a.B = B; a.values_out = values_dev;
+    ProfScope ps("k_value_fwd_predict");
+    if (!cstate_dev) return dispatch_fwd<5>(p, a, B, H / 32);
+    a.states = nullptr; a.cstate = cstate_dev; a.env_tmpl = tmpl_dev; a.envV = V; a.envQ = V / 4; a.env_slots = 1;
+    return dispatch_fwd<7>(p, a, B, H / 32);
+}
+
+// value-train forward of a minibatch: saves the activations like the policy's train forward, leaves dL/dy of
+// Flux.mse(V, target_col[idx]) in p->dY and the squared errors in p->loss_terms
+int32_t launch_value_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
+                               const float* target_col) {
+    FwdArgs a = {};
+    fill_weights(p, a);
+    a.states = ro->states.p; a.active = ro->active.p; a.idx = idx_dev; a.B = B;
+    a.act1 = (float4*)p->act1.p; a.act2 = (float4*)p->act2.p; a.dY = (float4*)p->dY.p; a.loss_terms = p->loss_terms.p;
+    for (int l = 0; l < 2; ++l)
+        a.act_mid[l] = (p->L > 2 && l < p->L - 2) ? (float4*)p->actm.p + (size_t)l * p->cap_tiles * (p->HID / 32) * 256 : nullptr;
+    a.vtarget = target_col; a.inv_B = (float)(1.0 / (double)B_global);
+    ProfScope ps("k_value_fwd_train");
+    if (!ro->compact) return dispatch_fwd<6>(p, a, B, ro->H / 32);
+    a.states = nullptr; a.cstate = ro->cstate.p; a.xs_out = p->xs.p;
+    a.env_tmpl = ro->tmpl.p; a.envV = ro->V; a.envQ = ro->V / 4; a.env_slots = 1;
+    return dispatch_fwd<8>(p, a, B, ro->H / 32);
 }
 
 int32_t launch_categorical(const float* probs, const float* u, int64_t B, int64_t A, int32_t* actions, float* psel,

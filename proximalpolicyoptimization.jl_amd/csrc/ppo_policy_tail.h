@@ -44,6 +44,9 @@ struct FwdArgs {
     int32_t nl2; float4* act_mid[2]; uint32_t park_off;
     // bf16 compute mode (ppo_policy_bf16.hip): bf16 fragment streams and bf16 saved activations
     const uint4* w1b; const uint4* w2b; const uint4* w3c; uint4* act1b; uint4* act2b;
+    // critic (k_policy_fwd value modes, value_tail): state values out, indexed like the states (predict); regression target per
+    // transition id (train).  Appended last: the offsets of every field above are what the other kernels were built with
+    float* values_out; const float* vtarget;
 };
 
 // value of lane (lane ^ OFF), OFF < 32.  Same lane mapping as __shfl_xor (which hipcc lowers to ds_bpermute_b32: an
@@ -237,4 +240,43 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
         if (lane == 0) { a.loss_terms[state * 2] = minval; a.loss_terms[state * 2 + 1] = (double)(-hl); }
     }
     return sampled;
+}
+
+// ---- critic: the same MLP read as a state value.  V(s) = mean of the 4 outputs of every half-edge row of an ACTIVE quad
+// (the rows policy_tail's mask keeps), 0 for a state without one; loss = Flux.mse(V, target) over the global minibatch.
+// VMODE 0 (predict): values_out[out_index] = V.
+// VMODE 1 (train):   dY = dL/dy = 2 (V - target) / (B_global * n) on the n = 16 * active-quads outputs of active rows, exactly
+//                    0.0f on the others; loss_terms[state] = (-(V - target)^2, 0) -- the slab reduction's -(sum)/B_global
+//                    then leaves the mse where the policy's ppo loss goes.  target: the caller's early fetch (TailPre rule).
+// A handful of adds, one division and the DPP butterfly: no exp / log, so the tail is short serial time for the workgroup.
+template <int VMODE, int TPS>
+__device__ __forceinline__ void value_tail(const FwdArgs& a, const int64_t state, const uint32_t act, const float (&l)[TPS][4],
+                                           const int lane, const int j, const int h, const int64_t out_index, const float target) {
+    bool on[TPS];
+    float s = 0.0f;
+#pragma unroll
+    for (int ts = 0; ts < TPS; ++ts) {
+        on[ts] = (act >> (8 * ts + (j >> 2))) & 1u;
+        const float st = on[ts] ? ((l[ts][0] + l[ts][1]) + l[ts][2]) + l[ts][3] : 0.0f;
+        s = (ts == 0) ? st : s + st;                       // tile partials in tile order, then the butterfly
+    }
+    s = wave32_sum(s);
+    const uint32_t quads = (TPS == 4) ? act : (act & ((1u << (8 * TPS)) - 1u));
+    const int nq = __builtin_popcount(quads);              // wave-uniform
+    const float n = (float)(16 * nq);                      // 4 rows per quad x 4 outputs per row
+    const float v = nq ? s / n : 0.0f;
+    if (VMODE == 0) {
+        if (lane == 0) a.values_out[out_index] = v;
+    } else {
+        const float d = v - target;
+        const float g = nq ? ((2.0f * d) * a.inv_B) / n : 0.0f;
+        if (h == 0) {
+#pragma unroll
+            for (int ts = 0; ts < TPS; ++ts) {
+                const float gi = on[ts] ? g : 0.0f;
+                a.dY[((size_t)state * TPS + ts) * 32 + j] = make_float4(gi, gi, gi, gi);
+            }
+        }
+        if (lane == 0) { a.loss_terms[state * 2] = -((double)d * (double)d); a.loss_terms[state * 2 + 1] = 0.0; }
+    }
 }

@@ -77,6 +77,15 @@ TrainRoute train_route(int32_t dtype, int F, int HID, int L, int H, bool compact
     return r;
 }
 
+ValueRoute value_route(int32_t dtype, int F, int HID, int L, int H, bool compact, int64_t states, const PpoKnobs& k) {
+    const int tps = H / 32;
+    if (dtype != PPO_DTYPE_F32) return {TrainBwd::None, "a bf16-dtype critic is not supported: the value modes exist in the fp32-MFMA forward only"};
+    if (F != 72 && tps != 1) return {TrainBwd::None, "unsupported policy/state shape (F,HID,H) for the gfx950 kernels"};
+    if (F != 72 && compact) return {TrainBwd::None, "compact rollouts need the built-in env's F = 72"};
+    const TrainBwd b = train_route(dtype, F, HID, L, H, compact, states, k).bwd;
+    return {b == TrainBwd::Wgrad ? TrainBwd::Small : b, nullptr};
+}
+
 // diagnostic for the tests (not part of include/ppo_hip.h): the kernels train_route picks for a shape under the current
 // knobs, named as a kernel trace lists them demangled (first kernel of each half).  No HIP call.
 extern "C" int32_t ppo_debug_train_route(int32_t dtype, int32_t F, int32_t hid, int32_t L, int32_t H, int32_t compact,
@@ -106,5 +115,23 @@ extern "C" int32_t ppo_debug_train_route(int32_t dtype, int32_t F, int32_t hid, 
     case TrainBwd::Bf16: snprintf(bwd, cap, "k_policy_bwd_bf16<72,%d>", hid); break;
     }
     if (r.fwd == TrainFwd::None) { ppo_set_error(r.err); return PPO_ERR_UNSUPPORTED; }
+    return PPO_OK;
+}
+
+// the same for the critic's training pass (value_route): fwd is k_policy_fwd in value-train mode 6 (rows) or 8 (snapshots)
+extern "C" int32_t ppo_debug_value_route(int32_t dtype, int32_t F, int32_t hid, int32_t L, int32_t H, int32_t compact,
+                                         int64_t states, char* fwd, char* bwd, int64_t cap) {
+    ARG_CHECK((dtype == PPO_DTYPE_F32 || dtype == PPO_DTYPE_BF16) && (F == 72 || F == 216) && (hid == 128 || hid == 256) && L >= 1 && L <= 4 && (H == 32 || H == 128) && states >= 1,
+              "ppo_debug_value_route: shape");
+    ARG_CHECK(fwd && bwd && cap >= 64, "ppo_debug_value_route: output buffers");
+    const ValueRoute r = value_route(dtype, F, hid, L, H, compact != 0, states, ppo_knobs());
+    if (r.bwd == TrainBwd::None) { snprintf(fwd, cap, "none"); snprintf(bwd, cap, "none"); ppo_set_error(r.err); return PPO_ERR_UNSUPPORTED; }
+    snprintf(fwd, cap, "k_policy_fwd<%d,%d,%d,%d,%d>", F, hid, compact ? 8 : 6, H / 32, L != 2 ? 1 : 0);
+    switch (r.bwd) {
+    case TrainBwd::Small: snprintf(bwd, cap, "k_policy_bwd_data%s<%d,%d>", L == 2 ? "" : "_deep", F, hid); break;
+    case TrainBwd::X6: snprintf(bwd, cap, "k_policy_bwd_x6<72,%d>", hid); break;
+    case TrainBwd::Fused: snprintf(bwd, cap, "k_policy_bwd<%d,%d>", F, hid); break;
+    default: snprintf(bwd, cap, "none"); break;
+    }
     return PPO_OK;
 }
