@@ -53,6 +53,8 @@ def main():
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32")
     ap.add_argument("--critic", action="store_true", help="train a device critic of the policy's shape and use its GAE(0.95) advantage")
+    ap.add_argument("--target-kl", type=float, default=None,
+                    help="end an iteration's epochs after the first one whose approx_kl exceeds this (inf: report the statistics only)")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "best_policy.bson"))
     args = ap.parse_args()
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
@@ -66,12 +68,16 @@ def main():
     policy = PPO.HipPolicy(72, 128, 2, 4, seed=0, dtype=args.dtype)
     optimizer = PPO.Optimiser(PPO.Adam(3e-4))                # an iterable composite, like Flux.Optimiser(Adam(...))
     evaluator = SaveBestModel(args.out)
+    policy.target_kl = args.target_kl                        # None = off: the loss dict is then the reference's three histories
     extra = {}
     if args.critic:                                          # fp32 critic; its own optimiser (keyword-only arguments of ppo_iterate_)
         extra = dict(critic=PPO.HipCritic(72, 128, 2, seed=1), critic_optimizer=PPO.Optimiser(PPO.Adam(1e-3)), gae_lambda=0.95)
     PPO.ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size, args.iterations, evaluator,
                      epochs_per_iteration, discount, epsilon, entropy_weight, verbose=False, **extra)
     evaluator(policy, env, optimizer)
+    for key in ("approx_kl", "clip_fraction", "explained_variance"):   # present when a target_kl is set
+        if key in evaluator.loss:
+            print("%s (last %d): %s" % (key, min(4, len(evaluator.loss[key])), " ".join("%.4f" % x for x in evaluator.loss[key][-4:])))
     best = PPO.load_policy(args.out)                          # BSON.@load path policy
     print("best average return %.3f (first %.3f); checkpoint holds Policy(%d, %d, %d, %d)"
           % (evaluator.best_return, evaluator.mean_returns[0], best.in_channels, best.hidden_channels,

@@ -347,6 +347,34 @@ int32_t ppo_train(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, double ep
                   int32_t rank, int32_t world, ppo_allreduce_fn allreduce, void* allreduce_ctx, double* ppo_hist,
                   double* entropy_hist, double* lr_hist);
 
+/* ---------------------------------------------------------------- update statistics and target-KL early stopping
+ * No reference op: the reference reports the two losses and the learning rate.  While a target_kl is set on the policy
+ * handle (below; +inf = record only), every train forward stores the probability ratio r = p_new(a|s) / p_old(a|s) of
+ * each state (the quotient its surrogate forms); ppo_train reduces an epoch's ratios once, in fp64 and in a fixed order,
+ * and keeps per epoch
+ *     approx_kl     = mean((r - 1) - log r)      (the estimator Stable-Baselines3 and CleanRL report under that name)
+ *     old_approx_kl = mean(-log r)
+ *     clip_fraction = mean(|r - 1| > epsilon)
+ * Each transition enters with the parameters its own minibatch saw, i.e. before that minibatch's update, like there.
+ * Read them with ppo_policy_last_train_stats.  With target_kl == 0 (off, the default) nothing is stored or reduced -- the
+ * store costs the train forward a measurable 0.2 % -- and the three statistics read NaN; epochs_run is kept either way.
+ * target_kl (a property of the policy handle): when > 0, ppo_train ends after the first epoch whose
+ * approx_kl is not <= target_kl (so Inf and NaN end it); that epoch's updates stay applied, no epoch is cut short.  The
+ * epoch count of the optimiser (permutation key), the ExpDecay / InvDecay counters and the history arrays advance for
+ * the epochs that ran only; history entries behind them are left untouched.  +inf records without ever stopping.
+ * Data parallel: with world > 1 and target_kl > 0 the four sums behind the statistics are exchanged through the hook once
+ * per epoch (one more call, 12 * world floats), so every rank holds the same GLOBAL statistics and takes the same
+ * decision; target_kl must then be the same on every rank, like num_epochs.  With target_kl == 0 no call is added. */
+/* no reference op.  0 off; > 0 or +inf on; < 0 / NaN: PPO_ERR_ARG */
+int32_t ppo_policy_set_target_kl(ppo_policy_t pol, double target_kl);
+/* no reference op */
+int32_t ppo_policy_get_target_kl(ppo_policy_t pol, double* target_kl);
+/* no reference op.  Of the latest ppo_train on this policy: epochs_run, stopped_early (1: fewer epochs ran than were
+ * asked for), and the first min(cap, epochs_run) entries of each per-epoch array (NaN for a call that ran with
+ * target_kl == 0); every output may be NULL */
+int32_t ppo_policy_last_train_stats(ppo_policy_t pol, int32_t cap, int32_t* epochs_run, int32_t* stopped_early,
+                                    double* approx_kl, double* old_approx_kl, double* clip_fraction);
+
 /* ---------------------------------------------------------------- critic (device state values)
  * A critic is an ordinary ppo_policy_t made by ppo_policy_create(F, hidden, L, 4) and read as a state value: the mean of
  * the 4 outputs of every half-edge row that belongs to an ACTIVE quad,
@@ -375,6 +403,13 @@ int32_t ppo_value_forward_backward(ppo_policy_t critic, ppo_rollouts_t ro, const
  * unweighted mean of the per-batch losses, lr_hist from the chain.  opt: any optimiser made for `critic`. */
 int32_t ppo_value_train(ppo_policy_t critic, ppo_adam_t opt, ppo_rollouts_t ro, int64_t batch_size, int32_t num_epochs,
                         int32_t target, const int64_t* perm, uint64_t seed, double* mse_hist, double* lr_hist);
+/* no reference op.  The sums behind the critic's explained variance, over the valid transitions of the buffer, with V =
+ * rows 0 .. T-1 of the buffer's device values (ppo_rollouts_compute_values / _gae / _gae_critic first: PPO_ERR_ARG
+ * otherwise) and t = the PPO_VTARGET_* column: sums5 = n, sum x, sum x^2, sum y, sum y^2 in fp64 and a fixed order, where
+ * x = t - t0 and y = (t - V) - (t0 - V0) are taken relative to the first transition of the dataset (ppo_rollouts_get_index)
+ * so that a variance is not a difference of large numbers.  Explained variance = 1 - Var(y) / Var(x) with
+ * Var(z) = sum z^2 / n - (sum z / n)^2, NaN when Var(x) == 0. */
+int32_t ppo_rollouts_value_moments(ppo_rollouts_t ro, int32_t target, double* sums5);
 
 /* Native hook (the default of bench.py and DataParallel): the same all-reduce as ONE RCCL call made by the library
  * itself on the engine's stream -- no host-language callback per optimiser step.  RCCL is resolved with dlopen at first

@@ -291,10 +291,33 @@ function PPO.ppo_train!(p::HipPolicy, optimizer, r::HipRollouts, epsilon, batch_
                    hook, C_NULL, ph, eh, lh)
     opt_done!(optimizer)                               # lr history == get_optimizer_learning_rate(optimizer) afterwards
     check(status)
-    for e in 1:num_epochs
+    n = last_train_stats(p).epochs_run                 # fewer than num_epochs when set_target_kl! ended the call early
+    for e in 1:n
         @printf "EPOCH : %d \t PPO LOSS : %1.4f\t ENTROPY LOSS : %1.4f \t LR : %1.1e\n" e ph[e] eh[e] lh[e]
     end
-    ph, eh, lh
+    ph[1:n], eh[1:n], lh[1:n]
+end
+# ---- update statistics (include/ppo_hip.h "update statistics"; no reference op): approx_kl = mean((r - 1) - log r),
+# old_approx_kl = mean(-log r) and clip_fraction = mean(|r - 1| > epsilon) of every epoch of the latest ppo_train!, and the
+# target-KL stop: ppo_train! ends after the first epoch whose approx_kl exceeds target_kl (nothing / 0 = off, Inf = record only)
+function set_target_kl!(p::HipPolicy, target_kl)
+    check(ccall((:ppo_policy_set_target_kl, LIB), Int32, (Ptr{Cvoid}, Float64), p.h, target_kl === nothing ? 0.0 : Float64(target_kl)))
+end
+function target_kl(p::HipPolicy)
+    t = Ref{Float64}()
+    check(ccall((:ppo_policy_get_target_kl, LIB), Int32, (Ptr{Cvoid}, Ref{Float64}), p.h, t))
+    t[] == 0 ? nothing : t[]
+end
+function last_train_stats(p::HipPolicy)
+    n, stopped = Ref{Int32}(), Ref{Int32}()
+    check(ccall((:ppo_policy_last_train_stats, LIB), Int32,
+                (Ptr{Cvoid}, Int32, Ref{Int32}, Ref{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                p.h, Int32(0), n, stopped, C_NULL, C_NULL, C_NULL))
+    kl, okl, cf = zeros(n[]), zeros(n[]), zeros(n[])
+    check(ccall((:ppo_policy_last_train_stats, LIB), Int32,
+                (Ptr{Cvoid}, Int32, Ref{Int32}, Ref{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                p.h, n[], n, stopped, kl, okl, cf))
+    (epochs_run = Int(n[]), stopped_early = stopped[] != 0, approx_kl = kl, old_approx_kl = okl, clip_fraction = cf)
 end
 # ---- device critic: a HipPolicy(F, hidden, L, 4) read as a state value (mean of the outputs of the active quads' rows),
 # trained with Flux.mse; its state values feed GAE without leaving the device (include/ppo_hip.h "critic")
@@ -330,6 +353,15 @@ function value_train!(c::HipPolicy, optimizer, r::HipRollouts, batch_size, num_e
     opt_done!(optimizer)
     check(status)
     mh, lh
+end
+
+# 1 - Var(t - V) / Var(t) over the valid transitions, V = the values compute_values! / compute_gae_critic! left on the device
+function explained_variance(r::HipRollouts; target = :lambda_returns)
+    s = zeros(5)
+    check(ccall((:ppo_rollouts_value_moments, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}), r.h, VTARGET[target], s))
+    var_t = s[3] / s[1] - (s[2] / s[1])^2
+    var_d = s[5] / s[1] - (s[4] / s[1])^2
+    var_t == 0 ? NaN : 1 - var_d / var_t
 end
 
 # ppo_iterate!(policy, env, optimizer, ...) (src/train.jl:210-249) then works unchanged once

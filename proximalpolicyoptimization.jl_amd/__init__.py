@@ -57,6 +57,7 @@ __all__ = [
     "save_policy", "load_policy", "forward_backward",
     "HipCritic", "state_values", "batch_state_values", "compute_values_", "compute_gae_critic_", "value_forward_backward",
     "value_train_", "pooled_state_value", "value_loss",
+    "kl_stats", "explained_variance_", "explained_variance_from_sums",
 ]
 
 
@@ -362,6 +363,31 @@ class HipPolicy:
         out = np.empty(self.num_params, np.float32)
         call("ppo_policy_get_grad", self._h, _p(out, _lib.c_f32p))
         return out
+
+    @property
+    def target_kl(self):
+        """None (off, the default), or the approx_kl above which ppo_train_ ends after the epoch that reached it
+        (float("inf"): record the statistics, never stop).  The statistics are collected while a target is set only (the
+        extra store costs the train forward 0.2 %); with a target set, ppo_iterate_ reports them."""
+        t = C.c_double(0)
+        call("ppo_policy_get_target_kl", self._h, C.byref(t))
+        return None if t.value == 0.0 else t.value
+
+    @target_kl.setter
+    def target_kl(self, value):
+        call("ppo_policy_set_target_kl", self._h, 0.0 if value is None else float(value))
+
+    def last_train_stats(self):
+        """Of the latest ppo_train_ on this policy: {"epochs_run", "stopped_early", "approx_kl", "old_approx_kl",
+        "clip_fraction"}, the last three one entry per epoch that ran (kl_stats of that epoch's probability ratios; NaN
+        when the call ran with target_kl = None)."""
+        n, stopped = C.c_int32(0), C.c_int32(0)
+        call("ppo_policy_last_train_stats", self._h, 0, C.byref(n), C.byref(stopped), None, None, None)
+        kl, okl, cf = (np.zeros(n.value, np.float64) for _ in range(3))
+        call("ppo_policy_last_train_stats", self._h, n.value, C.byref(n), C.byref(stopped), _p(kl, _lib.c_f64p),
+             _p(okl, _lib.c_f64p), _p(cf, _lib.c_f64p))
+        return {"epochs_run": n.value, "stopped_early": bool(stopped.value), "approx_kl": list(kl),
+                "old_approx_kl": list(okl), "clip_fraction": list(cf)}
 
     def grad_buffer_dev(self):
         ptr, n = C.c_void_p(), C.c_int64(0)
@@ -1029,6 +1055,33 @@ def compute_gae_critic_(rollouts, env, critic, gamma, lam, fetch=True):
     return (adv, ret) if fetch else None
 
 
+def kl_stats(ratio, epsilon):
+    """What ppo_train_ keeps per epoch, from probability ratios r = p_new(a|s) / p_old(a|s) in plain numpy float64:
+    {"approx_kl": mean((r - 1) - log r), "old_approx_kl": mean(-log r), "clip_fraction": mean(|r - 1| > epsilon)}.
+    For users of the generic path, and the statement the device reduction is tested against."""
+    r = np.asarray(ratio).astype(np.float64).reshape(-1)
+    lg = np.log(r)
+    return {"approx_kl": float(np.sum((r - 1.0) - lg) / r.size), "old_approx_kl": float(np.sum(-lg) / r.size),
+            "clip_fraction": float(np.count_nonzero(np.abs(r - 1.0) > float(epsilon)) / r.size)}
+
+
+def explained_variance_from_sums(sums5):
+    """1 - Var(t - V) / Var(t) from (n, sum x, sum x^2, sum y, sum y^2), x and y being t and t - V up to a constant shift
+    each (ppo_rollouts_value_moments).  NaN when Var(t) == 0."""
+    n, sx, sxx, sy, syy = (float(s) for s in sums5)
+    var_t = sxx / n - (sx / n) ** 2
+    var_d = syy / n - (sy / n) ** 2
+    return float("nan") if var_t == 0.0 else 1.0 - var_d / var_t
+
+
+def explained_variance_(rollouts, target="lambda_returns"):
+    """The critic's explained variance over the valid transitions of the buffer, reduced on the device: V = the state
+    values compute_values_ / compute_gae_critic_ / compute_gae_ left there, target as in value_train_."""
+    s = np.zeros(5, np.float64)
+    call("ppo_rollouts_value_moments", rollouts._h, _value_target(target), _p(s, _lib.c_f64p))
+    return explained_variance_from_sums(s)
+
+
 class BufferDataset:
     """src/rollout_buffer.jl:95-147.  Non-owning view; indices are 1-based like the reference."""
 
@@ -1194,8 +1247,11 @@ def ppo_train_(policy, optimizer, dataset, epsilon, batch_size, num_epochs, entr
              _p(ph, _lib.c_f64p), _p(eh, _lib.c_f64p), _p(lh, _lib.c_f64p))
     finally:
         optimizer._pull()                                  # decayed ExpDecay etas: get_optimizer_learning_rate == lr_history
+    ran = C.c_int32(0)                                     # fewer than num_epochs when policy.target_kl ended the call
+    call("ppo_policy_last_train_stats", policy._h, 0, C.byref(ran), None, None, None, None)
+    ph, eh, lh = ph[:ran.value], eh[:ran.value], lh[:ran.value]
     if verbose:
-        for e in range(num_epochs):                                                         # :146
+        for e in range(ran.value):                                                          # :146
             print("EPOCH : %d \t PPO LOSS : %1.4f\t ENTROPY LOSS : %1.4f \t LR : %1.1e" % (e + 1, ph[e], eh[e], lh[e]))
     return list(ph), list(eh), list(lh)                     # lr = get_optimizer_learning_rate per epoch (:144)
 
@@ -1251,8 +1307,16 @@ def ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size,
     the end, :198-201).
     critic (keyword only; None = the reference's loop, advantage = returns): a HipCritic with its own critic_optimizer.
     Each iteration then is collect, GAE(discount, gae_lambda) from the critic as it stands, ppo_train_ on that advantage,
-    value_train_ on the lambda-returns for value_epochs (default epochs_per_iteration) epochs; loss gains "value"."""
+    value_train_ on the lambda-returns for value_epochs (default epochs_per_iteration) epochs; loss gains "value".
+    With policy.target_kl set (float("inf") to record without stopping) loss also gains "approx_kl" and "clip_fraction",
+    one entry per epoch that ran, and with a critic "explained_variance", one per iteration, of the values the critic
+    had before that iteration's update."""
     loss = {"ppo": [], "entropy": [], "lr": []}
+    stats = getattr(policy, "target_kl", None) is not None
+    if stats:
+        loss["approx_kl"], loss["clip_fraction"] = [], []
+        if critic is not None:
+            loss["explained_variance"] = []
     if critic is not None:
         if critic_optimizer is None:
             raise PPOError(-1, "AssertionError: a critic needs its own critic_optimizer")
@@ -1273,6 +1337,8 @@ def ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size,
             compute_gae_critic_(dataset.rollouts, env, critic, discount, gae_lambda, fetch=False)
             p, e, lr = ppo_train_(policy, optimizer, dataset, epsilon, minibatch_size, epochs_per_iteration,
                                   entropy_weight, verbose=verbose, advantage="gae")
+            if stats:
+                loss["explained_variance"].append(explained_variance_(dataset.rollouts, "lambda_returns"))
             v, _ = value_train_(critic, critic_optimizer, dataset, minibatch_size,
                                 epochs_per_iteration if value_epochs is None else value_epochs,
                                 target="lambda_returns", verbose=verbose)
@@ -1280,6 +1346,10 @@ def ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size,
         loss["ppo"] += p
         loss["entropy"] += e
         loss["lr"] += lr
+        if stats:
+            st = policy.last_train_stats()
+            loss["approx_kl"] += st["approx_kl"]
+            loss["clip_fraction"] += st["clip_fraction"]
         save_loss(evaluator, loss)       # :196,247 -- like the reference, an evaluator without a save_loss method throws
     if state_data_path is not None and os.path.isdir(state_data_path):
         if verbose:

@@ -120,6 +120,10 @@ SIGNATURES = {
     "ppo_rollouts_compute_gae_critic": [H, H, H, C.c_double, C.c_double, c_f32p, c_f32p],
     "ppo_value_forward_backward": [H, H, c_i64p, C.c_int64, C.c_int64, C.c_int32, c_f64p],
     "ppo_value_train": [H, H, H, C.c_int64, C.c_int32, C.c_int32, c_i64p, C.c_uint64, c_f64p, c_f64p],
+    "ppo_policy_set_target_kl": [H, C.c_double],
+    "ppo_policy_get_target_kl": [H, c_f64p],
+    "ppo_policy_last_train_stats": [H, C.c_int32, c_i32p, c_i32p, c_f64p, c_f64p, c_f64p],
+    "ppo_rollouts_value_moments": [H, C.c_int32, c_f64p],
     "ppo_rccl_probe": [],
     "ppo_rccl_unique_id": [C.c_void_p],
     "ppo_rccl_init": [C.c_int32, C.c_int32, C.c_void_p],

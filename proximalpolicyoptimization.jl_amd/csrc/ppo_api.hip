@@ -793,7 +793,7 @@ int32_t ppo_collect_rollouts(ppo_rollouts_t ro, ppo_env_t env, ppo_policy_t pol,
         PPO_TRY(disk_sink_step(ro, t));                 // out-of-core store: async D2H of step t on the copy stream
     }
     }
-    ro->T = T; ro->adv_T = -1;
+    ro->T = T; ro->adv_T = -1; ro->values_T = -1;
     PPO_TRY(set_index_all(ro));
     // compute_state_value!: returns overwrite the rewards column (src/rollout_buffer.jl:55-64)
     PPO_TRY(launch_returns_tn(ro->rewards.p, ro->done.p, ro->returns.p, T, N, discount, discount_is_f32));
@@ -839,7 +839,7 @@ int32_t ppo_collect_rollouts_episodes(ppo_rollouts_t ro, ppo_env_t env, ppo_poli
             if (all) break;
         }
     }
-    ro->T = T; ro->adv_T = -1;
+    ro->T = T; ro->adv_T = -1; ro->values_T = -1;
     // dataset order = env-major concatenation of whole episodes (the reference's flat buffer)
     std::vector<uint8_t> valid((size_t)T * N);
     PPO_TRY(d2h(valid.data(), ro->valid.p, (size_t)T * N));
@@ -927,7 +927,7 @@ static int32_t evaluate_impl(ppo_policy_s* pol, ppo_env_s* env, ppo_rollouts_s* 
         }
     }
     ARG_CHECK(all, "evaluator: the episodes did not finish within max_actions steps each");
-    scratch->T = 0; scratch->len = 0; scratch->adv_T = -1;
+    scratch->T = 0; scratch->len = 0; scratch->adv_T = -1; scratch->values_T = -1;
     values.resize((size_t)num_traj);
     PPO_TRY(d2h(values.data(), out.p, (size_t)num_traj));
     return ppo_env_check_errors(env, nullptr);
@@ -1022,7 +1022,7 @@ int32_t ppo_rollouts_set(ppo_rollouts_t ro, int64_t T, const int8_t* states, con
     PPO_TRY(h2d(ro->actions.p, actions0, n)); PPO_TRY(h2d(ro->p_sel.p, p_sel, n)); PPO_TRY(h2d(ro->returns.p, returns, n));
     PPO_TRY(h2d(ro->rewards.p, returns, n));
     if (terminal) PPO_TRY(h2d(ro->done.p, terminal, n));
-    ro->T = T; ro->adv_T = -1;
+    ro->T = T; ro->adv_T = -1; ro->values_T = -1;
     return set_index_all(ro);
 }
 
@@ -1036,7 +1036,7 @@ int32_t ppo_rollouts_compute_gae(ppo_rollouts_t ro, const float* values, double 
     PPO_TRY(ro->values.alloc(n + ro->N)); PPO_TRY(ro->adv.alloc((size_t)ro->capT * ro->N)); PPO_TRY(ro->lam_ret.alloc((size_t)ro->capT * ro->N));
     PPO_TRY(h2d(ro->values.p, values, n + ro->N));
     PPO_TRY(launch_gae_tn(ro->rewards.p, ro->done.p, ro->values.p, ro->adv.p, ro->lam_ret.p, ro->T, ro->N, gamma, lambda));
-    ro->adv_T = ro->T;
+    ro->adv_T = ro->T; ro->values_T = ro->T;
     if (adv_out) PPO_TRY(d2h(adv_out, ro->adv.p, n));
     if (lambda_returns_out) PPO_TRY(d2h(lambda_returns_out, ro->lam_ret.p, n));
     return PPO_OK;
@@ -1055,6 +1055,7 @@ static int32_t train_reserve(ppo_policy_s* p, int64_t B, bool compact = false) {
     // one gradient slab per backward workgroup: 256, or 512 where two workgroups share a CU (fp32 HID = 128, F = 72)
     PPO_TRY(p->slabs.alloc((size_t)((p->HID == 128 && p->F == 72) ? 512 : 256) * slab_floats(p->F, p->HID, p->L)));
     PPO_TRY(p->idx.alloc((size_t)B));
+    PPO_TRY(p->ratio.alloc((size_t)B)); p->ratio_last = nullptr; p->ratio_last_n = 0;
     p->cap_tiles = B;
     return PPO_OK;
 }
@@ -1062,8 +1063,14 @@ static int32_t train_reserve(ppo_policy_s* p, int64_t B, bool compact = false) {
 // idx_dev: transition ids (already resolved through the dataset index)
 static int32_t forward_backward_dev(ppo_policy_s* pol, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B,
                                     int64_t B_global, double eps, double ew, int32_t adv_mode, ppo_adam_s* fuse_opt = nullptr,
-                                    float* fuse_hist2 = nullptr) {
+                                    float* fuse_hist2 = nullptr, float* ratio_dst = nullptr) {
     PPO_TRY(train_reserve(pol, B * (ro->H / 32), ro->compact));
+    // the tail's probability ratios, stored while a target_kl is set only (measured: the store costs the train forward 0.2 %,
+    // more than the run-to-run spread of the benchmark): the caller's slice of an epoch column (ppo_train), else the
+    // policy's minibatch buffer
+    const bool keep_ratio = pol->target_kl != 0.0;
+    pol->ratio_out = !keep_ratio ? nullptr : ratio_dst ? ratio_dst : pol->ratio.p;
+    if (keep_ratio && !ratio_dst) { pol->ratio_last = pol->ratio.p; pol->ratio_last_n = (int64_t)pol->ratio.n; }
     const float* adv = ro->returns.p;                       // batch_advantage = returns (reference-equivalent)
     if (adv_mode == PPO_ADV_GAE || adv_mode == PPO_ADV_GAE_NORMALISED) {
         ARG_CHECK(ro->adv.p && ro->adv_T == ro->T, "batch_advantage: GAE mode needs ppo_rollouts_compute_gae on these rollouts first");
@@ -1148,6 +1155,15 @@ int32_t ppo_debug_train_outputs(ppo_policy_t pol, int64_t tiles, float* dY, doub
     return PPO_OK;
 }
 
+// likewise: the probability ratios p_new / p_old the loss tail stored, one per state -- of the latest forward in minibatch
+// order (n up to the capacity of that buffer: what lies behind the minibatch is whatever an earlier, larger one left), or,
+// after ppo_train, of its latest epoch in the order of that epoch's permutation (n up to the dataset length)
+int32_t ppo_debug_train_ratios(ppo_policy_t pol, int64_t n, float* out) {
+    ARG_CHECK(pol && out, "ppo_debug_train_ratios: null argument");
+    ARG_CHECK(pol->ratio_last && n >= 1 && n <= pol->ratio_last_n, "ppo_debug_train_ratios: no ratios stored, or n out of range");
+    return d2h(out, pol->ratio_last, (size_t)n);
+}
+
 int32_t ppo_step_batch(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, const int64_t* sample_idx, int64_t B,
                        double epsilon, double entropy_weight, int32_t adv_mode, double* ppoloss, double* entropyloss) {
     PPO_TRY(ppo_forward_backward(pol, ro, sample_idx, B, B, epsilon, entropy_weight, adv_mode));
@@ -1216,6 +1232,19 @@ int32_t ppo_train(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, double ep
     if (perm) PPO_TRY(permd.alloc(len));
     PPO_TRY(hist.alloc((size_t)nb * 2));
     std::vector<float> hh((size_t)nb * 2);
+    // per-epoch statistics of the probability ratios (ppo_stats.hip), while a target_kl is set: every minibatch's train
+    // forward stores its ratios in its slice of one column, one reduction per epoch reads the column, its four sums come
+    // back with the loss history.  target_kl == 0: nothing is stored, launched or copied, the statistics are NaN
+    const double target_kl = pol->target_kl;
+    const bool stats = target_kl != 0.0;
+    if (stats) {
+        if (pol->ratio_col.n < (size_t)len) { pol->ratio_last = nullptr; pol->ratio_last_n = 0; }
+        PPO_TRY(pol->ratio_col.alloc((size_t)len));
+        PPO_TRY(pol->stats_part.alloc(stats_part_doubles()));
+    }
+    pol->stats_kl.clear(); pol->stats_old_kl.clear(); pol->stats_clip.clear(); pol->stats_stopped = 0;
+    DevBuf<float> sx;                                                  // the ranks' sums, three floats per double
+    if (world > 1 && target_kl > 0) PPO_TRY(sx.alloc((size_t)12 * world));
     for (int32_t ep = 0; ep < num_epochs; ++ep) {
         if (perm) {                                                    // randperm(num_data)  src/train.jl:93
             PPO_TRY(h2d(permd.p, perm + (size_t)ep * len, (size_t)len));
@@ -1234,7 +1263,7 @@ int32_t ppo_train(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, double ep
             for (int64_t l : lens) Bg += std::max<int64_t>(0, std::min(batch_size, l - start));
             // single-rank training: Adam and the re-pack ride in the slab-reduction launch (PPO_FUSE_REDUCE_ADAM=0: separate launches)
             const bool fused = ppo_knobs().fuse_reduce_adam && !allreduce && B > 0;
-            if (B > 0) PPO_TRY(forward_backward_dev(pol, ro, order.p + start, B, Bg, epsilon, entropy_weight, adv_mode, fused ? opt : nullptr, hist.p + 2 * b));
+            if (B > 0) PPO_TRY(forward_backward_dev(pol, ro, order.p + start, B, Bg, epsilon, entropy_weight, adv_mode, fused ? opt : nullptr, hist.p + 2 * b, stats ? pol->ratio_col.p + start : nullptr));
             else HIP_TRY(hipMemsetAsync(pol->grad.p, 0, (size_t)(pol->np + 2) * sizeof(float), g_stream));   // shard exhausted
             if (allreduce) {                     // every rank of a data-parallel run; a world of 1 may pass it too
                 ProfScope ps("allreduce");
@@ -1244,12 +1273,47 @@ int32_t ppo_train(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, double ep
             if (!fused) PPO_TRY(launch_adam(opt, hist.p + 2 * b));                  // Flux.update!  :81 (+ loss history)
         }
         opt->epochs_done += 1;
+        double st[4] = {NAN, NAN, NAN, 1.0};                                         // sum(-log r), sum((r - 1) - log r), clipped, n
+        if (stats) {
+            PPO_TRY(launch_ratio_stats(pol->ratio_col.p, len, epsilon, pol->stats_part.p));
+            pol->ratio_last = pol->ratio_col.p; pol->ratio_last_n = len;
+            HIP_TRY(hipMemcpyAsync(st, pol->stats_part.p, sizeof(st), hipMemcpyDeviceToHost, g_stream));   // waited for just below
+        }
         PPO_TRY(d2h(hh.data(), hist.p, (size_t)nb * 2));
         double sp = 0.0, se = 0.0;
         for (int64_t i = 0; i < nb; ++i) { sp += hh[2 * i]; se += hh[2 * i + 1]; }
         if (ppo_hist) ppo_hist[ep] = sp / (double)nb;                               // unweighted mean over batches :127
         if (entropy_hist) entropy_hist[ep] = se / (double)nb;
         if (lr_hist) lr_hist[ep] = opt->lr();                                       // :144,155-158
+        if (world > 1 && target_kl > 0) {
+            // every rank must take the same decision: gather all ranks' sums EXACTLY (a one-hot [world][4][3] vector through
+            // the hook's sum, each double as three floats whose sum it is) and add them in rank order
+            std::vector<float> hx((size_t)12 * world, 0.0f);
+            for (int q = 0; q < 4; ++q) {
+                float* d = hx.data() + 12 * (size_t)rank + 3 * q;
+                d[0] = (float)st[q];
+                if (std::isfinite(st[q]) && std::isfinite(d[0])) {
+                    const double r1 = st[q] - (double)d[0];
+                    d[1] = (float)r1; d[2] = (float)(r1 - (double)d[1]);
+                }
+            }
+            PPO_TRY(h2d(sx.p, hx.data(), hx.size()));
+            if (allreduce(allreduce_ctx, sx.p, 12 * (int64_t)world) != 0) { ppo_set_error("all-reduce hook failed (ratio statistics)"); return PPO_ERR_ARG; }
+            PPO_TRY(d2h(hx.data(), sx.p, hx.size()));
+            for (int q = 0; q < 4; ++q) {
+                st[q] = 0.0;
+                for (int32_t r = 0; r < world; ++r) {
+                    const float* d = hx.data() + 12 * (size_t)r + 3 * q;
+                    st[q] += ((double)d[0] + (double)d[1]) + (double)d[2];
+                }
+            }
+        }
+        const double kl = st[1] / st[3];
+        pol->stats_kl.push_back(kl); pol->stats_old_kl.push_back(st[0] / st[3]); pol->stats_clip.push_back(st[2] / st[3]);
+        if (target_kl > 0 && !(kl <= target_kl)) {          // Inf and NaN stop too; this epoch's updates stay applied
+            pol->stats_stopped = ep + 1 < num_epochs ? 1 : 0;
+            break;
+        }
     }
     int32_t f = 0;
     PPO_TRY(d2h(&f, pol->err.p, 1));
@@ -1257,6 +1321,32 @@ int32_t ppo_train(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, double ep
     return PPO_OK;
 }
 
+
+// ---- per-epoch KL / clip-fraction statistics and target-KL early stopping (no reference op)
+int32_t ppo_policy_set_target_kl(ppo_policy_t pol, double target_kl) {
+    ARG_CHECK(target_kl >= 0.0, "policy_set_target_kl: target_kl must be 0 (off), positive or +inf");    // NaN fails it too
+    ARG_CHECK(pol, "policy_set_target_kl: null policy");
+    pol->target_kl = target_kl;
+    return PPO_OK;
+}
+int32_t ppo_policy_get_target_kl(ppo_policy_t pol, double* target_kl) {
+    ARG_CHECK(pol && target_kl, "policy_get_target_kl: null argument");
+    *target_kl = pol->target_kl;
+    return PPO_OK;
+}
+int32_t ppo_policy_last_train_stats(ppo_policy_t pol, int32_t cap, int32_t* epochs_run, int32_t* stopped_early,
+                                    double* approx_kl, double* old_approx_kl, double* clip_fraction) {
+    ARG_CHECK(pol && cap >= 0, "policy_last_train_stats: null policy or negative capacity");
+    const size_t n = pol->stats_kl.size(), m = std::min(n, (size_t)cap);
+    if (epochs_run) *epochs_run = (int32_t)n;
+    if (stopped_early) *stopped_early = pol->stats_stopped;
+    for (size_t i = 0; i < m; ++i) {
+        if (approx_kl) approx_kl[i] = pol->stats_kl[i];
+        if (old_approx_kl) old_approx_kl[i] = pol->stats_old_kl[i];
+        if (clip_fraction) clip_fraction[i] = pol->stats_clip[i];
+    }
+    return PPO_OK;
+}
 
 // ================================================================ critic
 // A critic is a ppo_policy_t read as a state value (include/ppo_hip.h): the refusals every value entry point shares
@@ -1303,6 +1393,7 @@ static int32_t compute_values_dev(const char* who, ppo_rollouts_s* ro, ppo_env_s
     } else {
         HIP_TRY(hipMemsetAsync(ro->values.p + n, 0, (size_t)ro->N * sizeof(float), g_stream));
     }
+    ro->values_T = ro->T;
     return PPO_OK;
 }
 
@@ -1335,6 +1426,17 @@ static int32_t value_target(ppo_rollouts_s* ro, int32_t target, const float** co
         ARG_CHECK(ro->lam_ret.p && ro->adv_T == ro->T, "value target: lambda-returns mode needs ppo_rollouts_compute_gae on these rollouts first");
     *col = target == PPO_VTARGET_RETURNS ? ro->returns.p : ro->lam_ret.p;
     return PPO_OK;
+}
+
+int32_t ppo_rollouts_value_moments(ppo_rollouts_t ro, int32_t target, double* sums5) {
+    ARG_CHECK(ro && sums5, "value_moments: null argument");
+    ARG_CHECK(ro->T >= 1 && ro->len >= 1, "value_moments: empty rollout buffer");
+    ARG_CHECK(ro->values.p && ro->values_T == ro->T, "value_moments: needs ppo_rollouts_compute_values or ppo_rollouts_compute_gae on these rollouts first");
+    const float* col = nullptr;
+    PPO_TRY(value_target(ro, target, &col));
+    PPO_TRY(ro->stats_part.alloc(stats_part_doubles()));
+    PPO_TRY(launch_value_moments(col, ro->values.p, ro->valid.p, ro->index.p, ro->T * ro->N, ro->stats_part.p));
+    return d2h(sums5, ro->stats_part.p, 5);
 }
 
 // idx_dev: transition ids (already resolved through the dataset index)

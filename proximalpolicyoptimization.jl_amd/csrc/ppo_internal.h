@@ -130,6 +130,16 @@ struct ppo_policy_s {
     int32_t nwg_small = 0;             // slabs holding its small-gradient tails (0: the same slabs)
     int64_t last_B = 0;
     double last_entropy_weight = 0.0;
+    // probability ratios p_new(a|s) / p_old(a|s) of the train forward (ppo_policy_tail.h) and what ppo_train makes of them
+    DevBuf<float> ratio;               // [cap_tiles] one minibatch (ppo_forward_backward / ppo_step_batch), minibatch order
+    DevBuf<float> ratio_col;           // [len] one epoch of ppo_train: the minibatch at dataset position `start` writes at start
+    float* ratio_out = nullptr;        // where the next train forward stores them (forward_backward_dev sets it)
+    const float* ratio_last = nullptr; // what ppo_debug_train_ratios reads: the latest forward's, or the latest epoch's column
+    int64_t ratio_last_n = 0;          // floats readable there
+    DevBuf<double> stats_part;         // block partials of the two reductions, then their results (ppo_stats.hip)
+    double target_kl = 0.0;            // ppo_policy_set_target_kl: 0 off
+    int32_t stats_stopped = 0;         // the latest ppo_train: ended by target_kl before num_epochs
+    std::vector<double> stats_kl, stats_old_kl, stats_clip;   // ... and its per-epoch statistics (epochs that ran)
 };
 
 // one member of a Flux.Optimiser chain (ppo_optimiser_create) other than Adam, whose hyper-parameters and state are the
@@ -192,6 +202,8 @@ struct ppo_rollouts_s {
     DevBuf<float> adv;         // [T][N] GAE(gamma, lambda) advantages (PPO_ADV_GAE*)
     DevBuf<float> lam_ret;     // [T][N] lambda-returns adv + V
     int64_t adv_T = -1;        // T the adv column was computed for (-1: none)
+    int64_t values_T = -1;     // T the values were computed for (-1: none)
+    DevBuf<double> stats_part; // workspace and result of k_value_moments (ppo_stats.hip)
     bool all_valid = true;
     DiskSink* sink = nullptr;  // optional out-of-core store (ppo_rollouts_attach_disk)
     ~ppo_rollouts_s();
@@ -333,4 +345,12 @@ int64_t clip_slot_count(const ppo_policy_s* p);                     // ClipNorm 
 int32_t launch_adam(ppo_adam_s* o, float* hist2_or_null);           // any handle: a chain other than Adam alone -> k_chain_update
 int32_t launch_categorical(const float* probs, const float* u, int64_t B, int64_t A, int32_t* actions, float* psel,
                            int32_t* err);
+// ppo_stats.hip -- fixed-order fp64 reductions; part: workspace of stats_part_doubles() doubles, the results land in its
+// first 4 (ratio statistics: sum(-log r), sum((r - 1) - log r), count(|r - 1| > eps), n) resp. 5 (value moments) doubles
+size_t stats_part_doubles();
+int32_t launch_ratio_stats(const float* ratio, int64_t n, double eps, double* part);
+// over the transitions with valid[i] != 0 of [0, n): n, sum x, sum x^2, sum y, sum y^2 with x = t - t[i0], y = (t - v) - (t - v)[i0],
+// i0 = first_id[0] (a valid transition: the first of the dataset)
+int32_t launch_value_moments(const float* target, const float* values, const uint8_t* valid, const int32_t* first_id,
+                             int64_t n, double* part);
 int32_t launch_feistel_index(const int32_t* index_dev, int64_t len, uint64_t seed, uint32_t epoch, int32_t* out_dev);

@@ -693,7 +693,7 @@ int32_t launch_policy_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32
     a.act1 = (float4*)p->act1.p; a.act2 = (float4*)p->act2.p; a.dY = (float4*)p->dY.p; a.loss_terms = p->loss_terms.p;
     for (int l = 0; l < 2; ++l)          // deep policies: the hidden layers between the first and the last
         a.act_mid[l] = (p->L > 2 && l < p->L - 2) ? (float4*)p->actm.p + (size_t)l * p->cap_tiles * (p->HID / 32) * 256 : nullptr;
-    a.actions = ro->actions.p; a.p_old = ro->p_sel.p; a.adv = adv_col;
+    a.actions = ro->actions.p; a.p_old = ro->p_sel.p; a.adv = adv_col; a.ratio_out = p->ratio_out;
     a.eps = eps; a.c_over_B = (float)(entropy_weight / (double)B_global); a.inv_B = (float)(1.0 / (double)B_global);
     ProfScope ps("k_policy_fwd_train");
     if (ro->compact) {      // env snapshots instead of observation rows (MODE 4 / the CS form of the split kernel)

@@ -47,6 +47,9 @@ struct FwdArgs {
     // critic (k_policy_fwd value modes, value_tail): state values out, indexed like the states (predict); regression target per
     // transition id (train).  Appended last: the offsets of every field above are what the other kernels were built with
     float* values_out; const float* vtarget;
+    // MODE 2, optional: ratio_out[state] = p_new(a|s) / p_old(a|s) of every state of the minibatch, the quotient the
+    // surrogate forms (per-epoch KL / clip-fraction statistics, ppo_stats.hip).  Appended last, like the two above
+    float* ratio_out;
 };
 
 // value of lane (lane ^ OFF), OFF < 32.  Same lane mapping as __shfl_xor (which hipcc lowers to ds_bpermute_b32: an
@@ -237,7 +240,10 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
                 if (TPS == 1 && dy_copy) dy_copy[j] = dyv;
             }
         }
-        if (lane == 0) { a.loss_terms[state * 2] = minval; a.loss_terms[state * 2 + 1] = (double)(-hl); }
+        if (lane == 0) {
+            a.loss_terms[state * 2] = minval; a.loss_terms[state * 2 + 1] = (double)(-hl);
+            if (a.ratio_out) a.ratio_out[state] = ps / po;                   // the quotient inside `gain`
+        }
     }
     return sampled;
 }

@@ -341,7 +341,7 @@ int32_t launch_policy_train_tile(ppo_policy_s* p, ppo_rollouts_s* ro, const int3
     a.w1p = (const float4*)p->w1p.p; a.w2p = (const float4*)p->w2p.p; a.b1p = (const float4*)p->b1p.p;
     a.b2p = (const float4*)p->b2p.p; a.w3p = (const float4*)p->w3p.p; a.b3 = p->b3.p;
     a.states = ro->states.p; a.active = ro->active.p; a.idx = idx_dev; a.B = B;
-    a.dY = (float4*)p->dY.p; a.loss_terms = p->loss_terms.p;
+    a.dY = (float4*)p->dY.p; a.loss_terms = p->loss_terms.p; a.ratio_out = p->ratio_out;
     a.actions = ro->actions.p; a.p_old = ro->p_sel.p; a.adv = adv_col;
     a.eps = eps; a.c_over_B = (float)(entropy_weight / (double)B_global); a.inv_B = (float)(1.0 / (double)B_global);
     ta.w2tp = (const float4*)p->w2tp.p;
