@@ -31,6 +31,12 @@
 //      8 k-tiles x 2 k-steps x 6 = 96 MFMAs.
 // The next tile's layer-1 / layer-2 fragments arrive by LDS-DMA during phase C into regions only this wave touches
 // and that are dead by then (its dZ2 fragment images, its H2^T rows).
+//
+// Addresses.  The vector memory instructions of the tile loop and the dW2 / dW1 slab write have wave-uniform bases: they are issued
+// with the base in SGPRs and a 32-bit lane offset (global_load v, s[..]), not with a 64-bit address per lane.  The wave issues in
+// order, so the clocks a load takes to issue are clocks its next MFMA waits: the 48 W2 piece loads of the dH1 chain cost
+// the wave about as much as the chain's 96 MFMAs.  Neither the depth of the ring (3 .. 8 entries), nor serving the stream
+// from the L1, nor fetching the dZ2 fragments a k-step ahead moves the chain; the addressing form does.
 #include "ppo_internal.h"
 #include "ppo_device.h"
 #include <cstdlib>
@@ -68,8 +74,6 @@ struct XCfg {
 // VALU ops, instead of living in ~30 loop-invariant registers that hipcc hoists out of the tile loop and spills
 #define X6_LANE() unsigned ln = (unsigned)lane; asm volatile("" : "+v"(ln)); const int j = (int)(ln & 31u), h = (int)(ln >> 5); (void)j; (void)h
 
-// W2 piece fragments in flight ahead of the dH1 chain (3 per k-step).  HID = 256 runs at the 256-register budget: with
-// the chain's two accumulators a ring of 6 spills one accumulator tile inside the chain loop, 3 fits
 #ifndef PPO_X6_DMA_SPREAD
 // next-tile LDS-DMA loads spread through phase C's MFMA loop (bit 0: layer 2, bit 1: layer 1) or issued together in front of
 // it (0).  Off: the loads have to land before the barrier that ends the tile (see the loop), and the pieces issued last
@@ -79,9 +83,10 @@ struct XCfg {
 #ifndef PPO_X6_RING
 #define PPO_X6_RING 6
 #endif
-// W2 pieces in flight per wave in the dH1 chain.  The chain waits on the L2 (one k-step of prefetch distance is ~200-400 clocks
-// of MFMA work, an L2 hit is longer), so the ring is as deep as the registers allow: at HID = 256 that is 4 (256 VGPRs, no
-// scratch; 6 spills 72 B and measured slower, 3 -> 4: 0.2484 -> 0.2440 ms, gpurun_out/rd4, tools/r3_rd4_ab.sh)
+// W2 pieces in flight per wave in the dH1 chain (3 per k-step).  At HID = 256 the kernel runs at the 256-register budget: 4
+// fit, 6 spill 72 B inside the chain loop.  Depth is not what the chain waits for: with the third dW1 accumulator tile parked
+// in LDS across the chain (its 9 live columns; 253 VGPRs, no scratch) rings of 6 and 8 measured 1-2 % SLOWER than 4, with
+// and without the scalar-base loads (profiles/r05_w2_ring_ab.txt), so the parking was not kept.  3 -> 4 was worth 1.8 %.
 #ifndef PPO_X6_RING_256
 #define PPO_X6_RING_256 4
 #endif
@@ -157,14 +162,15 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_bwd_x6(BwdXArgs a) {
     // asm (see ppo_policy_bwd.hip for why hipcc must not know) and waited for with an explicit vmcnt(0) in front of the barrier that
     // ends the tile
     auto dma_frag = [&](const float4* base, int64_t t, unsigned dst_lds, unsigned ln) {
-        const float4* src = base + ((size_t)t * NT + w) * 4 * 64 + ln;
+        const float4* const sb = base + ((size_t)t * NT + w) * 4 * 64;     // wave-uniform: scalar base + 32-bit lane offset
+        const unsigned voff = ln * 16u;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             unsigned keep;
-            const float4* gsrc = src + q * 64;
+            const float4* gsrc = sb + q * 64;
             const unsigned dst = dst_lds + (unsigned)q * 1024u;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3 nt\n\ts_mov_b32 m0, %0"
+                         : "=&s"(keep) : "v"(voff), "s"(dst), "s"(gsrc) : "memory");
         }
     };
     // one of the four 1 KiB pieces of such a load (phase C issues them one per fragment set, between the MFMAs: eight loads
@@ -332,7 +338,7 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_bwd_x6(BwdXArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
             // one pass over the k-steps; per k-step the three W2 pieces (lo, mid, hi: 1 + 2 + 3 MFMAs against the dZ2 pieces).
-            // The stream pointer is a scalar that advances 1 KiB per piece, the fragment pointer advances per ring round:
+            // The stream offset is a scalar that advances 3 KiB per k-step, the fragment pointer advances per ring round:
             // nothing here is a per-step address the compiler could hoist out of the tile loop and spill
             // The leading terms (h h) and the small ones (h m + m h, 2^-8; h l + m m + l h, 2^-16) in separate accumulators,
             // added at the end: inside one MFMA the 16 products and the accumulator are aligned to the largest of them before
@@ -342,7 +348,10 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_bwd_x6(BwdXArgs a) {
             f32x16 accs;
 #pragma unroll
             for (int r = 0; r < 16; ++r) accs[r] = 0.0f;
-            const char* wn = wx + (size_t)RD * 1024;
+            // the stream position is a SCALAR byte offset from the wave's stream (opaque, so that it is not folded into a
+            // 64-bit address per lane): the reloads below are global_load v, s[..] with a 32-bit lane offset
+            unsigned wo = (unsigned)RD * 1024u;
+            asm volatile("" : "+s"(wo));
             // ring entry i of the stream (i = 3 k + piece) lives in slot i % RD; a round is the fewest k-steps after which the
             // slots repeat (RD = 3: 1, RD = 6: 2, RD = 4: 4), so every slot index below is a compile-time constant
             constexpr int RU = (RD % 3 == 0) ? RD / 3 : RD;
@@ -363,19 +372,20 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_bwd_x6(BwdXArgs a) {
                     const uint4 z_l = *reinterpret_cast<const uint4*>(zp + (u * 3 + 2) * 1024);
                     accs = x_mfma(z_h, ring[s0], accs);
                     __builtin_amdgcn_sched_barrier(0);
-                    ring[s0] = *reinterpret_cast<const uint4*>(wn + lo16);
+                    ring[s0] = *reinterpret_cast<const uint4*>(wx + (lo16 + wo));
                     __builtin_amdgcn_sched_barrier(0);
                     accs = x_mfma(z_m, ring[s1], accs);
                     accs = x_mfma(z_h, ring[s1], accs);
                     __builtin_amdgcn_sched_barrier(0);
-                    ring[s1] = *reinterpret_cast<const uint4*>(wn + 1024 + lo16);
+                    ring[s1] = *reinterpret_cast<const uint4*>(wx + (lo16 + wo + 1024u));
                     __builtin_amdgcn_sched_barrier(0);
                     accs = x_mfma(z_l, ring[s2], accs);
                     accs = x_mfma(z_m, ring[s2], accs);
                     acc = x_mfma(z_h, ring[s2], acc);
                     __builtin_amdgcn_sched_barrier(0);
-                    ring[s2] = *reinterpret_cast<const uint4*>(wn + 2048 + lo16);
-                    wn += 3 * 1024;
+                    ring[s2] = *reinterpret_cast<const uint4*>(wx + (lo16 + wo + 2048u));
+                    wo += 3 * 1024;
+                    asm volatile("" : "+s"(wo));
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 zp += RU * 3 * 1024;
@@ -542,15 +552,20 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_bwd_x6(BwdXArgs a) {
     float* sb2 = sb1 + HID;
     float* sw3 = sb2 + HID;                              // [HID][4]
     float* sb3 = sw3 + HID * 4;
+    unsigned l4 = (unsigned)lane * 4u;                  // (scalar tile base + 32-bit lane offset, as in the tile loop)
+    asm volatile("" : "+v"(l4));
 #pragma unroll
-    for (int kt = 0; kt < NT; ++kt)
+    for (int kt = 0; kt < NT; ++kt) {
+        const uint64_t tb = x_uniform_addr(sW2 + (size_t)(w * NT + kt) * 16 * 64);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) sW2[((size_t)(w * NT + kt) * 16 + r) * 64 + lane] = accW2[kt][r];
+        for (int r = 0; r < 16; ++r) *x_gptr<float>(tb, l4 + (unsigned)r * 256u) = accW2[kt][r];
+    }
 #pragma unroll
     for (int it = 0; it < NI; ++it) {
         if (32 * it + j >= F) continue;                 // padding columns (inputs 72 .. 95): k_grad_reduce never reads them
+        const uint64_t tb = x_uniform_addr(sW1 + (size_t)(w * NI + it) * 16 * 64);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) sW1[((size_t)(w * NI + it) * 16 + r) * 64 + lane] = accW1[it][r];
+        for (int r = 0; r < 16; ++r) *x_gptr<float>(tb, l4 + (unsigned)r * 256u) = accW1[it][r];
     }
     // db1[k] = dW1[k][input 72] (the ones column): column 8 of input tile 2, held by lanes 8 and 40
     if (j == F - 64) {

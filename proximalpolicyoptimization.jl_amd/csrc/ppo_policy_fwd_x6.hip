@@ -284,11 +284,18 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
 
     uint2 xr[T][K1];
     auto load_x = [&](int i, int64_t rec, unsigned ln) {
-        const char* row = reinterpret_cast<const char*>(a.states) + (size_t)rec * 32 * F + (ln & 31u) * (unsigned)F + (ln >> 5) * 8u;
+        // every global access of this kernel: wave-uniform base in SGPRs + 32-bit lane offset (x_uniform_addr, ppo_x6.h); the
+        // offsets are opaque so that they are not widened and folded into a 64-bit address per lane
+        const uint64_t rb = x_uniform_addr(reinterpret_cast<const char*>(a.states) + (size_t)rec * 32 * F);
+        const unsigned row = (ln & 31u) * (unsigned)F + (ln >> 5) * 8u;
 #pragma unroll
         for (int s = 0; s < K1; ++s) {
             const bool pad = (s == K1 - 1) && (ln >> 5);
-            const uint2 v = *reinterpret_cast<const uint2*>(row + (pad ? 0 : 16 * s));
+            unsigned ro = row + (pad ? 0u : 16u * s);
+            asm volatile("" : "+v"(ro));
+            typedef unsigned u32x2l __attribute__((ext_vector_type(2)));
+            const u32x2l vv = *x_gptr<const u32x2l>(rb, ro);
+            const uint2 v = make_uint2(vv.x, vv.y);
             xr[i][s] = pad ? make_uint2(0u, 0u) : v;
         }
     };
@@ -368,12 +375,14 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
                 lrelu16(acc[i]);
                 const int64_t tile = g * T + i;
                 if (tile < a.B) {
-                    float4* dst = a.act1 + ((size_t)tile * NT + w) * 4 * 64;
+                    const uint64_t dst = x_uniform_addr(a.act1 + ((size_t)tile * NT + w) * 4 * 64);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         typedef float f32x4l __attribute__((ext_vector_type(4)));
                         const f32x4l t = {acc[i][4 * q], acc[i][4 * q + 1], acc[i][4 * q + 2], acc[i][4 * q + 3]};
-                        __builtin_nontemporal_store(t, reinterpret_cast<f32x4l*>(dst + q * 64 + ln));
+                        unsigned so = ln * 16u + (unsigned)q * 1024u;
+                        asm volatile("" : "+v"(so));
+                        __builtin_nontemporal_store(t, x_gptr<f32x4l>(dst, so));
                     }
                 }
                 char* const fown = frag + ((size_t)i * NT + w) * 6 * 1024;
@@ -393,7 +402,7 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
             }
         }
         FXSTAMP(1);
-        constexpr int RD = 6;
+        constexpr int RD = 6;                                           // 12 (170 VGPRs) is not faster at either width: level to 2 % slower (profiles/r05_w2_ring_ab.txt)
         static_assert(KS % (RD / 3) == 0, "ring rounds");
         static_assert(RD * 1024 <= PPO_X6_W2_PAD_BYTES, "the last ring round reads RD pieces past the end of the W2 stream");
         uint4 ring[RD];
@@ -431,7 +440,8 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
             }
             const unsigned lo16 = ln * 16u;
             const char* zp = frag + lo16;
-            const char* wn = w2s + (size_t)RD * 1024;
+            unsigned wo = (unsigned)RD * 1024u;                         // stream position: a scalar byte offset (see load_x)
+            asm volatile("" : "+s"(wo));
 #pragma unroll 1
             for (int k0 = 0; k0 < KS; k0 += RD / 3) {
 #pragma unroll
@@ -451,10 +461,11 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
                         acc[i] = x_mfma(wh, z_h, acc[i]);
                     }
                     __builtin_amdgcn_sched_barrier(0);
-                    ring[3 * u + 0] = *reinterpret_cast<const uint4*>(wn + lo16);          // the last round reads RD KiB ahead (padding / next wave's stream)
-                    ring[3 * u + 1] = *reinterpret_cast<const uint4*>(wn + 1024 + lo16);
-                    ring[3 * u + 2] = *reinterpret_cast<const uint4*>(wn + 2048 + lo16);
-                    wn += 3 * 1024;
+                    ring[3 * u + 0] = *reinterpret_cast<const uint4*>(w2s + (lo16 + wo));  // the last round reads RD KiB ahead (padding / next wave's stream)
+                    ring[3 * u + 1] = *reinterpret_cast<const uint4*>(w2s + (lo16 + wo + 1024u));
+                    ring[3 * u + 2] = *reinterpret_cast<const uint4*>(w2s + (lo16 + wo + 2048u));
+                    wo += 3 * 1024;
+                    asm volatile("" : "+s"(wo));
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 zp += (RD / 3) * 3 * 1024;
@@ -468,12 +479,14 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
                 lrelu16(acc[i]);
                 const int64_t tile = g * T + i;
                 if (tile < a.B) {
-                    float4* dst = a.act2 + ((size_t)tile * NT + w) * 4 * 64;
+                    const uint64_t dst = x_uniform_addr(a.act2 + ((size_t)tile * NT + w) * 4 * 64);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         typedef float f32x4l __attribute__((ext_vector_type(4)));
                         const f32x4l t = {acc[i][4 * q], acc[i][4 * q + 1], acc[i][4 * q + 2], acc[i][4 * q + 3]};
-                        __builtin_nontemporal_store(t, reinterpret_cast<f32x4l*>(dst + q * 64 + ln));
+                        unsigned so = ln * 16u + (unsigned)q * 1024u;
+                        asm volatile("" : "+v"(so));
+                        __builtin_nontemporal_store(t, x_gptr<f32x4l>(dst, so));
                     }
                 }
                 float p0 = 0.f, p1 = 0.f, p2 = 0.f, p3 = 0.f;

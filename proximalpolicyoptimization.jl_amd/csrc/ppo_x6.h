@@ -42,4 +42,13 @@ __device__ __forceinline__ uint4 x_tr_frag(const char* p0, const char* p1) {
     const uint2 a = __builtin_bit_cast(uint2, u0), b = __builtin_bit_cast(uint2, u1);
     return make_uint4(a.x, a.y, b.x, b.y);
 }
-
+// A wave-uniform global address as a scalar: base + 32-bit lane offset then selects the load / store form with a scalar base
+// (global_load v, s[..]) instead of a 64-bit address per lane, which costs the issuing wave fewer clocks per instruction
+__device__ __forceinline__ uint64_t x_uniform_addr(const void* p) {
+    const uint64_t v = reinterpret_cast<uint64_t>(p);
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+}
+template <class T>
+__device__ __forceinline__ __attribute__((address_space(1))) T* x_gptr(uint64_t base, unsigned off) {
+    return reinterpret_cast<__attribute__((address_space(1))) T*>(base + off);
+}
