@@ -1220,6 +1220,18 @@ def forward_backward(policy, dataset, batch_indices, epsilon, entropy_weight, B_
     return a.value, b.value
 
 
+def _perm0(perm, num_epochs, n):
+    """The caller's [num_epochs, n] 1-based permutations as the contiguous 0-based int64 array the library reads (None stays None)."""
+    if perm is None:
+        return None
+    return np.ascontiguousarray(np.asarray(perm, np.int64).reshape(num_epochs, n) - 1)
+
+
+def _check_batch_size(batch_size, n):
+    if not (1 <= batch_size <= n):
+        raise PPOError(-1, "AssertionError: 1 <= batch_size <= num_data")                    # src/train.jl:88
+
+
 def ppo_train_(policy, optimizer, dataset, epsilon, batch_size, num_epochs, entropy_weight, perm=None, seed=0,
                parallel=None, verbose=True, advantage="returns"):
     """PPO.ppo_train!(policy, optimizer, dataset, epsilon, batch_size, num_epochs, entropy_weight)
@@ -1227,9 +1239,7 @@ def ppo_train_(policy, optimizer, dataset, epsilon, batch_size, num_epochs, entr
     perm: optional [num_epochs, len] 1-based permutations standing in for randperm (:93)."""
     oh = optimizer._handle(policy)
     n = len(dataset)
-    pp = None
-    if perm is not None:
-        pp = np.ascontiguousarray(np.asarray(perm, np.int64).reshape(num_epochs, n) - 1)
+    pp = _perm0(perm, num_epochs, n)
     ph, eh, lh = (np.zeros(num_epochs, np.float64) for _ in range(3))
     rank, world, fn, keep = 0, 1, _lib.ALLREDUCE_FN(0), None
     if parallel is not None and (parallel.world > 1 or parallel.force_hook):
@@ -1238,8 +1248,8 @@ def ppo_train_(policy, optimizer, dataset, epsilon, batch_size, num_epochs, entr
         fn = keep
     # the data-parallel shards may differ in length: the batch_size assert is then made inside ppo_train on the
     # shortest shard, identically on every rank (a local raise here would leave the other ranks in a collective)
-    if world == 1 and not (1 <= batch_size <= n):
-        raise PPOError(-1, "AssertionError: 1 <= batch_size <= num_data")                    # :88
+    if world == 1:
+        _check_batch_size(batch_size, n)
     try:
         call("ppo_train", policy._h, oh, dataset.rollouts._h, float(epsilon), int(batch_size), int(num_epochs),
              float(entropy_weight), _adv_mode(advantage), _p(pp, _lib.c_i64p) if pp is not None else None, int(seed),
@@ -1282,11 +1292,8 @@ def value_train_(critic, optimizer, dataset, batch_size, num_epochs, target="ret
     t = _value_target(target)
     oh = optimizer._handle(critic)
     n = len(dataset)
-    pp = None
-    if perm is not None:
-        pp = np.ascontiguousarray(np.asarray(perm, np.int64).reshape(num_epochs, n) - 1)
-    if not (1 <= batch_size <= n):
-        raise PPOError(-1, "AssertionError: 1 <= batch_size <= num_data")
+    pp = _perm0(perm, num_epochs, n)
+    _check_batch_size(batch_size, n)
     mh, lh = np.zeros(num_epochs, np.float64), np.zeros(num_epochs, np.float64)
     try:
         call("ppo_value_train", critic._h, oh, dataset.rollouts._h, int(batch_size), int(num_epochs), t,

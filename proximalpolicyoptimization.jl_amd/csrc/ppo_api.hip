@@ -1,6 +1,6 @@
-// ppo_api.hip -- extern "C" surface of libppo_hip.so (include/ppo_hip.h): handle management and
-// the host-side orchestration of collect_rollouts! / ppo_train! (launch order only; all math is
-// in the kernels).  There is NO CPU fallback: every entry point runs on the GPU or fails.
+// ppo_api.hip -- extern "C" surface of libppo_hip.so (include/ppo_hip.h): engine state, handle management and
+// the host-side orchestration of collect_rollouts! (launch order only; all math is in the kernels); training
+// and the critic are in ppo_train.hip.  There is NO CPU fallback: every entry point runs on the GPU or fails.
 #include "ppo_internal.h"
 #include "ppo_device.h"
 #include <algorithm>
@@ -56,21 +56,6 @@ static int32_t ensure_init() {
     HIP_TRY(hipStreamCreate(&g_stream));
     g_own_stream = true;
     g_init = true;
-    return PPO_OK;
-}
-
-template <typename T>
-static int32_t h2d(T* dst, const T* src, size_t n) {
-    if (n == 0) return PPO_OK;
-    HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, g_stream));
-    HIP_TRY(hipStreamSynchronize(g_stream));
-    return PPO_OK;
-}
-template <typename T>
-static int32_t d2h(T* dst, const T* src, size_t n) {
-    if (n == 0) return PPO_OK;
-    HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, g_stream));
-    HIP_TRY(hipStreamSynchronize(g_stream));
     return PPO_OK;
 }
 
@@ -1039,501 +1024,6 @@ int32_t ppo_rollouts_compute_gae(ppo_rollouts_t ro, const float* values, double 
     ro->adv_T = ro->T; ro->values_T = ro->T;
     if (adv_out) PPO_TRY(d2h(adv_out, ro->adv.p, n));
     if (lambda_returns_out) PPO_TRY(d2h(lambda_returns_out, ro->lam_ret.p, n));
-    return PPO_OK;
-}
-
-// ================================================================ training
-// B = number of 32-row tiles of the minibatch (states * H/32)
-static int32_t train_reserve(ppo_policy_s* p, int64_t B, bool compact = false) {
-    if (compact) PPO_TRY(p->xs.alloc((size_t)std::max(B, p->cap_tiles) * 32 * p->F));
-    if (B <= p->cap_tiles) return PPO_OK;
-    const size_t NT = p->HID / 32;
-    PPO_TRY(p->act1.alloc((size_t)B * NT * 1024));
-    if (p->L >= 2) PPO_TRY(p->act2.alloc((size_t)B * NT * 1024));
-    if (p->L > 2) PPO_TRY(p->actm.alloc((size_t)(p->L - 2) * B * NT * 1024));       // hidden layers between the first and the last
-    PPO_TRY(p->dY.alloc((size_t)B * 128)); PPO_TRY(p->loss_terms.alloc((size_t)B * 2));
-    // one gradient slab per backward workgroup: 256, or 512 where two workgroups share a CU (fp32 HID = 128, F = 72)
-    PPO_TRY(p->slabs.alloc((size_t)((p->HID == 128 && p->F == 72) ? 512 : 256) * slab_floats(p->F, p->HID, p->L)));
-    PPO_TRY(p->idx.alloc((size_t)B));
-    PPO_TRY(p->ratio.alloc((size_t)B)); p->ratio_last = nullptr; p->ratio_last_n = 0;
-    p->cap_tiles = B;
-    return PPO_OK;
-}
-
-// idx_dev: transition ids (already resolved through the dataset index)
-static int32_t forward_backward_dev(ppo_policy_s* pol, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B,
-                                    int64_t B_global, double eps, double ew, int32_t adv_mode, ppo_adam_s* fuse_opt = nullptr,
-                                    float* fuse_hist2 = nullptr, float* ratio_dst = nullptr) {
-    PPO_TRY(train_reserve(pol, B * (ro->H / 32), ro->compact));
-    // the tail's probability ratios, stored while a target_kl is set only (measured: the store costs the train forward 0.2 %,
-    // more than the run-to-run spread of the benchmark): the caller's slice of an epoch column (ppo_train), else the
-    // policy's minibatch buffer
-    const bool keep_ratio = pol->target_kl != 0.0;
-    pol->ratio_out = !keep_ratio ? nullptr : ratio_dst ? ratio_dst : pol->ratio.p;
-    if (keep_ratio && !ratio_dst) { pol->ratio_last = pol->ratio.p; pol->ratio_last_n = (int64_t)pol->ratio.n; }
-    const float* adv = ro->returns.p;                       // batch_advantage = returns (reference-equivalent)
-    if (adv_mode == PPO_ADV_GAE || adv_mode == PPO_ADV_GAE_NORMALISED) {
-        ARG_CHECK(ro->adv.p && ro->adv_T == ro->T, "batch_advantage: GAE mode needs ppo_rollouts_compute_gae on these rollouts first");
-        adv = ro->adv.p;
-    }
-    if (adv_mode == PPO_ADV_RETURNS_NORMALISED || adv_mode == PPO_ADV_GAE_NORMALISED) {   // normalised over this rank's minibatch
-        PPO_TRY(pol->adv_col.alloc((size_t)ro->capT * ro->N));
-        PPO_TRY(launch_adv_normalise(adv, idx_dev, B, pol->adv_col.p));
-        adv = pol->adv_col.p;
-    }
-    const TrainRoute r = train_route(pol->dtype, pol->F, pol->HID, pol->L, ro->H, ro->compact, B, ppo_knobs());
-    if (r.fwd == TrainFwd::None) { ppo_set_error(r.err); return PPO_ERR_UNSUPPORTED; }
-    if (r.bwd == TrainBwd::Wgrad || r.bwd == TrainBwd::Small) {
-        const size_t frag = (size_t)pol->cap_tiles * (pol->HID / 32) * 1024;     // dZ in fragment order, like act1 / act2
-        PPO_TRY(pol->dz1f.alloc(frag));
-        if (pol->L >= 2) PPO_TRY(pol->dz2f.alloc(frag));
-        if (pol->L > 2) PPO_TRY(pol->dzm.alloc((size_t)(pol->L - 2) * frag));
-    }
-    if (r.fwd == TrainFwd::TrainTile) PPO_TRY(launch_policy_train_tile(pol, ro, idx_dev, B, B_global, eps, ew, adv));
-    else PPO_TRY(launch_policy_train_fwd(pol, ro, idx_dev, B, B_global, eps, ew, adv, r.fwd));
-    switch (r.bwd) {
-    case TrainBwd::Small: PPO_TRY(launch_policy_bwd_small(pol, ro, idx_dev, B)); break;
-    case TrainBwd::X6: PPO_TRY(launch_policy_bwd_x6(pol, ro, idx_dev, B)); break;
-    case TrainBwd::Fused: PPO_TRY(launch_policy_bwd(pol, ro, idx_dev, B)); break;
-    case TrainBwd::Bf16: PPO_TRY(launch_policy_bwd_bf16(pol, ro, idx_dev, B)); break;
-    default: break;                                         // Wgrad: launched by launch_policy_train_tile
-    }
-    PPO_TRY(launch_grad_reduce(pol, B, B_global, ew, fuse_opt, fuse_hist2));
-    pol->last_B = B; pol->last_entropy_weight = ew;
-    return PPO_OK;
-}
-
-__global__ void k_gather_index(const int32_t* __restrict__ index, const int64_t* __restrict__ pos, int64_t B,
-                               int64_t len, int32_t* __restrict__ out, int32_t* __restrict__ err) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B) return;
-    const int64_t p = pos[i];
-    if (p < 0 || p >= len) { atomicOr(err, 16); out[i] = index[0]; return; }
-    out[i] = index[p];
-}
-
-int32_t ppo_forward_backward(ppo_policy_t pol, ppo_rollouts_t ro, const int64_t* sample_idx, int64_t B,
-                             int64_t B_global, double epsilon, double entropy_weight, int32_t adv_mode) {
-    ARG_CHECK(pol && ro && sample_idx, "step_batch!: null argument");
-    ARG_CHECK(B >= 1 && B <= ro->len, "step_batch!: 1 <= batch_size <= num_data (src/train.jl:88)");
-    ARG_CHECK(B_global >= B, "step_batch!: B_global < B");
-    ARG_CHECK(pol->F == ro->F && (ro->H == 32 || ro->H == 128), "step_batch!: shape mismatch");
-    if (adv_mode < PPO_ADV_RETURNS || adv_mode > PPO_ADV_GAE_NORMALISED) { ppo_set_error("batch_advantage: unknown advantage mode"); return PPO_ERR_UNSUPPORTED; }
-    for (int64_t i = 0; i < B; ++i) ARG_CHECK(sample_idx[i] >= 0 && sample_idx[i] < ro->len, "dataset index out of range (src/rollout_buffer.jl:105-106)");
-    PPO_TRY(train_reserve(pol, B * (ro->H / 32)));
-    DevBuf<int64_t> pos;
-    PPO_TRY(pos.alloc(B));
-    PPO_TRY(h2d(pos.p, sample_idx, (size_t)B));
-    hipLaunchKernelGGL(k_gather_index, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, g_stream, ro->index.p, pos.p, B,
-                       ro->len, pol->idx.p, pol->err.p);
-    HIP_TRY(hipGetLastError());
-    PPO_TRY(forward_backward_dev(pol, ro, pol->idx.p, B, B_global, epsilon, entropy_weight, adv_mode));
-    HIP_TRY(hipStreamSynchronize(g_stream));
-    return PPO_OK;
-}
-
-int32_t ppo_adam_apply(ppo_adam_t opt, ppo_policy_t pol) {
-    ARG_CHECK(opt && pol && opt->pol == pol, "update!: optimiser was created for another policy");
-    return launch_adam(opt, nullptr);
-}
-
-int32_t ppo_last_losses(ppo_policy_t pol, double* ppoloss, double* entropyloss) {
-    ARG_CHECK(pol, "null");
-    float t[2];
-    PPO_TRY(d2h(t, pol->grad.p + pol->np, 2));
-    if (ppoloss) *ppoloss = t[0];
-    if (entropyloss) *entropyloss = t[1];
-    return PPO_OK;
-}
-
-// diagnostic for the tests (not part of include/ppo_hip.h): what the last training forward left per tile of its minibatch, in
-// minibatch order -- the dL/dlogits rows [tiles][32][4] and the two loss terms [tiles][2]
-int32_t ppo_debug_train_outputs(ppo_policy_t pol, int64_t tiles, float* dY, double* loss_terms) {
-    ARG_CHECK(pol && tiles >= 1 && tiles <= pol->cap_tiles, "ppo_debug_train_outputs: tiles out of range");
-    if (dY) PPO_TRY(d2h(dY, pol->dY.p, (size_t)tiles * 128));
-    if (loss_terms) PPO_TRY(d2h(loss_terms, pol->loss_terms.p, (size_t)tiles * 2));
-    return PPO_OK;
-}
-
-// likewise: the probability ratios p_new / p_old the loss tail stored, one per state -- of the latest forward in minibatch
-// order (n up to the capacity of that buffer: what lies behind the minibatch is whatever an earlier, larger one left), or,
-// after ppo_train, of its latest epoch in the order of that epoch's permutation (n up to the dataset length)
-int32_t ppo_debug_train_ratios(ppo_policy_t pol, int64_t n, float* out) {
-    ARG_CHECK(pol && out, "ppo_debug_train_ratios: null argument");
-    ARG_CHECK(pol->ratio_last && n >= 1 && n <= pol->ratio_last_n, "ppo_debug_train_ratios: no ratios stored, or n out of range");
-    return d2h(out, pol->ratio_last, (size_t)n);
-}
-
-int32_t ppo_step_batch(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, const int64_t* sample_idx, int64_t B,
-                       double epsilon, double entropy_weight, int32_t adv_mode, double* ppoloss, double* entropyloss) {
-    PPO_TRY(ppo_forward_backward(pol, ro, sample_idx, B, B, epsilon, entropy_weight, adv_mode));
-    PPO_TRY(ppo_last_losses(pol, ppoloss, entropyloss));
-    return ppo_adam_apply(opt, pol);
-}
-
-__global__ void k_perm_index(const int32_t* __restrict__ index, const int64_t* __restrict__ perm, int64_t len,
-                             int32_t* __restrict__ out, int32_t* __restrict__ err) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= len) return;
-    const int64_t p = perm[i];
-    if (p < 0 || p >= len) { atomicOr(err, 16); out[i] = index[0]; return; }
-    out[i] = index[p];
-}
-
-int32_t ppo_train(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, double epsilon, int64_t batch_size,
-                  int32_t num_epochs, double entropy_weight, int32_t adv_mode, const int64_t* perm, uint64_t seed,
-                  int32_t rank, int32_t world, ppo_allreduce_fn allreduce, void* allreduce_ctx, double* ppo_hist,
-                  double* entropy_hist, double* lr_hist) {
-    ARG_CHECK(pol && opt && ro && opt->pol == pol, "ppo_train!: null/mismatched argument");
-    const int64_t len = ro->len;
-    ARG_CHECK(num_epochs >= 0 && world >= 1 && rank >= 0 && rank < world, "ppo_train!: bad epochs/rank/world");
-    ARG_CHECK(world == 1 || allreduce, "ppo_train!: world > 1 needs an all-reduce hook");
-    ARG_CHECK(pol->F == ro->F && (ro->H == 32 || ro->H == 128), "ppo_train!: shape mismatch");
-    ARG_CHECK(batch_size >= 1, "1 <= batch_size <= num_data (src/train.jl:88)");
-    if (adv_mode < PPO_ADV_RETURNS || adv_mode > PPO_ADV_GAE_NORMALISED) { ppo_set_error("batch_advantage: unknown advantage mode"); return PPO_ERR_UNSUPPORTED; }
-    // Data-parallel shards may differ in length (remainder envs, episode-mode rollouts): every rank learns every
-    // rank's dataset length once per call -- an all-gather spelled as the hook's sum all-reduce over a one-hot
-    // [2*world] vector (length split into two exactly representable floats) -- and derives from them the SAME
-    // number of optimiser steps and the exact global minibatch size of each step.  A rank whose shard is exhausted
-    // contributes a zero gradient to the remaining steps, so all ranks issue the same collectives.
-    std::vector<int64_t> lens((size_t)world, len);
-    if (world > 1) {
-        DevBuf<float> xch;
-        PPO_TRY(xch.alloc((size_t)2 * world));
-        std::vector<float> hx((size_t)2 * world, 0.0f);
-        hx[2 * (size_t)rank] = (float)(len >> 12); hx[2 * (size_t)rank + 1] = (float)(len & 4095);
-        PPO_TRY(h2d(xch.p, hx.data(), hx.size()));
-        if (allreduce(allreduce_ctx, xch.p, 2 * (int64_t)world) != 0) { ppo_set_error("all-reduce hook failed (shard-length exchange)"); return PPO_ERR_ARG; }
-        // a rank that fails locally from here on must not leave the others blocked in their next collective: every rank
-        // carries its status into ONE more tiny all-reduce and all of them return together
-        int32_t local = d2h(hx.data(), xch.p, hx.size());
-        if (local == PPO_OK) {
-            for (int32_t r = 0; r < world; ++r) lens[(size_t)r] = ((int64_t)hx[2 * (size_t)r] << 12) + (int64_t)hx[2 * (size_t)r + 1];
-            if (lens[(size_t)rank] != len) {
-                ppo_set_error("AssertionError: ppo_train!: shard-length exchange is inconsistent (two ranks with the same rank id, "
-                              "or a hook that does not SUM the buffer it is handed?)");
-                local = PPO_ERR_ARG;
-            }
-        }
-        float bad = local == PPO_OK ? 0.0f : 1.0f;
-        const int32_t hs = h2d(xch.p, &bad, 1);
-        if (allreduce(allreduce_ctx, xch.p, 1) != 0) { ppo_set_error("all-reduce hook failed (status agreement)"); return PPO_ERR_ARG; }
-        PPO_TRY(hs);
-        PPO_TRY(d2h(&bad, xch.p, 1));
-        if (local != PPO_OK) return local;
-        if (bad != 0.0f) { ppo_set_error("ppo_train!: another data-parallel rank failed in the shard-length exchange"); return PPO_ERR_ARG; }
-    }
-    int64_t nb = 0, min_len = len;
-    for (int64_t l : lens) { nb = std::max(nb, (l + batch_size - 1) / batch_size); min_len = std::min(min_len, l); }
-    ARG_CHECK(batch_size <= min_len, "1 <= batch_size <= num_data (src/train.jl:88) on every data-parallel shard");
-    PPO_TRY(train_reserve(pol, batch_size * (ro->H / 32)));
-    DevBuf<int32_t> order; DevBuf<int64_t> permd; DevBuf<float> hist;
-    PPO_TRY(order.alloc(len));
-    if (perm) PPO_TRY(permd.alloc(len));
-    PPO_TRY(hist.alloc((size_t)nb * 2));
-    std::vector<float> hh((size_t)nb * 2);
-    // per-epoch statistics of the probability ratios (ppo_stats.hip), while a target_kl is set: every minibatch's train
-    // forward stores its ratios in its slice of one column, one reduction per epoch reads the column, its four sums come
-    // back with the loss history.  target_kl == 0: nothing is stored, launched or copied, the statistics are NaN
-    const double target_kl = pol->target_kl;
-    const bool stats = target_kl != 0.0;
-    if (stats) {
-        if (pol->ratio_col.n < (size_t)len) { pol->ratio_last = nullptr; pol->ratio_last_n = 0; }
-        PPO_TRY(pol->ratio_col.alloc((size_t)len));
-        PPO_TRY(pol->stats_part.alloc(stats_part_doubles()));
-    }
-    pol->stats_kl.clear(); pol->stats_old_kl.clear(); pol->stats_clip.clear(); pol->stats_stopped = 0;
-    DevBuf<float> sx;                                                  // the ranks' sums, three floats per double
-    if (world > 1 && target_kl > 0) PPO_TRY(sx.alloc((size_t)12 * world));
-    for (int32_t ep = 0; ep < num_epochs; ++ep) {
-        if (perm) {                                                    // randperm(num_data)  src/train.jl:93
-            PPO_TRY(h2d(permd.p, perm + (size_t)ep * len, (size_t)len));
-            hipLaunchKernelGGL(k_perm_index, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, g_stream, ro->index.p,
-                               permd.p, len, order.p, pol->err.p);
-            HIP_TRY(hipGetLastError());
-        } else {
-            // keyed by (seed, epochs this optimiser has trained): no process-global state, so the same seed with a
-            // fresh optimiser reproduces the run and a restored optimiser (ppo_adam_set_epoch_count) resumes it
-            PPO_TRY(launch_feistel_index(ro->index.p, len, seed, (uint32_t)opt->epochs_done, order.p));
-        }
-        for (int64_t b = 0; b < nb; ++b) {                                          // :95-96 (last batch may be short)
-            const int64_t start = b * batch_size;
-            const int64_t B = std::max<int64_t>(0, std::min(batch_size, len - start));
-            int64_t Bg = 0;
-            for (int64_t l : lens) Bg += std::max<int64_t>(0, std::min(batch_size, l - start));
-            // single-rank training: Adam and the re-pack ride in the slab-reduction launch (PPO_FUSE_REDUCE_ADAM=0: separate launches)
-            const bool fused = ppo_knobs().fuse_reduce_adam && !allreduce && B > 0;
-            if (B > 0) PPO_TRY(forward_backward_dev(pol, ro, order.p + start, B, Bg, epsilon, entropy_weight, adv_mode, fused ? opt : nullptr, hist.p + 2 * b, stats ? pol->ratio_col.p + start : nullptr));
-            else HIP_TRY(hipMemsetAsync(pol->grad.p, 0, (size_t)(pol->np + 2) * sizeof(float), g_stream));   // shard exhausted
-            if (allreduce) {                     // every rank of a data-parallel run; a world of 1 may pass it too
-                ProfScope ps("allreduce");
-                const int32_t s = allreduce(allreduce_ctx, pol->grad.p, pol->np + 2);
-                if (s != 0) { ppo_set_error("all-reduce hook failed"); return PPO_ERR_ARG; }
-            }
-            if (!fused) PPO_TRY(launch_adam(opt, hist.p + 2 * b));                  // Flux.update!  :81 (+ loss history)
-        }
-        opt->epochs_done += 1;
-        double st[4] = {NAN, NAN, NAN, 1.0};                                         // sum(-log r), sum((r - 1) - log r), clipped, n
-        if (stats) {
-            PPO_TRY(launch_ratio_stats(pol->ratio_col.p, len, epsilon, pol->stats_part.p));
-            pol->ratio_last = pol->ratio_col.p; pol->ratio_last_n = len;
-            HIP_TRY(hipMemcpyAsync(st, pol->stats_part.p, sizeof(st), hipMemcpyDeviceToHost, g_stream));   // waited for just below
-        }
-        PPO_TRY(d2h(hh.data(), hist.p, (size_t)nb * 2));
-        double sp = 0.0, se = 0.0;
-        for (int64_t i = 0; i < nb; ++i) { sp += hh[2 * i]; se += hh[2 * i + 1]; }
-        if (ppo_hist) ppo_hist[ep] = sp / (double)nb;                               // unweighted mean over batches :127
-        if (entropy_hist) entropy_hist[ep] = se / (double)nb;
-        if (lr_hist) lr_hist[ep] = opt->lr();                                       // :144,155-158
-        if (world > 1 && target_kl > 0) {
-            // every rank must take the same decision: gather all ranks' sums EXACTLY (a one-hot [world][4][3] vector through
-            // the hook's sum, each double as three floats whose sum it is) and add them in rank order
-            std::vector<float> hx((size_t)12 * world, 0.0f);
-            for (int q = 0; q < 4; ++q) {
-                float* d = hx.data() + 12 * (size_t)rank + 3 * q;
-                d[0] = (float)st[q];
-                if (std::isfinite(st[q]) && std::isfinite(d[0])) {
-                    const double r1 = st[q] - (double)d[0];
-                    d[1] = (float)r1; d[2] = (float)(r1 - (double)d[1]);
-                }
-            }
-            PPO_TRY(h2d(sx.p, hx.data(), hx.size()));
-            if (allreduce(allreduce_ctx, sx.p, 12 * (int64_t)world) != 0) { ppo_set_error("all-reduce hook failed (ratio statistics)"); return PPO_ERR_ARG; }
-            PPO_TRY(d2h(hx.data(), sx.p, hx.size()));
-            for (int q = 0; q < 4; ++q) {
-                st[q] = 0.0;
-                for (int32_t r = 0; r < world; ++r) {
-                    const float* d = hx.data() + 12 * (size_t)r + 3 * q;
-                    st[q] += ((double)d[0] + (double)d[1]) + (double)d[2];
-                }
-            }
-        }
-        const double kl = st[1] / st[3];
-        pol->stats_kl.push_back(kl); pol->stats_old_kl.push_back(st[0] / st[3]); pol->stats_clip.push_back(st[2] / st[3]);
-        if (target_kl > 0 && !(kl <= target_kl)) {          // Inf and NaN stop too; this epoch's updates stay applied
-            pol->stats_stopped = ep + 1 < num_epochs ? 1 : 0;
-            break;
-        }
-    }
-    int32_t f = 0;
-    PPO_TRY(d2h(&f, pol->err.p, 1));
-    if (f) { ppo_set_error("AssertionError (device flag): permutation / dataset index out of range"); return PPO_ERR_DEVICE_FLAG; }
-    return PPO_OK;
-}
-
-
-// ---- per-epoch KL / clip-fraction statistics and target-KL early stopping (no reference op)
-int32_t ppo_policy_set_target_kl(ppo_policy_t pol, double target_kl) {
-    ARG_CHECK(target_kl >= 0.0, "policy_set_target_kl: target_kl must be 0 (off), positive or +inf");    // NaN fails it too
-    ARG_CHECK(pol, "policy_set_target_kl: null policy");
-    pol->target_kl = target_kl;
-    return PPO_OK;
-}
-int32_t ppo_policy_get_target_kl(ppo_policy_t pol, double* target_kl) {
-    ARG_CHECK(pol && target_kl, "policy_get_target_kl: null argument");
-    *target_kl = pol->target_kl;
-    return PPO_OK;
-}
-int32_t ppo_policy_last_train_stats(ppo_policy_t pol, int32_t cap, int32_t* epochs_run, int32_t* stopped_early,
-                                    double* approx_kl, double* old_approx_kl, double* clip_fraction) {
-    ARG_CHECK(pol && cap >= 0, "policy_last_train_stats: null policy or negative capacity");
-    const size_t n = pol->stats_kl.size(), m = std::min(n, (size_t)cap);
-    if (epochs_run) *epochs_run = (int32_t)n;
-    if (stopped_early) *stopped_early = pol->stats_stopped;
-    for (size_t i = 0; i < m; ++i) {
-        if (approx_kl) approx_kl[i] = pol->stats_kl[i];
-        if (old_approx_kl) old_approx_kl[i] = pol->stats_old_kl[i];
-        if (clip_fraction) clip_fraction[i] = pol->stats_clip[i];
-    }
-    return PPO_OK;
-}
-
-// ================================================================ critic
-// A critic is a ppo_policy_t read as a state value (include/ppo_hip.h): the refusals every value entry point shares
-static int32_t value_checks(const char* who, ppo_policy_s* critic, int32_t F) {
-    if (critic->dtype != PPO_DTYPE_F32) {
-        ppo_set_error(std::string(who) + ": a bf16-dtype critic is not supported (the value modes exist in the fp32-MFMA forward only)");
-        return PPO_ERR_UNSUPPORTED;
-    }
-    if (critic->F != F) {
-        ppo_set_error(std::string(who) + ": the critic's input width F = " + std::to_string(critic->F) + " differs from the buffer's F = " + std::to_string(F));
-        return PPO_ERR_UNSUPPORTED;
-    }
-    return PPO_OK;
-}
-
-int32_t ppo_value_forward(ppo_policy_t critic, const int8_t* states, const uint32_t* active, int64_t B, int32_t H, float* values) {
-    ARG_CHECK(critic && states && active && values, "state_values: null argument");
-    ARG_CHECK(B >= 1, "state_values: empty batch");
-    if (H != 32 && H != 128) { ppo_set_error("value_forward: H must be 32 (Q=8) or 128 (Q=32) half-edges in this build"); return PPO_ERR_UNSUPPORTED; }
-    PPO_TRY(value_checks("value_forward", critic, critic->F));
-    DevBuf<int8_t> s; DevBuf<uint32_t> a; DevBuf<float> v;
-    const size_t ns = (size_t)B * H * critic->F;
-    PPO_TRY(s.alloc(ns)); PPO_TRY(a.alloc(B)); PPO_TRY(v.alloc(B));
-    PPO_TRY(h2d(s.p, states, ns)); PPO_TRY(h2d(a.p, active, (size_t)B));
-    PPO_TRY(launch_value_predict(critic, s.p, nullptr, a.p, nullptr, 0, B, H, v.p));
-    return d2h(values, v.p, (size_t)B);
-}
-
-// ro->values [T+1][N] on the device: rows 0 .. T-1 from the stored states (one launch, either storage form), row T from the
-// envs' current observation (zeros without an env)
-static int32_t compute_values_dev(const char* who, ppo_rollouts_s* ro, ppo_env_s* env, ppo_policy_s* critic) {
-    ARG_CHECK(ro->T >= 1, "compute_values: empty rollout buffer");
-    ARG_CHECK(ro->H == 32 || ro->H == 128, "compute_values: shape mismatch");
-    PPO_TRY(value_checks(who, critic, ro->F));
-    if (env) ARG_CHECK(ro->N == env->N && ro->H == env->H && ro->F == env->F, "compute_values: rollouts were created for another env shape");
-    const size_t n = (size_t)ro->T * ro->N;
-    PPO_TRY(ro->values.alloc((size_t)(ro->capT + 1) * ro->N));
-    PPO_TRY(launch_value_predict(critic, ro->compact ? nullptr : ro->states.p, ro->compact ? ro->cstate.p : nullptr, ro->active.p,
-                                 ro->tmpl.p, ro->V, (int64_t)n, ro->H, ro->values.p));
-    if (env) {
-        PPO_TRY(env->obs_tmp.alloc((size_t)env->N * env->H * env->F));
-        PPO_TRY(launch_env_observe(env, env->obs_tmp.p, nullptr));
-        PPO_TRY(launch_value_predict(critic, env->obs_tmp.p, nullptr, env->active.p, nullptr, 0, env->N, env->H, ro->values.p + n));
-    } else {
-        HIP_TRY(hipMemsetAsync(ro->values.p + n, 0, (size_t)ro->N * sizeof(float), g_stream));
-    }
-    ro->values_T = ro->T;
-    return PPO_OK;
-}
-
-int32_t ppo_rollouts_compute_values(ppo_rollouts_t ro, ppo_env_t env, ppo_policy_t critic, float* values_out) {
-    ARG_CHECK(ro && critic, "compute_values: null argument");
-    PPO_TRY(compute_values_dev("compute_values", ro, env, critic));
-    if (values_out) return d2h(values_out, ro->values.p, (size_t)(ro->T + 1) * ro->N);
-    HIP_TRY(hipStreamSynchronize(g_stream));
-    return PPO_OK;
-}
-
-int32_t ppo_rollouts_compute_gae_critic(ppo_rollouts_t ro, ppo_env_t env, ppo_policy_t critic, double gamma, double lambda,
-                                        float* adv_out, float* lambda_returns_out) {
-    ARG_CHECK(ro && critic, "compute_gae_critic: null argument");
-    PPO_TRY(compute_values_dev("compute_gae_critic", ro, env, critic));
-    const size_t n = (size_t)ro->T * ro->N;
-    PPO_TRY(ro->adv.alloc((size_t)ro->capT * ro->N)); PPO_TRY(ro->lam_ret.alloc((size_t)ro->capT * ro->N));
-    PPO_TRY(launch_gae_tn(ro->rewards.p, ro->done.p, ro->values.p, ro->adv.p, ro->lam_ret.p, ro->T, ro->N, gamma, lambda));
-    ro->adv_T = ro->T;
-    if (adv_out) PPO_TRY(d2h(adv_out, ro->adv.p, n));
-    if (lambda_returns_out) PPO_TRY(d2h(lambda_returns_out, ro->lam_ret.p, n));
-    HIP_TRY(hipStreamSynchronize(g_stream));
-    return PPO_OK;
-}
-
-// the regression target column [T][N] of a value-training call
-static int32_t value_target(ppo_rollouts_s* ro, int32_t target, const float** col) {
-    if (target != PPO_VTARGET_RETURNS && target != PPO_VTARGET_LAMBDA_RETURNS) { ppo_set_error("value target: unknown target"); return PPO_ERR_UNSUPPORTED; }
-    if (target == PPO_VTARGET_LAMBDA_RETURNS)
-        ARG_CHECK(ro->lam_ret.p && ro->adv_T == ro->T, "value target: lambda-returns mode needs ppo_rollouts_compute_gae on these rollouts first");
-    *col = target == PPO_VTARGET_RETURNS ? ro->returns.p : ro->lam_ret.p;
-    return PPO_OK;
-}
-
-int32_t ppo_rollouts_value_moments(ppo_rollouts_t ro, int32_t target, double* sums5) {
-    ARG_CHECK(ro && sums5, "value_moments: null argument");
-    ARG_CHECK(ro->T >= 1 && ro->len >= 1, "value_moments: empty rollout buffer");
-    ARG_CHECK(ro->values.p && ro->values_T == ro->T, "value_moments: needs ppo_rollouts_compute_values or ppo_rollouts_compute_gae on these rollouts first");
-    const float* col = nullptr;
-    PPO_TRY(value_target(ro, target, &col));
-    PPO_TRY(ro->stats_part.alloc(stats_part_doubles()));
-    PPO_TRY(launch_value_moments(col, ro->values.p, ro->valid.p, ro->index.p, ro->T * ro->N, ro->stats_part.p));
-    return d2h(sums5, ro->stats_part.p, 5);
-}
-
-// idx_dev: transition ids (already resolved through the dataset index)
-static int32_t value_forward_backward_dev(ppo_policy_s* critic, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B,
-                                          int64_t B_global, const float* target_col, ppo_adam_s* fuse_opt = nullptr,
-                                          float* fuse_hist2 = nullptr) {
-    PPO_TRY(train_reserve(critic, B * (ro->H / 32), ro->compact));
-    const ValueRoute r = value_route(critic->dtype, critic->F, critic->HID, critic->L, ro->H, ro->compact, B, ppo_knobs());
-    if (r.bwd == TrainBwd::None) { ppo_set_error(r.err); return PPO_ERR_UNSUPPORTED; }
-    if (r.bwd == TrainBwd::Small) {
-        const size_t frag = (size_t)critic->cap_tiles * (critic->HID / 32) * 1024;     // dZ in fragment order, like act1 / act2
-        PPO_TRY(critic->dz1f.alloc(frag));
-        if (critic->L >= 2) PPO_TRY(critic->dz2f.alloc(frag));
-        if (critic->L > 2) PPO_TRY(critic->dzm.alloc((size_t)(critic->L - 2) * frag));
-    }
-    PPO_TRY(launch_value_train_fwd(critic, ro, idx_dev, B, B_global, target_col));
-    switch (r.bwd) {
-    case TrainBwd::Small: PPO_TRY(launch_policy_bwd_small(critic, ro, idx_dev, B)); break;
-    case TrainBwd::X6: PPO_TRY(launch_policy_bwd_x6(critic, ro, idx_dev, B)); break;
-    default: PPO_TRY(launch_policy_bwd(critic, ro, idx_dev, B)); break;     // Fused
-    }
-    PPO_TRY(launch_grad_reduce(critic, B, B_global, 0.0, fuse_opt, fuse_hist2));
-    critic->last_B = B; critic->last_entropy_weight = 0.0;
-    return PPO_OK;
-}
-
-int32_t ppo_value_forward_backward(ppo_policy_t critic, ppo_rollouts_t ro, const int64_t* sample_idx, int64_t B,
-                                   int64_t B_global, int32_t target, double* loss_out) {
-    ARG_CHECK(critic && ro && sample_idx, "value_forward_backward: null argument");
-    ARG_CHECK(B >= 1 && B <= ro->len, "value_forward_backward: 1 <= batch_size <= num_data");
-    ARG_CHECK(B_global >= B, "value_forward_backward: B_global < B");
-    ARG_CHECK(ro->H == 32 || ro->H == 128, "value_forward_backward: shape mismatch");
-    PPO_TRY(value_checks("value_forward_backward", critic, ro->F));
-    const float* col = nullptr;
-    PPO_TRY(value_target(ro, target, &col));
-    for (int64_t i = 0; i < B; ++i) ARG_CHECK(sample_idx[i] >= 0 && sample_idx[i] < ro->len, "dataset index out of range (src/rollout_buffer.jl:105-106)");
-    PPO_TRY(train_reserve(critic, B * (ro->H / 32)));
-    DevBuf<int64_t> pos;
-    PPO_TRY(pos.alloc(B));
-    PPO_TRY(h2d(pos.p, sample_idx, (size_t)B));
-    hipLaunchKernelGGL(k_gather_index, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, g_stream, ro->index.p, pos.p, B,
-                       ro->len, critic->idx.p, critic->err.p);
-    HIP_TRY(hipGetLastError());
-    PPO_TRY(value_forward_backward_dev(critic, ro, critic->idx.p, B, B_global, col));
-    if (loss_out) {
-        float t = 0.0f;
-        PPO_TRY(d2h(&t, critic->grad.p + critic->np, 1));
-        *loss_out = t;
-    }
-    HIP_TRY(hipStreamSynchronize(g_stream));
-    return PPO_OK;
-}
-
-// ppo_train's epoch loop for the critic (single rank): same permutation keying, slices and histories
-int32_t ppo_value_train(ppo_policy_t critic, ppo_adam_t opt, ppo_rollouts_t ro, int64_t batch_size, int32_t num_epochs,
-                        int32_t target, const int64_t* perm, uint64_t seed, double* mse_hist, double* lr_hist) {
-    ARG_CHECK(critic && opt && ro && opt->pol == critic, "value_train: null/mismatched argument");
-    const int64_t len = ro->len;
-    ARG_CHECK(num_epochs >= 0, "value_train: bad epochs");
-    ARG_CHECK(ro->H == 32 || ro->H == 128, "value_train: shape mismatch");
-    PPO_TRY(value_checks("value_train", critic, ro->F));
-    const float* col = nullptr;
-    PPO_TRY(value_target(ro, target, &col));
-    ARG_CHECK(batch_size >= 1 && batch_size <= len, "1 <= batch_size <= num_data (src/train.jl:88)");
-    const int64_t nb = (len + batch_size - 1) / batch_size;
-    PPO_TRY(train_reserve(critic, batch_size * (ro->H / 32)));
-    DevBuf<int32_t> order; DevBuf<int64_t> permd; DevBuf<float> hist;
-    PPO_TRY(order.alloc(len));
-    if (perm) PPO_TRY(permd.alloc(len));
-    PPO_TRY(hist.alloc((size_t)nb * 2));
-    std::vector<float> hh((size_t)nb * 2);
-    for (int32_t ep = 0; ep < num_epochs; ++ep) {
-        if (perm) {
-            PPO_TRY(h2d(permd.p, perm + (size_t)ep * len, (size_t)len));
-            hipLaunchKernelGGL(k_perm_index, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, g_stream, ro->index.p,
-                               permd.p, len, order.p, critic->err.p);
-            HIP_TRY(hipGetLastError());
-        } else {
-            PPO_TRY(launch_feistel_index(ro->index.p, len, seed, (uint32_t)opt->epochs_done, order.p));
-        }
-        for (int64_t b = 0; b < nb; ++b) {                                          // last batch may be short
-            const int64_t start = b * batch_size;
-            const int64_t B = std::min(batch_size, len - start);
-            const bool fused = ppo_knobs().fuse_reduce_adam != 0;
-            PPO_TRY(value_forward_backward_dev(critic, ro, order.p + start, B, B, col, fused ? opt : nullptr, hist.p + 2 * b));
-            if (!fused) PPO_TRY(launch_adam(opt, hist.p + 2 * b));
-        }
-        opt->epochs_done += 1;
-        PPO_TRY(d2h(hh.data(), hist.p, (size_t)nb * 2));
-        double sm = 0.0;
-        for (int64_t i = 0; i < nb; ++i) sm += hh[2 * i];
-        if (mse_hist) mse_hist[ep] = sm / (double)nb;                               // unweighted mean over batches
-        if (lr_hist) lr_hist[ep] = opt->lr();
-    }
-    int32_t f = 0;
-    PPO_TRY(d2h(&f, critic->err.p, 1));
-    if (f) { ppo_set_error("AssertionError (device flag): permutation / dataset index out of range"); return PPO_ERR_DEVICE_FLAG; }
     return PPO_OK;
 }
 

@@ -32,8 +32,7 @@ struct DiskHeader { char magic[4]; uint32_t version; int64_t N; int32_t H, F, A,
 struct DiskTemplateTag { uint64_t tmpl_hash; int32_t env_kind; int32_t reserved; };
 static int32_t template_hash(const ppo_rollouts_s* ro, uint64_t* out) {
     std::vector<int8_t> t((size_t)ro->H * PPO_TPL);
-    HIP_TRY(hipMemcpyAsync(t.data(), ro->tmpl.p, t.size(), hipMemcpyDeviceToHost, ppo_stream()));
-    HIP_TRY(hipStreamSynchronize(ppo_stream()));
+    PPO_TRY(d2h(t.data(), ro->tmpl.p, t.size()));
     uint64_t h = 1469598103934665603ull;
     for (int8_t b : t) { h ^= (uint8_t)b; h *= 1099511628211ull; }
     *out = h;
@@ -375,8 +374,7 @@ int32_t disk_sink_finish(ppo_rollouts_s* ro) {
     // returns column (the reference rewrites trajectory.csv with the returns at this point)
     const size_t n = (size_t)ro->T * ro->N;
     std::vector<float> ret(n);
-    HIP_TRY(hipMemcpyAsync(ret.data(), ro->returns.p, n * 4, hipMemcpyDeviceToHost, ppo_stream()));
-    HIP_TRY(hipStreamSynchronize(ppo_stream()));
+    PPO_TRY(d2h(ret.data(), ro->returns.p, n));
     if (fseek(s->f, 0, SEEK_END) != 0 || fwrite(ret.data(), 4, n, s->f) != n) { ppo_set_error("DiskRollouts: returns write failed"); return PPO_ERR_ARG; }
     fclose(s->f); s->f = nullptr;
     return PPO_OK;

@@ -33,6 +33,22 @@ int ppo_hip_fail(hipError_t e, const char* what, const char* file, int line);
 #define PPO_TRY(expr)                                                        \
     do { int32_t _s = (expr); if (_s != PPO_OK) return _s; } while (0)
 
+// host <-> device copies on the engine's stream, complete on return
+template <typename T>
+inline int32_t h2d(T* dst, const T* src, size_t n) {
+    if (n == 0) return PPO_OK;
+    HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, ppo_stream()));
+    HIP_TRY(hipStreamSynchronize(ppo_stream()));
+    return PPO_OK;
+}
+template <typename T>
+inline int32_t d2h(T* dst, const T* src, size_t n) {
+    if (n == 0) return PPO_OK;
+    HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, ppo_stream()));
+    HIP_TRY(hipStreamSynchronize(ppo_stream()));
+    return PPO_OK;
+}
+
 // kernel timing registry (bench roofline leg)
 struct ProfScope {
     const char* name; hipEvent_t e0, e1; bool on;
@@ -133,7 +149,7 @@ struct ppo_policy_s {
     // probability ratios p_new(a|s) / p_old(a|s) of the train forward (ppo_policy_tail.h) and what ppo_train makes of them
     DevBuf<float> ratio;               // [cap_tiles] one minibatch (ppo_forward_backward / ppo_step_batch), minibatch order
     DevBuf<float> ratio_col;           // [len] one epoch of ppo_train: the minibatch at dataset position `start` writes at start
-    float* ratio_out = nullptr;        // where the next train forward stores them (forward_backward_dev sets it)
+    float* ratio_out = nullptr;        // where the next train forward stores them (train_pass_dev sets it)
     const float* ratio_last = nullptr; // what ppo_debug_train_ratios reads: the latest forward's, or the latest epoch's column
     int64_t ratio_last_n = 0;          // floats readable there
     DevBuf<double> stats_part;         // block partials of the two reductions, then their results (ppo_stats.hip)
@@ -293,19 +309,29 @@ struct PpoKnobs {
 };
 const PpoKnobs& ppo_knobs();
 
+// What one training pass minimises: the policy's clipped PPO loss with its entropy bonus, or a critic's (a ppo_policy_t
+// read as a state value) Flux.mse against a target column.  TrainObjective: the loss inputs of one pass
+enum class Objective { Policy, Value };
+struct TrainObjective {
+    Objective kind;
+    // Policy
+    double eps = 0.0, entropy_weight = 0.0;
+    int32_t adv_mode = PPO_ADV_RETURNS;
+    float* ratio_dst = nullptr;        // where the pass stores its probability ratios while a target_kl is set (nullptr: the
+                                       // policy's minibatch buffer)
+    // Value
+    const float* target_col = nullptr; // regression target indexed by transition id
+};
+
 // The kernels that run one training minibatch.  TrainTile runs forward, loss and backward-data in one launch and is
-// always followed by Wgrad (k_policy_wgrad<TR = true>).
+// always followed by Wgrad (k_policy_wgrad<TR = true>).  Objective::Value: the forward is always Fwd -- k_policy_fwd in a
+// value-train mode, the only forward with one -- followed by the backward the policy would take at that shape and size; where
+// that is the one-tile pass, whose weight-gradient kernel only runs from inside it, the three-product Small backward.
 enum class TrainFwd { None, TrainTile, X6S, X6T, X6, Split, Fwd, Bf16 };
 enum class TrainBwd { None, Wgrad, Small, X6, Fused, Bf16 };
 struct TrainRoute { TrainFwd fwd; TrainBwd bwd; const char* err; };      // err: why fwd is None
 // dtype: PPO_DTYPE_*; HID: kernel width (128 / 256); H: rows per state (32 / 128); states: minibatch size
-TrainRoute train_route(int32_t dtype, int F, int HID, int L, int H, bool compact, int64_t states, const PpoKnobs& k);
-
-// The critic's training pass (ppo_value_train): its forward is always k_policy_fwd in a value-train mode -- the only forward
-// with one -- followed by the backward train_route picks for the shape and size; where that is the one-tile pass, whose
-// weight-gradient kernel only runs from inside it, the three-product Small backward.  bwd == None: err says why.
-struct ValueRoute { TrainBwd bwd; const char* err; };
-ValueRoute value_route(int32_t dtype, int F, int HID, int L, int H, bool compact, int64_t states, const PpoKnobs& k);
+TrainRoute train_route(int32_t dtype, int F, int HID, int L, int H, bool compact, int64_t states, const PpoKnobs& k, Objective obj);
 
 // train-pass launchers: each launches what train_route chose and checks nothing else
 int32_t launch_policy_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B,

@@ -56,9 +56,7 @@ extern "C" int32_t ppo_philox4x32_10(const uint32_t* ctr4, const uint32_t* key2,
     HIP_TRY(hipMemcpyAsync(c.p, ctr4, (size_t)16 * n, hipMemcpyHostToDevice, ppo_stream()));
     hipLaunchKernelGGL(k_philox, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ppo_stream(), c.p, key2[0], key2[1], n, o.p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out4, o.p, (size_t)16 * n, hipMemcpyDeviceToHost, ppo_stream()));
-    HIP_TRY(hipStreamSynchronize(ppo_stream()));
-    return PPO_OK;
+    return d2h(out4, o.p, (size_t)4 * n);
 }
 
 extern "C" int32_t ppo_loss_with_entropy(const float* probs, const int64_t* lin_idx1, const float* p_old,
@@ -79,8 +77,7 @@ extern "C" int32_t ppo_loss_with_entropy(const float* probs, const int64_t* lin_
     hipLaunchKernelGGL(k_sum2, dim3(1), dim3(256), 0, st, terms.p, B, out.p);
     HIP_TRY(hipGetLastError());
     double h[2];
-    HIP_TRY(hipMemcpyAsync(h, out.p, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    PPO_TRY(d2h(h, out.p, 2));
     if (ppoloss) *ppoloss = -(h[0] / (double)B);
     if (entropyloss) *entropyloss = -(h[1] / (double)B);
     return PPO_OK;

@@ -684,25 +684,31 @@ int32_t launch_policy_rollout_persistent(ppo_policy_s* p, ppo_env_s* e, ppo_roll
     return PPO_OK;
 }
 
-// form: any TrainFwd but None and TrainTile (train_route)
-int32_t launch_policy_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B,
-                                int64_t B_global, double eps, double entropy_weight, const float* adv_col, TrainFwd form) {
-    FwdArgs a = {};
+// what both train forwards take from the workspace: the minibatch through idx, the saved activations, dL/dy and the loss terms
+static void fill_train(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global, FwdArgs& a) {
     fill_weights(p, a);
     a.states = ro->states.p; a.active = ro->active.p; a.idx = idx_dev; a.B = B;
     a.act1 = (float4*)p->act1.p; a.act2 = (float4*)p->act2.p; a.dY = (float4*)p->dY.p; a.loss_terms = p->loss_terms.p;
     for (int l = 0; l < 2; ++l)          // deep policies: the hidden layers between the first and the last
         a.act_mid[l] = (p->L > 2 && l < p->L - 2) ? (float4*)p->actm.p + (size_t)l * p->cap_tiles * (p->HID / 32) * 256 : nullptr;
-    a.actions = ro->actions.p; a.p_old = ro->p_sel.p; a.adv = adv_col; a.ratio_out = p->ratio_out;
-    a.eps = eps; a.c_over_B = (float)(entropy_weight / (double)B_global); a.inv_B = (float)(1.0 / (double)B_global);
-    ProfScope ps("k_policy_fwd_train");
-    if (ro->compact) {      // env snapshots instead of observation rows (MODE 4 / the CS form of the split kernel)
+    a.inv_B = (float)(1.0 / (double)B_global);
+    if (ro->compact) {      // env snapshots instead of observation rows: the rows are re-derived from them and left in p->xs
+                            // (minibatch order) for the backward
         a.states = nullptr; a.cstate = ro->cstate.p; a.xs_out = p->xs.p;
         a.env_tmpl = ro->tmpl.p; a.envV = ro->V; a.envQ = ro->V / 4; a.env_slots = 1;
     }
-    switch (form) {
+}
+
+// form: any TrainFwd but None and TrainTile (train_route)
+int32_t launch_policy_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B,
+                                int64_t B_global, double eps, double entropy_weight, const float* adv_col, TrainFwd form) {
+    FwdArgs a = {};
+    fill_train(p, ro, idx_dev, B, B_global, a);
+    a.actions = ro->actions.p; a.p_old = ro->p_sel.p; a.adv = adv_col; a.ratio_out = p->ratio_out;
+    a.eps = eps; a.c_over_B = (float)(entropy_weight / (double)B_global);
+    ProfScope ps("k_policy_fwd_train");
+    switch (form) {         // compact: MODE 4 / the CS form of the split kernel
     case TrainFwd::Split: return launch_policy_train_fwd_split(p, a, B, ro->compact);     // ppo_policy_fwd_split.hip
-    // compact: the rows are re-derived from the env snapshots and left in p->xs (minibatch order) for the backward
     case TrainFwd::Bf16: return launch_policy_fwd_bf16(p, a, ro->compact ? 4 : 2, B, ro->H / 32);
     case TrainFwd::Fwd: return ro->compact ? dispatch_fwd<4>(p, a, B, ro->H / 32) : dispatch_fwd<2>(p, a, B, ro->H / 32);
     default: return launch_policy_train_fwd_x6(p, a, B, form, ro->compact);               // ppo_policy_fwd_x6.hip
@@ -729,17 +735,10 @@ int32_t launch_value_predict(ppo_policy_s* p, const int8_t* states_dev, const in
 int32_t launch_value_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
                                const float* target_col) {
     FwdArgs a = {};
-    fill_weights(p, a);
-    a.states = ro->states.p; a.active = ro->active.p; a.idx = idx_dev; a.B = B;
-    a.act1 = (float4*)p->act1.p; a.act2 = (float4*)p->act2.p; a.dY = (float4*)p->dY.p; a.loss_terms = p->loss_terms.p;
-    for (int l = 0; l < 2; ++l)
-        a.act_mid[l] = (p->L > 2 && l < p->L - 2) ? (float4*)p->actm.p + (size_t)l * p->cap_tiles * (p->HID / 32) * 256 : nullptr;
-    a.vtarget = target_col; a.inv_B = (float)(1.0 / (double)B_global);
+    fill_train(p, ro, idx_dev, B, B_global, a);
+    a.vtarget = target_col;
     ProfScope ps("k_value_fwd_train");
-    if (!ro->compact) return dispatch_fwd<6>(p, a, B, ro->H / 32);
-    a.states = nullptr; a.cstate = ro->cstate.p; a.xs_out = p->xs.p;
-    a.env_tmpl = ro->tmpl.p; a.envV = ro->V; a.envQ = ro->V / 4; a.env_slots = 1;
-    return dispatch_fwd<8>(p, a, B, ro->H / 32);
+    return !ro->compact ? dispatch_fwd<6>(p, a, B, ro->H / 32) : dispatch_fwd<8>(p, a, B, ro->H / 32);
 }
 
 int32_t launch_categorical(const float* probs, const float* u, int64_t B, int64_t A, int32_t* actions, float* psel,

@@ -42,15 +42,23 @@ int32_t ppo_set_rollout_compact(int32_t mode) { g_knobs.rollout_compact = mode <
 int32_t ppo_set_rollout_split_max_envs(int64_t envs) { g_knobs.rollout_split_max_envs = envs < 0 ? g_start.rollout_split_max_envs : envs; return PPO_OK; }
 }  // extern "C"
 
-TrainRoute train_route(int32_t dtype, int F, int HID, int L, int H, bool compact, int64_t states, const PpoKnobs& k) {
-    const bool f32 = dtype == PPO_DTYPE_F32;
+TrainRoute train_route(int32_t dtype, int F, int HID, int L, int H, bool compact, int64_t states, const PpoKnobs& k, Objective obj) {
+    const bool f32 = dtype == PPO_DTYPE_F32, value = obj == Objective::Value;
     const int tps = H / 32;
     const int64_t tiles = states * tps;
     const bool split_images = F == 72 && L == 2;        // the policy holds the split-fp32 weight images (ppo_policy_create)
+    if (value) {                                        // what the fp32-MFMA forward refuses, before anything else
+        if (!f32) return {TrainFwd::None, TrainBwd::None, "a bf16-dtype critic is not supported: the value modes exist in the fp32-MFMA forward only"};
+        if (F != 72 && tps != 1) return {TrainFwd::None, TrainBwd::None, "unsupported policy/state shape (F,HID,H) for the gfx950 kernels"};
+        if (F != 72 && compact) return {TrainFwd::None, TrainBwd::None, "compact rollouts need the built-in env's F = 72"};
+    }
     // small minibatches: the whole training pass of a tile on one CU, then the weight gradients
-    if (tiles <= k.train_tile_max_tiles && f32 && split_images && H == 32 && !compact) return {TrainFwd::TrainTile, TrainBwd::Wgrad, nullptr};
+    if (tiles <= k.train_tile_max_tiles && f32 && split_images && H == 32 && !compact)
+        return value ? TrainRoute{TrainFwd::Fwd, TrainBwd::Small, nullptr} : TrainRoute{TrainFwd::TrainTile, TrainBwd::Wgrad, nullptr};
     TrainRoute r = {TrainFwd::None, TrainBwd::None, nullptr};
-    if (k.bwd_split && states <= k.fwd_x6_max_states && f32 && split_images && (tps == 1 || (tps == 4 && HID == 256))) {
+    if (value) {
+        r.fwd = TrainFwd::Fwd;
+    } else if (k.bwd_split && states <= k.fwd_x6_max_states && f32 && split_images && (tps == 1 || (tps == 4 && HID == 256))) {
         // Dense products as split-fp32 MFMAs: Q = 32 states one workgroup each, Q = 8 from the switch point two tiles per pass
         const int64_t t2 = k.fwd_x6_t2_min_tiles[HID == 256];
         r.fwd = tps == 4 ? TrainFwd::X6S : (t2 > 0 && tiles >= t2) ? TrainFwd::X6T : TrainFwd::X6;
@@ -77,24 +85,16 @@ TrainRoute train_route(int32_t dtype, int F, int HID, int L, int H, bool compact
     return r;
 }
 
-ValueRoute value_route(int32_t dtype, int F, int HID, int L, int H, bool compact, int64_t states, const PpoKnobs& k) {
-    const int tps = H / 32;
-    if (dtype != PPO_DTYPE_F32) return {TrainBwd::None, "a bf16-dtype critic is not supported: the value modes exist in the fp32-MFMA forward only"};
-    if (F != 72 && tps != 1) return {TrainBwd::None, "unsupported policy/state shape (F,HID,H) for the gfx950 kernels"};
-    if (F != 72 && compact) return {TrainBwd::None, "compact rollouts need the built-in env's F = 72"};
-    const TrainBwd b = train_route(dtype, F, HID, L, H, compact, states, k).bwd;
-    return {b == TrainBwd::Wgrad ? TrainBwd::Small : b, nullptr};
-}
-
-// diagnostic for the tests (not part of include/ppo_hip.h): the kernels train_route picks for a shape under the current
-// knobs, named as a kernel trace lists them demangled (first kernel of each half).  No HIP call.
-extern "C" int32_t ppo_debug_train_route(int32_t dtype, int32_t F, int32_t hid, int32_t L, int32_t H, int32_t compact,
-                                         int64_t states, char* fwd, char* bwd, int64_t cap) {
+// diagnostics for the tests (not part of include/ppo_hip.h): the kernels train_route picks for a shape and an objective under
+// the current knobs, named as a kernel trace lists them demangled (first kernel of each half).  No HIP call.
+static int32_t debug_route(const char* who, Objective obj, int32_t dtype, int32_t F, int32_t hid, int32_t L, int32_t H,
+                           int32_t compact, int64_t states, char* fwd, char* bwd, int64_t cap) {
     ARG_CHECK((dtype == PPO_DTYPE_F32 || dtype == PPO_DTYPE_BF16) && (F == 72 || F == 216) && (hid == 128 || hid == 256) && L >= 1 && L <= 4 && (H == 32 || H == 128) && states >= 1,
-              "ppo_debug_train_route: shape");
-    ARG_CHECK(fwd && bwd && cap >= 64, "ppo_debug_train_route: output buffers");
-    const TrainRoute r = train_route(dtype, F, hid, L, H, compact != 0, states, ppo_knobs());
-    const int tps = H / 32, mode = compact ? 4 : 2;
+              std::string(who) + ": shape");
+    ARG_CHECK(fwd && bwd && cap >= 64, std::string(who) + ": output buffers");
+    const TrainRoute r = train_route(dtype, F, hid, L, H, compact != 0, states, ppo_knobs(), obj);
+    // k_policy_fwd's train modes: 2 rows / 4 snapshots through idx; the value-train modes 6 / 8 likewise
+    const int tps = H / 32, mode = (obj == Objective::Value ? 6 : 2) + (compact ? 2 : 0);
     switch (r.fwd) {
     case TrainFwd::None: snprintf(fwd, cap, "none"); break;
     case TrainFwd::TrainTile: snprintf(fwd, cap, "k_policy_train_tile<72,%d>", hid); break;
@@ -118,20 +118,11 @@ extern "C" int32_t ppo_debug_train_route(int32_t dtype, int32_t F, int32_t hid, 
     return PPO_OK;
 }
 
-// the same for the critic's training pass (value_route): fwd is k_policy_fwd in value-train mode 6 (rows) or 8 (snapshots)
+extern "C" int32_t ppo_debug_train_route(int32_t dtype, int32_t F, int32_t hid, int32_t L, int32_t H, int32_t compact,
+                                         int64_t states, char* fwd, char* bwd, int64_t cap) {
+    return debug_route("ppo_debug_train_route", Objective::Policy, dtype, F, hid, L, H, compact, states, fwd, bwd, cap);
+}
 extern "C" int32_t ppo_debug_value_route(int32_t dtype, int32_t F, int32_t hid, int32_t L, int32_t H, int32_t compact,
                                          int64_t states, char* fwd, char* bwd, int64_t cap) {
-    ARG_CHECK((dtype == PPO_DTYPE_F32 || dtype == PPO_DTYPE_BF16) && (F == 72 || F == 216) && (hid == 128 || hid == 256) && L >= 1 && L <= 4 && (H == 32 || H == 128) && states >= 1,
-              "ppo_debug_value_route: shape");
-    ARG_CHECK(fwd && bwd && cap >= 64, "ppo_debug_value_route: output buffers");
-    const ValueRoute r = value_route(dtype, F, hid, L, H, compact != 0, states, ppo_knobs());
-    if (r.bwd == TrainBwd::None) { snprintf(fwd, cap, "none"); snprintf(bwd, cap, "none"); ppo_set_error(r.err); return PPO_ERR_UNSUPPORTED; }
-    snprintf(fwd, cap, "k_policy_fwd<%d,%d,%d,%d,%d>", F, hid, compact ? 8 : 6, H / 32, L != 2 ? 1 : 0);
-    switch (r.bwd) {
-    case TrainBwd::Small: snprintf(bwd, cap, "k_policy_bwd_data%s<%d,%d>", L == 2 ? "" : "_deep", F, hid); break;
-    case TrainBwd::X6: snprintf(bwd, cap, "k_policy_bwd_x6<72,%d>", hid); break;
-    case TrainBwd::Fused: snprintf(bwd, cap, "k_policy_bwd<%d,%d>", F, hid); break;
-    default: snprintf(bwd, cap, "none"); break;
-    }
-    return PPO_OK;
+    return debug_route("ppo_debug_value_route", Objective::Value, dtype, F, hid, L, H, compact, states, fwd, bwd, cap);
 }
