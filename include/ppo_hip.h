@@ -411,6 +411,34 @@ int32_t ppo_value_train(ppo_policy_t critic, ppo_adam_t opt, ppo_rollouts_t ro, 
  * Var(z) = sum z^2 / n - (sum z / n)^2, NaN when Var(x) == 0. */
 int32_t ppo_rollouts_value_moments(ppo_rollouts_t ro, int32_t target, double* sums5);
 
+/* ---------------------------------------------------------------- critic: PPO-clipped value loss
+ * No reference op: the value half of PPO's trust region (PPO2, CleanRL, Stable-Baselines3 clip_range_vf).  While a
+ * value_clip c is set on the critic handle, ppo_value_forward_backward and ppo_value_train minimise, instead of the mse,
+ *     sum_b max((V_b - t_b)^2, (Vclip_b - t_b)^2) / B_global,    Vclip = Vold + clamp(V - Vold, -c, c)
+ * (no factor 1/2: it continues Flux.mse), where Vold is the buffer's device value of that transition -- rows 0 .. T-1 of
+ * what ppo_rollouts_compute_values / _gae / _gae_critic left there, i.e. the values the critic had before the update.
+ * In fp32, with c = (float)value_clip: delta = V - Vold; a state is inside when |delta| <= c (decided on delta itself);
+ * outside, Vclip = Vold + copysign(c, delta), and the unclipped square is kept when |V - t| >= |Vclip - t| (a tie keeps it).
+ * A state whose clipped square is the larger one contributes (Vclip - t)^2 to the loss and exactly 0 to the gradient.
+ * value_clip: 0 = off (the default: gradients, losses and parameters are bit for bit those of the mse; nothing is
+ * allocated, stored, launched or copied), > 0 on, +inf = record the statistics and never clip (every state is inside: the
+ * mse bit for bit); negative or NaN: PPO_ERR_ARG.  A clip set on a buffer whose values are missing or stale (a collection
+ * since) is refused by both entry points before anything is launched: PPO_ERR_ARG, "value clipping needs
+ * ppo_rollouts_compute_values or ppo_rollouts_compute_gae on these rollouts first".
+ * Statistics: while the clip is set, ppo_value_train reduces every epoch's delta once, in fp64 and in a fixed order, to
+ *     clip_fraction  = mean(|delta| > c)
+ *     mean_sq_change = mean(delta^2)
+ * each transition entering with the parameters its own minibatch saw.  ppo_value_forward_backward applies the clip and
+ * stores no statistics.  Single rank like the critic; not persisted in checkpoints (like target_kl). */
+/* no reference op.  0 off; > 0 or +inf on; < 0 / NaN: PPO_ERR_ARG */
+int32_t ppo_policy_set_value_clip(ppo_policy_t critic, double clip);
+/* no reference op */
+int32_t ppo_policy_get_value_clip(ppo_policy_t critic, double* clip);
+/* no reference op.  Of the latest ppo_value_train on this handle: epochs_run and the first min(cap, epochs_run) entries
+ * of each per-epoch array (NaN for a call that ran with the clip off); every output may be NULL */
+int32_t ppo_policy_last_value_stats(ppo_policy_t critic, int32_t cap, int32_t* epochs_run, double* clip_fraction,
+                                    double* mean_sq_change);
+
 /* Native hook (the default of bench.py and DataParallel): the same all-reduce as ONE RCCL call made by the library
  * itself on the engine's stream -- no host-language callback per optimiser step.  RCCL is resolved with dlopen at first
  * use (a host that already carries an RCCL, e.g. torch, shares its copy).  The engine owns no rendezvous: the host

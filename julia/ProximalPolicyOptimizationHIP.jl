@@ -355,6 +355,28 @@ function value_train!(c::HipPolicy, optimizer, r::HipRollouts, batch_size, num_e
     mh, lh
 end
 
+# ---- PPO's clipped value loss (include/ppo_hip.h "critic: PPO-clipped value loss"; no reference op): with a clip c set on the
+# critic, value_forward_backward / value_train! minimise max((V - t)^2, (Vold + clamp(V - Vold, -c, c) - t)^2), Vold = the values
+# compute_values! / compute_gae_critic! left on the device (nothing / 0 = off, Inf = record the statistics only); value_train!
+# then keeps per epoch clip_fraction = mean(|V - Vold| > c) and mean_sq_change = mean((V - Vold)^2)
+function set_value_clip!(c::HipPolicy, clip)
+    check(ccall((:ppo_policy_set_value_clip, LIB), Int32, (Ptr{Cvoid}, Float64), c.h, clip === nothing ? 0.0 : Float64(clip)))
+end
+function value_clip(c::HipPolicy)
+    t = Ref{Float64}()
+    check(ccall((:ppo_policy_get_value_clip, LIB), Int32, (Ptr{Cvoid}, Ref{Float64}), c.h, t))
+    t[] == 0 ? nothing : t[]
+end
+function last_value_stats(c::HipPolicy)
+    n = Ref{Int32}()
+    check(ccall((:ppo_policy_last_value_stats, LIB), Int32, (Ptr{Cvoid}, Int32, Ref{Int32}, Ptr{Float64}, Ptr{Float64}),
+                c.h, Int32(0), n, C_NULL, C_NULL))
+    cf, ms = zeros(n[]), zeros(n[])
+    check(ccall((:ppo_policy_last_value_stats, LIB), Int32, (Ptr{Cvoid}, Int32, Ref{Int32}, Ptr{Float64}, Ptr{Float64}),
+                c.h, n[], n, cf, ms))
+    (epochs_run = Int(n[]), clip_fraction = cf, mean_sq_change = ms)
+end
+
 # 1 - Var(t - V) / Var(t) over the valid transitions, V = the values compute_values! / compute_gae_critic! left on the device
 function explained_variance(r::HipRollouts; target = :lambda_returns)
     s = zeros(5)

@@ -56,7 +56,7 @@ __all__ = [
     "permute_", "shuffle_", "single_trajectory_return", "smoothed_entropy", "clamped_entropy", "ppo_loss", "step_epoch_",
     "save_policy", "load_policy", "forward_backward",
     "HipCritic", "state_values", "batch_state_values", "compute_values_", "compute_gae_critic_", "value_forward_backward",
-    "value_train_", "pooled_state_value", "value_loss",
+    "value_train_", "pooled_state_value", "value_loss", "value_loss_clipped",
     "kl_stats", "explained_variance_", "explained_variance_from_sums",
 ]
 
@@ -389,6 +389,33 @@ class HipPolicy:
         return {"epochs_run": n.value, "stopped_early": bool(stopped.value), "approx_kl": list(kl),
                 "old_approx_kl": list(okl), "clip_fraction": list(cf)}
 
+    @property
+    def value_clip(self):
+        """For a handle that serves as a critic: None (off, the default: Flux.mse), or the range c of PPO's clipped value loss
+        max((V - t)^2, (V_old + clamp(V - V_old, -c, c) - t)^2) that value_forward_backward / value_train_ then minimise,
+        V_old being the values compute_values_ / compute_gae_critic_ / compute_gae_ left in the rollout buffer
+        (float("inf"): record the statistics, never clip).  With a clip set, ppo_iterate_ reports "value_clip_fraction"."""
+        c = C.c_double(0)
+        call("ppo_policy_get_value_clip", self._h, C.byref(c))
+        return None if c.value == 0.0 else c.value
+
+    @value_clip.setter
+    def value_clip(self, value):
+        c = 0.0 if value is None else float(value)
+        if not c >= 0.0:                                                  # NaN fails it too
+            raise PPOError(-1, "AssertionError: value_clip must be None (off), positive or float('inf')")
+        call("ppo_policy_set_value_clip", self._h, c)
+
+    def last_value_stats(self):
+        """Of the latest value_train_ on this handle: {"epochs_run", "clip_fraction", "mean_sq_change"}, the last two one entry
+        per epoch: the share of states whose value left [V_old - c, V_old + c] and the mean of (V - V_old)^2, each state with
+        the parameters its own minibatch saw (NaN when the call ran with value_clip = None)."""
+        n = C.c_int32(0)
+        call("ppo_policy_last_value_stats", self._h, 0, C.byref(n), None, None)
+        cf, ms = np.zeros(n.value, np.float64), np.zeros(n.value, np.float64)
+        call("ppo_policy_last_value_stats", self._h, n.value, C.byref(n), _p(cf, _lib.c_f64p), _p(ms, _lib.c_f64p))
+        return {"epochs_run": n.value, "clip_fraction": list(cf), "mean_sq_change": list(ms)}
+
     def grad_buffer_dev(self):
         ptr, n = C.c_void_p(), C.c_int64(0)
         call("ppo_policy_grad_buffer_dev", self._h, C.byref(ptr), C.byref(n))
@@ -481,6 +508,23 @@ def value_loss(values, targets):
     """Flux.mse(values, targets) in float32 arithmetic -> float."""
     d = np.asarray(values, np.float32) - np.asarray(targets, np.float32)
     return float(np.mean(d * d, dtype=np.float32))
+
+
+def value_loss_clipped(values, old_values, targets, clip):
+    """PPO's clipped value loss in float32 arithmetic, as the device forms it -> float: the mean of
+    max((V - t)^2, (Vclip - t)^2) with Vclip = V_old + clamp(V - V_old, -clip, clip); whether V left the range is decided on
+    V - V_old itself, and a tie of the two squares keeps the unclipped one.  clip None: value_loss."""
+    if clip is None:
+        return value_loss(values, targets)
+    v, vo, t = (np.asarray(x, np.float32) for x in (values, old_values, targets))
+    c = np.float32(clip)
+    delta = v - vo
+    with np.errstate(invalid="ignore"):
+        vc = vo + np.copysign(c, delta)
+        d, dc = v - t, vc - t
+        keep = (np.abs(delta) <= c) | (np.abs(d) >= np.abs(dc))
+    term = np.where(keep, d, dc).astype(np.float32)
+    return float(np.mean(term * term, dtype=np.float32))
 
 
 # ------------------------------------------------------------------ optimiser
@@ -1317,7 +1361,8 @@ def ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size,
     value_train_ on the lambda-returns for value_epochs (default epochs_per_iteration) epochs; loss gains "value".
     With policy.target_kl set (float("inf") to record without stopping) loss also gains "approx_kl" and "clip_fraction",
     one entry per epoch that ran, and with a critic "explained_variance", one per iteration, of the values the critic
-    had before that iteration's update."""
+    had before that iteration's update.  With critic.value_clip set, loss gains "value_clip_fraction", one entry per value
+    epoch."""
     loss = {"ppo": [], "entropy": [], "lr": []}
     stats = getattr(policy, "target_kl", None) is not None
     if stats:
@@ -1330,6 +1375,8 @@ def ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size,
         if state_data_path is not None:
             raise PPOError(-4, "a critic with disk-backed rollouts is not supported")
         loss["value"] = []
+        if getattr(critic, "value_clip", None) is not None:
+            loss["value_clip_fraction"] = []
     for it in range(1, num_ppo_iterations + 1):
         evaluator(policy, env, optimizer)                                                    # :181,226
         if verbose:
@@ -1350,6 +1397,8 @@ def ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size,
                                 epochs_per_iteration if value_epochs is None else value_epochs,
                                 target="lambda_returns", verbose=verbose)
             loss["value"] += v
+            if "value_clip_fraction" in loss:
+                loss["value_clip_fraction"] += critic.last_value_stats()["clip_fraction"]
         loss["ppo"] += p
         loss["entropy"] += e
         loss["lr"] += lr

@@ -124,6 +124,9 @@ SIGNATURES = {
     "ppo_policy_get_target_kl": [H, c_f64p],
     "ppo_policy_last_train_stats": [H, C.c_int32, c_i32p, c_i32p, c_f64p, c_f64p, c_f64p],
     "ppo_rollouts_value_moments": [H, C.c_int32, c_f64p],
+    "ppo_policy_set_value_clip": [H, C.c_double],
+    "ppo_policy_get_value_clip": [H, c_f64p],
+    "ppo_policy_last_value_stats": [H, C.c_int32, c_i32p, c_f64p, c_f64p],
     "ppo_rccl_probe": [],
     "ppo_rccl_unique_id": [C.c_void_p],
     "ppo_rccl_init": [C.c_int32, C.c_int32, C.c_void_p],

@@ -156,6 +156,11 @@ struct ppo_policy_s {
     double target_kl = 0.0;            // ppo_policy_set_target_kl: 0 off
     int32_t stats_stopped = 0;         // the latest ppo_train: ended by target_kl before num_epochs
     std::vector<double> stats_kl, stats_old_kl, stats_clip;   // ... and its per-epoch statistics (epochs that ran)
+    // critic: PPO's clipped value loss (ppo_policy_set_value_clip) and what ppo_value_train makes of V - vold
+    double value_clip = 0.0;           // 0 off; > 0 on; +inf: record the statistics, never clip
+    DevBuf<float> vdelta_col;          // [len] one epoch of ppo_value_train: the minibatch at dataset position `start` writes at start
+    int64_t vdelta_n = 0;              // floats ppo_debug_value_deltas may read there (the latest epoch's), 0: none
+    std::vector<double> vstats_clip, vstats_msq;   // the latest ppo_value_train, per epoch: clip_fraction, mean_sq_change
 };
 
 // one member of a Flux.Optimiser chain (ppo_optimiser_create) other than Adam, whose hyper-parameters and state are the
@@ -321,6 +326,10 @@ struct TrainObjective {
                                        // policy's minibatch buffer)
     // Value
     const float* target_col = nullptr; // regression target indexed by transition id
+    const float* vold_col = nullptr;   // clipped value loss: the values the critic had before the update, by transition id
+                                       // (train_pass_dev fills it and vclip from the critic handle and the buffer)
+    float vclip = 0.0f;                // ... and the clip range
+    float* vdelta_dst = nullptr;       // where the pass stores V - vold per state while the clip is set (nullptr: nowhere)
 };
 
 // The kernels that run one training minibatch.  TrainTile runs forward, loss and backward-data in one launch and is
@@ -338,11 +347,12 @@ int32_t launch_policy_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32
                                 int64_t B_global, double eps, double entropy_weight, const float* adv_col, TrainFwd form);
 int32_t launch_policy_bwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B);
 // critic (ppo_policy_fwd.hip value modes): state values of B stored states (rows, or snapshots when cstate_dev is given), and
-// the value-train forward of a minibatch against target_col (indexed by transition id)
+// the value-train forward of a minibatch against target_col (indexed by transition id); vold_col (likewise indexed, optional):
+// the clipped value loss with range vclip, V - vold of every state to vdelta_dst (optional, minibatch order)
 int32_t launch_value_predict(ppo_policy_s* p, const int8_t* states_dev, const int8_t* cstate_dev, const uint32_t* active_dev,
                              const int8_t* tmpl_dev, int32_t V, int64_t B, int32_t H, float* values_dev);
 int32_t launch_value_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
-                               const float* target_col);
+                               const float* target_col, const float* vold_col, float vclip, float* vdelta_dst);
 // the same fused backward with its row contractions (dW2, dW1) as split-fp32 products on the bf16 matrix pipe
 // (ppo_policy_bwd_x6.hip)
 int32_t launch_policy_bwd_x6(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B);
@@ -375,6 +385,8 @@ int32_t launch_categorical(const float* probs, const float* u, int64_t B, int64_
 // first 4 (ratio statistics: sum(-log r), sum((r - 1) - log r), count(|r - 1| > eps), n) resp. 5 (value moments) doubles
 size_t stats_part_doubles();
 int32_t launch_ratio_stats(const float* ratio, int64_t n, double eps, double* part);
+// value-clip statistics over n deltas V - vold: count(|delta| > c), sum delta^2, n in the first 3 doubles
+int32_t launch_value_clip_stats(const float* delta, int64_t n, float c, double* part);
 // over the transitions with valid[i] != 0 of [0, n): n, sum x, sum x^2, sum y, sum y^2 with x = t - t[i0], y = (t - v) - (t - v)[i0],
 // i0 = first_id[0] (a valid transition: the first of the dataset)
 int32_t launch_value_moments(const float* target, const float* values, const uint8_t* valid, const int32_t* first_id,

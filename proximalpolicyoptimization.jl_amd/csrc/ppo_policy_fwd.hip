@@ -52,12 +52,16 @@ static __device__ __forceinline__ void act_store_nt(float4* p, float4 v) {
 #endif
 // k_policy_fwd's MODE: 0 probabilities, 1 one rollout step, 2 train forward (rows gathered through idx), 3 persistent
 // rollout, 4 train forward from compact env snapshots (through idx); and the critic's (value_tail instead of policy_tail):
-// 5 value-predict on rows [B][H][F], 6 value-train (= 2), 7 value-predict on snapshots [B][2V], 8 value-train (= 4)
-constexpr bool fwd_mode_value(int m) { return m >= 5 && m <= 8; }
-constexpr bool fwd_mode_train(int m) { return m == 2 || m == 4 || m == 6 || m == 8; }    // saves activations, writes dY
-constexpr bool fwd_mode_gather(int m) { return m == 2 || m == 6; }                       // expanded rows through idx
-constexpr bool fwd_mode_snap(int m) { return m == 4 || m == 7 || m == 8; }               // one env snapshot per state in LDS
-constexpr bool fwd_mode_snap_idx(int m) { return m == 4 || m == 8; }                     // ... fetched through idx, rows -> xs_out
+// 5 value-predict on rows [B][H][F], 6 value-train (= 2), 7 value-predict on snapshots [B][2V], 8 value-train (= 4);
+// 9 / 10: 6 / 8 with PPO's clipped value loss (value_tail VMODE 2).  Own modes rather than a runtime test in the tail: with the
+// test, value_train_ at the headline shape measured 0.4 % more per iteration's critic part with the clip unset (the register
+// allocation of k_policy_fwd<72,256,6,1,0> moved), outside the range of the parent's own runs; 6 / 8 are now the parent's code
+constexpr bool fwd_mode_value(int m) { return m >= 5 && m <= 10; }
+constexpr bool fwd_mode_vclip(int m) { return m == 9 || m == 10; }
+constexpr bool fwd_mode_train(int m) { return m == 2 || m == 4 || m == 6 || m == 8 || fwd_mode_vclip(m); }   // saves activations, writes dY
+constexpr bool fwd_mode_gather(int m) { return m == 2 || m == 6 || m == 9; }             // expanded rows through idx
+constexpr bool fwd_mode_snap(int m) { return m == 4 || m == 7 || m == 8 || m == 10; }    // one env snapshot per state in LDS
+constexpr bool fwd_mode_snap_idx(int m) { return m == 4 || m == 8 || m == 10; }          // ... fetched through idx, rows -> xs_out
 
 template <int F, int HID>
 struct FwdCfg { static constexpr int WPS = (HID >= 256 || F > 128) ? 1 : PPO_FWD_WPS_SMALL; };
@@ -202,8 +206,9 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
         }
         const uint32_t act = (MODE == 3) ? *er.active : (SNAP ? act_next : a.active[sid]);
         // value-train: the target is fetched here, ahead of the activation stores it would otherwise queue behind (vmcnt)
-        float vtarget = 0.0f;
+        float vtarget = 0.0f, vold = 0.0f;
         if (VALUE && TRAIN) vtarget = a.vtarget[sid];
+        if (fwd_mode_vclip(MODE)) vold = a.vold[sid];                  // clipped value loss: the old value, likewise
         if (SNAP) fetch_snapshot(state + nwaves < a.B ? state + nwaves : state);      // lands under this state's MFMAs
         const uint32_t tick_val = (MODE == 3) ? *er.tick : ((MODE == 1) ? a.tick[state] : 0u);
         const int64_t out_index = (MODE == 3) ? tt * a.B + state : state;
@@ -448,7 +453,7 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
 
         FSTAMP(4);
         int sampled = 0;
-        if constexpr (VALUE) value_tail<TRAIN ? 1 : 0, TPS>(a, state, act, l, lane, j, h, out_index, vtarget);
+        if constexpr (VALUE) value_tail<fwd_mode_vclip(MODE) ? 2 : (TRAIN ? 1 : 0), TPS>(a, state, act, l, lane, j, h, out_index, vtarget, vold);
         else sampled = policy_tail<TMODE, TPS, false>(a, state, sid, act, l, lane, j, h, tick_val, out_index);
         if (MODE == 3) {
             // update!: the observed mask, then step!(env, a), reward, is_terminal (src/collect_rollouts.jl:9-14) and the
@@ -731,13 +736,16 @@ int32_t launch_value_predict(ppo_policy_s* p, const int8_t* states_dev, const in
 }
 
 // value-train forward of a minibatch: saves the activations like the policy's train forward, leaves dL/dy of
-// Flux.mse(V, target_col[idx]) in p->dY and the squared errors in p->loss_terms
+// Flux.mse(V, target_col[idx]) in p->dY and the squared errors in p->loss_terms; with vold_col the clipped value loss against
+// those old values (range vclip), the per-state V - vold going to vdelta_dst when given
 int32_t launch_value_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
-                               const float* target_col) {
+                               const float* target_col, const float* vold_col, float vclip, float* vdelta_dst) {
     FwdArgs a = {};
     fill_train(p, ro, idx_dev, B, B_global, a);
     a.vtarget = target_col;
+    a.vold = vold_col; a.vclip = vclip; a.vdelta_out = vold_col ? vdelta_dst : nullptr;
     ProfScope ps("k_value_fwd_train");
+    if (vold_col) return !ro->compact ? dispatch_fwd<9>(p, a, B, ro->H / 32) : dispatch_fwd<10>(p, a, B, ro->H / 32);
     return !ro->compact ? dispatch_fwd<6>(p, a, B, ro->H / 32) : dispatch_fwd<8>(p, a, B, ro->H / 32);
 }
 

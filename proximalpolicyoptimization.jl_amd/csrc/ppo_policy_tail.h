@@ -50,6 +50,10 @@ struct FwdArgs {
     // MODE 2, optional: ratio_out[state] = p_new(a|s) / p_old(a|s) of every state of the minibatch, the quotient the
     // surrogate forms (per-epoch KL / clip-fraction statistics, ppo_stats.hip).  Appended last, like the two above
     float* ratio_out;
+    // value-train, optional (PPO's clipped value loss, value_tail): vold = the values the critic had before the update,
+    // indexed by transition id like vtarget (nullptr: plain mse); vclip = the clip range; vdelta_out[state] = V - vold of
+    // every state of the minibatch (per-epoch value-clip statistics, ppo_stats.hip; nullptr: not stored).  Appended last
+    const float* vold; float vclip; float* vdelta_out;
 };
 
 // value of lane (lane ^ OFF), OFF < 32.  Same lane mapping as __shfl_xor (which hipcc lowers to ds_bpermute_b32: an
@@ -254,10 +258,17 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
 // VMODE 1 (train):   dY = dL/dy = 2 (V - target) / (B_global * n) on the n = 16 * active-quads outputs of active rows, exactly
 //                    0.0f on the others; loss_terms[state] = (-(V - target)^2, 0) -- the slab reduction's -(sum)/B_global
 //                    then leaves the mse where the policy's ppo loss goes.  target: the caller's early fetch (TailPre rule).
+// VMODE 2 (train, clipped; k_policy_fwd modes 9 / 10, chosen by the host while a value clip is set): the loss is PPO's clipped value loss
+//                    max((V - t)^2, (Vclip - t)^2), Vclip = vold + clamp(V - vold, -c, c), c = a.vclip, vold = the caller's
+//                    early fetch of a.vold[transition]: whether V left the range is decided on delta = V - vold itself
+//                    (vold + clamp(delta) need not reproduce V in fp32), a tie of the two squares keeps the unclipped one,
+//                    and a state whose clipped square is the larger one has dY exactly 0.0f on every row.  c = +inf: every
+//                    state is inside, the plain mse bit for bit.  a.vdelta_out (optional): delta per state of the minibatch.
 // A handful of adds, one division and the DPP butterfly: no exp / log, so the tail is short serial time for the workgroup.
 template <int VMODE, int TPS>
 __device__ __forceinline__ void value_tail(const FwdArgs& a, const int64_t state, const uint32_t act, const float (&l)[TPS][4],
-                                           const int lane, const int j, const int h, const int64_t out_index, const float target) {
+                                           const int lane, const int j, const int h, const int64_t out_index, const float target,
+                                           const float vold = 0.0f) {
     bool on[TPS];
     float s = 0.0f;
 #pragma unroll
@@ -275,7 +286,18 @@ __device__ __forceinline__ void value_tail(const FwdArgs& a, const int64_t state
         if (lane == 0) a.values_out[out_index] = v;
     } else {
         const float d = v - target;
-        const float g = nq ? ((2.0f * d) * a.inv_B) / n : 0.0f;
+        float term = d, delta = 0.0f;
+        bool keep = true;
+        if (VMODE == 2) {
+            const float c = a.vclip;
+            delta = v - vold;
+            const bool inside = fabsf(delta) <= c;
+            const float vc = vold + copysignf(c, delta);   // used only when !inside
+            const float dc = vc - target;
+            keep = inside || fabsf(d) >= fabsf(dc);        // the unclipped square is the larger one; a tie keeps it
+            term = keep ? d : dc;
+        }
+        const float g = (nq && keep) ? ((2.0f * d) * a.inv_B) / n : 0.0f;
         if (h == 0) {
 #pragma unroll
             for (int ts = 0; ts < TPS; ++ts) {
@@ -283,6 +305,9 @@ __device__ __forceinline__ void value_tail(const FwdArgs& a, const int64_t state
                 a.dY[((size_t)state * TPS + ts) * 32 + j] = make_float4(gi, gi, gi, gi);
             }
         }
-        if (lane == 0) { a.loss_terms[state * 2] = -((double)d * (double)d); a.loss_terms[state * 2 + 1] = 0.0; }
+        if (lane == 0) {
+            a.loss_terms[state * 2] = -((double)term * (double)term); a.loss_terms[state * 2 + 1] = 0.0;
+            if (VMODE == 2 && a.vdelta_out) a.vdelta_out[state] = delta;
+        }
     }
 }

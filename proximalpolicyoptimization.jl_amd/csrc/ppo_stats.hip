@@ -2,9 +2,11 @@
 // two losses and the learning rate only):
 //   k_ratio_stats    over the probability ratios r = p_new(a|s) / p_old(a|s) the loss tail stored (ppo_policy_tail.h):
 //                    sum(-log r), sum((r - 1) - log r), count(|r - 1| > eps), n  ->  old_approx_kl, approx_kl, clip_fraction
+//   k_value_clip_stats over the changes delta = V - V_old the critic's loss tail stored while a value clip is set:
+//                    count(|delta| > c), sum(delta^2), n  ->  clip_fraction, mean_sq_change
 //   k_value_moments  over the valid transitions of a rollout buffer: the five shifted sums behind the critic's explained
 //                    variance 1 - Var(t - V) / Var(t)
-// Both in fp64 with a FIXED summation order that depends on the element count only: every thread walks its 16-byte groups
+// All in fp64 with a FIXED summation order that depends on the element count only: every thread walks its 16-byte groups
 // in ascending order, a butterfly over the wave, the block's waves in order, the blocks in order (second launch, one wave:
 // lane l takes blocks l, l + 64, ... in order, then the butterfly).  No float atomics, so a second run repeats the first
 // bit for bit.  Bandwidth-trivial (4 bytes per transition), hence simple rather than tuned.
@@ -84,6 +86,29 @@ __global__ __launch_bounds__(STATS_THREADS) void k_ratio_stats(const float* __re
     block_sum_store<4>(acc, partials + (size_t)blockIdx.x * 4);
 }
 
+// c: the fp32 clip range the tail compared with, so that the count is the tail's own `inside` decision
+__device__ __forceinline__ void vclip_term(const float dl, const float c, double (&acc)[3]) {
+    const double dd = (double)dl;
+    acc[0] = acc[0] + (fabsf(dl) > c ? 1.0 : 0.0);
+    acc[1] = acc[1] + dd * dd;
+    acc[2] = acc[2] + 1.0;
+}
+
+// delta: 16-byte aligned
+__global__ __launch_bounds__(STATS_THREADS) void k_value_clip_stats(const float* __restrict__ delta, int64_t n, float c,
+                                                                    double* __restrict__ partials) {
+    double acc[3] = {0.0, 0.0, 0.0};
+    const int64_t n4 = n >> 2, total = (int64_t)gridDim.x * STATS_THREADS;
+    const int64_t g = (int64_t)blockIdx.x * STATS_THREADS + threadIdx.x;
+    for (int64_t q = g; q < n4; q += total) {
+        const float4 v = reinterpret_cast<const float4*>(delta)[q];
+        vclip_term(v.x, c, acc); vclip_term(v.y, c, acc); vclip_term(v.z, c, acc); vclip_term(v.w, c, acc);
+    }
+    const int64_t i = (n4 << 2) + g;                       // the n & 3 elements behind the last whole group
+    if (i < n) vclip_term(delta[i], c, acc);
+    block_sum_store<3>(acc, partials + (size_t)blockIdx.x * 3);
+}
+
 __device__ __forceinline__ void moment_term(const float t, const float v, const uint8_t on, const double st, const double sd,
                                             double (&acc)[5]) {
     if (!on) return;
@@ -121,6 +146,15 @@ int32_t launch_ratio_stats(const float* ratio, int64_t n, double eps, double* pa
     ProfScope ps("k_ratio_stats");
     hipLaunchKernelGGL(k_ratio_stats, dim3(blocks), dim3(STATS_THREADS), 0, ppo_stream(), ratio, n, eps, part + STATS_RESULT);
     hipLaunchKernelGGL(k_stats_finish<4>, dim3(1), dim3(64), 0, ppo_stream(), part + STATS_RESULT, blocks, part);
+    HIP_TRY(hipGetLastError());
+    return PPO_OK;
+}
+
+int32_t launch_value_clip_stats(const float* delta, int64_t n, float c, double* part) {
+    const int blocks = stats_blocks(n);
+    ProfScope ps("k_value_clip_stats");
+    hipLaunchKernelGGL(k_value_clip_stats, dim3(blocks), dim3(STATS_THREADS), 0, ppo_stream(), delta, n, c, part + STATS_RESULT);
+    hipLaunchKernelGGL(k_stats_finish<3>, dim3(1), dim3(64), 0, ppo_stream(), part + STATS_RESULT, blocks, part);
     HIP_TRY(hipGetLastError());
     return PPO_OK;
 }

@@ -57,7 +57,14 @@ static int32_t train_pass_dev(ppo_policy_s* net, ppo_rollouts_s* ro, const int32
         if (net->L >= 2) PPO_TRY(net->dz2f.alloc(frag));
         if (net->L > 2) PPO_TRY(net->dzm.alloc((size_t)(net->L - 2) * frag));
     }
-    if (!policy) PPO_TRY(launch_value_train_fwd(net, ro, idx_dev, B, B_global, obj.target_col));
+    if (!policy) {
+        // PPO's clipped value loss while the critic handle has a clip range: against the buffer's values of before the update
+        // (the callers have checked that they are there), V - vold going to the caller's slice of an epoch column if any
+        TrainObjective o = obj;
+        if (net->value_clip != 0.0) { o.vold_col = ro->values.p; o.vclip = (float)net->value_clip; }
+        else o.vdelta_dst = nullptr;
+        PPO_TRY(launch_value_train_fwd(net, ro, idx_dev, B, B_global, o.target_col, o.vold_col, o.vclip, o.vdelta_dst));
+    }
     else if (r.fwd == TrainFwd::TrainTile) PPO_TRY(launch_policy_train_tile(net, ro, idx_dev, B, B_global, obj.eps, obj.entropy_weight, adv));
     else PPO_TRY(launch_policy_train_fwd(net, ro, idx_dev, B, B_global, obj.eps, obj.entropy_weight, adv, r.fwd));
     switch (r.bwd) {
@@ -216,7 +223,8 @@ static int32_t sum_ratio_stats(double st[4], DevBuf<float>& sx, int32_t rank, in
 // The epoch loop of ppo_train and ppo_value_train, after their own argument checks: num_epochs passes over a fresh
 // permutation of the dataset in minibatches of batch_size, an optimiser step after each.  hist0 / hist1: per-epoch means of
 // the two per-batch loss columns (ppo and entropy loss; a critic's mse is column 0).  world > 1: data-parallel, through the
-// all-reduce hook.  Objective::Policy adds the per-epoch ratio statistics and the target_kl stop
+// all-reduce hook.  Objective::Policy adds the per-epoch ratio statistics and the target_kl stop, Objective::Value the per-epoch
+// value-clip statistics while the critic handle has a value clip
 static int32_t train_epochs(ppo_policy_s* net, ppo_adam_s* opt, ppo_rollouts_s* ro, const TrainObjective& obj, int64_t batch_size,
                             int32_t num_epochs, const int64_t* perm, uint64_t seed, int32_t rank, int32_t world,
                             ppo_allreduce_fn allreduce, void* allreduce_ctx, double* hist0, double* hist1, double* lr_hist) {
@@ -239,6 +247,17 @@ static int32_t train_epochs(ppo_policy_s* net, ppo_adam_s* opt, ppo_rollouts_s* 
     // train forward stores its ratios in its slice of one column, one reduction per epoch reads the column, its four sums come
     // back with the loss history.  target_kl == 0: nothing is stored, launched or copied, the statistics are NaN
     const bool policy = obj.kind == Objective::Policy;
+    // likewise for a critic while a value clip is set: V - vold of every minibatch in its slice of one column, one reduction per
+    // epoch (count(|delta| > c), sum delta^2, n).  value_clip == 0: nothing is allocated, stored, launched or copied
+    const bool vstats = !policy && net->value_clip != 0.0;
+    if (!policy) {
+        if (vstats) {
+            if (net->vdelta_col.n < (size_t)len) net->vdelta_n = 0;
+            PPO_TRY(net->vdelta_col.alloc((size_t)len));
+            PPO_TRY(net->stats_part.alloc(stats_part_doubles()));
+        }
+        net->vstats_clip.clear(); net->vstats_msq.clear();
+    }
     const double target_kl = policy ? net->target_kl : 0.0;
     const bool stats = target_kl != 0.0;
     DevBuf<float> sx;                                                  // the ranks' sums, three floats per double
@@ -269,6 +288,7 @@ static int32_t train_epochs(ppo_policy_s* net, ppo_adam_s* opt, ppo_rollouts_s* 
             const bool fused = ppo_knobs().fuse_reduce_adam && !allreduce && B > 0;
             TrainObjective o = obj;
             o.ratio_dst = stats ? net->ratio_col.p + start : nullptr;
+            o.vdelta_dst = vstats ? net->vdelta_col.p + start : nullptr;
             if (B > 0) PPO_TRY(train_pass_dev(net, ro, order.p + start, B, Bg, o, fused ? opt : nullptr, hist.p + 2 * b));
             else HIP_TRY(hipMemsetAsync(net->grad.p, 0, (size_t)(net->np + 2) * sizeof(float), ppo_stream()));   // shard exhausted
             if (allreduce) {                     // every rank of a data-parallel run; a world of 1 may pass it too
@@ -285,13 +305,22 @@ static int32_t train_epochs(ppo_policy_s* net, ppo_adam_s* opt, ppo_rollouts_s* 
             net->ratio_last = net->ratio_col.p; net->ratio_last_n = len;
             HIP_TRY(hipMemcpyAsync(st, net->stats_part.p, sizeof(st), hipMemcpyDeviceToHost, ppo_stream()));   // waited for just below
         }
+        double vst[3] = {NAN, NAN, 1.0};                                             // count(|delta| > c), sum delta^2, n
+        if (vstats) {
+            PPO_TRY(launch_value_clip_stats(net->vdelta_col.p, len, (float)net->value_clip, net->stats_part.p));
+            net->vdelta_n = len;
+            HIP_TRY(hipMemcpyAsync(vst, net->stats_part.p, sizeof(vst), hipMemcpyDeviceToHost, ppo_stream()));  // waited for just below
+        }
         PPO_TRY(d2h(hh.data(), hist.p, (size_t)nb * 2));
         double s0 = 0.0, s1 = 0.0;
         for (int64_t i = 0; i < nb; ++i) { s0 += hh[2 * i]; s1 += hh[2 * i + 1]; }
         if (hist0) hist0[ep] = s0 / (double)nb;                                     // unweighted mean over batches :127
         if (hist1) hist1[ep] = s1 / (double)nb;
         if (lr_hist) lr_hist[ep] = opt->lr();                                       // :144,155-158
-        if (!policy) continue;
+        if (!policy) {
+            net->vstats_clip.push_back(vst[0] / vst[2]); net->vstats_msq.push_back(vst[1] / vst[2]);
+            continue;
+        }
         if (world > 1 && target_kl > 0) PPO_TRY(sum_ratio_stats(st, sx, rank, world, allreduce, allreduce_ctx));
         const double kl = st[1] / st[3];
         net->stats_kl.push_back(kl); net->stats_old_kl.push_back(st[0] / st[3]); net->stats_clip.push_back(st[2] / st[3]);
@@ -349,6 +378,39 @@ int32_t ppo_policy_last_train_stats(ppo_policy_t pol, int32_t cap, int32_t* epoc
     return PPO_OK;
 }
 
+// ---- PPO's clipped value loss for a critic (no reference op): the clip range is a property of the handle
+int32_t ppo_policy_set_value_clip(ppo_policy_t critic, double clip) {
+    ARG_CHECK(clip >= 0.0, "policy_set_value_clip: value_clip must be 0 (off), positive or +inf");        // NaN fails it too
+    ARG_CHECK(critic, "policy_set_value_clip: null policy");
+    critic->value_clip = clip;
+    return PPO_OK;
+}
+int32_t ppo_policy_get_value_clip(ppo_policy_t critic, double* clip) {
+    ARG_CHECK(critic && clip, "policy_get_value_clip: null argument");
+    *clip = critic->value_clip;
+    return PPO_OK;
+}
+int32_t ppo_policy_last_value_stats(ppo_policy_t critic, int32_t cap, int32_t* epochs_run, double* clip_fraction,
+                                    double* mean_sq_change) {
+    ARG_CHECK(critic && cap >= 0, "policy_last_value_stats: null policy or negative capacity");
+    const size_t n = critic->vstats_clip.size(), m = std::min(n, (size_t)cap);
+    if (epochs_run) *epochs_run = (int32_t)n;
+    for (size_t i = 0; i < m; ++i) {
+        if (clip_fraction) clip_fraction[i] = critic->vstats_clip[i];
+        if (mean_sq_change) mean_sq_change[i] = critic->vstats_msq[i];
+    }
+    return PPO_OK;
+}
+
+// diagnostic for the tests (not part of include/ppo_hip.h), like ppo_debug_train_ratios: V - vold of every state of the latest
+// epoch of the latest ppo_value_train that ran with a value clip, in the order of that epoch's permutation (n up to the
+// dataset length)
+int32_t ppo_debug_value_deltas(ppo_policy_t critic, int64_t n, float* out) {
+    ARG_CHECK(critic && out, "ppo_debug_value_deltas: null argument");
+    ARG_CHECK(critic->vdelta_n > 0 && n >= 1 && n <= critic->vdelta_n, "ppo_debug_value_deltas: no deltas stored, or n out of range");
+    return d2h(out, critic->vdelta_col.p, (size_t)n);
+}
+
 // ================================================================ critic
 // A critic is a ppo_policy_t read as a state value (include/ppo_hip.h): the refusals every value entry point shares
 static int32_t value_checks(const char* who, ppo_policy_s* critic, int32_t F) {
@@ -360,6 +422,13 @@ static int32_t value_checks(const char* who, ppo_policy_s* critic, int32_t F) {
         ppo_set_error(std::string(who) + ": the critic's input width F = " + std::to_string(critic->F) + " differs from the buffer's F = " + std::to_string(F));
         return PPO_ERR_UNSUPPORTED;
     }
+    return PPO_OK;
+}
+
+// a value clip needs the values the critic had before the update: the buffer's, of these rollouts
+static int32_t value_clip_check(const ppo_policy_s* critic, const ppo_rollouts_s* ro) {
+    if (critic->value_clip == 0.0) return PPO_OK;
+    ARG_CHECK(ro->values.p && ro->values_T == ro->T, "value clipping needs ppo_rollouts_compute_values or ppo_rollouts_compute_gae on these rollouts first");
     return PPO_OK;
 }
 
@@ -449,6 +518,7 @@ int32_t ppo_value_forward_backward(ppo_policy_t critic, ppo_rollouts_t ro, const
     PPO_TRY(value_checks("value_forward_backward", critic, ro->F));
     TrainObjective obj = {Objective::Value};
     PPO_TRY(value_target(ro, target, &obj.target_col));
+    PPO_TRY(value_clip_check(critic, ro));
     DevBuf<int64_t> pos;
     PPO_TRY(gather_minibatch(critic, ro, sample_idx, B, pos));
     PPO_TRY(train_pass_dev(critic, ro, critic->idx.p, B, B_global, obj));
@@ -461,7 +531,8 @@ int32_t ppo_value_forward_backward(ppo_policy_t critic, ppo_rollouts_t ro, const
     return PPO_OK;
 }
 
-// the epoch loop for a critic (single rank): the handle's last_train_stats stay what the policy's ppo_train left
+// the epoch loop for a critic (single rank): the handle's last_train_stats stay what the policy's ppo_train left; its
+// last_value_stats are this call's
 int32_t ppo_value_train(ppo_policy_t critic, ppo_adam_t opt, ppo_rollouts_t ro, int64_t batch_size, int32_t num_epochs,
                         int32_t target, const int64_t* perm, uint64_t seed, double* mse_hist, double* lr_hist) {
     ARG_CHECK(critic && opt && ro && opt->pol == critic, "value_train: null/mismatched argument");
@@ -471,6 +542,7 @@ int32_t ppo_value_train(ppo_policy_t critic, ppo_adam_t opt, ppo_rollouts_t ro, 
     PPO_TRY(value_checks("value_train", critic, ro->F));
     TrainObjective obj = {Objective::Value};
     PPO_TRY(value_target(ro, target, &obj.target_col));
+    PPO_TRY(value_clip_check(critic, ro));
     ARG_CHECK(batch_size >= 1 && batch_size <= len, "1 <= batch_size <= num_data (src/train.jl:88)");
     return train_epochs(critic, opt, ro, obj, batch_size, num_epochs, perm, seed, 0, 1, nullptr, nullptr, mse_hist, nullptr, lr_hist);
 }

@@ -3,7 +3,8 @@
 minibatch 4096): iterations with and without a critic of the policy's shape, ALTERNATING in one process on one GPU, each
 ending in a device synchronise.  Without: collect + ppo_train_ (advantage = returns).  With: collect + compute_gae_critic_ +
 ppo_train_(advantage = "gae") + value_train_(target = "lambda_returns", same epochs).  Writes profiles/value_timing.json, or
-the file named third.  Usage: tools/value_timing.py [pairs] [hid] [out.json]"""
+the file named third.  A fourth argument sets critic.value_clip (PPO's clipped value loss and its per-epoch statistics).
+Usage: tools/value_timing.py [pairs] [hid] [out.json] [value_clip]"""
 import json, os, statistics, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,6 +19,9 @@ pol = PPO.HipPolicy(72, HID, 2, 4, seed=0)
 opt = PPO.Optimiser(PPO.Adam(3e-4))
 critic = PPO.HipCritic(72, HID, 2, seed=1)
 copt = PPO.Optimiser(PPO.Adam(1e-3))
+CLIP = float(sys.argv[4]) if len(sys.argv) > 4 else None
+if CLIP is not None:
+    critic.value_clip = CLIP
 
 
 def iteration(with_critic, it):
@@ -44,7 +48,7 @@ for i in range(PAIRS):
         times[w].append(iteration(w, i + 1))
 med = {w: statistics.median(v) for w, v in times.items()}
 out = {"workload": "%d envs x %d steps, Policy(72,%d,2,4) and a critic of the same shape, %d epochs, minibatch %d" % (N, T, HID, EPOCHS, MB),
-       "pairs": PAIRS, "without_critic_s": times[False], "with_critic_s": times[True],
+       "pairs": PAIRS, "value_clip": CLIP, "without_critic_s": times[False], "with_critic_s": times[True],
        "median_without_s": med[False], "median_with_s": med[True], "ratio": med[True] / med[False],
        "env_steps_per_s_without": N * T / med[False], "env_steps_per_s_with": N * T / med[True],
        "spread_without": (max(times[False]) - min(times[False])) / med[False]}
