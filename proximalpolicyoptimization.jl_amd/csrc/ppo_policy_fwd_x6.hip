@@ -245,29 +245,51 @@ __global__ __launch_bounds__(HID * 2, 4) void k_policy_fwd_train_x6(FwdArgs a, c
 // through both layers against ONE pass over its weight stream: every W1 / W2 piece fragment feeds T MFMAs.  T x 48 KB of H1
 // fragments: one workgroup per CU, two waves per SIMD; the T independent accumulator chains per wave stand in for the second
 // workgroup's latency hiding.
+// At HID = 256 the workgroup has T HELPER waves behind its NT compute waves (waves NT .. NT + T - 1; helper i serves tile i of
+// every pass).  What does not depend on the feature tile is theirs, once per tile instead of once per compute wave or as serial time:
+//   X image   the state rows of tile i of the NEXT pass: id through the scalar cache, row loads, int8 -> bf16 conversion and
+//             pack (exact), written to LDS as the ten B-operand fragments xb[i][s] of layer 1 in the compute waves' lane layout
+//             -- between barriers (1) and (2), under the compute waves' layer 2; the compute waves read them with ds_read_b128
+//   loss tail the wave-ordered sum of tile i's partial logits, + b3, policy_tail with inputs fetched one pass ahead -- behind
+//             barrier (2), beside the compute waves' layer 1 of the next pass
+// Every wave runs the same barriers: the prologue's and two per pass (the pass loop's bound is workgroup-uniform).  One image
+// and one sP buffer are enough: pass p's image is read between barrier (2) of pass p - 1 and barrier (1) of pass p and pass
+// p + 1's is written between barriers (1) and (2) of pass p; sP of pass p is read by the helpers between barrier (2) of pass
+// p and their barrier (1) of pass p + 1, and pass p + 1's partials are written behind that barrier.
+// HID = 128 (two workgroups per CU) measured level with helper waves (profiles/fwd_helper_waves_bench_parent_vs_branch.json) and
+// keeps the shape without them: every compute wave loads and converts the rows of both tiles, waves 0 and 1 run the tails.
 template <int HID, int T>
 struct FXTCfg {
     static constexpr int F = 72, NT = HID / 32, KS = HID / 16, K1 = 5;
+    static constexpr bool HELP = HID == 256;                               // helper waves: a compile-time choice per width
+    static constexpr int WAVES = NT + (HELP ? T : 0), THREADS = WAVES * 64; // compute waves + one helper wave per tile of a pass
     static constexpr size_t oFr = 0, szFr = (size_t)T * NT * 6 * 1024;
     static constexpr size_t oP = oFr + szFr, oW3 = oP + (size_t)T * NT * 1024, oB1 = oW3 + (size_t)2 * NT * 256,
-                            oB2 = oB1 + (size_t)NT * 128, total = oB2 + (size_t)NT * 128;
-    static_assert(total <= 160 * 1024, "LDS budget");
+                            oB2 = oB1 + (size_t)NT * 128, oX = oB2 + (size_t)NT * 128,                 // X image [T][K1][64 lanes][16 B]
+                            total = oX + (HELP ? (size_t)T * K1 * 1024 : 0);
+    static constexpr int WG_PER_CU = HID == 256 ? 1 : 2;
+    static_assert(total * WG_PER_CU <= 160 * 1024, "LDS budget");
+    static_assert(oX % 16 == 0, "ds_read_b128 / ds_write_b128 alignment of the X image");
 };
 
 template <int HID, int T>
-__global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, const uint4* __restrict__ w1x, const uint4* __restrict__ w2fx, int x_by_tile) {
+__global__ __launch_bounds__((FXTCfg<HID, T>::THREADS), (FXTCfg<HID, T>::WG_PER_CU)) void k_policy_fwd_train_x6t(FwdArgs a, const uint4* __restrict__ w1x, const uint4* __restrict__ w2fx, int x_by_tile) {
     using C = FXTCfg<HID, T>;
     constexpr int F = C::F, NT = C::NT, KS = C::KS, K1 = C::K1;
+    constexpr bool HELP = C::HELP;
     static_assert(T <= NT, "one tail wave per tile");
-    static_assert(T == 2, "two scalar id loads per pass; waves 0 and 1 run the tails");
+    static_assert(T == 2, "two scalar id loads per pass; two waves run the tails");
     extern __shared__ __attribute__((aligned(16))) char smem_c[];
     char* const frag = smem_c + C::oFr;                                    // [T][feature tile][k-step 2][piece 3][64 lanes][16 B]
     float4* const sP = reinterpret_cast<float4*>(smem_c + C::oP);          // [T][NT][64] layer-3 partial dots
     float4* const sW3p = reinterpret_cast<float4*>(smem_c + C::oW3);
     float4* const sB1 = reinterpret_cast<float4*>(smem_c + C::oB1);
     float4* const sB2 = reinterpret_cast<float4*>(smem_c + C::oB2);
+    uint4* const sX = reinterpret_cast<uint4*>(smem_c + C::oX);            // [T][K1][64] layer-1 B-operand fragments of the pass
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool helper = HELP && w >= NT;                                   // wave-uniform
+    const int hi = helper ? w - NT : 0;                                    // the helper's tile of every pass
 #ifdef PPO_FX6_STAMP
     unsigned long long st_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_t = clock64();
 #define FXSTAMP(i) do { unsigned long long _n = clock64(); st_sum[i] += _n - st_t; st_t = _n; } while (0)
@@ -276,14 +298,14 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
 #endif
     // b3 once per kernel (the loss tail adds it to every tile's logits)
     const float b3_0 = a.b3[0], b3_1 = a.b3[1], b3_2 = a.b3[2], b3_3 = a.b3[3];
-    for (int i = tid; i < 2 * NT * 16; i += NT * 64) sW3p[i] = a.w3p[i];
-    for (int i = tid; i < NT * 8; i += NT * 64) { sB1[i] = a.b1p[i]; sB2[i] = a.b2p[i]; }
-    __syncthreads();
-    const char* const w1s = reinterpret_cast<const char*>(w1x + (size_t)w * K1 * 3 * 64);
+    for (int i = tid; i < 2 * NT * 16; i += C::THREADS) sW3p[i] = a.w3p[i];
+    for (int i = tid; i < NT * 8; i += C::THREADS) { sB1[i] = a.b1p[i]; sB2[i] = a.b2p[i]; }
+    const char* const w1s = reinterpret_cast<const char*>(w1x + (size_t)w * K1 * 3 * 64);     // (compute waves only)
     const char* const w2s = reinterpret_cast<const char*>(w2fx + (size_t)w * KS * 3 * 64);
 
-    uint2 xr[T][K1];
-    auto load_x = [&](int i, int64_t rec, unsigned ln) {
+    // ---- helper waves: the state rows of the helper's tile as a lane's B-operand source, 8 int8 per k-step
+    uint2 xr[K1];
+    auto load_x = [&](int64_t rec, unsigned ln) {
         // every global access of this kernel: wave-uniform base in SGPRs + 32-bit lane offset (x_uniform_addr, ppo_x6.h); the
         // offsets are opaque so that they are not widened and folded into a 64-bit address per lane
         const uint64_t rb = x_uniform_addr(reinterpret_cast<const char*>(a.states) + (size_t)rec * 32 * F);
@@ -296,36 +318,120 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
             typedef unsigned u32x2l __attribute__((ext_vector_type(2)));
             const u32x2l vv = *x_gptr<const u32x2l>(rb, ro);
             const uint2 v = make_uint2(vv.x, vv.y);
-            xr[i][s] = pad ? make_uint2(0u, 0u) : v;
+            xr[s] = pad ? make_uint2(0u, 0u) : v;
+        }
+    };
+    // int8 -> bf16 (exact): the float of the byte, upper 16 bits; five lane-linear 16-byte LDS writes = the fragments xb[hi][s]
+    auto write_x = [&](unsigned ln) {
+        uint4* const dst = sX + (size_t)hi * K1 * 64;
+#pragma unroll
+        for (int s = 0; s < K1; ++s) {
+            float v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (float)(int)(int8_t)((e < 4 ? xr[s].x : xr[s].y) >> (8 * (e & 3)));
+            dst[s * 64 + ln] = make_uint4(x_perm(v[0], v[1]), x_perm(v[2], v[3]), x_perm(v[4], v[5]), x_perm(v[6], v[7]));
         }
     };
     // tile i of group g is g*T + i; a group that runs past the minibatch re-does the last tile and discards it
     auto tile_of = [&](int64_t g, int i) { const int64_t t = g * T + i; return t < a.B ? t : a.B - 1; };
-    // transition ids of a pass through the scalar cache, both in one wait (a vector load + readfirstlane waits on vmcnt(0), i.e.
-    // on every activation store and operand load the wave has in flight)
-    int cid[T] = {0, 0}, nid[T] = {0, 0};
-    auto sload_ids = [&](int64_t g, int (&id)[T]) {
+    // transition id of the helper's tile through the scalar cache (a vector load + readfirstlane waits on vmcnt(0), i.e. on
+    // every store and load the wave has in flight)
+    int cid = 0, nid = 0;
+    auto sload_id = [&](int64_t g, int& id) {
+        const int32_t* const ip = a.idx + tile_of(g, hi);
+        asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(id) : "s"(ip) : "memory");
+    };
+    // what the loss tail of a pass reads -- the active word, action, old probability and advantage of the helper's tile --
+    // requested one pass ahead, right behind that pass's state rows: vector loads, so they land with the rows (scalar loads
+    // would share lgkmcnt with the LDS traffic: the next LDS wait behind them would wait for their memory round trip).  The
+    // tail then has no memory round trip left
+    uint32_t tact = 0u, nact = 0u;
+    TailPre tpre = {0, 0.0f, 0.0f}, npre = {0, 0.0f, 0.0f};
+    auto load_tail_in = [&](const int id, uint32_t& act, TailPre& pre) {
+        act = a.active[id]; pre.ab = a.actions[id]; pre.po = a.p_old[id]; pre.adv = a.adv[id];
+    };
+    // ---- without helper waves: every compute wave holds the rows of both tiles and the ids; waves 0 and 1 the tail inputs
+    uint2 cxr[T][K1];
+    auto c_load_x = [&](int i, int64_t rec, unsigned ln) {
+        const uint64_t rb = x_uniform_addr(reinterpret_cast<const char*>(a.states) + (size_t)rec * 32 * F);
+        const unsigned row = (ln & 31u) * (unsigned)F + (ln >> 5) * 8u;
+#pragma unroll
+        for (int s = 0; s < K1; ++s) {
+            const bool pad = (s == K1 - 1) && (ln >> 5);
+            unsigned ro = row + (pad ? 0u : 16u * s);
+            asm volatile("" : "+v"(ro));
+            typedef unsigned u32x2l __attribute__((ext_vector_type(2)));
+            const u32x2l vv = *x_gptr<const u32x2l>(rb, ro);
+            const uint2 v = make_uint2(vv.x, vv.y);
+            cxr[i][s] = pad ? make_uint2(0u, 0u) : v;
+        }
+    };
+    // both ids of a pass in one wait
+    int ccid[T] = {0, 0}, cnid[T] = {0, 0};
+    auto c_sload_ids = [&](int64_t g, int (&id)[T]) {
         const int32_t* const ip0 = a.idx + tile_of(g, 0);
         const int32_t* const ip1 = a.idx + tile_of(g, 1);
         asm volatile("s_load_dword %0, %2, 0x0\n\ts_load_dword %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)"
                      : "=&s"(id[0]), "=&s"(id[1]) : "s"(ip0), "s"(ip1) : "memory");
     };
-    // what the loss tail of a pass reads -- the active word, action, old probability and advantage of the tile of wave w (waves
-    // >= T fetch tile 0's and never use them) -- requested one pass ahead, right behind that pass's state rows: vector loads, so
-    // they land with the rows, whose wait layer 2 pays anyway (scalar loads would share lgkmcnt with the LDS traffic: the next
-    // LDS wait behind them would wait for their memory round trip).  The tail then has no memory round trip left: before, it
-    // waited on idx (vmcnt(0), behind the H2 stores), then active, then actions / p_old / adv, then b3, one after another
-    uint32_t tact = 0u, nact = 0u;
-    TailPre tpre = {0, 0.0f, 0.0f}, npre = {0, 0.0f, 0.0f};
-    auto load_tail_in = [&](const int (&id)[T], uint32_t& act, TailPre& pre) {
-        const int32_t s = w == 1 ? id[1] : id[0];
-        act = a.active[s]; pre.ab = a.actions[s]; pre.po = a.p_old[s]; pre.adv = a.adv[s];
-    };
-    if ((int64_t)blockIdx.x * T < a.B) {
-        sload_ids(blockIdx.x, cid);
+    // (waves >= T fetch tile 0's tail inputs and never use them)
+    auto c_load_tail_in = [&](const int (&id)[T], uint32_t& act, TailPre& pre) { load_tail_in(w == 1 ? id[1] : id[0], act, pre); };
+    if (!HELP && (int64_t)blockIdx.x * T < a.B) {
+        c_sload_ids(blockIdx.x, ccid);
 #pragma unroll
-        for (int i = 0; i < T; ++i) load_x(i, x_by_tile ? tile_of(blockIdx.x, i) : (int64_t)cid[i], (unsigned)lane);
+        for (int i = 0; i < T; ++i) c_load_x(i, x_by_tile ? tile_of(blockIdx.x, i) : (int64_t)ccid[i], (unsigned)lane);
+        c_load_tail_in(ccid, tact, tpre);
+    }
+    if (helper && (int64_t)blockIdx.x * T < a.B) {                      // the first pass's image and tail inputs
+        sload_id(blockIdx.x, cid);
+        load_x(x_by_tile ? tile_of(blockIdx.x, hi) : (int64_t)cid, (unsigned)lane);
         load_tail_in(cid, tact, tpre);
+        write_x((unsigned)lane);
+    }
+    __syncthreads();
+#ifdef PPO_FX6_STAMP
+    // compute waves 0 and NT - 1 and helper wave NT: [workgroup][3][8]
+#define FXSTORE() do { if (a.stamps && lane == 0 && (w == 0 || w == NT - 1 || w == NT))   /* (no wave NT without helpers) */   \
+        for (int i = 0; i < 8; ++i) a.stamps[((size_t)blockIdx.x * 3 + (w == 0 ? 0 : w == NT - 1 ? 1 : 2)) * 8 + i] = st_sum[i]; } while (0)
+#else
+#define FXSTORE() do { } while (0)
+#endif
+    if (helper) {
+        // ================= helper wave: the barriers of the compute waves' pass loop below, one for one
+        for (int64_t g = blockIdx.x; g * T < a.B; g += gridDim.x) {
+            __syncthreads();                                            // (1) the compute waves have read the X image of pass g
+            FXSTAMP(0);
+            // the next pass's rows and tail inputs (the last pass re-does its own), requested first thing: under layer 2
+            const int64_t gn = ((g + gridDim.x) * T < a.B) ? g + gridDim.x : g;
+            X6F_LANE();
+            sload_id(gn, nid);
+            load_x(x_by_tile ? tile_of(gn, hi) : (int64_t)nid, ln);
+            load_tail_in(nid, nact, npre);
+            FXSTAMP(1);
+            write_x(ln);
+            FXSTAMP(2);
+            __syncthreads();                                            // (2) partial logits of pass g in LDS; the next image is written
+            FXSTAMP(3);
+            if (g * T + hi < a.B) {                                     // the loss tail of tile hi, beside the compute waves' next layer 1
+                // partial logits in wave (= feature tile) order, the two lane halves, b3; then the epilogue every forward shares
+                const int64_t tile = g * T + hi;
+                const float4* sPi = sP + (size_t)hi * NT * 64;
+                float4 s = sPi[ln];
+#pragma unroll
+                for (int u = 1; u < NT; ++u) { const float4 q4 = sPi[u * 64 + ln]; s.x += q4.x; s.y += q4.y; s.z += q4.z; s.w += q4.w; }
+                float l[1][4];
+                l[0][0] = (s.x + __shfl_xor(s.x, 32)) + b3_0;
+                l[0][1] = (s.y + __shfl_xor(s.y, 32)) + b3_1;
+                l[0][2] = (s.z + __shfl_xor(s.z, 32)) + b3_2;
+                l[0][3] = (s.w + __shfl_xor(s.w, 32)) + b3_3;
+                policy_tail<2, 1, false>(a, tile, cid, tact, l, (int)ln, j, h, 0u, 0, &tpre);
+            }
+            FXSTAMP(4);
+            cid = nid;
+            tact = nact; tpre = npre;
+        }
+        FXSTORE();
+        return;
     }
     for (int64_t g = blockIdx.x; g * T < a.B; g += gridDim.x) {
         // ================= layer 1: H1 tile w of the T states
@@ -347,11 +453,13 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
                 }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) accs[i][r] = 0.0f;
+                // the state rows as bf16 operand fragments: the helper waves' image of this pass
 #pragma unroll
                 for (int s = 0; s < K1; ++s) {
+                    if (HELP) { xb[i][s] = sX[(i * K1 + s) * 64 + ln]; continue; }
                     float v[8];
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = (float)(int)(int8_t)((e < 4 ? xr[i][s].x : xr[i][s].y) >> (8 * (e & 3)));
+                    for (int e = 0; e < 8; ++e) v[e] = (float)(int)(int8_t)((e < 4 ? cxr[i][s].x : cxr[i][s].y) >> (8 * (e & 3)));
                     xb[i][s] = make_uint4(x_perm(v[0], v[1]), x_perm(v[2], v[3]), x_perm(v[4], v[5]), x_perm(v[6], v[7]));
                 }
             }
@@ -412,17 +520,17 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
 #pragma unroll
             for (int q = 0; q < RD; ++q) ring[q] = *reinterpret_cast<const uint4*>(w2s + (lo + (unsigned)q * 1024u));
         }
-        {
+        if (!HELP) {                                                    // the next pass's rows and tail inputs (the last pass re-does its own)
             const int64_t gn = ((g + gridDim.x) * T < a.B) ? g + gridDim.x : g;
             unsigned ln2 = (unsigned)lane;
             asm volatile("" : "+v"(ln2));
-            sload_ids(gn, nid);
+            c_sload_ids(gn, cnid);
 #pragma unroll
-            for (int i = 0; i < T; ++i) load_x(i, x_by_tile ? tile_of(gn, i) : (int64_t)nid[i], ln2);
-            load_tail_in(nid, nact, npre);
+            for (int i = 0; i < T; ++i) c_load_x(i, x_by_tile ? tile_of(gn, i) : (int64_t)cnid[i], ln2);
+            c_load_tail_in(cnid, nact, npre);
         }
         FXSTAMP(2);
-        __syncthreads();                                                // (1) every layer-1 tile of the T states is in LDS
+        __syncthreads();                                                // (1) every layer-1 tile of the T states is in LDS; the X image is free
         FXSTAMP(3);
         // ================= layer 2
         {
@@ -503,29 +611,29 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6t(FwdArgs a, 
         FXSTAMP(5);
         __syncthreads();                                                // (2) partial logits in LDS; the H1 fragments are free
         FXSTAMP(6);
-        if (w < T && g * T + w < a.B) {                                 // wave i runs the loss tail of tile i
-            X6F_LANE();
-            const int64_t tile = g * T + w;
-            const int32_t sidw = w == 0 ? cid[0] : cid[1];
-            const float4* sPi = sP + (size_t)w * NT * 64;
-            float4 s = sPi[ln];
+        if (!HELP) {
+            if (w < T && g * T + w < a.B) {                             // wave i runs the loss tail of tile i
+                X6F_LANE();
+                const int64_t tile = g * T + w;
+                const int32_t sidw = w == 0 ? ccid[0] : ccid[1];
+                const float4* sPi = sP + (size_t)w * NT * 64;
+                float4 s = sPi[ln];
 #pragma unroll
-            for (int u = 1; u < NT; ++u) { const float4 q4 = sPi[u * 64 + ln]; s.x += q4.x; s.y += q4.y; s.z += q4.z; s.w += q4.w; }
-            float l[1][4];
-            l[0][0] = (s.x + __shfl_xor(s.x, 32)) + b3_0;
-            l[0][1] = (s.y + __shfl_xor(s.y, 32)) + b3_1;
-            l[0][2] = (s.z + __shfl_xor(s.z, 32)) + b3_2;
-            l[0][3] = (s.w + __shfl_xor(s.w, 32)) + b3_3;
-            policy_tail<2, 1, false>(a, tile, sidw, tact, l, (int)ln, j, h, 0u, 0, &tpre);
+                for (int u = 1; u < NT; ++u) { const float4 q4 = sPi[u * 64 + ln]; s.x += q4.x; s.y += q4.y; s.z += q4.z; s.w += q4.w; }
+                float l[1][4];
+                l[0][0] = (s.x + __shfl_xor(s.x, 32)) + b3_0;
+                l[0][1] = (s.y + __shfl_xor(s.y, 32)) + b3_1;
+                l[0][2] = (s.z + __shfl_xor(s.z, 32)) + b3_2;
+                l[0][3] = (s.w + __shfl_xor(s.w, 32)) + b3_3;
+                policy_tail<2, 1, false>(a, tile, sidw, tact, l, (int)ln, j, h, 0u, 0, &tpre);
+            }
+            FXSTAMP(7);
+            ccid[0] = cnid[0]; ccid[1] = cnid[1];
+            tact = nact; tpre = npre;
         }
-        FXSTAMP(7);
-        cid[0] = nid[0]; cid[1] = nid[1];
-        tact = nact; tpre = npre;
     }
-#ifdef PPO_FX6_STAMP
-    if (a.stamps && lane == 0 && (w == 0 || w == NT - 1))
-        for (int i = 0; i < 8; ++i) a.stamps[((size_t)blockIdx.x * 2 + (w ? 1 : 0)) * 8 + i] = st_sum[i];
-#endif
+    FXSTORE();
+#undef FXSTORE
 #undef FXSTAMP
 }
 
@@ -768,19 +876,19 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6s(FwdArgs a, 
 }
 
 #ifdef PPO_FX6_STAMP
-// diagnostic build (make -C csrc fxstamp, tools/fx6_stamps.py): per-phase clocks of k_policy_fwd_train_x6t, [workgroup][wave 0 / last][8]
+// diagnostic build (make -C csrc fxstamp, tools/fx6_stamps.py): per-phase clocks of k_policy_fwd_train_x6t, [workgroup][wave 0 / last compute / first helper][8]
 static unsigned long long* g_fx6_stamps = nullptr;
 extern "C" int32_t ppo_debug_fx6_stamps(unsigned long long* out) {
     if (!g_fx6_stamps) return -1;
     (void)hipDeviceSynchronize();
-    return hipMemcpy(out, g_fx6_stamps, 512 * 2 * 8 * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
+    return hipMemcpy(out, g_fx6_stamps, 512 * 3 * 8 * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
 }
 #endif
 
 // fp32 Policy(72, h, 2, 4); form X6S: Q = 32 states at HID = 256, X6T / X6: Q = 8 states (train_route)
 int32_t launch_policy_train_fwd_x6(ppo_policy_s* p, FwdArgs& a, int64_t B, TrainFwd form, bool compact) {
 #ifdef PPO_FX6_STAMP
-    if (!g_fx6_stamps) { (void)hipMalloc((void**)&g_fx6_stamps, 512 * 2 * 8 * 8); (void)hipMemset(g_fx6_stamps, 0, 512 * 2 * 8 * 8); }
+    if (!g_fx6_stamps) { (void)hipMalloc((void**)&g_fx6_stamps, 512 * 3 * 8 * 8); (void)hipMemset(g_fx6_stamps, 0, 512 * 3 * 8 * 8); }
     a.stamps = g_fx6_stamps;
 #endif
     if (compact) {
@@ -805,9 +913,9 @@ int32_t launch_policy_train_fwd_x6(ppo_policy_s* p, FwdArgs& a, int64_t B, Train
     } while (0)
     // Q = 32 states: one workgroup per state, its four tiles in two passes
     if (form == TrainFwd::X6S) LAUNCH((k_policy_fwd_train_x6s<256, 4>), (FXSCfg<256, 4>::total), B, 256, 512);
-    // two tiles per pass; HID = 128: 54 KB of LDS per workgroup, two (four-wave) workgroups per CU
-    else if (form == TrainFwd::X6T && p->HID == 256) LAUNCH((k_policy_fwd_train_x6t<256, 2>), (FXTCfg<256, 2>::total), (B + 1) / 2, 256, 512);
-    else if (form == TrainFwd::X6T) LAUNCH((k_policy_fwd_train_x6t<128, 2>), (FXTCfg<128, 2>::total), (B + 1) / 2, 512, 256);
+    // two tiles per pass; HID = 256: 8 compute + 2 helper waves; HID = 128: 59 KB of LDS per workgroup, two (four-wave) workgroups per CU
+    else if (form == TrainFwd::X6T && p->HID == 256) LAUNCH((k_policy_fwd_train_x6t<256, 2>), (FXTCfg<256, 2>::total), (B + 1) / 2, 256, (FXTCfg<256, 2>::THREADS));
+    else if (form == TrainFwd::X6T) LAUNCH((k_policy_fwd_train_x6t<128, 2>), (FXTCfg<128, 2>::total), (B + 1) / 2, 512, (FXTCfg<128, 2>::THREADS));
     else if (p->HID == 256) LAUNCH(k_policy_fwd_train_x6<256>, FXCfg<256>::total, B, 256 * FXCfg<256>::WG_PER_CU, 512);
     else LAUNCH(k_policy_fwd_train_x6<128>, FXCfg<128>::total, B, 256 * FXCfg<128>::WG_PER_CU, 256);
 #undef LAUNCH

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Diagnostic: per-phase cycle shares of k_policy_fwd_train_x6t (the two-tiles-per-pass split train forward; needs
-libppo_hip_fxstamp.so: make -C csrc fxstamp).  Shares only -- never quote this build's run time (stamps cost cycles).
+"""Diagnostic: per-phase cycle shares of k_policy_fwd_train_x6t (the two-tiles-per-pass split train forward: two compute waves
+and one of its two helper waves; needs libppo_hip_fxstamp.so: make -C csrc fxstamp).  Shares only -- never quote this build's run time (stamps cost cycles).
 usage: fx6_stamps.py [hid=256] [states=4096]"""
 import ctypes as C, os, sys
 import numpy as np
@@ -23,16 +23,20 @@ for _ in range(3):
     PPO.forward_backward(pol, ds, sel, 0.05, 0.01)
 groups = (nst + 1) // 2
 nwg = min(256 if hid == 256 else 512, groups)
-out = np.zeros(512 * 2 * 8, np.uint64)
+out = np.zeros(512 * 3 * 8, np.uint64)
 L.ppo_debug_fx6_stamps.argtypes = [C.c_void_p]
 assert L.ppo_debug_fx6_stamps(out.ctypes.data) == 0
-s = out[: nwg * 16].reshape(nwg, 2, 8).astype(np.float64)
+s = out[: nwg * 24].reshape(nwg, 3, 8).astype(np.float64)        # [workgroup][compute wave 0 / last compute wave / helper wave 0][8]
 passes = groups / nwg
-names = ["layer 1: X convert + 15 x 2 MFMAs", "H1 store, split, LDS fragments", "W2 ring fill + next X issue", "barrier 1",
-         "layer 2: hid/16 k-steps x 12 MFMAs", "H2 store + layer-3 partial dots", "barrier 2", "loss tail (waves 0, 1)"]
-for wv in (0, 1):
+helpers = s[:, 2, :].sum() > 0                                   # HID = 128 runs without helper waves: X and the tails on the compute waves
+compute = ["layer 1: X image read + 15 x 2 MFMAs" if helpers else "layer 1: X convert + 15 x 2 MFMAs", "H1 store, split, LDS fragments",
+           "W2 ring fill" if helpers else "W2 ring fill + next X issue", "barrier 1", "layer 2: hid/16 k-steps x 12 MFMAs",
+           "H2 store + layer-3 partial dots", "barrier 2", "(unused)" if helpers else "loss tail (waves 0, 1)"]
+helper = ["barrier 1 (after the previous tail)", "next id + row / tail-input load issue", "wait, convert, pack, X image write",
+          "barrier 2", "loss tail", "(unused)", "(unused)", "(unused)"]
+for wv, who, names in ((0, "compute wave 0", compute), (1, "last compute wave", compute), (2, "helper wave 0", helper))[: 3 if helpers else 2]:
     m = s[:, wv, :].mean(axis=0)
-    print("wave %s: total %.0f cycles/WG (%.0f per two-tile pass; MFMA issue of the SIMD's two waves: %d)" %
-          ("0" if wv == 0 else "last", m.sum(), m.sum() / passes, 2 * 2 * (15 + hid // 16 * 6) * 32))
+    print("%s: total %.0f cycles/WG (%.0f per two-tile pass; MFMA issue of a SIMD's two compute waves: %d)" %
+          (who, m.sum(), m.sum() / passes, 2 * 2 * (15 + hid // 16 * 6) * 32))
     for n, v in zip(names, m):
-        print("   %-36s %8.0f per pass  %5.1f %%" % (n, v / passes, 100 * v / m.sum()))
+        print("   %-40s %8.0f per pass  %5.1f %%" % (n, v / passes, 100 * v / m.sum()))
