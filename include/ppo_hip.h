@@ -380,7 +380,8 @@ int32_t ppo_policy_last_train_stats(ppo_policy_t pol, int32_t cap, int32_t* epoc
  * the 4 outputs of every half-edge row that belongs to an ACTIVE quad,
  *     V(s) = (sum over active rows r, outputs i of y[r][i]) / (4 * number of active rows),   0 when no quad is active,
  * trained with Flux.mse(V, target).  Parameters, gradient, optimiser chains and checkpoints are the policy's.  fp32 dtype
- * only (PPO_ERR_UNSUPPORTED for a bf16 critic, and for one whose F differs from the buffer's); single rank. */
+ * only (PPO_ERR_UNSUPPORTED for a bf16 critic, and for one whose F differs from the buffer's).  Data parallel through
+ * ppo_value_train_dp and ppo_rollouts_value_moments_shifts; the other entry points are local to their rank. */
 #define PPO_VTARGET_RETURNS 0         /* regress on the buffer's returns column                                     */
 #define PPO_VTARGET_LAMBDA_RETURNS 1  /* ... on the lambda-returns adv + V of the latest GAE call on these rollouts */
 /* values[b] = V(states[b]): host arrays in and out like ppo_policy_forward */
@@ -403,6 +404,17 @@ int32_t ppo_value_forward_backward(ppo_policy_t critic, ppo_rollouts_t ro, const
  * unweighted mean of the per-batch losses, lr_hist from the chain.  opt: any optimiser made for `critic`. */
 int32_t ppo_value_train(ppo_policy_t critic, ppo_adam_t opt, ppo_rollouts_t ro, int64_t batch_size, int32_t num_epochs,
                         int32_t target, const int64_t* perm, uint64_t seed, double* mse_hist, double* lr_hist);
+/* ppo_value_train across data-parallel ranks: rank / world / allreduce / allreduce_ctx as in ppo_train, with the same
+ * shard-length exchange, union minibatches, zero gradient from an exhausted shard and batch_size held against the
+ * shortest shard on every rank alike.  Every rank keeps a replica of the critic and of its optimiser; after the call the
+ * replicas are bit-identical and mse_hist is the GLOBAL history (each step's loss is the mean over the samples all ranks
+ * contributed to it).  ppo_value_train is this call with (0, 1, NULL, NULL).  While a value_clip is set and world > 1,
+ * the three sums behind the value-clip statistics are exchanged through the hook once per epoch (one more call,
+ * 9 * world floats) and added in rank order, so ppo_policy_last_value_stats is the same on every rank; value_clip must
+ * then be the same on every rank, like target_kl and num_epochs. */
+int32_t ppo_value_train_dp(ppo_policy_t critic, ppo_adam_t opt, ppo_rollouts_t ro, int64_t batch_size, int32_t num_epochs,
+                           int32_t target, const int64_t* perm, uint64_t seed, int32_t rank, int32_t world,
+                           ppo_allreduce_fn allreduce, void* allreduce_ctx, double* mse_hist, double* lr_hist);
 /* no reference op.  The sums behind the critic's explained variance, over the valid transitions of the buffer, with V =
  * rows 0 .. T-1 of the buffer's device values (ppo_rollouts_compute_values / _gae / _gae_critic first: PPO_ERR_ARG
  * otherwise) and t = the PPO_VTARGET_* column: sums5 = n, sum x, sum x^2, sum y, sum y^2 in fp64 and a fixed order, where
@@ -410,6 +422,11 @@ int32_t ppo_value_train(ppo_policy_t critic, ppo_adam_t opt, ppo_rollouts_t ro, 
  * so that a variance is not a difference of large numbers.  Explained variance = 1 - Var(y) / Var(x) with
  * Var(z) = sum z^2 / n - (sum z / n)^2, NaN when Var(x) == 0. */
 int32_t ppo_rollouts_value_moments(ppo_rollouts_t ro, int32_t target, double* sums5);
+/* no reference op.  ppo_rollouts_value_moments plus the two shifts its sums are relative to: shifts2 = t0, t0 - V0 (each
+ * from the two floats the reduction read).  Sums of different buffers have different shifts and cannot be added; with the
+ * shifts each buffer gives its own n, mean and sum of squared deviations of t and of t - V, which merge exactly
+ * (data-parallel shards: explained_variance_from_shards in the Python package). */
+int32_t ppo_rollouts_value_moments_shifts(ppo_rollouts_t ro, int32_t target, double* sums5, double* shifts2);
 
 /* ---------------------------------------------------------------- critic: PPO-clipped value loss
  * No reference op: the value half of PPO's trust region (PPO2, CleanRL, Stable-Baselines3 clip_range_vf).  While a
@@ -429,7 +446,7 @@ int32_t ppo_rollouts_value_moments(ppo_rollouts_t ro, int32_t target, double* su
  *     clip_fraction  = mean(|delta| > c)
  *     mean_sq_change = mean(delta^2)
  * each transition entering with the parameters its own minibatch saw.  ppo_value_forward_backward applies the clip and
- * stores no statistics.  Single rank like the critic; not persisted in checkpoints (like target_kl). */
+ * stores no statistics.  Across data-parallel ranks: ppo_value_train_dp.  Not persisted in checkpoints (like target_kl). */
 /* no reference op.  0 off; > 0 or +inf on; < 0 / NaN: PPO_ERR_ARG */
 int32_t ppo_policy_set_value_clip(ppo_policy_t critic, double clip);
 /* no reference op */

@@ -344,12 +344,22 @@ function value_forward_backward(c::HipPolicy, r::HipRollouts, idx::Vector{Int64}
                 c.h, r.h, idx .- 1, length(idx), B_global, VTARGET[target], loss))
     loss[]
 end
-function value_train!(c::HipPolicy, optimizer, r::HipRollouts, batch_size, num_epochs; target = :returns)
+# rank / world / hook as in ppo_train!: every rank trains its replica of the critic on its own shard, the loss history and the
+# value-clip statistics are the global ones
+function value_train!(c::HipPolicy, optimizer, r::HipRollouts, batch_size, num_epochs; target = :returns,
+                      rank = 0, world = 1, hook = C_NULL)
     oh = opt_handle(optimizer)
     mh, lh = zeros(num_epochs), zeros(num_epochs)
-    status = ccall((:ppo_value_train, LIB), Int32,
-                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Int64}, UInt64, Ptr{Float64}, Ptr{Float64}),
-                   c.h, oh, r.h, batch_size, num_epochs, VTARGET[target], C_NULL, SEED[], mh, lh)
+    status = if world == 1 && hook == C_NULL
+        ccall((:ppo_value_train, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Int64}, UInt64, Ptr{Float64}, Ptr{Float64}),
+              c.h, oh, r.h, batch_size, num_epochs, VTARGET[target], C_NULL, SEED[], mh, lh)
+    else
+        ccall((:ppo_value_train_dp, LIB), Int32,
+              (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Int32, Ptr{Int64}, UInt64, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid},
+               Ptr{Float64}, Ptr{Float64}),
+              c.h, oh, r.h, batch_size, num_epochs, VTARGET[target], C_NULL, SEED[], rank, world, hook, C_NULL, mh, lh)
+    end
     opt_done!(optimizer)
     check(status)
     mh, lh
@@ -384,6 +394,15 @@ function explained_variance(r::HipRollouts; target = :lambda_returns)
     var_t = s[3] / s[1] - (s[2] / s[1])^2
     var_d = s[5] / s[1] - (s[4] / s[1])^2
     var_t == 0 ? NaN : 1 - var_d / var_t
+end
+# one data-parallel rank's share of it: (n, mean t, M2 t, mean (t - V), M2 (t - V)), M2 = the sum of squared deviations.  The
+# host gathers the ranks' rows and merges them in rank order (Chan's pairwise formula) before forming 1 - M2_d / M2_t
+function value_moments_row(r::HipRollouts; target = :lambda_returns)
+    s, sh = zeros(5), zeros(2)
+    check(ccall((:ppo_rollouts_value_moments_shifts, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}),
+                r.h, VTARGET[target], s, sh))
+    n = s[1]
+    (n, sh[1] + s[2] / n, s[3] - s[2]^2 / n, sh[2] + s[4] / n, s[5] - s[4]^2 / n)
 end
 
 # ppo_iterate!(policy, env, optimizer, ...) (src/train.jl:210-249) then works unchanged once

@@ -409,7 +409,8 @@ class HipPolicy:
     def last_value_stats(self):
         """Of the latest value_train_ on this handle: {"epochs_run", "clip_fraction", "mean_sq_change"}, the last two one entry
         per epoch: the share of states whose value left [V_old - c, V_old + c] and the mean of (V - V_old)^2, each state with
-        the parameters its own minibatch saw (NaN when the call ran with value_clip = None)."""
+        the parameters its own minibatch saw (NaN when the call ran with value_clip = None).  After
+        value_train_(..., parallel=): over the states of all ranks, the same on every rank."""
         n = C.c_int32(0)
         call("ppo_policy_last_value_stats", self._h, 0, C.byref(n), None, None)
         cf, ms = np.zeros(n.value, np.float64), np.zeros(n.value, np.float64)
@@ -1118,12 +1119,54 @@ def explained_variance_from_sums(sums5):
     return float("nan") if var_t == 0.0 else 1.0 - var_d / var_t
 
 
-def explained_variance_(rollouts, target="lambda_returns"):
+def value_moments_row(sums5, shifts2):
+    """One shard's (n, mean t, M2 t, mean d, M2 d), d = t - V and M2 = the sum of squared deviations from the mean, in float64
+    from its shifted sums and its two shifts (ppo_rollouts_value_moments_shifts).  n == 0 gives a row of zeros."""
+    n, sx, sxx, sy, syy = (float(s) for s in sums5)
+    if n == 0.0:
+        return (0.0, 0.0, 0.0, 0.0, 0.0)
+    st, sd = (float(s) for s in shifts2)
+    return (n, st + sx / n, sxx - sx * sx / n, sd + sy / n, syy - sy * sy / n)
+
+
+def explained_variance_from_shards(rows):
+    """1 - Var(t - V) / Var(t) over the union of shards, from one value_moments_row per shard: merged in the order given with
+    the pairwise formula (Chan et al.), so every caller holding the same rows gets the same float.  A shard with n == 0 is
+    skipped; NaN when Var(t) == 0 or every shard is empty."""
+    n = mt = m2t = md = m2d = 0.0
+    for nb, mtb, m2tb, mdb, m2db in ((float(x) for x in r) for r in rows):
+        if nb == 0.0:
+            continue
+        tot = n + nb
+        dt, dd = mtb - mt, mdb - md
+        mt, md = mt + dt * (nb / tot), md + dd * (nb / tot)
+        m2t, m2d = m2t + m2tb + dt * dt * (n * nb / tot), m2d + m2db + dd * dd * (n * nb / tot)
+        n = tot
+    return float("nan") if n == 0.0 or m2t == 0.0 else 1.0 - m2d / m2t
+
+
+def explained_variance_(rollouts, target="lambda_returns", parallel=None):
     """The critic's explained variance over the valid transitions of the buffer, reduced on the device: V = the state
-    values compute_values_ / compute_gae_critic_ / compute_gae_ left there, target as in value_train_."""
+    values compute_values_ / compute_gae_critic_ / compute_gae_ left there, target as in value_train_.
+    parallel (a DataParallel with world > 1): over the union of every rank's buffer, collectively -- each rank's
+    value_moments_row is gathered exactly (a one-hot [world, 5] float64 tensor through DataParallel.allreduce_) and the rows
+    are merged in rank order, so every rank returns the same float."""
+    t = _value_target(target)
     s = np.zeros(5, np.float64)
-    call("ppo_rollouts_value_moments", rollouts._h, _value_target(target), _p(s, _lib.c_f64p))
-    return explained_variance_from_sums(s)
+    if parallel is None or parallel.world == 1:
+        call("ppo_rollouts_value_moments", rollouts._h, t, _p(s, _lib.c_f64p))
+        return explained_variance_from_sums(s)
+    import torch
+    import torch.distributed as dist
+    rows = np.zeros((parallel.world, 5), np.float64)
+    if len(rollouts):                                       # an empty shard joins the collective with a row of zeros
+        sh = np.zeros(2, np.float64)
+        call("ppo_rollouts_value_moments_shifts", rollouts._h, t, _p(s, _lib.c_f64p), _p(sh, _lib.c_f64p))
+        rows[parallel.rank] = value_moments_row(s, sh)
+    x = torch.from_numpy(rows)
+    host = dist.get_backend() == "gloo"                     # "nccl" (= RCCL) reduces device tensors only
+    x = parallel.allreduce_(x if host else x.cuda())
+    return explained_variance_from_shards(x.cpu().numpy())
 
 
 class BufferDataset:
@@ -1330,18 +1373,29 @@ def value_forward_backward(critic, dataset, batch_indices, target="returns", B_g
     return out.value
 
 
-def value_train_(critic, optimizer, dataset, batch_size, num_epochs, target="returns", perm=None, seed=0, verbose=True):
+def value_train_(critic, optimizer, dataset, batch_size, num_epochs, target="returns", perm=None, seed=0, verbose=True,
+                 parallel=None):
     """ppo_train_'s epoch loop for the critic -> (mse_history, lr_history).  optimizer: any Optimiser chain, bound to the
-    critic (not the one that trains the policy).  Single rank."""
+    critic (not the one that trains the policy).
+    parallel: as in ppo_train_ -- every rank holds a replica of the critic and of its optimiser and passes its own shard;
+    the replicas stay bit-identical, the mse history and critic.last_value_stats() are the global ones.  critic.value_clip
+    must be the same on every rank, like policy.target_kl and num_epochs."""
     t = _value_target(target)
     oh = optimizer._handle(critic)
     n = len(dataset)
     pp = _perm0(perm, num_epochs, n)
-    _check_batch_size(batch_size, n)
+    rank, world, fn, keep = 0, 1, _lib.ALLREDUCE_FN(0), None
+    if parallel is not None and (parallel.world > 1 or parallel.force_hook):
+        rank, world = parallel.rank, parallel.world
+        keep = parallel.make_hook(critic)
+        fn = keep
+    if world == 1:                                         # else inside ppo_value_train_dp, on the shortest shard (see ppo_train_)
+        _check_batch_size(batch_size, n)
     mh, lh = np.zeros(num_epochs, np.float64), np.zeros(num_epochs, np.float64)
     try:
-        call("ppo_value_train", critic._h, oh, dataset.rollouts._h, int(batch_size), int(num_epochs), t,
-             _p(pp, _lib.c_i64p) if pp is not None else None, int(seed), _p(mh, _lib.c_f64p), _p(lh, _lib.c_f64p))
+        call("ppo_value_train_dp", critic._h, oh, dataset.rollouts._h, int(batch_size), int(num_epochs), t,
+             _p(pp, _lib.c_i64p) if pp is not None else None, int(seed), int(rank), int(world), fn, None,
+             _p(mh, _lib.c_f64p), _p(lh, _lib.c_f64p))
     finally:
         optimizer._pull()
     if verbose:
@@ -1352,7 +1406,7 @@ def value_train_(critic, optimizer, dataset, batch_size, num_epochs, target="ret
 
 def ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size, num_ppo_iterations, evaluator,
                  epochs_per_iteration, discount, epsilon, entropy_weight, state_data_path=None, verbose=True, *,
-                 critic=None, critic_optimizer=None, gae_lambda=0.95, value_epochs=None):
+                 critic=None, critic_optimizer=None, gae_lambda=0.95, value_epochs=None, **options):
     """PPO.ppo_iterate! (src/train.jl:164-249), positional argument order preserved: 11 arguments = in-memory
     method, a 12th `state_data_path` = the disk method (rollouts through DiskRollouts, directory removed at
     the end, :198-201).
@@ -1362,7 +1416,14 @@ def ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size,
     With policy.target_kl set (float("inf") to record without stopping) loss also gains "approx_kl" and "clip_fraction",
     one entry per epoch that ran, and with a critic "explained_variance", one per iteration, of the values the critic
     had before that iteration's update.  With critic.value_clip set, loss gains "value_clip_fraction", one entry per value
-    epoch."""
+    epoch.
+    parallel (keyword only; the one name **options takes -- tests/test_value_host.py pins the set of named keywords): a
+    DataParallel.  `env` is then this rank's shard (DataParallel.env_shard, global_offset); ppo_train_, value_train_ and
+    explained_variance_ run across the ranks, so policy, critic and every list of the loss dict are the same on all of them.
+    The GAE and any advantage normalisation stay per rank.  None runs the single-process loop."""
+    parallel = options.pop("parallel", None)
+    if options:
+        raise TypeError("ppo_iterate_() got an unexpected keyword argument %r" % sorted(options)[0])
     loss = {"ppo": [], "entropy": [], "lr": []}
     stats = getattr(policy, "target_kl", None) is not None
     if stats:
@@ -1386,16 +1447,16 @@ def ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size,
         dataset = construct_dataset(rollouts)
         if critic is None:
             p, e, lr = ppo_train_(policy, optimizer, dataset, epsilon, minibatch_size, epochs_per_iteration,
-                                  entropy_weight, verbose=verbose)
+                                  entropy_weight, parallel=parallel, verbose=verbose)
         else:
             compute_gae_critic_(dataset.rollouts, env, critic, discount, gae_lambda, fetch=False)
             p, e, lr = ppo_train_(policy, optimizer, dataset, epsilon, minibatch_size, epochs_per_iteration,
-                                  entropy_weight, verbose=verbose, advantage="gae")
+                                  entropy_weight, parallel=parallel, verbose=verbose, advantage="gae")
             if stats:
-                loss["explained_variance"].append(explained_variance_(dataset.rollouts, "lambda_returns"))
+                loss["explained_variance"].append(explained_variance_(dataset.rollouts, "lambda_returns", parallel=parallel))
             v, _ = value_train_(critic, critic_optimizer, dataset, minibatch_size,
                                 epochs_per_iteration if value_epochs is None else value_epochs,
-                                target="lambda_returns", verbose=verbose)
+                                target="lambda_returns", verbose=verbose, parallel=parallel)
             loss["value"] += v
             if "value_clip_fraction" in loss:
                 loss["value_clip_fraction"] += critic.last_value_stats()["clip_fraction"]

@@ -120,10 +120,13 @@ SIGNATURES = {
     "ppo_rollouts_compute_gae_critic": [H, H, H, C.c_double, C.c_double, c_f32p, c_f32p],
     "ppo_value_forward_backward": [H, H, c_i64p, C.c_int64, C.c_int64, C.c_int32, c_f64p],
     "ppo_value_train": [H, H, H, C.c_int64, C.c_int32, C.c_int32, c_i64p, C.c_uint64, c_f64p, c_f64p],
+    "ppo_value_train_dp": [H, H, H, C.c_int64, C.c_int32, C.c_int32, c_i64p, C.c_uint64, C.c_int32, C.c_int32, ALLREDUCE_FN,
+                           C.c_void_p, c_f64p, c_f64p],
     "ppo_policy_set_target_kl": [H, C.c_double],
     "ppo_policy_get_target_kl": [H, c_f64p],
     "ppo_policy_last_train_stats": [H, C.c_int32, c_i32p, c_i32p, c_f64p, c_f64p, c_f64p],
     "ppo_rollouts_value_moments": [H, C.c_int32, c_f64p],
+    "ppo_rollouts_value_moments_shifts": [H, C.c_int32, c_f64p, c_f64p],
     "ppo_policy_set_value_clip": [H, C.c_double],
     "ppo_policy_get_value_clip": [H, c_f64p],
     "ppo_policy_last_value_stats": [H, C.c_int32, c_i32p, c_f64p, c_f64p],

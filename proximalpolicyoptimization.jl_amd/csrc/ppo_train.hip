@@ -195,12 +195,15 @@ static int32_t exchange_shard_lengths(std::vector<int64_t>& lens, int32_t rank, 
     return PPO_OK;
 }
 
-// every rank must take the same target_kl decision: gather all ranks' ratio sums EXACTLY (a one-hot [world][4][3] vector
-// through the hook's sum, each double as three floats whose sum it is) and add them in rank order.  sx: [12 * world]
-static int32_t sum_ratio_stats(double st[4], DevBuf<float>& sx, int32_t rank, int32_t world, ppo_allreduce_fn allreduce, void* allreduce_ctx) {
-    std::vector<float> hx((size_t)12 * world, 0.0f);
-    for (int q = 0; q < 4; ++q) {
-        float* d = hx.data() + 12 * (size_t)rank + 3 * q;
+// every rank must hold the same per-epoch statistics (and take the same target_kl decision): gather all ranks' k sums EXACTLY
+// (a one-hot [world][k][3] vector through the hook's sum, each double as three floats whose sum it is) and add them in rank
+// order.  sx: [3 * k * world]; what: the statistics' name for the error text
+static int32_t sum_rank_sums(double* st, int k, DevBuf<float>& sx, int32_t rank, int32_t world, ppo_allreduce_fn allreduce,
+                             void* allreduce_ctx, const char* what) {
+    const size_t row = (size_t)3 * k;
+    std::vector<float> hx(row * world, 0.0f);
+    for (int q = 0; q < k; ++q) {
+        float* d = hx.data() + row * (size_t)rank + 3 * q;
         d[0] = (float)st[q];
         if (std::isfinite(st[q]) && std::isfinite(d[0])) {
             const double r1 = st[q] - (double)d[0];
@@ -208,12 +211,12 @@ static int32_t sum_ratio_stats(double st[4], DevBuf<float>& sx, int32_t rank, in
         }
     }
     PPO_TRY(h2d(sx.p, hx.data(), hx.size()));
-    if (allreduce(allreduce_ctx, sx.p, 12 * (int64_t)world) != 0) { ppo_set_error("all-reduce hook failed (ratio statistics)"); return PPO_ERR_ARG; }
+    if (allreduce(allreduce_ctx, sx.p, (int64_t)hx.size()) != 0) { ppo_set_error(std::string("all-reduce hook failed (") + what + ")"); return PPO_ERR_ARG; }
     PPO_TRY(d2h(hx.data(), sx.p, hx.size()));
-    for (int q = 0; q < 4; ++q) {
+    for (int q = 0; q < k; ++q) {
         st[q] = 0.0;
         for (int32_t r = 0; r < world; ++r) {
-            const float* d = hx.data() + 12 * (size_t)r + 3 * q;
+            const float* d = hx.data() + row * (size_t)r + 3 * q;
             st[q] += ((double)d[0] + (double)d[1]) + (double)d[2];
         }
     }
@@ -224,7 +227,7 @@ static int32_t sum_ratio_stats(double st[4], DevBuf<float>& sx, int32_t rank, in
 // permutation of the dataset in minibatches of batch_size, an optimiser step after each.  hist0 / hist1: per-epoch means of
 // the two per-batch loss columns (ppo and entropy loss; a critic's mse is column 0).  world > 1: data-parallel, through the
 // all-reduce hook.  Objective::Policy adds the per-epoch ratio statistics and the target_kl stop, Objective::Value the per-epoch
-// value-clip statistics while the critic handle has a value clip
+// value-clip statistics while the critic handle has a value clip; with world > 1 either kind is summed over the ranks
 static int32_t train_epochs(ppo_policy_s* net, ppo_adam_s* opt, ppo_rollouts_s* ro, const TrainObjective& obj, int64_t batch_size,
                             int32_t num_epochs, const int64_t* perm, uint64_t seed, int32_t rank, int32_t world,
                             ppo_allreduce_fn allreduce, void* allreduce_ctx, double* hist0, double* hist1, double* lr_hist) {
@@ -258,9 +261,10 @@ static int32_t train_epochs(ppo_policy_s* net, ppo_adam_s* opt, ppo_rollouts_s* 
         }
         net->vstats_clip.clear(); net->vstats_msq.clear();
     }
+    DevBuf<float> sx;                                                  // the ranks' sums, three floats per double
+    if (world > 1 && vstats) PPO_TRY(sx.alloc((size_t)9 * world));
     const double target_kl = policy ? net->target_kl : 0.0;
     const bool stats = target_kl != 0.0;
-    DevBuf<float> sx;                                                  // the ranks' sums, three floats per double
     if (policy) {
         if (stats) {
             if (net->ratio_col.n < (size_t)len) { net->ratio_last = nullptr; net->ratio_last_n = 0; }
@@ -318,10 +322,11 @@ static int32_t train_epochs(ppo_policy_s* net, ppo_adam_s* opt, ppo_rollouts_s* 
         if (hist1) hist1[ep] = s1 / (double)nb;
         if (lr_hist) lr_hist[ep] = opt->lr();                                       // :144,155-158
         if (!policy) {
+            if (world > 1 && vstats) PPO_TRY(sum_rank_sums(vst, 3, sx, rank, world, allreduce, allreduce_ctx, "value-clip statistics"));
             net->vstats_clip.push_back(vst[0] / vst[2]); net->vstats_msq.push_back(vst[1] / vst[2]);
             continue;
         }
-        if (world > 1 && target_kl > 0) PPO_TRY(sum_ratio_stats(st, sx, rank, world, allreduce, allreduce_ctx));
+        if (world > 1 && target_kl > 0) PPO_TRY(sum_rank_sums(st, 4, sx, rank, world, allreduce, allreduce_ctx, "ratio statistics"));
         const double kl = st[1] / st[3];
         net->stats_kl.push_back(kl); net->stats_old_kl.push_back(st[0] / st[3]); net->stats_clip.push_back(st[2] / st[3]);
         if (target_kl > 0 && !(kl <= target_kl)) {          // Inf and NaN stop too; this epoch's updates stay applied
@@ -509,6 +514,22 @@ int32_t ppo_rollouts_value_moments(ppo_rollouts_t ro, int32_t target, double* su
     return d2h(sums5, ro->stats_part.p, 5);
 }
 
+// the same sums with the two shifts k_value_moments took them relative to, so that shards can be merged: t[i0] and
+// t[i0] - V[i0], i0 = the first transition of the dataset, read back as the two floats the kernel read
+int32_t ppo_rollouts_value_moments_shifts(ppo_rollouts_t ro, int32_t target, double* sums5, double* shifts2) {
+    ARG_CHECK(shifts2, "value_moments: null argument");
+    PPO_TRY(ppo_rollouts_value_moments(ro, target, sums5));
+    const float* col = nullptr;
+    PPO_TRY(value_target(ro, target, &col));
+    int32_t i0 = 0;
+    float t0 = 0.0f, v0 = 0.0f;
+    PPO_TRY(d2h(&i0, ro->index.p, 1));
+    ARG_CHECK(i0 >= 0 && (int64_t)i0 < ro->T * ro->N, "value_moments: dataset index out of range");
+    PPO_TRY(d2h(&t0, col + i0, 1)); PPO_TRY(d2h(&v0, ro->values.p + i0, 1));
+    shifts2[0] = (double)t0; shifts2[1] = (double)t0 - (double)v0;
+    return PPO_OK;
+}
+
 int32_t ppo_value_forward_backward(ppo_policy_t critic, ppo_rollouts_t ro, const int64_t* sample_idx, int64_t B,
                                    int64_t B_global, int32_t target, double* loss_out) {
     ARG_CHECK(critic && ro && sample_idx, "value_forward_backward: null argument");
@@ -531,20 +552,28 @@ int32_t ppo_value_forward_backward(ppo_policy_t critic, ppo_rollouts_t ro, const
     return PPO_OK;
 }
 
-// the epoch loop for a critic (single rank): the handle's last_train_stats stay what the policy's ppo_train left; its
-// last_value_stats are this call's
-int32_t ppo_value_train(ppo_policy_t critic, ppo_adam_t opt, ppo_rollouts_t ro, int64_t batch_size, int32_t num_epochs,
-                        int32_t target, const int64_t* perm, uint64_t seed, double* mse_hist, double* lr_hist) {
+// the epoch loop for a critic, data-parallel like ppo_train: the handle's last_train_stats stay what the policy's ppo_train
+// left; its last_value_stats are this call's, summed over the ranks.  The checks that read no handle come first
+int32_t ppo_value_train_dp(ppo_policy_t critic, ppo_adam_t opt, ppo_rollouts_t ro, int64_t batch_size, int32_t num_epochs,
+                           int32_t target, const int64_t* perm, uint64_t seed, int32_t rank, int32_t world,
+                           ppo_allreduce_fn allreduce, void* allreduce_ctx, double* mse_hist, double* lr_hist) {
+    ARG_CHECK(num_epochs >= 0 && world >= 1 && rank >= 0 && rank < world, "value_train: bad epochs/rank/world");
+    ARG_CHECK(world == 1 || allreduce, "value_train: world > 1 needs an all-reduce hook");
     ARG_CHECK(critic && opt && ro && opt->pol == critic, "value_train: null/mismatched argument");
-    const int64_t len = ro->len;
-    ARG_CHECK(num_epochs >= 0, "value_train: bad epochs");
     ARG_CHECK(ro->H == 32 || ro->H == 128, "value_train: shape mismatch");
     PPO_TRY(value_checks("value_train", critic, ro->F));
     TrainObjective obj = {Objective::Value};
     PPO_TRY(value_target(ro, target, &obj.target_col));
     PPO_TRY(value_clip_check(critic, ro));
-    ARG_CHECK(batch_size >= 1 && batch_size <= len, "1 <= batch_size <= num_data (src/train.jl:88)");
-    return train_epochs(critic, opt, ro, obj, batch_size, num_epochs, perm, seed, 0, 1, nullptr, nullptr, mse_hist, nullptr, lr_hist);
+    // shards may differ in length: with world > 1 train_epochs holds batch_size against the shortest one, on every rank alike
+    ARG_CHECK(batch_size >= 1 && (world > 1 || batch_size <= ro->len), "1 <= batch_size <= num_data (src/train.jl:88)");
+    return train_epochs(critic, opt, ro, obj, batch_size, num_epochs, perm, seed, rank, world, allreduce, allreduce_ctx, mse_hist,
+                        nullptr, lr_hist);
+}
+
+int32_t ppo_value_train(ppo_policy_t critic, ppo_adam_t opt, ppo_rollouts_t ro, int64_t batch_size, int32_t num_epochs,
+                        int32_t target, const int64_t* perm, uint64_t seed, double* mse_hist, double* lr_hist) {
+    return ppo_value_train_dp(critic, opt, ro, batch_size, num_epochs, target, perm, seed, 0, 1, nullptr, nullptr, mse_hist, lr_hist);
 }
 
 }  // extern "C"
