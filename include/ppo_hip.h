@@ -86,6 +86,11 @@ int32_t ppo_compute_returns_tn(const float* rewards, const uint8_t* done, int64_
 /* GAE(gamma,lambda) extension (values [T+1,N]); lambda=1, V=0 == ppo_compute_returns_tn */
 int32_t ppo_gae_tn(const float* rewards, const uint8_t* done, const float* values, int64_t T,
                    int64_t N, double gamma, double lambda, float* adv_out, float* ret_out);
+/* the same scan with a bootstrap column boot [T,N] (no reference op): a done row takes V[t+1] := boot[t] instead of 0 while
+ * the trace is still cut there.  boot = the value of the state a time-limit truncation cut the episode in, exactly 0.0f at
+ * real terminals and at rows that are not done; boot == 0 everywhere gives ppo_gae_tn's numbers */
+int32_t ppo_gae_boot_tn(const float* rewards, const uint8_t* done, const float* values, const float* boot, int64_t T,
+                        int64_t N, double gamma, double lambda, float* adv_out, float* ret_out);
 /* rand(Categorical(p)) for B rows of A probabilities given B uniforms   src/collect_rollouts.jl:6-7
  * actions 0-based; err[b]=1 when the sampled entry has p==0 (the reference's @assert) */
 int32_t ppo_categorical_sample(const float* probs, const float* u, int64_t B, int64_t A,
@@ -267,6 +272,24 @@ int32_t ppo_rollouts_get_index(ppo_rollouts_t ro, int64_t* idx);
  * compute_returns (src/collect_rollouts.jl:26-42) bit for bit. */
 int32_t ppo_rollouts_compute_gae(ppo_rollouts_t ro, const float* values, double gamma, double lambda,
                                  float* adv_out_or_null, float* lambda_returns_out_or_null);
+/* ppo_rollouts_compute_gae with the bootstrap column of ppo_gae_boot_tn, boot [T][N] from the host (a user's critic on
+ * the final states of ppo_rollouts_truncated, or of the user's own env).  Works on any buffer.  The column stays in the
+ * buffer (ppo_rollouts_get_boot) */
+int32_t ppo_rollouts_compute_gae_boot(ppo_rollouts_t ro, const float* values, const float* boot, double gamma, double lambda,
+                                      float* adv_out_or_null, float* lambda_returns_out_or_null);
+/* Time-limit truncations of a buffer collected from the built-in env (no reference op).  The env ends an episode at its
+ * optimum (a terminal) or after max_actions steps (a truncation) and records both as `done`; which one it was is
+ * re-derived on the device by replaying the stored action on the stored state: terminated = (sum |score| == |sum score|
+ * over the active quads behind the step).  truncated_out [T][N]: 1 at done && valid transitions that did not reach the
+ * optimum, 0 everywhere else.  count_out: their number K.  final_states_out [K][H][F] / final_active_out [K]: the
+ * observation and the active word of the state each of them was cut in, in ascending transition id t*N + n; asked for
+ * with capacity < K: PPO_ERR_ARG (call once with null outputs for K).  A buffer without an env template
+ * (ppo_rollouts_create_shape): PPO_ERR_UNSUPPORTED */
+int32_t ppo_rollouts_truncated(ppo_rollouts_t ro, uint8_t* truncated_out_or_null, int8_t* final_states_out_or_null,
+                               uint32_t* final_active_out_or_null, int64_t capacity, int64_t* count_out);
+/* the boot column [T][N] the latest ppo_rollouts_compute_gae_boot / _gae_critic_boot on these rollouts left in the
+ * buffer (none since the latest collection: PPO_ERR_ARG) */
+int32_t ppo_rollouts_get_boot(ppo_rollouts_t ro, float* boot_out);
 /* load columns from host (tests / generic host-side envs) */
 int32_t ppo_rollouts_set(ppo_rollouts_t ro, int64_t T, const int8_t* states, const uint32_t* active,
                          const int32_t* actions0, const float* p_sel, const float* returns,
@@ -395,6 +418,14 @@ int32_t ppo_rollouts_compute_values(ppo_rollouts_t ro, ppo_env_t env_or_null, pp
  * asked for; ppo_train(..., PPO_ADV_GAE*) works after it */
 int32_t ppo_rollouts_compute_gae_critic(ppo_rollouts_t ro, ppo_env_t env_or_null, ppo_policy_t critic, double gamma,
                                         double lambda, float* adv_out_or_null, float* lambda_returns_out_or_null);
+/* the same with time-limit truncations bootstrapped: ppo_rollouts_compute_values, then ppo_rollouts_truncated's replay,
+ * one critic forward over the K final states, their values scattered into the boot column, and the scan of
+ * ppo_gae_boot_tn.  One 8-byte count (K, also to n_truncated_out) crosses to the host; no state or value column does
+ * unless an output is asked for.  The returns column (PPO_VTARGET_RETURNS) is not bootstrapped.  A buffer without an env
+ * template: PPO_ERR_UNSUPPORTED (use ppo_rollouts_compute_gae_boot with final values of your own) */
+int32_t ppo_rollouts_compute_gae_critic_boot(ppo_rollouts_t ro, ppo_env_t env_or_null, ppo_policy_t critic, double gamma,
+                                             double lambda, float* adv_out_or_null, float* lambda_returns_out_or_null,
+                                             int64_t* n_truncated_out_or_null);
 /* forward + mse + backward of one minibatch (sample_idx as in ppo_forward_backward): the flat gradient of
  * sum_b (V(s_b) - target_b)^2 / B_global goes to the critic's gradient buffer (ppo_policy_get_grad), that loss to
  * loss_out (optional).  target: PPO_VTARGET_*; lambda-returns need a GAE call on these rollouts first (PPO_ERR_ARG). */

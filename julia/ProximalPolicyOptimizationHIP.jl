@@ -277,6 +277,33 @@ function compute_gae!(r::HipRollouts, values::Matrix{Float32}, gamma, lambda)   
     check(ccall((:ppo_rollouts_compute_gae, LIB), Int32, (Ptr{Cvoid}, Ptr{Float32}, Float64, Float64, Ptr{Float32}, Ptr{Float32}),
                 r.h, values, Float64(gamma), Float64(lambda), C_NULL, C_NULL))
 end
+# ... with time-limit truncations bootstrapped (no reference op): final_values [N, T] column-major == [T][N], the caller's
+# value of the state each truncated episode was cut in, 0 at real terminals and at transitions that end no episode
+function compute_gae!(r::HipRollouts, values::Matrix{Float32}, final_values::Matrix{Float32}, gamma, lambda)
+    check(ccall((:ppo_rollouts_compute_gae_boot, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Float32}, Ptr{Float32}, Float64, Float64, Ptr{Float32}, Ptr{Float32}),
+                r.h, values, final_values, Float64(gamma), Float64(lambda), C_NULL, C_NULL))
+end
+# standalone scan, rewards / done / boot [N, T] and values [N, T+1] column-major -> (advantages, lambda_returns)
+function gae_boot_tn(rewards::Matrix{Float32}, done::Matrix{UInt8}, values::Matrix{Float32}, boot::Matrix{Float32}, gamma, lambda)
+    adv, ret = similar(rewards), similar(rewards)
+    check(ccall((:ppo_gae_boot_tn, LIB), Int32,
+                (Ptr{Float32}, Ptr{UInt8}, Ptr{Float32}, Ptr{Float32}, Int64, Int64, Float64, Float64, Ptr{Float32}, Ptr{Float32}),
+                rewards, done, values, boot, size(rewards, 2), size(rewards, 1), Float64(gamma), Float64(lambda), adv, ret))
+    adv, ret
+end
+# which done transitions of a built-in-env buffer were time limits, and the states they cut the episodes in: the number K,
+# and with fetch the observations [F, H, K], active words [K] (ascending transition id) for a host critic
+function truncated_transitions(r::HipRollouts, H, F; fetch = true)
+    k = Ref{Int64}()
+    check(ccall((:ppo_rollouts_truncated, LIB), Int32, (Ptr{Cvoid}, Ptr{UInt8}, Ptr{Int8}, Ptr{UInt32}, Int64, Ref{Int64}),
+                r.h, C_NULL, C_NULL, C_NULL, 0, k))
+    fetch || return k[]
+    states, active = zeros(Int8, F, H, k[]), zeros(UInt32, k[])
+    check(ccall((:ppo_rollouts_truncated, LIB), Int32, (Ptr{Cvoid}, Ptr{UInt8}, Ptr{Int8}, Ptr{UInt32}, Int64, Ref{Int64}),
+                r.h, C_NULL, states, active, k[], k))
+    k[], states, active
+end
 
 # ppo_train!(policy, optimizer, dataset, epsilon, batch_size, num_epochs, entropy_weight) (src/train.jl:130-153).
 # rank / world / hook: data-parallel runs (one process per GPU; INTEGRATION.md section 5); single process: 0 / 1 / C_NULL
@@ -337,6 +364,14 @@ function compute_gae_critic!(r::HipRollouts, env::Union{Nothing,HipVecEnv}, c::H
     check(ccall((:ppo_rollouts_compute_gae_critic, LIB), Int32,
                 (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Ptr{Float32}, Ptr{Float32}),
                 r.h, env === nothing ? C_NULL : env.h, c.h, Float64(gamma), Float64(lambda), C_NULL, C_NULL))
+end
+# ... with time-limit truncations bootstrapped from the critic's value of the replayed final states -> their number
+function compute_gae_critic_boot!(r::HipRollouts, env::Union{Nothing,HipVecEnv}, c::HipPolicy, gamma, lambda)
+    k = Ref{Int64}()
+    check(ccall((:ppo_rollouts_compute_gae_critic_boot, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Ptr{Float32}, Ptr{Float32}, Ref{Int64}),
+                r.h, env === nothing ? C_NULL : env.h, c.h, Float64(gamma), Float64(lambda), C_NULL, C_NULL, k))
+    k[]
 end
 function value_forward_backward(c::HipPolicy, r::HipRollouts, idx::Vector{Int64}; target = :returns, B_global = length(idx))
     loss = Ref{Float64}()

@@ -46,7 +46,7 @@ __all__ = [
     "PPOError", "HipVecEnv", "HipPolicy", "Adam", "ExpDecay", "Descent", "Momentum", "Nesterov", "RMSProp", "ClipValue", "ClipNorm", "WeightDecay", "InvDecay", "AdamW", "Optimiser", "StateData", "BufferRollouts", "BufferDataset",
     "state", "reward", "is_terminal", "reset_", "step_", "action_probabilities", "batch_action_probabilities",
     "batch_state", "number_of_actions_per_state", "batch_advantage", "save_loss", "compute_returns",
-    "compute_returns_tn", "gae_tn", "compute_gae_", "profile_gae", "collect_rollouts_", "collect_rollouts_steps_", "construct_dataset",
+    "compute_returns_tn", "gae_tn", "gae_boot_tn", "truncated_transitions_", "compute_gae_", "profile_gae", "collect_rollouts_", "collect_rollouts_steps_", "construct_dataset",
     "simplified_ppo_clip", "get_linear_action_index", "ppo_loss_with_entropy", "categorical_sample", "step_batch_",
     "ppo_train_", "ppo_iterate_", "get_optimizer_learning_rate", "index_to_action", "action_mask", "DataParallel",
     "device_count", "average_returns", "average_best_returns", "average_normalized_returns",
@@ -842,6 +842,22 @@ def gae_tn(rewards, done, values, gamma, lam):
     return adv, ret
 
 
+def gae_boot_tn(rewards, done, values, boot, gamma, lam):
+    """gae_tn with a bootstrap column boot [T,N]: a done row takes V[t+1] := boot[t] instead of 0 (the trace is still cut
+    there).  boot = the value of the state a time-limit truncation cut the episode in, 0 at real terminals and elsewhere."""
+    r = np.ascontiguousarray(rewards, np.float32)
+    d = np.ascontiguousarray(done, np.uint8)
+    v = np.ascontiguousarray(values, np.float32)
+    b = np.ascontiguousarray(boot, np.float32)
+    T, N = r.shape
+    if d.shape != (T, N) or b.shape != (T, N) or v.shape != (T + 1, N):
+        raise PPOError(-1, "AssertionError: done and boot must be [T, N], values [T+1, N] = [%d, %d]" % (T + 1, N))
+    adv, ret = np.empty_like(r), np.empty_like(r)
+    call("ppo_gae_boot_tn", _p(r, _lib.c_f32p), _p(d, _lib.c_u8p), _p(v, _lib.c_f32p), _p(b, _lib.c_f32p), T, N, float(gamma),
+         float(lam), _p(adv, _lib.c_f32p), _p(ret, _lib.c_f32p))
+    return adv, ret
+
+
 def categorical_sample(probs, u):
     """rand(Categorical(p)) for rows of probs [B,A] with uniforms u[B]; returns 1-based actions,
     selected probabilities and the ap[a] > 0 assertion flags (src/collect_rollouts.jl:6-7)."""
@@ -902,6 +918,7 @@ class BufferRollouts:
     def __init__(self):
         self._h = None
         self._env = None
+        self.n_truncated = None  # time-limit truncations the latest compute_gae_critic_(..., bootstrap_truncated=True) found
         self._host = None        # generic (user-defined env) mode: the reference's own AoS columns (generic.HostRollouts)
 
     def _ensure(self, env, T):
@@ -968,6 +985,12 @@ class BufferRollouts:
     @property
     def valid(self):
         return self._get("ppo_rollouts_get_valid", np.uint8, _lib.c_u8p).astype(bool)
+
+    @property
+    def boot_values(self):
+        """The bootstrap column [T,N] the latest compute_gae_(..., final_values=) / compute_gae_critic_(...,
+        bootstrap_truncated=True) on these rollouts left on the device."""
+        return self._get("ppo_rollouts_get_boot", np.float32, _lib.c_f32p)
 
     @property
     def state_data(self):
@@ -1065,17 +1088,45 @@ def collect_rollouts_steps_(rollouts, env, policy, num_steps, discount, record_p
     call("ppo_collect_rollouts", h, env._h, policy._h, int(num_steps), g, f32, int(bool(record_probs)))
 
 
-def compute_gae_(rollouts, values, gamma, lam):
+def compute_gae_(rollouts, values, gamma, lam, final_values=None):
     """batch_advantage as GAE(gamma, lambda): `values` [T+1, N] are the caller's state values (row T = bootstrap).  The
-    advantage column stays on the device for ppo_train_(..., advantage="gae"); returns (advantages, lambda_returns)."""
+    advantage column stays on the device for ppo_train_(..., advantage="gae"); returns (advantages, lambda_returns).
+    final_values [T, N] (None: today's call): the caller's value of the state an episode was cut in at every time-limit
+    truncation (truncated_transitions_ lists them and their final states), 0 at real terminals and everywhere else; a done
+    row then bootstraps from it instead of from 0.  The buffer's returns column is not bootstrapped."""
     T, N = rollouts.dims()
     v = np.ascontiguousarray(values, np.float32)
     if v.shape != (T + 1, N):
         raise PPOError(-1, "AssertionError: values must be [T+1, N] = [%d, %d]" % (T + 1, N))
     adv, ret = np.empty((T, N), np.float32), np.empty((T, N), np.float32)
-    call("ppo_rollouts_compute_gae", rollouts._h, _p(v, _lib.c_f32p), float(gamma), float(lam), _p(adv, _lib.c_f32p),
-         _p(ret, _lib.c_f32p))
+    if final_values is None:
+        call("ppo_rollouts_compute_gae", rollouts._h, _p(v, _lib.c_f32p), float(gamma), float(lam), _p(adv, _lib.c_f32p),
+             _p(ret, _lib.c_f32p))
+        return adv, ret
+    b = np.ascontiguousarray(final_values, np.float32)
+    if b.shape != (T, N):
+        raise PPOError(-1, "AssertionError: final_values must be [T, N] = [%d, %d]" % (T, N))
+    call("ppo_rollouts_compute_gae_boot", rollouts._h, _p(v, _lib.c_f32p), _p(b, _lib.c_f32p), float(gamma), float(lam),
+         _p(adv, _lib.c_f32p), _p(ret, _lib.c_f32p))
     return adv, ret
+
+
+def truncated_transitions_(rollouts, fetch_states=True):
+    """Which `done` transitions of a buffer collected from the built-in env were time limits (max_actions) and not the
+    optimum, found on the device by replaying the stored action on the stored state.  Returns (flags [T,N] bool, final
+    states [K,H,F] int8, final active [K] uint32): the state each of the K truncated episodes was cut in, in ascending
+    transition id t*N + n -- what a host critic needs for compute_gae_(..., final_values=).  fetch_states=False: (flags,
+    None, None).  A buffer of a user-defined env (no env template) is refused."""
+    T, N = rollouts.dims()
+    flags = np.empty((T, N), np.uint8)
+    k = C.c_int64(0)
+    call("ppo_rollouts_truncated", rollouts._h, _p(flags, _lib.c_u8p), None, None, 0, C.byref(k))
+    if not fetch_states:
+        return flags.astype(bool), None, None
+    env = rollouts._env
+    st, act = np.empty((k.value, env.H, env.F), np.int8), np.empty(k.value, np.uint32)
+    call("ppo_rollouts_truncated", rollouts._h, None, _p(st, _lib.c_i8p), _p(act, _lib.c_u32p), k.value, C.byref(k))
+    return flags.astype(bool), st, act
 
 
 def compute_values_(rollouts, env, critic):
@@ -1087,16 +1138,25 @@ def compute_values_(rollouts, env, critic):
     return v
 
 
-def compute_gae_critic_(rollouts, env, critic, gamma, lam, fetch=True):
+def compute_gae_critic_(rollouts, env, critic, gamma, lam, fetch=True, bootstrap_truncated=False):
     """compute_values_ + the GAE(gamma, lambda) scan without a host trip; the advantage column stays on the device for
     ppo_train_(..., advantage="gae"), the lambda-returns for value_train_(..., target="lambda_returns").
-    fetch=True returns (advantages, lambda_returns) [T,N]; fetch=False copies nothing back and returns None."""
+    fetch=True returns (advantages, lambda_returns) [T,N]; fetch=False copies nothing back and returns None.
+    bootstrap_truncated=True: an episode the env's time limit cut bootstraps from the critic's value of the state it was cut
+    in (replayed on the device, truncated_transitions_) instead of from 0; rollouts.boot_values is that column and
+    rollouts.n_truncated the number of truncations.  The returns column (target="returns") is not bootstrapped."""
     T, N = rollouts.dims()
     adv = ret = None
     if fetch:
         adv, ret = np.empty((T, N), np.float32), np.empty((T, N), np.float32)
-    call("ppo_rollouts_compute_gae_critic", rollouts._h, env._h if env is not None else None, critic._h, float(gamma),
-         float(lam), _p(adv, _lib.c_f32p) if fetch else None, _p(ret, _lib.c_f32p) if fetch else None)
+    if not bootstrap_truncated:
+        call("ppo_rollouts_compute_gae_critic", rollouts._h, env._h if env is not None else None, critic._h, float(gamma),
+             float(lam), _p(adv, _lib.c_f32p) if fetch else None, _p(ret, _lib.c_f32p) if fetch else None)
+        return (adv, ret) if fetch else None
+    k = C.c_int64(0)
+    call("ppo_rollouts_compute_gae_critic_boot", rollouts._h, env._h if env is not None else None, critic._h, float(gamma),
+         float(lam), _p(adv, _lib.c_f32p) if fetch else None, _p(ret, _lib.c_f32p) if fetch else None, C.byref(k))
+    rollouts.n_truncated = k.value
     return (adv, ret) if fetch else None
 
 
@@ -1364,7 +1424,8 @@ def _value_target(target):
 
 def value_forward_backward(critic, dataset, batch_indices, target="returns", B_global=None):
     """Gradient of Flux.mse(V(dataset[batch_indices]), target) (no update): leaves it in critic.grad(); returns the loss.
-    target: "returns" (the buffer's returns) or "lambda_returns" (adv + V of the latest GAE call on these rollouts)."""
+    target: "returns" (the buffer's returns; never bootstrapped through time-limit truncations) or "lambda_returns" (adv + V of
+    the latest GAE call on these rollouts, bootstrapped if that call was)."""
     t = _value_target(target)
     ii = np.ascontiguousarray(np.asarray(batch_indices, np.int64) - 1)
     out = C.c_double(0)
@@ -1376,7 +1437,9 @@ def value_forward_backward(critic, dataset, batch_indices, target="returns", B_g
 def value_train_(critic, optimizer, dataset, batch_size, num_epochs, target="returns", perm=None, seed=0, verbose=True,
                  parallel=None):
     """ppo_train_'s epoch loop for the critic -> (mse_history, lr_history).  optimizer: any Optimiser chain, bound to the
-    critic (not the one that trains the policy).
+    critic (not the one that trains the policy).  target as in value_forward_backward: "lambda_returns" follows the latest
+    GAE call (bootstrapped through time-limit truncations if that call was), "returns" is the reference's compute_returns
+    and is not bootstrapped.
     parallel: as in ppo_train_ -- every rank holds a replica of the critic and of its optimiser and passes its own shard;
     the replicas stay bit-identical, the mse history and critic.last_value_stats() are the global ones.  critic.value_clip
     must be the same on every rank, like policy.target_kl and num_epochs."""
@@ -1420,8 +1483,15 @@ def ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size,
     parallel (keyword only; the one name **options takes -- tests/test_value_host.py pins the set of named keywords): a
     DataParallel.  `env` is then this rank's shard (DataParallel.env_shard, global_offset); ppo_train_, value_train_ and
     explained_variance_ run across the ranks, so policy, critic and every list of the loss dict are the same on all of them.
-    The GAE and any advantage normalisation stay per rank.  None runs the single-process loop."""
+    The GAE and any advantage normalisation stay per rank.  None runs the single-process loop.
+    bootstrap_truncated (keyword only, the second name **options takes; without a critic there is no GAE and it does
+    nothing): every iteration's GAE bootstraps the episodes the env's time limit cut from the critic's value of the state they
+    were cut in
+    (compute_gae_critic_(..., bootstrap_truncated=True)), per rank like the GAE itself; loss gains "truncated", the number of
+    truncated transitions per iteration (this rank's).  value_train_'s lambda-returns and "explained_variance" are then the
+    bootstrapped ones."""
     parallel = options.pop("parallel", None)
+    bootstrap = bool(options.pop("bootstrap_truncated", False))
     if options:
         raise TypeError("ppo_iterate_() got an unexpected keyword argument %r" % sorted(options)[0])
     loss = {"ppo": [], "entropy": [], "lr": []}
@@ -1438,6 +1508,8 @@ def ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size,
         loss["value"] = []
         if getattr(critic, "value_clip", None) is not None:
             loss["value_clip_fraction"] = []
+        if bootstrap:
+            loss["truncated"] = []
     for it in range(1, num_ppo_iterations + 1):
         evaluator(policy, env, optimizer)                                                    # :181,226
         if verbose:
@@ -1449,7 +1521,11 @@ def ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size,
             p, e, lr = ppo_train_(policy, optimizer, dataset, epsilon, minibatch_size, epochs_per_iteration,
                                   entropy_weight, parallel=parallel, verbose=verbose)
         else:
-            compute_gae_critic_(dataset.rollouts, env, critic, discount, gae_lambda, fetch=False)
+            if bootstrap:
+                compute_gae_critic_(dataset.rollouts, env, critic, discount, gae_lambda, fetch=False, bootstrap_truncated=True)
+                loss["truncated"].append(dataset.rollouts.n_truncated)
+            else:
+                compute_gae_critic_(dataset.rollouts, env, critic, discount, gae_lambda, fetch=False)
             p, e, lr = ppo_train_(policy, optimizer, dataset, epsilon, minibatch_size, epochs_per_iteration,
                                   entropy_weight, parallel=parallel, verbose=verbose, advantage="gae")
             if stats:

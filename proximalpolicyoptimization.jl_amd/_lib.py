@@ -32,6 +32,7 @@ SIGNATURES = {
     "ppo_compute_returns": [c_f32p, c_u8p, C.c_int64, C.c_double, C.c_int32, c_f32p],
     "ppo_compute_returns_tn": [c_f32p, c_u8p, C.c_int64, C.c_int64, C.c_double, C.c_int32, c_f32p],
     "ppo_gae_tn": [c_f32p, c_u8p, c_f32p, C.c_int64, C.c_int64, C.c_double, C.c_double, c_f32p, c_f32p],
+    "ppo_gae_boot_tn": [c_f32p, c_u8p, c_f32p, c_f32p, C.c_int64, C.c_int64, C.c_double, C.c_double, c_f32p, c_f32p],
     "ppo_categorical_sample": [c_f32p, c_f32p, C.c_int64, C.c_int64, c_i32p, c_f32p, c_i32p],
     "ppo_linear_action_index": [c_i64p, C.c_int64, C.c_int64, c_i64p],
     "ppo_loss_with_entropy": [c_f32p, c_i64p, c_f32p, c_f32p, C.c_int64, C.c_int64, C.c_double, c_f64p, c_f64p],
@@ -115,6 +116,10 @@ SIGNATURES = {
     "ppo_profile_returns": [C.c_int64, C.c_int64, C.c_double, C.c_int32, c_f64p],
     "ppo_profile_gae": [C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int32, c_f64p],
     "ppo_rollouts_compute_gae": [H, c_f32p, C.c_double, C.c_double, c_f32p, c_f32p],
+    "ppo_rollouts_compute_gae_boot": [H, c_f32p, c_f32p, C.c_double, C.c_double, c_f32p, c_f32p],
+    "ppo_rollouts_truncated": [H, c_u8p, c_i8p, c_u32p, C.c_int64, c_i64p],
+    "ppo_rollouts_get_boot": [H, c_f32p],
+    "ppo_rollouts_compute_gae_critic_boot": [H, H, H, C.c_double, C.c_double, c_f32p, c_f32p, c_i64p],
     "ppo_value_forward": [H, c_i8p, c_u32p, C.c_int64, C.c_int32, c_f32p],
     "ppo_rollouts_compute_values": [H, H, H, c_f32p],
     "ppo_rollouts_compute_gae_critic": [H, H, H, C.c_double, C.c_double, c_f32p, c_f32p],

@@ -216,6 +216,21 @@ int32_t ppo_gae_tn(const float* rewards, const uint8_t* done, const float* value
     return d2h(ret_out, o.p, n);
 }
 
+int32_t ppo_gae_boot_tn(const float* rewards, const uint8_t* done, const float* values, const float* boot, int64_t T, int64_t N,
+                        double gamma, double lambda, float* adv_out, float* ret_out) {
+    ARG_CHECK(T >= 0 && N >= 0, "gae_boot_tn: negative size");
+    const size_t n = (size_t)T * N;
+    if (n == 0) return PPO_OK;
+    ARG_CHECK(rewards && done && values && boot && adv_out && ret_out, "gae_boot_tn: null buffer");
+    PPO_TRY(ensure_init());
+    DevBuf<float> r, v, b, a, o; DevBuf<uint8_t> t;
+    PPO_TRY(r.alloc(n)); PPO_TRY(v.alloc(n + N)); PPO_TRY(b.alloc(n)); PPO_TRY(a.alloc(n)); PPO_TRY(o.alloc(n)); PPO_TRY(t.alloc(n));
+    PPO_TRY(h2d(r.p, rewards, n)); PPO_TRY(h2d(t.p, done, n)); PPO_TRY(h2d(v.p, values, n + N)); PPO_TRY(h2d(b.p, boot, n));
+    PPO_TRY(launch_gae_boot_tn(r.p, t.p, v.p, b.p, a.p, o.p, T, N, gamma, lambda));
+    PPO_TRY(d2h(adv_out, a.p, n));
+    return d2h(ret_out, o.p, n);
+}
+
 int32_t ppo_categorical_sample(const float* probs, const float* u, int64_t B, int64_t A, int32_t* actions,
                                float* p_sel, int32_t* err) {
     PPO_TRY(ensure_init());
@@ -778,7 +793,7 @@ int32_t ppo_collect_rollouts(ppo_rollouts_t ro, ppo_env_t env, ppo_policy_t pol,
         PPO_TRY(disk_sink_step(ro, t));                 // out-of-core store: async D2H of step t on the copy stream
     }
     }
-    ro->T = T; ro->adv_T = -1; ro->values_T = -1;
+    ro->T = T; ro->adv_T = -1; ro->values_T = -1; ro->boot_T = -1;
     PPO_TRY(set_index_all(ro));
     // compute_state_value!: returns overwrite the rewards column (src/rollout_buffer.jl:55-64)
     PPO_TRY(launch_returns_tn(ro->rewards.p, ro->done.p, ro->returns.p, T, N, discount, discount_is_f32));
@@ -824,7 +839,7 @@ int32_t ppo_collect_rollouts_episodes(ppo_rollouts_t ro, ppo_env_t env, ppo_poli
             if (all) break;
         }
     }
-    ro->T = T; ro->adv_T = -1; ro->values_T = -1;
+    ro->T = T; ro->adv_T = -1; ro->values_T = -1; ro->boot_T = -1;
     // dataset order = env-major concatenation of whole episodes (the reference's flat buffer)
     std::vector<uint8_t> valid((size_t)T * N);
     PPO_TRY(d2h(valid.data(), ro->valid.p, (size_t)T * N));
@@ -912,7 +927,7 @@ static int32_t evaluate_impl(ppo_policy_s* pol, ppo_env_s* env, ppo_rollouts_s* 
         }
     }
     ARG_CHECK(all, "evaluator: the episodes did not finish within max_actions steps each");
-    scratch->T = 0; scratch->len = 0; scratch->adv_T = -1; scratch->values_T = -1;
+    scratch->T = 0; scratch->len = 0; scratch->adv_T = -1; scratch->values_T = -1; scratch->boot_T = -1;
     values.resize((size_t)num_traj);
     PPO_TRY(d2h(values.data(), out.p, (size_t)num_traj));
     return ppo_env_check_errors(env, nullptr);
@@ -1007,7 +1022,7 @@ int32_t ppo_rollouts_set(ppo_rollouts_t ro, int64_t T, const int8_t* states, con
     PPO_TRY(h2d(ro->actions.p, actions0, n)); PPO_TRY(h2d(ro->p_sel.p, p_sel, n)); PPO_TRY(h2d(ro->returns.p, returns, n));
     PPO_TRY(h2d(ro->rewards.p, returns, n));
     if (terminal) PPO_TRY(h2d(ro->done.p, terminal, n));
-    ro->T = T; ro->adv_T = -1; ro->values_T = -1;
+    ro->T = T; ro->adv_T = -1; ro->values_T = -1; ro->boot_T = -1;
     return set_index_all(ro);
 }
 
@@ -1025,6 +1040,29 @@ int32_t ppo_rollouts_compute_gae(ppo_rollouts_t ro, const float* values, double 
     if (adv_out) PPO_TRY(d2h(adv_out, ro->adv.p, n));
     if (lambda_returns_out) PPO_TRY(d2h(lambda_returns_out, ro->lam_ret.p, n));
     return PPO_OK;
+}
+
+// the same with a host-supplied bootstrap column [T][N] (ppo_gae_boot_tn): any buffer, any env
+int32_t ppo_rollouts_compute_gae_boot(ppo_rollouts_t ro, const float* values, const float* boot, double gamma, double lambda,
+                                      float* adv_out, float* lambda_returns_out) {
+    ARG_CHECK(ro && values && boot, "compute_gae_boot: null argument");
+    ARG_CHECK(ro->T >= 1, "compute_gae_boot: empty rollout buffer");
+    const size_t n = (size_t)ro->T * ro->N;
+    PPO_TRY(ro->values.alloc(n + ro->N)); PPO_TRY(ro->adv.alloc((size_t)ro->capT * ro->N)); PPO_TRY(ro->lam_ret.alloc((size_t)ro->capT * ro->N));
+    PPO_TRY(ro->boot.alloc((size_t)ro->capT * ro->N));
+    PPO_TRY(h2d(ro->values.p, values, n + ro->N)); PPO_TRY(h2d(ro->boot.p, boot, n));
+    PPO_TRY(launch_gae_boot_tn(ro->rewards.p, ro->done.p, ro->values.p, ro->boot.p, ro->adv.p, ro->lam_ret.p, ro->T, ro->N, gamma, lambda));
+    ro->adv_T = ro->T; ro->values_T = ro->T; ro->boot_T = ro->T;
+    if (adv_out) PPO_TRY(d2h(adv_out, ro->adv.p, n));
+    if (lambda_returns_out) PPO_TRY(d2h(lambda_returns_out, ro->lam_ret.p, n));
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    return PPO_OK;
+}
+
+int32_t ppo_rollouts_get_boot(ppo_rollouts_t ro, float* boot_out) {
+    ARG_CHECK(ro && boot_out, "get_boot: null argument");
+    ARG_CHECK(ro->boot.p && ro->boot_T == ro->T && ro->T >= 1, "get_boot: needs ppo_rollouts_compute_gae_boot or ppo_rollouts_compute_gae_critic_boot on these rollouts first");
+    return d2h(boot_out, ro->boot.p, (size_t)ro->T * ro->N);
 }
 
 }  // extern "C"

@@ -224,6 +224,16 @@ struct ppo_rollouts_s {
     DevBuf<float> lam_ret;     // [T][N] lambda-returns adv + V
     int64_t adv_T = -1;        // T the adv column was computed for (-1: none)
     int64_t values_T = -1;     // T the values were computed for (-1: none)
+    // time-limit bootstrap (ppo_gae_boot.hip): which done transitions were truncations, and what the critic makes of the
+    // states they cut the episodes in
+    DevBuf<uint8_t> truncated; // [T][N] 1: done && valid and the optimum not reached
+    DevBuf<int32_t> trunc_ids; // [K] their transition ids, ascending
+    DevBuf<int32_t> trunc_counts;  // compaction workspace: block counts / offsets, then the 8-byte total
+    DevBuf<int8_t> boot_cstate;    // [K][2V] post-step env snapshots of those transitions
+    DevBuf<uint32_t> boot_active;  // [K]
+    DevBuf<float> boot_vals;   // [K] the critic's values of them
+    DevBuf<float> boot;        // [T][N] boot_vals scattered to their transitions (or host-supplied), 0 elsewhere
+    int64_t boot_T = -1;       // T the boot column was computed for (-1: none)
     DevBuf<double> stats_part; // workspace and result of k_value_moments (ppo_stats.hip)
     bool all_valid = true;
     DiskSink* sink = nullptr;  // optional out-of-core store (ppo_rollouts_attach_disk)
@@ -256,6 +266,14 @@ int32_t launch_returns_tn(const float* r, const uint8_t* done, float* out, int64
 int32_t launch_returns_flat(const float* r, const uint8_t* term, float* out, int64_t n, double discount, int f32mode);
 int32_t launch_gae_tn(const float* r, const uint8_t* done, const float* values, float* adv, float* ret,
                       int64_t T, int64_t N, double gamma, double lambda);
+
+int32_t launch_gae_boot_tn(const float* r, const uint8_t* done, const float* values, const float* boot, float* adv,
+                           float* ret, int64_t T, int64_t N, double gamma, double lambda);
+// ppo_gae_boot.hip: the buffer's truncated flags, their ascending ids and their count (the one host crossing); the
+// post-step snapshots of those K transitions; vals[k] -> boot[ids[k]] over a zeroed column
+int32_t launch_truncated(ppo_rollouts_s* ro, int64_t* K_out);
+int32_t launch_truncated_states(ppo_rollouts_s* ro, int64_t K, int8_t* cstate_out, uint32_t* active_out);
+int32_t launch_boot_scatter(ppo_rollouts_s* ro, const float* vals, int64_t K, float* boot);
 
 int32_t launch_env_reset(ppo_env_s* e, int only_done);
 // evaluator bookkeeping folded into the env step of the episodes mode (test/quad_game_utilities.jl:280-307,369-387,

@@ -194,19 +194,30 @@ __global__ void k_returns_flat(const float* __restrict__ r, const uint8_t* __res
 // HBM-bound: 17 B per transition (r f32 + done u8 + V f32 in, adv f32 + ret f32 out; V[t+1] is the V[t] of the row
 // scanned just before, carried in a register, so every value is read once).
 
+// Both forms take a template parameter BOOT: with it, `boot` [T][N] holds the critic's value of the state
+// an episode was cut in at a time-limit truncation (exactly 0.0f everywhere else), and a done row bootstraps from it,
+//     vnext = done[t] ? (double)boot[t] : V[t+1]
+// while the trace is still cut there ((gamma * lambda) * nd).  Without it the statements are the ones above; the
+// kernels k_gae_tn / k_gae_tn_x4 are the BOOT = 0 bodies under their old names and signatures.
+
 // small-N form: one lane per column (scalar, coalesced rows)
-__global__ void k_gae_tn(const float* __restrict__ r, const uint8_t* __restrict__ done, const float* __restrict__ val,
-                         float* __restrict__ adv, float* __restrict__ ret, int64_t T, int64_t N, double gamma,
-                         double lambda) {
+template <int BOOT>
+__device__ __forceinline__ void gae_tn_scan(const float* __restrict__ r, const uint8_t* __restrict__ done,
+                                            const float* __restrict__ val, const float* __restrict__ boot,
+                                            float* __restrict__ adv, float* __restrict__ ret, int64_t T, int64_t N,
+                                            double gamma, double lambda) {
     const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
     double a = 0.0;
     const double gl = gamma * lambda;
     double vn = (double)val[T * N + n];
     for (int64_t t = T - 1; t >= 0; --t) {
-        const double nd = done[t * N + n] ? 0.0 : 1.0;
+        const bool dn = done[t * N + n] != 0;
+        const double nd = dn ? 0.0 : 1.0;
         const double v = (double)val[t * N + n];
-        const double vnext = vn * nd;
+        double vnext;
+        if (BOOT) vnext = dn ? (double)boot[t * N + n] : vn;
+        else vnext = vn * nd;
         const double gvn = gamma * vnext;
         const double delta = ((double)r[t * N + n] + gvn) - v;
         const double carry = (gl * nd) * a;
@@ -216,6 +227,16 @@ __global__ void k_gae_tn(const float* __restrict__ r, const uint8_t* __restrict_
         vn = v;
     }
 }
+__global__ void k_gae_tn(const float* __restrict__ r, const uint8_t* __restrict__ done, const float* __restrict__ val,
+                         float* __restrict__ adv, float* __restrict__ ret, int64_t T, int64_t N, double gamma,
+                         double lambda) {
+    gae_tn_scan<0>(r, done, val, nullptr, adv, ret, T, N, gamma, lambda);
+}
+__global__ void k_gae_boot_tn(const float* __restrict__ r, const uint8_t* __restrict__ done, const float* __restrict__ val,
+                              const float* __restrict__ boot, float* __restrict__ adv, float* __restrict__ ret, int64_t T,
+                              int64_t N, double gamma, double lambda) {
+    gae_tn_scan<1>(r, done, val, boot, adv, ret, T, N, gamma, lambda);
+}
 
 // Wide form for large N (N % 4 == 0), the LDS-staged structure of k_returns_tn_x4: a workgroup owns COLS adjacent
 // columns; per pass of RW_ROWS time rows every wave loads its share of the three input tiles with full-width accesses
@@ -223,16 +244,18 @@ __global__ void k_gae_tn(const float* __restrict__ r, const uint8_t* __restrict_
 // -- one column per lane, the exact sequential fp64 recurrence, A and V[t+1] carried in registers across passes, no
 // cross-wave dependency -- writing adv over the r tile and ret over the V tile; after a second barrier both tiles
 // leave with wide stores.  Two tile sets are ping-ponged so the loads of pass p+1 are in flight during the scan of p.
-template <int COLS, int RW_ROWS>
-__global__ __launch_bounds__(COLS) void k_gae_tn_x4(const float* __restrict__ r, const uint8_t* __restrict__ done,
-                                                    const float* __restrict__ val, float* __restrict__ adv,
-                                                    float* __restrict__ ret, int64_t T, int64_t N, double gamma,
-                                                    double lambda) {
+// BOOT: a fourth fp32 tile sB takes the boot column through the same loads (29 B per transition instead of 17).
+template <int COLS, int RW_ROWS, int BOOT>
+__device__ __forceinline__ void gae_tn_x4_scan(const float* __restrict__ r, const uint8_t* __restrict__ done,
+                                               const float* __restrict__ val, const float* __restrict__ boot,
+                                               float* __restrict__ adv, float* __restrict__ ret, int64_t T, int64_t N,
+                                               double gamma, double lambda) {
     constexpr int W = COLS / 64, RS = 256 / COLS, RPW = RW_ROWS / (W * RS);
     static_assert(RPW >= 1 && RPW * W * RS == RW_ROWS, "tile shape");
     __shared__ __attribute__((aligned(16))) float sR[2][RW_ROWS][COLS];
     __shared__ __attribute__((aligned(16))) float sV[2][RW_ROWS][COLS];
     __shared__ __attribute__((aligned(16))) uint8_t sD[2][RW_ROWS][COLS];
+    __shared__ __attribute__((aligned(16))) float sB[BOOT ? 2 : 1][BOOT ? RW_ROWS : 1][BOOT ? COLS : 4];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int64_t c0 = (int64_t)blockIdx.x * COLS;
     const int lr = lane / (COLS / 4), lc = (lane % (COLS / 4)) * 4;
@@ -244,7 +267,7 @@ __global__ __launch_bounds__(COLS) void k_gae_tn_x4(const float* __restrict__ r,
     double a = 0.0;
     double vn = (sc < N) ? (double)val[T * N + sc] : 0.0;       // V[T]: bootstrap value behind the last row
 
-    float4 rv[RPW], vv[RPW];
+    float4 rv[RPW], vv[RPW], bv[BOOT ? RPW : 1];
     uint32_t dv[RPW];
     auto tile_row = [&](int i) { return (w * RPW + i) * RS + lr; };
     auto load_regs = [&](int64_t p) {
@@ -258,6 +281,10 @@ __global__ __launch_bounds__(COLS) void k_gae_tn_x4(const float* __restrict__ r,
                 vv[i] = *reinterpret_cast<const float4*>(val + t * N + cl);
                 dv[i] = *reinterpret_cast<const uint32_t*>(done + t * N + cl);
             }
+            if (BOOT) {
+                bv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (wide_ok && t >= 0) bv[i] = *reinterpret_cast<const float4*>(boot + t * N + cl);
+            }
         }
     };
     auto park = [&](int buf) {
@@ -266,6 +293,7 @@ __global__ __launch_bounds__(COLS) void k_gae_tn_x4(const float* __restrict__ r,
             *reinterpret_cast<float4*>(&sR[buf][tile_row(i)][lc]) = rv[i];
             *reinterpret_cast<float4*>(&sV[buf][tile_row(i)][lc]) = vv[i];
             *reinterpret_cast<uint32_t*>(&sD[buf][tile_row(i)][lc]) = dv[i];
+            if (BOOT) *reinterpret_cast<float4*>(&sB[buf][tile_row(i)][lc]) = bv[i];
         }
     };
     load_regs(0);
@@ -280,8 +308,11 @@ __global__ __launch_bounds__(COLS) void k_gae_tn_x4(const float* __restrict__ r,
             if (base + row < 0) break;
             const double x = (double)sR[buf][row][64 * w + lane];
             const double v = (double)sV[buf][row][64 * w + lane];
-            const double nd = sD[buf][row][64 * w + lane] ? 0.0 : 1.0;
-            const double vnext = vn * nd;
+            const bool dn = sD[buf][row][64 * w + lane] != 0;
+            const double nd = dn ? 0.0 : 1.0;
+            double vnext;
+            if (BOOT) vnext = dn ? (double)sB[buf][row][64 * w + lane] : vn;
+            else vnext = vn * nd;
             const double gvn = gamma * vnext;
             const double delta = (x + gvn) - v;
             const double carry = (gl * nd) * a;
@@ -303,6 +334,21 @@ __global__ __launch_bounds__(COLS) void k_gae_tn_x4(const float* __restrict__ r,
         if (p + 1 < npass) park(buf ^ 1);
         __syncthreads();
     }
+}
+
+template <int COLS, int RW_ROWS>
+__global__ __launch_bounds__(COLS) void k_gae_tn_x4(const float* __restrict__ r, const uint8_t* __restrict__ done,
+                                                    const float* __restrict__ val, float* __restrict__ adv,
+                                                    float* __restrict__ ret, int64_t T, int64_t N, double gamma,
+                                                    double lambda) {
+    gae_tn_x4_scan<COLS, RW_ROWS, 0>(r, done, val, nullptr, adv, ret, T, N, gamma, lambda);
+}
+template <int COLS, int RW_ROWS>
+__global__ __launch_bounds__(COLS) void k_gae_boot_tn_x4(const float* __restrict__ r, const uint8_t* __restrict__ done,
+                                                         const float* __restrict__ val, const float* __restrict__ boot,
+                                                         float* __restrict__ adv, float* __restrict__ ret, int64_t T,
+                                                         int64_t N, double gamma, double lambda) {
+    gae_tn_x4_scan<COLS, RW_ROWS, 1>(r, done, val, boot, adv, ret, T, N, gamma, lambda);
 }
 
 int32_t launch_returns_tn(const float* r, const uint8_t* done, float* out, int64_t T, int64_t N, double discount,
@@ -363,6 +409,28 @@ int32_t launch_gae_tn(const float* r, const uint8_t* done, const float* values, 
     }
     dim3 grid((unsigned)((N + 63) / 64));
     hipLaunchKernelGGL(k_gae_tn, grid, dim3(64), 0, ppo_stream(), r, done, values, adv, ret, T, N, gamma, lambda);
+    HIP_TRY(hipGetLastError());
+    return PPO_OK;
+}
+
+// The scan with the bootstrap column.  Same split between the two forms and the same two widths as launch_gae_tn, so a
+// buffer takes the same form with and without the column.  The fourth tile makes a pass 26 B of LDS per element and buffer
+// pair: 128 columns x 16 rows and 256 columns x 8 rows are both 53 KB, three workgroups per CU (256 x 16 would be 106 KB,
+// one workgroup and so one wave per SIMD: nothing left to overlap the scan of one workgroup with the loads of another)
+int32_t launch_gae_boot_tn(const float* r, const uint8_t* done, const float* values, const float* boot, float* adv, float* ret,
+                           int64_t T, int64_t N, double gamma, double lambda) {
+    if (T <= 0 || N <= 0) return PPO_OK;
+    ProfScope ps("k_gae_boot_tn");
+    if (N % 4 == 0 && N >= 16384) {
+        const int cols = (N / 256 >= 1024) ? 256 : 128;
+        dim3 gridw((unsigned)((N + cols - 1) / cols));
+        if (cols == 256) hipLaunchKernelGGL((k_gae_boot_tn_x4<256, 8>), gridw, dim3(256), 0, ppo_stream(), r, done, values, boot, adv, ret, T, N, gamma, lambda);
+        else hipLaunchKernelGGL((k_gae_boot_tn_x4<128, 16>), gridw, dim3(128), 0, ppo_stream(), r, done, values, boot, adv, ret, T, N, gamma, lambda);
+        HIP_TRY(hipGetLastError());
+        return PPO_OK;
+    }
+    dim3 grid((unsigned)((N + 63) / 64));
+    hipLaunchKernelGGL(k_gae_boot_tn, grid, dim3(64), 0, ppo_stream(), r, done, values, boot, adv, ret, T, N, gamma, lambda);
     HIP_TRY(hipGetLastError());
     return PPO_OK;
 }

@@ -494,6 +494,72 @@ int32_t ppo_rollouts_compute_gae_critic(ppo_rollouts_t ro, ppo_env_t env, ppo_po
     return PPO_OK;
 }
 
+// the replay needs the built-in env's buffer: its template, and the snapshot (or the rows it can be read back from)
+static int32_t truncation_checks(const char* who, const ppo_rollouts_s* ro) {
+    ARG_CHECK(ro->T >= 1, "truncated: empty rollout buffer");
+    if (ro->V == 0 || !ro->tmpl.p) {
+        ppo_set_error(std::string(who) + ": the buffer has no env template, so its final states cannot be replayed; pass final values of your own to ppo_rollouts_compute_gae_boot");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    ARG_CHECK((ro->V == 32 || ro->V == 128) && ro->H == ro->V && ro->F == 2 * PPO_TPL, "truncated: shape mismatch");
+    ARG_CHECK(ro->compact ? ro->cstate.p != nullptr : ro->states.p != nullptr, "truncated: the buffer holds no states");
+    return PPO_OK;
+}
+
+// flags, ids and K (the one count that crosses), then the K post-step snapshots in ro->boot_cstate / boot_active
+static int32_t truncated_dev(ppo_rollouts_s* ro, int64_t* K) {
+    PPO_TRY(launch_truncated(ro, K));
+    ARG_CHECK(*K >= 0 && *K <= ro->T * ro->N, "truncated: count out of range");
+    PPO_TRY(ro->boot_cstate.alloc((size_t)*K * 2 * ro->V)); PPO_TRY(ro->boot_active.alloc((size_t)*K));
+    return launch_truncated_states(ro, *K, ro->boot_cstate.p, ro->boot_active.p);
+}
+
+int32_t ppo_rollouts_truncated(ppo_rollouts_t ro, uint8_t* truncated_out, int8_t* final_states_out, uint32_t* final_active_out,
+                               int64_t capacity, int64_t* count_out) {
+    ARG_CHECK(ro && count_out, "truncated: null argument");
+    ARG_CHECK(capacity >= 0, "truncated: negative capacity");
+    PPO_TRY(truncation_checks("truncated", ro));
+    int64_t K = 0;
+    PPO_TRY(truncated_dev(ro, &K));
+    *count_out = K;
+    if (truncated_out) PPO_TRY(d2h(truncated_out, ro->truncated.p, (size_t)ro->T * ro->N));
+    if (final_states_out || final_active_out) ARG_CHECK(capacity >= K, "truncated: capacity is below the number of truncated transitions");
+    if (final_states_out && K > 0) {       // observations re-derived from the snapshots on the device, <= 256 MiB at a time
+        const size_t per = (size_t)ro->H * ro->F, total = (size_t)K;
+        const size_t chunk = std::max<size_t>(1, std::min(total, ((size_t)256 << 20) / per));
+        PPO_TRY(ro->expand_tmp.alloc(chunk * per));
+        for (size_t o = 0; o < total; o += chunk) {
+            const size_t c = std::min(chunk, total - o);
+            PPO_TRY(launch_expand_states(ro->boot_cstate.p + o * 2 * ro->V, ro->boot_active.p + o, ro->tmpl.p, (int64_t)c, ro->V / 4, ro->expand_tmp.p));
+            PPO_TRY(d2h(final_states_out + o * per, ro->expand_tmp.p, c * per));
+        }
+    }
+    if (final_active_out) PPO_TRY(d2h(final_active_out, ro->boot_active.p, (size_t)K));
+    HIP_TRY(hipStreamSynchronize(ppo_stream()));
+    return PPO_OK;
+}
+
+int32_t ppo_rollouts_compute_gae_critic_boot(ppo_rollouts_t ro, ppo_env_t env, ppo_policy_t critic, double gamma, double lambda,
+                                             float* adv_out, float* lambda_returns_out, int64_t* n_truncated_out) {
+    ARG_CHECK(ro && critic, "compute_gae_critic_boot: null argument");
+    PPO_TRY(truncation_checks("compute_gae_critic_boot", ro));
+    PPO_TRY(compute_values_dev("compute_gae_critic_boot", ro, env, critic));
+    const size_t n = (size_t)ro->T * ro->N;
+    int64_t K = 0;
+    PPO_TRY(truncated_dev(ro, &K));
+    PPO_TRY(ro->boot_vals.alloc((size_t)K)); PPO_TRY(ro->boot.alloc((size_t)ro->capT * ro->N));
+    PPO_TRY(launch_value_predict(critic, nullptr, ro->boot_cstate.p, ro->boot_active.p, ro->tmpl.p, ro->V, K, ro->H, ro->boot_vals.p));
+    PPO_TRY(launch_boot_scatter(ro, ro->boot_vals.p, K, ro->boot.p));
+    PPO_TRY(ro->adv.alloc((size_t)ro->capT * ro->N)); PPO_TRY(ro->lam_ret.alloc((size_t)ro->capT * ro->N));
+    PPO_TRY(launch_gae_boot_tn(ro->rewards.p, ro->done.p, ro->values.p, ro->boot.p, ro->adv.p, ro->lam_ret.p, ro->T, ro->N, gamma, lambda));
+    ro->adv_T = ro->T; ro->boot_T = ro->T;
+    if (n_truncated_out) *n_truncated_out = K;
+    if (adv_out) PPO_TRY(d2h(adv_out, ro->adv.p, n));
+    if (lambda_returns_out) PPO_TRY(d2h(lambda_returns_out, ro->lam_ret.p, n));
+    HIP_TRY(hipStreamSynchronize(ppo_stream()));
+    return PPO_OK;
+}
+
 // the regression target column [T][N] of a value-training call
 static int32_t value_target(ppo_rollouts_s* ro, int32_t target, const float** col) {
     if (target != PPO_VTARGET_RETURNS && target != PPO_VTARGET_LAMBDA_RETURNS) { ppo_set_error("value target: unknown target"); return PPO_ERR_UNSUPPORTED; }
