@@ -167,6 +167,19 @@ __global__ __launch_bounds__(256) void k_flag_scatter(const uint8_t* __restrict_
     }
 }
 
+static int64_t compact_blocks(int64_t n) { return (n + CP_BLOCK - 1) / CP_BLOCK; }
+
+// ids[0 .. K) = the positions of the non-zero flags[0 .. n), ascending; *total = K.  counts: compact_blocks(n) words of
+// workspace; ids: room for n
+static int32_t launch_compact_flags(const uint8_t* flags, int64_t n, int32_t* counts, int32_t* ids, int64_t* total) {
+    const int64_t nb = compact_blocks(n);
+    hipLaunchKernelGGL(k_flag_count, dim3((unsigned)nb), dim3(256), 0, ppo_stream(), flags, n, counts);
+    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(256), 0, ppo_stream(), counts, nb, total);
+    hipLaunchKernelGGL(k_flag_scatter, dim3((unsigned)nb), dim3(256), 0, ppo_stream(), flags, n, counts, ids);
+    HIP_TRY(hipGetLastError());
+    return PPO_OK;
+}
+
 // boot[ids[k]] = vals[k] over a column the caller zeroed
 __global__ void k_boot_scatter(const int32_t* __restrict__ ids, const float* __restrict__ vals, int64_t K, float* __restrict__ boot) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -184,7 +197,7 @@ static BootView view_of(const ppo_rollouts_s* ro) {
 // checked: built-in env buffer (V = 32 or 128, F = 72), T >= 1
 int32_t launch_truncated(ppo_rollouts_s* ro, int64_t* K_out) {
     const int64_t n = ro->T * ro->N;
-    const int64_t nb = (n + CP_BLOCK - 1) / CP_BLOCK;
+    const int64_t nb = compact_blocks(n);
     PPO_TRY(ro->truncated.alloc((size_t)ro->capT * ro->N)); PPO_TRY(ro->trunc_ids.alloc((size_t)ro->capT * ro->N));
     PPO_TRY(ro->trunc_counts.alloc((size_t)nb + 4));         // [nb] block counts, then the 8-byte total (8-byte aligned)
     int64_t* total = reinterpret_cast<int64_t*>(ro->trunc_counts.p + ((nb + 1) & ~(int64_t)1));
@@ -196,11 +209,25 @@ int32_t launch_truncated(ppo_rollouts_s* ro, int64_t* K_out) {
         else hipLaunchKernelGGL(k_boot_flags<32>, g, dim3(GB_THREADS), 0, ppo_stream(), b, ro->done.p, ro->valid.p, n, ro->truncated.p);
         HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_flag_count, dim3((unsigned)nb), dim3(256), 0, ppo_stream(), ro->truncated.p, n, ro->trunc_counts.p);
-    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(256), 0, ppo_stream(), ro->trunc_counts.p, nb, total);
-    hipLaunchKernelGGL(k_flag_scatter, dim3((unsigned)nb), dim3(256), 0, ppo_stream(), ro->truncated.p, n, ro->trunc_counts.p, ro->trunc_ids.p);
-    HIP_TRY(hipGetLastError());
+    PPO_TRY(launch_compact_flags(ro->truncated.p, n, ro->trunc_counts.p, ro->trunc_ids.p, total));
     return d2h(K_out, total, 1);
+}
+
+// diagnostic for the tests (not part of include/ppo_hip.h), like ppo_debug_train_ratios: the compaction alone on host flags of
+// any length.  ids_out [n]: the ascending positions of the non-zero flags, then -1 (the device buffer is filled with 0xFF
+// bytes first, so a write behind the K-th entry shows)
+extern "C" int32_t ppo_debug_compact_flags(const uint8_t* flags, int64_t n, int32_t* ids_out, int64_t* K) {
+    PPO_TRY(ppo_device_synchronize());
+    ARG_CHECK(flags && ids_out && K && n >= 1 && n <= 0x7fffffff, "ppo_debug_compact_flags: null argument or n outside [1, 2^31)");
+    const int64_t nb = compact_blocks(n);
+    DevBuf<uint8_t> f; DevBuf<int32_t> counts, ids;
+    PPO_TRY(f.alloc((size_t)n)); PPO_TRY(ids.alloc((size_t)n)); PPO_TRY(counts.alloc((size_t)nb + 4));
+    int64_t* total = reinterpret_cast<int64_t*>(counts.p + ((nb + 1) & ~(int64_t)1));
+    PPO_TRY(h2d(f.p, flags, (size_t)n));
+    HIP_TRY(hipMemsetAsync(ids.p, 0xFF, (size_t)n * sizeof(int32_t), ppo_stream()));
+    PPO_TRY(launch_compact_flags(f.p, n, counts.p, ids.p, total));
+    PPO_TRY(d2h(K, total, 1));
+    return d2h(ids_out, ids.p, (size_t)n);
 }
 
 // post-step snapshots [K][2V] and active words [K] of the transitions launch_truncated listed

@@ -169,3 +169,39 @@ int32_t launch_value_moments(const float* target, const float* values, const uin
     HIP_TRY(hipGetLastError());
     return PPO_OK;
 }
+
+// ---- diagnostics for the tests (not part of include/ppo_hip.h), like ppo_debug_train_ratios: the three reductions on host
+// columns of any length, through the launch functions above and a workspace of the size the product path allocates
+static int32_t debug_stats_begin(const char* who, const void* a, const void* out, int64_t n, DevBuf<double>& part) {
+    PPO_TRY(ppo_device_synchronize());
+    if (!a || !out || n < 1) { ppo_set_error(std::string("AssertionError: ") + who + ": null argument or n < 1"); return PPO_ERR_ARG; }
+    return part.alloc(stats_part_doubles());
+}
+
+extern "C" int32_t ppo_debug_ratio_stats(const float* r, int64_t n, double eps, double* out4) {
+    DevBuf<double> part; DevBuf<float> col;
+    PPO_TRY(debug_stats_begin("ppo_debug_ratio_stats", r, out4, n, part));
+    PPO_TRY(col.alloc((size_t)n)); PPO_TRY(h2d(col.p, r, (size_t)n));
+    PPO_TRY(launch_ratio_stats(col.p, n, eps, part.p));
+    return d2h(out4, part.p, 4);
+}
+
+extern "C" int32_t ppo_debug_value_clip_stats(const float* delta, int64_t n, float c, double* out3) {
+    DevBuf<double> part; DevBuf<float> col;
+    PPO_TRY(debug_stats_begin("ppo_debug_value_clip_stats", delta, out3, n, part));
+    PPO_TRY(col.alloc((size_t)n)); PPO_TRY(h2d(col.p, delta, (size_t)n));
+    PPO_TRY(launch_value_clip_stats(col.p, n, c, part.p));
+    return d2h(out3, part.p, 3);
+}
+
+extern "C" int32_t ppo_debug_value_moments(const float* t, const float* v, const uint8_t* valid, int64_t first_id, int64_t n,
+                                           double* out5) {
+    DevBuf<double> part; DevBuf<float> tc, vc; DevBuf<uint8_t> on; DevBuf<int32_t> first;
+    PPO_TRY(debug_stats_begin("ppo_debug_value_moments", t, out5, n, part));
+    ARG_CHECK(v && valid && first_id >= 0 && first_id < n && n <= 0x7fffffff, "ppo_debug_value_moments: null argument or first_id outside [0, n)");
+    PPO_TRY(tc.alloc((size_t)n)); PPO_TRY(vc.alloc((size_t)n)); PPO_TRY(on.alloc((size_t)n)); PPO_TRY(first.alloc(1));
+    const int32_t i0 = (int32_t)first_id;
+    PPO_TRY(h2d(tc.p, t, (size_t)n)); PPO_TRY(h2d(vc.p, v, (size_t)n)); PPO_TRY(h2d(on.p, valid, (size_t)n)); PPO_TRY(h2d(first.p, &i0, 1));
+    PPO_TRY(launch_value_moments(tc.p, vc.p, on.p, first.p, n, part.p));
+    return d2h(out5, part.p, 5);
+}
