@@ -201,10 +201,10 @@ int32_t ppo_adam_set_epoch_count(ppo_adam_t opt, int64_t epochs);
  *   ClipValue (thresh)   ClipNorm (thresh)   WeightDecay (wd)   InvDecay (gamma)
  * The handle is a ppo_adam_t: ppo_train / ppo_step_batch / ppo_adam_apply take it unchanged; ppo_train's lr history is
  * the left-to-right product of the etas of the members that have one, after each epoch (the reference's ppo_train!
- * fails on a member without eta; the engine goes beyond it here).  A chain of Adam alone runs ppo_adam_create's
- * kernels.  ppo_adam_get_lr returns that product on a chain; ppo_adam_set_lr / _get_state / _set_state need a chain of
- * Adam alone (use the member calls below).  Unknown kind: PPO_ERR_UNSUPPORTED; bad n, duplicate kind, a NaN or
- * negative thresh: PPO_ERR_ARG. */
+ * fails on a member without eta; the engine goes beyond it here).  ppo_adam_create makes the chain of Adam alone, and
+ * such a chain runs the Adam kernels however it was made.  ppo_adam_get_lr returns that product on any chain;
+ * ppo_adam_set_lr / _get_state / _set_state are the member-0 calls below and need a chain of Adam alone.
+ * Unknown kind: PPO_ERR_UNSUPPORTED; bad n, duplicate kind, a NaN or negative thresh: PPO_ERR_ARG. */
 #define PPO_OPT_ADAM 1
 #define PPO_OPT_EXPDECAY 2
 #define PPO_OPT_DESCENT 3

@@ -508,50 +508,34 @@ int32_t ppo_policy_forward(ppo_policy_t pol, const int8_t* states, const uint32_
 }
 
 // ================================================================ optimiser
+// every handle is a Flux.Optimiser chain (include/ppo_hip.h); ppo_adam_* are the chain of Adam alone
 int32_t ppo_adam_create(ppo_policy_t pol, double eta, double beta1, double beta2, double eps, ppo_adam_t* out) {
-    ARG_CHECK(pol && out, "adam_create: null");
-    ppo_adam_s* o = new ppo_adam_s();
-    o->pol = pol; o->eta = eta; o->beta1 = beta1; o->beta2 = beta2; o->eps = eps;
-    o->beta_pow[0] = beta1; o->beta_pow[1] = beta2;
-    int32_t s;
-    if ((s = o->m.alloc(pol->np)) || (s = o->v.alloc(pol->np))) { delete o; return s; }
-    (void)hipMemsetAsync(o->m.p, 0, pol->np * 4, g_stream);
-    (void)hipMemsetAsync(o->v.p, 0, pol->np * 4, g_stream);
-    *out = o;
-    return PPO_OK;
+    const int32_t kind = PPO_OPT_ADAM;
+    const double hyper[5] = {eta, beta1, beta2, eps, 0.0};
+    return ppo_optimiser_create(pol, 1, &kind, hyper, out);
 }
 int32_t ppo_adam_destroy(ppo_adam_t opt) { if (opt) { (void)hipStreamSynchronize(g_stream); delete opt; } return PPO_OK; }
 int32_t ppo_adam_get_lr(ppo_adam_t opt, double* eta) { ARG_CHECK(opt && eta, "null"); *eta = opt->lr(); return PPO_OK; }
 int32_t ppo_adam_set_lr(ppo_adam_t opt, double eta) {
     ARG_CHECK(opt && opt->adam_only(), "adam_set_lr: null, or a chain (ppo_optimiser_set_eta)");
-    opt->eta = eta;
-    return PPO_OK;
+    return ppo_optimiser_set_eta(opt, 0, eta);
 }
 int32_t ppo_adam_get_state(ppo_adam_t opt, float* m, float* v, double* bp) {
     ARG_CHECK(opt && opt->adam_only(), "adam_get_state: null, or a chain (ppo_optimiser_get_state)");
-    if (m) PPO_TRY(flat_to_host(opt->pol, m, opt->m.p));
-    if (v) PPO_TRY(flat_to_host(opt->pol, v, opt->v.p));
-    if (bp) { bp[0] = opt->beta_pow[0]; bp[1] = opt->beta_pow[1]; }
-    return PPO_OK;
+    return ppo_optimiser_get_state(opt, 0, m, v, bp, nullptr);
 }
 int32_t ppo_adam_set_state(ppo_adam_t opt, const float* m, const float* v, const double* bp) {
     ARG_CHECK(opt && opt->adam_only(), "adam_set_state: null, or a chain (ppo_optimiser_set_state)");
-    if (m) PPO_TRY(flat_to_device(opt->pol, m, opt->m.p));
-    if (v) PPO_TRY(flat_to_device(opt->pol, v, opt->v.p));
-    if (bp) { opt->beta_pow[0] = bp[0]; opt->beta_pow[1] = bp[1]; }
-    return PPO_OK;
+    return ppo_optimiser_set_state(opt, 0, m, v, bp, nullptr);
 }
 
 int32_t ppo_adam_get_epoch_count(ppo_adam_t opt, int64_t* epochs) { ARG_CHECK(opt && epochs, "null"); *epochs = opt->epochs_done; return PPO_OK; }
 int32_t ppo_adam_set_epoch_count(ppo_adam_t opt, int64_t epochs) { ARG_CHECK(opt && epochs >= 0, "bad epoch count"); opt->epochs_done = epochs; return PPO_OK; }
 
-// Flux.Optimiser chain (include/ppo_hip.h): the Adam member keeps its hyper-parameters and state in the handle's own Adam
-// fields, so a chain of Adam alone is exactly a ppo_adam_create handle
 double ppo_adam_s::lr() const {
-    if (nmem == 0) return eta;
     double p = 1.0;                                     // get_optimizer_learning_rate: prod(opt.eta for opt in optimizer)
     for (int j = 0; j < nmem; ++j)                      // the members without eta are skipped (the reference would fail)
-        if (has_eta(mem[j].kind)) p *= mem[j].kind == PPO_OPT_ADAM ? eta : mem[j].eta;
+        if (has_eta(mem[j].kind)) p *= mem[j].eta;
     return p;
 }
 
@@ -561,6 +545,12 @@ static int32_t check_hyper(int32_t kind, const double* h) {
         ARG_CHECK(h[2] >= 1 && h[2] == std::floor(h[2]) && h[4] == std::floor(h[4]), "ExpDecay: integer decay_step >= 1 and start");
     if (kind == PPO_OPT_CLIPVALUE || kind == PPO_OPT_CLIPNORM)
         ARG_CHECK(h[0] >= 0, std::string(kind == PPO_OPT_CLIPNORM ? "ClipNorm" : "ClipValue") + ": thresh must be >= 0 (and not NaN)");
+    return PPO_OK;
+}
+
+static int32_t alloc_zeroed(DevBuf<float>& b, size_t n) {
+    PPO_TRY(b.alloc(n));
+    (void)hipMemsetAsync(b.p, 0, n * 4, g_stream);
     return PPO_OK;
 }
 
@@ -577,28 +567,19 @@ int32_t ppo_optimiser_create(ppo_policy_t pol, int32_t n, const int32_t* kinds, 
     }
     ppo_adam_s* o = new ppo_adam_s();
     o->pol = pol; o->nmem = n;
-    o->eta = 0.0; o->beta1 = o->beta2 = o->eps = 0.0; o->beta_pow[0] = o->beta_pow[1] = 0.0;
     int32_t s = PPO_OK;
     for (int32_t j = 0; j < n && s == PPO_OK; ++j) {
         const double* h = hyper + 5 * (size_t)j;
         OptMember& e = o->mem[j];
         e.kind = kinds[j];
-        if (e.kind == PPO_OPT_ADAM) {
-            o->eta = h[0]; o->beta1 = h[1]; o->beta2 = h[2]; o->eps = h[3];
-            o->beta_pow[0] = h[1]; o->beta_pow[1] = h[2];
-            if ((s = o->m.alloc(pol->np)) || (s = o->v.alloc(pol->np))) break;
-            (void)hipMemsetAsync(o->m.p, 0, pol->np * 4, g_stream);
-            (void)hipMemsetAsync(o->v.p, 0, pol->np * 4, g_stream);
-        } else {
-            e.eta = h[0]; e.h1 = h[1]; e.h2 = h[2]; e.h3 = h[3]; e.h4 = h[4];
-            if (e.kind == PPO_OPT_MOMENTUM || e.kind == PPO_OPT_NESTEROV || e.kind == PPO_OPT_RMSPROP) {
-                if ((s = e.s.alloc(pol->np))) break;
-                (void)hipMemsetAsync(e.s.p, 0, pol->np * 4, g_stream);
-            }
-            if (e.kind == PPO_OPT_CLIPNORM) {
-                o->clip_slots = clip_slot_count(pol);
-                if ((s = o->clip_d.alloc(pol->np)) || (s = o->clip_part.alloc(2 * (size_t)o->clip_slots))) break;
-            }
+        e.eta = h[0]; e.h1 = h[1]; e.h2 = h[2]; e.h3 = h[3]; e.h4 = h[4];
+        const bool adam = e.kind == PPO_OPT_ADAM;
+        if (adam) { e.beta_pow[0] = h[1]; e.beta_pow[1] = h[2]; }
+        if (adam || e.kind == PPO_OPT_MOMENTUM || e.kind == PPO_OPT_NESTEROV || e.kind == PPO_OPT_RMSPROP) s = alloc_zeroed(e.s, pol->np);
+        if (adam && s == PPO_OK) s = alloc_zeroed(e.s1, pol->np);
+        if (e.kind == PPO_OPT_CLIPNORM) {
+            o->clip_slots = clip_slot_count(pol);
+            if ((s = o->clip_d.alloc(pol->np)) || (s = o->clip_part.alloc(2 * (size_t)o->clip_slots))) break;
         }
     }
     if (s != PPO_OK) { delete o; return s; }
@@ -607,67 +588,55 @@ int32_t ppo_optimiser_create(ppo_policy_t pol, int32_t n, const int32_t* kinds, 
 }
 
 static int32_t chain_member(ppo_adam_t opt, int32_t member) {
-    ARG_CHECK(opt && member >= 0 && member < std::max(opt->nmem, 1), "optimiser: null handle or member out of range");
+    ARG_CHECK(opt && member >= 0 && member < opt->nmem, "optimiser: null handle or member out of range");
     return PPO_OK;
 }
-static int32_t kind_of(ppo_adam_t opt, int32_t member) { return opt->nmem == 0 ? PPO_OPT_ADAM : opt->mem[member].kind; }
 
 int32_t ppo_optimiser_get_eta(ppo_adam_t opt, int32_t member, double* eta) {
     PPO_TRY(chain_member(opt, member));
     ARG_CHECK(eta, "null");
-    ARG_CHECK(has_eta(kind_of(opt, member)), "optimiser_get_eta: the member has no eta (ppo_optimiser_get_hyper)");
-    *eta = kind_of(opt, member) == PPO_OPT_ADAM ? opt->eta : opt->mem[member].eta;
+    ARG_CHECK(has_eta(opt->mem[member].kind), "optimiser_get_eta: the member has no eta (ppo_optimiser_get_hyper)");
+    *eta = opt->mem[member].eta;
     return PPO_OK;
 }
 int32_t ppo_optimiser_set_eta(ppo_adam_t opt, int32_t member, double eta) {
     PPO_TRY(chain_member(opt, member));
-    ARG_CHECK(has_eta(kind_of(opt, member)), "optimiser_set_eta: the member has no eta (ppo_optimiser_set_hyper)");
-    (kind_of(opt, member) == PPO_OPT_ADAM ? opt->eta : opt->mem[member].eta) = eta;
+    ARG_CHECK(has_eta(opt->mem[member].kind), "optimiser_set_eta: the member has no eta (ppo_optimiser_set_hyper)");
+    opt->mem[member].eta = eta;
     return PPO_OK;
 }
 int32_t ppo_optimiser_get_hyper(ppo_adam_t opt, int32_t member, double* h) {
     PPO_TRY(chain_member(opt, member));
     ARG_CHECK(h, "null");
-    if (kind_of(opt, member) == PPO_OPT_ADAM) { h[0] = opt->eta; h[1] = opt->beta1; h[2] = opt->beta2; h[3] = opt->eps; h[4] = 0.0; }
-    else { const OptMember& e = opt->mem[member]; h[0] = e.eta; h[1] = e.h1; h[2] = e.h2; h[3] = e.h3; h[4] = e.h4; }
+    const OptMember& e = opt->mem[member];
+    h[0] = e.eta; h[1] = e.h1; h[2] = e.h2; h[3] = e.h3; h[4] = e.h4;
     return PPO_OK;
 }
 int32_t ppo_optimiser_set_hyper(ppo_adam_t opt, int32_t member, const double* h) {
     PPO_TRY(chain_member(opt, member));
     ARG_CHECK(h, "null");
-    const int32_t k = kind_of(opt, member);
-    PPO_TRY(check_hyper(k, h));
-    if (k == PPO_OPT_ADAM) { opt->eta = h[0]; opt->beta1 = h[1]; opt->beta2 = h[2]; opt->eps = h[3]; }   // beta powers stay
-    else { OptMember& e = opt->mem[member]; e.eta = h[0]; e.h1 = h[1]; e.h2 = h[2]; e.h3 = h[3]; e.h4 = h[4]; }
+    OptMember& e = opt->mem[member];
+    PPO_TRY(check_hyper(e.kind, h));
+    e.eta = h[0]; e.h1 = h[1]; e.h2 = h[2]; e.h3 = h[3]; e.h4 = h[4];   // Adam: the beta powers stay
     return PPO_OK;
 }
 int32_t ppo_optimiser_get_state(ppo_adam_t opt, int32_t member, float* s0, float* s1, double* scalars2, int64_t* count) {
     PPO_TRY(chain_member(opt, member));
-    const int32_t k = kind_of(opt, member);
-    OptMember* e = opt->nmem ? &opt->mem[member] : nullptr;
-    if (k == PPO_OPT_ADAM) {
-        if (s0) PPO_TRY(flat_to_host(opt->pol, s0, opt->m.p));
-        if (s1) PPO_TRY(flat_to_host(opt->pol, s1, opt->v.p));
-        if (scalars2) { scalars2[0] = opt->beta_pow[0]; scalars2[1] = opt->beta_pow[1]; }
-    } else if (s0 && e->s.p) {
-        PPO_TRY(flat_to_host(opt->pol, s0, e->s.p));
-    }
-    if (count) *count = (k == PPO_OPT_EXPDECAY || k == PPO_OPT_INVDECAY) ? e->count : 0;
+    const OptMember& e = opt->mem[member];
+    if (s0 && e.s.p) PPO_TRY(flat_to_host(opt->pol, s0, e.s.p));
+    if (s1 && e.s1.p) PPO_TRY(flat_to_host(opt->pol, s1, e.s1.p));
+    if (scalars2 && e.kind == PPO_OPT_ADAM) { scalars2[0] = e.beta_pow[0]; scalars2[1] = e.beta_pow[1]; }
+    if (count) *count = e.count;                        // 0 for every member but ExpDecay / InvDecay
     return PPO_OK;
 }
 int32_t ppo_optimiser_set_state(ppo_adam_t opt, int32_t member, const float* s0, const float* s1, const double* scalars2,
                                 const int64_t* count) {
     PPO_TRY(chain_member(opt, member));
-    const int32_t k = kind_of(opt, member);
-    OptMember* e = opt->nmem ? &opt->mem[member] : nullptr;
-    if (k == PPO_OPT_ADAM) {
-        if (s0) PPO_TRY(flat_to_device(opt->pol, s0, opt->m.p));
-        if (s1) PPO_TRY(flat_to_device(opt->pol, s1, opt->v.p));
-        if (scalars2) { opt->beta_pow[0] = scalars2[0]; opt->beta_pow[1] = scalars2[1]; }
-    } else if (s0 && e->s.p) {
-        PPO_TRY(flat_to_device(opt->pol, s0, e->s.p));
-    }
-    if (count && (k == PPO_OPT_EXPDECAY || k == PPO_OPT_INVDECAY)) { ARG_CHECK(*count >= 0, "negative update count"); e->count = *count; }
+    OptMember& e = opt->mem[member];
+    if (s0 && e.s.p) PPO_TRY(flat_to_device(opt->pol, s0, e.s.p));
+    if (s1 && e.s1.p) PPO_TRY(flat_to_device(opt->pol, s1, e.s1.p));
+    if (scalars2 && e.kind == PPO_OPT_ADAM) { e.beta_pow[0] = scalars2[0]; e.beta_pow[1] = scalars2[1]; }
+    if (count && (e.kind == PPO_OPT_EXPDECAY || e.kind == PPO_OPT_INVDECAY)) { ARG_CHECK(*count >= 0, "negative update count"); e.count = *count; }
     return PPO_OK;
 }
 

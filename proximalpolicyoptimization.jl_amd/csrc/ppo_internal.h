@@ -163,26 +163,24 @@ struct ppo_policy_s {
     std::vector<double> vstats_clip, vstats_msq;   // the latest ppo_value_train, per epoch: clip_fraction, mean_sq_change
 };
 
-// one member of a Flux.Optimiser chain (ppo_optimiser_create) other than Adam, whose hyper-parameters and state are the
-// handle's own eta / beta / m / v / beta_pow fields
+// one member of a Flux.Optimiser chain: its hyper row of ppo_optimiser_create and its state
 struct OptMember {
     int32_t kind = 0;                  // PPO_OPT_*
-    double eta = 0.0, h1 = 0.0, h2 = 0.0, h3 = 0.0, h4 = 0.0;   // hyper rows of ppo_optimiser_create (eta in front; the
-                                       // members without eta keep thresh / wd / gamma in its place)
+    double eta = 0.0, h1 = 0.0, h2 = 0.0, h3 = 0.0, h4 = 0.0;   // the hyper row (eta in front; the members without eta keep
+                                       // thresh / wd / gamma in its place): Adam eta, beta1, beta2, eps
     int64_t count = 0;                 // ExpDecay / InvDecay: update! calls seen
-    DevBuf<float> s;                   // Momentum / Nesterov velocity, RMSProp acc
+    DevBuf<float> s, s1;               // Adam m, v; Momentum / Nesterov velocity and RMSProp acc (s alone)
+    double beta_pow[2] = {0.0, 0.0};   // Adam: beta1^t, beta2^t of the next step
 };
 
 inline bool has_eta(int32_t kind) { return kind >= PPO_OPT_ADAM && kind <= PPO_OPT_RMSPROP; }   // ClipValue .. InvDecay have none
 
+// every optimiser handle is a chain: ppo_adam_create makes the chain of Adam alone that ppo_optimiser_create makes
 struct ppo_adam_s {
     ppo_policy_s* pol;
-    double eta, beta1, beta2, eps;
-    double beta_pow[2];
     int64_t epochs_done = 0;           // epochs trained through ppo_train: keys the minibatch permutation with the seed
-    DevBuf<float> m, v;
-    // chain (ppo_optimiser_create): nmem members in chain order; 0 = a ppo_adam_create handle.  A chain of Adam alone
-    // runs the Adam kernels (k_reduce_adam / k_adam); every other chain the chain kernels (k_reduce_chain / k_chain_update)
+    // nmem = 1..4 members in chain order.  A chain of Adam alone runs the Adam kernels (k_reduce_adam / k_adam); every
+    // other chain the chain kernels (k_reduce_chain / k_chain_update)
     int32_t nmem = 0;
     OptMember mem[4];
     // ClipNorm member: the update splits in two launches around it (ppo_optim.hip): D of the members before it, and
@@ -190,7 +188,7 @@ struct ppo_adam_s {
     DevBuf<float> clip_d;              // [np]
     DevBuf<double> clip_part;          // [clip_slots][2]
     int64_t clip_slots = 0;
-    bool adam_only() const { return nmem == 0 || (nmem == 1 && mem[0].kind == PPO_OPT_ADAM); }
+    bool adam_only() const { return nmem == 1 && mem[0].kind == PPO_OPT_ADAM; }
     double lr() const;                 // left-to-right product of the members' etas (get_optimizer_learning_rate)
 };
 
@@ -255,10 +253,11 @@ void disk_sink_destroy(DiskSink* s);
 // ---------------------------------------------------------------- packed layout sizes
 // one gradient slab: [dW of the L-1 hidden->hidden layers][dW1, input padded to 32][db1][db of the L-1 layers][dW3][db3 + pad]
 // (L == 2: exactly the round-1 layout W2, W1, b1, b2, W3, b3)
-static inline size_t slab_floats(int F, int HID, int L = 2) {
+static inline size_t slab_elems(int F, int HID, int L = 2) {    // without the padding: what the slab reduction walks
     const int FP = ((F + 31) / 32) * 32;
-    return (size_t)(L - 1) * HID * HID + (size_t)HID * FP + (size_t)HID * L + (size_t)HID * PPO_OUT + 64;
+    return (size_t)(L - 1) * HID * HID + (size_t)HID * FP + (size_t)HID * L + (size_t)HID * PPO_OUT + 4;
 }
+static inline size_t slab_floats(int F, int HID, int L = 2) { return slab_elems(F, HID, L) + 60; }
 
 // ---------------------------------------------------------------- kernel launchers (defined in the .hip files)
 int32_t launch_returns_tn(const float* r, const uint8_t* done, float* out, int64_t T, int64_t N,

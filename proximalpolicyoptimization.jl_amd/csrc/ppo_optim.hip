@@ -81,15 +81,15 @@ __device__ __forceinline__ void fuse_one(const ClipFuse&, const ParamLayout&, co
 // the four partial sums meet in LDS and are added in a fixed order.  4x the waves of a one-thread-per-element
 // layout: the 87 MB slab walk needs the memory-level parallelism (341 blocks of one wave per SIMD did 3.3 TB/s).
 // nwg_w slabs carry weight-gradient partials, nwg_s slabs the small-gradient tails (equal for the fused backward).
-// Fuse: AdamFuse (k_grad_reduce<AdamFuse>, timed as k_grad_reduce / k_reduce_adam) or ChainFuse (k_grad_reduce<ChainFuse>,
-// timed as k_reduce_chain); the Adam instantiation is the instruction stream of the former non-template kernel
+// Fuse: AdamFuse (k_grad_reduce<AdamFuse>, timed as k_grad_reduce / k_reduce_adam), ChainFuse (timed as k_reduce_chain) or
+// ClipFuse (k_reduce_clip)
 template <typename Fuse>
 __global__ __launch_bounds__(256) void k_grad_reduce(const float* __restrict__ slabs, size_t slab_stride, int nwg_w, int nwg_s, ParamLayout L,
                                                      float* __restrict__ grad, const double* __restrict__ terms, int64_t B,
                                                      double inv_Bg, double entropy_weight, Fuse A, PackPtrs P) {
     if (blockIdx.x == gridDim.x - 1) {          // the extra last block reduces the per-sample loss terms
         loss_reduce_block(terms, B, inv_Bg, entropy_weight, grad + L.np);
-        if (A.on && A.hist2 && threadIdx.x == 0) { A.hist2[0] = grad[L.np]; A.hist2[1] = grad[L.np + 1]; }   // per-batch loss history (k_adam's job otherwise)
+        if (A.on && A.hist2 && threadIdx.x == 0) { A.hist2[0] = grad[L.np]; A.hist2[1] = grad[L.np + 1]; }   // per-batch loss history (k_opt_update's job otherwise)
         return;
     }
     __shared__ float part[4][64];
@@ -288,14 +288,22 @@ __device__ __forceinline__ void pack_one(const ParamLayout& L, const PackPtrs& P
     }
 }
 
-// Flux legacy Adam on one parameter (the arithmetic of k_adam), then its packed copies
-__device__ __forceinline__ void adam_one(const AdamFuse& A, const ParamLayout& L, const PackPtrs& P, int64_t i, float g) {
+// Flux legacy Adam on one element: element arithmetic in Float64 (Float64 hyper-parameters against Float32 arrays), Float32
+// stores; the bias-correction powers bp1, bp2 are tracked in Float64 on the host.  Returns D (x -= D is the caller's)
+__device__ __forceinline__ float adam_delta(float* m, float* v, int64_t i, float g, double eta, double beta1, double beta2,
+                                            double eps, double bp1, double bp2) {
     const double gd = (double)g;
-    const float mn = (float)(A.beta1 * (double)A.m[i] + (1.0 - A.beta1) * gd);
-    const float vn = (float)(A.beta2 * (double)A.v[i] + ((1.0 - A.beta2) * gd) * gd);
-    A.m[i] = mn; A.v[i] = vn;
-    const double delta = (double)mn / (1.0 - A.bp1) / (sqrt((double)vn / (1.0 - A.bp2)) + A.eps) * A.eta;
-    const float x = A.params[i] - (float)delta;
+    const float mn = (float)(beta1 * (double)m[i] + (1.0 - beta1) * gd);
+    const float vn = (float)(beta2 * (double)v[i] + ((1.0 - beta2) * gd) * gd);
+    m[i] = mn; v[i] = vn;
+    return (float)((double)mn / (1.0 - bp1) / (sqrt((double)vn / (1.0 - bp2)) + eps) * eta);
+}
+
+// Adam on one parameter, then its packed copies.  x is loaded after adam_delta's m, v stores, which the compiler must take to
+// alias it: written as one expression the load moves in front of them and k_grad_reduce<AdamFuse> schedules differently
+__device__ __forceinline__ void adam_one(const AdamFuse& A, const ParamLayout& L, const PackPtrs& P, int64_t i, float g) {
+    const float d = adam_delta(A.m, A.v, i, g, A.eta, A.beta1, A.beta2, A.eps, A.bp1, A.bp2);
+    const float x = A.params[i] - d;
     A.params[i] = x;
     pack_one(L, P, i, x);
 }
@@ -304,24 +312,6 @@ __global__ void k_pack_params(const float* __restrict__ params, ParamLayout L, P
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= L.np) return;
     pack_one(L, P, i, params[i]);
-}
-
-// Flux legacy Adam: element arithmetic in Float64 (Float64 hyper-parameters against Float32
-// arrays), Float32 stores; bias-correction powers tracked in Float64 on the host.
-__global__ void k_adam(float* __restrict__ params, const float* __restrict__ grad, float* __restrict__ m,
-                       float* __restrict__ v, ParamLayout L, PackPtrs P, double eta, double beta1, double beta2,
-                       double eps, double bp1, double bp2, float* __restrict__ hist2) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (hist2 && i < 2) hist2[i] = grad[L.np + i];       // per-batch loss history (after any all-reduce)
-    if (i >= L.np) return;
-    const double gd = (double)grad[i];
-    const float mn = (float)(beta1 * (double)m[i] + (1.0 - beta1) * gd);
-    const float vn = (float)(beta2 * (double)v[i] + ((1.0 - beta2) * gd) * gd);
-    m[i] = mn; v[i] = vn;
-    const double delta = (double)mn / (1.0 - bp1) / (sqrt((double)vn / (1.0 - bp2)) + eps) * eta;
-    const float x = params[i] - (float)delta;
-    params[i] = x;
-    pack_one(L, P, i, x);
 }
 
 // Flux.update! through a chain on one parameter: D = g, D = apply!(member, x, D) in chain order, each member's D rounded
@@ -334,13 +324,8 @@ __device__ __forceinline__ float chain_delta(const ChainFuse& C, int64_t i, floa
         const double* c = C.c[j];
         const double dd = (double)d;
         const int kind = C.kind[j];
-        if (kind == PPO_OPT_ADAM) {                                        // the arithmetic of k_adam
-            float* m = C.s0[j];
-            float* v = C.s1[j];
-            const float mn = (float)(c[1] * (double)m[i] + (1.0 - c[1]) * dd);
-            const float vn = (float)(c[2] * (double)v[i] + ((1.0 - c[2]) * dd) * dd);
-            m[i] = mn; v[i] = vn;
-            d = (float)((double)mn / (1.0 - c[4]) / (sqrt((double)vn / (1.0 - c[5])) + c[3]) * c[0]);
+        if (kind == PPO_OPT_ADAM) {
+            d = adam_delta(C.s0[j], C.s1[j], i, d, c[0], c[1], c[2], c[3], c[4], c[5]);
         } else if (kind == PPO_OPT_EXPDECAY || kind == PPO_OPT_DESCENT) {  // D .*= eta
             d = (float)(dd * c[0]);
         } else if (kind == PPO_OPT_MOMENTUM) {                             // v = rho v - eta D; D = -v
@@ -398,12 +383,14 @@ __device__ __forceinline__ void chain_one(const ChainFuse& C, const ParamLayout&
     pack_one(L, P, i, x);
 }
 
-// standalone chain update (all-reduce hook path, ppo_step_batch, ppo_adam_apply): k_adam with the chain
-__global__ void k_chain_update(const float* __restrict__ grad, ParamLayout L, PackPtrs P, ChainFuse C) {
+// standalone update (all-reduce hook path, ppo_step_batch, ppo_adam_apply): k_opt_update<AdamFuse> is timed as k_adam,
+// k_opt_update<ChainFuse> as k_chain_update
+template <typename Fuse>
+__global__ void k_opt_update(const float* __restrict__ grad, ParamLayout L, PackPtrs P, Fuse A) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (C.hist2 && i < 2) C.hist2[i] = grad[L.np + i];   // per-batch loss history (after any all-reduce)
+    if (A.hist2 && i < 2) A.hist2[i] = grad[L.np + i];   // per-batch loss history (after any all-reduce)
     if (i >= L.np) return;
-    chain_one(C, L, P, i, grad[i]);
+    fuse_one(A, L, P, i, grad[i]);
 }
 
 // ClipNorm phase 1 behind an all-reduce (hook path, ppo_step_batch, ppo_adam_apply): slot = Flux-order index / 32
@@ -509,7 +496,8 @@ int32_t launch_pack_params(ppo_policy_s* p) {
 }
 
 // one optimiser step of a chain: the members' scalars for this step (ExpDecay advances its counter and, on schedule, its eta
-// first: Flux's apply! does it before it scales the first array), then the Adam member's beta powers after the launch
+// first: Flux's apply! does it before it scales the first array); the Adam member's beta powers advance after the launch
+// (chain_done)
 static ChainFuse chain_step(ppo_adam_s* o, float* hist2) {
     ChainFuse C = {};
     C.params = o->pol->params.p; C.hist2 = hist2; C.on = 1; C.n = o->nmem;
@@ -518,10 +506,6 @@ static ChainFuse chain_step(ppo_adam_s* o, float* hist2) {
         double* c = C.c[j];
         C.kind[j] = e.kind;
         switch (e.kind) {
-        case PPO_OPT_ADAM:
-            c[0] = o->eta; c[1] = o->beta1; c[2] = o->beta2; c[3] = o->eps; c[4] = o->beta_pow[0]; c[5] = o->beta_pow[1];
-            C.s0[j] = o->m.p; C.s1[j] = o->v.p;
-            break;
         case PPO_OPT_EXPDECAY: {   // h1 decay, h2 decay_step, h3 clip, h4 start
             const int64_t n = ++e.count, st = (int64_t)e.h2, start = (int64_t)e.h4;
             // Flux decays when exactly one array's counter is on schedule: once per step for decay_step > 1; with decay_step
@@ -537,9 +521,10 @@ static ChainFuse chain_step(ppo_adam_s* o, float* hist2) {
         }
         case PPO_OPT_CLIPNORM:     // not a chain_delta member: split_at_clip takes it out (thresh: ClipMap)
             break;
-        default:                   // Descent (eta), Momentum / Nesterov (eta, rho), RMSProp (eta, rho, epsilon), ClipValue
-            c[0] = e.eta; c[1] = e.h1; c[2] = e.h2;   // (thresh), WeightDecay (wd)
-            C.s0[j] = e.s.p;
+        default:                   // the hyper row as it stands and the state arrays the member has: Adam (with its beta
+                                   // powers), Descent, Momentum, Nesterov, RMSProp, ClipValue (thresh), WeightDecay (wd)
+            c[0] = e.eta; c[1] = e.h1; c[2] = e.h2; c[3] = e.h3; c[4] = e.beta_pow[0]; c[5] = e.beta_pow[1];
+            C.s0[j] = e.s.p; C.s1[j] = e.s1.p;
             break;
         }
     }
@@ -553,14 +538,10 @@ static int clip_position(const ppo_adam_s* o) {
     return -1;
 }
 
-static size_t slab_total(const ParamLayout& L) {
-    return (size_t)L.NL2 * L.HID * L.HID + (size_t)L.HID * L.FP + (size_t)L.HID * (1 + L.NL2) + (size_t)L.HID * 4 + 4;
-}
-
 // slots: k_grad_reduce<ClipFuse> writes two per 64-element block, k_chain_clip1 eight per 256-thread block
 int64_t clip_slot_count(const ppo_policy_s* p) {
     const ParamLayout L = layout_of(p);
-    return std::max<int64_t>(2 * (int64_t)((slab_total(L) + 63) / 64), 8 * ((L.np + 255) / 256));
+    return std::max<int64_t>(2 * (int64_t)((slab_elems(p->F, p->HID, p->L) + 63) / 64), 8 * ((L.np + 255) / 256));
 }
 
 // the chain of this step (chain_step) split around its ClipNorm at position c: members [0, c) for phase 1, (c, n) for phase 2
@@ -612,88 +593,84 @@ static int32_t launch_clip_apply(ppo_adam_s* o, const ParamLayout& L, const Chai
     HIP_TRY(hipGetLastError());
     return PPO_OK;
 }
-static void chain_done(ppo_adam_s* o) {
-    for (int j = 0; j < o->nmem; ++j)
-        if (o->mem[j].kind == PPO_OPT_ADAM) { o->beta_pow[0] *= o->beta1; o->beta_pow[1] *= o->beta2; }
+
+// this step's ClipFuse (members before the ClipNorm) and the members after it
+static ClipFuse clip_fuse(ppo_adam_s* o, float* hist2, ChainFuse& after) {
+    ClipFuse A = {};
+    split_at_clip(chain_step(o, hist2), clip_position(o), A.C, after);
+    A.hist2 = hist2; A.on = 1; A.dbuf = o->clip_d.p; A.part = o->clip_part.p;
+    return A;
 }
 
-// slab reduction + (one extra block) loss-term reduction in a single launch
-int32_t launch_grad_reduce(ppo_policy_s* p, int64_t B, int64_t B_global, double entropy_weight, ppo_adam_s* fuse, float* hist2) {
-    ParamLayout L = layout_of(p);
-    const size_t total = (size_t)L.NL2 * L.HID * L.HID + (size_t)L.HID * L.FP + (size_t)L.HID * (1 + L.NL2) + (size_t)L.HID * 4 + 4;
-    if (fuse && clip_position(fuse) >= 0) {
-        ClipFuse A = {};
-        ChainFuse after;
-        split_at_clip(chain_step(fuse, hist2), clip_position(fuse), A.C, after);
-        A.hist2 = hist2; A.on = 1; A.dbuf = fuse->clip_d.p; A.part = fuse->clip_part.p;
-        {
-            ProfScope ps("k_reduce_clip");
-            hipLaunchKernelGGL(k_grad_reduce<ClipFuse>, dim3((unsigned)((total + 63) / 64) + 1), dim3(256), 0, ppo_stream(), p->slabs.p,
-                               slab_floats(p->F, p->HID, p->L), p->nwg_bwd, p->nwg_small ? p->nwg_small : p->nwg_bwd, L, p->grad.p, p->loss_terms.p, B,
-                               1.0 / (double)B_global, entropy_weight, A, packs_of(p));
-            HIP_TRY(hipGetLastError());
-        }
-        PPO_TRY(launch_clip_apply(fuse, L, after, true));
-        chain_done(fuse);
-        return PPO_OK;
-    }
-    if (fuse && !fuse->adam_only()) {
-        const ChainFuse C = chain_step(fuse, hist2);
-        ProfScope ps("k_reduce_chain");
-        hipLaunchKernelGGL(k_grad_reduce<ChainFuse>, dim3((unsigned)((total + 63) / 64) + 1), dim3(256), 0, ppo_stream(), p->slabs.p,
-                           slab_floats(p->F, p->HID, p->L), p->nwg_bwd, p->nwg_small ? p->nwg_small : p->nwg_bwd, L, p->grad.p, p->loss_terms.p, B, 1.0 / (double)B_global,
-                           entropy_weight, C, packs_of(p));
-        HIP_TRY(hipGetLastError());
-        chain_done(fuse);
-        return PPO_OK;
-    }
+// a chain of Adam alone: the Adam kernels' argument
+static AdamFuse adam_fuse(const ppo_adam_s* o, float* hist2) {
+    const OptMember& e = o->mem[0];
     AdamFuse A = {};
-    if (fuse) {
-        A.params = p->params.p; A.m = fuse->m.p; A.v = fuse->v.p; A.eta = fuse->eta; A.beta1 = fuse->beta1; A.beta2 = fuse->beta2;
-        A.eps = fuse->eps; A.bp1 = fuse->beta_pow[0]; A.bp2 = fuse->beta_pow[1]; A.hist2 = hist2; A.on = 1;
-    }
-    ProfScope ps(fuse ? "k_reduce_adam" : "k_grad_reduce");
-    hipLaunchKernelGGL(k_grad_reduce<AdamFuse>, dim3((unsigned)((total + 63) / 64) + 1), dim3(256), 0, ppo_stream(), p->slabs.p,
-                       slab_floats(p->F, p->HID, p->L), p->nwg_bwd, p->nwg_small ? p->nwg_small : p->nwg_bwd, L, p->grad.p, p->loss_terms.p, B, 1.0 / (double)B_global,
-                       entropy_weight, A, packs_of(p));
+    A.params = o->pol->params.p; A.m = e.s.p; A.v = e.s1.p; A.eta = e.eta; A.beta1 = e.h1; A.beta2 = e.h2; A.eps = e.h3;
+    A.bp1 = e.beta_pow[0]; A.bp2 = e.beta_pow[1]; A.hist2 = hist2; A.on = 1;
+    return A;
+}
+
+// after a step's launches: the Adam member's beta powers for the next step
+static void chain_done(ppo_adam_s* o) {
+    for (int j = 0; j < o->nmem; ++j)
+        if (o->mem[j].kind == PPO_OPT_ADAM) { o->mem[j].beta_pow[0] *= o->mem[j].h1; o->mem[j].beta_pow[1] *= o->mem[j].h2; }
+}
+
+template <typename Fuse>
+static int32_t reduce_launch(const char* name, ppo_policy_s* p, const ParamLayout& L, int64_t B, int64_t B_global,
+                             double entropy_weight, const Fuse& A) {
+    ProfScope ps(name);
+    hipLaunchKernelGGL(k_grad_reduce<Fuse>, dim3((unsigned)((slab_elems(p->F, p->HID, p->L) + 63) / 64) + 1), dim3(256), 0, ppo_stream(),
+                       p->slabs.p, slab_floats(p->F, p->HID, p->L), p->nwg_bwd, p->nwg_small ? p->nwg_small : p->nwg_bwd, L, p->grad.p,
+                       p->loss_terms.p, B, 1.0 / (double)B_global, entropy_weight, A, packs_of(p));
     HIP_TRY(hipGetLastError());
-    if (fuse) { fuse->beta_pow[0] *= fuse->beta1; fuse->beta_pow[1] *= fuse->beta2; }
+    return PPO_OK;
+}
+
+template <typename Fuse>
+static int32_t update_launch(const char* name, ppo_policy_s* p, const ParamLayout& L, const Fuse& A) {
+    ProfScope ps(name);
+    hipLaunchKernelGGL(k_opt_update<Fuse>, dim3((unsigned)((L.np + 255) / 256)), dim3(256), 0, ppo_stream(), p->grad.p, L, packs_of(p), A);
+    HIP_TRY(hipGetLastError());
+    return PPO_OK;
+}
+
+// slab reduction + (one extra block) loss-term reduction in a single launch; with `fuse`, its optimiser step in the same launch
+int32_t launch_grad_reduce(ppo_policy_s* p, int64_t B, int64_t B_global, double entropy_weight, ppo_adam_s* fuse, float* hist2) {
+    const ParamLayout L = layout_of(p);
+    if (!fuse) return reduce_launch("k_grad_reduce", p, L, B, B_global, entropy_weight, AdamFuse{});
+    if (clip_position(fuse) >= 0) {
+        ChainFuse after;
+        PPO_TRY(reduce_launch("k_reduce_clip", p, L, B, B_global, entropy_weight, clip_fuse(fuse, hist2, after)));
+        PPO_TRY(launch_clip_apply(fuse, L, after, true));
+    } else if (fuse->adam_only()) {
+        PPO_TRY(reduce_launch("k_reduce_adam", p, L, B, B_global, entropy_weight, adam_fuse(fuse, hist2)));
+    } else {
+        PPO_TRY(reduce_launch("k_reduce_chain", p, L, B, B_global, entropy_weight, chain_step(fuse, hist2)));
+    }
+    chain_done(fuse);
     return PPO_OK;
 }
 
 int32_t launch_adam(ppo_adam_s* o, float* hist2) {
     ppo_policy_s* p = o->pol;
-    ParamLayout L = layout_of(p);
+    const ParamLayout L = layout_of(p);
     if (clip_position(o) >= 0) {
-        ClipFuse A = {};
         ChainFuse after;
-        split_at_clip(chain_step(o, hist2), clip_position(o), A.C, after);
-        A.hist2 = hist2; A.on = 1; A.dbuf = o->clip_d.p; A.part = o->clip_part.p;
+        const ClipFuse A = clip_fuse(o, hist2, after);
         {
             ProfScope ps("k_chain_clip1");
             hipLaunchKernelGGL(k_chain_clip1, dim3((unsigned)((L.np + 255) / 256)), dim3(256), 0, ppo_stream(), p->grad.p, L, A);
             HIP_TRY(hipGetLastError());
         }
         PPO_TRY(launch_clip_apply(o, L, after, false));
-        chain_done(o);
-        return PPO_OK;
+    } else if (o->adam_only()) {
+        PPO_TRY(update_launch("k_adam", p, L, adam_fuse(o, hist2)));
+    } else {
+        PPO_TRY(update_launch("k_chain_update", p, L, chain_step(o, hist2)));
     }
-    if (!o->adam_only()) {
-        const ChainFuse C = chain_step(o, hist2);
-        ProfScope ps("k_chain_update");
-        hipLaunchKernelGGL(k_chain_update, dim3((unsigned)((L.np + 255) / 256)), dim3(256), 0, ppo_stream(), p->grad.p, L,
-                           packs_of(p), C);
-        HIP_TRY(hipGetLastError());
-        chain_done(o);
-        return PPO_OK;
-    }
-    ProfScope ps("k_adam");
-    hipLaunchKernelGGL(k_adam, dim3((unsigned)((L.np + 255) / 256)), dim3(256), 0, ppo_stream(), p->params.p, p->grad.p,
-                       o->m.p, o->v.p, L, packs_of(p), o->eta, o->beta1, o->beta2, o->eps, o->beta_pow[0],
-                       o->beta_pow[1], hist2);
-    HIP_TRY(hipGetLastError());
-    o->beta_pow[0] *= o->beta1;
-    o->beta_pow[1] *= o->beta2;
+    chain_done(o);
     return PPO_OK;
 }
 
