@@ -82,6 +82,12 @@ def main():
     print("best average return %.3f (first %.3f); checkpoint holds Policy(%d, %d, %d, %d)"
           % (evaluator.best_return, evaluator.mean_returns[0], best.in_channels, best.hidden_channels,
              best.num_hidden_layers, best.num_output))
+    # what the policy is for: improve given states.  Best of 64 stochastic trajectories from each of 8 fresh states
+    fresh = PPO.HipVecEnv(num_envs=8, Q=8, max_actions=32, seed=99)
+    st = fresh.internal()
+    found = PPO.search_best_states_(evaluator.eval_env, best, st["score"], st["degree"], fresh.active_quads(), 64)
+    print("best-of-64 search on 8 fresh states: current_score - opt_score %s -> %s (winning clone %s, after %s steps)"
+          % (found["initial_gap"].tolist(), found["best_gap"].tolist(), found["best_clone"].tolist(), found["best_step"].tolist()))
     return evaluator
 
 

@@ -119,6 +119,12 @@ int32_t ppo_env_get_reward(ppo_env_t env, float* out);                  /* rewar
 int32_t ppo_env_get_terminal(ppo_env_t env, uint8_t* out);              /* is_terminal :18 */
 int32_t ppo_env_get_internal(ppo_env_t env, int8_t* score, int8_t* degree, int32_t* steps,
                              uint32_t* episode, uint32_t* tick);
+/* Caller-supplied env states: score and degree [N][V] (V = 4Q), active [N] active-quad words.  Leaves every env as reset!
+ * would, with these arrays in place of the Philox draw: steps = 0, reward = 0, done = 0; the episode and tick counters are
+ * untouched.  Checked on the host before anything is uploaded (PPO_ERR_ARG): active != 0, no bit at or above Q, every entry
+ * of an inactive quad 0 in both arrays. */
+int32_t ppo_env_set_internal(ppo_env_t env, const int8_t* score, const int8_t* degree, const uint32_t* active);
+int32_t ppo_env_get_active(ppo_env_t env, uint32_t* active);
 int32_t ppo_env_check_errors(ppo_env_t env, int32_t* flags_or_null);
 /* rand(Categorical(ap)) walks the CDF sequentially; when the fp32 sum of ap stops short of u (u within 2^-24 of 1) the
  * walk ends on the LAST action, and if that action is masked the reference's `@assert ap[a] > 0.0` throws
@@ -545,6 +551,31 @@ int32_t ppo_average_normalized_returns(ppo_policy_t pol, ppo_env_t env, ppo_roll
                                        int64_t num_trajectories, double* mean, double* std);
 int32_t ppo_evaluate_trajectories(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_trajectories,
                                   int32_t kind, double* values);
+
+/* best_state_in_rollout(wrapper, policy)                     test/quad_game_utilities.jl:341-358
+ * One stochastic trajectory per slot; the state (start included) at argmin(current_score - opt_score) comes back: the FIRST
+ * minimum, like Julia's argmin.  Per trajectory: best_state [2V] = score[V] then degree[V], best_active, best_gap, best_step
+ * (steps played when it was reached; 0 = the start), length, initial_gap; optional trace [max_actions] = initial_score -
+ * current_score behind every step (single_trajectory_scores :309-323; INT32_MIN behind the trajectory's end) and
+ * type_counts [4] = actions played by type a % 4 (count_non_flips, test/random_quad.jl:9-27, is types 2 and 3).
+ *   reset_first = 1: the average_best_returns convention -- trajectory e on env e mod N, reset! before each, env-major output.
+ *   reset_first = 0: num_trajectories <= N; env n < num_trajectories plays one trajectory from the state it holds, no reset!
+ *                    runs and no episode counter is consumed; an env that is already terminal is PPO_ERR_ARG. */
+int32_t ppo_best_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_trajectories,
+                        int32_t reset_first, int8_t* best_state, uint32_t* best_active, int32_t* best_gap,
+                        int32_t* best_step, int32_t* length, int32_t* initial_gap, int32_t* trace_or_null,
+                        int32_t* type_counts_or_null);
+/* Best of K trajectories from each of num_starts caller-supplied states (score, degree [num_starts][V], active
+ * [num_starts], checked like ppo_env_set_internal), 1 <= K <= N.  Sampling is keyed on (global env id, tick), so the K envs
+ * loaded with one start play K different trajectories.  Rounds of N / K starts: env n of a round holds start n / K as clone
+ * n % K, the envs behind them idle (their ticks do not move).  Per start: the winner's best_state [2V], best_active,
+ * best_gap, best_clone, best_step, initial_gap; ties go to the lowest clone, then that clone's first minimum.  Optional
+ * clone_gaps [num_starts][K]: every clone's best gap.  No reset! runs: episode counters are unchanged, ticks advance by the
+ * steps each env played, the envs that played are left terminal. */
+int32_t ppo_search_best_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
+                               const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
+                               uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
+                               int32_t* initial_gap, int32_t* clone_gaps_or_null);
 
 /* timing of the dominant kernels of the last ppo_train / ppo_collect_rollouts call, measured with
  * HIP events on the engine's stream (bench.py roofline leg) */

@@ -270,6 +270,53 @@ function evaluate_trajectories(env::HipVecEnv, p::HipPolicy, num_trajectories, k
     v
 end
 
+# caller-supplied env states: score, degree [V, N] column-major == [N][V] (V = 4Q), active [N]; every env is left as reset!
+# would leave it, the episode and tick counters stay
+function set_internal!(env::HipVecEnv, score::Matrix{Int8}, degree::Matrix{Int8}, active::Vector{UInt32})
+    check(ccall((:ppo_env_set_internal, LIB), Int32, (Ptr{Cvoid}, Ptr{Int8}, Ptr{Int8}, Ptr{UInt32}), env.h, score, degree, active))
+end
+function active_quads(env::HipVecEnv)
+    a = zeros(UInt32, env.N)
+    check(ccall((:ppo_env_get_active, LIB), Int32, (Ptr{Cvoid}, Ptr{UInt32}), env.h, a))
+    a
+end
+
+# best_state_in_rollout (test/quad_game_utilities.jl:341-358) for num_trajectories trajectories; reset_first = true: the
+# average_best_returns convention (reset! before each, env-major), false: every env below num_trajectories plays one
+# trajectory from the state it holds.  best_state[:, i] = score[V] then degree[V] of trajectory i's best state; trace[:, i] =
+# single_trajectory_scores (:309-323; typemin(Int32) behind the end); type_counts[3:4, i] sum to count_non_flips
+function best_states(env::HipVecEnv, p::HipPolicy, num_trajectories; reset_first = true)
+    scratch = HipRollouts()
+    h = ensure!(scratch, env, 1)
+    nt, V = Int(num_trajectories), 4 * env.Q
+    st, act = zeros(Int8, 2V, nt), zeros(UInt32, nt)
+    gap, step, len, init = zeros(Int32, nt), zeros(Int32, nt), zeros(Int32, nt), zeros(Int32, nt)
+    trace, types = zeros(Int32, env.max_actions, nt), zeros(Int32, 4, nt)
+    check(ccall((:ppo_best_states, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Int8}, Ptr{UInt32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32},
+                 Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+                p.h, env.h, h, nt, Int32(reset_first), st, act, gap, step, len, init, trace, types))
+    (best_state = st, best_active = act, best_gap = gap, best_step = step, length = len, initial_gap = init, trace = trace,
+     type_counts = types)
+end
+best_state_in_rollout(env::HipVecEnv, p::HipPolicy) = best_states(env, p, env.N; reset_first = false)
+
+# best of K trajectories from each start state: score, degree [V, M] column-major == [M][V], active [M]
+function search_best_states(env::HipVecEnv, p::HipPolicy, score::Matrix{Int8}, degree::Matrix{Int8}, active::Vector{UInt32}, K)
+    scratch = HipRollouts()
+    h = ensure!(scratch, env, 1)
+    M, V = length(active), 4 * env.Q
+    st, act = zeros(Int8, 2V, M), zeros(UInt32, M)
+    gap, clone, step, init = zeros(Int32, M), zeros(Int32, M), zeros(Int32, M), zeros(Int32, M)
+    gaps = zeros(Int32, Int(K), M)
+    check(ccall((:ppo_search_best_states, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Int8}, Ptr{Int8}, Ptr{UInt32}, Ptr{Int8}, Ptr{UInt32},
+                 Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+                p.h, env.h, h, M, Int64(K), score, degree, active, st, act, gap, clone, step, init, gaps))
+    (best_state = st, best_active = act, best_gap = gap, best_clone = clone, best_step = step, initial_gap = init,
+     clone_gaps = gaps)
+end
+
 # batch_advantage plugin mode handed to the engine: 0 = returns (PPO.batch_advantage above), 1 = normalised returns,
 # 2 / 3 = GAE(gamma, lambda) / normalised GAE over values supplied through compute_gae!
 const ADV_MODE = Ref{Int32}(0)

@@ -58,6 +58,8 @@ __all__ = [
     "HipCritic", "state_values", "batch_state_values", "compute_values_", "compute_gae_critic_", "value_forward_backward",
     "value_train_", "pooled_state_value", "value_loss", "value_loss_clipped",
     "kl_stats", "explained_variance_", "explained_variance_from_sums",
+    "check_internal", "best_states_", "best_state_in_rollout", "single_trajectory_scores", "count_non_flips",
+    "search_best_states_",
 ]
 
 
@@ -272,6 +274,21 @@ class HipVecEnv:
         call("ppo_env_get_internal", self._h, _p(sc, _lib.c_i8p), _p(dg, _lib.c_i8p), _p(st, _lib.c_i32p),
              _p(ep, _lib.c_u32p), _p(tk, _lib.c_u32p))
         return dict(score=sc, degree=dg, steps=st, episode=ep, tick=tk)
+
+    def set_internal(self, score, degree, active):
+        """Load caller-supplied states (check_internal's conditions; one per env): every env is left as reset! would leave
+        it (steps 0, reward 0, not terminal) with these arrays in place of the random draw; the episode and tick counters
+        are untouched."""
+        sc, dg, act = check_internal(score, degree, active, self.Q)
+        if sc.shape[0] != self.N:
+            raise PPOError(-1, "AssertionError: set_internal expects one state per env")
+        call("ppo_env_set_internal", self._h, _p(sc, _lib.c_i8p), _p(dg, _lib.c_i8p), _p(act, _lib.c_u32p))
+
+    def active_quads(self):
+        """The active-quad word of every env (uint32 [N])."""
+        act = np.empty(self.N, np.uint32)
+        call("ppo_env_get_active", self._h, _p(act, _lib.c_u32p))
+        return act
 
 
 @state.register(HipVecEnv)
@@ -1595,6 +1612,109 @@ def evaluate_trajectories(env, policy, num_trajectories, kind):
     scratch, h = _evaluator_scratch(env)
     out = np.zeros(int(num_trajectories), np.float64)
     call("ppo_evaluate_trajectories", policy._h, env._h, h, int(num_trajectories), k, _p(out, _lib.c_f64p))
+    return out
+
+
+# ------------------------------------------------------------------ best state of a rollout, best-of-K search
+def check_internal(score, degree, active, Q):
+    """What HipVecEnv.set_internal and search_best_states_ require of caller-supplied env states (ppo_env_set_internal checks
+    the same before it uploads anything): score, degree [n, 4Q] int8, active [n] active-quad words with active != 0, no bit
+    at or above Q, and every entry of an inactive quad 0 in both arrays.  Returns the three arrays C-contiguous;
+    PPOError(PPO_ERR_ARG) otherwise."""
+    V = 4 * int(Q)
+    sc, dg = np.ascontiguousarray(score, np.int8), np.ascontiguousarray(degree, np.int8)
+    act = np.ascontiguousarray(np.atleast_1d(active), np.uint32)
+    if sc.ndim != 2 or sc.shape[1] != V or dg.shape != sc.shape or act.shape != (sc.shape[0],):
+        raise PPOError(-1, "AssertionError: env state: score and degree must be [n, %d], active [n]" % V)
+    if np.any(act == 0):
+        raise PPOError(-1, "AssertionError: env state: no active quad")
+    if Q < 32 and np.any(act >> np.uint32(Q)):
+        raise PPOError(-1, "AssertionError: env state: active bit at or above Q")
+    off = ((act[:, None] >> (np.arange(V, dtype=np.uint32) >> 2)[None, :]) & 1) == 0
+    if np.any(sc[off]) or np.any(dg[off]):
+        raise PPOError(-1, "AssertionError: env state: nonzero entry of an inactive quad")
+    return sc, dg, act
+
+
+def _best_states(env, policy, num_trajectories, reset_first, scores, action_types):
+    nt, V = int(num_trajectories), 4 * env.Q
+    scratch, h = _evaluator_scratch(env)
+    st, act = np.zeros((nt, 2 * V), np.int8), np.zeros(nt, np.uint32)
+    gap, step, length, init = (np.zeros(nt, np.int32) for _ in range(4))
+    tr = np.zeros((nt, env.max_actions), np.int32) if scores else None
+    tc = np.zeros((nt, 4), np.int32) if action_types else None
+    call("ppo_best_states", policy._h, env._h, h, nt, int(bool(reset_first)), _p(st, _lib.c_i8p), _p(act, _lib.c_u32p),
+         _p(gap, _lib.c_i32p), _p(step, _lib.c_i32p), _p(length, _lib.c_i32p), _p(init, _lib.c_i32p),
+         None if tr is None else _p(tr, _lib.c_i32p), None if tc is None else _p(tc, _lib.c_i32p))
+    out = dict(best_state=st, best_score=st[:, :V], best_degree=st[:, V:], best_active=act, best_gap=gap, best_step=step,
+               length=length, initial_gap=init)
+    if scores:
+        out["trace"] = tr
+    if action_types:
+        out["type_counts"] = tc
+    return out
+
+
+def best_states_(env, policy, num_trajectories, scores=False, action_types=False):
+    """best_state_in_rollout (test/quad_game_utilities.jl:341-358) over num_trajectories trajectories in the
+    average_best_returns convention: trajectory e on env e mod N, reset! before each, env-major output.  Returns a dict of
+    arrays, one row per trajectory: best_state [2V] (best_score / best_degree are its halves), best_active, best_gap
+    (current_score - opt_score of that state), best_step (steps played when it was reached, 0 = the start: the first
+    minimum, like argmin), length, initial_gap; scores=True adds trace [max_actions] (single_trajectory_scores:
+    initial_score - current_score behind every step, INT32_MIN behind the end), action_types=True adds type_counts [4]."""
+    return _best_states(env, policy, num_trajectories, True, scores, action_types)
+
+
+def best_state_in_rollout(env, policy, rng=None):
+    """best_state_in_rollout(wrapper, policy) (test/quad_game_utilities.jl:341-358), the reference's argument order: every
+    env plays one stochastic trajectory from the state it holds (no reset!, no episode counter consumed) and the state at
+    argmin(current_score - opt_score) comes back -- for a HipVecEnv the dict of best_states_ over all N envs, for any other
+    env object a deep copy of it in that state."""
+    if not isinstance(env, HipVecEnv):
+        return generic.best_state_in_rollout(_this_module(), env, policy, rng)
+    return _best_states(env, policy, env.N, False, False, False)
+
+
+def single_trajectory_scores(env, policy, rng=None):
+    """single_trajectory_scores(wrapper, policy) (test/quad_game_utilities.jl:309-323): initial_score - current_score behind
+    every step of one trajectory from the current state.  HipVecEnv: a list of N int32 arrays, one per env."""
+    if not isinstance(env, HipVecEnv):
+        return generic.single_trajectory_scores(_this_module(), env, policy, rng)
+    r = _best_states(env, policy, env.N, False, True, False)
+    return [r["trace"][n, :r["length"][n]].copy() for n in range(env.N)]
+
+
+def count_non_flips(env, policy, rng=None):
+    """count_non_flips(wrapper, policy) (test/random_quad.jl:9-27): how many actions of one trajectory from the current
+    state were of type 3 or 4 (1-based; a % 4 >= 2 here).  HipVecEnv: int64 [N]."""
+    if not isinstance(env, HipVecEnv):
+        return generic.count_non_flips(_this_module(), env, policy, rng)
+    r = _best_states(env, policy, env.N, False, False, True)
+    return r["type_counts"][:, 2:].sum(axis=1, dtype=np.int64)
+
+
+def search_best_states_(env, policy, score, degree, active, K, clone_gaps=False):
+    """Best of K stochastic trajectories from each caller-supplied start state (score, degree [M, 4Q], active [M]):
+    K resident envs are loaded with one start and, sampling being keyed on (global env id, tick), play K different
+    trajectories; N // K starts run at a time.  Returns a dict of arrays, one row per start: best_state [2V] (best_score /
+    best_degree), best_active, best_gap, best_clone, best_step, initial_gap; clone_gaps=True adds clone_gaps [M, K].  Ties go
+    to the lowest clone, then its first minimum.  No reset! runs: episode counters stay, ticks advance by the steps played,
+    the envs that played are left terminal."""
+    sc, dg, act = check_internal(score, degree, active, env.Q)
+    M, V, K = sc.shape[0], 4 * env.Q, int(K)
+    if not 1 <= K <= env.N:
+        raise PPOError(-1, "AssertionError: search_best_states: 1 <= K <= N")
+    scratch, h = _evaluator_scratch(env)
+    st, bact = np.zeros((M, 2 * V), np.int8), np.zeros(M, np.uint32)
+    gap, clone, step, init = (np.zeros(M, np.int32) for _ in range(4))
+    cg = np.zeros((M, K), np.int32) if clone_gaps else None
+    call("ppo_search_best_states", policy._h, env._h, h, M, K, _p(sc, _lib.c_i8p), _p(dg, _lib.c_i8p), _p(act, _lib.c_u32p),
+         _p(st, _lib.c_i8p), _p(bact, _lib.c_u32p), _p(gap, _lib.c_i32p), _p(clone, _lib.c_i32p), _p(step, _lib.c_i32p),
+         _p(init, _lib.c_i32p), None if cg is None else _p(cg, _lib.c_i32p))
+    out = dict(best_state=st, best_score=st[:, :V], best_degree=st[:, V:], best_active=bact, best_gap=gap, best_clone=clone,
+               best_step=step, initial_gap=init)
+    if clone_gaps:
+        out["clone_gaps"] = cg
     return out
 
 

@@ -46,6 +46,11 @@ SIGNATURES = {
     "ppo_env_get_reward": [H, c_f32p],
     "ppo_env_get_terminal": [H, c_u8p],
     "ppo_env_get_internal": [H, c_i8p, c_i8p, c_i32p, c_u32p, c_u32p],
+    "ppo_env_set_internal": [H, c_i8p, c_i8p, c_u32p],
+    "ppo_env_get_active": [H, c_u32p],
+    "ppo_best_states": [H, H, H, C.c_int64, C.c_int32, c_i8p, c_u32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p],
+    "ppo_search_best_states": [H, H, H, C.c_int64, C.c_int64, c_i8p, c_i8p, c_u32p, c_i8p, c_u32p, c_i32p, c_i32p, c_i32p,
+                               c_i32p, c_i32p],
     "ppo_set_rollout_persistent": [C.c_int32],
     "ppo_set_rollout_compact": [C.c_int32],
     "ppo_env_check_errors": [H, c_i32p],

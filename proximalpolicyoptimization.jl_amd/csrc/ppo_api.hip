@@ -361,6 +361,40 @@ int32_t ppo_env_get_internal(ppo_env_t env, int8_t* score, int8_t* degree, int32
     return PPO_OK;
 }
 
+// what ppo_env_set_internal and ppo_search_best_states require of caller-supplied env states ([count][V] each, [count]
+// active-quad words): a state reset! or step! could have left.  Checked on the host before anything is uploaded
+static int32_t check_internal_host(int32_t Q, int64_t count, const int8_t* score, const int8_t* degree, const uint32_t* active) {
+    const int V = 4 * Q;
+    for (int64_t n = 0; n < count; ++n) {
+        const uint32_t act = active[n];
+        ARG_CHECK(act != 0, "env state: no active quad");
+        ARG_CHECK(Q >= 32 || (act >> Q) == 0, "env state: active bit at or above Q");
+        for (int v = 0; v < V; ++v)
+            if (!((act >> (v >> 2)) & 1u))
+                ARG_CHECK(score[n * V + v] == 0 && degree[n * V + v] == 0, "env state: nonzero entry of an inactive quad");
+    }
+    return PPO_OK;
+}
+
+int32_t ppo_env_set_internal(ppo_env_t env, const int8_t* score, const int8_t* degree, const uint32_t* active) {
+    ARG_CHECK(env && score && degree && active, "env_set_internal: null argument");
+    PPO_TRY(check_internal_host(env->Q, env->N, score, degree, active));
+    const size_t N = (size_t)env->N;
+    PPO_TRY(h2d(env->score.p, score, N * env->V));
+    PPO_TRY(h2d(env->degree.p, degree, N * env->V));
+    PPO_TRY(h2d(env->active.p, active, N));
+    HIP_TRY(hipMemsetAsync(env->steps.p, 0, N * 4, g_stream));         // as reset! leaves them; episode and tick stay
+    HIP_TRY(hipMemsetAsync(env->reward.p, 0, N * 4, g_stream));
+    HIP_TRY(hipMemsetAsync(env->done.p, 0, N, g_stream));
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    return PPO_OK;
+}
+
+int32_t ppo_env_get_active(ppo_env_t env, uint32_t* active) {
+    ARG_CHECK(env && active, "env_get_active: null argument");
+    return d2h(active, env->active.p, (size_t)env->N);
+}
+
 // ================================================================ policy
 // Hidden widths other than 128 / 256 run on the next wider kernel with ZERO-PADDED hidden units.  That is exact, not an
 // approximation: a padded unit has zero input weights and zero bias, so its activation is leakyrelu(0) = 0; its outgoing
@@ -863,6 +897,29 @@ int32_t ppo_average_returns(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scra
 // num_trajectories whole episodes, trajectory e on resident env e mod N like ppo_collect_rollouts_episodes; the
 // per-episode value is tracked inside the env step (k_env_step, EvalView), nothing but one value per trajectory
 // comes back.  Row 0 of `scratch` is the only rollout storage touched.  values: [num_trajectories], env-major.
+// The step loop of the evaluators and of the best-state search: observe, policy forward + sample, env step with the
+// bookkeeping of `ev` (k_env_step) or `tv` (k_env_step_track), until every env has used up its episodes_left (polled every
+// 8 steps) or Tmax steps have run.  Row 0 of `scratch` is the only rollout storage touched.
+static int32_t play_quotas(ppo_policy_s* pol, ppo_env_s* env, ppo_rollouts_s* scratch, int64_t Tmax, const EvalView* ev,
+                           const TrackView* tv, bool* all_done) {
+    const int64_t N = env->N;
+    std::vector<int32_t> left((size_t)N);
+    bool all = false;
+    for (int64_t t = 0; t < Tmax && !all; ++t) {
+        PPO_TRY(launch_env_observe(env, scratch->states.p, scratch->active.p));
+        PPO_TRY(launch_policy_rollout(pol, env, scratch->states.p, scratch->active.p, scratch->actions.p, scratch->p_sel.p, nullptr));
+        if (tv) PPO_TRY(launch_env_step_track(env, scratch->actions.p, scratch->rewards.p, scratch->done.p, scratch->valid.p, *tv));
+        else PPO_TRY(launch_env_step(env, scratch->actions.p, scratch->rewards.p, scratch->done.p, scratch->valid.p, 0, 1, ev));
+        if ((t & 7) == 7 || t + 1 == Tmax) {            // poll completion every 8 steps
+            PPO_TRY(d2h(left.data(), env->episodes_left.p, (size_t)N));
+            all = true;
+            for (int64_t n = 0; n < N; ++n) if (left[n] > 0) { all = false; break; }
+        }
+    }
+    *all_done = all;
+    return PPO_OK;
+}
+
 static int32_t evaluate_impl(ppo_policy_s* pol, ppo_env_s* env, ppo_rollouts_s* scratch, int64_t num_traj, int32_t kind,
                              std::vector<double>& values) {
     PPO_TRY(check_shapes(scratch, env, pol));
@@ -883,18 +940,8 @@ static int32_t evaluate_impl(ppo_policy_s* pol, ppo_env_s* env, ppo_rollouts_s* 
     hipLaunchKernelGGL(k_episode_quota, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, g_stream, env->episodes_left.p, N,
                        num_traj);
     PPO_TRY(launch_env_reset(env, 0));                                  // reset!(env) before the first trajectory
-    std::vector<int32_t> left((size_t)N);
     bool all = false;
-    for (int64_t t = 0; t < Tmax && !all; ++t) {
-        PPO_TRY(launch_env_observe(env, scratch->states.p, scratch->active.p));
-        PPO_TRY(launch_policy_rollout(pol, env, scratch->states.p, scratch->active.p, scratch->actions.p, scratch->p_sel.p, nullptr));
-        PPO_TRY(launch_env_step(env, scratch->actions.p, scratch->rewards.p, scratch->done.p, scratch->valid.p, 0, 1, &ev));
-        if ((t & 7) == 7 || t + 1 == Tmax) {            // poll completion every 8 steps
-            PPO_TRY(d2h(left.data(), env->episodes_left.p, (size_t)N));
-            all = true;
-            for (int64_t n = 0; n < N; ++n) if (left[n] > 0) { all = false; break; }
-        }
-    }
+    PPO_TRY(play_quotas(pol, env, scratch, Tmax, &ev, nullptr, &all));
     ARG_CHECK(all, "evaluator: the episodes did not finish within max_actions steps each");
     scratch->T = 0; scratch->len = 0; scratch->adv_T = -1; scratch->values_T = -1; scratch->boot_T = -1;
     values.resize((size_t)num_traj);
@@ -939,6 +986,122 @@ int32_t ppo_average_normalized_returns(ppo_policy_t pol, ppo_env_t env, ppo_roll
     PPO_TRY(evaluate_impl(pol, env, scratch, num_trajectories, 3, v));
     mean_std(v, mean, std);
     return PPO_OK;
+}
+
+// ---------------------------------------------------------------- best state of a rollout, best-of-K search
+// device storage of TrackView records: `slots` output records and the per-env running values
+struct TrackBufs {
+    DevBuf<int32_t> per_env, ints, trace, types; DevBuf<int8_t> state; DevBuf<uint32_t> active;
+    TrackView tv;
+    int32_t alloc(int64_t N, int64_t slots, int32_t V, int32_t max_actions, bool want_trace, bool want_types) {
+        const size_t S = (size_t)slots;
+        PPO_TRY(per_env.alloc((size_t)3 * N)); PPO_TRY(ints.alloc(4 * S)); PPO_TRY(state.alloc(S * 2 * V)); PPO_TRY(active.alloc(S));
+        HIP_TRY(hipMemsetAsync(per_env.p, 0, (size_t)3 * N * 4, g_stream));
+        HIP_TRY(hipMemsetAsync(ints.p, 0, 4 * S * 4, g_stream));
+        HIP_TRY(hipMemsetAsync(state.p, 0, S * 2 * V, g_stream));
+        HIP_TRY(hipMemsetAsync(active.p, 0, S * 4, g_stream));
+        tv.t_in = per_env.p; tv.ep_init = per_env.p + N; tv.ep_count = per_env.p + 2 * N;
+        tv.best_state = state.p; tv.best_active = active.p;
+        tv.best_gap = ints.p; tv.best_step = ints.p + S; tv.length = ints.p + 2 * S; tv.initial_gap = ints.p + 3 * S;
+        tv.num_traj = slots;
+        if (want_trace) {
+            PPO_TRY(trace.alloc(S * max_actions));
+            HIP_TRY(hipMemsetAsync(trace.p, 0, S * max_actions * 4, g_stream));
+            tv.trace = trace.p;
+        }
+        if (want_types) {
+            PPO_TRY(types.alloc(S * 4));
+            HIP_TRY(hipMemsetAsync(types.p, 0, S * 4 * 4, g_stream));
+            tv.type_counts = types.p;
+        }
+        return PPO_OK;
+    }
+};
+
+// best_state_in_rollout (test/quad_game_utilities.jl:341-358) for num_trajectories trajectories, with
+// single_trajectory_scores (:309-323) and the action-type counts behind count_non_flips (test/random_quad.jl:9-27)
+int32_t ppo_best_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_trajectories,
+                        int32_t reset_first, int8_t* best_state, uint32_t* best_active, int32_t* best_gap,
+                        int32_t* best_step, int32_t* length, int32_t* initial_gap, int32_t* trace_or_null,
+                        int32_t* type_counts_or_null) {
+    ARG_CHECK(best_state && best_active && best_gap && best_step && length && initial_gap, "best_states: null argument");
+    PPO_TRY(check_shapes(scratch, env, pol));
+    const int64_t N = env->N, nt = num_trajectories;
+    ARG_CHECK(nt >= 1, "best_states: num_trajectories must be >= 1");
+    if (!reset_first) {
+        ARG_CHECK(nt <= N, "best_states: without reset! every env plays at most one trajectory (num_trajectories <= N)");
+        std::vector<uint8_t> dn((size_t)N);
+        PPO_TRY(d2h(dn.data(), env->done.p, (size_t)N));
+        for (int64_t n = 0; n < nt; ++n) ARG_CHECK(!dn[n], "best_states: an env that is to play is already terminal");
+    }
+    const int64_t per_env = (nt + N - 1) / N;
+    const int32_t M = env->max_actions, V = env->V;
+    PPO_TRY(rollouts_reserve(scratch, 1, false));
+    TrackBufs b;
+    PPO_TRY(b.alloc(N, nt, V, M, trace_or_null != nullptr, type_counts_or_null != nullptr));
+    hipLaunchKernelGGL(k_episode_quota, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, g_stream, env->episodes_left.p, N, nt);
+    if (reset_first) PPO_TRY(launch_env_reset(env, 0));                 // reset!(env) before the first trajectory
+    bool all = false;
+    PPO_TRY(play_quotas(pol, env, scratch, per_env * M, nullptr, &b.tv, &all));
+    ARG_CHECK(all, "best_states: the trajectories did not finish within max_actions steps each");
+    scratch->T = 0; scratch->len = 0; scratch->adv_T = -1; scratch->values_T = -1; scratch->boot_T = -1;
+    const size_t S = (size_t)nt;
+    PPO_TRY(d2h(best_state, b.state.p, S * 2 * V)); PPO_TRY(d2h(best_active, b.active.p, S));
+    PPO_TRY(d2h(best_gap, b.tv.best_gap, S)); PPO_TRY(d2h(best_step, b.tv.best_step, S));
+    PPO_TRY(d2h(length, b.tv.length, S)); PPO_TRY(d2h(initial_gap, b.tv.initial_gap, S));
+    if (trace_or_null) {
+        PPO_TRY(d2h(trace_or_null, b.trace.p, S * M));
+        for (size_t s = 0; s < S; ++s)                                    // entries behind the trajectory's end
+            for (int32_t t = std::max(length[s], 0); t < M; ++t) trace_or_null[s * M + t] = INT32_MIN;
+    }
+    if (type_counts_or_null) PPO_TRY(d2h(type_counts_or_null, b.types.p, S * 4));
+    return ppo_env_check_errors(env, nullptr);
+}
+
+// Best-of-K search from caller-supplied start states.  Sampling is keyed on (global env id, tick), so K resident envs loaded
+// with one state play K different trajectories: rounds of S = N / K starts, each a load (k_env_load_starts), the tracked
+// step loop and one reduction (k_search_argmin).  No reset! runs: the episode counters stay, ticks advance by the steps played.
+int32_t ppo_search_best_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
+                               const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
+                               uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
+                               int32_t* initial_gap, int32_t* clone_gaps_or_null) {
+    ARG_CHECK(score && degree && active && best_state && best_active && best_gap && best_clone && best_step && initial_gap,
+              "search_best_states: null argument");
+    PPO_TRY(check_shapes(scratch, env, pol));
+    const int64_t N = env->N, Mst = num_starts;
+    ARG_CHECK(Mst >= 1 && K >= 1 && K <= N, "search_best_states: need num_starts >= 1 and 1 <= K <= N");
+    PPO_TRY(check_internal_host(env->Q, Mst, score, degree, active));
+    const int32_t V = env->V;
+    const int64_t S = N / K;
+    PPO_TRY(rollouts_reserve(scratch, 1, false));
+    std::vector<int8_t> snap((size_t)Mst * 2 * V);                       // k_env_snapshot's layout: score[V] then degree[V]
+    for (int64_t m = 0; m < Mst; ++m) {
+        std::memcpy(&snap[(size_t)m * 2 * V], score + m * V, (size_t)V);
+        std::memcpy(&snap[(size_t)m * 2 * V + V], degree + m * V, (size_t)V);
+    }
+    DevBuf<int8_t> d_start; DevBuf<uint32_t> d_act; DevBuf<int32_t> d_clone, d_gaps;
+    PPO_TRY(d_start.alloc(snap.size())); PPO_TRY(d_act.alloc((size_t)Mst)); PPO_TRY(d_clone.alloc((size_t)Mst));
+    PPO_TRY(h2d(d_start.p, snap.data(), snap.size())); PPO_TRY(h2d(d_act.p, active, (size_t)Mst));
+    if (clone_gaps_or_null) PPO_TRY(d_gaps.alloc((size_t)Mst * K));
+    TrackBufs rec, out;                                                  // per-env records of a round (slot = env); the winners
+    PPO_TRY(rec.alloc(N, N, V, env->max_actions, false, false));
+    PPO_TRY(out.alloc(1, Mst, V, env->max_actions, false, false));
+    for (int64_t base = 0; base < Mst; base += S) {
+        const int64_t Sr = std::min(S, Mst - base);
+        HIP_TRY(hipMemsetAsync(rec.tv.ep_count, 0, (size_t)N * 4, g_stream));
+        PPO_TRY(launch_env_load_starts(env, d_start.p + (size_t)base * 2 * V, d_act.p + base, Sr * K, K, rec.tv.t_in));
+        bool all = false;
+        PPO_TRY(play_quotas(pol, env, scratch, env->max_actions, nullptr, &rec.tv, &all));
+        ARG_CHECK(all, "search_best_states: the trajectories did not finish within max_actions steps");
+        PPO_TRY(launch_search_argmin(rec.tv, V, Sr, K, out.tv, d_clone.p, clone_gaps_or_null ? d_gaps.p : nullptr, base));
+    }
+    scratch->T = 0; scratch->len = 0; scratch->adv_T = -1; scratch->values_T = -1; scratch->boot_T = -1;
+    const size_t Ms = (size_t)Mst;
+    PPO_TRY(d2h(best_state, out.state.p, Ms * 2 * V)); PPO_TRY(d2h(best_active, out.active.p, Ms));
+    PPO_TRY(d2h(best_gap, out.tv.best_gap, Ms)); PPO_TRY(d2h(best_step, out.tv.best_step, Ms));
+    PPO_TRY(d2h(initial_gap, out.tv.initial_gap, Ms)); PPO_TRY(d2h(best_clone, d_clone.p, Ms));
+    if (clone_gaps_or_null) PPO_TRY(d2h(clone_gaps_or_null, d_gaps.p, Ms * (size_t)K));
+    return ppo_env_check_errors(env, nullptr);
 }
 
 #define RO_GETTER(name, member, type, per)                                                     \

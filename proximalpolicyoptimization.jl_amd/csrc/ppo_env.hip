@@ -114,6 +114,133 @@ __global__ void k_env_step(EnvView e, const int32_t* __restrict__ actions, float
     }
 }
 
+// The episodes-mode step with the bookkeeping of best_state_in_rollout (test/quad_game_utilities.jl:341-358): the reference
+// keeps a copy of the wrapper behind every step and returns the one at argmin(current_score - opt_score); here the env's
+// thread keeps the best state so far in the trajectory's output slot and replaces it only on a STRICTLY lower gap (argmin
+// returns the first minimum; the start state is candidate 0).  Also single_trajectory_scores (:309-323: initial_score -
+// current_score behind every step) and the action types count_non_flips counts (test/random_quad.jl:9-27).  Same idle
+// branch, env_step_ref call, outputs and reset-on-done as k_env_step's episodes mode; the snapshot copies are dword copies
+// (V % 4 == 0, rows start dword aligned).
+__global__ void k_env_step_track(EnvView e, const int32_t* __restrict__ actions, float* __restrict__ reward_out,
+                                 uint8_t* __restrict__ done_out, uint8_t* __restrict__ valid_out, TrackView tv) {
+    const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= e.N) return;
+    const int64_t q = tv.num_traj / e.N, rem = tv.num_traj % e.N;
+    const int64_t slot = n * q + (n < rem ? n : rem) + tv.ep_count[n];   // env n's trajectories are consecutive
+    if (e.episodes_left[n] <= 0 || slot >= tv.num_traj) {                // this env already played its trajectories
+        if (valid_out) valid_out[n] = 0;
+        if (reward_out) reward_out[n] = 0.0f;
+        if (done_out) done_out[n] = 1;
+        return;
+    }
+    const EnvRef er = ref_of(e, n);
+    const int dv = e.V / 4;
+    uint32_t* __restrict__ bs = reinterpret_cast<uint32_t*>(tv.best_state + slot * 2 * e.V);
+    const uint32_t* sc4 = reinterpret_cast<const uint32_t*>(er.sc);
+    const uint32_t* dg4 = reinterpret_cast<const uint32_t*>(er.dg);
+    int t = tv.t_in[n];
+    int best_gap;
+    if (t == 0) {                                                        // first step! of a trajectory: the start state
+        const uint32_t act = *er.active;
+        const int cur = env_total_abs(er.sc, act, e.Q), sum = env_total_sum(er.sc, act, e.Q);
+        best_gap = cur - (sum < 0 ? -sum : sum);
+        for (int d = 0; d < dv; ++d) { bs[d] = sc4[d]; bs[dv + d] = dg4[d]; }
+        tv.best_active[slot] = act; tv.best_gap[slot] = best_gap; tv.best_step[slot] = 0; tv.initial_gap[slot] = best_gap;
+        tv.ep_init[n] = cur;
+    } else {
+        best_gap = tv.best_gap[slot];
+    }
+    const int a = actions[n];
+    float rew; uint8_t dn;
+    int score_after = 0;
+    const int errf = env_step_ref(const_of(e), er, a, rew, dn, &score_after);
+    if (errf) atomicOr(e.err, errf);
+    if (errf & 4) return;                          // step! on a terminated env: nothing recorded
+    if (reward_out) reward_out[n] = rew;
+    if (done_out) done_out[n] = dn;
+    if (valid_out) valid_out[n] = 1;
+    t += 1;
+    const uint32_t act = *er.active;
+    const int sum = env_total_sum(er.sc, act, e.Q);
+    const int gap = score_after - (sum < 0 ? -sum : sum);
+    if (gap < best_gap) {
+        for (int d = 0; d < dv; ++d) { bs[d] = sc4[d]; bs[dv + d] = dg4[d]; }
+        tv.best_active[slot] = act; tv.best_gap[slot] = gap; tv.best_step[slot] = t;
+    }
+    if (tv.trace && t <= e.max_actions) tv.trace[slot * e.max_actions + (t - 1)] = tv.ep_init[n] - score_after;
+    if (tv.type_counts) tv.type_counts[slot * 4 + ((a < 0 || a >= 16 * e.Q) ? 0 : (a & 3))] += 1;
+    if (dn) {
+        tv.length[slot] = t;
+        tv.ep_count[n] += 1;
+        tv.t_in[n] = 0;
+        const int left = e.episodes_left[n] - 1;
+        e.episodes_left[n] = left;
+        if (left > 0) env_reset_one(e, n);
+    } else {
+        tv.t_in[n] = t;
+    }
+}
+
+// best-of-K search, load: one thread per dword of every env's state.  Env n < busy takes start n / K (clone n % K) and is
+// left as reset! leaves an env, with one episode to play; the others idle
+__global__ void k_env_load_starts(EnvView e, const uint32_t* __restrict__ start_state, const uint32_t* __restrict__ start_active,
+                                  int64_t busy, int64_t K, int32_t* __restrict__ t_in) {
+    const int dv = e.V / 4;
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t n = gid / (2 * dv);
+    if (n >= e.N) return;
+    const int d = (int)(gid - n * 2 * dv);
+    if (n >= busy) {
+        if (d == 0) e.episodes_left[n] = 0;
+        return;
+    }
+    const int64_t s = n / K;
+    int8_t* dst = (d < dv) ? (e.score + n * e.V) : (e.degree + n * e.V);
+    reinterpret_cast<uint32_t*>(dst)[d < dv ? d : d - dv] = start_state[s * 2 * dv + d];
+    if (d == 0) {
+        e.active[n] = start_active[s]; e.steps[n] = 0; e.reward[n] = 0.0f; e.done[n] = 0;
+        e.episodes_left[n] = 1; t_in[n] = 0;
+    }
+}
+
+// best-of-K search, reduction: one workgroup per start.  Threads stride over the K clones (envs s*K ..) holding
+// min(gap << 32 | clone) -- a gap is sum|s| - |sum s| >= 0, so the unsigned order is the order of (gap, clone) and ties go to
+// the lowest clone -- then a wave reduction by shuffles, one LDS exchange across the four waves, and the whole workgroup
+// copies the winner's record
+__global__ __launch_bounds__(256) void k_search_argmin(TrackView tv, int V, int64_t K, TrackView out,
+                                                       int32_t* __restrict__ best_clone, int32_t* __restrict__ clone_gaps,
+                                                       int64_t out_base) {
+    __shared__ unsigned long long wave_min[4];
+    const int tid = threadIdx.x;
+    const int64_t s = blockIdx.x, o = out_base + s;
+    unsigned long long best = ~0ull;
+    for (int64_t c = tid; c < K; c += 256) {
+        const int g = tv.best_gap[s * K + c];
+        if (clone_gaps) clone_gaps[o * K + c] = g;
+        const unsigned long long key = ((unsigned long long)(uint32_t)g << 32) | (unsigned long long)(uint32_t)c;
+        best = key < best ? key : best;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const uint32_t hi = __shfl_xor((uint32_t)(best >> 32), off), lo = __shfl_xor((uint32_t)best, off);
+        const unsigned long long other = ((unsigned long long)hi << 32) | lo;
+        best = other < best ? other : best;
+    }
+    if ((tid & 63) == 0) wave_min[tid >> 6] = best;
+    __syncthreads();
+    best = wave_min[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) best = wave_min[w] < best ? wave_min[w] : best;
+    const int64_t clone = (int64_t)(uint32_t)best, env = s * K + clone;
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(tv.best_state + env * 2 * V);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(out.best_state + o * 2 * V);
+    for (int d = tid; d < V / 2; d += 256) dst[d] = src[d];
+    if (tid == 0) {
+        out.best_active[o] = tv.best_active[env]; out.best_gap[o] = tv.best_gap[env]; out.best_step[o] = tv.best_step[env];
+        out.initial_gap[o] = tv.initial_gap[env]; best_clone[o] = (int32_t)clone;
+    }
+}
+
 // state(env): obs[n][h][f] int8, f<36 template scores, f>=36 template degrees, 0 where the
 // template entry is missing or its quad is inactive (test/quad_game_utilities.jl:35-37,46-59).
 // One thread per output dword (4 features): coalesced 4-byte stores.
@@ -215,6 +342,33 @@ int32_t launch_env_step(ppo_env_s* e, const int32_t* actions_dev, float* reward_
     dim3 grid((unsigned)((e->N + 63) / 64));
     hipLaunchKernelGGL(k_env_step, grid, dim3(64), 0, ppo_stream(), view_of(e), actions_dev, reward_out, done_out,
                        valid_out, auto_reset, episodes_mode, (ev && episodes_mode) ? *ev : EvalView());
+    HIP_TRY(hipGetLastError());
+    return PPO_OK;
+}
+
+int32_t launch_env_step_track(ppo_env_s* e, const int32_t* actions_dev, float* reward_out, uint8_t* done_out,
+                              uint8_t* valid_out, const TrackView& tv) {
+    ProfScope ps("k_env_step");
+    dim3 grid((unsigned)((e->N + 63) / 64));
+    hipLaunchKernelGGL(k_env_step_track, grid, dim3(64), 0, ppo_stream(), view_of(e), actions_dev, reward_out, done_out,
+                       valid_out, tv);
+    HIP_TRY(hipGetLastError());
+    return PPO_OK;
+}
+
+int32_t launch_env_load_starts(ppo_env_s* e, const int8_t* start_state, const uint32_t* start_active, int64_t busy, int64_t K,
+                               int32_t* t_in) {
+    const int64_t total = e->N * (int64_t)(e->V / 2);
+    hipLaunchKernelGGL(k_env_load_starts, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ppo_stream(), view_of(e),
+                       reinterpret_cast<const uint32_t*>(start_state), start_active, busy, K, t_in);
+    HIP_TRY(hipGetLastError());
+    return PPO_OK;
+}
+
+int32_t launch_search_argmin(const TrackView& tv, int32_t V, int64_t S, int64_t K, const TrackView& out, int32_t* best_clone,
+                             int32_t* clone_gaps, int64_t out_base) {
+    hipLaunchKernelGGL(k_search_argmin, dim3((unsigned)S), dim3(256), 0, ppo_stream(), tv, (int)V, K, out, best_clone,
+                       clone_gaps, out_base);
     HIP_TRY(hipGetLastError());
     return PPO_OK;
 }

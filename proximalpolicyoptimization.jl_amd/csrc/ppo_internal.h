@@ -290,6 +290,34 @@ struct EvalView {
 };
 int32_t launch_env_step(ppo_env_s* e, const int32_t* actions_dev, float* reward_out, uint8_t* done_out,
                         uint8_t* valid_out, int auto_reset, int episodes_mode, const EvalView* ev = nullptr);
+// best-state bookkeeping folded into the env step of the episodes mode (best_state_in_rollout, single_trajectory_scores
+// test/quad_game_utilities.jl:309-323,341-358; count_non_flips test/random_quad.jl:9-27): k_env_step_track, a sibling of
+// k_env_step on the same env_step_ref.  The record of the trajectory in flight lives in its own output slot (the slot is
+// known from its first step on), so finishing a trajectory copies nothing: gap = current_score - opt_score.
+struct TrackView {
+    int32_t* t_in = nullptr;       // [N] steps the trajectory in flight has played (0: its first step! is still to come)
+    int32_t* ep_init = nullptr;    // [N] score at its start
+    int32_t* ep_count = nullptr;   // [N] trajectories this env has finished
+    int8_t* best_state = nullptr;  // [num_traj][2V] score[V] then degree[V] of the best state so far (k_env_snapshot's layout)
+    uint32_t* best_active = nullptr;   // [num_traj]
+    int32_t* best_gap = nullptr;   // [num_traj] its gap
+    int32_t* best_step = nullptr;  // [num_traj] steps played when it was reached (0: the start; argmin's first minimum)
+    int32_t* length = nullptr;     // [num_traj] steps of the whole trajectory (written on done)
+    int32_t* initial_gap = nullptr;    // [num_traj]
+    int32_t* trace = nullptr;      // [num_traj][max_actions] initial score - score behind step t, optional
+    int32_t* type_counts = nullptr;    // [num_traj][4] actions played by type a % 4, optional (zeroed by the caller)
+    int64_t num_traj = 0;          // slots, env-major like EvalView::out
+};
+int32_t launch_env_step_track(ppo_env_s* e, const int32_t* actions_dev, float* reward_out, uint8_t* done_out,
+                              uint8_t* valid_out, const TrackView& tv);
+// best-of-K search: start s of the round (snapshot start[s], active[s]) into envs s*K .. s*K + K - 1 as reset! would leave
+// them (steps, reward, done = 0) with one episode to play; every env from busy on idles (episodes_left = 0)
+int32_t launch_env_load_starts(ppo_env_s* e, const int8_t* start_state, const uint32_t* start_active, int64_t busy, int64_t K,
+                               int32_t* t_in);
+// ... and its reduction: winner of the K clones of each of S starts (lowest gap, then lowest clone) from the per-env
+// records of `tv` (slot = env) into record out_base + s of `out`; clone_gaps (optional): [..][K] every clone's best gap
+int32_t launch_search_argmin(const TrackView& tv, int32_t V, int64_t S, int64_t K, const TrackView& out, int32_t* best_clone,
+                             int32_t* clone_gaps, int64_t out_base);
 int32_t launch_env_observe(ppo_env_s* e, int8_t* obs_out, uint32_t* active_out);
 // compact rollout storage: env snapshot of every env (score[V] then degree[V]) -> cstate_out [N][2V]
 int32_t launch_env_snapshot(ppo_env_s* e, int8_t* cstate_out);

@@ -121,6 +121,68 @@ def average_returns_host(P, policy, env, num_trajectories, rng=None):
     return float(r.mean()), float(r.std(ddof=1)) if r.size > 1 else float("nan")
 
 
+def _sample_step(P, policy, env, rng):
+    """probs = action_probabilities(policy, state(wrapper)); action = rand(Categorical(probs)); step!(wrapper, action) --
+    the loop body the reference's trajectory helpers share.  Returns the 1-based action."""
+    ap = np.ascontiguousarray(P.action_probabilities(policy, P.state(env)), np.float32)
+    a1, _, _ = P.categorical_sample(ap[None, :], np.array([rng.random(dtype=np.float32)], np.float32))
+    P.step_(env, int(a1[0]))
+    return int(a1[0])
+
+
+def _game(env):
+    """wrapper.env of the reference's wrappers: the object that holds current_score / opt_score / initial_score (the
+    wrapper itself when it has no `env` field)."""
+    return getattr(env, "env", env)
+
+
+def best_state_in_rollout(P, env, policy, rng=None):
+    """best_state_in_rollout(wrapper, policy) (test/quad_game_utilities.jl:341-358): plays one stochastic trajectory from the
+    wrapper's current state, keeps a deep copy behind every step and returns the copy at argmin(current_score - opt_score)
+    (the first minimum; the start state is the first candidate)."""
+    import copy
+    rng = rng or np.random.default_rng()
+    wrappers = [copy.deepcopy(env)]
+    scores = [_game(env).current_score - _game(env).opt_score]
+    done = P.is_terminal(env)
+    while not done:
+        _sample_step(P, policy, env, rng)
+        done = P.is_terminal(env)
+        wrappers.append(copy.deepcopy(env))
+        scores.append(_game(env).current_score - _game(env).opt_score)
+    return wrappers[int(np.argmin(scores))]
+
+
+def single_trajectory_scores(P, env, policy, rng=None):
+    """single_trajectory_scores(wrapper, policy) (test/quad_game_utilities.jl:309-323): initial_score - current_score behind
+    every step of one stochastic trajectory."""
+    rng = rng or np.random.default_rng()
+    initial_score = _game(env).initial_score
+    scores = []
+    done = P.is_terminal(env)
+    while not done:
+        _sample_step(P, policy, env, rng)
+        scores.append(initial_score - _game(env).current_score)
+        done = P.is_terminal(env)
+    return scores
+
+
+def count_non_flips(P, env, policy, rng=None):
+    """count_non_flips(wrapper, policy) (test/random_quad.jl:9-27): actions of type > 2 (1-based) in one trajectory."""
+    rng = rng or np.random.default_rng()
+    counter = 0
+    done = P.is_terminal(env)
+    while not done:
+        ap = np.ascontiguousarray(P.action_probabilities(policy, P.state(env)), np.float32)
+        a1, _, _ = P.categorical_sample(ap[None, :], np.array([rng.random(dtype=np.float32)], np.float32))
+        _, _, t = P.index_to_action(int(a1[0]))
+        if t > 2:
+            counter += 1
+        P.step_(env, int(a1[0]))
+        done = P.is_terminal(env)
+    return counter
+
+
 class HostDataset:
     """BufferDataset over a HostRollouts (src/rollout_buffer.jl:95-147): getindex(Int | Vector) with the user's
     batch_state plugin, 1-based indices."""
