@@ -576,6 +576,25 @@ int32_t ppo_search_best_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t s
                                const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
                                uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
                                int32_t* initial_gap, int32_t* clone_gaps_or_null);
+/* Resampling search: ppo_search_best_states' schedule (rounds of N / K starts, clone n % K of start n / K on env n, no
+ * reset!, ticks advance by the steps played) with a resample event behind every interval-th loop step t of a round (t %
+ * interval == 0, t < max_actions), for every start of the round:
+ *   fold  the clone with the lowest (record best_gap, clone) of all K: its record (best_state, best_active, best_gap,
+ *         best_step, initial_gap) becomes the start's result on the start's first fold, later only on a strictly lower gap;
+ *   rank  the live clones (not terminal) ascending by (current_score - opt_score of the state held now, clone); the first
+ *         m = min(survivors, live) keep their state;
+ *   copy  the clone of rank r >= m takes score, degree, active, steps, reward, its whole record and its step count from the
+ *         clone of rank (r - m) % m; tick, episode and done stay its own, so the copies diverge at the next step.
+ * One more fold runs behind the round's last step.  best_step counts loop steps along the lineage.  clone_gaps (optional):
+ * every clone's record gap at that last fold.  donors (optional) [num_starts][E][K], E = (max_actions - 1) / interval: the
+ * donor clone of a receiver, -1 for a live clone that kept its state, -2 for a terminal clone and for every clone of an
+ * event that did not run because the round had finished.  interval >= max_actions runs no event: ppo_search_best_states.
+ * interval < 1 or survivors outside 1 .. K: PPO_ERR_ARG; K > 4096: PPO_ERR_UNSUPPORTED. */
+int32_t ppo_search_resample_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
+                                   const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
+                                   uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
+                                   int32_t* initial_gap, int32_t* clone_gaps_or_null, int64_t interval, int64_t survivors,
+                                   int32_t* donors_or_null);
 
 /* timing of the dominant kernels of the last ppo_train / ppo_collect_rollouts call, measured with
  * HIP events on the engine's stream (bench.py roofline leg) */

@@ -317,6 +317,27 @@ function search_best_states(env::HipVecEnv, p::HipPolicy, score::Matrix{Int8}, d
      clone_gaps = gaps)
 end
 
+# search_best_states with a resample event behind every interval-th step: each start folds its clones' records into its
+# result, then the live clones of rank >= min(survivors, live) by (current gap, clone) take the state and record of the
+# best-ranked ones.  donors[:, e, i]: per clone of start i at event e the donor clone, -1 kept its state, -2 terminal / no event
+function search_resample_states(env::HipVecEnv, p::HipPolicy, score::Matrix{Int8}, degree::Matrix{Int8}, active::Vector{UInt32},
+                                K, interval, survivors)
+    scratch = HipRollouts()
+    h = ensure!(scratch, env, 1)
+    M, V = length(active), 4 * env.Q
+    st, act = zeros(Int8, 2V, M), zeros(UInt32, M)
+    gap, clone, step, init = zeros(Int32, M), zeros(Int32, M), zeros(Int32, M), zeros(Int32, M)
+    gaps = zeros(Int32, Int(K), M)
+    donors = fill(Int32(-2), Int(K), div(env.max_actions - 1, Int(interval)), M)
+    check(ccall((:ppo_search_resample_states, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Int8}, Ptr{Int8}, Ptr{UInt32}, Ptr{Int8}, Ptr{UInt32},
+                 Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int64, Int64, Ptr{Int32}),
+                p.h, env.h, h, M, Int64(K), score, degree, active, st, act, gap, clone, step, init, gaps, Int64(interval),
+                Int64(survivors), donors))
+    (best_state = st, best_active = act, best_gap = gap, best_clone = clone, best_step = step, initial_gap = init,
+     clone_gaps = gaps, donors = donors)
+end
+
 # batch_advantage plugin mode handed to the engine: 0 = returns (PPO.batch_advantage above), 1 = normalised returns,
 # 2 / 3 = GAE(gamma, lambda) / normalised GAE over values supplied through compute_gae!
 const ADV_MODE = Ref{Int32}(0)

@@ -59,7 +59,7 @@ __all__ = [
     "value_train_", "pooled_state_value", "value_loss", "value_loss_clipped",
     "kl_stats", "explained_variance_", "explained_variance_from_sums",
     "check_internal", "best_states_", "best_state_in_rollout", "single_trajectory_scores", "count_non_flips",
-    "search_best_states_",
+    "search_best_states_", "search_resample_states_", "check_resample",
 ]
 
 
@@ -1713,6 +1713,56 @@ def search_best_states_(env, policy, score, degree, active, K, clone_gaps=False)
          _p(init, _lib.c_i32p), None if cg is None else _p(cg, _lib.c_i32p))
     out = dict(best_state=st, best_score=st[:, :V], best_degree=st[:, V:], best_active=bact, best_gap=gap, best_clone=clone,
                best_step=step, initial_gap=init)
+    if clone_gaps:
+        out["clone_gaps"] = cg
+    return out
+
+
+RESAMPLE_MAX_K = 4096        # k_search_resample stages one 8-byte rank key per clone in LDS
+
+
+def check_resample(N, K, interval, survivors):
+    """What search_resample_states_ requires of its schedule on N envs (ppo_search_resample_states checks the same):
+    interval >= 1 and 1 <= survivors <= K <= N, else PPOError(PPO_ERR_ARG); K above RESAMPLE_MAX_K is
+    PPOError(PPO_ERR_UNSUPPORTED).  Returns the three as ints."""
+    K, R, m0 = int(K), int(interval), int(survivors)
+    if R < 1:
+        raise PPOError(-1, "AssertionError: search_resample_states: interval must be >= 1")
+    if not 1 <= m0 <= K <= int(N):
+        raise PPOError(-1, "AssertionError: search_resample_states: 1 <= survivors <= K <= N")
+    if K > RESAMPLE_MAX_K:
+        raise PPOError(-4, "search_resample_states: K above %d clones is not supported" % RESAMPLE_MAX_K)
+    return K, R, m0
+
+
+def search_resample_states_(env, policy, score, degree, active, K, interval, survivors, donors=False, clone_gaps=False):
+    """search_best_states_ with resampling: behind every `interval`-th step of a round (t % interval == 0, t < max_actions)
+    each start folds its K clones' records into its result (the lowest (best_gap, clone); the first fold as it is, later
+    ones only on a strictly lower gap), ranks its live clones by (current_score - opt_score now, clone) and overwrites
+    every clone of rank r >= m = min(survivors, live) with state, record and step count of the clone of rank (r - m) % m.
+    The copies keep their own ticks, so they diverge at the next step.  One more fold behind the round's last step gives the
+    result.  Returns the dict of search_best_states_ (best_step counts steps along the lineage); donors=True adds donors
+    [M, E, K] int32 with E = (max_actions - 1) // interval: a receiver's donor clone, -1 a live clone that kept its state, -2
+    a terminal clone or an event that no longer ran; clone_gaps=True adds every clone's record gap at the last fold.
+    interval >= max_actions runs no event (search_best_states_); survivors == K copies nothing.  HipVecEnv only."""
+    if not isinstance(env, HipVecEnv):
+        raise PPOError(-4, "search_resample_states_ needs a HipVecEnv")
+    sc, dg, act = check_internal(score, degree, active, env.Q)
+    M, V = sc.shape[0], 4 * env.Q
+    K, R, m0 = check_resample(env.N, K, interval, survivors)
+    scratch, h = _evaluator_scratch(env)
+    st, bact = np.zeros((M, 2 * V), np.int8), np.zeros(M, np.uint32)
+    gap, clone, step, init = (np.zeros(M, np.int32) for _ in range(4))
+    cg = np.zeros((M, K), np.int32) if clone_gaps else None
+    dn = np.full((M, (env.max_actions - 1) // R, K), -2, np.int32) if donors else None
+    call("ppo_search_resample_states", policy._h, env._h, h, M, K, _p(sc, _lib.c_i8p), _p(dg, _lib.c_i8p),
+         _p(act, _lib.c_u32p), _p(st, _lib.c_i8p), _p(bact, _lib.c_u32p), _p(gap, _lib.c_i32p), _p(clone, _lib.c_i32p),
+         _p(step, _lib.c_i32p), _p(init, _lib.c_i32p), None if cg is None else _p(cg, _lib.c_i32p), R, m0,
+         None if dn is None else _p(dn, _lib.c_i32p))
+    out = dict(best_state=st, best_score=st[:, :V], best_degree=st[:, V:], best_active=bact, best_gap=gap, best_clone=clone,
+               best_step=step, initial_gap=init)
+    if donors:
+        out["donors"] = dn
     if clone_gaps:
         out["clone_gaps"] = cg
     return out

@@ -51,6 +51,8 @@ SIGNATURES = {
     "ppo_best_states": [H, H, H, C.c_int64, C.c_int32, c_i8p, c_u32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p],
     "ppo_search_best_states": [H, H, H, C.c_int64, C.c_int64, c_i8p, c_i8p, c_u32p, c_i8p, c_u32p, c_i32p, c_i32p, c_i32p,
                                c_i32p, c_i32p],
+    "ppo_search_resample_states": [H, H, H, C.c_int64, C.c_int64, c_i8p, c_i8p, c_u32p, c_i8p, c_u32p, c_i32p, c_i32p, c_i32p,
+                                   c_i32p, c_i32p, C.c_int64, C.c_int64, c_i32p],
     "ppo_set_rollout_persistent": [C.c_int32],
     "ppo_set_rollout_compact": [C.c_int32],
     "ppo_env_check_errors": [H, c_i32p],

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 
 
@@ -900,8 +901,9 @@ int32_t ppo_average_returns(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scra
 // The step loop of the evaluators and of the best-state search: observe, policy forward + sample, env step with the
 // bookkeeping of `ev` (k_env_step) or `tv` (k_env_step_track), until every env has used up its episodes_left (polled every
 // 8 steps) or Tmax steps have run.  Row 0 of `scratch` is the only rollout storage touched.
+// after_step (optional) runs behind the env step of loop step t, before the poll (the resampling search's events).
 static int32_t play_quotas(ppo_policy_s* pol, ppo_env_s* env, ppo_rollouts_s* scratch, int64_t Tmax, const EvalView* ev,
-                           const TrackView* tv, bool* all_done) {
+                           const TrackView* tv, bool* all_done, const std::function<int32_t(int64_t)>* after_step = nullptr) {
     const int64_t N = env->N;
     std::vector<int32_t> left((size_t)N);
     bool all = false;
@@ -910,6 +912,7 @@ static int32_t play_quotas(ppo_policy_s* pol, ppo_env_s* env, ppo_rollouts_s* sc
         PPO_TRY(launch_policy_rollout(pol, env, scratch->states.p, scratch->active.p, scratch->actions.p, scratch->p_sel.p, nullptr));
         if (tv) PPO_TRY(launch_env_step_track(env, scratch->actions.p, scratch->rewards.p, scratch->done.p, scratch->valid.p, *tv));
         else PPO_TRY(launch_env_step(env, scratch->actions.p, scratch->rewards.p, scratch->done.p, scratch->valid.p, 0, 1, ev));
+        if (after_step) PPO_TRY((*after_step)(t));
         if ((t & 7) == 7 || t + 1 == Tmax) {            // poll completion every 8 steps
             PPO_TRY(d2h(left.data(), env->episodes_left.p, (size_t)N));
             all = true;
@@ -1101,6 +1104,77 @@ int32_t ppo_search_best_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t s
     PPO_TRY(d2h(best_gap, out.tv.best_gap, Ms)); PPO_TRY(d2h(best_step, out.tv.best_step, Ms));
     PPO_TRY(d2h(initial_gap, out.tv.initial_gap, Ms)); PPO_TRY(d2h(best_clone, d_clone.p, Ms));
     if (clone_gaps_or_null) PPO_TRY(d2h(clone_gaps_or_null, d_gaps.p, Ms * (size_t)K));
+    return ppo_env_check_errors(env, nullptr);
+}
+
+// Resampling search: ppo_search_best_states' schedule with a resample event (k_search_resample: fold, rank,
+// copy) behind every interval-th step of a round, and one more fold behind the round's last step.  The events ride in
+// play_quotas' loop, which polls completion every 8 steps as for every other caller: an event costs a launch, no copy.
+int32_t ppo_search_resample_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
+                                   const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
+                                   uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
+                                   int32_t* initial_gap, int32_t* clone_gaps_or_null, int64_t interval, int64_t survivors,
+                                   int32_t* donors_or_null) {
+    ARG_CHECK(score && degree && active && best_state && best_active && best_gap && best_clone && best_step && initial_gap,
+              "search_resample_states: null argument");
+    PPO_TRY(check_shapes(scratch, env, pol));
+    const int64_t N = env->N, Mst = num_starts;
+    ARG_CHECK(Mst >= 1 && K >= 1 && K <= N, "search_resample_states: need num_starts >= 1 and 1 <= K <= N");
+    ARG_CHECK(interval >= 1, "search_resample_states: interval must be >= 1");
+    ARG_CHECK(survivors >= 1 && survivors <= K, "search_resample_states: need 1 <= survivors <= K");
+    PPO_TRY(check_internal_host(env->Q, Mst, score, degree, active));
+    if (K > PPO_RESAMPLE_MAX_K) {
+        ppo_set_error("search_resample_states: K above 4096 clones is not supported (the rank keys are staged in LDS)");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    const int32_t V = env->V, M = env->max_actions;
+    const int64_t S = N / K, E = (M - 1) / interval;
+    PPO_TRY(rollouts_reserve(scratch, 1, false));
+    std::vector<int8_t> snap((size_t)Mst * 2 * V);                       // k_env_snapshot's layout: score[V] then degree[V]
+    for (int64_t m = 0; m < Mst; ++m) {
+        std::memcpy(&snap[(size_t)m * 2 * V], score + m * V, (size_t)V);
+        std::memcpy(&snap[(size_t)m * 2 * V + V], degree + m * V, (size_t)V);
+    }
+    DevBuf<int8_t> d_start; DevBuf<uint32_t> d_act; DevBuf<int32_t> d_clone, d_gaps, d_donors;
+    PPO_TRY(d_start.alloc(snap.size())); PPO_TRY(d_act.alloc((size_t)Mst)); PPO_TRY(d_clone.alloc((size_t)Mst));
+    PPO_TRY(h2d(d_start.p, snap.data(), snap.size())); PPO_TRY(h2d(d_act.p, active, (size_t)Mst));
+    if (clone_gaps_or_null) PPO_TRY(d_gaps.alloc((size_t)Mst * K));
+    const size_t log_len = (size_t)Mst * (size_t)E * (size_t)K;
+    const bool want_log = donors_or_null && log_len > 0;
+    if (want_log) {                                                      // an event that never runs: every clone had terminated
+        std::fill(donors_or_null, donors_or_null + log_len, -2);
+        PPO_TRY(d_donors.alloc(log_len));
+        PPO_TRY(h2d(d_donors.p, donors_or_null, log_len));
+    }
+    TrackBufs rec, out;                                                  // per-env records of a round (slot = env); the results
+    PPO_TRY(rec.alloc(N, N, V, M, false, false));
+    PPO_TRY(out.alloc(1, Mst, V, M, false, false));
+    for (int64_t base = 0; base < Mst; base += S) {
+        const int64_t Sr = std::min(S, Mst - base);
+        HIP_TRY(hipMemsetAsync(rec.tv.ep_count, 0, (size_t)N * 4, g_stream));
+        PPO_TRY(launch_env_load_starts(env, d_start.p + (size_t)base * 2 * V, d_act.p + base, Sr * K, K, rec.tv.t_in));
+        int first = 1;
+        const std::function<int32_t(int64_t)> event = [&](int64_t t) -> int32_t {
+            const int64_t played = t + 1;                                // loop steps since the round's load
+            if (played % interval != 0 || played >= M) return PPO_OK;
+            PPO_TRY(launch_search_resample(env, rec.tv, Sr, K, survivors, first, out.tv, d_clone.p, base,
+                                           want_log ? d_donors.p : nullptr, E, played / interval - 1, nullptr));
+            first = 0;
+            return PPO_OK;
+        };
+        bool all = false;
+        PPO_TRY(play_quotas(pol, env, scratch, M, nullptr, &rec.tv, &all, &event));
+        ARG_CHECK(all, "search_resample_states: the trajectories did not finish within max_actions steps");
+        PPO_TRY(launch_search_resample(env, rec.tv, Sr, K, survivors, first | 2, out.tv, d_clone.p, base, nullptr, E, 0,
+                                       clone_gaps_or_null ? d_gaps.p : nullptr));
+    }
+    scratch->T = 0; scratch->len = 0; scratch->adv_T = -1; scratch->values_T = -1; scratch->boot_T = -1;
+    const size_t Ms = (size_t)Mst;
+    PPO_TRY(d2h(best_state, out.state.p, Ms * 2 * V)); PPO_TRY(d2h(best_active, out.active.p, Ms));
+    PPO_TRY(d2h(best_gap, out.tv.best_gap, Ms)); PPO_TRY(d2h(best_step, out.tv.best_step, Ms));
+    PPO_TRY(d2h(initial_gap, out.tv.initial_gap, Ms)); PPO_TRY(d2h(best_clone, d_clone.p, Ms));
+    if (clone_gaps_or_null) PPO_TRY(d2h(clone_gaps_or_null, d_gaps.p, Ms * (size_t)K));
+    if (want_log) PPO_TRY(d2h(donors_or_null, d_donors.p, log_len));
     return ppo_env_check_errors(env, nullptr);
 }
 

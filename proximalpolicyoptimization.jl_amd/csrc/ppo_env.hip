@@ -241,6 +241,113 @@ __global__ __launch_bounds__(256) void k_search_argmin(TrackView tv, int V, int6
     }
 }
 
+// resampling search, one event: one workgroup per start, fold -> rank -> copy.
+//   fold   k_search_argmin's reduction over the K records of the start (terminal clones included); the winner's record goes
+//          to the start's output record on the round's first fold (flags & 1), afterwards only on a STRICTLY lower gap.  A
+//          barrier separates it from the copies, which overwrite receivers' records.  flags & 2: the fold is all that runs.
+//   rank   live clones (done == 0) by (cur_gap, clone), cur_gap recomputed from the env's score bytes; the keys
+//          cur_gap << 32 | clone sit in LDS (~0 for a terminal clone) and a clone's rank is the number of lower keys: every
+//          lane of a wave reads the same LDS address, a broadcast.  Ranks below m = min(survivors, live) keep their state.
+//   copy   the clone of rank rho >= m takes state, record and t_in of the clone of rank (rho - m) % m: scalars by one thread
+//          per clone, score / degree / best_state as dwords across the workgroup.  Donors are never receivers: in place.
+// Dynamic LDS, 48 + 12 * Kp bytes (Kp = K rounded up to 8): wave_min [4], live count, keys [Kp], by_rank [Kp], rank_of [Kp];
+// every carve offset is a multiple of 16.
+extern __shared__ __attribute__((aligned(16))) unsigned char resample_lds[];
+__global__ __launch_bounds__(256) void k_search_resample(EnvView e, TrackView tv, int K, int survivors, int flags,
+                                                         TrackView out, int32_t* __restrict__ best_clone, int64_t out_base,
+                                                         int32_t* __restrict__ donors, int64_t E, int64_t event,
+                                                         int32_t* __restrict__ clone_gaps) {
+    unsigned long long* wave_min = reinterpret_cast<unsigned long long*>(resample_lds);
+    int* live_count = reinterpret_cast<int*>(resample_lds + 32);
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(resample_lds + 48);
+    const int Kp = (K + 7) & ~7;
+    uint16_t* by_rank = reinterpret_cast<uint16_t*>(keys + Kp);
+    uint16_t* rank_of = by_rank + Kp;
+    const int tid = threadIdx.x, V = e.V, dv = V / 4;
+    const int64_t s = blockIdx.x, o = out_base + s, env0 = s * K;
+    // ---- fold
+    const int out_gap = (flags & 1) ? 0 : out.best_gap[o];               // read by everyone before the barrier below
+    if (tid == 0) *live_count = 0;
+    unsigned long long best = ~0ull;
+    for (int c = tid; c < K; c += 256) {
+        const int g = tv.best_gap[env0 + c];
+        if (clone_gaps) clone_gaps[o * K + c] = g;
+        const unsigned long long key = ((unsigned long long)(uint32_t)g << 32) | (unsigned long long)(uint32_t)c;
+        best = key < best ? key : best;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const uint32_t hi = __shfl_xor((uint32_t)(best >> 32), off), lo = __shfl_xor((uint32_t)best, off);
+        const unsigned long long other = ((unsigned long long)hi << 32) | lo;
+        best = other < best ? other : best;
+    }
+    if ((tid & 63) == 0) wave_min[tid >> 6] = best;
+    __syncthreads();
+    best = wave_min[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) best = wave_min[w] < best ? wave_min[w] : best;
+    if ((flags & 1) || (int)(uint32_t)(best >> 32) < out_gap) {
+        const int64_t wenv = env0 + (int64_t)(uint32_t)best;
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(tv.best_state + wenv * 2 * V);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(out.best_state + o * 2 * V);
+        for (int d = tid; d < 2 * dv; d += 256) dst[d] = src[d];
+        if (tid == 0) {
+            out.best_active[o] = tv.best_active[wenv]; out.best_gap[o] = tv.best_gap[wenv];
+            out.best_step[o] = tv.best_step[wenv]; out.initial_gap[o] = tv.initial_gap[wenv];
+            best_clone[o] = (int32_t)(uint32_t)best;
+        }
+    }
+    if (flags & 2) return;
+    // ---- rank
+    for (int c = tid; c < K; c += 256) {
+        const int64_t n = env0 + c;
+        unsigned long long key = ~0ull;
+        if (!e.done[n]) {
+            const uint32_t act = e.active[n];
+            const int8_t* sc = e.score + n * V;
+            const int cur = env_total_abs(sc, act, e.Q), sum = env_total_sum(sc, act, e.Q);
+            key = ((unsigned long long)(uint32_t)(cur - (sum < 0 ? -sum : sum)) << 32) | (unsigned long long)(uint32_t)c;
+            atomicAdd(live_count, 1);
+        }
+        keys[c] = key;
+    }
+    __syncthreads();                              // the keys are staged; the winner's record is read (the copies may start)
+    const int live = *live_count, m = survivors < live ? survivors : live;
+    for (int c = tid; c < K; c += 256) {
+        const unsigned long long key = keys[c];
+        int r = 0xFFFF;                           // terminal
+        if (key != ~0ull) {
+            r = 0;
+            for (int j = 0; j < K; ++j) r += keys[j] < key ? 1 : 0;
+            if (r < m) by_rank[r] = (uint16_t)c;
+        }
+        rank_of[c] = (uint16_t)r;
+    }
+    __syncthreads();
+    // ---- copy
+    for (int c = tid; c < K; c += 256) {
+        const int r = rank_of[c];
+        int donor = r == 0xFFFF ? -2 : -1;
+        if (r != 0xFFFF && r >= m) {
+            donor = by_rank[(r - m) % m];
+            const int64_t n = env0 + c, d = env0 + donor;
+            e.active[n] = e.active[d]; e.steps[n] = e.steps[d]; e.reward[n] = e.reward[d];
+            tv.best_active[n] = tv.best_active[d]; tv.best_gap[n] = tv.best_gap[d]; tv.best_step[n] = tv.best_step[d];
+            tv.initial_gap[n] = tv.initial_gap[d]; tv.t_in[n] = tv.t_in[d];
+        }
+        if (donors) donors[(o * E + event) * K + c] = donor;
+    }
+    for (int i = tid; i < K * V; i += 256) {      // V dwords per clone: score [dv], degree [dv], best_state [2 dv]
+        const int c = i / V, d = i - c * V;
+        const int r = rank_of[c];
+        if (r == 0xFFFF || r < m) continue;
+        const int64_t n = env0 + c, dn = env0 + by_rank[(r - m) % m];
+        if (d < dv) reinterpret_cast<uint32_t*>(e.score + n * V)[d] = reinterpret_cast<const uint32_t*>(e.score + dn * V)[d];
+        else if (d < 2 * dv) reinterpret_cast<uint32_t*>(e.degree + n * V)[d - dv] = reinterpret_cast<const uint32_t*>(e.degree + dn * V)[d - dv];
+        else reinterpret_cast<uint32_t*>(tv.best_state + n * 2 * V)[d - 2 * dv] = reinterpret_cast<const uint32_t*>(tv.best_state + dn * 2 * V)[d - 2 * dv];
+    }
+}
+
 // state(env): obs[n][h][f] int8, f<36 template scores, f>=36 template degrees, 0 where the
 // template entry is missing or its quad is inactive (test/quad_game_utilities.jl:35-37,46-59).
 // One thread per output dword (4 features): coalesced 4-byte stores.
@@ -369,6 +476,21 @@ int32_t launch_search_argmin(const TrackView& tv, int32_t V, int64_t S, int64_t 
                              int32_t* clone_gaps, int64_t out_base) {
     hipLaunchKernelGGL(k_search_argmin, dim3((unsigned)S), dim3(256), 0, ppo_stream(), tv, (int)V, K, out, best_clone,
                        clone_gaps, out_base);
+    HIP_TRY(hipGetLastError());
+    return PPO_OK;
+}
+
+int32_t launch_search_resample(ppo_env_s* e, const TrackView& tv, int64_t S, int64_t K, int64_t survivors, int flags,
+                               const TrackView& out, int32_t* best_clone, int64_t out_base, int32_t* donors, int64_t E,
+                               int64_t event, int32_t* clone_gaps) {
+    if (K < 1 || K > PPO_RESAMPLE_MAX_K || S < 1 || S * K > e->N || e->V % 4 != 0) {
+        ppo_set_error("search_resample: unsupported shape");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    ProfScope ps((flags & 2) ? "k_search_fold" : "k_search_resample");
+    const size_t lds = 48 + 12 * (size_t)((K + 7) & ~(int64_t)7);
+    hipLaunchKernelGGL(k_search_resample, dim3((unsigned)S), dim3(256), lds, ppo_stream(), view_of(e), tv, (int)K,
+                       (int)survivors, flags, out, best_clone, out_base, donors, E, event, clone_gaps);
     HIP_TRY(hipGetLastError());
     return PPO_OK;
 }

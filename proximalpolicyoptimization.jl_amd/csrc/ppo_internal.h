@@ -318,6 +318,16 @@ int32_t launch_env_load_starts(ppo_env_s* e, const int8_t* start_state, const ui
 // records of `tv` (slot = env) into record out_base + s of `out`; clone_gaps (optional): [..][K] every clone's best gap
 int32_t launch_search_argmin(const TrackView& tv, int32_t V, int64_t S, int64_t K, const TrackView& out, int32_t* best_clone,
                              int32_t* clone_gaps, int64_t out_base);
+// resampling search, one launch for the S starts of a round: fold the K per-env records of every start into
+// record out_base + s of `out` (flags & 1: the round's first fold takes the winner as it is, later ones only a strictly
+// lower gap), then -- unless flags & 2, the fold behind a round's last step -- rank the live clones by (cur_gap, clone) and
+// overwrite every clone of rank >= m = min(survivors, live) with state, record and t_in of the clone of rank (rank - m) % m.
+// donors (optional): [..][E][K] log, row `event`; clone_gaps (optional): [..][K] every clone's record gap.  K above
+// PPO_RESAMPLE_MAX_K (the keys are staged in LDS): PPO_ERR_UNSUPPORTED
+constexpr int64_t PPO_RESAMPLE_MAX_K = 4096;
+int32_t launch_search_resample(ppo_env_s* e, const TrackView& tv, int64_t S, int64_t K, int64_t survivors, int flags,
+                               const TrackView& out, int32_t* best_clone, int64_t out_base, int32_t* donors, int64_t E,
+                               int64_t event, int32_t* clone_gaps);
 int32_t launch_env_observe(ppo_env_s* e, int8_t* obs_out, uint32_t* active_out);
 // compact rollout storage: env snapshot of every env (score[V] then degree[V]) -> cstate_out [N][2V]
 int32_t launch_env_snapshot(ppo_env_s* e, int8_t* cstate_out);
