@@ -596,6 +596,45 @@ int32_t ppo_search_resample_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts
                                    int32_t* initial_gap, int32_t* clone_gaps_or_null, int64_t interval, int64_t survivors,
                                    int32_t* donors_or_null);
 
+/* The action path to the best state.  A best state is a snapshot of the built-in env; what a caller who holds a real mesh
+ * next to it needs is the SEQUENCE OF ACTIONS that leads there (the reference's step!(wrapper, quad, edge, type) and
+ * plot_trajectory replay actions onto a mesh).  The three calls above, each with one more output of 0-based int16 action
+ * indices (an index is below 16 Q <= 512); every other argument and result is the plain call's:
+ *   ppo_best_states_actions           actions [num_trajectories][max_actions]: the whole trajectory, -1 behind `length`; its
+ *                                     first best_step entries lead from the trajectory's start to best_state;
+ *   ppo_search_best_states_path       path [num_starts][max_actions]: the winner's first best_step actions, -1 behind them;
+ *   ppo_search_resample_states_path   path [num_starts][max_actions], likewise.  The action history belongs to the LINEAGE:
+ *                                     a receiver takes the donor's played prefix together with its record and step count,
+ *                                     and a fold that takes a winner's record takes the first best_step entries of that
+ *                                     winner's history with it.  best_step counts steps along the lineage, so the path has
+ *                                     best_step entries.
+ * In every case ppo_env_apply_paths(start, path) gives best_state, best_active and best_gap, with applied == best_step. */
+int32_t ppo_best_states_actions(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_trajectories,
+                                int32_t reset_first, int8_t* best_state, uint32_t* best_active, int32_t* best_gap,
+                                int32_t* best_step, int32_t* length, int32_t* initial_gap, int32_t* trace_or_null,
+                                int32_t* type_counts_or_null, int16_t* actions);
+int32_t ppo_search_best_states_path(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
+                                    const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
+                                    uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
+                                    int32_t* initial_gap, int32_t* clone_gaps_or_null, int16_t* path);
+int32_t ppo_search_resample_states_path(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
+                                        const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
+                                        uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
+                                        int32_t* initial_gap, int32_t* clone_gaps_or_null, int64_t interval, int64_t survivors,
+                                        int32_t* donors_or_null, int16_t* path);
+/* Teacher-forced replay without a policy: path m of paths [M][stride] (0-based actions; an entry < 0 ends a path) is
+ * applied to start m (score, degree [M][V], active [M], checked like ppo_env_set_internal), which begins as reset! leaves an
+ * env (steps = 0, not terminal).  A path ends at its first entry < 0, after stride entries, or once the state is terminal
+ * (the optimum reached, or max_actions steps), whichever comes first.  Per path: out_state [2V] = score[V] then degree[V],
+ * out_active, out_gap = current_score - opt_score of that state, applied = the actions stepped; optional trace [M][stride] =
+ * initial_score - current_score behind every step, INT32_MIN behind `applied`.  The env handle supplies Q, max_actions and
+ * no_action_reward only: the resident envs, their ticks, episode counters and error flags are unchanged.  PPO_ERR_ARG before
+ * anything runs: a bad start, an entry >= 16 Q, stride < 1.  PPO_ERR_DEVICE_FLAG, the outputs filled: an action on an
+ * inactive quad (the step counts and changes nothing, as step! does). */
+int32_t ppo_env_apply_paths(ppo_env_t env, int64_t M, const int8_t* score, const int8_t* degree, const uint32_t* active,
+                            const int16_t* paths, int64_t stride, int8_t* out_state, uint32_t* out_active, int32_t* out_gap,
+                            int32_t* applied, int32_t* trace_or_null);
+
 /* timing of the dominant kernels of the last ppo_train / ppo_collect_rollouts call, measured with
  * HIP events on the engine's stream (bench.py roofline leg) */
 /* measurement helper: run the return scan `iters` times on device-resident synthetic [T,N] columns (no host

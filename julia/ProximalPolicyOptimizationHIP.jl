@@ -338,6 +338,76 @@ function search_resample_states(env::HipVecEnv, p::HipPolicy, score::Matrix{Int8
      clone_gaps = gaps, donors = donors)
 end
 
+# The action path to the best state: what step!(wrapper, quad, edge, type) replays onto a mesh.  The three calls above with one
+# more output, Int16 [max_actions, n] of 1-based action indices (as the rollout buffer's selected_actions), 0 behind a path's
+# end.  The library speaks 0-based indices with -1 as padding: the shim adds / subtracts the 1.  (Int16 arrays cross the ccall
+# as Ptr{Cvoid}.)
+function best_states_actions(env::HipVecEnv, p::HipPolicy, num_trajectories; reset_first = true)
+    scratch = HipRollouts()
+    h = ensure!(scratch, env, 1)
+    nt, V = Int(num_trajectories), 4 * env.Q
+    st, act = zeros(Int8, 2V, nt), zeros(UInt32, nt)
+    gap, step, len, init = zeros(Int32, nt), zeros(Int32, nt), zeros(Int32, nt), zeros(Int32, nt)
+    trace, types = zeros(Int32, env.max_actions, nt), zeros(Int32, 4, nt)
+    actions = zeros(Int16, env.max_actions, nt)
+    check(ccall((:ppo_best_states_actions, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Int8}, Ptr{UInt32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32},
+                 Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Cvoid}),
+                p.h, env.h, h, nt, Int32(reset_first), st, act, gap, step, len, init, trace, types, actions))
+    (best_state = st, best_active = act, best_gap = gap, best_step = step, length = len, initial_gap = init, trace = trace,
+     type_counts = types, actions = actions .+ Int16(1))
+end
+# path[1:best_step[i], i]: the winner's actions from start i to its best state
+function search_best_states_path(env::HipVecEnv, p::HipPolicy, score::Matrix{Int8}, degree::Matrix{Int8}, active::Vector{UInt32}, K)
+    scratch = HipRollouts()
+    h = ensure!(scratch, env, 1)
+    M, V = length(active), 4 * env.Q
+    st, act = zeros(Int8, 2V, M), zeros(UInt32, M)
+    gap, clone, step, init = zeros(Int32, M), zeros(Int32, M), zeros(Int32, M), zeros(Int32, M)
+    gaps = zeros(Int32, Int(K), M)
+    path = zeros(Int16, env.max_actions, M)
+    check(ccall((:ppo_search_best_states_path, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Int8}, Ptr{Int8}, Ptr{UInt32}, Ptr{Int8}, Ptr{UInt32},
+                 Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Cvoid}),
+                p.h, env.h, h, M, Int64(K), score, degree, active, st, act, gap, clone, step, init, gaps, path))
+    (best_state = st, best_active = act, best_gap = gap, best_clone = clone, best_step = step, initial_gap = init,
+     clone_gaps = gaps, path = path .+ Int16(1))
+end
+# ... along the lineage of the result: a copy carries the donor's actions with its record
+function search_resample_states_path(env::HipVecEnv, p::HipPolicy, score::Matrix{Int8}, degree::Matrix{Int8},
+                                     active::Vector{UInt32}, K, interval, survivors)
+    scratch = HipRollouts()
+    h = ensure!(scratch, env, 1)
+    M, V = length(active), 4 * env.Q
+    st, act = zeros(Int8, 2V, M), zeros(UInt32, M)
+    gap, clone, step, init = zeros(Int32, M), zeros(Int32, M), zeros(Int32, M), zeros(Int32, M)
+    gaps = zeros(Int32, Int(K), M)
+    donors = fill(Int32(-2), Int(K), div(env.max_actions - 1, Int(interval)), M)
+    path = zeros(Int16, env.max_actions, M)
+    check(ccall((:ppo_search_resample_states_path, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Int8}, Ptr{Int8}, Ptr{UInt32}, Ptr{Int8}, Ptr{UInt32},
+                 Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int64, Int64, Ptr{Int32}, Ptr{Cvoid}),
+                p.h, env.h, h, M, Int64(K), score, degree, active, st, act, gap, clone, step, init, gaps, Int64(interval),
+                Int64(survivors), donors, path))
+    (best_state = st, best_active = act, best_gap = gap, best_clone = clone, best_step = step, initial_gap = init,
+     clone_gaps = gaps, donors = donors, path = path .+ Int16(1))
+end
+# teacher-forced replay without a policy: paths [stride, M] column-major == [M][stride], 1-based, anything <= 0 ends a path;
+# start i (score, degree [V, M], active [M]) begins as reset! leaves an env.  env supplies Q, max_actions and no_action_reward
+# only.  apply_paths(env, starts..., r.path) of a search result r gives r.best_state, r.best_active, r.best_gap, applied == r.best_step
+function apply_paths(env::HipVecEnv, score::Matrix{Int8}, degree::Matrix{Int8}, active::Vector{UInt32}, paths::Matrix{Int16})
+    M, V, stride = length(active), 4 * env.Q, size(paths, 1)
+    raw = max.(paths, Int16(0)) .- Int16(1)
+    st, act = zeros(Int8, 2V, M), zeros(UInt32, M)
+    gap, applied = zeros(Int32, M), zeros(Int32, M)
+    trace = zeros(Int32, stride, M)
+    check(ccall((:ppo_env_apply_paths, LIB), Int32,
+                (Ptr{Cvoid}, Int64, Ptr{Int8}, Ptr{Int8}, Ptr{UInt32}, Ptr{Cvoid}, Int64, Ptr{Int8}, Ptr{UInt32}, Ptr{Int32},
+                 Ptr{Int32}, Ptr{Int32}),
+                env.h, M, score, degree, active, raw, Int64(stride), st, act, gap, applied, trace))
+    (state = st, active = act, gap = gap, applied = applied, trace = trace)
+end
+
 # batch_advantage plugin mode handed to the engine: 0 = returns (PPO.batch_advantage above), 1 = normalised returns,
 # 2 / 3 = GAE(gamma, lambda) / normalised GAE over values supplied through compute_gae!
 const ADV_MODE = Ref{Int32}(0)

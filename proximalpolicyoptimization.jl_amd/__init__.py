@@ -59,7 +59,7 @@ __all__ = [
     "value_train_", "pooled_state_value", "value_loss", "value_loss_clipped",
     "kl_stats", "explained_variance_", "explained_variance_from_sums",
     "check_internal", "best_states_", "best_state_in_rollout", "single_trajectory_scores", "count_non_flips",
-    "search_best_states_", "search_resample_states_", "check_resample",
+    "search_best_states_", "search_resample_states_", "check_resample", "apply_paths_", "check_paths",
 ]
 
 
@@ -1636,33 +1636,47 @@ def check_internal(score, degree, active, Q):
     return sc, dg, act
 
 
-def _best_states(env, policy, num_trajectories, reset_first, scores, action_types):
+def _paths_out(raw):
+    """0-based device rows with -1 as padding -> the reference's 1-based action indices with 0 as padding."""
+    return (raw + 1).astype(np.int16)
+
+
+def _best_states(env, policy, num_trajectories, reset_first, scores, action_types, actions=False):
     nt, V = int(num_trajectories), 4 * env.Q
     scratch, h = _evaluator_scratch(env)
     st, act = np.zeros((nt, 2 * V), np.int8), np.zeros(nt, np.uint32)
     gap, step, length, init = (np.zeros(nt, np.int32) for _ in range(4))
     tr = np.zeros((nt, env.max_actions), np.int32) if scores else None
     tc = np.zeros((nt, 4), np.int32) if action_types else None
-    call("ppo_best_states", policy._h, env._h, h, nt, int(bool(reset_first)), _p(st, _lib.c_i8p), _p(act, _lib.c_u32p),
-         _p(gap, _lib.c_i32p), _p(step, _lib.c_i32p), _p(length, _lib.c_i32p), _p(init, _lib.c_i32p),
-         None if tr is None else _p(tr, _lib.c_i32p), None if tc is None else _p(tc, _lib.c_i32p))
+    args = (policy._h, env._h, h, nt, int(bool(reset_first)), _p(st, _lib.c_i8p), _p(act, _lib.c_u32p),
+            _p(gap, _lib.c_i32p), _p(step, _lib.c_i32p), _p(length, _lib.c_i32p), _p(init, _lib.c_i32p),
+            None if tr is None else _p(tr, _lib.c_i32p), None if tc is None else _p(tc, _lib.c_i32p))
+    if actions:
+        ac = np.zeros((nt, env.max_actions), np.int16)
+        call("ppo_best_states_actions", *args, _p(ac, _lib.c_i16p))
+    else:
+        call("ppo_best_states", *args)
     out = dict(best_state=st, best_score=st[:, :V], best_degree=st[:, V:], best_active=act, best_gap=gap, best_step=step,
                length=length, initial_gap=init)
     if scores:
         out["trace"] = tr
     if action_types:
         out["type_counts"] = tc
+    if actions:
+        out["actions"] = _paths_out(ac)
     return out
 
 
-def best_states_(env, policy, num_trajectories, scores=False, action_types=False):
+def best_states_(env, policy, num_trajectories, scores=False, action_types=False, actions=False):
     """best_state_in_rollout (test/quad_game_utilities.jl:341-358) over num_trajectories trajectories in the
     average_best_returns convention: trajectory e on env e mod N, reset! before each, env-major output.  Returns a dict of
     arrays, one row per trajectory: best_state [2V] (best_score / best_degree are its halves), best_active, best_gap
     (current_score - opt_score of that state), best_step (steps played when it was reached, 0 = the start: the first
     minimum, like argmin), length, initial_gap; scores=True adds trace [max_actions] (single_trajectory_scores:
-    initial_score - current_score behind every step, INT32_MIN behind the end), action_types=True adds type_counts [4]."""
-    return _best_states(env, policy, num_trajectories, True, scores, action_types)
+    initial_score - current_score behind every step, INT32_MIN behind the end), action_types=True adds type_counts [4],
+    actions=True adds actions [max_actions] int16: the trajectory's 1-based action indices (as selected_actions and step_
+    speak them), 0 behind its end; the first best_step of them lead from the trajectory's start to best_state."""
+    return _best_states(env, policy, num_trajectories, True, scores, action_types, actions)
 
 
 def best_state_in_rollout(env, policy, rng=None):
@@ -1693,13 +1707,14 @@ def count_non_flips(env, policy, rng=None):
     return r["type_counts"][:, 2:].sum(axis=1, dtype=np.int64)
 
 
-def search_best_states_(env, policy, score, degree, active, K, clone_gaps=False):
+def search_best_states_(env, policy, score, degree, active, K, clone_gaps=False, path=False):
     """Best of K stochastic trajectories from each caller-supplied start state (score, degree [M, 4Q], active [M]):
     K resident envs are loaded with one start and, sampling being keyed on (global env id, tick), play K different
     trajectories; N // K starts run at a time.  Returns a dict of arrays, one row per start: best_state [2V] (best_score /
     best_degree), best_active, best_gap, best_clone, best_step, initial_gap; clone_gaps=True adds clone_gaps [M, K].  Ties go
     to the lowest clone, then its first minimum.  No reset! runs: episode counters stay, ticks advance by the steps played,
-    the envs that played are left terminal."""
+    the envs that played are left terminal.  path=True adds path [M, max_actions] int16: the winner's best_step 1-based
+    actions from the start to best_state, 0 behind them (apply_paths_ replays them)."""
     sc, dg, act = check_internal(score, degree, active, env.Q)
     M, V, K = sc.shape[0], 4 * env.Q, int(K)
     if not 1 <= K <= env.N:
@@ -1708,13 +1723,20 @@ def search_best_states_(env, policy, score, degree, active, K, clone_gaps=False)
     st, bact = np.zeros((M, 2 * V), np.int8), np.zeros(M, np.uint32)
     gap, clone, step, init = (np.zeros(M, np.int32) for _ in range(4))
     cg = np.zeros((M, K), np.int32) if clone_gaps else None
-    call("ppo_search_best_states", policy._h, env._h, h, M, K, _p(sc, _lib.c_i8p), _p(dg, _lib.c_i8p), _p(act, _lib.c_u32p),
-         _p(st, _lib.c_i8p), _p(bact, _lib.c_u32p), _p(gap, _lib.c_i32p), _p(clone, _lib.c_i32p), _p(step, _lib.c_i32p),
-         _p(init, _lib.c_i32p), None if cg is None else _p(cg, _lib.c_i32p))
+    args = (policy._h, env._h, h, M, K, _p(sc, _lib.c_i8p), _p(dg, _lib.c_i8p), _p(act, _lib.c_u32p),
+            _p(st, _lib.c_i8p), _p(bact, _lib.c_u32p), _p(gap, _lib.c_i32p), _p(clone, _lib.c_i32p), _p(step, _lib.c_i32p),
+            _p(init, _lib.c_i32p), None if cg is None else _p(cg, _lib.c_i32p))
+    if path:
+        pa = np.zeros((M, env.max_actions), np.int16)
+        call("ppo_search_best_states_path", *args, _p(pa, _lib.c_i16p))
+    else:
+        call("ppo_search_best_states", *args)
     out = dict(best_state=st, best_score=st[:, :V], best_degree=st[:, V:], best_active=bact, best_gap=gap, best_clone=clone,
                best_step=step, initial_gap=init)
     if clone_gaps:
         out["clone_gaps"] = cg
+    if path:
+        out["path"] = _paths_out(pa)
     return out
 
 
@@ -1735,7 +1757,8 @@ def check_resample(N, K, interval, survivors):
     return K, R, m0
 
 
-def search_resample_states_(env, policy, score, degree, active, K, interval, survivors, donors=False, clone_gaps=False):
+def search_resample_states_(env, policy, score, degree, active, K, interval, survivors, donors=False, clone_gaps=False,
+                            path=False):
     """search_best_states_ with resampling: behind every `interval`-th step of a round (t % interval == 0, t < max_actions)
     each start folds its K clones' records into its result (the lowest (best_gap, clone); the first fold as it is, later
     ones only on a strictly lower gap), ranks its live clones by (current_score - opt_score now, clone) and overwrites
@@ -1744,7 +1767,9 @@ def search_resample_states_(env, policy, score, degree, active, K, interval, sur
     result.  Returns the dict of search_best_states_ (best_step counts steps along the lineage); donors=True adds donors
     [M, E, K] int32 with E = (max_actions - 1) // interval: a receiver's donor clone, -1 a live clone that kept its state, -2
     a terminal clone or an event that no longer ran; clone_gaps=True adds every clone's record gap at the last fold.
-    interval >= max_actions runs no event (search_best_states_); survivors == K copies nothing.  HipVecEnv only."""
+    interval >= max_actions runs no event (search_best_states_); survivors == K copies nothing.  path=True adds path
+    [M, max_actions] int16: the best_step 1-based actions that lead from the start to best_state along the result's lineage
+    (a copy carries the donor's actions with its record), 0 behind them.  HipVecEnv only."""
     if not isinstance(env, HipVecEnv):
         raise PPOError(-4, "search_resample_states_ needs a HipVecEnv")
     sc, dg, act = check_internal(score, degree, active, env.Q)
@@ -1755,16 +1780,62 @@ def search_resample_states_(env, policy, score, degree, active, K, interval, sur
     gap, clone, step, init = (np.zeros(M, np.int32) for _ in range(4))
     cg = np.zeros((M, K), np.int32) if clone_gaps else None
     dn = np.full((M, (env.max_actions - 1) // R, K), -2, np.int32) if donors else None
-    call("ppo_search_resample_states", policy._h, env._h, h, M, K, _p(sc, _lib.c_i8p), _p(dg, _lib.c_i8p),
-         _p(act, _lib.c_u32p), _p(st, _lib.c_i8p), _p(bact, _lib.c_u32p), _p(gap, _lib.c_i32p), _p(clone, _lib.c_i32p),
-         _p(step, _lib.c_i32p), _p(init, _lib.c_i32p), None if cg is None else _p(cg, _lib.c_i32p), R, m0,
-         None if dn is None else _p(dn, _lib.c_i32p))
+    args = (policy._h, env._h, h, M, K, _p(sc, _lib.c_i8p), _p(dg, _lib.c_i8p),
+            _p(act, _lib.c_u32p), _p(st, _lib.c_i8p), _p(bact, _lib.c_u32p), _p(gap, _lib.c_i32p), _p(clone, _lib.c_i32p),
+            _p(step, _lib.c_i32p), _p(init, _lib.c_i32p), None if cg is None else _p(cg, _lib.c_i32p), R, m0,
+            None if dn is None else _p(dn, _lib.c_i32p))
+    if path:
+        pa = np.zeros((M, env.max_actions), np.int16)
+        call("ppo_search_resample_states_path", *args, _p(pa, _lib.c_i16p))
+    else:
+        call("ppo_search_resample_states", *args)
     out = dict(best_state=st, best_score=st[:, :V], best_degree=st[:, V:], best_active=bact, best_gap=gap, best_clone=clone,
                best_step=step, initial_gap=init)
     if donors:
         out["donors"] = dn
     if clone_gaps:
         out["clone_gaps"] = cg
+    if path:
+        out["path"] = _paths_out(pa)
+    return out
+
+
+def check_paths(paths, M, Q):
+    """What apply_paths_ requires of its paths (ppo_env_apply_paths checks the same): an integer array [M, stride] with
+    stride >= 1 of 1-based action indices <= 16 Q, anything <= 0 ending a path.  Returns them 0-based, int16, C-contiguous
+    (-1 where a path has ended); PPOError(PPO_ERR_ARG) otherwise."""
+    pa = np.asarray(paths)
+    if pa.ndim != 2 or pa.shape[0] != int(M) or pa.shape[1] < 1 or not np.issubdtype(pa.dtype, np.integer):
+        raise PPOError(-1, "AssertionError: env_apply_paths: paths must be an integer array [%d, stride], stride >= 1" % int(M))
+    if np.any(pa > 16 * int(Q)):
+        raise PPOError(-1, "AssertionError: env_apply_paths: action index out of range")
+    return np.ascontiguousarray(np.maximum(pa.astype(np.int64), 0) - 1, np.int16)
+
+
+def apply_paths_(env, score, degree, active, paths, scores=False):
+    """Teacher-forced replay without a policy: path m (paths [M, stride], 1-based action indices as selected_actions, step_
+    and the path / actions outputs of the searches speak them, 0 behind a path's end) is applied to start m (score, degree
+    [M, 4Q], active [M]), which begins as reset! leaves an env.  A path ends at its first 0, after stride entries or once
+    the state is terminal.  Returns a dict of arrays, one row per path: state [2V] (score / degree are its halves), active,
+    gap, applied (the actions stepped); scores=True adds trace [stride] (initial_score - current_score behind every step,
+    INT32_MIN behind applied).  env supplies Q, max_actions and no_action_reward only: its resident envs, ticks and counters
+    are unchanged.  Replaying a search's path from its start gives best_state, best_active, best_gap and applied ==
+    best_step.  HipVecEnv only."""
+    if not isinstance(env, HipVecEnv):
+        raise PPOError(-4, "apply_paths_ needs a HipVecEnv")
+    sc, dg, act = check_internal(score, degree, active, env.Q)
+    M, V = sc.shape[0], 4 * env.Q
+    pa = check_paths(paths, M, env.Q)
+    stride = pa.shape[1]
+    st, oact = np.zeros((M, 2 * V), np.int8), np.zeros(M, np.uint32)
+    gap, applied = np.zeros(M, np.int32), np.zeros(M, np.int32)
+    tr = np.zeros((M, stride), np.int32) if scores else None
+    call("ppo_env_apply_paths", env._h, M, _p(sc, _lib.c_i8p), _p(dg, _lib.c_i8p), _p(act, _lib.c_u32p), _p(pa, _lib.c_i16p),
+         stride, _p(st, _lib.c_i8p), _p(oact, _lib.c_u32p), _p(gap, _lib.c_i32p), _p(applied, _lib.c_i32p),
+         None if tr is None else _p(tr, _lib.c_i32p))
+    out = dict(state=st, score=st[:, :V], degree=st[:, V:], active=oact, gap=gap, applied=applied)
+    if scores:
+        out["trace"] = tr
     return out
 
 

@@ -13,6 +13,7 @@ c_f32p = C.POINTER(C.c_float)
 c_f64p = C.POINTER(C.c_double)
 c_u8p = C.POINTER(C.c_uint8)
 c_i8p = C.POINTER(C.c_int8)
+c_i16p = C.POINTER(C.c_int16)
 c_i32p = C.POINTER(C.c_int32)
 c_u32p = C.POINTER(C.c_uint32)
 c_i64p = C.POINTER(C.c_int64)
@@ -53,6 +54,13 @@ SIGNATURES = {
                                c_i32p, c_i32p],
     "ppo_search_resample_states": [H, H, H, C.c_int64, C.c_int64, c_i8p, c_i8p, c_u32p, c_i8p, c_u32p, c_i32p, c_i32p, c_i32p,
                                    c_i32p, c_i32p, C.c_int64, C.c_int64, c_i32p],
+    "ppo_best_states_actions": [H, H, H, C.c_int64, C.c_int32, c_i8p, c_u32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p,
+                                c_i16p],
+    "ppo_search_best_states_path": [H, H, H, C.c_int64, C.c_int64, c_i8p, c_i8p, c_u32p, c_i8p, c_u32p, c_i32p, c_i32p, c_i32p,
+                                    c_i32p, c_i32p, c_i16p],
+    "ppo_search_resample_states_path": [H, H, H, C.c_int64, C.c_int64, c_i8p, c_i8p, c_u32p, c_i8p, c_u32p, c_i32p, c_i32p,
+                                        c_i32p, c_i32p, c_i32p, C.c_int64, C.c_int64, c_i32p, c_i16p],
+    "ppo_env_apply_paths": [H, C.c_int64, c_i8p, c_i8p, c_u32p, c_i16p, C.c_int64, c_i8p, c_u32p, c_i32p, c_i32p, c_i32p],
     "ppo_set_rollout_persistent": [C.c_int32],
     "ppo_set_rollout_compact": [C.c_int32],
     "ppo_env_check_errors": [H, c_i32p],

@@ -994,9 +994,10 @@ int32_t ppo_average_normalized_returns(ppo_policy_t pol, ppo_env_t env, ppo_roll
 // ---------------------------------------------------------------- best state of a rollout, best-of-K search
 // device storage of TrackView records: `slots` output records and the per-env running values
 struct TrackBufs {
-    DevBuf<int32_t> per_env, ints, trace, types; DevBuf<int8_t> state; DevBuf<uint32_t> active;
+    DevBuf<int32_t> per_env, ints, trace, types; DevBuf<int8_t> state; DevBuf<uint32_t> active; DevBuf<int16_t> acts;
     TrackView tv;
-    int32_t alloc(int64_t N, int64_t slots, int32_t V, int32_t max_actions, bool want_trace, bool want_types) {
+    int32_t alloc(int64_t N, int64_t slots, int32_t V, int32_t max_actions, bool want_trace, bool want_types,
+                  bool want_actions = false) {
         const size_t S = (size_t)slots;
         PPO_TRY(per_env.alloc((size_t)3 * N)); PPO_TRY(ints.alloc(4 * S)); PPO_TRY(state.alloc(S * 2 * V)); PPO_TRY(active.alloc(S));
         HIP_TRY(hipMemsetAsync(per_env.p, 0, (size_t)3 * N * 4, g_stream));
@@ -1017,16 +1018,21 @@ struct TrackBufs {
             HIP_TRY(hipMemsetAsync(types.p, 0, S * 4 * 4, g_stream));
             tv.type_counts = types.p;
         }
+        if (want_actions) {                                               // -1 everywhere: what stays behind a trajectory's end
+            PPO_TRY(acts.alloc(S * max_actions));
+            HIP_TRY(hipMemsetAsync(acts.p, 0xFF, S * max_actions * sizeof(int16_t), g_stream));
+            tv.actions = acts.p;
+        }
         return PPO_OK;
     }
 };
 
 // best_state_in_rollout (test/quad_game_utilities.jl:341-358) for num_trajectories trajectories, with
 // single_trajectory_scores (:309-323) and the action-type counts behind count_non_flips (test/random_quad.jl:9-27)
-int32_t ppo_best_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_trajectories,
-                        int32_t reset_first, int8_t* best_state, uint32_t* best_active, int32_t* best_gap,
-                        int32_t* best_step, int32_t* length, int32_t* initial_gap, int32_t* trace_or_null,
-                        int32_t* type_counts_or_null) {
+static int32_t best_states_impl(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_trajectories,
+                                int32_t reset_first, int8_t* best_state, uint32_t* best_active, int32_t* best_gap,
+                                int32_t* best_step, int32_t* length, int32_t* initial_gap, int32_t* trace_or_null,
+                                int32_t* type_counts_or_null, int16_t* actions_or_null) {
     ARG_CHECK(best_state && best_active && best_gap && best_step && length && initial_gap, "best_states: null argument");
     PPO_TRY(check_shapes(scratch, env, pol));
     const int64_t N = env->N, nt = num_trajectories;
@@ -1041,7 +1047,7 @@ int32_t ppo_best_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch,
     const int32_t M = env->max_actions, V = env->V;
     PPO_TRY(rollouts_reserve(scratch, 1, false));
     TrackBufs b;
-    PPO_TRY(b.alloc(N, nt, V, M, trace_or_null != nullptr, type_counts_or_null != nullptr));
+    PPO_TRY(b.alloc(N, nt, V, M, trace_or_null != nullptr, type_counts_or_null != nullptr, actions_or_null != nullptr));
     hipLaunchKernelGGL(k_episode_quota, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, g_stream, env->episodes_left.p, N, nt);
     if (reset_first) PPO_TRY(launch_env_reset(env, 0));                 // reset!(env) before the first trajectory
     bool all = false;
@@ -1058,16 +1064,36 @@ int32_t ppo_best_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch,
             for (int32_t t = std::max(length[s], 0); t < M; ++t) trace_or_null[s * M + t] = INT32_MIN;
     }
     if (type_counts_or_null) PPO_TRY(d2h(type_counts_or_null, b.types.p, S * 4));
+    if (actions_or_null) PPO_TRY(d2h(actions_or_null, b.acts.p, S * M));
     return ppo_env_check_errors(env, nullptr);
+}
+
+int32_t ppo_best_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_trajectories,
+                        int32_t reset_first, int8_t* best_state, uint32_t* best_active, int32_t* best_gap,
+                        int32_t* best_step, int32_t* length, int32_t* initial_gap, int32_t* trace_or_null,
+                        int32_t* type_counts_or_null) {
+    return best_states_impl(pol, env, scratch, num_trajectories, reset_first, best_state, best_active, best_gap, best_step,
+                            length, initial_gap, trace_or_null, type_counts_or_null, nullptr);
+}
+
+// ... with every trajectory's 0-based actions: row [max_actions], -1 behind `length`; its first best_step
+// entries are the path to the best state
+int32_t ppo_best_states_actions(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_trajectories,
+                                int32_t reset_first, int8_t* best_state, uint32_t* best_active, int32_t* best_gap,
+                                int32_t* best_step, int32_t* length, int32_t* initial_gap, int32_t* trace_or_null,
+                                int32_t* type_counts_or_null, int16_t* actions) {
+    ARG_CHECK(actions, "best_states_actions: null argument");
+    return best_states_impl(pol, env, scratch, num_trajectories, reset_first, best_state, best_active, best_gap, best_step,
+                            length, initial_gap, trace_or_null, type_counts_or_null, actions);
 }
 
 // Best-of-K search from caller-supplied start states.  Sampling is keyed on (global env id, tick), so K resident envs loaded
 // with one state play K different trajectories: rounds of S = N / K starts, each a load (k_env_load_starts), the tracked
 // step loop and one reduction (k_search_argmin).  No reset! runs: the episode counters stay, ticks advance by the steps played.
-int32_t ppo_search_best_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
-                               const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
-                               uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
-                               int32_t* initial_gap, int32_t* clone_gaps_or_null) {
+static int32_t search_best_states_impl(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
+                                       const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
+                                       uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
+                                       int32_t* initial_gap, int32_t* clone_gaps_or_null, int16_t* path_or_null) {
     ARG_CHECK(score && degree && active && best_state && best_active && best_gap && best_clone && best_step && initial_gap,
               "search_best_states: null argument");
     PPO_TRY(check_shapes(scratch, env, pol));
@@ -1087,8 +1113,8 @@ int32_t ppo_search_best_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t s
     PPO_TRY(h2d(d_start.p, snap.data(), snap.size())); PPO_TRY(h2d(d_act.p, active, (size_t)Mst));
     if (clone_gaps_or_null) PPO_TRY(d_gaps.alloc((size_t)Mst * K));
     TrackBufs rec, out;                                                  // per-env records of a round (slot = env); the winners
-    PPO_TRY(rec.alloc(N, N, V, env->max_actions, false, false));
-    PPO_TRY(out.alloc(1, Mst, V, env->max_actions, false, false));
+    PPO_TRY(rec.alloc(N, N, V, env->max_actions, false, false, path_or_null != nullptr));
+    PPO_TRY(out.alloc(1, Mst, V, env->max_actions, false, false, path_or_null != nullptr));
     for (int64_t base = 0; base < Mst; base += S) {
         const int64_t Sr = std::min(S, Mst - base);
         HIP_TRY(hipMemsetAsync(rec.tv.ep_count, 0, (size_t)N * 4, g_stream));
@@ -1096,7 +1122,8 @@ int32_t ppo_search_best_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t s
         bool all = false;
         PPO_TRY(play_quotas(pol, env, scratch, env->max_actions, nullptr, &rec.tv, &all));
         ARG_CHECK(all, "search_best_states: the trajectories did not finish within max_actions steps");
-        PPO_TRY(launch_search_argmin(rec.tv, V, Sr, K, out.tv, d_clone.p, clone_gaps_or_null ? d_gaps.p : nullptr, base));
+        PPO_TRY(launch_search_argmin(rec.tv, V, Sr, K, out.tv, d_clone.p, clone_gaps_or_null ? d_gaps.p : nullptr, base,
+                                     env->max_actions));
     }
     scratch->T = 0; scratch->len = 0; scratch->adv_T = -1; scratch->values_T = -1; scratch->boot_T = -1;
     const size_t Ms = (size_t)Mst;
@@ -1104,17 +1131,37 @@ int32_t ppo_search_best_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t s
     PPO_TRY(d2h(best_gap, out.tv.best_gap, Ms)); PPO_TRY(d2h(best_step, out.tv.best_step, Ms));
     PPO_TRY(d2h(initial_gap, out.tv.initial_gap, Ms)); PPO_TRY(d2h(best_clone, d_clone.p, Ms));
     if (clone_gaps_or_null) PPO_TRY(d2h(clone_gaps_or_null, d_gaps.p, Ms * (size_t)K));
+    if (path_or_null) PPO_TRY(d2h(path_or_null, out.acts.p, Ms * (size_t)env->max_actions));
     return ppo_env_check_errors(env, nullptr);
+}
+
+int32_t ppo_search_best_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
+                               const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
+                               uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
+                               int32_t* initial_gap, int32_t* clone_gaps_or_null) {
+    return search_best_states_impl(pol, env, scratch, num_starts, K, score, degree, active, best_state, best_active, best_gap,
+                                   best_clone, best_step, initial_gap, clone_gaps_or_null, nullptr);
+}
+
+// ... with the path to every start's result: the winner's first best_step 0-based actions, -1 behind them
+int32_t ppo_search_best_states_path(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
+                                    const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
+                                    uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
+                                    int32_t* initial_gap, int32_t* clone_gaps_or_null, int16_t* path) {
+    ARG_CHECK(path, "search_best_states_path: null argument");
+    return search_best_states_impl(pol, env, scratch, num_starts, K, score, degree, active, best_state, best_active, best_gap,
+                                   best_clone, best_step, initial_gap, clone_gaps_or_null, path);
 }
 
 // Resampling search: ppo_search_best_states' schedule with a resample event (k_search_resample: fold, rank,
 // copy) behind every interval-th step of a round, and one more fold behind the round's last step.  The events ride in
 // play_quotas' loop, which polls completion every 8 steps as for every other caller: an event costs a launch, no copy.
-int32_t ppo_search_resample_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
-                                   const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
-                                   uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
-                                   int32_t* initial_gap, int32_t* clone_gaps_or_null, int64_t interval, int64_t survivors,
-                                   int32_t* donors_or_null) {
+static int32_t search_resample_states_impl(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts,
+                                           int64_t K, const int8_t* score, const int8_t* degree, const uint32_t* active,
+                                           int8_t* best_state, uint32_t* best_active, int32_t* best_gap, int32_t* best_clone,
+                                           int32_t* best_step, int32_t* initial_gap, int32_t* clone_gaps_or_null,
+                                           int64_t interval, int64_t survivors, int32_t* donors_or_null,
+                                           int16_t* path_or_null) {
     ARG_CHECK(score && degree && active && best_state && best_active && best_gap && best_clone && best_step && initial_gap,
               "search_resample_states: null argument");
     PPO_TRY(check_shapes(scratch, env, pol));
@@ -1147,8 +1194,8 @@ int32_t ppo_search_resample_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts
         PPO_TRY(h2d(d_donors.p, donors_or_null, log_len));
     }
     TrackBufs rec, out;                                                  // per-env records of a round (slot = env); the results
-    PPO_TRY(rec.alloc(N, N, V, M, false, false));
-    PPO_TRY(out.alloc(1, Mst, V, M, false, false));
+    PPO_TRY(rec.alloc(N, N, V, M, false, false, path_or_null != nullptr));
+    PPO_TRY(out.alloc(1, Mst, V, M, false, false, path_or_null != nullptr));
     for (int64_t base = 0; base < Mst; base += S) {
         const int64_t Sr = std::min(S, Mst - base);
         HIP_TRY(hipMemsetAsync(rec.tv.ep_count, 0, (size_t)N * 4, g_stream));
@@ -1158,7 +1205,7 @@ int32_t ppo_search_resample_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts
             const int64_t played = t + 1;                                // loop steps since the round's load
             if (played % interval != 0 || played >= M) return PPO_OK;
             PPO_TRY(launch_search_resample(env, rec.tv, Sr, K, survivors, first, out.tv, d_clone.p, base,
-                                           want_log ? d_donors.p : nullptr, E, played / interval - 1, nullptr));
+                                           want_log ? d_donors.p : nullptr, E, played / interval - 1, nullptr, played));
             first = 0;
             return PPO_OK;
         };
@@ -1166,7 +1213,7 @@ int32_t ppo_search_resample_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts
         PPO_TRY(play_quotas(pol, env, scratch, M, nullptr, &rec.tv, &all, &event));
         ARG_CHECK(all, "search_resample_states: the trajectories did not finish within max_actions steps");
         PPO_TRY(launch_search_resample(env, rec.tv, Sr, K, survivors, first | 2, out.tv, d_clone.p, base, nullptr, E, 0,
-                                       clone_gaps_or_null ? d_gaps.p : nullptr));
+                                       clone_gaps_or_null ? d_gaps.p : nullptr, 0));
     }
     scratch->T = 0; scratch->len = 0; scratch->adv_T = -1; scratch->values_T = -1; scratch->boot_T = -1;
     const size_t Ms = (size_t)Mst;
@@ -1175,7 +1222,72 @@ int32_t ppo_search_resample_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts
     PPO_TRY(d2h(initial_gap, out.tv.initial_gap, Ms)); PPO_TRY(d2h(best_clone, d_clone.p, Ms));
     if (clone_gaps_or_null) PPO_TRY(d2h(clone_gaps_or_null, d_gaps.p, Ms * (size_t)K));
     if (want_log) PPO_TRY(d2h(donors_or_null, d_donors.p, log_len));
+    if (path_or_null) PPO_TRY(d2h(path_or_null, out.acts.p, Ms * (size_t)M));
     return ppo_env_check_errors(env, nullptr);
+}
+
+int32_t ppo_search_resample_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
+                                   const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
+                                   uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
+                                   int32_t* initial_gap, int32_t* clone_gaps_or_null, int64_t interval, int64_t survivors,
+                                   int32_t* donors_or_null) {
+    return search_resample_states_impl(pol, env, scratch, num_starts, K, score, degree, active, best_state, best_active,
+                                       best_gap, best_clone, best_step, initial_gap, clone_gaps_or_null, interval, survivors,
+                                       donors_or_null, nullptr);
+}
+
+// ... with the path to every start's result.  The action history belongs to the lineage: a copy carries the
+// donor's played prefix with its record, and every fold that takes a winner's record takes the first best_step entries of
+// that winner's history with it -- before the event's copies can overwrite them
+int32_t ppo_search_resample_states_path(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
+                                        const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
+                                        uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
+                                        int32_t* initial_gap, int32_t* clone_gaps_or_null, int64_t interval, int64_t survivors,
+                                        int32_t* donors_or_null, int16_t* path) {
+    ARG_CHECK(path, "search_resample_states_path: null argument");
+    return search_resample_states_impl(pol, env, scratch, num_starts, K, score, degree, active, best_state, best_active,
+                                       best_gap, best_clone, best_step, initial_gap, clone_gaps_or_null, interval, survivors,
+                                       donors_or_null, path);
+}
+
+// Teacher-forced replay of action paths on caller-supplied states, without a policy: what checks a returned
+// path on the device.  The env handle supplies Q, max_actions and no_action_reward only: the resident envs, their ticks,
+// episode counters and error flag are untouched.  Everything is validated on the host before anything is uploaded
+int32_t ppo_env_apply_paths(ppo_env_t env, int64_t M, const int8_t* score, const int8_t* degree, const uint32_t* active,
+                            const int16_t* paths, int64_t stride, int8_t* out_state, uint32_t* out_active, int32_t* out_gap,
+                            int32_t* applied, int32_t* trace_or_null) {
+    ARG_CHECK(env && score && degree && active && paths && out_state && out_active && out_gap && applied,
+              "env_apply_paths: null argument");
+    ARG_CHECK(M >= 1, "env_apply_paths: need at least one path");
+    ARG_CHECK(stride >= 1 && stride <= INT32_MAX, "env_apply_paths: stride must be >= 1");
+    PPO_TRY(check_internal_host(env->Q, M, score, degree, active));
+    const int32_t V = env->V, A = 16 * env->Q;
+    const size_t Ms = (size_t)M, cells = Ms * (size_t)stride;
+    for (size_t i = 0; i < cells; ++i) ARG_CHECK(paths[i] < A, "env_apply_paths: action index out of range");
+    std::vector<int8_t> snap(Ms * 2 * V);                                // k_env_snapshot's layout: score[V] then degree[V]
+    for (size_t m = 0; m < Ms; ++m) {
+        std::memcpy(&snap[m * 2 * V], score + m * V, (size_t)V);
+        std::memcpy(&snap[m * 2 * V + V], degree + m * V, (size_t)V);
+    }
+    DevBuf<int8_t> d_start, d_state; DevBuf<uint32_t> d_act, d_oact; DevBuf<int16_t> d_paths; DevBuf<int32_t> d_ints, d_trace;
+    PPO_TRY(d_start.alloc(snap.size())); PPO_TRY(d_state.alloc(snap.size())); PPO_TRY(d_act.alloc(Ms)); PPO_TRY(d_oact.alloc(Ms));
+    PPO_TRY(d_paths.alloc(cells)); PPO_TRY(d_ints.alloc(6 * Ms + 1));     // gap, applied, work [4][M], the flag word
+    if (trace_or_null) PPO_TRY(d_trace.alloc(cells));
+    PPO_TRY(h2d(d_start.p, snap.data(), snap.size())); PPO_TRY(h2d(d_act.p, active, Ms)); PPO_TRY(h2d(d_paths.p, paths, cells));
+    HIP_TRY(hipMemsetAsync(d_ints.p, 0, (6 * Ms + 1) * 4, g_stream));
+    int32_t* d_err = d_ints.p + 6 * Ms;
+    PPO_TRY(launch_env_apply_paths(env, M, d_start.p, d_act.p, d_paths.p, (int32_t)stride, d_state.p, d_oact.p, d_ints.p,
+                                   d_ints.p + Ms, trace_or_null ? d_trace.p : nullptr, d_ints.p + 2 * Ms, d_err));
+    PPO_TRY(d2h(out_state, d_state.p, snap.size())); PPO_TRY(d2h(out_active, d_oact.p, Ms));
+    PPO_TRY(d2h(out_gap, d_ints.p, Ms)); PPO_TRY(d2h(applied, d_ints.p + Ms, Ms));
+    if (trace_or_null) PPO_TRY(d2h(trace_or_null, d_trace.p, cells));
+    int32_t f = 0;
+    PPO_TRY(d2h(&f, d_err, 1));
+    if (f) {
+        ppo_set_error("AssertionError (device flag): env_apply_paths: a path holds an action on an inactive quad");
+        return PPO_ERR_DEVICE_FLAG;
+    }
+    return PPO_OK;
 }
 
 #define RO_GETTER(name, member, type, per)                                                     \

@@ -3,6 +3,7 @@
 // QuadMeshGame's dynamics are not in the reference tree, so this is an honest synthetic stand-in
 // with exactly specified integer dynamics (DESIGN.md "Synthetic env"): SoA state in HBM, one
 // thread per env for the integer update, one thread per output dword for the observation.
+#include <algorithm>
 #include "ppo_env_device.h"
 
 struct EnvView {
@@ -118,7 +119,8 @@ __global__ void k_env_step(EnvView e, const int32_t* __restrict__ actions, float
 // keeps a copy of the wrapper behind every step and returns the one at argmin(current_score - opt_score); here the env's
 // thread keeps the best state so far in the trajectory's output slot and replaces it only on a STRICTLY lower gap (argmin
 // returns the first minimum; the start state is candidate 0).  Also single_trajectory_scores (:309-323: initial_score -
-// current_score behind every step) and the action types count_non_flips counts (test/random_quad.jl:9-27).  Same idle
+// current_score behind every step), the action types count_non_flips counts (test/random_quad.jl:9-27) and, optionally, the
+// action history: the action played at step t in entry t - 1 of the slot's row.  Same idle
 // branch, env_step_ref call, outputs and reset-on-done as k_env_step's episodes mode; the snapshot copies are dword copies
 // (V % 4 == 0, rows start dword aligned).
 __global__ void k_env_step_track(EnvView e, const int32_t* __restrict__ actions, float* __restrict__ reward_out,
@@ -169,6 +171,7 @@ __global__ void k_env_step_track(EnvView e, const int32_t* __restrict__ actions,
     }
     if (tv.trace && t <= e.max_actions) tv.trace[slot * e.max_actions + (t - 1)] = tv.ep_init[n] - score_after;
     if (tv.type_counts) tv.type_counts[slot * 4 + ((a < 0 || a >= 16 * e.Q) ? 0 : (a & 3))] += 1;
+    if (tv.actions && t <= e.max_actions) tv.actions[slot * e.max_actions + (t - 1)] = (int16_t)a;   // the action history
     if (dn) {
         tv.length[slot] = t;
         tv.ep_count[n] += 1;
@@ -206,10 +209,11 @@ __global__ void k_env_load_starts(EnvView e, const uint32_t* __restrict__ start_
 // best-of-K search, reduction: one workgroup per start.  Threads stride over the K clones (envs s*K ..) holding
 // min(gap << 32 | clone) -- a gap is sum|s| - |sum s| >= 0, so the unsigned order is the order of (gap, clone) and ties go to
 // the lowest clone -- then a wave reduction by shuffles, one LDS exchange across the four waves, and the whole workgroup
-// copies the winner's record
+// copies the winner's record -- and, where out.actions is set, the path to it: the first best_step entries of the winner's
+// action history (tv.actions, rows of M = max_actions entries), -1 behind them
 __global__ __launch_bounds__(256) void k_search_argmin(TrackView tv, int V, int64_t K, TrackView out,
                                                        int32_t* __restrict__ best_clone, int32_t* __restrict__ clone_gaps,
-                                                       int64_t out_base) {
+                                                       int64_t out_base, int M) {
     __shared__ unsigned long long wave_min[4];
     const int tid = threadIdx.x;
     const int64_t s = blockIdx.x, o = out_base + s;
@@ -235,6 +239,12 @@ __global__ __launch_bounds__(256) void k_search_argmin(TrackView tv, int V, int6
     const uint32_t* src = reinterpret_cast<const uint32_t*>(tv.best_state + env * 2 * V);
     uint32_t* dst = reinterpret_cast<uint32_t*>(out.best_state + o * 2 * V);
     for (int d = tid; d < V / 2; d += 256) dst[d] = src[d];
+    if (out.actions) {
+        const int len = tv.best_step[env];
+        const int16_t* hist = tv.actions + env * M;
+        int16_t* path = out.actions + o * M;
+        for (int i = tid; i < M; i += 256) path[i] = i < len ? hist[i] : (int16_t)-1;
+    }
     if (tid == 0) {
         out.best_active[o] = tv.best_active[env]; out.best_gap[o] = tv.best_gap[env]; out.best_step[o] = tv.best_step[env];
         out.initial_gap[o] = tv.initial_gap[env]; best_clone[o] = (int32_t)clone;
@@ -252,11 +262,17 @@ __global__ __launch_bounds__(256) void k_search_argmin(TrackView tv, int V, int6
 //          per clone, score / degree / best_state as dwords across the workgroup.  Donors are never receivers: in place.
 // Dynamic LDS, 48 + 12 * Kp bytes (Kp = K rounded up to 8): wave_min [4], live count, keys [Kp], by_rank [Kp], rank_of [Kp];
 // every carve offset is a multiple of 16.
+// PATH: the action history (tv.actions, rows of M = max_actions entries) belongs to the lineage.  A fold that
+// takes the winner's record also writes the first best_step entries of the winner's history to the start's output path
+// (out.actions) and -1 behind them -- read, like the snapshot, before the barrier that releases the copies, since the winner
+// may be a receiver of this event.  A copy takes the donor's entries 0 .. t_in - 1 with its t_in (at most `played`, the loop
+// steps of the round so far).  PATH = false compiles to the event without any of it.
 extern __shared__ __attribute__((aligned(16))) unsigned char resample_lds[];
+template <bool PATH>
 __global__ __launch_bounds__(256) void k_search_resample(EnvView e, TrackView tv, int K, int survivors, int flags,
                                                          TrackView out, int32_t* __restrict__ best_clone, int64_t out_base,
                                                          int32_t* __restrict__ donors, int64_t E, int64_t event,
-                                                         int32_t* __restrict__ clone_gaps) {
+                                                         int32_t* __restrict__ clone_gaps, int M, int played) {
     unsigned long long* wave_min = reinterpret_cast<unsigned long long*>(resample_lds);
     int* live_count = reinterpret_cast<int*>(resample_lds + 32);
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(resample_lds + 48);
@@ -291,6 +307,12 @@ __global__ __launch_bounds__(256) void k_search_resample(EnvView e, TrackView tv
         const uint32_t* src = reinterpret_cast<const uint32_t*>(tv.best_state + wenv * 2 * V);
         uint32_t* dst = reinterpret_cast<uint32_t*>(out.best_state + o * 2 * V);
         for (int d = tid; d < 2 * dv; d += 256) dst[d] = src[d];
+        if (PATH) {
+            const int len = tv.best_step[wenv];
+            const int16_t* hist = tv.actions + wenv * M;
+            int16_t* path = out.actions + o * M;
+            for (int i = tid; i < M; i += 256) path[i] = i < len ? hist[i] : (int16_t)-1;
+        }
         if (tid == 0) {
             out.best_active[o] = tv.best_active[wenv]; out.best_gap[o] = tv.best_gap[wenv];
             out.best_step[o] = tv.best_step[wenv]; out.initial_gap[o] = tv.initial_gap[wenv];
@@ -346,6 +368,58 @@ __global__ __launch_bounds__(256) void k_search_resample(EnvView e, TrackView tv
         else if (d < 2 * dv) reinterpret_cast<uint32_t*>(e.degree + n * V)[d - dv] = reinterpret_cast<const uint32_t*>(e.degree + dn * V)[d - dv];
         else reinterpret_cast<uint32_t*>(tv.best_state + n * 2 * V)[d - 2 * dv] = reinterpret_cast<const uint32_t*>(tv.best_state + dn * 2 * V)[d - 2 * dv];
     }
+    if (PATH) {                                   // the donor's played prefix: t_in[donor] <= played <= M entries per receiver
+        const int P = played < M ? played : M;    // 0 (the last fold passes it, and returns above): no entry, no i / P
+        for (int i = tid; P > 0 && i < K * P; i += 256) {
+            const int c = i / P, d = i - c * P;
+            const int r = rank_of[c];
+            if (r == 0xFFFF || r < m) continue;
+            const int64_t n = env0 + c, dn = env0 + by_rank[(r - m) % m];
+            if (d < tv.t_in[dn]) tv.actions[n * M + d] = tv.actions[dn * M + d];
+        }
+    }
+}
+
+// Teacher-forced replay of action paths: one thread per path, no policy, no resident env.  Path m starts
+// from snapshot m (score[V] then degree[V], k_env_snapshot's layout) as reset! leaves an env -- steps 0, not terminal -- and
+// plays paths[m][0 ..] with env_step_ref until an entry < 0, `stride` entries, or a terminal state.  The thread's env IS
+// its output record (out_state row m, out_active[m]); steps / reward / done / tick live in `work` [4][count] and are
+// thrown away.  trace (optional): initial score - score behind every step, INT32_MIN behind `applied`.  Error flags of
+// env_step_ref (an action on an inactive quad) are OR-ed into *err, a word of the call, not of the env handle.
+__global__ void k_env_apply_paths(EnvConst c, int64_t count, const uint32_t* __restrict__ start_state,
+                                  const uint32_t* __restrict__ start_active, const int16_t* __restrict__ paths, int stride,
+                                  int8_t* __restrict__ out_state, uint32_t* __restrict__ out_active, int32_t* __restrict__ out_gap,
+                                  int32_t* __restrict__ applied, int32_t* __restrict__ trace, int32_t* __restrict__ work,
+                                  int32_t* __restrict__ err) {
+    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= count) return;
+    const int dv = c.V / 4;
+    uint32_t* st = reinterpret_cast<uint32_t*>(out_state + m * 2 * c.V);
+    for (int d = 0; d < 2 * dv; ++d) st[d] = start_state[m * 2 * dv + d];
+    EnvRef er;
+    er.sc = out_state + m * 2 * c.V; er.dg = er.sc + c.V; er.active = out_active + m;
+    er.steps = work + m; er.reward = reinterpret_cast<float*>(work + count + m);
+    er.tick = reinterpret_cast<uint32_t*>(work + 2 * count + m);
+    er.done = reinterpret_cast<uint8_t*>(work + 3 * count) + m;
+    er.episode = er.tick;                         // step! never reads the episode counter
+    *er.active = start_active[m]; *er.steps = 0; *er.reward = 0.0f; *er.tick = 0u; *er.done = 0;
+    const int init = env_total_abs(er.sc, *er.active, c.Q);
+    int n = 0;
+    while (n < stride && !*er.done) {
+        const int a = paths[m * stride + n];
+        if (a < 0) break;
+        float rew; uint8_t dn;
+        int score_after = 0;
+        const int errf = env_step_ref(c, er, a, rew, dn, &score_after);
+        if (errf) atomicOr(err, errf);
+        if (trace) trace[m * stride + n] = init - score_after;
+        ++n;
+    }
+    if (trace) for (int i = n; i < stride; ++i) trace[m * stride + i] = INT32_MIN;
+    const uint32_t act = *er.active;
+    const int cur = env_total_abs(er.sc, act, c.Q), sum = env_total_sum(er.sc, act, c.Q);
+    out_gap[m] = cur - (sum < 0 ? -sum : sum);
+    applied[m] = n;
 }
 
 // state(env): obs[n][h][f] int8, f<36 template scores, f>=36 template degrees, 0 where the
@@ -473,24 +547,55 @@ int32_t launch_env_load_starts(ppo_env_s* e, const int8_t* start_state, const ui
 }
 
 int32_t launch_search_argmin(const TrackView& tv, int32_t V, int64_t S, int64_t K, const TrackView& out, int32_t* best_clone,
-                             int32_t* clone_gaps, int64_t out_base) {
+                             int32_t* clone_gaps, int64_t out_base, int32_t max_actions) {
+    if (out.actions && !tv.actions) {
+        ppo_set_error("search_argmin: a path is asked for and no action history was kept");
+        return PPO_ERR_ARG;
+    }
     hipLaunchKernelGGL(k_search_argmin, dim3((unsigned)S), dim3(256), 0, ppo_stream(), tv, (int)V, K, out, best_clone,
-                       clone_gaps, out_base);
+                       clone_gaps, out_base, (int)max_actions);
     HIP_TRY(hipGetLastError());
     return PPO_OK;
 }
 
 int32_t launch_search_resample(ppo_env_s* e, const TrackView& tv, int64_t S, int64_t K, int64_t survivors, int flags,
                                const TrackView& out, int32_t* best_clone, int64_t out_base, int32_t* donors, int64_t E,
-                               int64_t event, int32_t* clone_gaps) {
+                               int64_t event, int32_t* clone_gaps, int64_t played) {
     if (K < 1 || K > PPO_RESAMPLE_MAX_K || S < 1 || S * K > e->N || e->V % 4 != 0) {
         ppo_set_error("search_resample: unsupported shape");
         return PPO_ERR_UNSUPPORTED;
     }
+    const bool path = out.actions != nullptr;
+    if (path && (!tv.actions || played < 0)) {
+        ppo_set_error("search_resample: a path is asked for and no action history was kept");
+        return PPO_ERR_ARG;
+    }
     ProfScope ps((flags & 2) ? "k_search_fold" : "k_search_resample");
     const size_t lds = 48 + 12 * (size_t)((K + 7) & ~(int64_t)7);
-    hipLaunchKernelGGL(k_search_resample, dim3((unsigned)S), dim3(256), lds, ppo_stream(), view_of(e), tv, (int)K,
-                       (int)survivors, flags, out, best_clone, out_base, donors, E, event, clone_gaps);
+    const int M = e->max_actions, P = (int)std::min<int64_t>(played, M);
+    if (path)
+        hipLaunchKernelGGL(k_search_resample<true>, dim3((unsigned)S), dim3(256), lds, ppo_stream(), view_of(e), tv, (int)K,
+                           (int)survivors, flags, out, best_clone, out_base, donors, E, event, clone_gaps, M, P);
+    else
+        hipLaunchKernelGGL(k_search_resample<false>, dim3((unsigned)S), dim3(256), lds, ppo_stream(), view_of(e), tv, (int)K,
+                           (int)survivors, flags, out, best_clone, out_base, donors, E, event, clone_gaps, M, P);
+    HIP_TRY(hipGetLastError());
+    return PPO_OK;
+}
+
+int32_t launch_env_apply_paths(ppo_env_s* e, int64_t count, const int8_t* start_state, const uint32_t* start_active,
+                               const int16_t* paths, int32_t stride, int8_t* out_state, uint32_t* out_active, int32_t* out_gap,
+                               int32_t* applied, int32_t* trace_or_null, int32_t* work, int32_t* err) {
+    if (count <= 0) return PPO_OK;
+    if (stride < 1 || e->V % 4 != 0) {
+        ppo_set_error("env_apply_paths: unsupported shape");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    EnvConst c;
+    c.Q = e->Q; c.V = e->V; c.max_actions = e->max_actions; c.no_action_reward = e->no_action_reward; c.k0 = 0; c.k1 = 0;
+    hipLaunchKernelGGL(k_env_apply_paths, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, ppo_stream(), c, count,
+                       reinterpret_cast<const uint32_t*>(start_state), start_active, paths, (int)stride, out_state, out_active,
+                       out_gap, applied, trace_or_null, work, err);
     HIP_TRY(hipGetLastError());
     return PPO_OK;
 }

@@ -306,6 +306,9 @@ struct TrackView {
     int32_t* initial_gap = nullptr;    // [num_traj]
     int32_t* trace = nullptr;      // [num_traj][max_actions] initial score - score behind step t, optional
     int32_t* type_counts = nullptr;    // [num_traj][4] actions played by type a % 4, optional (zeroed by the caller)
+    int16_t* actions = nullptr;    // [num_traj][max_actions] the 0-based action played at step t in entry t - 1, optional (an
+                                   // action index is below 16 Q <= 512).  In a record of results (`out` of the searches): the
+                                   // path to the best state, best_step entries and -1 behind them
     int64_t num_traj = 0;          // slots, env-major like EvalView::out
 };
 int32_t launch_env_step_track(ppo_env_s* e, const int32_t* actions_dev, float* reward_out, uint8_t* done_out,
@@ -315,19 +318,29 @@ int32_t launch_env_step_track(ppo_env_s* e, const int32_t* actions_dev, float* r
 int32_t launch_env_load_starts(ppo_env_s* e, const int8_t* start_state, const uint32_t* start_active, int64_t busy, int64_t K,
                                int32_t* t_in);
 // ... and its reduction: winner of the K clones of each of S starts (lowest gap, then lowest clone) from the per-env
-// records of `tv` (slot = env) into record out_base + s of `out`; clone_gaps (optional): [..][K] every clone's best gap
+// records of `tv` (slot = env) into record out_base + s of `out`; clone_gaps (optional): [..][K] every clone's best gap.
+// out.actions set (tv.actions then too): the winner's first best_step actions to row out_base + s, -1 behind them
 int32_t launch_search_argmin(const TrackView& tv, int32_t V, int64_t S, int64_t K, const TrackView& out, int32_t* best_clone,
-                             int32_t* clone_gaps, int64_t out_base);
+                             int32_t* clone_gaps, int64_t out_base, int32_t max_actions);
 // resampling search, one launch for the S starts of a round: fold the K per-env records of every start into
 // record out_base + s of `out` (flags & 1: the round's first fold takes the winner as it is, later ones only a strictly
 // lower gap), then -- unless flags & 2, the fold behind a round's last step -- rank the live clones by (cur_gap, clone) and
 // overwrite every clone of rank >= m = min(survivors, live) with state, record and t_in of the clone of rank (rank - m) % m.
 // donors (optional): [..][E][K] log, row `event`; clone_gaps (optional): [..][K] every clone's record gap.  K above
-// PPO_RESAMPLE_MAX_K (the keys are staged in LDS): PPO_ERR_UNSUPPORTED
+// PPO_RESAMPLE_MAX_K (the keys are staged in LDS): PPO_ERR_UNSUPPORTED.
+// out.actions set (tv.actions then too): the action history travels with the record -- a fold that takes a
+// winner's record writes the first best_step entries of its history to row out_base + s of out.actions and -1 behind them,
+// a copy takes the donor's entries 0 .. t_in - 1.  played: loop steps of the round so far (an upper bound of every t_in)
 constexpr int64_t PPO_RESAMPLE_MAX_K = 4096;
 int32_t launch_search_resample(ppo_env_s* e, const TrackView& tv, int64_t S, int64_t K, int64_t survivors, int flags,
                                const TrackView& out, int32_t* best_clone, int64_t out_base, int32_t* donors, int64_t E,
-                               int64_t event, int32_t* clone_gaps);
+                               int64_t event, int32_t* clone_gaps, int64_t played);
+// teacher-forced replay: path m ([count][stride] 0-based actions, < 0 ends a path) from snapshot m (score[V]
+// then degree[V]) as reset! leaves an env, until the path ends or the state is terminal; out_state / out_active / out_gap /
+// applied per path, trace (optional) [count][stride].  work: [4][count] int32 scratch; err: one word, OR of the step's flags
+int32_t launch_env_apply_paths(ppo_env_s* e, int64_t count, const int8_t* start_state, const uint32_t* start_active,
+                               const int16_t* paths, int32_t stride, int8_t* out_state, uint32_t* out_active, int32_t* out_gap,
+                               int32_t* applied, int32_t* trace_or_null, int32_t* work, int32_t* err);
 int32_t launch_env_observe(ppo_env_s* e, int8_t* obs_out, uint32_t* active_out);
 // compact rollout storage: env snapshot of every env (score[V] then degree[V]) -> cstate_out [N][2V]
 int32_t launch_env_snapshot(ppo_env_s* e, int8_t* cstate_out);
