@@ -622,6 +622,23 @@ int32_t ppo_search_resample_states_path(ppo_policy_t pol, ppo_env_t env, ppo_rol
                                         uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
                                         int32_t* initial_gap, int32_t* clone_gaps_or_null, int64_t interval, int64_t survivors,
                                         int32_t* donors_or_null, int16_t* path);
+/* ppo_search_resample_states ranking by the critic's value.  `critic` is a ppo_policy_t read as a state value
+ * (ppo_value_forward).  The env's reward is old_total - new_total, so a trained critic estimates the score reduction still to
+ * come and cur_gap - V(s) where a clone will end.  In front of every event the envs are observed and the critic's forward
+ * runs on the device; a live clone then ranks by the fp32 number
+ *     s = fmaf(-(float)value_weight, v, (float)cur_gap),   v = V(state the clone holds behind the step), 0 if not finite,
+ * ascending, -0.0 before +0.0, ties to the lower clone.  Everything else -- the fold (by the record's real best_gap), terminal
+ * clones, m = min(survivors, live), the donor of rank r being rank (r - m) % m, the copy, the path -- is the plain call's;
+ * value_weight = 0 is the plain call.  event_values (optional) [num_starts][E][K] float: the raw v a live clone was ranked
+ * with, NaN for a terminal clone and for every clone of an event that did not run.  path may be null.  PPO_ERR_UNSUPPORTED:
+ * a bf16-dtype critic, a critic whose input width is not the env's F; PPO_ERR_ARG: value_weight negative, not finite or
+ * above FLT_MAX. */
+int32_t ppo_search_resample_states_value(ppo_policy_t pol, ppo_policy_t critic, ppo_env_t env, ppo_rollouts_t scratch,
+                                         int64_t num_starts, int64_t K, const int8_t* score, const int8_t* degree,
+                                         const uint32_t* active, int8_t* best_state, uint32_t* best_active, int32_t* best_gap,
+                                         int32_t* best_clone, int32_t* best_step, int32_t* initial_gap,
+                                         int32_t* clone_gaps_or_null, int64_t interval, int64_t survivors, double value_weight,
+                                         int32_t* donors_or_null, float* event_values_or_null, int16_t* path_or_null);
 /* Teacher-forced replay without a policy: path m of paths [M][stride] (0-based actions; an entry < 0 ends a path) is
  * applied to start m (score, degree [M][V], active [M], checked like ppo_env_set_internal), which begins as reset! leaves an
  * env (steps = 0, not terminal).  A path ends at its first entry < 0, after stride entries, or once the state is terminal

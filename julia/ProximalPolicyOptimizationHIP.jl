@@ -392,6 +392,29 @@ function search_resample_states_path(env::HipVecEnv, p::HipPolicy, score::Matrix
     (best_state = st, best_active = act, best_gap = gap, best_clone = clone, best_step = step, initial_gap = init,
      clone_gaps = gaps, donors = donors, path = path .+ Int16(1))
 end
+# ... ranking the live clones by where the critic (a HipPolicy with 4 outputs read as a state value) expects them to end: by
+# fma(-Float32(value_weight), V(s), Float32(current gap)) instead of the current gap; a V(s) that is not finite counts as 0.
+# event_values[:, e, i]: the V(s) every live clone of start i was ranked with at event e, NaN for a terminal clone / no event
+function search_resample_states_value(env::HipVecEnv, p::HipPolicy, critic::HipPolicy, score::Matrix{Int8}, degree::Matrix{Int8},
+                                      active::Vector{UInt32}, K, interval, survivors; value_weight = 1.0)
+    scratch = HipRollouts()
+    h = ensure!(scratch, env, 1)
+    M, V = length(active), 4 * env.Q
+    st, act = zeros(Int8, 2V, M), zeros(UInt32, M)
+    gap, clone, step, init = zeros(Int32, M), zeros(Int32, M), zeros(Int32, M), zeros(Int32, M)
+    gaps = zeros(Int32, Int(K), M)
+    donors = fill(Int32(-2), Int(K), div(env.max_actions - 1, Int(interval)), M)
+    event_values = fill(NaN32, Int(K), div(env.max_actions - 1, Int(interval)), M)
+    path = zeros(Int16, env.max_actions, M)
+    check(ccall((:ppo_search_resample_states_value, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Int8}, Ptr{Int8}, Ptr{UInt32}, Ptr{Int8},
+                 Ptr{UInt32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Int64, Int64, Float64, Ptr{Int32},
+                 Ptr{Float32}, Ptr{Cvoid}),
+                p.h, critic.h, env.h, h, M, Int64(K), score, degree, active, st, act, gap, clone, step, init, gaps,
+                Int64(interval), Int64(survivors), Float64(value_weight), donors, event_values, path))
+    (best_state = st, best_active = act, best_gap = gap, best_clone = clone, best_step = step, initial_gap = init,
+     clone_gaps = gaps, donors = donors, event_values = event_values, path = path .+ Int16(1))
+end
 # teacher-forced replay without a policy: paths [stride, M] column-major == [M][stride], 1-based, anything <= 0 ends a path;
 # start i (score, degree [V, M], active [M]) begins as reset! leaves an env.  env supplies Q, max_actions and no_action_reward
 # only.  apply_paths(env, starts..., r.path) of a search result r gives r.best_state, r.best_active, r.best_gap, applied == r.best_step

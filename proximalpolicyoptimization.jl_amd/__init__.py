@@ -1758,7 +1758,7 @@ def check_resample(N, K, interval, survivors):
 
 
 def search_resample_states_(env, policy, score, degree, active, K, interval, survivors, donors=False, clone_gaps=False,
-                            path=False):
+                            path=False, critic=None, value_weight=1.0, values=False):
     """search_best_states_ with resampling: behind every `interval`-th step of a round (t % interval == 0, t < max_actions)
     each start folds its K clones' records into its result (the lowest (best_gap, clone); the first fold as it is, later
     ones only on a strictly lower gap), ranks its live clones by (current_score - opt_score now, clone) and overwrites
@@ -1769,9 +1769,19 @@ def search_resample_states_(env, policy, score, degree, active, K, interval, sur
     a terminal clone or an event that no longer ran; clone_gaps=True adds every clone's record gap at the last fold.
     interval >= max_actions runs no event (search_best_states_); survivors == K copies nothing.  path=True adds path
     [M, max_actions] int16: the best_step 1-based actions that lead from the start to best_state along the result's lineage
-    (a copy carries the donor's actions with its record), 0 behind them.  HipVecEnv only."""
+    (a copy carries the donor's actions with its record), 0 behind them.  HipVecEnv only.
+    critic (a HipCritic): the live clones rank by where the critic expects them to end instead of where they
+    are -- by the fp32 number fmaf(-value_weight, V(s), cur_gap), V(s) the critic's value of the state the clone holds behind
+    the step (0 where it is not finite), computed on the device in front of every event.  The fold, the ranks and the copy
+    stay as they are; value_weight = 0 is the call without a critic.  values=True (needs a critic) adds event_values
+    [M, E, K] float32: the V(s) every live clone was ranked with, NaN for a terminal clone or an event that no longer ran.
+    value_weight must be finite and >= 0.  Without a critic the call is the one it has always been."""
     if not isinstance(env, HipVecEnv):
         raise PPOError(-4, "search_resample_states_ needs a HipVecEnv")
+    if critic is None and values:
+        raise PPOError(-1, "AssertionError: search_resample_states: values=True needs a critic")
+    if critic is not None and not (np.isfinite(np.float32(value_weight)) and float(value_weight) >= 0.0):
+        raise PPOError(-1, "AssertionError: search_resample_states: value_weight must be finite and >= 0")
     sc, dg, act = check_internal(score, degree, active, env.Q)
     M, V = sc.shape[0], 4 * env.Q
     K, R, m0 = check_resample(env.N, K, interval, survivors)
@@ -1780,15 +1790,19 @@ def search_resample_states_(env, policy, score, degree, active, K, interval, sur
     gap, clone, step, init = (np.zeros(M, np.int32) for _ in range(4))
     cg = np.zeros((M, K), np.int32) if clone_gaps else None
     dn = np.full((M, (env.max_actions - 1) // R, K), -2, np.int32) if donors else None
-    args = (policy._h, env._h, h, M, K, _p(sc, _lib.c_i8p), _p(dg, _lib.c_i8p),
+    ev = np.full((M, (env.max_actions - 1) // R, K), np.nan, np.float32) if values else None
+    pa = np.zeros((M, env.max_actions), np.int16) if path else None
+    args = (env._h, h, M, K, _p(sc, _lib.c_i8p), _p(dg, _lib.c_i8p),
             _p(act, _lib.c_u32p), _p(st, _lib.c_i8p), _p(bact, _lib.c_u32p), _p(gap, _lib.c_i32p), _p(clone, _lib.c_i32p),
-            _p(step, _lib.c_i32p), _p(init, _lib.c_i32p), None if cg is None else _p(cg, _lib.c_i32p), R, m0,
-            None if dn is None else _p(dn, _lib.c_i32p))
-    if path:
-        pa = np.zeros((M, env.max_actions), np.int16)
-        call("ppo_search_resample_states_path", *args, _p(pa, _lib.c_i16p))
+            _p(step, _lib.c_i32p), _p(init, _lib.c_i32p), None if cg is None else _p(cg, _lib.c_i32p), R, m0)
+    dnp = None if dn is None else _p(dn, _lib.c_i32p)
+    if critic is not None:
+        call("ppo_search_resample_states_value", policy._h, critic._h, *args, float(value_weight), dnp,
+             None if ev is None else _p(ev, _lib.c_f32p), None if pa is None else _p(pa, _lib.c_i16p))
+    elif path:
+        call("ppo_search_resample_states_path", policy._h, *args, dnp, _p(pa, _lib.c_i16p))
     else:
-        call("ppo_search_resample_states", *args)
+        call("ppo_search_resample_states", policy._h, *args, dnp)
     out = dict(best_state=st, best_score=st[:, :V], best_degree=st[:, V:], best_active=bact, best_gap=gap, best_clone=clone,
                best_step=step, initial_gap=init)
     if donors:
@@ -1797,6 +1811,8 @@ def search_resample_states_(env, policy, score, degree, active, K, interval, sur
         out["clone_gaps"] = cg
     if path:
         out["path"] = _paths_out(pa)
+    if values:
+        out["event_values"] = ev
     return out
 
 

@@ -60,6 +60,8 @@ SIGNATURES = {
                                     c_i32p, c_i32p, c_i16p],
     "ppo_search_resample_states_path": [H, H, H, C.c_int64, C.c_int64, c_i8p, c_i8p, c_u32p, c_i8p, c_u32p, c_i32p, c_i32p,
                                         c_i32p, c_i32p, c_i32p, C.c_int64, C.c_int64, c_i32p, c_i16p],
+    "ppo_search_resample_states_value": [H, H, H, H, C.c_int64, C.c_int64, c_i8p, c_i8p, c_u32p, c_i8p, c_u32p, c_i32p, c_i32p,
+                                         c_i32p, c_i32p, c_i32p, C.c_int64, C.c_int64, C.c_double, c_i32p, c_f32p, c_i16p],
     "ppo_env_apply_paths": [H, C.c_int64, c_i8p, c_i8p, c_u32p, c_i16p, C.c_int64, c_i8p, c_u32p, c_i32p, c_i32p, c_i32p],
     "ppo_set_rollout_persistent": [C.c_int32],
     "ppo_set_rollout_compact": [C.c_int32],

@@ -1156,12 +1156,17 @@ int32_t ppo_search_best_states_path(ppo_policy_t pol, ppo_env_t env, ppo_rollout
 // Resampling search: ppo_search_best_states' schedule with a resample event (k_search_resample: fold, rank,
 // copy) behind every interval-th step of a round, and one more fold behind the round's last step.  The events ride in
 // play_quotas' loop, which polls completion every 8 steps as for every other caller: an event costs a launch, no copy.
+// critic (optional): an event ranks the live clones by cur_gap - value_weight * V(state held now) instead of
+// cur_gap.  In front of the event the envs are observed into row 0 of `scratch` (the next loop step overwrites it anyway)
+// and the critic's forward turns the rows into one value per env, all on the device.  The last fold ranks nothing and
+// needs neither.  event_values (optional): [num_starts][E][K] log of the values the events read.
 static int32_t search_resample_states_impl(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts,
                                            int64_t K, const int8_t* score, const int8_t* degree, const uint32_t* active,
                                            int8_t* best_state, uint32_t* best_active, int32_t* best_gap, int32_t* best_clone,
                                            int32_t* best_step, int32_t* initial_gap, int32_t* clone_gaps_or_null,
                                            int64_t interval, int64_t survivors, int32_t* donors_or_null,
-                                           int16_t* path_or_null) {
+                                           int16_t* path_or_null, ppo_policy_t critic = nullptr, double value_weight = 0.0,
+                                           float* event_values_or_null = nullptr) {
     ARG_CHECK(score && degree && active && best_state && best_active && best_gap && best_clone && best_step && initial_gap,
               "search_resample_states: null argument");
     PPO_TRY(check_shapes(scratch, env, pol));
@@ -1169,6 +1174,16 @@ static int32_t search_resample_states_impl(ppo_policy_t pol, ppo_env_t env, ppo_
     ARG_CHECK(Mst >= 1 && K >= 1 && K <= N, "search_resample_states: need num_starts >= 1 and 1 <= K <= N");
     ARG_CHECK(interval >= 1, "search_resample_states: interval must be >= 1");
     ARG_CHECK(survivors >= 1 && survivors <= K, "search_resample_states: need 1 <= survivors <= K");
+    ARG_CHECK(critic || !event_values_or_null, "search_resample_states: a log of values needs a critic");
+    if (critic) {
+        PPO_TRY(value_checks("search_resample_states", critic, env->F));
+        if (env->H != 32 && env->H != 128) {
+            ppo_set_error("search_resample_states: the critic needs H = 32 (Q=8) or 128 (Q=32) half-edges in this build");
+            return PPO_ERR_UNSUPPORTED;
+        }
+        ARG_CHECK(std::isfinite(value_weight) && value_weight >= 0.0 && std::isfinite((float)value_weight),
+                  "search_resample_states: value_weight must be finite and >= 0");
+    }
     PPO_TRY(check_internal_host(env->Q, Mst, score, degree, active));
     if (K > PPO_RESAMPLE_MAX_K) {
         ppo_set_error("search_resample_states: K above 4096 clones is not supported (the rank keys are staged in LDS)");
@@ -1193,6 +1208,14 @@ static int32_t search_resample_states_impl(ppo_policy_t pol, ppo_env_t env, ppo_
         PPO_TRY(d_donors.alloc(log_len));
         PPO_TRY(h2d(d_donors.p, donors_or_null, log_len));
     }
+    DevBuf<float> d_values, d_vlog;                                      // the critic's value of every env; the log of them
+    const bool want_vlog = event_values_or_null && log_len > 0;
+    if (critic) PPO_TRY(d_values.alloc((size_t)N));
+    if (want_vlog) {                                                     // an event that never runs leaves NaN
+        std::fill(event_values_or_null, event_values_or_null + log_len, std::numeric_limits<float>::quiet_NaN());
+        PPO_TRY(d_vlog.alloc(log_len));
+        PPO_TRY(h2d(d_vlog.p, event_values_or_null, log_len));
+    }
     TrackBufs rec, out;                                                  // per-env records of a round (slot = env); the results
     PPO_TRY(rec.alloc(N, N, V, M, false, false, path_or_null != nullptr));
     PPO_TRY(out.alloc(1, Mst, V, M, false, false, path_or_null != nullptr));
@@ -1204,8 +1227,14 @@ static int32_t search_resample_states_impl(ppo_policy_t pol, ppo_env_t env, ppo_
         const std::function<int32_t(int64_t)> event = [&](int64_t t) -> int32_t {
             const int64_t played = t + 1;                                // loop steps since the round's load
             if (played % interval != 0 || played >= M) return PPO_OK;
+            if (critic) {                                                // V of the state every env holds behind the step
+                PPO_TRY(launch_env_observe(env, scratch->states.p, scratch->active.p));
+                PPO_TRY(launch_value_predict(critic, scratch->states.p, nullptr, scratch->active.p, nullptr, 0, N, env->H,
+                                             d_values.p));
+            }
             PPO_TRY(launch_search_resample(env, rec.tv, Sr, K, survivors, first, out.tv, d_clone.p, base,
-                                           want_log ? d_donors.p : nullptr, E, played / interval - 1, nullptr, played));
+                                           want_log ? d_donors.p : nullptr, E, played / interval - 1, nullptr, played,
+                                           critic ? d_values.p : nullptr, want_vlog ? d_vlog.p : nullptr, (float)value_weight));
             first = 0;
             return PPO_OK;
         };
@@ -1222,6 +1251,7 @@ static int32_t search_resample_states_impl(ppo_policy_t pol, ppo_env_t env, ppo_
     PPO_TRY(d2h(initial_gap, out.tv.initial_gap, Ms)); PPO_TRY(d2h(best_clone, d_clone.p, Ms));
     if (clone_gaps_or_null) PPO_TRY(d2h(clone_gaps_or_null, d_gaps.p, Ms * (size_t)K));
     if (want_log) PPO_TRY(d2h(donors_or_null, d_donors.p, log_len));
+    if (want_vlog) PPO_TRY(d2h(event_values_or_null, d_vlog.p, log_len));
     if (path_or_null) PPO_TRY(d2h(path_or_null, out.acts.p, Ms * (size_t)M));
     return ppo_env_check_errors(env, nullptr);
 }
@@ -1248,6 +1278,20 @@ int32_t ppo_search_resample_states_path(ppo_policy_t pol, ppo_env_t env, ppo_rol
     return search_resample_states_impl(pol, env, scratch, num_starts, K, score, degree, active, best_state, best_active,
                                        best_gap, best_clone, best_step, initial_gap, clone_gaps_or_null, interval, survivors,
                                        donors_or_null, path);
+}
+
+// ... ranking a start's live clones by where the critic expects them to end: cur_gap - value_weight * V(s)
+// in place of cur_gap.  The fold, the ranks, the copy and the path are the plain call's
+int32_t ppo_search_resample_states_value(ppo_policy_t pol, ppo_policy_t critic, ppo_env_t env, ppo_rollouts_t scratch,
+                                         int64_t num_starts, int64_t K, const int8_t* score, const int8_t* degree,
+                                         const uint32_t* active, int8_t* best_state, uint32_t* best_active, int32_t* best_gap,
+                                         int32_t* best_clone, int32_t* best_step, int32_t* initial_gap,
+                                         int32_t* clone_gaps_or_null, int64_t interval, int64_t survivors, double value_weight,
+                                         int32_t* donors_or_null, float* event_values_or_null, int16_t* path_or_null) {
+    ARG_CHECK(critic, "search_resample_states_value: null argument");
+    return search_resample_states_impl(pol, env, scratch, num_starts, K, score, degree, active, best_state, best_active,
+                                       best_gap, best_clone, best_step, initial_gap, clone_gaps_or_null, interval, survivors,
+                                       donors_or_null, path_or_null, critic, value_weight, event_values_or_null);
 }
 
 // Teacher-forced replay of action paths on caller-supplied states, without a policy: what checks a returned

@@ -267,12 +267,21 @@ __global__ __launch_bounds__(256) void k_search_argmin(TrackView tv, int V, int6
 // (out.actions) and -1 behind them -- read, like the snapshot, before the barrier that releases the copies, since the winner
 // may be a receiver of this event.  A copy takes the donor's entries 0 .. t_in - 1 with its t_in (at most `played`, the loop
 // steps of the round so far).  PATH = false compiles to the event without any of it.
+// VALUE: the rank key of a live clone is ord(s) << 32 | clone with s = fmaf(-w, v, (float)cur_gap) in fp32,
+// v = values[env] (0.0f where that is not finite) and ord the monotone map of fp32 bits to uint32 (all bits flipped under a
+// set sign bit, else the sign bit set).  s is never NaN (w, v and cur_gap are finite), so no live key is ~0.  `values` is
+// a buffer of its own, written before the launch from the states the clones hold and touched by no copy; it is read here,
+// in front of the barrier that releases the copies.  event_values (optional): [..][E][K] log, row `event`: the raw
+// values[env] of a live clone, a quiet NaN for a terminal one.  Fold, ranks, copy and LDS are the event's own; VALUE = false
+// compiles to the event without any of it.
 extern __shared__ __attribute__((aligned(16))) unsigned char resample_lds[];
-template <bool PATH>
+template <bool PATH, bool VALUE>
 __global__ __launch_bounds__(256) void k_search_resample(EnvView e, TrackView tv, int K, int survivors, int flags,
                                                          TrackView out, int32_t* __restrict__ best_clone, int64_t out_base,
                                                          int32_t* __restrict__ donors, int64_t E, int64_t event,
-                                                         int32_t* __restrict__ clone_gaps, int M, int played) {
+                                                         int32_t* __restrict__ clone_gaps, int M, int played,
+                                                         const float* __restrict__ values, float* __restrict__ event_values,
+                                                         float value_weight) {
     unsigned long long* wave_min = reinterpret_cast<unsigned long long*>(resample_lds);
     int* live_count = reinterpret_cast<int*>(resample_lds + 32);
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(resample_lds + 48);
@@ -328,8 +337,18 @@ __global__ __launch_bounds__(256) void k_search_resample(EnvView e, TrackView tv
             const uint32_t act = e.active[n];
             const int8_t* sc = e.score + n * V;
             const int cur = env_total_abs(sc, act, e.Q), sum = env_total_sum(sc, act, e.Q);
-            key = ((unsigned long long)(uint32_t)(cur - (sum < 0 ? -sum : sum)) << 32) | (unsigned long long)(uint32_t)c;
+            uint32_t hi = (uint32_t)(cur - (sum < 0 ? -sum : sum));
+            if (VALUE) {
+                const float raw = values[n];
+                if (event_values) event_values[(o * E + event) * K + c] = raw;
+                const float v = (__float_as_uint(raw) & 0x7F800000u) == 0x7F800000u ? 0.0f : raw;      // inf / NaN rank as 0
+                const uint32_t b = __float_as_uint(fmaf(-value_weight, v, (float)(int)hi));
+                hi = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+            }
+            key = ((unsigned long long)hi << 32) | (unsigned long long)(uint32_t)c;
             atomicAdd(live_count, 1);
+        } else if (VALUE && event_values) {
+            event_values[(o * E + event) * K + c] = __uint_as_float(0x7FC00000u);
         }
         keys[c] = key;
     }
@@ -560,7 +579,8 @@ int32_t launch_search_argmin(const TrackView& tv, int32_t V, int64_t S, int64_t 
 
 int32_t launch_search_resample(ppo_env_s* e, const TrackView& tv, int64_t S, int64_t K, int64_t survivors, int flags,
                                const TrackView& out, int32_t* best_clone, int64_t out_base, int32_t* donors, int64_t E,
-                               int64_t event, int32_t* clone_gaps, int64_t played) {
+                               int64_t event, int32_t* clone_gaps, int64_t played, const float* values, float* event_values,
+                               float value_weight) {
     if (K < 1 || K > PPO_RESAMPLE_MAX_K || S < 1 || S * K > e->N || e->V % 4 != 0) {
         ppo_set_error("search_resample: unsupported shape");
         return PPO_ERR_UNSUPPORTED;
@@ -573,12 +593,16 @@ int32_t launch_search_resample(ppo_env_s* e, const TrackView& tv, int64_t S, int
     ProfScope ps((flags & 2) ? "k_search_fold" : "k_search_resample");
     const size_t lds = 48 + 12 * (size_t)((K + 7) & ~(int64_t)7);
     const int M = e->max_actions, P = (int)std::min<int64_t>(played, M);
-    if (path)
-        hipLaunchKernelGGL(k_search_resample<true>, dim3((unsigned)S), dim3(256), lds, ppo_stream(), view_of(e), tv, (int)K,
-                           (int)survivors, flags, out, best_clone, out_base, donors, E, event, clone_gaps, M, P);
-    else
-        hipLaunchKernelGGL(k_search_resample<false>, dim3((unsigned)S), dim3(256), lds, ppo_stream(), view_of(e), tv, (int)K,
-                           (int)survivors, flags, out, best_clone, out_base, donors, E, event, clone_gaps, M, P);
+    const bool value = values != nullptr && !(flags & 2);               // the last fold ranks nothing
+#define LAUNCH_EVENT(PP, VV)                                                                                                  \
+    hipLaunchKernelGGL((k_search_resample<PP, VV>), dim3((unsigned)S), dim3(256), lds, ppo_stream(), view_of(e), tv, (int)K, \
+                       (int)survivors, flags, out, best_clone, out_base, donors, E, event, clone_gaps, M, P, values,          \
+                       event_values, value_weight)
+    if (path && value) LAUNCH_EVENT(true, true);
+    else if (path) LAUNCH_EVENT(true, false);
+    else if (value) LAUNCH_EVENT(false, true);
+    else LAUNCH_EVENT(false, false);
+#undef LAUNCH_EVENT
     HIP_TRY(hipGetLastError());
     return PPO_OK;
 }

@@ -331,10 +331,16 @@ int32_t launch_search_argmin(const TrackView& tv, int32_t V, int64_t S, int64_t 
 // out.actions set (tv.actions then too): the action history travels with the record -- a fold that takes a
 // winner's record writes the first best_step entries of its history to row out_base + s of out.actions and -1 behind them,
 // a copy takes the donor's entries 0 .. t_in - 1.  played: loop steps of the round so far (an upper bound of every t_in)
+// values set: [N] floats, one per env, written before this launch; a live clone ranks by
+// fmaf(-value_weight, values[env], (float)cur_gap) (a value that is not finite counting as 0) instead of cur_gap.
+// event_values (optional): [..][E][K] log of the values read, row `event`, NaN for a terminal clone
 constexpr int64_t PPO_RESAMPLE_MAX_K = 4096;
 int32_t launch_search_resample(ppo_env_s* e, const TrackView& tv, int64_t S, int64_t K, int64_t survivors, int flags,
                                const TrackView& out, int32_t* best_clone, int64_t out_base, int32_t* donors, int64_t E,
-                               int64_t event, int32_t* clone_gaps, int64_t played);
+                               int64_t event, int32_t* clone_gaps, int64_t played, const float* values = nullptr,
+                               float* event_values = nullptr, float value_weight = 0.0f);
+// the refusals every value entry point shares: a bf16-dtype critic, an input width other than F (ppo_train.hip)
+extern "C" int32_t value_checks(const char* who, ppo_policy_s* critic, int32_t F);
 // teacher-forced replay: path m ([count][stride] 0-based actions, < 0 ends a path) from snapshot m (score[V]
 // then degree[V]) as reset! leaves an env, until the path ends or the state is terminal; out_state / out_active / out_gap /
 // applied per path, trace (optional) [count][stride].  work: [4][count] int32 scratch; err: one word, OR of the step's flags

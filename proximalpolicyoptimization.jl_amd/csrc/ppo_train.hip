@@ -418,7 +418,7 @@ int32_t ppo_debug_value_deltas(ppo_policy_t critic, int64_t n, float* out) {
 
 // ================================================================ critic
 // A critic is a ppo_policy_t read as a state value (include/ppo_hip.h): the refusals every value entry point shares
-static int32_t value_checks(const char* who, ppo_policy_s* critic, int32_t F) {
+int32_t value_checks(const char* who, ppo_policy_s* critic, int32_t F) {
     if (critic->dtype != PPO_DTYPE_F32) {
         ppo_set_error(std::string(who) + ": a bf16-dtype critic is not supported (the value modes exist in the fp32-MFMA forward only)");
         return PPO_ERR_UNSUPPORTED;
