@@ -1,0 +1,80 @@
+#!/usr/bin/env python3
+"""Usage example: a self-imitation (expert-iteration) loop without a host trip -- search, collect the winners' paths, train.
+
+    starts = reset states of a fresh env
+    found  = PPO.search_best_states_(search_env, policy, *starts, K, path=True)      # best of K trajectories per start
+    PPO.collect_paths_(rollouts, env, policy, *starts, found["path"], discount)      # the paths as an ordinary rollout buffer
+    PPO.ppo_train_(policy, optimizer, PPO.construct_dataset(rollouts), epsilon, minibatch, epochs, entropy_weight)
+
+collect_paths_ replays every path on the device and leaves the state in front of each step, the path's action, the
+probability the CURRENT policy gives that action, reward, terminal flags and returns in the buffer, so every consumer of a
+sampled buffer takes it unchanged.
+
+The data is OFF-POLICY.  The actions were chosen by another sampler -- the best of K draws of the policy, not one draw -- and
+p_old is the current policy's probability of that sampler's action, not the probability the action was sampled with.  The
+ratio p_new / p_old therefore starts at 1 and the clipped surrogate limits how far one call moves the policy towards the
+searched actions; it is not the importance weight PPO's derivation assumes.  A path that ends short of the optimum is a
+truncation (terminal flag set on its last entry): with --critic the advantage is GAE bootstrapped from the critic's value of
+the state the path was cut in (compute_gae_critic_(..., bootstrap_truncated=True)).
+
+This script shows the calls and prints what it measures each round (the mean gap the search reaches, the transitions
+collected, the losses, the mean return of the plain stochastic policy).  Whether the loop learns faster or better than
+ppo_iterate_ on sampled rollouts has not been measured; the script makes no such claim.
+Run on the GPU box:  python examples/train_on_search_paths.py --rounds 10
+"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import ppo_amd as PPO  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=10)
+    ap.add_argument("--starts", type=int, default=256, help="start states per round (one resident env replays one path)")
+    ap.add_argument("--clones", type=int, default=16, help="K: trajectories the search plays from every start")
+    ap.add_argument("--critic", action="store_true", help="GAE(0.95) advantage from a device critic, bootstrapped where a path was cut")
+    args = ap.parse_args()
+
+    discount, epsilon, entropy_weight, max_actions = 1.0, 0.05, 0.01, 32
+    policy = PPO.HipPolicy(72, 128, 2, 4, seed=0)
+    optimizer = PPO.Optimiser(PPO.Adam(3e-4))
+    critic = PPO.HipCritic(72, 128, 2, seed=1) if args.critic else None
+    critic_optimizer = PPO.Optimiser(PPO.Adam(1e-3)) if args.critic else None
+    search_env = PPO.HipVecEnv(num_envs=args.starts * args.clones, Q=8, max_actions=max_actions, seed=7)
+    env = PPO.HipVecEnv(num_envs=args.starts, Q=8, max_actions=max_actions, seed=8)
+    eval_env = PPO.HipVecEnv(num_envs=1024, Q=8, max_actions=max_actions, seed=99)
+    rollouts = PPO.BufferRollouts()
+
+    for r in range(args.rounds):
+        fresh = PPO.HipVecEnv(num_envs=args.starts, Q=8, max_actions=max_actions, seed=1000 + r)   # this round's reset states
+        st = fresh.internal()
+        starts = (st["score"], st["degree"], fresh.active_quads())
+        found = PPO.search_best_states_(search_env, policy, *starts, args.clones, path=True)
+        PPO.collect_paths_(rollouts, env, policy, *starts, found["path"], discount)
+        dataset = PPO.construct_dataset(rollouts)
+        n = len(dataset)
+        if n == 0:                                            # every start was its own best state: nothing to imitate
+            print("round %d: the search improved no start" % r)
+            continue
+        advantage = "returns"
+        if critic is not None:
+            PPO.compute_gae_critic_(rollouts, env, critic, discount, 0.95, fetch=False, bootstrap_truncated=True)
+            advantage = "gae"
+        ph, eh, _ = PPO.ppo_train_(policy, optimizer, dataset, epsilon, min(1024, n), 2, entropy_weight, seed=r, verbose=False,
+                                   advantage=advantage)
+        line = "round %d: gap %.2f -> %.2f over %d starts, %d transitions, ppo loss %.4f, entropy loss %.4f" % (
+            r, found["initial_gap"].mean(), found["best_gap"].mean(), args.starts, n, ph[-1], eh[-1])
+        if critic is not None:
+            vh, _ = PPO.value_train_(critic, critic_optimizer, dataset, min(1024, n), 2, target="lambda_returns", seed=r, verbose=False)
+            line += ", value loss %.4f, %d cut paths" % (vh[-1], rollouts.n_truncated)
+        ret, dev = PPO.average_returns(policy, eval_env, 1024)
+        print(line + "; stochastic policy: mean return %.3f (std %.3f)" % (ret, dev))
+    return policy
+
+
+if __name__ == "__main__":
+    main()

@@ -652,6 +652,27 @@ int32_t ppo_env_apply_paths(ppo_env_t env, int64_t M, const int8_t* score, const
                             const int16_t* paths, int64_t stride, int8_t* out_state, uint32_t* out_active, int32_t* out_gap,
                             int32_t* applied, int32_t* trace_or_null);
 
+/* Teacher-forced collection: the collector that plays GIVEN actions instead of sampled ones and leaves an
+ * ordinary rollout buffer behind, so that the paths of a search (or recorded action histories) can be trained on without a
+ * host replay.  Starts and paths as for ppo_env_apply_paths: path m of paths [M][stride] (0-based; its declared length is
+ * the index of its first entry < 0, at most stride) on start m, 1 <= M <= N.  Resident envs 0 .. M - 1 are loaded with the
+ * starts as reset! leaves an env; the loop of ppo_collect_rollouts_episodes then runs T = max(1, longest declared length)
+ * steps: observe, (snapshot,) the policy forward WITHOUT sampling -- p_sel = the probability the policy gives the path's
+ * action in the state in front of the step --, step!.  Env n idles at step t (valid 0, reward 0, done 1, untouched) when
+ * n >= M, t is at or behind its path's declared length, or it is terminal.  terminal = is_terminal OR "the path's last
+ * entry": every path is a whole episode for the return scan and GAE, and a path cut short of the optimum is a truncation
+ * for ppo_rollouts_compute_gae_critic_boot, which then bootstraps from the critic's value of the state it was cut in.
+ * Storage form (compact / expanded), index (env-major, valid transitions only), length and returns as the episodes form
+ * leaves them; record_probs as ppo_collect_rollouts.  The envs that played keep the states their paths ended in, their
+ * ticks advanced by the steps played, their episode counters unchanged; the other envs and the env's flag word are
+ * untouched.  PPO_ERR_ARG before anything runs: M < 1, M > N, stride < 1, a bad start, an entry >= 16 Q.
+ * PPO_ERR_UNSUPPORTED: a bf16-dtype policy, a disk sink attached to ro, H other than 32 / 128.  PPO_ERR_DEVICE_FLAG, the
+ * buffer filled: an action on an inactive quad -- played and penalised as step! does, recorded with valid = 0 and
+ * p_sel = 0, so it is in no dataset (the forward reports it in bit 64 of the call's flag word, the step in bit 1). */
+int32_t ppo_collect_paths(ppo_rollouts_t ro, ppo_env_t env, ppo_policy_t pol, int64_t M, const int8_t* score,
+                          const int8_t* degree, const uint32_t* active, const int16_t* paths, int64_t stride,
+                          double discount, int32_t discount_is_f32, int32_t record_probs);
+
 /* timing of the dominant kernels of the last ppo_train / ppo_collect_rollouts call, measured with
  * HIP events on the engine's stream (bench.py roofline leg) */
 /* measurement helper: run the return scan `iters` times on device-resident synthetic [T,N] columns (no host

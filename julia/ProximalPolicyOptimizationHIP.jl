@@ -430,6 +430,19 @@ function apply_paths(env::HipVecEnv, score::Matrix{Int8}, degree::Matrix{Int8}, 
                 env.h, M, score, degree, active, raw, Int64(stride), st, act, gap, applied, trace))
     (state = st, active = act, gap = gap, applied = applied, trace = trace)
 end
+# teacher-forced collection: env i (i <= M <= env.N) is loaded with start i and plays paths[:, i] instead of sampled actions;
+# r becomes an ordinary rollout buffer -- the state in front of every step, the path's action, the probability the CURRENT
+# policy gives it, reward, terminal (is_terminal or the path's last entry), returns -- that construct_dataset, train! and the
+# critic calls take unchanged.  The data is off-policy: p_old is the policy's probability of another sampler's action
+function collect_paths!(r::HipRollouts, env::HipVecEnv, p::HipPolicy, score::Matrix{Int8}, degree::Matrix{Int8},
+                        active::Vector{UInt32}, paths::Matrix{Int16}, discount)
+    M, stride = length(active), size(paths, 1)
+    raw = max.(paths, Int16(0)) .- Int16(1)
+    h = ensure!(r, env, max(stride, 1))
+    check(ccall((:ppo_collect_paths, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Int8}, Ptr{Int8}, Ptr{UInt32}, Ptr{Cvoid}, Int64, Float64, Int32, Int32),
+                h, env.h, p.h, M, score, degree, active, raw, Int64(stride), Float64(discount), discount isa Float32, Int32(0)))
+end
 
 # batch_advantage plugin mode handed to the engine: 0 = returns (PPO.batch_advantage above), 1 = normalised returns,
 # 2 / 3 = GAE(gamma, lambda) / normalised GAE over values supplied through compute_gae!

@@ -60,6 +60,7 @@ __all__ = [
     "kl_stats", "explained_variance_", "explained_variance_from_sums",
     "check_internal", "best_states_", "best_state_in_rollout", "single_trajectory_scores", "count_non_flips",
     "search_best_states_", "search_resample_states_", "check_resample", "apply_paths_", "check_paths",
+    "collect_paths_",
 ]
 
 
@@ -1103,6 +1104,38 @@ def collect_rollouts_steps_(rollouts, env, policy, num_steps, discount, record_p
     h = rollouts._ensure(env, int(num_steps))
     g, f32 = _discount_args(discount)
     call("ppo_collect_rollouts", h, env._h, policy._h, int(num_steps), g, f32, int(bool(record_probs)))
+
+
+def collect_paths_(rollouts, env, policy, score, degree, active, paths, discount, record_probs=False):
+    """Teacher-forced collection: resident env m < M is loaded with start m (score, degree [M, 4Q], active [M]; M <= N) as
+    reset! leaves an env and plays path m (paths [M, stride], 1-based action indices as the searches' path output and
+    apply_paths_ speak them, anything <= 0 ends a path) instead of sampled actions.  `rollouts` becomes an ordinary buffer
+    of T = max(1, longest path) steps: the state in front of every step (compact or expanded storage, as the collectors
+    choose), the path's action, the probability the CURRENT policy gives it, reward, terminal, valid, returns and the
+    env-major dataset index -- what construct_dataset, ppo_train_, forward_backward, value_train_, compute_values_ and
+    compute_gae_critic_ take unchanged.  An env idles (valid False, action 0) behind its path's end, once it is terminal,
+    and from M on.  terminal = is_terminal or "the path's last entry": a path is a whole episode for the returns and GAE, and
+    a path cut short of the optimum is a truncation, so compute_gae_critic_(..., bootstrap_truncated=True) bootstraps from the
+    critic's value of the state it was cut in.  The data is off-policy: selected_action_probabilities is this policy's
+    probability of another sampler's action.  The envs that played keep their final states, ticks advanced by the steps
+    played, episode counters unchanged; the others are untouched.  An action on an inactive quad is played and penalised
+    as step! does, recorded with valid False and probability 0 (in no dataset), and the call raises
+    PPOError(PPO_ERR_DEVICE_FLAG) with the buffer filled.  HipVecEnv and a fp32 HipPolicy only.  Returns nothing."""
+    if not isinstance(env, HipVecEnv):
+        raise PPOError(-4, "collect_paths_ needs a HipVecEnv")
+    if not isinstance(policy, HipPolicy):
+        _not_implemented("action_probabilities")
+    if isinstance(rollouts, DiskRollouts):
+        raise PPOError(-4, "collect_paths_: DiskRollouts are not supported")
+    sc, dg, act = check_internal(score, degree, active, env.Q)
+    M = sc.shape[0]
+    if not 1 <= M <= env.N:
+        raise PPOError(-1, "AssertionError: collect_paths!: need 1 <= M <= N paths (one resident env plays one path)")
+    pa = check_paths(paths, M, env.Q)
+    h = rollouts._ensure(env, pa.shape[1])
+    g, f32 = _discount_args(discount)
+    call("ppo_collect_paths", h, env._h, policy._h, M, _p(sc, _lib.c_i8p), _p(dg, _lib.c_i8p), _p(act, _lib.c_u32p),
+         _p(pa, _lib.c_i16p), pa.shape[1], g, f32, int(bool(record_probs)))
 
 
 def compute_gae_(rollouts, values, gamma, lam, final_values=None):

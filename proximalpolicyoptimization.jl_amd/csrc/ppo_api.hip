@@ -1334,6 +1334,94 @@ int32_t ppo_env_apply_paths(ppo_env_t env, int64_t M, const int8_t* score, const
     return PPO_OK;
 }
 
+// Teacher-forced collection: envs 0 .. M - 1 are loaded with the starts and play the given paths instead of
+// sampled actions, and what they pass through is left in `ro` as an ordinary rollout buffer.  The loop is the episodes
+// mode's -- observe, snapshot when compact, forward, step -- with the forced forward and the forced step; the host knows every
+// path's declared length, so T is known in front of the loop and nothing is polled.  The flag word is the call's own: a
+// path with an action on an inactive quad does not leave the env handle flagged
+int32_t ppo_collect_paths(ppo_rollouts_t ro, ppo_env_t env, ppo_policy_t pol, int64_t M, const int8_t* score, const int8_t* degree,
+                          const uint32_t* active, const int16_t* paths, int64_t stride, double discount, int32_t discount_is_f32,
+                          int32_t record_probs) {
+    PPO_TRY(check_shapes(ro, env, pol));
+    ARG_CHECK(score && degree && active && paths, "collect_paths!: null argument");
+    const int64_t N = env->N;
+    ARG_CHECK(M >= 1 && M <= N, "collect_paths!: need 1 <= M <= N paths (one resident env plays one path)");
+    ARG_CHECK(stride >= 1 && stride <= INT32_MAX, "collect_paths!: stride must be >= 1");
+    PPO_TRY(check_internal_host(env->Q, M, score, degree, active));
+    const int32_t V = env->V, A = 16 * env->Q;
+    const size_t Ms = (size_t)M, cells = Ms * (size_t)stride;
+    std::vector<int32_t> lens(Ms);                                       // declared length: the index of the first negative entry
+    int64_t T = 1;
+    for (size_t m = 0; m < Ms; ++m) {
+        int64_t len = stride;
+        for (int64_t i = 0; i < stride; ++i) {
+            const int16_t a = paths[m * (size_t)stride + i];
+            ARG_CHECK(a < A, "collect_paths!: action index out of range");
+            if (a < 0 && i < len) len = i;
+        }
+        lens[m] = (int32_t)len;
+        T = std::max(T, len);
+    }
+    if (pol->dtype != PPO_DTYPE_F32) {
+        ppo_set_error("collect_paths!: a bf16-dtype policy is not supported (the teacher-forced mode exists in the fp32-MFMA forward only)");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    if (ro->sink) {
+        ppo_set_error("collect_paths!: a buffer with a disk sink attached is not supported");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    const bool compact = want_compact(ro, T);
+    PPO_TRY(rollouts_reserve(ro, T, compact));
+    const size_t srow = (size_t)N * env->H * env->F, crow = (size_t)N * 2 * V;
+    if (compact) PPO_TRY(env->obs_tmp.alloc(srow));
+    if (record_probs) PPO_TRY(ro->full_probs.alloc((size_t)T * N * env->A));
+    std::vector<int8_t> snap(Ms * 2 * V);                                // k_env_snapshot's layout: score[V] then degree[V]
+    for (size_t m = 0; m < Ms; ++m) {
+        std::memcpy(&snap[m * 2 * V], score + m * V, (size_t)V);
+        std::memcpy(&snap[m * 2 * V + V], degree + m * V, (size_t)V);
+    }
+    DevBuf<int8_t> d_start; DevBuf<uint32_t> d_act; DevBuf<int16_t> d_paths; DevBuf<int32_t> d_ints;
+    PPO_TRY(d_start.alloc(snap.size())); PPO_TRY(d_act.alloc(Ms)); PPO_TRY(d_paths.alloc(cells));
+    PPO_TRY(d_ints.alloc(Ms + (size_t)N + 1));                           // lens [M], the load's step counters [N], the flag word
+    PPO_TRY(h2d(d_start.p, snap.data(), snap.size())); PPO_TRY(h2d(d_act.p, active, Ms)); PPO_TRY(h2d(d_paths.p, paths, cells));
+    PPO_TRY(h2d(d_ints.p, lens.data(), Ms));
+    int32_t* d_err = d_ints.p + Ms + N;
+    HIP_TRY(hipMemsetAsync(d_err, 0, 4, g_stream));
+    // envs 0 .. M - 1 as reset! leaves an env, one start each; the envs behind them keep what they hold and idle
+    PPO_TRY(launch_env_load_starts(env, d_start.p, d_act.p, M, 1, d_ints.p + Ms));
+    for (int64_t t = 0; t < T; ++t) {
+        int8_t* st = compact ? env->obs_tmp.p : ro->states.p + (size_t)t * srow;
+        uint32_t* am = ro->active.p + (size_t)t * N;
+        int32_t* ac = ro->actions.p + t * N;
+        PPO_TRY(launch_env_observe(env, st, am));
+        if (compact) PPO_TRY(launch_env_snapshot(env, ro->cstate.p + (size_t)t * crow));
+        PPO_TRY(launch_paths_feed(env, d_paths.p, d_ints.p, M, stride, t, ac));
+        PPO_TRY(launch_policy_forced(pol, env, st, am, ac, ro->p_sel.p + t * N,
+                                     record_probs ? ro->full_probs.p + (size_t)t * N * env->A : nullptr, d_err));
+        PPO_TRY(launch_env_step_forced(env, ac, d_ints.p, t, ro->rewards.p + t * N, ro->done.p + t * N, ro->valid.p + t * N, d_err));
+    }
+    ro->T = T; ro->adv_T = -1; ro->values_T = -1; ro->boot_T = -1;
+    // dataset order = env-major concatenation of the paths, valid transitions only (the episodes mode's order)
+    std::vector<uint8_t> valid((size_t)T * N);
+    PPO_TRY(d2h(valid.data(), ro->valid.p, (size_t)T * N));
+    std::vector<int32_t> index;
+    index.reserve((size_t)T * N);
+    for (int64_t n = 0; n < N; ++n)
+        for (int64_t t = 0; t < T; ++t)
+            if (valid[(size_t)t * N + n]) index.push_back((int32_t)(t * N + n));
+    ro->len = (int64_t)index.size();
+    ro->all_valid = false;
+    PPO_TRY(h2d(ro->index.p, index.data(), index.size()));
+    PPO_TRY(launch_returns_tn(ro->rewards.p, ro->done.p, ro->returns.p, T, N, discount, discount_is_f32));
+    int32_t f = 0;
+    PPO_TRY(d2h(&f, d_err, 1));
+    if (f) {
+        ppo_set_error("AssertionError (device flag): collect_paths!: a path holds an action on an inactive quad (its transition is recorded with valid = 0 and probability 0)");
+        return PPO_ERR_DEVICE_FLAG;
+    }
+    return PPO_OK;
+}
+
 #define RO_GETTER(name, member, type, per)                                                     \
     int32_t name(ppo_rollouts_t ro, type* out) {                                               \
         ARG_CHECK(ro && out, #name ": null");                                                  \

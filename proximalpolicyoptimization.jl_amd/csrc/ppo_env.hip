@@ -441,6 +441,43 @@ __global__ void k_env_apply_paths(EnvConst c, int64_t count, const uint32_t* __r
     applied[m] = n;
 }
 
+// Teacher-forced collection, feed: the action env n is given at loop step t, into the rollout buffer's action
+// column.  THE definition of "idle": env n plays paths[n][t] unless n >= M, t is at or behind the path's declared length
+// (lens[n] = index of its first negative entry, at most stride: worked out by the host, which needs it for T anyway) or the
+// env is terminal; an idle env gets -1.  The forced forward and the forced step both read this column and nothing else
+__global__ void k_paths_feed(EnvView e, const int16_t* __restrict__ paths, const int32_t* __restrict__ lens, int64_t M,
+                             int64_t stride, int64_t t, int32_t* __restrict__ actions_out) {
+    const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= e.N) return;
+    int a = -1;
+    if (n < M && t < (int64_t)lens[n] && !e.done[n]) a = paths[n * stride + t];
+    actions_out[n] = a;
+}
+
+// ... and the step beside k_env_step: one thread per env.  An idle env (action < 0) records valid = 0, reward = 0, done = 1
+// like the idle branch of the episodes mode and its state, tick included, stays.  Every other env (then n < M) steps with
+// env_step_ref; done_out = the env's own done OR "this was the path's last entry" (t + 1 == lens[n]), so that a path is a
+// whole episode for the return scan, GAE and the truncation detector.  An action on an inactive quad is played and
+// penalised as step! does and recorded with valid = 0: it never enters the dataset.  No reset, no episode bookkeeping;
+// flags go to *err, a word of the call
+__global__ void k_env_step_forced(EnvView e, const int32_t* __restrict__ actions, const int32_t* __restrict__ lens, int64_t t,
+                                  float* __restrict__ reward_out, uint8_t* __restrict__ done_out,
+                                  uint8_t* __restrict__ valid_out, int32_t* __restrict__ err) {
+    const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= e.N) return;
+    const int a = actions[n];
+    if (a < 0) {
+        valid_out[n] = 0; reward_out[n] = 0.0f; done_out[n] = 1;
+        return;
+    }
+    float rew; uint8_t dn;
+    const int errf = env_step_ref(const_of(e), ref_of(e, n), a, rew, dn);
+    if (errf) atomicOr(err, errf);
+    reward_out[n] = rew;
+    done_out[n] = (uint8_t)(dn || t + 1 >= (int64_t)lens[n]);
+    valid_out[n] = (errf & 1) ? 0 : 1;
+}
+
 // state(env): obs[n][h][f] int8, f<36 template scores, f>=36 template degrees, 0 where the
 // template entry is missing or its quad is inactive (test/quad_game_utilities.jl:35-37,46-59).
 // One thread per output dword (4 features): coalesced 4-byte stores.
@@ -620,6 +657,23 @@ int32_t launch_env_apply_paths(ppo_env_s* e, int64_t count, const int8_t* start_
     hipLaunchKernelGGL(k_env_apply_paths, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, ppo_stream(), c, count,
                        reinterpret_cast<const uint32_t*>(start_state), start_active, paths, (int)stride, out_state, out_active,
                        out_gap, applied, trace_or_null, work, err);
+    HIP_TRY(hipGetLastError());
+    return PPO_OK;
+}
+
+int32_t launch_paths_feed(ppo_env_s* e, const int16_t* paths, const int32_t* lens, int64_t M, int64_t stride, int64_t t,
+                          int32_t* actions_out) {
+    hipLaunchKernelGGL(k_paths_feed, dim3((unsigned)((e->N + 255) / 256)), dim3(256), 0, ppo_stream(), view_of(e), paths, lens, M,
+                       stride, t, actions_out);
+    HIP_TRY(hipGetLastError());
+    return PPO_OK;
+}
+
+int32_t launch_env_step_forced(ppo_env_s* e, const int32_t* actions_dev, const int32_t* lens, int64_t t, float* reward_out,
+                               uint8_t* done_out, uint8_t* valid_out, int32_t* err) {
+    ProfScope ps("k_env_step_forced");
+    hipLaunchKernelGGL(k_env_step_forced, dim3((unsigned)((e->N + 63) / 64)), dim3(64), 0, ppo_stream(), view_of(e), actions_dev,
+                       lens, t, reward_out, done_out, valid_out, err);
     HIP_TRY(hipGetLastError());
     return PPO_OK;
 }

@@ -347,6 +347,15 @@ extern "C" int32_t value_checks(const char* who, ppo_policy_s* critic, int32_t F
 int32_t launch_env_apply_paths(ppo_env_s* e, int64_t count, const int8_t* start_state, const uint32_t* start_active,
                                const int16_t* paths, int32_t stride, int8_t* out_state, uint32_t* out_active, int32_t* out_gap,
                                int32_t* applied, int32_t* trace_or_null, int32_t* work, int32_t* err);
+// teacher-forced collection, loop step t.  Feed: actions_out[n] = paths[n][t] (0-based; [M][stride], lens[n] =
+// the path's declared length <= stride), or -1 for an idle env: n >= M, t >= lens[n], or the env is terminal.  Forced forward:
+// launch_policy_forced below.  Forced step: every env with an action >= 0 steps (env_step_ref), done = its own done or
+// t + 1 == lens[n], valid = 0 for an action on an inactive quad; an idle env records valid 0, reward 0, done 1 and is not
+// touched.  err: one word of the caller's, OR of the step's flags and the forward's bit 64
+int32_t launch_paths_feed(ppo_env_s* e, const int16_t* paths, const int32_t* lens, int64_t M, int64_t stride, int64_t t,
+                          int32_t* actions_out);
+int32_t launch_env_step_forced(ppo_env_s* e, const int32_t* actions_dev, const int32_t* lens, int64_t t, float* reward_out,
+                               uint8_t* done_out, uint8_t* valid_out, int32_t* err);
 int32_t launch_env_observe(ppo_env_s* e, int8_t* obs_out, uint32_t* active_out);
 // compact rollout storage: env snapshot of every env (score[V] then degree[V]) -> cstate_out [N][2V]
 int32_t launch_env_snapshot(ppo_env_s* e, int8_t* cstate_out);
@@ -360,6 +369,10 @@ int32_t launch_policy_probs(ppo_policy_s* p, const int8_t* states_dev, const uin
                             int32_t H, float* probs_dev);
 int32_t launch_policy_rollout(ppo_policy_s* p, ppo_env_s* e, const int8_t* states_dev, const uint32_t* active_dev,
                               int32_t* actions_out, float* psel_out, float* full_probs_or_null);
+// one teacher-forced step (k_policy_fwd MODE 11): actions_io[n] = env n's given action (kept; < 0 idles), psel_out[n] = its
+// probability under the policy, 0 for an idle env or an inactive quad (bit 64 of *err).  A bf16-dtype policy: PPO_ERR_UNSUPPORTED
+int32_t launch_policy_forced(ppo_policy_s* p, ppo_env_s* e, const int8_t* states_dev, const uint32_t* active_dev,
+                             int32_t* actions_io, float* psel_out, float* full_probs_or_null, int32_t* err);
 // adv_col: the advantage column indexed by transition id (ro->returns for PPO_ADV_RETURNS)
 int32_t launch_policy_rollout_persistent(ppo_policy_s* p, ppo_env_s* e, ppo_rollouts_s* ro, int64_t T, int record_probs,
                                          int64_t t0 = 0);

@@ -56,6 +56,8 @@ static __device__ __forceinline__ void act_store_nt(float4* p, float4 v) {
 // 9 / 10: 6 / 8 with PPO's clipped value loss (value_tail VMODE 2).  Own modes rather than a runtime test in the tail: with the
 // test, value_train_ at the headline shape measured 0.4 % more per iteration's critic part with the clip unset (the register
 // allocation of k_policy_fwd<72,256,6,1,0> moved), outside the range of the parent's own runs; 6 / 8 are now the parent's code
+// 11: one teacher-forced step: MODE 1's forward and outputs with the action read from a.actions instead of
+// sampled (policy_tail's mode 11); an own mode for the same reason, MODE 1 is the parent's code
 constexpr bool fwd_mode_value(int m) { return m >= 5 && m <= 10; }
 constexpr bool fwd_mode_vclip(int m) { return m == 9 || m == 10; }
 constexpr bool fwd_mode_train(int m) { return m == 2 || m == 4 || m == 6 || m == 8 || fwd_mode_vclip(m); }   // saves activations, writes dY
@@ -212,6 +214,9 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
         if (SNAP) fetch_snapshot(state + nwaves < a.B ? state + nwaves : state);      // lands under this state's MFMAs
         const uint32_t tick_val = (MODE == 3) ? *er.tick : ((MODE == 1) ? a.tick[state] : 0u);
         const int64_t out_index = (MODE == 3) ? tt * a.B + state : state;
+        // teacher-forced step: the state's given action, fetched here like the tick so that it has landed by the tail
+        [[maybe_unused]] TailPre forced = {0, 0.0f, 0.0f};
+        if constexpr (MODE == 11) forced.ab = a.actions[state];
         float l[TPS][4];
         // multi-tile states: the tile loop stays a real loop (no 4x code blow-up, no cross-tile hoisting that
         // would spill); the 4 logits per lane of each tile are parked in LDS and re-read after the loop
@@ -454,6 +459,7 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
         FSTAMP(4);
         int sampled = 0;
         if constexpr (VALUE) value_tail<fwd_mode_vclip(MODE) ? 2 : (TRAIN ? 1 : 0), TPS>(a, state, act, l, lane, j, h, out_index, vtarget, vold);
+        else if constexpr (MODE == 11) sampled = policy_tail<11, TPS, false>(a, state, sid, act, l, lane, j, h, 0u, out_index, &forced);
         else sampled = policy_tail<TMODE, TPS, false>(a, state, sid, act, l, lane, j, h, tick_val, out_index);
         if (MODE == 3) {
             // update!: the observed mask, then step!(env, a), reward, is_terminal (src/collect_rollouts.jl:9-14) and the
@@ -631,6 +637,23 @@ int32_t launch_policy_rollout(ppo_policy_s* p, ppo_env_s* e, const int8_t* state
         if (rs != PPO_ERR_UNSUPPORTED) return rs;
     }
     return dispatch_fwd<1>(p, a, e->N, e->H / 32);
+}
+
+// One teacher-forced step (MODE 11): actions_io[n] holds env n's given 0-based action (< 0: the env idles) and keeps it;
+// psel_out[n] = the policy's probability of it (0 for an idle env or an action on an inactive quad, the latter also setting
+// bit 64 of *err, a word of the caller's).  The per-step launch only: no split-rollout form, no persistent form, no bf16 mode
+int32_t launch_policy_forced(ppo_policy_s* p, ppo_env_s* e, const int8_t* states_dev, const uint32_t* active_dev,
+                             int32_t* actions_io, float* psel_out, float* full_probs_or_null, int32_t* err) {
+    if (p->dtype != PPO_DTYPE_F32) {
+        ppo_set_error("collect_paths!: a bf16-dtype policy is not supported (the teacher-forced mode exists in the fp32-MFMA forward only)");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    FwdArgs a = {};
+    fill_weights(p, a);
+    a.states = states_dev; a.active = active_dev; a.B = e->N;
+    a.actions = actions_io; a.actions_out = actions_io; a.psel_out = psel_out; a.full_probs = full_probs_or_null; a.err = err;
+    ProfScope ps("k_policy_fwd_forced");
+    return dispatch_fwd<11>(p, a, e->N, e->H / 32);
 }
 
 // Persistent rollout (MODE 3): T steps of all N envs in one launch.  Returns PPO_ERR_UNSUPPORTED (without setting an

@@ -105,6 +105,7 @@ struct TailPre { int ab; float po; float adv; };
 // MODE 2 also serves the train forward from compact states (kernel MODE 4).
 // MODE 1 / 3 (rollout): tick_val = the env's tick (Philox counter word), out_index = position of the transition in
 // the output columns (state for one step, t*N + state for the persistent rollout); returns the sampled action.
+// MODE 11 (teacher-forced step): the MODE 1 outputs for the action in pre->ab instead of a sampled one; returns it.
 // dy_copy (MODE 2, TPS == 1, optional): a second destination for the state's 32 dL/dlogits rows, e.g. an LDS tile of the
 // calling workgroup (k_policy_train_tile keeps the whole training pass of a tile on the CU).
 template <int MODE, int TPS, bool DYBF16>
@@ -196,6 +197,34 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
             a.psel_out[out_index] = psel;
         }
         sampled = ia;
+        if (a.full_probs && h == 0) {
+#pragma unroll
+            for (int ts = 0; ts < TPS; ++ts)
+                reinterpret_cast<float4*>(a.full_probs)[((size_t)out_index * TPS + ts) * 32 + j] =
+                    make_float4(p[ts][0], p[ts][1], p[ts][2], p[ts][3]);
+        }
+    }
+    if (MODE == 11) {
+        // teacher-forced: the action is given -- pre->ab, the caller's early fetch of a.actions[out_index], 0-based,
+        // wave-uniform -- and p[action] is picked like the training tail picks p[ab]: no Philox call, no walk.  ab < 0 (an idle
+        // env): probability 0.  An action on an inactive quad: the mask left it exactly 0; it is written as 0 and reported
+        // in flag bit 64 (the rollout tail owns 8 and 32, the env step 1, 2 and 4, the minibatch gather 16)
+        const int ab = pre->ab;
+        const int abc = ab < 0 ? 0 : ab;
+        float cand = 0.0f;
+#pragma unroll
+        for (int ts = 0; ts < TPS; ++ts)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) cand = ((abc >> 7) == ts && (abc & 3) == i) ? p[ts][i] : cand;
+        float psel = __shfl(cand, (abc & 127) >> 2);
+        const bool off_quad = ab >= 0 && !((act >> (abc >> 4)) & 1u);
+        if (ab < 0 || off_quad) psel = 0.0f;
+        if (lane == 0) {
+            if (off_quad) atomicOr(a.err, 64);
+            a.actions_out[out_index] = ab;
+            a.psel_out[out_index] = psel;
+        }
+        sampled = ab;
         if (a.full_probs && h == 0) {
 #pragma unroll
             for (int ts = 0; ts < TPS; ++ts)
