@@ -4,22 +4,28 @@
     starts = reset states of a fresh env
     found  = PPO.search_best_states_(search_env, policy, *starts, K, path=True)      # best of K trajectories per start
     PPO.collect_paths_(rollouts, env, policy, *starts, found["path"], discount)      # the paths as an ordinary rollout buffer
-    PPO.ppo_train_(policy, optimizer, PPO.construct_dataset(rollouts), epsilon, minibatch, epochs, entropy_weight)
+    PPO.imitate_train_(policy, optimizer, PPO.construct_dataset(rollouts), minibatch, epochs, entropy_weight)   # --loss clone
 
 collect_paths_ replays every path on the device and leaves the state in front of each step, the path's action, the
 probability the CURRENT policy gives that action, reward, terminal flags and returns in the buffer, so every consumer of a
 sampled buffer takes it unchanged.
 
 The data is OFF-POLICY.  The actions were chosen by another sampler -- the best of K draws of the policy, not one draw -- and
-p_old is the current policy's probability of that sampler's action, not the probability the action was sampled with.  The
-ratio p_new / p_old therefore starts at 1 and the clipped surrogate limits how far one call moves the policy towards the
-searched actions; it is not the importance weight PPO's derivation assumes.  A path that ends short of the optimum is a
-truncation (terminal flag set on its last entry): with --critic the advantage is GAE bootstrapped from the critic's value of
-the state the path was cut in (compute_gae_critic_(..., bootstrap_truncated=True)).
+p_old is the current policy's probability of that sampler's action, not the probability the action was sampled with.
+--loss chooses what is minimised on it:
+    clone (default)  imitate_train_, uniform weights: the cross-entropy -mean log pi(a | s) of the paths' actions (behaviour
+                     cloning, as in expert iteration); p_old is not read
+    sil              imitate_train_(weights="positive_advantage"): -mean(max(adv, 0) log pi(a | s)) (self-imitation); adv is
+                     the buffer's returns, or with --critic GAE at lambda = 1 (R - V), bootstrapped where a path was cut
+    ppo              ppo_train_: the ratio p_new / p_old starts at 1 and the clipped surrogate limits how far one call moves
+                     the policy towards the searched actions; it is not the importance weight PPO's derivation assumes
+A path that ends short of the optimum is a truncation (terminal flag set on its last entry): with --critic the advantage is
+GAE bootstrapped from the critic's value of the state the path was cut in (compute_gae_critic_(..., bootstrap_truncated=True);
+lambda 0.95 for --loss ppo, 1 for --loss sil).
 
 This script shows the calls and prints what it measures each round (the mean gap the search reaches, the transitions
 collected, the losses, the mean return of the plain stochastic policy).  Whether the loop learns faster or better than
-ppo_iterate_ on sampled rollouts has not been measured; the script makes no such claim.
+ppo_iterate_ on sampled rollouts, and which --loss serves it best, has not been measured; the script makes no such claim.
 Run on the GPU box:  python examples/train_on_search_paths.py --rounds 10
 """
 import argparse
@@ -36,7 +42,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--starts", type=int, default=256, help="start states per round (one resident env replays one path)")
     ap.add_argument("--clones", type=int, default=16, help="K: trajectories the search plays from every start")
-    ap.add_argument("--critic", action="store_true", help="GAE(0.95) advantage from a device critic, bootstrapped where a path was cut")
+    ap.add_argument("--critic", action="store_true", help="GAE advantage from a device critic, bootstrapped where a path was cut")
+    ap.add_argument("--loss", choices=("ppo", "clone", "sil"), default="clone",
+                    help="clone: cross-entropy on the paths' actions; sil: weighted by max(advantage, 0); ppo: the clipped surrogate")
     args = ap.parse_args()
 
     discount, epsilon, entropy_weight, max_actions = 1.0, 0.05, 0.01, 32
@@ -62,12 +70,17 @@ def main():
             continue
         advantage = "returns"
         if critic is not None:
-            PPO.compute_gae_critic_(rollouts, env, critic, discount, 0.95, fetch=False, bootstrap_truncated=True)
+            PPO.compute_gae_critic_(rollouts, env, critic, discount, 1.0 if args.loss == "sil" else 0.95, fetch=False,
+                                    bootstrap_truncated=True)
             advantage = "gae"
-        ph, eh, _ = PPO.ppo_train_(policy, optimizer, dataset, epsilon, min(1024, n), 2, entropy_weight, seed=r, verbose=False,
-                                   advantage=advantage)
-        line = "round %d: gap %.2f -> %.2f over %d starts, %d transitions, ppo loss %.4f, entropy loss %.4f" % (
-            r, found["initial_gap"].mean(), found["best_gap"].mean(), args.starts, n, ph[-1], eh[-1])
+        if args.loss == "ppo":
+            ph, eh, _ = PPO.ppo_train_(policy, optimizer, dataset, epsilon, min(1024, n), 2, entropy_weight, seed=r, verbose=False,
+                                       advantage=advantage)
+        else:
+            ph, eh, _ = PPO.imitate_train_(policy, optimizer, dataset, min(1024, n), 2, entropy_weight, seed=r, verbose=False,
+                                           weights="uniform" if args.loss == "clone" else "positive_advantage", advantage=advantage)
+        line = "round %d: gap %.2f -> %.2f over %d starts, %d transitions, %s loss %.4f, entropy loss %.4f" % (
+            r, found["initial_gap"].mean(), found["best_gap"].mean(), args.starts, n, args.loss, ph[-1], eh[-1])
         if critic is not None:
             vh, _ = PPO.value_train_(critic, critic_optimizer, dataset, min(1024, n), 2, target="lambda_returns", seed=r, verbose=False)
             line += ", value loss %.4f, %d cut paths" % (vh[-1], rollouts.n_truncated)

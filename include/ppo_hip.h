@@ -376,6 +376,32 @@ int32_t ppo_train(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, double ep
                   int32_t rank, int32_t world, ppo_allreduce_fn allreduce, void* allreduce_ctx, double* ppo_hist,
                   double* entropy_hist, double* lr_hist);
 
+/* ---------------------------------------------------------------- behaviour cloning (imitation) on a rollout buffer
+ * No reference op.  Supervised learning on the buffer's stored actions -- the action paths of a search collected by
+ * ppo_collect_paths, or recorded action histories: the policy minimises
+ *     -(1 / B_global) sum_i w_i log pi(a_i | s_i)  +  entropy_weight * (the entropy term of ppo_loss_with_entropy)
+ * with log pi formed as a log-softmax over the actions of active quads, (l[a] - max l) - log sum exp(l - max l), so that an
+ * action the current policy gives a probability that underflows to 0 still has a finite loss and gradient; the gradient is
+ * (w / B_global)(p_k - [k == a]) per logit.  Every stored action must lie on an active quad (as for ppo_forward_backward).
+ * weight_mode: PPO_IMITATE_UNIFORM, w = 1 (behaviour cloning); PPO_IMITATE_POSITIVE_ADVANTAGE, w = max(adv, 0) with adv the
+ * column adv_mode names (self-imitation learning): PPO_ADV_RETURNS or PPO_ADV_GAE -- the latter needs a GAE call on these
+ * rollouts first (PPO_ERR_ARG); the two normalised modes and an unknown weight mode are PPO_ERR_UNSUPPORTED.  adv_mode is
+ * checked in both weight modes and read in the weighted one.  p_old is not read; no probability ratio is stored.
+ * fp32 dtype only (a bf16-dtype policy: PPO_ERR_UNSUPPORTED), any fp32 policy shape ppo_forward_backward takes. */
+#define PPO_IMITATE_UNIFORM 0
+#define PPO_IMITATE_POSITIVE_ADVANTAGE 1
+/* gradient only, like ppo_forward_backward (same argument checks); the two loss columns through ppo_last_losses: the
+ * cross-entropy and entropy_weight * entropy loss */
+int32_t ppo_imitate_forward_backward(ppo_policy_t pol, ppo_rollouts_t ro, const int64_t* sample_idx, int64_t B,
+                                     int64_t B_global, double entropy_weight, int32_t weight_mode, int32_t adv_mode);
+/* ppo_train's epoch loop on that objective: perm / seed / rank / world / allreduce / allreduce_ctx and the three history
+ * arrays as there (ce_hist: per-epoch mean of the per-batch cross-entropies).  The policy's target_kl is not read: the
+ * call never stops early, stores no ratios and leaves ppo_policy_last_train_stats what the latest ppo_train left. */
+int32_t ppo_imitate_train(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, int64_t batch_size, int32_t num_epochs,
+                          double entropy_weight, int32_t weight_mode, int32_t adv_mode, const int64_t* perm, uint64_t seed,
+                          int32_t rank, int32_t world, ppo_allreduce_fn allreduce, void* allreduce_ctx, double* ce_hist,
+                          double* entropy_hist, double* lr_hist);
+
 /* ---------------------------------------------------------------- update statistics and target-KL early stopping
  * No reference op: the reference reports the two losses and the learning rate.  While a target_kl is set on the policy
  * handle (below; +inf = record only), every train forward stores the probability ratio r = p_new(a|s) / p_old(a|s) of

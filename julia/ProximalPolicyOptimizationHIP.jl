@@ -498,6 +498,34 @@ function PPO.ppo_train!(p::HipPolicy, optimizer, r::HipRollouts, epsilon, batch_
     end
     ph[1:n], eh[1:n], lh[1:n]
 end
+# ---- behaviour cloning (include/ppo_hip.h "behaviour cloning"; no reference op): supervised learning on the buffer's stored
+# actions (collect_paths! of a search's paths, or recorded action histories): -mean(w log pi(a|s)) plus the entropy term.
+# weights = :uniform (w = 1) or :positive_advantage (w = max(adv, 0), self-imitation) with advantage = :returns or :gae
+const IMITATE_WEIGHTS = Dict(:uniform => Int32(0), :positive_advantage => Int32(1))
+const IMITATE_ADV = Dict(:returns => Int32(0), :gae => Int32(2))
+function imitate_forward_backward(p::HipPolicy, r::HipRollouts, idx::Vector{Int64}; entropy_weight = 0.0, weights = :uniform,
+                                  advantage = :returns, B_global = length(idx))
+    check(ccall((:ppo_imitate_forward_backward, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Int64, Int64, Float64, Int32, Int32),
+                p.h, r.h, idx .- 1, length(idx), B_global, Float64(entropy_weight), IMITATE_WEIGHTS[weights], IMITATE_ADV[advantage]))
+    ce, el = Ref{Float64}(), Ref{Float64}()
+    check(ccall((:ppo_last_losses, LIB), Int32, (Ptr{Cvoid}, Ref{Float64}, Ref{Float64}), p.h, ce, el))
+    ce[], el[]
+end
+# the epoch loop of ppo_train! on that loss -> (ce_history, entropy_history, lr_history); never stops early, leaves
+# last_train_stats(p) what the latest ppo_train! left.  rank / world / hook as in ppo_train!
+function imitate_train!(p::HipPolicy, optimizer, r::HipRollouts, batch_size, num_epochs; entropy_weight = 0.0, weights = :uniform,
+                        advantage = :returns, rank = 0, world = 1, hook = C_NULL)
+    oh = opt_handle(optimizer)
+    ch, eh, lh = zeros(num_epochs), zeros(num_epochs), zeros(num_epochs)
+    status = ccall((:ppo_imitate_train, LIB), Int32,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Float64, Int32, Int32, Ptr{Int64}, UInt64, Int32, Int32,
+                    Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                   p.h, oh, r.h, batch_size, num_epochs, Float64(entropy_weight), IMITATE_WEIGHTS[weights], IMITATE_ADV[advantage],
+                   C_NULL, SEED[], rank, world, hook, C_NULL, ch, eh, lh)
+    opt_done!(optimizer)
+    check(status)
+    ch, eh, lh
+end
 # ---- update statistics (include/ppo_hip.h "update statistics"; no reference op): approx_kl = mean((r - 1) - log r),
 # old_approx_kl = mean(-log r) and clip_fraction = mean(|r - 1| > epsilon) of every epoch of the latest ppo_train!, and the
 # target-KL stop: ppo_train! ends after the first epoch whose approx_kl exceeds target_kl (nothing / 0 = off, Inf = record only)

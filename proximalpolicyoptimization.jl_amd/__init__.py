@@ -61,6 +61,7 @@ __all__ = [
     "check_internal", "best_states_", "best_state_in_rollout", "single_trajectory_scores", "count_non_flips",
     "search_best_states_", "search_resample_states_", "check_resample", "apply_paths_", "check_paths",
     "collect_paths_",
+    "imitate_forward_backward", "imitate_train_", "imitation_loss",
 ]
 
 
@@ -544,6 +545,28 @@ def value_loss_clipped(values, old_values, targets, clip):
         keep = (np.abs(delta) <= c) | (np.abs(d) >= np.abs(dc))
     term = np.where(keep, d, dc).astype(np.float32)
     return float(np.mean(term * term, dtype=np.float32))
+
+
+def imitation_loss(logits, mask, actions, weights=None):
+    """The imitation (behaviour-cloning) loss column 0 on given logits, in float32 arithmetic as the device forms it (plain
+    numpy host mirror, for users of the generic path) -> float: -mean_i(w_i log pi(a_i | s_i)), log pi the log-softmax over
+    the actions of active quads, (l[a] - max l) - log sum exp(l - max l), finite where exp underflows.  logits [B, A]; mask:
+    [B, A] bools (True = allowed), or the [B] active-quad bit masks (action k belongs to quad k // 16); actions [B] 0-based,
+    each allowed; weights [B] (None: 1), clamped at 0 like the device's max(adv, 0)."""
+    l = np.asarray(logits, np.float32)
+    B, A = l.shape
+    m = np.asarray(mask)
+    if m.ndim == 1:
+        bits = m.astype(np.uint32)
+        m = ((bits[:, None] >> (np.arange(A) // 16).astype(np.uint32)[None, :]) & 1).astype(bool)
+    m = m.astype(bool)
+    a = np.asarray(actions, np.int64)
+    w = np.ones(B, np.float32) if weights is None else np.maximum(np.asarray(weights, np.float32), np.float32(0))
+    lm = np.where(m, l, np.float32(-np.inf))
+    mx = lm.max(axis=1)
+    S = np.where(m, np.exp(l - mx[:, None], dtype=np.float32), np.float32(0)).sum(axis=1, dtype=np.float32)
+    logp = (l[np.arange(B), a] - mx) - np.log(S, dtype=np.float32)
+    return float(-np.mean(w * logp, dtype=np.float32))
 
 
 # ------------------------------------------------------------------ optimiser
@@ -1461,6 +1484,65 @@ def ppo_train_(policy, optimizer, dataset, epsilon, batch_size, num_epochs, entr
         for e in range(ran.value):                                                          # :146
             print("EPOCH : %d \t PPO LOSS : %1.4f\t ENTROPY LOSS : %1.4f \t LR : %1.1e" % (e + 1, ph[e], eh[e], lh[e]))
     return list(ph), list(eh), list(lh)                     # lr = get_optimizer_learning_rate per epoch (:144)
+
+
+IMITATION_WEIGHTS = {"uniform": 0, "positive_advantage": 1}
+
+
+def _imitation_modes(weights, advantage):
+    """(weight_mode, adv_mode) of the imitation entry points: an unknown `weights` and the normalised advantage modes
+    (the weights are max(advantage, 0) of a buffer column as it is) are refused like the library refuses them."""
+    if weights not in IMITATION_WEIGHTS:
+        raise PPOError(-4, "imitation weights must be one of %s" % sorted(IMITATION_WEIGHTS))
+    a = _adv_mode(advantage)
+    if advantage.endswith("_normalised"):
+        raise PPOError(-4, "imitation: the normalised advantage modes are not supported")
+    return IMITATION_WEIGHTS[weights], a
+
+
+def imitate_forward_backward(policy, dataset, batch_indices, entropy_weight=0.0, weights="uniform", advantage="returns",
+                             B_global=None):
+    """Gradient (no update) of the behaviour-cloning loss on dataset[batch_indices] (1-based): the cross-entropy
+    -(1 / B_global) sum w log pi(a | s) of the stored actions plus the entropy term of ppo_loss_with_entropy; leaves it in
+    policy.grad() and returns (cross_entropy, entropy_weight * entropy loss).  weights: "uniform" (w = 1) or
+    "positive_advantage" (w = max(adv, 0), self-imitation), adv the column `advantage` names: "returns", or "gae" after a
+    GAE call on these rollouts.  p_old is not read."""
+    wm, am = _imitation_modes(weights, advantage)
+    ii = np.ascontiguousarray(np.asarray(batch_indices, np.int64) - 1)
+    call("ppo_imitate_forward_backward", policy._h, dataset.rollouts._h, _p(ii, _lib.c_i64p), ii.size,
+         int(B_global or ii.size), float(entropy_weight), wm, am)
+    a, b = C.c_double(0), C.c_double(0)
+    call("ppo_last_losses", policy._h, C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+def imitate_train_(policy, optimizer, dataset, batch_size, num_epochs, entropy_weight=0.0, weights="uniform",
+                   advantage="returns", perm=None, seed=0, parallel=None, verbose=True):
+    """ppo_train_'s epoch loop on the behaviour-cloning loss (imitate_forward_backward) -> (ce_history, entropy_history,
+    lr_history), num_epochs entries each: policy.target_kl is not read, the call never stops early and leaves
+    policy.last_train_stats() what the latest ppo_train_ left.  perm, seed and parallel as in ppo_train_."""
+    wm, am = _imitation_modes(weights, advantage)
+    oh = optimizer._handle(policy)
+    n = len(dataset)
+    pp = _perm0(perm, num_epochs, n)
+    ch, eh, lh = (np.zeros(num_epochs, np.float64) for _ in range(3))
+    rank, world, fn, keep = 0, 1, _lib.ALLREDUCE_FN(0), None
+    if parallel is not None and (parallel.world > 1 or parallel.force_hook):
+        rank, world = parallel.rank, parallel.world
+        keep = parallel.make_hook(policy)
+        fn = keep
+    if world == 1:                                         # else inside the library, on the shortest shard (see ppo_train_)
+        _check_batch_size(batch_size, n)
+    try:
+        call("ppo_imitate_train", policy._h, oh, dataset.rollouts._h, int(batch_size), int(num_epochs), float(entropy_weight),
+             wm, am, _p(pp, _lib.c_i64p) if pp is not None else None, int(seed), int(rank), int(world), fn, None,
+             _p(ch, _lib.c_f64p), _p(eh, _lib.c_f64p), _p(lh, _lib.c_f64p))
+    finally:
+        optimizer._pull()
+    if verbose:
+        for e in range(num_epochs):
+            print("EPOCH : %d \t CE LOSS : %1.4f\t ENTROPY LOSS : %1.4f \t LR : %1.1e" % (e + 1, ch[e], eh[e], lh[e]))
+    return list(ch), list(eh), list(lh)
 
 
 VALUE_TARGETS = {"returns": 0, "lambda_returns": 1}

@@ -122,6 +122,9 @@ SIGNATURES = {
     "ppo_step_batch": [H, H, H, c_i64p, C.c_int64, C.c_double, C.c_double, C.c_int32, c_f64p, c_f64p],
     "ppo_train": [H, H, H, C.c_double, C.c_int64, C.c_int32, C.c_double, C.c_int32, c_i64p, C.c_uint64, C.c_int32,
                   C.c_int32, ALLREDUCE_FN, C.c_void_p, c_f64p, c_f64p, c_f64p],
+    "ppo_imitate_forward_backward": [H, H, c_i64p, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_int32],
+    "ppo_imitate_train": [H, H, H, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_int32, c_i64p, C.c_uint64, C.c_int32,
+                          C.c_int32, ALLREDUCE_FN, C.c_void_p, c_f64p, c_f64p, c_f64p],
     "ppo_rollouts_attach_disk": [H, C.c_char_p, C.c_int32],
     "ppo_rollouts_detach_disk": [H],
     "ppo_set_disk_async": [C.c_int32],

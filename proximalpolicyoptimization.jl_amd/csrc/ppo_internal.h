@@ -402,8 +402,9 @@ struct PpoKnobs {
 const PpoKnobs& ppo_knobs();
 
 // What one training pass minimises: the policy's clipped PPO loss with its entropy bonus, or a critic's (a ppo_policy_t
-// read as a state value) Flux.mse against a target column.  TrainObjective: the loss inputs of one pass
-enum class Objective { Policy, Value };
+// read as a state value) Flux.mse against a target column, or the policy's cross-entropy on the buffer's actions (behaviour
+// cloning).  TrainObjective: the loss inputs of one pass
+enum class Objective { Policy, Value, Imitate };
 struct TrainObjective {
     Objective kind;
     // Policy
@@ -417,12 +418,15 @@ struct TrainObjective {
                                        // (train_pass_dev fills it and vclip from the critic handle and the buffer)
     float vclip = 0.0f;                // ... and the clip range
     float* vdelta_dst = nullptr;       // where the pass stores V - vold per state while the clip is set (nullptr: nowhere)
+    // Imitate (entropy_weight and adv_mode as for Policy; adv_mode names the weights' column, read in the weighted form only)
+    int32_t weight_mode = PPO_IMITATE_UNIFORM;
 };
 
 // The kernels that run one training minibatch.  TrainTile runs forward, loss and backward-data in one launch and is
 // always followed by Wgrad (k_policy_wgrad<TR = true>).  Objective::Value: the forward is always Fwd -- k_policy_fwd in a
 // value-train mode, the only forward with one -- followed by the backward the policy would take at that shape and size; where
 // that is the one-tile pass, whose weight-gradient kernel only runs from inside it, the three-product Small backward.
+// Objective::Imitate: likewise, k_policy_fwd in an imitation mode (12 / 13).
 enum class TrainFwd { None, TrainTile, X6S, X6T, X6, Split, Fwd, Bf16 };
 enum class TrainBwd { None, Wgrad, Small, X6, Fused, Bf16 };
 struct TrainRoute { TrainFwd fwd; TrainBwd bwd; const char* err; };      // err: why fwd is None
@@ -440,6 +444,10 @@ int32_t launch_value_predict(ppo_policy_s* p, const int8_t* states_dev, const in
                              const int8_t* tmpl_dev, int32_t V, int64_t B, int32_t H, float* values_dev);
 int32_t launch_value_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
                                const float* target_col, const float* vold_col, float vclip, float* vdelta_dst);
+// imitation train forward (ppo_policy_fwd.hip modes 12 / 13): cross-entropy of the buffer's actions, weighted by
+// max(weight_col[transition], 0) (nullptr: uniform weights), plus the policy's entropy term
+int32_t launch_imitate_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
+                                 double entropy_weight, const float* weight_col);
 // the same fused backward with its row contractions (dW2, dW1) as split-fp32 products on the bf16 matrix pipe
 // (ppo_policy_bwd_x6.hip)
 int32_t launch_policy_bwd_x6(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B);

@@ -58,12 +58,15 @@ static __device__ __forceinline__ void act_store_nt(float4* p, float4 v) {
 // allocation of k_policy_fwd<72,256,6,1,0> moved), outside the range of the parent's own runs; 6 / 8 are now the parent's code
 // 11: one teacher-forced step: MODE 1's forward and outputs with the action read from a.actions instead of
 // sampled (policy_tail's mode 11); an own mode for the same reason, MODE 1 is the parent's code
+// 12 / 13: imitation train forward: 2 / 4 with the cross-entropy of the stored action as the loss tail
+// (policy_tail's mode 12); own modes for the same reason, 2 / 4 are the parent's code
 constexpr bool fwd_mode_value(int m) { return m >= 5 && m <= 10; }
 constexpr bool fwd_mode_vclip(int m) { return m == 9 || m == 10; }
-constexpr bool fwd_mode_train(int m) { return m == 2 || m == 4 || m == 6 || m == 8 || fwd_mode_vclip(m); }   // saves activations, writes dY
-constexpr bool fwd_mode_gather(int m) { return m == 2 || m == 6 || m == 9; }             // expanded rows through idx
-constexpr bool fwd_mode_snap(int m) { return m == 4 || m == 7 || m == 8 || m == 10; }    // one env snapshot per state in LDS
-constexpr bool fwd_mode_snap_idx(int m) { return m == 4 || m == 8 || m == 10; }          // ... fetched through idx, rows -> xs_out
+constexpr bool fwd_mode_imitate(int m) { return m == 12 || m == 13; }
+constexpr bool fwd_mode_train(int m) { return m == 2 || m == 4 || m == 6 || m == 8 || fwd_mode_vclip(m) || fwd_mode_imitate(m); }   // saves activations, writes dY
+constexpr bool fwd_mode_gather(int m) { return m == 2 || m == 6 || m == 9 || m == 12; }  // expanded rows through idx
+constexpr bool fwd_mode_snap(int m) { return m == 4 || m == 7 || m == 8 || m == 10 || m == 13; }    // one env snapshot per state in LDS
+constexpr bool fwd_mode_snap_idx(int m) { return m == 4 || m == 8 || m == 10 || m == 13; }          // ... fetched through idx, rows -> xs_out
 
 template <int F, int HID>
 struct FwdCfg { static constexpr int WPS = (HID >= 256 || F > 128) ? 1 : PPO_FWD_WPS_SMALL; };
@@ -103,9 +106,10 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
     // (value-train from snapshots keeps half the train ring at two waves per SIMD: with 16 groups next to the row
     // re-derivation it does not fit the 256 registers)
     constexpr int PFV = (PFT < 8) ? PFT : 8;
-    constexpr int PF = (FwdCfg<F, HID>::WPS == 1) ? PFW : (TRAIN ? ((VALUE && SNAP) ? PFV : PFT) : 4);   // weight-fragment groups kept in flight per wave
+    // (the imitation forward from snapshots likewise: with 16 groups mode 13 spills where MODE 4 does, 196 / 60 / 116 bytes per lane)
+    constexpr int PF = (FwdCfg<F, HID>::WPS == 1) ? PFW : (TRAIN ? (((VALUE || fwd_mode_imitate(MODE)) && SNAP) ? PFV : PFT) : 4);   // weight-fragment groups kept in flight per wave
     constexpr bool OBS = (MODE == 3 || SNAP);           // the state rows are re-derived from an env snapshot in LDS
-    constexpr int TMODE = TRAIN ? 2 : MODE;             // policy_tail's mode
+    constexpr int TMODE = fwd_mode_imitate(MODE) ? 12 : (TRAIN ? 2 : MODE);   // policy_tail's mode
     static_assert(F % 8 == 0 && HID % 32 == 0, "shape");
     static_assert(PF * 64 * 4 <= PPO_PACK_PAD, "the ring reads PF groups past the end of a packed weight stream: padding must cover it");
     const int lane = threadIdx.x & 63;
@@ -217,6 +221,8 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
         // teacher-forced step: the state's given action, fetched here like the tick so that it has landed by the tail
         [[maybe_unused]] TailPre forced = {0, 0.0f, 0.0f};
         if constexpr (MODE == 11) forced.ab = a.actions[state];
+        // imitation: the stored action and its weight (a.adv == nullptr: uniform), ahead of the activation stores like vtarget
+        if constexpr (fwd_mode_imitate(MODE)) { forced.ab = a.actions[sid]; forced.adv = a.adv ? a.adv[sid] : 1.0f; }
         float l[TPS][4];
         // multi-tile states: the tile loop stays a real loop (no 4x code blow-up, no cross-tile hoisting that
         // would spill); the 4 logits per lane of each tile are parked in LDS and re-read after the loop
@@ -460,6 +466,7 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
         int sampled = 0;
         if constexpr (VALUE) value_tail<fwd_mode_vclip(MODE) ? 2 : (TRAIN ? 1 : 0), TPS>(a, state, act, l, lane, j, h, out_index, vtarget, vold);
         else if constexpr (MODE == 11) sampled = policy_tail<11, TPS, false>(a, state, sid, act, l, lane, j, h, 0u, out_index, &forced);
+        else if constexpr (fwd_mode_imitate(MODE)) sampled = policy_tail<12, TPS, false>(a, state, sid, act, l, lane, j, h, 0u, out_index, &forced);
         else sampled = policy_tail<TMODE, TPS, false>(a, state, sid, act, l, lane, j, h, tick_val, out_index);
         if (MODE == 3) {
             // update!: the observed mask, then step!(env, a), reward, is_terminal (src/collect_rollouts.jl:9-14) and the
@@ -741,6 +748,19 @@ int32_t launch_policy_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32
     case TrainFwd::Fwd: return ro->compact ? dispatch_fwd<4>(p, a, B, ro->H / 32) : dispatch_fwd<2>(p, a, B, ro->H / 32);
     default: return launch_policy_train_fwd_x6(p, a, B, form, ro->compact);               // ppo_policy_fwd_x6.hip
     }
+}
+
+// imitation train forward (modes 12 / 13): the policy's train forward with the cross-entropy of the buffer's actions as the loss;
+// weight_col: the weights' column by transition id, clamped at 0 in the tail (nullptr: uniform weights).  Only this fp32-MFMA
+// forward has the mode
+int32_t launch_imitate_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
+                                 double entropy_weight, const float* weight_col) {
+    FwdArgs a = {};
+    fill_train(p, ro, idx_dev, B, B_global, a);
+    a.actions = ro->actions.p; a.adv = weight_col;
+    a.c_over_B = (float)(entropy_weight / (double)B_global);
+    ProfScope ps("k_policy_fwd_imitate");
+    return !ro->compact ? dispatch_fwd<12>(p, a, B, ro->H / 32) : dispatch_fwd<13>(p, a, B, ro->H / 32);
 }
 
 // ---- critic (value modes 5 .. 8): only this fp32-MFMA forward has them

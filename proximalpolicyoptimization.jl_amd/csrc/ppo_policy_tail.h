@@ -106,6 +106,8 @@ struct TailPre { int ab; float po; float adv; };
 // MODE 1 / 3 (rollout): tick_val = the env's tick (Philox counter word), out_index = position of the transition in
 // the output columns (state for one step, t*N + state for the persistent rollout); returns the sampled action.
 // MODE 11 (teacher-forced step): the MODE 1 outputs for the action in pre->ab instead of a sampled one; returns it.
+// MODE 12 (imitation train forward, kernel MODES 12 / 13): MODE 2's outputs for the cross-entropy of the action in pre->ab,
+// weighted by max(pre->adv, 0); pre is required.
 // dy_copy (MODE 2, TPS == 1, optional): a second destination for the state's 32 dL/dlogits rows, e.g. an LDS tile of the
 // calling workgroup (k_policy_train_tile keeps the whole training pass of a tile on the CU).
 template <int MODE, int TPS, bool DYBF16>
@@ -231,6 +233,49 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
                 reinterpret_cast<float4*>(a.full_probs)[((size_t)out_index * TPS + ts) * 32 + j] =
                     make_float4(p[ts][0], p[ts][1], p[ts][2], p[ts][3]);
         }
+    }
+    if (MODE == 12) {
+        // behaviour cloning (kernel MODES 12 / 13): cross-entropy of the stored action, -w log pi(a|s), with MODE 2's
+        // entropy term.  pre: the caller's early fetch -- ab the 0-based action (on an active quad, MODE 2's precondition), adv
+        // the weight column's entry (1 for uniform weights); w = max(adv, 0).  log pi in the log-softmax form (l[a] - m) - log S
+        // and dL/dlogit_k = (w / B_global)(p_k - [k == a]) without a division by p[a]: both stay finite where exp(l[a] - m)
+        // underflows to 0, the searched action the current policy finds very unlikely.  No p_old, no clip, no ratio
+        const int ab = pre->ab;
+        const float w = fmaxf(pre->adv, 0.0f);
+        float cand = 0.0f;
+#pragma unroll
+        for (int ts = 0; ts < TPS; ++ts)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) cand = ((ab >> 7) == ts && (ab & 3) == i) ? l[ts][i] : cand;
+        const float la = __shfl(cand, (ab & 127) >> 2);
+        const float logp = (la - m) - logf(ssum);
+        const float sA = 1e-8f / (float)A;                                   // smooth/size(probs,1)  src/train.jl:22
+        float lg[TPS][4], hl = 0.0f;
+#pragma unroll
+        for (int ts = 0; ts < TPS; ++ts)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { const float sp = p[ts][i] + sA; lg[ts][i] = logf(sp); hl += sp * lg[ts][i]; }
+        hl = wave32_sum(hl);
+        float dpe[TPS][4], dot = 0.0f;
+#pragma unroll
+        for (int ts = 0; ts < TPS; ++ts)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { dpe[ts][i] = a.c_over_B * (lg[ts][i] + 1.0f); dot += p[ts][i] * dpe[ts][i]; }
+        dot = wave32_sum(dot);
+        const float wB = w * a.inv_B;
+        if (h == 0) {
+#pragma unroll
+            for (int ts = 0; ts < TPS; ++ts) {
+                float dy[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float pd = (128 * ts + 4 * j + i == ab) ? p[ts][i] - 1.0f : p[ts][i];       // p_k - [k == a]
+                    dy[i] = dy_round<DYBF16>(wB * pd + p[ts][i] * (dpe[ts][i] - dot));
+                }
+                a.dY[((size_t)state * TPS + ts) * 32 + j] = make_float4(dy[0], dy[1], dy[2], dy[3]);
+            }
+        }
+        if (lane == 0) { a.loss_terms[state * 2] = (double)(w * logp); a.loss_terms[state * 2 + 1] = (double)(-hl); }
     }
     if (MODE == 2) {
         const int ab = pre ? pre->ab : a.actions[sid];

@@ -43,11 +43,13 @@ int32_t ppo_set_rollout_split_max_envs(int64_t envs) { g_knobs.rollout_split_max
 }  // extern "C"
 
 TrainRoute train_route(int32_t dtype, int F, int HID, int L, int H, bool compact, int64_t states, const PpoKnobs& k, Objective obj) {
-    const bool f32 = dtype == PPO_DTYPE_F32, value = obj == Objective::Value;
+    // (value: the objectives only the fp32-MFMA forward has a tail for -- a critic's mse and the imitation cross-entropy)
+    const bool f32 = dtype == PPO_DTYPE_F32, value = obj != Objective::Policy;
     const int tps = H / 32;
     const int64_t tiles = states * tps;
     const bool split_images = F == 72 && L == 2;        // the policy holds the split-fp32 weight images (ppo_policy_create)
     if (value) {                                        // what the fp32-MFMA forward refuses, before anything else
+        if (!f32 && obj == Objective::Imitate) return {TrainFwd::None, TrainBwd::None, "imitation training of a bf16-dtype policy is not supported: the imitation modes exist in the fp32-MFMA forward only"};
         if (!f32) return {TrainFwd::None, TrainBwd::None, "a bf16-dtype critic is not supported: the value modes exist in the fp32-MFMA forward only"};
         if (F != 72 && tps != 1) return {TrainFwd::None, TrainBwd::None, "unsupported policy/state shape (F,HID,H) for the gfx950 kernels"};
         if (F != 72 && compact) return {TrainFwd::None, TrainBwd::None, "compact rollouts need the built-in env's F = 72"};
@@ -93,8 +95,8 @@ static int32_t debug_route(const char* who, Objective obj, int32_t dtype, int32_
               std::string(who) + ": shape");
     ARG_CHECK(fwd && bwd && cap >= 64, std::string(who) + ": output buffers");
     const TrainRoute r = train_route(dtype, F, hid, L, H, compact != 0, states, ppo_knobs(), obj);
-    // k_policy_fwd's train modes: 2 rows / 4 snapshots through idx; the value-train modes 6 / 8 likewise
-    const int tps = H / 32, mode = (obj == Objective::Value ? 6 : 2) + (compact ? 2 : 0);
+    // k_policy_fwd's train modes: 2 rows / 4 snapshots through idx; the value-train modes 6 / 8 and the imitation modes 12 / 13 likewise
+    const int tps = H / 32, mode = obj == Objective::Imitate ? (compact ? 13 : 12) : (obj == Objective::Value ? 6 : 2) + (compact ? 2 : 0);
     switch (r.fwd) {
     case TrainFwd::None: snprintf(fwd, cap, "none"); break;
     case TrainFwd::TrainTile: snprintf(fwd, cap, "k_policy_train_tile<72,%d>", hid); break;
@@ -125,4 +127,8 @@ extern "C" int32_t ppo_debug_train_route(int32_t dtype, int32_t F, int32_t hid, 
 extern "C" int32_t ppo_debug_value_route(int32_t dtype, int32_t F, int32_t hid, int32_t L, int32_t H, int32_t compact,
                                          int64_t states, char* fwd, char* bwd, int64_t cap) {
     return debug_route("ppo_debug_value_route", Objective::Value, dtype, F, hid, L, H, compact, states, fwd, bwd, cap);
+}
+extern "C" int32_t ppo_debug_imitate_route(int32_t dtype, int32_t F, int32_t hid, int32_t L, int32_t H, int32_t compact,
+                                           int64_t states, char* fwd, char* bwd, int64_t cap) {
+    return debug_route("ppo_debug_imitate_route", Objective::Imitate, dtype, F, hid, L, H, compact, states, fwd, bwd, cap);
 }

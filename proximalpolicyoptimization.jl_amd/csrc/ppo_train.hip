@@ -1,6 +1,6 @@
 // ppo_train.hip -- the training half of the extern "C" surface (include/ppo_hip.h): one minibatch pass and one epoch loop,
-// driven for the policy (step_batch! / ppo_train!) and for a critic (value_forward_backward / value_train), and the
-// critic's state values and GAE.  Host orchestration only: launch order, all math is in the kernels.
+// driven for the policy (step_batch! / ppo_train!), for a critic (value_forward_backward / value_train) and for the policy's
+// imitation objective (imitate_forward_backward / imitate_train), and the critic's state values and GAE.  Host orchestration only: launch order, all math is in the kernels.
 #include "ppo_internal.h"
 #include <algorithm>
 #include <cmath>
@@ -25,13 +25,33 @@ static int32_t train_reserve(ppo_policy_s* p, int64_t B, bool compact = false) {
     return PPO_OK;
 }
 
+// batch_advantage: the column (by transition id) adv_mode selects for a minibatch -- the PPO surrogate's advantages, and the
+// weights of the weighted imitation loss
+static int32_t advantage_column(ppo_policy_s* net, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int32_t adv_mode,
+                                const float** col) {
+    const float* adv = ro->returns.p;                       // batch_advantage = returns (reference-equivalent)
+    if (adv_mode == PPO_ADV_GAE || adv_mode == PPO_ADV_GAE_NORMALISED) {
+        ARG_CHECK(ro->adv.p && ro->adv_T == ro->T, "batch_advantage: GAE mode needs ppo_rollouts_compute_gae on these rollouts first");
+        adv = ro->adv.p;
+    }
+    if (adv_mode == PPO_ADV_RETURNS_NORMALISED || adv_mode == PPO_ADV_GAE_NORMALISED) {   // normalised over this rank's minibatch
+        PPO_TRY(net->adv_col.alloc((size_t)ro->capT * ro->N));
+        PPO_TRY(launch_adv_normalise(adv, idx_dev, B, net->adv_col.p));
+        adv = net->adv_col.p;
+    }
+    *col = adv;
+    return PPO_OK;
+}
+
 // One minibatch: train forward, backward, slab reduction (+ the optimiser step when fuse_opt is given).
 // idx_dev: transition ids (already resolved through the dataset index)
 static int32_t train_pass_dev(ppo_policy_s* net, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
                               const TrainObjective& obj, ppo_adam_s* fuse_opt = nullptr, float* fuse_hist2 = nullptr) {
     PPO_TRY(train_reserve(net, B * (ro->H / 32), ro->compact));
-    const bool policy = obj.kind == Objective::Policy;
-    const float* adv = ro->returns.p;                       // batch_advantage = returns (reference-equivalent)
+    const bool policy = obj.kind == Objective::Policy, imitate = obj.kind == Objective::Imitate;
+    const float* adv = nullptr;                             // imitation with uniform weights: no column
+    if (policy || (imitate && obj.weight_mode == PPO_IMITATE_POSITIVE_ADVANTAGE))
+        PPO_TRY(advantage_column(net, ro, idx_dev, B, obj.adv_mode, &adv));
     if (policy) {
         // the tail's probability ratios, stored while a target_kl is set only (measured: the store costs the train forward
         // 0.2 %, more than the run-to-run spread of the benchmark): the caller's slice of an epoch column (train_epochs), else
@@ -39,15 +59,6 @@ static int32_t train_pass_dev(ppo_policy_s* net, ppo_rollouts_s* ro, const int32
         const bool keep_ratio = net->target_kl != 0.0;
         net->ratio_out = !keep_ratio ? nullptr : obj.ratio_dst ? obj.ratio_dst : net->ratio.p;
         if (keep_ratio && !obj.ratio_dst) { net->ratio_last = net->ratio.p; net->ratio_last_n = (int64_t)net->ratio.n; }
-        if (obj.adv_mode == PPO_ADV_GAE || obj.adv_mode == PPO_ADV_GAE_NORMALISED) {
-            ARG_CHECK(ro->adv.p && ro->adv_T == ro->T, "batch_advantage: GAE mode needs ppo_rollouts_compute_gae on these rollouts first");
-            adv = ro->adv.p;
-        }
-        if (obj.adv_mode == PPO_ADV_RETURNS_NORMALISED || obj.adv_mode == PPO_ADV_GAE_NORMALISED) {   // normalised over this rank's minibatch
-            PPO_TRY(net->adv_col.alloc((size_t)ro->capT * ro->N));
-            PPO_TRY(launch_adv_normalise(adv, idx_dev, B, net->adv_col.p));
-            adv = net->adv_col.p;
-        }
     }
     const TrainRoute r = train_route(net->dtype, net->F, net->HID, net->L, ro->H, ro->compact, B, ppo_knobs(), obj.kind);
     if (r.fwd == TrainFwd::None) { ppo_set_error(r.err); return PPO_ERR_UNSUPPORTED; }
@@ -57,7 +68,8 @@ static int32_t train_pass_dev(ppo_policy_s* net, ppo_rollouts_s* ro, const int32
         if (net->L >= 2) PPO_TRY(net->dz2f.alloc(frag));
         if (net->L > 2) PPO_TRY(net->dzm.alloc((size_t)(net->L - 2) * frag));
     }
-    if (!policy) {
+    if (imitate) PPO_TRY(launch_imitate_train_fwd(net, ro, idx_dev, B, B_global, obj.entropy_weight, adv));
+    else if (!policy) {
         // PPO's clipped value loss while the critic handle has a clip range: against the buffer's values of before the update
         // (the callers have checked that they are there), V - vold going to the caller's slice of an epoch column if any
         TrainObjective o = obj;
@@ -227,7 +239,8 @@ static int32_t sum_rank_sums(double* st, int k, DevBuf<float>& sx, int32_t rank,
 // permutation of the dataset in minibatches of batch_size, an optimiser step after each.  hist0 / hist1: per-epoch means of
 // the two per-batch loss columns (ppo and entropy loss; a critic's mse is column 0).  world > 1: data-parallel, through the
 // all-reduce hook.  Objective::Policy adds the per-epoch ratio statistics and the target_kl stop, Objective::Value the per-epoch
-// value-clip statistics while the critic handle has a value clip; with world > 1 either kind is summed over the ranks
+// value-clip statistics while the critic handle has a value clip; with world > 1 either kind is summed over the ranks.
+// Objective::Imitate keeps no statistics of either kind, leaves the handle's as they are and never stops early
 static int32_t train_epochs(ppo_policy_s* net, ppo_adam_s* opt, ppo_rollouts_s* ro, const TrainObjective& obj, int64_t batch_size,
                             int32_t num_epochs, const int64_t* perm, uint64_t seed, int32_t rank, int32_t world,
                             ppo_allreduce_fn allreduce, void* allreduce_ctx, double* hist0, double* hist1, double* lr_hist) {
@@ -252,8 +265,9 @@ static int32_t train_epochs(ppo_policy_s* net, ppo_adam_s* opt, ppo_rollouts_s* 
     const bool policy = obj.kind == Objective::Policy;
     // likewise for a critic while a value clip is set: V - vold of every minibatch in its slice of one column, one reduction per
     // epoch (count(|delta| > c), sum delta^2, n).  value_clip == 0: nothing is allocated, stored, launched or copied
-    const bool vstats = !policy && net->value_clip != 0.0;
-    if (!policy) {
+    const bool value = obj.kind == Objective::Value;
+    const bool vstats = value && net->value_clip != 0.0;
+    if (value) {
         if (vstats) {
             if (net->vdelta_col.n < (size_t)len) net->vdelta_n = 0;
             PPO_TRY(net->vdelta_col.alloc((size_t)len));
@@ -321,11 +335,11 @@ static int32_t train_epochs(ppo_policy_s* net, ppo_adam_s* opt, ppo_rollouts_s* 
         if (hist0) hist0[ep] = s0 / (double)nb;                                     // unweighted mean over batches :127
         if (hist1) hist1[ep] = s1 / (double)nb;
         if (lr_hist) lr_hist[ep] = opt->lr();                                       // :144,155-158
-        if (!policy) {
+        if (value) {
             if (world > 1 && vstats) PPO_TRY(sum_rank_sums(vst, 3, sx, rank, world, allreduce, allreduce_ctx, "value-clip statistics"));
             net->vstats_clip.push_back(vst[0] / vst[2]); net->vstats_msq.push_back(vst[1] / vst[2]);
-            continue;
         }
+        if (!policy) continue;
         if (world > 1 && target_kl > 0) PPO_TRY(sum_rank_sums(st, 4, sx, rank, world, allreduce, allreduce_ctx, "ratio statistics"));
         const double kl = st[1] / st[3];
         net->stats_kl.push_back(kl); net->stats_old_kl.push_back(st[0] / st[3]); net->stats_clip.push_back(st[2] / st[3]);
@@ -356,6 +370,50 @@ int32_t ppo_train(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, double ep
                         entropy_hist, lr_hist);
 }
 
+
+// ---- behaviour cloning (no reference op): the policy's cross-entropy on the buffer's actions
+// what both entry points check of their two mode arguments: the weights' column is read in the weighted form only
+static int32_t imitate_modes(int32_t weight_mode, int32_t adv_mode) {
+    if (weight_mode != PPO_IMITATE_UNIFORM && weight_mode != PPO_IMITATE_POSITIVE_ADVANTAGE) { ppo_set_error("imitation: unknown weight mode"); return PPO_ERR_UNSUPPORTED; }
+    if (adv_mode < PPO_ADV_RETURNS || adv_mode > PPO_ADV_GAE_NORMALISED) { ppo_set_error("batch_advantage: unknown advantage mode"); return PPO_ERR_UNSUPPORTED; }
+    if (adv_mode == PPO_ADV_RETURNS_NORMALISED || adv_mode == PPO_ADV_GAE_NORMALISED) {
+        ppo_set_error("imitation: the weights are max(advantage, 0) of the returns or the GAE column; the normalised advantage modes are not supported");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    return PPO_OK;
+}
+
+int32_t ppo_imitate_forward_backward(ppo_policy_t pol, ppo_rollouts_t ro, const int64_t* sample_idx, int64_t B, int64_t B_global,
+                                     double entropy_weight, int32_t weight_mode, int32_t adv_mode) {
+    ARG_CHECK(pol && ro && sample_idx, "imitate_forward_backward: null argument");
+    ARG_CHECK(B >= 1 && B <= ro->len, "imitate_forward_backward: 1 <= batch_size <= num_data (src/train.jl:88)");
+    ARG_CHECK(B_global >= B, "imitate_forward_backward: B_global < B");
+    ARG_CHECK(pol->F == ro->F && (ro->H == 32 || ro->H == 128), "imitate_forward_backward: shape mismatch");
+    PPO_TRY(imitate_modes(weight_mode, adv_mode));
+    DevBuf<int64_t> pos;
+    PPO_TRY(gather_minibatch(pol, ro, sample_idx, B, pos));
+    TrainObjective obj = {Objective::Imitate};
+    obj.entropy_weight = entropy_weight; obj.adv_mode = adv_mode; obj.weight_mode = weight_mode;
+    PPO_TRY(train_pass_dev(pol, ro, pol->idx.p, B, B_global, obj));
+    HIP_TRY(hipStreamSynchronize(ppo_stream()));
+    return PPO_OK;
+}
+
+int32_t ppo_imitate_train(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, int64_t batch_size, int32_t num_epochs,
+                          double entropy_weight, int32_t weight_mode, int32_t adv_mode, const int64_t* perm, uint64_t seed,
+                          int32_t rank, int32_t world, ppo_allreduce_fn allreduce, void* allreduce_ctx, double* ce_hist,
+                          double* entropy_hist, double* lr_hist) {
+    ARG_CHECK(pol && opt && ro && opt->pol == pol, "imitate_train!: null/mismatched argument");
+    ARG_CHECK(num_epochs >= 0 && world >= 1 && rank >= 0 && rank < world, "imitate_train!: bad epochs/rank/world");
+    ARG_CHECK(world == 1 || allreduce, "imitate_train!: world > 1 needs an all-reduce hook");
+    ARG_CHECK(pol->F == ro->F && (ro->H == 32 || ro->H == 128), "imitate_train!: shape mismatch");
+    ARG_CHECK(batch_size >= 1, "1 <= batch_size <= num_data (src/train.jl:88)");
+    PPO_TRY(imitate_modes(weight_mode, adv_mode));
+    TrainObjective obj = {Objective::Imitate};
+    obj.entropy_weight = entropy_weight; obj.adv_mode = adv_mode; obj.weight_mode = weight_mode;
+    return train_epochs(pol, opt, ro, obj, batch_size, num_epochs, perm, seed, rank, world, allreduce, allreduce_ctx, ce_hist,
+                        entropy_hist, lr_hist);
+}
 
 // ---- per-epoch KL / clip-fraction statistics and target-KL early stopping (no reference op)
 int32_t ppo_policy_set_target_kl(ppo_policy_t pol, double target_kl) {

@@ -1,0 +1,128 @@
+"""Behaviour cloning across two data-parallel ranks on ONE GPU (gloo for the exchange, like tests/test_gpu_value_two_ranks.py):
+imitate_train_(..., parallel=) on shards of unequal length -- replicas bit-identical, histories equal on both ranks, and the
+parameters those of the single-rank float64 schedule on the union of the shards.
+
+The two rank processes are started ONCE for the module and joined against a deadline: a missed collective ends the children
+and fails the tests, it cannot hang them."""
+import os
+import socket
+import time
+from datetime import timedelta
+
+import numpy as np
+import pytest
+
+import imitation_ref as ref
+from test_gpu_imitation import ETA, schedule_bars
+
+pytestmark = pytest.mark.gpu
+
+F, HID, LAYERS = 72, 128, 2
+DEADLINE = 120.0                                # seconds for both ranks
+BATCH = 40                                      # 14 + 13 envs, 6 steps: 84 / 78 samples -> steps of 40+40, 40+38 and 4+0 samples
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _rank_main(rank, world, port, base):
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import torch
+    import torch.distributed as dist
+    import ppo_amd as P
+    dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world,
+                            timeout=timedelta(seconds=DEADLINE))
+    torch.cuda.set_device(0)
+    dp = P.DataParallel(rank, world)
+    off, n = dp.env_shard(27)
+    env = P.HipVecEnv(num_envs=n, Q=8, max_actions=10, seed=5, global_offset=off)
+    pol = P.HipPolicy(F, HID, LAYERS, 4, seed=3)
+    ro = P.BufferRollouts()
+    P.collect_rollouts_steps_(ro, env, pol, 6, 1.0)
+    ds = P.construct_dataset(ro)
+    p0 = pol.params.copy()
+    perm = np.stack([np.arange(len(ds)) + 1] * 2)
+    ch, eh, lh = P.imitate_train_(pol, P.Optimiser(P.Adam(ETA)), ds, BATCH, 2, perm=perm, parallel=dp, verbose=False)
+    try:                                        # above the SHORTEST shard: refused on every rank alike, nobody left waiting
+        P.imitate_train_(pol, P.Optimiser(P.Adam(ETA)), ds, 80, 1, parallel=dp, verbose=False)
+        bad = ""
+    except P.PPOError as e:
+        bad = str(e)
+    st, act = ro.state_data
+    np.savez(base + "_rank%d.npz" % rank, ch=ch, eh=eh, lh=lh, params=pol.params, p0=p0, bad=bad, index=ro.index(), n=len(ds),
+             st=st.reshape(-1, 32, F), act=act.reshape(-1), a0=ro.selected_actions.reshape(-1) - 1)
+    torch.cuda.synchronize()
+    dist.destroy_process_group()
+
+
+@pytest.fixture(scope="module")
+def P(ppo):
+    if ppo.device_count() < 1:
+        pytest.fail("no HIP device: the gpu-marked tests must run on the GPU box")
+    return ppo
+
+
+@pytest.fixture(scope="module")
+def ranks(P, tmp_path_factory):
+    import torch.multiprocessing as mp
+    base = str(tmp_path_factory.mktemp("idp") / "dp")
+    ctx = mp.spawn(_rank_main, args=(2, _free_port(), base), nprocs=2, join=False)
+    end = time.monotonic() + DEADLINE
+    why = None
+    try:
+        while not ctx.join(timeout=1.0):
+            if time.monotonic() > end:
+                why = "the rank processes did not finish within %d s (a missed collective?)" % DEADLINE
+                break
+    except Exception as e:                      # noqa: BLE001 -- a rank raised: reported by the test
+        why = "a rank process failed: %s" % e
+    finally:
+        for p in ctx.processes:
+            if p.is_alive():
+                p.terminate()
+            p.join(10)
+    files = [base + "_rank%d.npz" % r for r in (0, 1)]
+    if why or not all(os.path.isfile(f) for f in files):
+        pytest.fail(why or "the ranks left no results")
+    return [np.load(f) for f in files]
+
+
+def test_two_unequal_shards(P, ranks):
+    """Same number of collectives on both ranks although one runs out of samples; every step's gradient is the mean over the
+    samples both contributed: histories and parameters against a float64 replay of the union batches with Flux.Adam."""
+    r0, r1 = ranks
+    assert (int(r0["n"]), int(r1["n"])) == (84, 78)
+    assert np.array_equal(r0["params"], r1["params"]), "replicas must hold bit-identical parameters after training"
+    for k in ("ch", "eh", "lh"):
+        assert np.array_equal(r0[k], r1[k]) and r0[k].shape == (2,), k
+    assert np.array_equal(r0["p0"], r1["p0"]) and not r0["eh"].any()
+    for r in (r0, r1):
+        assert "batch_size" in str(r["bad"]), str(r["bad"])
+        assert np.array_equal(r["index"], np.arange(int(r["n"]))), "storage order is dataset order here"
+    p = np.asarray(r0["p0"], np.float64)
+    m, v, bp = np.zeros_like(p), np.zeros_like(p), [0.9, 0.999]
+    hist = []
+    for ep in range(2):
+        losses = []
+        for b in range(3):
+            sel = [slice(BATCH * b, min(BATCH * (b + 1), int(r["n"]))) for r in (r0, r1)]
+            cat = lambda k: np.concatenate([r[k][s] for r, s in zip((r0, r1), sel)])      # noqa: E731
+            assert len(cat("act")) == (80, 78, 4)[b]
+            ce, _, g, _ = ref.loss_grad(p, F, HID, LAYERS, cat("st"), cat("act"), cat("a0"), np.ones(len(cat("act"))))
+            losses.append(ce)
+            m = 0.9 * m + 0.1 * g
+            v = 0.999 * v + 0.001 * g * g
+            p = p - m / (1 - bp[0]) / (np.sqrt(v / (1 - bp[1])) + 1e-8) * ETA
+            bp = [bp[0] * 0.9, bp[1] * 0.999]
+        hist.append(float(np.mean(losses)))
+    ok, fig = schedule_bars(r0["params"], p, r0["ch"], hist, 6)
+    print("unequal shards: ce history", r0["ch"].tolist(), "float64 replay", hist, fig)
+    assert ok, fig
+    assert r0["ch"][-1] < r0["ch"][0] and hist[-1] < hist[0]
