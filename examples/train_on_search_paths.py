@@ -23,6 +23,12 @@ A path that ends short of the optimum is a truncation (terminal flag set on its 
 GAE bootstrapped from the critic's value of the state the path was cut in (compute_gae_critic_(..., bootstrap_truncated=True);
 lambda 0.95 for --loss ppo, 1 for --loss sil).
 
+--temperature sets the policy's selection for the SEARCH step alone (with PPO.selecting(policy, "sample", tau): ...): the K
+clones of a start sample from softmax(logits / tau), so a temperature above 1 keeps them apart once training has sharpened the
+policy, and one below 1 focuses an untrained one.  collect_paths_ and the training calls never read the selection: p_old and
+the loss stay those of the untempered policy.  Each round also scores the policy's mode, the greedy roll-out
+(selecting(policy, "greedy")), next to the sampled return.
+
 This script shows the calls and prints what it measures each round (the mean gap the search reaches, the transitions
 collected, the losses, the mean return of the plain stochastic policy).  Whether the loop learns faster or better than
 ppo_iterate_ on sampled rollouts, and which --loss serves it best, has not been measured; the script makes no such claim.
@@ -45,6 +51,8 @@ def main():
     ap.add_argument("--critic", action="store_true", help="GAE advantage from a device critic, bootstrapped where a path was cut")
     ap.add_argument("--loss", choices=("ppo", "clone", "sil"), default="clone",
                     help="clone: cross-entropy on the paths' actions; sil: weighted by max(advantage, 0); ppo: the clipped surrogate")
+    ap.add_argument("--temperature", type=float, default=1.0,
+                    help="selection temperature of the search step (1: the policy's own distribution; > 1 flatter, < 1 sharper)")
     args = ap.parse_args()
 
     discount, epsilon, entropy_weight, max_actions = 1.0, 0.05, 0.01, 32
@@ -61,7 +69,8 @@ def main():
         fresh = PPO.HipVecEnv(num_envs=args.starts, Q=8, max_actions=max_actions, seed=1000 + r)   # this round's reset states
         st = fresh.internal()
         starts = (st["score"], st["degree"], fresh.active_quads())
-        found = PPO.search_best_states_(search_env, policy, *starts, args.clones, path=True)
+        with PPO.selecting(policy, "sample", args.temperature):               # the search alone; restored behind it
+            found = PPO.search_best_states_(search_env, policy, *starts, args.clones, path=True)
         PPO.collect_paths_(rollouts, env, policy, *starts, found["path"], discount)
         dataset = PPO.construct_dataset(rollouts)
         n = len(dataset)
@@ -85,7 +94,9 @@ def main():
             vh, _ = PPO.value_train_(critic, critic_optimizer, dataset, min(1024, n), 2, target="lambda_returns", seed=r, verbose=False)
             line += ", value loss %.4f, %d cut paths" % (vh[-1], rollouts.n_truncated)
         ret, dev = PPO.average_returns(policy, eval_env, 1024)
-        print(line + "; stochastic policy: mean return %.3f (std %.3f)" % (ret, dev))
+        with PPO.selecting(policy, "greedy"):
+            gret, _ = PPO.average_returns(policy, eval_env, 1024)
+        print(line + "; stochastic policy: mean return %.3f (std %.3f), greedy %.3f" % (ret, dev, gret))
     return policy
 
 

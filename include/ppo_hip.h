@@ -699,6 +699,27 @@ int32_t ppo_collect_paths(ppo_rollouts_t ro, ppo_env_t env, ppo_policy_t pol, in
                           const int8_t* degree, const uint32_t* active, const int16_t* paths, int64_t stride,
                           double discount, int32_t discount_is_f32, int32_t record_probs);
 
+/* Action selection of the calls that APPLY a policy (no reference op).  A policy handle carries a selection
+ * (rule, temperature), default (PPO_SELECT_SAMPLE, 1.0), which is what every call did before the setter existed.  Per step, on
+ * the logits l the forward holds in front of its softmax:
+ *     inv = (float)(1.0 / temperature);  l' = l * inv (one fp32 multiply per logit);  p = the masked softmax of l';
+ *     PPO_SELECT_SAMPLE: a = rand(Categorical(p)), the same inverse-CDF walk on the same Philox uniform of (global env id, tick);
+ *     PPO_SELECT_GREEDY: a = argmax(p), the LOWEST action index among the largest p (Julia's argmax); no random number is drawn;
+ *     p_sel = p[a], the tempered probability.
+ * Greedy with temperature != 1 is allowed and is defined on the tempered p.  Ticks and episode counters move as they always do.
+ * READ by: ppo_average_returns / _best_returns / _normalized_returns, ppo_evaluate_trajectories, ppo_best_states(_actions),
+ * ppo_search_best_states(_path), ppo_search_resample_states(_path, _value).  (With a non-default selection ppo_average_returns
+ * is the mean / std of ppo_evaluate_trajectories kind 1, the same statistic.)
+ * NOT READ by: ppo_collect_rollouts, _episodes, _steps, ppo_collect_paths, ppo_policy_forward and every training call -- a
+ * rollout buffer's p_old must be the probability under the distribution the training pass differentiates, which is the
+ * untempered softmax.
+ * PPO_ERR_ARG: an unknown rule; a temperature that is NaN, infinite or <= 0.  The setter makes no device call.  A bf16-dtype
+ * policy keeps the default only: a reading call returns PPO_ERR_UNSUPPORTED while another selection is set. */
+#define PPO_SELECT_SAMPLE 0
+#define PPO_SELECT_GREEDY 1
+int32_t ppo_policy_set_selection(ppo_policy_t pol, int32_t rule, double temperature);
+int32_t ppo_policy_get_selection(ppo_policy_t pol, int32_t* rule, double* temperature);
+
 /* timing of the dominant kernels of the last ppo_train / ppo_collect_rollouts call, measured with
  * HIP events on the engine's stream (bench.py roofline leg) */
 /* measurement helper: run the return scan `iters` times on device-resident synthetic [T,N] columns (no host

@@ -548,6 +548,20 @@ function last_train_stats(p::HipPolicy)
                 p.h, n[], n, stopped, kl, okl, cf))
     (epochs_run = Int(n[]), stopped_early = stopped[] != 0, approx_kl = kl, old_approx_kl = okl, clip_fraction = cf)
 end
+# ---- action selection (include/ppo_hip.h "Action selection"; no reference op): how the evaluators, best_states! and the searches
+# choose an action -- :sample draws rand(Categorical(p)), :greedy plays argmax(p), p = softmax(logits / temperature).  The
+# default (:sample, 1.0) is the reference's rule.  collect_rollouts!, collect_paths!, action_probabilities and train! never read it
+const SELECT_RULES = (:sample, :greedy)
+function set_selection!(p::HipPolicy, rule::Symbol = :sample, temperature = 1.0)
+    r = findfirst(==(rule), SELECT_RULES)
+    r === nothing && error("set_selection!: rule must be :sample or :greedy")
+    check(ccall((:ppo_policy_set_selection, LIB), Int32, (Ptr{Cvoid}, Int32, Float64), p.h, Int32(r - 1), Float64(temperature)))
+end
+function get_selection(p::HipPolicy)
+    r, t = Ref{Int32}(), Ref{Float64}()
+    check(ccall((:ppo_policy_get_selection, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Float64}), p.h, r, t))
+    (SELECT_RULES[r[] + 1], t[])
+end
 # ---- device critic: a HipPolicy(F, hidden, L, 4) read as a state value (mean of the outputs of the active quads' rows),
 # trained with Flux.mse; its state values feed GAE without leaving the device (include/ppo_hip.h "critic")
 const VTARGET = Dict(:returns => Int32(0), :lambda_returns => Int32(1))

@@ -26,6 +26,7 @@ Plugin functions are generic: calling one on an object that does not overload it
 Indices that cross this API are 1-based like the reference; the C ABI below is 0-based.
 All compute runs in the HIP library; nothing here falls back to the CPU.
 """
+import contextlib
 import ctypes as C
 import functools
 import os
@@ -62,6 +63,7 @@ __all__ = [
     "search_best_states_", "search_resample_states_", "check_resample", "apply_paths_", "check_paths",
     "collect_paths_",
     "imitate_forward_backward", "imitate_train_", "imitation_loss",
+    "check_selection", "selecting", "SELECT_RULES",
 ]
 
 
@@ -435,6 +437,28 @@ class HipPolicy:
         cf, ms = np.zeros(n.value, np.float64), np.zeros(n.value, np.float64)
         call("ppo_policy_last_value_stats", self._h, n.value, C.byref(n), _p(cf, _lib.c_f64p), _p(ms, _lib.c_f64p))
         return {"epochs_run": n.value, "clip_fraction": list(cf), "mean_sq_change": list(ms)}
+
+    @property
+    def selection(self):
+        """(rule, temperature): how the calls that APPLY this policy on a HipVecEnv choose an action -- the evaluators
+        (average_returns, average_best_returns, average_normalized_returns, evaluate_trajectories), best_states_ /
+        best_state_in_rollout and its siblings, search_best_states_ and search_resample_states_.  rule "sample" draws
+        rand(Categorical(p)), "greedy" plays argmax(p) (the lowest index among equal maxima); p = softmax(logits / temperature).
+        The default ("sample", 1.0) is the reference's rule.  The setter takes "sample", "greedy", (rule, temperature) or None
+        (the default).  The collectors, action_probabilities and every training call never read it: a buffer's p_old must be
+        the probability under the distribution the training pass differentiates.  fp32 policies only."""
+        r, t = C.c_int32(0), C.c_double(0)
+        call("ppo_policy_get_selection", self._h, C.byref(r), C.byref(t))
+        return SELECT_RULES[r.value], t.value
+
+    @selection.setter
+    def selection(self, value):
+        if value is None:
+            value = ("sample", 1.0)
+        elif isinstance(value, str):
+            value = (value, 1.0)
+        rule, temperature = check_selection(*value)
+        call("ppo_policy_set_selection", self._h, SELECT_RULES.index(rule), temperature)
 
     def grad_buffer_dev(self):
         ptr, n = C.c_void_p(), C.c_int64(0)
@@ -1685,7 +1709,8 @@ def ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size,
 
 def average_returns(policy, env, num_trajectories):
     """PPO.average_returns(policy, env, num_trajectories) (src/evaluate.jl:18-25) -> (mean, std) of the
-    undiscounted episode return under the stochastic policy (std with the n-1 correction like Flux.std)."""
+    undiscounted episode return under the stochastic policy (std with the n-1 correction like Flux.std).  On a HipVecEnv
+    the actions are chosen under policy.selection; the default is the reference's rule."""
     if not isinstance(env, HipVecEnv):
         return generic.average_returns_host(_this_module(), policy, env, num_trajectories)
     scratch = BufferRollouts()
@@ -1870,6 +1895,36 @@ def check_resample(N, K, interval, survivors):
     if K > RESAMPLE_MAX_K:
         raise PPOError(-4, "search_resample_states: K above %d clones is not supported" % RESAMPLE_MAX_K)
     return K, R, m0
+
+
+SELECT_RULES = ("sample", "greedy")        # PPO_SELECT_SAMPLE, PPO_SELECT_GREEDY
+
+
+def check_selection(rule, temperature=1.0):
+    """What HipPolicy.selection requires (ppo_policy_set_selection checks the same): rule "sample" or "greedy", temperature
+    finite and > 0, else PPOError(PPO_ERR_ARG).  Returns (rule, float(temperature)); touches no library."""
+    if not isinstance(rule, str) or rule not in SELECT_RULES:
+        raise PPOError(-1, "AssertionError: selection: rule must be 'sample' or 'greedy'")
+    try:
+        t = float(temperature)
+    except (TypeError, ValueError):
+        raise PPOError(-1, "AssertionError: selection: temperature must be a number")
+    if not (np.isfinite(t) and t > 0.0):
+        raise PPOError(-1, "AssertionError: selection: temperature must be finite and > 0")
+    return rule, t
+
+
+@contextlib.contextmanager
+def selecting(policy, rule="sample", temperature=1.0):
+    """with selecting(policy, "greedy"): ... -- sets policy.selection for the block and restores the previous one on exit, e.g.
+    inside an evaluator callback of ppo_iterate_ so that the collectors' policy is scored by its mode."""
+    new = check_selection(rule, temperature)
+    old = policy.selection
+    policy.selection = new
+    try:
+        yield policy
+    finally:
+        policy.selection = old
 
 
 def search_resample_states_(env, policy, score, degree, active, K, interval, survivors, donors=False, clone_gaps=False,

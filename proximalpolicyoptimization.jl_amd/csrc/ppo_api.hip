@@ -859,10 +859,20 @@ int32_t ppo_collect_rollouts_episodes(ppo_rollouts_t ro, ppo_env_t env, ppo_poli
     return ppo_env_check_errors(env, nullptr);
 }
 
+static int32_t evaluate_impl(ppo_policy_s* pol, ppo_env_s* env, ppo_rollouts_s* scratch, int64_t num_traj, int32_t kind,
+                             std::vector<double>& values);
+static void mean_std(const std::vector<double>& x, double* mean, double* std);
+
 // average_returns (src/evaluate.jl:18-25): undiscounted return of each whole episode, then Flux.mean / Flux.std
 int32_t ppo_average_returns(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_trajectories,
                             double* mean, double* std) {
     ARG_CHECK(pol && env && scratch && mean && std && num_trajectories >= 1, "average_returns: bad argument");
+    if (!default_selection(pol)) {     // the collectors never read the selection: kind 1 of the evaluators is the same statistic
+        std::vector<double> v;
+        PPO_TRY(evaluate_impl(pol, env, scratch, num_trajectories, 1, v));
+        mean_std(v, mean, std);
+        return PPO_OK;
+    }
     const int64_t N = env->N;
     const int64_t per_env = (num_trajectories + N - 1) / N;
     PPO_TRY(ppo_collect_rollouts_episodes(scratch, env, pol, num_trajectories, 1.0, 0));   // exactly num_trajectories (:19-22)
@@ -901,6 +911,7 @@ int32_t ppo_average_returns(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scra
 // The step loop of the evaluators and of the best-state search: observe, policy forward + sample, env step with the
 // bookkeeping of `ev` (k_env_step) or `tv` (k_env_step_track), until every env has used up its episodes_left (polled every
 // 8 steps) or Tmax steps have run.  Row 0 of `scratch` is the only rollout storage touched.
+// The action is chosen under the policy's selection (ppo_policy_set_selection; the default is the sampled rollout step).
 // after_step (optional) runs behind the env step of loop step t, before the poll (the resampling search's events).
 static int32_t play_quotas(ppo_policy_s* pol, ppo_env_s* env, ppo_rollouts_s* scratch, int64_t Tmax, const EvalView* ev,
                            const TrackView* tv, bool* all_done, const std::function<int32_t(int64_t)>* after_step = nullptr) {
@@ -909,7 +920,7 @@ static int32_t play_quotas(ppo_policy_s* pol, ppo_env_s* env, ppo_rollouts_s* sc
     bool all = false;
     for (int64_t t = 0; t < Tmax && !all; ++t) {
         PPO_TRY(launch_env_observe(env, scratch->states.p, scratch->active.p));
-        PPO_TRY(launch_policy_rollout(pol, env, scratch->states.p, scratch->active.p, scratch->actions.p, scratch->p_sel.p, nullptr));
+        PPO_TRY(launch_policy_select(pol, env, scratch->states.p, scratch->active.p, scratch->actions.p, scratch->p_sel.p, nullptr));
         if (tv) PPO_TRY(launch_env_step_track(env, scratch->actions.p, scratch->rewards.p, scratch->done.p, scratch->valid.p, *tv));
         else PPO_TRY(launch_env_step(env, scratch->actions.p, scratch->rewards.p, scratch->done.p, scratch->valid.p, 0, 1, ev));
         if (after_step) PPO_TRY((*after_step)(t));
@@ -960,6 +971,36 @@ static void mean_std(const std::vector<double>& x, double* mean, double* std) {
     for (double v : x) s += (v - m) * (v - m);
     *mean = m;
     *std = x.size() > 1 ? std::sqrt(s / (double)(x.size() - 1)) : NAN;   // Flux.std: corrected (n-1)
+}
+
+// ---- action selection of the calls behind play_quotas (no reference op): a property of the policy handle
+int32_t ppo_policy_set_selection(ppo_policy_t pol, int32_t rule, double temperature) {
+    ARG_CHECK(rule == PPO_SELECT_SAMPLE || rule == PPO_SELECT_GREEDY, "policy_set_selection: rule must be 0 (sample) or 1 (greedy)");
+    ARG_CHECK(std::isfinite(temperature) && temperature > 0.0, "policy_set_selection: temperature must be finite and > 0");
+    ARG_CHECK(pol, "policy_set_selection: null policy");
+    pol->select_rule = rule;
+    pol->select_temperature = temperature;
+    return PPO_OK;
+}
+int32_t ppo_policy_get_selection(ppo_policy_t pol, int32_t* rule, double* temperature) {
+    ARG_CHECK(pol && rule && temperature, "policy_get_selection: null argument");
+    *rule = pol->select_rule;
+    *temperature = pol->select_temperature;
+    return PPO_OK;
+}
+// diagnostic for the tests (not part of include/ppo_hip.h), like ppo_debug_train_ratios: what one step of play_quotas would
+// choose for every env from the state and tick it holds -- observe, launch_policy_select -- WITHOUT the env step: actions [N]
+// (0-based) and p_sel [N], which no call behind play_quotas returns.  The envs keep state, tick and counters; their flag word
+// takes the tail's bits
+extern "C" int32_t ppo_debug_select_step(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int32_t* actions, float* p_sel) {
+    ARG_CHECK(pol && env && scratch && actions && p_sel, "ppo_debug_select_step: null argument");
+    PPO_TRY(check_shapes(scratch, env, pol));
+    PPO_TRY(rollouts_reserve(scratch, 1, false));
+    PPO_TRY(launch_env_observe(env, scratch->states.p, scratch->active.p));
+    PPO_TRY(launch_policy_select(pol, env, scratch->states.p, scratch->active.p, scratch->actions.p, scratch->p_sel.p, nullptr));
+    scratch->T = 0; scratch->len = 0; scratch->adv_T = -1; scratch->values_T = -1; scratch->boot_T = -1;
+    PPO_TRY(d2h(actions, scratch->actions.p, (size_t)env->N));
+    return d2h(p_sel, scratch->p_sel.p, (size_t)env->N);
 }
 
 int32_t ppo_evaluate_trajectories(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_trajectories,

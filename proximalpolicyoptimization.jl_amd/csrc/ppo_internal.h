@@ -161,7 +161,12 @@ struct ppo_policy_s {
     DevBuf<float> vdelta_col;          // [len] one epoch of ppo_value_train: the minibatch at dataset position `start` writes at start
     int64_t vdelta_n = 0;              // floats ppo_debug_value_deltas may read there (the latest epoch's), 0: none
     std::vector<double> vstats_clip, vstats_msq;   // the latest ppo_value_train, per epoch: clip_fraction, mean_sq_change
+    // action selection of the calls that APPLY the policy (ppo_policy_set_selection); the collectors, the
+    // forward and the training calls never read it
+    int32_t select_rule = PPO_SELECT_SAMPLE;
+    double select_temperature = 1.0;   // finite, > 0
 };
+inline bool default_selection(const ppo_policy_s* p) { return p->select_rule == PPO_SELECT_SAMPLE && p->select_temperature == 1.0; }
 
 // one member of a Flux.Optimiser chain: its hyper row of ppo_optimiser_create and its state
 struct OptMember {
@@ -369,6 +374,10 @@ int32_t launch_policy_probs(ppo_policy_s* p, const int8_t* states_dev, const uin
                             int32_t H, float* probs_dev);
 int32_t launch_policy_rollout(ppo_policy_s* p, ppo_env_s* e, const int8_t* states_dev, const uint32_t* active_dev,
                               int32_t* actions_out, float* psel_out, float* full_probs_or_null);
+// one step under the policy's selection: launch_policy_rollout for the default ("sample", 1), otherwise k_policy_fwd MODE 14
+// (tempered sampling) / 15 (greedy), same outputs.  A bf16-dtype policy with a non-default selection: PPO_ERR_UNSUPPORTED
+int32_t launch_policy_select(ppo_policy_s* p, ppo_env_s* e, const int8_t* states_dev, const uint32_t* active_dev,
+                             int32_t* actions_out, float* psel_out, float* full_probs_or_null);
 // one teacher-forced step (k_policy_fwd MODE 11): actions_io[n] = env n's given action (kept; < 0 idles), psel_out[n] = its
 // probability under the policy, 0 for an idle env or an inactive quad (bit 64 of *err).  A bf16-dtype policy: PPO_ERR_UNSUPPORTED
 int32_t launch_policy_forced(ppo_policy_s* p, ppo_env_s* e, const int8_t* states_dev, const uint32_t* active_dev,

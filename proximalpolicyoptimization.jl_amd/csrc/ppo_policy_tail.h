@@ -27,7 +27,7 @@ struct FwdArgs {
     // MODE 2
     float4* act1; float4* act2; float4* dY; double* loss_terms;
     const int32_t* actions; const float* p_old; const float* adv;
-    double eps; float c_over_B; float inv_B;
+    double eps; float c_over_B; float inv_B;      // (MODE 14 / 15, which train nothing: inv_B = 1 / selection temperature)
     // MODE 3 (persistent rollout: T steps of every env in ONE launch; env state lives in the wave's LDS slots)
     int64_t T;                                                   // steps
     int8_t* env_score; int8_t* env_degree; uint32_t* env_active; int32_t* env_steps; float* env_reward;
@@ -108,6 +108,8 @@ struct TailPre { int ab; float po; float adv; };
 // MODE 11 (teacher-forced step): the MODE 1 outputs for the action in pre->ab instead of a sampled one; returns it.
 // MODE 12 (imitation train forward, kernel MODES 12 / 13): MODE 2's outputs for the cross-entropy of the action in pre->ab,
 // weighted by max(pre->adv, 0); pre is required.
+// MODE 14 / 15 (selection rules): MODE 1 on the logits times a.inv_B (= 1 / temperature); 14 samples like MODE 1,
+// 15 takes the first maximum of p instead (tick_val unused).  l is scaled in place.
 // dy_copy (MODE 2, TPS == 1, optional): a second destination for the state's 32 dL/dlogits rows, e.g. an LDS tile of the
 // calling workgroup (k_policy_train_tile keeps the whole training pass of a tile on the CU).
 template <int MODE, int TPS, bool DYBF16>
@@ -117,6 +119,15 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
                                            const TailPre* pre = nullptr, float4* dy_copy = nullptr) {
     int sampled = 0;
     constexpr int A = 128 * TPS;
+    if (MODE == 14 || MODE == 15) {
+        // selection temperature: l' = l * (float)(1 / temperature), one fp32 multiply per logit in front of the
+        // masked max (a.inv_B carries the factor: the rollout modes have no other use for that field)
+        const float inv = a.inv_B;
+#pragma unroll
+        for (int ts = 0; ts < TPS; ++ts)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) l[ts][i] = l[ts][i] * inv;
+    }
     // ---- masked softmax over the A = 128*TPS logits of the state (quad of row 32ts+j = 8ts + j/4)
     bool on[TPS];
     float m = -INFINITY;
@@ -149,8 +160,8 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
                     make_float4(p[ts][0], p[ts][1], p[ts][2], p[ts][3]);
         }
     }
-    if (MODE == 1 || MODE == 3) {
-        // rand(Categorical(p)): sequential fp32 inverse-CDF walk, same uniform as the oracle
+    if (MODE == 1 || MODE == 3 || MODE == 14) {
+        // rand(Categorical(p)): sequential fp32 inverse-CDF walk, same uniform as the oracle (MODE 14: over the tempered p)
         uint32_t rnd[4];
         philox4x32_10((uint32_t)(a.global_offset + state), tick_val, 0u, 0u, a.k0, a.k1, rnd);
         const float u = u01_from_u32(rnd[0]);
@@ -199,6 +210,46 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
             a.psel_out[out_index] = psel;
         }
         sampled = ia;
+        if (a.full_probs && h == 0) {
+#pragma unroll
+            for (int ts = 0; ts < TPS; ++ts)
+                reinterpret_cast<float4*>(a.full_probs)[((size_t)out_index * TPS + ts) * 32 + j] =
+                    make_float4(p[ts][0], p[ts][1], p[ts][2], p[ts][3]);
+        }
+    }
+    if (MODE == 15) {
+        // greedy: the lowest action index among those with the largest p, Julia's argmax.  No Philox call, no walk.
+        // Per lane the first maximum in index order (tile, then i: strictly greater replaces), then a butterfly over the 32 lanes
+        // of a half on the pair (p, index) in which equal p keeps the lower index -- both halves hold the same p, so every lane
+        // ends with the winner.  p >= 0 or NaN (a state without an active quad: 0 / 0): NaN never replaces, the result is then
+        // action 0 with p_sel NaN in every lane and flag bit 8, as the sampled tail leaves such a state
+        float bp = -1.0f;
+        int bi = 0;
+#pragma unroll
+        for (int ts = 0; ts < TPS; ++ts)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const bool take = p[ts][i] > bp;
+                bi = take ? 128 * ts + 4 * j + i : bi;
+                bp = take ? p[ts][i] : bp;
+            }
+#define PPO_ARGMAX_STEP(OFF)                                                                   \
+        {                                                                                      \
+            const float op = xor_lane<OFF>(bp);                                                \
+            const int oi = __float_as_int(xor_lane<OFF>(__int_as_float(bi)));                  \
+            const bool take = op > bp || (op == bp && oi < bi);                                \
+            bi = take ? oi : bi;                                                               \
+            bp = take ? op : bp;                                                               \
+        }
+        PPO_ARGMAX_STEP(16) PPO_ARGMAX_STEP(8) PPO_ARGMAX_STEP(4) PPO_ARGMAX_STEP(2) PPO_ARGMAX_STEP(1)
+#undef PPO_ARGMAX_STEP
+        const float psel = (bp >= 0.0f) ? bp : p[0][0];
+        if (lane == 0) {
+            if (!(psel > 0.0f)) atomicOr(a.err, 8);
+            a.actions_out[out_index] = bi;
+            a.psel_out[out_index] = psel;
+        }
+        sampled = bi;
         if (a.full_probs && h == 0) {
 #pragma unroll
             for (int ts = 0; ts < TPS; ++ts)

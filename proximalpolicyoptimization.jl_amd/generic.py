@@ -96,9 +96,18 @@ def collect_rollouts_host_(P, rollouts, env, policy, num_episodes, discount, rng
     compute_state_value_(P, rollouts, discount)                            # :78
 
 
+def _require_default_selection(P, policy, who):
+    """The host loops below apply a policy by rand(Categorical(action_probabilities)) only: a HipPolicy whose selection
+    (HipPolicy.selection) is not the default would silently be sampled at temperature 1."""
+    if isinstance(policy, P.HipPolicy) and policy.selection != ("sample", 1.0):
+        raise NotImplementedError("%s on a generic env samples at temperature 1: the policy's selection %r is honoured on a "
+                                  "HipVecEnv only" % (who, policy.selection))
+
+
 def single_trajectory_return(P, policy, env, rng=None):
     """single_trajectory_return(policy, env) (src/evaluate.jl:1-16): undiscounted return of one stochastic episode
     from the env's CURRENT state (the caller resets)."""
+    _require_default_selection(P, policy, "single_trajectory_return")
     rng = rng or np.random.default_rng()
     ret = 0.0
     done = P.is_terminal(env)
@@ -113,6 +122,7 @@ def single_trajectory_return(P, policy, env, rng=None):
 
 def average_returns_host(P, policy, env, num_trajectories, rng=None):
     """average_returns(policy, env, num_trajectories) (src/evaluate.jl:18-25), generic method: mean and sample std."""
+    _require_default_selection(P, policy, "average_returns")
     rets = []
     for _ in range(int(num_trajectories)):
         P.reset_(env)
@@ -140,6 +150,7 @@ def best_state_in_rollout(P, env, policy, rng=None):
     """best_state_in_rollout(wrapper, policy) (test/quad_game_utilities.jl:341-358): plays one stochastic trajectory from the
     wrapper's current state, keeps a deep copy behind every step and returns the copy at argmin(current_score - opt_score)
     (the first minimum; the start state is the first candidate)."""
+    _require_default_selection(P, policy, "best_state_in_rollout")
     import copy
     rng = rng or np.random.default_rng()
     wrappers = [copy.deepcopy(env)]
@@ -156,6 +167,7 @@ def best_state_in_rollout(P, env, policy, rng=None):
 def single_trajectory_scores(P, env, policy, rng=None):
     """single_trajectory_scores(wrapper, policy) (test/quad_game_utilities.jl:309-323): initial_score - current_score behind
     every step of one stochastic trajectory."""
+    _require_default_selection(P, policy, "single_trajectory_scores")
     rng = rng or np.random.default_rng()
     initial_score = _game(env).initial_score
     scores = []
@@ -169,6 +181,7 @@ def single_trajectory_scores(P, env, policy, rng=None):
 
 def count_non_flips(P, env, policy, rng=None):
     """count_non_flips(wrapper, policy) (test/random_quad.jl:9-27): actions of type > 2 (1-based) in one trajectory."""
+    _require_default_selection(P, policy, "count_non_flips")
     rng = rng or np.random.default_rng()
     counter = 0
     done = P.is_terminal(env)
