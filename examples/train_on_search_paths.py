@@ -29,6 +29,11 @@ policy, and one below 1 focuses an untrained one.  collect_paths_ and the traini
 the loss stay those of the untempered policy.  Each round also scores the policy's mode, the greedy roll-out
 (selecting(policy, "greedy")), next to the sampled return.
 
+--top-k / --top-p truncate what the search's clones sample from (HipPolicy.truncation, through selecting(..., top_k=, top_p=)):
+the k likeliest actions, or the likeliest set that reaches probability mass top_p, renormalised.  With a temperature above 1
+that keeps the clones apart without moving probability onto the long tail of moves the policy has learnt to be useless.  Like
+the temperature it is the search step's alone.
+
 This script shows the calls and prints what it measures each round (the mean gap the search reaches, the transitions
 collected, the losses, the mean return of the plain stochastic policy).  Whether the loop learns faster or better than
 ppo_iterate_ on sampled rollouts, and which --loss serves it best, has not been measured; the script makes no such claim.
@@ -53,6 +58,9 @@ def main():
                     help="clone: cross-entropy on the paths' actions; sil: weighted by max(advantage, 0); ppo: the clipped surrogate")
     ap.add_argument("--temperature", type=float, default=1.0,
                     help="selection temperature of the search step (1: the policy's own distribution; > 1 flatter, < 1 sharper)")
+    ap.add_argument("--top-k", type=int, default=0, help="the search step samples from the k likeliest actions only (0: all)")
+    ap.add_argument("--top-p", type=float, default=1.0,
+                    help="the search step samples from the likeliest actions that reach this probability mass only (1: all)")
     args = ap.parse_args()
 
     discount, epsilon, entropy_weight, max_actions = 1.0, 0.05, 0.01, 32
@@ -69,7 +77,7 @@ def main():
         fresh = PPO.HipVecEnv(num_envs=args.starts, Q=8, max_actions=max_actions, seed=1000 + r)   # this round's reset states
         st = fresh.internal()
         starts = (st["score"], st["degree"], fresh.active_quads())
-        with PPO.selecting(policy, "sample", args.temperature):               # the search alone; restored behind it
+        with PPO.selecting(policy, "sample", args.temperature, top_k=args.top_k, top_p=args.top_p):   # the search alone; restored behind it
             found = PPO.search_best_states_(search_env, policy, *starts, args.clones, path=True)
         PPO.collect_paths_(rollouts, env, policy, *starts, found["path"], discount)
         dataset = PPO.construct_dataset(rollouts)

@@ -720,6 +720,24 @@ int32_t ppo_collect_paths(ppo_rollouts_t ro, ppo_env_t env, ppo_policy_t pol, in
 int32_t ppo_policy_set_selection(ppo_policy_t pol, int32_t rule, double temperature);
 int32_t ppo_policy_get_selection(ppo_policy_t pol, int32_t* rule, double* temperature);
 
+/* Truncation of the distribution that PPO_SELECT_SAMPLE draws from: top-k and nucleus (no reference op).  A policy
+ * handle carries a truncation (top_k, top_p), default (0, 1.0), separate from the selection and composing with it.  Per step, on
+ * the tempered masked softmax p of the selection above (A entries):
+ *     b precedes a  iff  p[b] > p[a] || (p[b] == p[a] && b < a)      -- equal probabilities rank by the lower index, like greedy;
+ *     rank(a) = the number of b that precede a;  mass_before(a) = the fp32 sum of their p[b], added one by one in ascending b;
+ *     keep(a) = (top_k == 0 || rank(a) < top_k) && (top_p == 1.0f || mass_before(a) < (float)top_p);
+ *     q = keep ? p : 0;  S' = the sum of q in the softmax's own order;  p'' = q / S' (one fp32 division per entry);
+ *     a = rand(Categorical(p'')) by the same walk on the same Philox uniform;  p_sel = p''[a].
+ * The arg-max has rank 0 and mass 0 and is always kept; top_k = 1 plays greedy's action with p_sel = 1.  Any non-default
+ * truncation renormalises, also one that keeps everything (top_k >= A).  top_p = 1 skips the mass test; it does not test
+ * mass_before < 1.  PPO_SELECT_GREEDY ignores the truncation: every truncation keeps the arg-max.
+ * READ by the calls that read the selection, NOT READ by the others: ppo_collect_rollouts, _episodes, _steps,
+ * ppo_collect_paths, ppo_policy_forward and every training call never see it, for the selection's reason.
+ * PPO_ERR_ARG: top_k < 0; top_p NaN, <= 0 or > 1 (judged before the handle).  The setter makes no device call.  A bf16-dtype
+ * policy keeps the default only: a reading call returns PPO_ERR_UNSUPPORTED while another truncation is set. */
+int32_t ppo_policy_set_truncation(ppo_policy_t pol, int32_t top_k, double top_p);
+int32_t ppo_policy_get_truncation(ppo_policy_t pol, int32_t* top_k, double* top_p);
+
 /* timing of the dominant kernels of the last ppo_train / ppo_collect_rollouts call, measured with
  * HIP events on the engine's stream (bench.py roofline leg) */
 /* measurement helper: run the return scan `iters` times on device-resident synthetic [T,N] columns (no host

@@ -562,6 +562,17 @@ function get_selection(p::HipPolicy)
     check(ccall((:ppo_policy_get_selection, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Float64}), p.h, r, t))
     (SELECT_RULES[r[] + 1], t[])
 end
+# ---- truncation of the distribution :sample draws from (include/ppo_hip.h "Truncation"; no reference op): the top_k likeliest
+# actions (0: all) and the likeliest set whose mass in front of an action is below top_p (1.0: all), renormalised; read where the
+# selection is read.  :greedy ignores it
+function set_truncation!(p::HipPolicy, top_k::Integer = 0, top_p = 1.0)
+    check(ccall((:ppo_policy_set_truncation, LIB), Int32, (Ptr{Cvoid}, Int32, Float64), p.h, Int32(top_k), Float64(top_p)))
+end
+function get_truncation(p::HipPolicy)
+    k, t = Ref{Int32}(), Ref{Float64}()
+    check(ccall((:ppo_policy_get_truncation, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Float64}), p.h, k, t))
+    (Int(k[]), t[])
+end
 # ---- device critic: a HipPolicy(F, hidden, L, 4) read as a state value (mean of the outputs of the active quads' rows),
 # trained with Flux.mse; its state values feed GAE without leaving the device (include/ppo_hip.h "critic")
 const VTARGET = Dict(:returns => Int32(0), :lambda_returns => Int32(1))

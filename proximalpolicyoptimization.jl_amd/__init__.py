@@ -64,6 +64,7 @@ __all__ = [
     "collect_paths_",
     "imitate_forward_backward", "imitate_train_", "imitation_loss",
     "check_selection", "selecting", "SELECT_RULES",
+    "check_truncation", "DEFAULT_TRUNCATION",
 ]
 
 
@@ -459,6 +460,23 @@ class HipPolicy:
             value = (value, 1.0)
         rule, temperature = check_selection(*value)
         call("ppo_policy_set_selection", self._h, SELECT_RULES.index(rule), temperature)
+
+    @property
+    def truncation(self):
+        """(top_k, top_p): the truncation of the tempered distribution that rule "sample" of `selection` draws from, read by the
+        calls that read the selection and by no other.  top_k keeps the k likeliest actions (0: all), top_p the likeliest set
+        whose probability mass in front of an action is below top_p (1.0: all); equal probabilities rank by the lower index;
+        the kept probabilities are renormalised and p_sel is the renormalised one.  Both compose (an action is kept when both
+        keep it) and compose with the temperature.  "greedy" ignores it: the arg-max is always kept.  The default (0, 1.0) is
+        no truncation; the setter takes a pair or None (the default).  fp32 policies only."""
+        k, p = C.c_int32(0), C.c_double(0)
+        call("ppo_policy_get_truncation", self._h, C.byref(k), C.byref(p))
+        return k.value, p.value
+
+    @truncation.setter
+    def truncation(self, value):
+        top_k, top_p = check_truncation(*(DEFAULT_TRUNCATION if value is None else value))
+        call("ppo_policy_set_truncation", self._h, top_k, top_p)
 
     def grad_buffer_dev(self):
         ptr, n = C.c_void_p(), C.c_int64(0)
@@ -1914,17 +1932,41 @@ def check_selection(rule, temperature=1.0):
     return rule, t
 
 
+DEFAULT_TRUNCATION = (0, 1.0)
+
+
+def check_truncation(top_k=0, top_p=1.0):
+    """What HipPolicy.truncation requires (ppo_policy_set_truncation checks the same): top_k an integer >= 0 that fits an int32
+    (0: no limit), top_p a number in (0, 1] (1: no limit), else PPOError(PPO_ERR_ARG).  Returns (int(top_k), float(top_p));
+    touches no library."""
+    if isinstance(top_k, (bool, np.bool_)) or not isinstance(top_k, (int, np.integer)):
+        raise PPOError(-1, "AssertionError: truncation: top_k must be an integer")
+    if not 0 <= int(top_k) <= 2 ** 31 - 1:
+        raise PPOError(-1, "AssertionError: truncation: top_k must be >= 0 (0: no limit) and fit an int32")
+    try:
+        p = float(top_p)
+    except (TypeError, ValueError):
+        raise PPOError(-1, "AssertionError: truncation: top_p must be a number")
+    if not (p > 0.0 and p <= 1.0):
+        raise PPOError(-1, "AssertionError: truncation: top_p must be in (0, 1] (1: no limit)")
+    return int(top_k), p
+
+
 @contextlib.contextmanager
-def selecting(policy, rule="sample", temperature=1.0):
-    """with selecting(policy, "greedy"): ... -- sets policy.selection for the block and restores the previous one on exit, e.g.
-    inside an evaluator callback of ppo_iterate_ so that the collectors' policy is scored by its mode."""
+def selecting(policy, rule="sample", temperature=1.0, top_k=0, top_p=1.0):
+    """with selecting(policy, "greedy"): ... -- sets policy.selection and policy.truncation for the block and restores the previous
+    ones on exit, e.g. inside an evaluator callback of ppo_iterate_ so that the collectors' policy is scored by its mode, or
+    around a search: with selecting(policy, "sample", 2.0, top_p=0.9): search_best_states_(...)."""
     new = check_selection(rule, temperature)
-    old = policy.selection
+    new_trunc = check_truncation(top_k, top_p)
+    old, old_trunc = policy.selection, policy.truncation
     policy.selection = new
+    policy.truncation = new_trunc
     try:
         yield policy
     finally:
         policy.selection = old
+        policy.truncation = old_trunc
 
 
 def search_resample_states_(env, policy, score, degree, active, K, interval, survivors, donors=False, clone_gaps=False,

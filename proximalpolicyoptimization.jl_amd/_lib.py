@@ -66,6 +66,8 @@ SIGNATURES = {
     "ppo_collect_paths": [H, H, H, C.c_int64, c_i8p, c_i8p, c_u32p, c_i16p, C.c_int64, C.c_double, C.c_int32, C.c_int32],
     "ppo_policy_set_selection": [H, C.c_int32, C.c_double],
     "ppo_policy_get_selection": [H, c_i32p, c_f64p],
+    "ppo_policy_set_truncation": [H, C.c_int32, C.c_double],
+    "ppo_policy_get_truncation": [H, c_i32p, c_f64p],
     "ppo_set_rollout_persistent": [C.c_int32],
     "ppo_set_rollout_compact": [C.c_int32],
     "ppo_env_check_errors": [H, c_i32p],

@@ -867,7 +867,7 @@ static void mean_std(const std::vector<double>& x, double* mean, double* std);
 int32_t ppo_average_returns(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_trajectories,
                             double* mean, double* std) {
     ARG_CHECK(pol && env && scratch && mean && std && num_trajectories >= 1, "average_returns: bad argument");
-    if (!default_selection(pol)) {     // the collectors never read the selection: kind 1 of the evaluators is the same statistic
+    if (!default_selection(pol) || !default_truncation(pol)) {     // the collectors never read the selection or the truncation: kind 1 of the evaluators is the same statistic
         std::vector<double> v;
         PPO_TRY(evaluate_impl(pol, env, scratch, num_trajectories, 1, v));
         mean_std(v, mean, std);
@@ -986,6 +986,21 @@ int32_t ppo_policy_get_selection(ppo_policy_t pol, int32_t* rule, double* temper
     ARG_CHECK(pol && rule && temperature, "policy_get_selection: null argument");
     *rule = pol->select_rule;
     *temperature = pol->select_temperature;
+    return PPO_OK;
+}
+// ---- truncation of the distribution the "sample" rule draws from (no reference op), read where the selection is
+int32_t ppo_policy_set_truncation(ppo_policy_t pol, int32_t top_k, double top_p) {
+    ARG_CHECK(top_k >= 0, "policy_set_truncation: top_k must be >= 0 (0: no limit)");
+    ARG_CHECK(top_p > 0.0 && top_p <= 1.0, "policy_set_truncation: top_p must be in (0, 1] (1: no limit)");     // NaN fails both
+    ARG_CHECK(pol, "policy_set_truncation: null policy");
+    pol->trunc_top_k = top_k;
+    pol->trunc_top_p = top_p;
+    return PPO_OK;
+}
+int32_t ppo_policy_get_truncation(ppo_policy_t pol, int32_t* top_k, double* top_p) {
+    ARG_CHECK(pol && top_k && top_p, "policy_get_truncation: null argument");
+    *top_k = pol->trunc_top_k;
+    *top_p = pol->trunc_top_p;
     return PPO_OK;
 }
 // diagnostic for the tests (not part of include/ppo_hip.h), like ppo_debug_train_ratios: what one step of play_quotas would

@@ -165,8 +165,14 @@ struct ppo_policy_s {
     // forward and the training calls never read it
     int32_t select_rule = PPO_SELECT_SAMPLE;
     double select_temperature = 1.0;   // finite, > 0
+    // truncation of the tempered distribution the "sample" rule draws from (ppo_policy_set_truncation): the top_k
+    // likeliest actions (0: all) and the likeliest set whose mass in front of an action stays below top_p (1: all).  Read where
+    // the selection is read, and by the same calls only
+    int32_t trunc_top_k = 0;           // >= 0
+    double trunc_top_p = 1.0;          // in (0, 1]
 };
 inline bool default_selection(const ppo_policy_s* p) { return p->select_rule == PPO_SELECT_SAMPLE && p->select_temperature == 1.0; }
+inline bool default_truncation(const ppo_policy_s* p) { return p->trunc_top_k == 0 && p->trunc_top_p == 1.0; }
 
 // one member of a Flux.Optimiser chain: its hyper row of ppo_optimiser_create and its state
 struct OptMember {
@@ -375,7 +381,9 @@ int32_t launch_policy_probs(ppo_policy_s* p, const int8_t* states_dev, const uin
 int32_t launch_policy_rollout(ppo_policy_s* p, ppo_env_s* e, const int8_t* states_dev, const uint32_t* active_dev,
                               int32_t* actions_out, float* psel_out, float* full_probs_or_null);
 // one step under the policy's selection: launch_policy_rollout for the default ("sample", 1), otherwise k_policy_fwd MODE 14
-// (tempered sampling) / 15 (greedy), same outputs.  A bf16-dtype policy with a non-default selection: PPO_ERR_UNSUPPORTED
+// (tempered sampling) / 15 (greedy) / 16 (tempered sampling from the truncated distribution: rule "sample" with a non-default
+// truncation, at any temperature), same outputs.  A bf16-dtype policy with a non-default selection or truncation:
+// PPO_ERR_UNSUPPORTED
 int32_t launch_policy_select(ppo_policy_s* p, ppo_env_s* e, const int8_t* states_dev, const uint32_t* active_dev,
                              int32_t* actions_out, float* psel_out, float* full_probs_or_null);
 // one teacher-forced step (k_policy_fwd MODE 11): actions_io[n] = env n's given action (kept; < 0 idles), psel_out[n] = its

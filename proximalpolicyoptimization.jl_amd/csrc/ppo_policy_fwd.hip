@@ -62,6 +62,8 @@ static __device__ __forceinline__ void act_store_nt(float4* p, float4 v) {
 // (policy_tail's mode 12); own modes for the same reason, 2 / 4 are the parent's code
 // 14 / 15: one rollout step under a selection rule: MODE 1's forward with the logits scaled by 1 / temperature in
 // front of the softmax; 14 samples like MODE 1, 15 plays the first maximum (policy_tail's modes 14 / 15).  Own modes again
+// 16: 14 sampling from the top-k / nucleus truncation of the tempered distribution (policy_tail's mode 16).  An
+// own mode once more: 14 is the parent's code
 constexpr bool fwd_mode_value(int m) { return m >= 5 && m <= 10; }
 constexpr bool fwd_mode_vclip(int m) { return m == 9 || m == 10; }
 constexpr bool fwd_mode_imitate(int m) { return m == 12 || m == 13; }
@@ -218,7 +220,7 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
         if (VALUE && TRAIN) vtarget = a.vtarget[sid];
         if (fwd_mode_vclip(MODE)) vold = a.vold[sid];                  // clipped value loss: the old value, likewise
         if (SNAP) fetch_snapshot(state + nwaves < a.B ? state + nwaves : state);      // lands under this state's MFMAs
-        const uint32_t tick_val = (MODE == 3) ? *er.tick : ((MODE == 1 || MODE == 14) ? a.tick[state] : 0u);
+        const uint32_t tick_val = (MODE == 3) ? *er.tick : ((MODE == 1 || MODE == 14 || MODE == 16) ? a.tick[state] : 0u);
         const int64_t out_index = (MODE == 3) ? tt * a.B + state : state;
         // teacher-forced step: the state's given action, fetched here like the tick so that it has landed by the tail
         [[maybe_unused]] TailPre forced = {0, 0.0f, 0.0f};
@@ -667,14 +669,21 @@ int32_t launch_policy_forced(ppo_policy_s* p, ppo_env_s* e, const int8_t* states
 
 // One rollout step under the policy's selection, for the callers that APPLY a policy (play_quotas): the default
 // ("sample", 1) is launch_policy_rollout itself, with its split and bf16 branches; any other selection launches MODE 14
-// (tempered sampling) or MODE 15 (greedy) through the per-step dispatch only: no split-rollout form, no persistent form, no bf16
+// (tempered sampling) or MODE 15 (greedy) through the per-step dispatch only: no split-rollout form, no persistent form, no bf16.
+// Rule "sample" with a non-default truncation launches MODE 16 instead, at any temperature, 1 included; greedy
+// plays the arg-max, which every truncation keeps, and stays MODE 15
 int32_t launch_policy_select(ppo_policy_s* p, ppo_env_s* e, const int8_t* states_dev, const uint32_t* active_dev,
                              int32_t* actions_out, float* psel_out, float* full_probs_or_null) {
-    if (default_selection(p))
+    const bool truncated = !default_truncation(p) && p->select_rule == PPO_SELECT_SAMPLE;
+    if (default_selection(p) && !truncated)
         return launch_policy_rollout(p, e, states_dev, active_dev, actions_out, psel_out, full_probs_or_null);
     if (p->dtype != PPO_DTYPE_F32) {
-        ppo_set_error("selection: a bf16-dtype policy plays the default selection (\"sample\", 1) only (the tempered and greedy "
-                      "modes exist in the fp32-MFMA forward only)");
+        if (default_selection(p))
+            ppo_set_error("truncation: a bf16-dtype policy plays the default truncation (top_k 0, top_p 1) only (the truncated "
+                          "sampling mode exists in the fp32-MFMA forward only)");
+        else
+            ppo_set_error("selection: a bf16-dtype policy plays the default selection (\"sample\", 1) only (the tempered and greedy "
+                          "modes exist in the fp32-MFMA forward only)");
         return PPO_ERR_UNSUPPORTED;
     }
     FwdArgs a = {};
@@ -686,6 +695,12 @@ int32_t launch_policy_select(ppo_policy_s* p, ppo_env_s* e, const int8_t* states
     if (p->select_rule == PPO_SELECT_GREEDY) {
         ProfScope ps("k_policy_fwd_greedy");
         return dispatch_fwd<15>(p, a, e->N, e->H / 32);
+    }
+    if (truncated) {
+        a.eps = (double)p->trunc_top_k;
+        a.c_over_B = (float)p->trunc_top_p;
+        ProfScope ps("k_policy_fwd_truncated");
+        return dispatch_fwd<16>(p, a, e->N, e->H / 32);
     }
     ProfScope ps("k_policy_fwd_tempered");
     return dispatch_fwd<14>(p, a, e->N, e->H / 32);

@@ -27,7 +27,8 @@ struct FwdArgs {
     // MODE 2
     float4* act1; float4* act2; float4* dY; double* loss_terms;
     const int32_t* actions; const float* p_old; const float* adv;
-    double eps; float c_over_B; float inv_B;      // (MODE 14 / 15, which train nothing: inv_B = 1 / selection temperature)
+    double eps; float c_over_B; float inv_B;      // (MODE 14 / 15 / 16, which train nothing: inv_B = 1 / selection temperature;
+                                                  //  MODE 16: eps = top_k, an integer a double holds exactly, c_over_B = top_p)
     // MODE 3 (persistent rollout: T steps of every env in ONE launch; env state lives in the wave's LDS slots)
     int64_t T;                                                   // steps
     int8_t* env_score; int8_t* env_degree; uint32_t* env_active; int32_t* env_steps; float* env_reward;
@@ -110,6 +111,8 @@ struct TailPre { int ab; float po; float adv; };
 // weighted by max(pre->adv, 0); pre is required.
 // MODE 14 / 15 (selection rules): MODE 1 on the logits times a.inv_B (= 1 / temperature); 14 samples like MODE 1,
 // 15 takes the first maximum of p instead (tick_val unused).  l is scaled in place.
+// MODE 16 (truncated sampling): MODE 14 on the top-k / nucleus truncation of the tempered p, renormalised;
+// a.eps = top_k (0: all), a.c_over_B = top_p (1: all).
 // dy_copy (MODE 2, TPS == 1, optional): a second destination for the state's 32 dL/dlogits rows, e.g. an LDS tile of the
 // calling workgroup (k_policy_train_tile keeps the whole training pass of a tile on the CU).
 template <int MODE, int TPS, bool DYBF16>
@@ -119,7 +122,7 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
                                            const TailPre* pre = nullptr, float4* dy_copy = nullptr) {
     int sampled = 0;
     constexpr int A = 128 * TPS;
-    if (MODE == 14 || MODE == 15) {
+    if (MODE == 14 || MODE == 15 || MODE == 16) {
         // selection temperature: l' = l * (float)(1 / temperature), one fp32 multiply per logit in front of the
         // masked max (a.inv_B carries the factor: the rollout modes have no other use for that field)
         const float inv = a.inv_B;
@@ -152,6 +155,69 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
 #pragma unroll
         for (int i = 0; i < 4; ++i) p[ts][i] = p[ts][i] / ssum;
 
+    if (MODE == 16) {
+        // top-k / nucleus truncation.  b precedes a iff p[b] > p[a] || (p[b] == p[a] && b < a); rank(a) counts the b
+        // that precede a, mass(a) adds their p[b] in ascending b (fp32, one rounding per add).  One pass over b = 0 .. A - 1 in
+        // ascending order serves every a: p[b] is broadcast by readlane like the walk below broadcasts it, and each lane updates
+        // the rank and the mass of its 4 * TPS entries.  b = 128 tb + 4 jb + ib with tb and ib compile-time and the lane jb a
+        // rolled loop (v_readlane takes its lane from an SGPR): 32 bodies' worth less code than the full unroll, same order.
+        // "b < a" for a = 128 ts + 4 j + i needs no index compare: ts != tb decides it at compile time, ts == tb leaves
+        // j > jb, or j >= jb where ib < i.  A state without an active quad has p NaN everywhere: no comparison holds, rank and
+        // mass stay 0, everything is kept and NaN stays NaN -- what MODE 14 leaves for such a state.
+        const int top_k = (int)a.eps;
+        const float top_p = a.c_over_B;
+        int rk[TPS][4];
+        float ms[TPS][4];
+#pragma unroll
+        for (int ts = 0; ts < TPS; ++ts)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { rk[ts][i] = 0; ms[ts][i] = 0.0f; }
+#pragma unroll
+        for (int tb = 0; tb < TPS; ++tb) {
+#pragma unroll 1
+            for (int jb = 0; jb < 32; ++jb) {
+                const bool behind = j > jb, at_or_behind = j >= jb;
+#pragma unroll
+                for (int ib = 0; ib < 4; ++ib) {
+                    const float pb = readlane_f(p[tb][ib], jb);
+#pragma unroll
+                    for (int ts = 0; ts < TPS; ++ts)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            // where b < a an equal p precedes too: pb >= pa in one compare where the tiles decide it.
+                            // (| and & on purpose: || and && become a branch on the exec mask per entry, measured 75 us
+                            // per launch of 4096 states at Q = 8 where this form takes 46)
+                            const float pa = p[ts][i];
+                            bool prec;
+                            if (ts > tb) prec = pb >= pa;
+                            else if (ts < tb) prec = pb > pa;
+                            else prec = (pb > pa) | ((pb == pa) & (ib < i ? at_or_behind : behind));
+                            rk[ts][i] = prec ? rk[ts][i] + 1 : rk[ts][i];
+                            ms[ts][i] = prec ? ms[ts][i] + pb : ms[ts][i];
+                        }
+                }
+            }
+        }
+        // keep, renormalise: the sum of the kept p in the softmax's own order, one division per entry.  Any truncation that
+        // reaches this mode renormalises, also one that keeps everything
+        float ksum = 0.0f;
+#pragma unroll
+        for (int ts = 0; ts < TPS; ++ts) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const bool keep = (top_k == 0 || rk[ts][i] < top_k) && (top_p == 1.0f || ms[ts][i] < top_p);
+                p[ts][i] = keep ? p[ts][i] : 0.0f;
+            }
+            const float st = ((p[ts][0] + p[ts][1]) + p[ts][2]) + p[ts][3];
+            ksum = (ts == 0) ? st : ksum + st;
+        }
+        ksum = wave32_sum(ksum);
+#pragma unroll
+        for (int ts = 0; ts < TPS; ++ts)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) p[ts][i] = p[ts][i] / ksum;
+    }
+
     if (MODE == 0) {
         if (h == 0) {
 #pragma unroll
@@ -160,8 +226,9 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
                     make_float4(p[ts][0], p[ts][1], p[ts][2], p[ts][3]);
         }
     }
-    if (MODE == 1 || MODE == 3 || MODE == 14) {
-        // rand(Categorical(p)): sequential fp32 inverse-CDF walk, same uniform as the oracle (MODE 14: over the tempered p)
+    if (MODE == 1 || MODE == 3 || MODE == 14 || MODE == 16) {
+        // rand(Categorical(p)): sequential fp32 inverse-CDF walk, same uniform as the oracle (MODE 14: over the tempered p;
+        // MODE 16: over its renormalised truncation)
         uint32_t rnd[4];
         philox4x32_10((uint32_t)(a.global_offset + state), tick_val, 0u, 0u, a.k0, a.k1, rnd);
         const float u = u01_from_u32(rnd[0]);

@@ -102,6 +102,9 @@ def _require_default_selection(P, policy, who):
     if isinstance(policy, P.HipPolicy) and policy.selection != ("sample", 1.0):
         raise NotImplementedError("%s on a generic env samples at temperature 1: the policy's selection %r is honoured on a "
                                   "HipVecEnv only" % (who, policy.selection))
+    if isinstance(policy, P.HipPolicy) and policy.truncation != (0, 1.0):      # likewise (HipPolicy.truncation)
+        raise NotImplementedError("%s on a generic env samples from the whole distribution: the policy's truncation %r is "
+                                  "honoured on a HipVecEnv only" % (who, policy.truncation))
 
 
 def single_trajectory_return(P, policy, env, rng=None):
