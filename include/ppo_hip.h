@@ -550,7 +550,21 @@ int32_t ppo_rollouts_detach_disk(ppo_rollouts_t ro);
  * collection into the same buffer, detach and destroy wait for it too).  With mode 0 the file is complete when
  * ppo_collect_rollouts returns, as before (the reference's rollouts_to_disk is synchronous: src/rollouts_to_disk.jl:73-132). */
 int32_t ppo_set_disk_async(int32_t mode);
+/* the mode in force (0 / 1), whether it came from ppo_set_disk_async or from PPO_DISK_ASYNC at load */
+int32_t ppo_get_disk_async(int32_t* mode);
 int32_t ppo_rollouts_disk_sync(ppo_rollouts_t ro);
+/* Write failures (disk full, file size limit, I/O error) are host errors; each is reported exactly once, as PPO_ERR_ARG with
+ * a ppo_last_error that names the write.
+ *   mode 0: ppo_collect_rollouts itself fails -- for a record, for the returns column, and for the tail of the returns column
+ *           that the stream only writes when the file is closed.
+ *   mode 1: ppo_collect_rollouts may have returned PPO_OK already.  The failure is then reported by the FIRST wait point that
+ *           follows: ppo_rollouts_disk_sync, ppo_rollouts_detach_disk (the sink is detached all the same), a second
+ *           ppo_rollouts_attach_disk, or the next ppo_collect_rollouts into the same attached buffer, which reports the previous
+ *           file's failure and starts nothing (no env step, no new file); the call after it runs normally.
+ *           ppo_rollouts_destroy has no status for it: it waits, leaves ppo_last_error set, and never blocks on a failed writer.
+ * What is left on disk: a reported failure unlinks <dir>/rollout.bin, so the directory never yields a dataset
+ * (ppo_rollouts_load_disk: "trajectory file missing").  The buffer's columns in HBM are complete and usable, the pinned
+ * records return to the pool, and the next collection -- into this sink or a fresh one -- is unaffected. */
 /* DiskDataset: read <dir>/rollout.bin back into the (device) rollout buffer; shapes must match the env it was
  * created for.  All transitions are valid afterwards. */
 int32_t ppo_rollouts_load_disk(ppo_rollouts_t ro, const char* dir);

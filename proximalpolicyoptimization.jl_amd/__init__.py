@@ -1159,9 +1159,9 @@ def collect_rollouts_steps_(rollouts, env, policy, num_steps, discount, record_p
         call("ppo_rollouts_attach_disk", h, rollouts.state_data_directory.encode(), int(pinned_slots))
         g, f32 = _discount_args(discount)
         call("ppo_collect_rollouts", h, env._h, policy._h, int(num_steps), g, f32, 0)
-        if not _DISK_ASYNC[0]:
+        rollouts._device = dev                       # before detach: a failed detach leaves the columns reachable
+        if not _disk_async():
             call("ppo_rollouts_detach_disk", h)      # (deferred finish: disk_sync detaches once the file is complete)
-        rollouts._device = dev
         rollouts.num_samples = len(dev)
         with open(rollouts.trajectory_filename, "w", newline="") as f:          # attach wiped it: keep the header
             f.write(",".join(DiskRollouts.FINAL) + "\n")
@@ -1422,19 +1422,27 @@ def set_disk_async(on=None):
     the writer thread finishes rollout.bin while training runs; disk_sync(rollouts) (or the next collection) waits for it.
     None / False = the file is complete when collect_rollouts_ returns (default, the reference's behaviour)."""
     call("ppo_set_disk_async", -1 if on is None else int(bool(on)))
-    _DISK_ASYNC[0] = bool(on)
 
 
-_DISK_ASYNC = [False]
+def _disk_async():
+    """The library's mode, not a copy of it: PPO_DISK_ASYNC=1 in the environment turns it on without set_disk_async."""
+    m = C.c_int32(0)
+    call("ppo_get_disk_async", C.byref(m))
+    return bool(m.value)
 
 
 def disk_sync(rollouts):
     """Wait until the rollout file of a streamed collection is complete, then detach the store (only needed after
-    set_disk_async(True); a no-op otherwise)."""
-    dev = getattr(rollouts, "_device", None) or rollouts
+    set_disk_async(True); a no-op otherwise).  A write of the deferred finish that failed raises PPOError here (or at
+    whichever wait point comes first: include/ppo_hip.h); rollout.bin is then gone."""
+    dev = getattr(rollouts, "_device", None)
+    if dev is None:                                  # (not `or`: a buffer of length 0 is falsy and still has a store)
+        dev = rollouts
     if getattr(dev, "_h", None):
-        call("ppo_rollouts_disk_sync", dev._h)
-        call("ppo_rollouts_detach_disk", dev._h)
+        try:
+            call("ppo_rollouts_disk_sync", dev._h)
+        finally:
+            call("ppo_rollouts_detach_disk", dev._h)
 
 
 def load_disk_rollouts(state_data_dir, env):

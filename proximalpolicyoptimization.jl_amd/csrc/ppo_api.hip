@@ -751,6 +751,7 @@ int32_t ppo_collect_rollouts(ppo_rollouts_t ro, ppo_env_t env, ppo_policy_t pol,
                              int32_t discount_is_f32, int32_t record_probs) {
     PPO_TRY(check_shapes(ro, env, pol));
     ARG_CHECK(T >= 1, "collect_rollouts!: T must be >= 1");
+    PPO_TRY(disk_sink_settle_previous(ro));        // a failed deferred finish of the previous file: nothing of this call starts
     const bool compact = want_compact(ro, T);
     PPO_TRY(rollouts_reserve(ro, T, compact));
     const int64_t N = env->N;

@@ -4,7 +4,8 @@
 // thread drains the pinned ring into one append-only file.
 //
 // File format (little endian): header {magic "PPOR", u32 version, i64 N, i32 H, i32 F, i32 A, i32 V, i64 T}
-// (version 2: then {u64 FNV-1a of the template-vertex table, i32 env kind, i32 0}, checked on load)
+// (version 2: then {u64 FNV-1a of the template-vertex table, i32 env kind, i32 0}, checked on load; the hash starts from
+//  1469598103934665603, the published offset basis less its last digit: part of the format, every file carries it)
 // then T step records  [states][active N u32][actions N i32][p_sel N f32][rewards N f32][done N u8]
 // then the returns column [T][N] f32 (written after compute_returns).
 //   version 1: states = the expanded observations, N*H*F int8 (2304 B per env-step for Q = 8)
@@ -69,6 +70,7 @@ struct DiskSink {
 // that fits PPO_DISK_ASYNC_MAX_BYTES (default 1 GiB), so the disk never holds the collection back
 static int g_disk_async = [] { const char* v = getenv("PPO_DISK_ASYNC"); return v ? atoi(v) != 0 : 0; }();
 extern "C" int32_t ppo_set_disk_async(int32_t mode) { g_disk_async = mode < 0 ? 0 : (mode != 0); return PPO_OK; }
+extern "C" int32_t ppo_get_disk_async(int32_t* mode) { ARG_CHECK(mode, "null"); *mode = g_disk_async; return PPO_OK; }
 static size_t disk_async_budget() { const char* v = getenv("PPO_DISK_ASYNC_MAX_BYTES"); return v ? (size_t)atoll(v) : ((size_t)1 << 30); }
 
 // Process-wide pool of pinned records: the reference creates a fresh DiskRollouts every PPO iteration
@@ -176,15 +178,35 @@ static bool disk_sink_settle(DiskSink* s) {
         s->cv.notify_all();
         s->writer.join();
     }
-    if (s->fin_pending) { ok = !s->failed && s->fin_done; s->fin_pending = false; }
-    if (s->f) { if (fclose(s->f) != 0) ok = false; s->f = nullptr; }
+    // only a deferred finish is reported from here: a synchronous collection that failed said so itself, and what is left of
+    // its file is closed without a second report
+    const bool pending = s->fin_pending;
+    if (pending) { ok = !s->failed && s->fin_done; s->fin_pending = false; }
+    if (s->f) { if (fclose(s->f) != 0 && pending) ok = false; s->f = nullptr; }
     return ok;
 }
 
-void disk_sink_destroy(DiskSink* s) {
-    if (!s) return;
-    (void)disk_sink_settle(s);
-    if (s->f) fclose(s->f);
+// Every reported write failure removes what there is of <dir>/rollout.bin: the directory never yields a dataset afterwards
+// (ppo_rollouts_load_disk: "trajectory file missing").  The name goes at once, the blocks when the stream is closed.
+static int32_t disk_sink_fail(DiskSink* s, const std::string& what) {
+    (void)unlink((s->dir + "/rollout.bin").c_str());
+    ppo_set_error("DiskRollouts: " + what + "; the incomplete rollout.bin was removed");
+    return PPO_ERR_ARG;
+}
+static const char* const kDeferredFailed = "a write of the deferred finish failed (disk full?)";
+
+// wait point: a deferred finish that failed is reported by the first of disk_sync, the next collection, detach and destroy
+int32_t disk_sink_settle_previous(ppo_rollouts_s* ro) {
+    DiskSink* s = ro->sink;
+    if (!s || disk_sink_settle(s)) return PPO_OK;
+    return disk_sink_fail(s, std::string(kDeferredFailed) + ": the previous collection's file is lost and this collection was not started");
+}
+
+// false: a deferred finish had failed and nobody had been told yet (ppo_last_error is set)
+bool disk_sink_destroy(DiskSink* s) {
+    if (!s) return true;
+    const bool ok = disk_sink_settle(s);
+    if (!ok) (void)disk_sink_fail(s, kDeferredFailed);
     // a device -> host copy may still be in flight into a record (error / early-detach paths): the records go back to a
     // process-wide pool, so nobody else may receive one before the copy stream has drained
     if (s->copy_stream) (void)hipStreamSynchronize(s->copy_stream);
@@ -196,9 +218,10 @@ void disk_sink_destroy(DiskSink* s) {
     for (auto e : s->copied) (void)hipEventDestroy(e);
     if (s->copy_stream) (void)hipStreamDestroy(s->copy_stream);
     delete s;
+    return ok;
 }
 
-ppo_rollouts_s::~ppo_rollouts_s() { disk_sink_destroy(sink); sink = nullptr; }
+ppo_rollouts_s::~ppo_rollouts_s() { (void)disk_sink_destroy(sink); sink = nullptr; }   // no status to return: ppo_last_error stays set
 
 static size_t state_bytes(const ppo_rollouts_s* ro, bool compact) {
     return (size_t)ro->N * (compact ? (size_t)2 * ro->V : (size_t)ro->H * ro->F);
@@ -211,7 +234,11 @@ static size_t record_bytes(const ppo_rollouts_s* ro, bool compact) {
 extern "C" int32_t ppo_rollouts_attach_disk(ppo_rollouts_t ro, const char* dir, int32_t pinned_slots) {
     ARG_CHECK(ro && dir && dir[0], "DiskRollouts: bad argument");
     ARG_CHECK(pinned_slots >= 2 && pinned_slots <= 64, "DiskRollouts: 2..64 pinned slots");
-    if (ro->sink) { disk_sink_destroy(ro->sink); ro->sink = nullptr; }
+    if (ro->sink) {                                             // a wait point like detach
+        const bool ok = disk_sink_destroy(ro->sink);
+        ro->sink = nullptr;
+        if (!ok) return PPO_ERR_ARG;
+    }
     // prepare_state_data_directory: wipe and recreate (src/rollouts_to_disk.jl:7-13)
     if (rm_rf(dir) != 0) { ppo_set_error(std::string("DiskRollouts: cannot clear ") + dir); return PPO_ERR_ARG; }
     if (mkdir(dir, 0777) != 0) { ppo_set_error(std::string("DiskRollouts: cannot create ") + dir); return PPO_ERR_ARG; }
@@ -234,9 +261,9 @@ extern "C" int32_t ppo_rollouts_attach_disk(ppo_rollouts_t ro, const char* dir, 
 
 extern "C" int32_t ppo_rollouts_detach_disk(ppo_rollouts_t ro) {
     ARG_CHECK(ro, "null");
-    disk_sink_destroy(ro->sink);
+    const bool ok = disk_sink_destroy(ro->sink);               // the sink is gone either way
     ro->sink = nullptr;
-    return PPO_OK;
+    return ok ? PPO_OK : PPO_ERR_ARG;
 }
 
 int disk_sink_slots(const ppo_rollouts_s* ro) { return ro->sink ? ro->sink->slots : 0; }
@@ -246,14 +273,14 @@ int disk_sink_chunk(const ppo_rollouts_s* ro) { return ro->sink ? std::max(1, st
 extern "C" int32_t ppo_rollouts_disk_sync(ppo_rollouts_t ro) {
     ARG_CHECK(ro, "null");
     if (!ro->sink) return PPO_OK;
-    if (!disk_sink_settle(ro->sink)) { ppo_set_error("DiskRollouts: writer failed (disk full?)"); return PPO_ERR_ARG; }
+    if (!disk_sink_settle(ro->sink)) return disk_sink_fail(ro->sink, kDeferredFailed);
     return PPO_OK;
 }
 
 int32_t disk_sink_begin(ppo_rollouts_s* ro, int64_t T) {
     DiskSink* s = ro->sink;
     if (!s) return PPO_OK;
-    (void)disk_sink_settle(s);                        // a previous collection (its deferred finish included): restart the file
+    PPO_TRY(disk_sink_settle_previous(ro));           // a previous collection (its deferred finish included): restart the file
     s->enq = s->written = 0; s->stop = false; s->failed = false; s->fin_pending = s->fin_done = false;
     const size_t rec = record_bytes(ro, ro->compact);           // the storage form is decided per collection
     if (s->copy_stream) HIP_TRY(hipStreamSynchronize(s->copy_stream));   // nothing of a previous collection is still landing
@@ -323,7 +350,7 @@ int32_t disk_sink_step(ppo_rollouts_s* ro, int64_t t) {
         std::unique_lock<std::mutex> lk(s->mu);
         s->cv.wait(lk, [&] { return s->failed || s->written + s->slots > t; });
     }
-    if (s->failed) { ppo_set_error("DiskRollouts: writer failed (disk full?)"); return PPO_ERR_ARG; }
+    if (s->failed) return disk_sink_fail(s, "a record write failed (disk full?)");
     const size_t N = (size_t)ro->N, sb = state_bytes(ro, ro->compact);
     HIP_TRY(hipEventRecord(s->produced[slot], ppo_stream()));
     HIP_TRY(hipStreamWaitEvent(s->copy_stream, s->produced[slot], 0));
@@ -370,13 +397,15 @@ int32_t disk_sink_finish(ppo_rollouts_s* ro) {
     }
     s->cv.notify_all();
     s->writer.join();
-    if (s->failed) { ppo_set_error("DiskRollouts: writer failed"); return PPO_ERR_ARG; }
+    if (s->failed) return disk_sink_fail(s, "a record write failed (disk full?)");
     // returns column (the reference rewrites trajectory.csv with the returns at this point)
     const size_t n = (size_t)ro->T * ro->N;
     std::vector<float> ret(n);
     PPO_TRY(d2h(ret.data(), ro->returns.p, n));
-    if (fseek(s->f, 0, SEEK_END) != 0 || fwrite(ret.data(), 4, n, s->f) != n) { ppo_set_error("DiskRollouts: returns write failed"); return PPO_ERR_ARG; }
-    fclose(s->f); s->f = nullptr;
+    if (fseek(s->f, 0, SEEK_END) != 0 || fwrite(ret.data(), 4, n, s->f) != n) return disk_sink_fail(s, "the returns column write failed (disk full?)");
+    // the stream keeps the tail of a large fwrite in its buffer: a write error there shows only when it is flushed
+    FILE* f = s->f; s->f = nullptr;
+    if (fclose(f) != 0) return disk_sink_fail(s, "the returns column write failed when the file was closed (disk full?)");
     return PPO_OK;
 }
 

@@ -259,7 +259,8 @@ int disk_sink_slots(const ppo_rollouts_s* ro);                // pinned records 
 int disk_sink_chunk(const ppo_rollouts_s* ro);                // steps per persistent launch of a streamed collection
 int32_t disk_sink_step(ppo_rollouts_s* ro, int64_t t);       // after the kernels of step t were enqueued
 int32_t disk_sink_finish(ppo_rollouts_s* ro);                // after the return scan: appends returns, flushes
-void disk_sink_destroy(DiskSink* s);
+bool disk_sink_destroy(DiskSink* s);                           // false: an unreported deferred-finish failure (ppo_last_error set)
+int32_t disk_sink_settle_previous(ppo_rollouts_s* ro);         // waits for a deferred finish; its failure is reported here
 
 // ---------------------------------------------------------------- packed layout sizes
 // one gradient slab: [dW of the L-1 hidden->hidden layers][dW1, input padded to 32][db1][db of the L-1 layers][dW3][db3 + pad]
