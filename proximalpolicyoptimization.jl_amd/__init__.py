@@ -1739,35 +1739,33 @@ def average_returns(policy, env, num_trajectories):
     the actions are chosen under policy.selection; the default is the reference's rule."""
     if not isinstance(env, HipVecEnv):
         return generic.average_returns_host(_this_module(), policy, env, num_trajectories)
-    scratch = BufferRollouts()
     per_env = -(-int(num_trajectories) // env.N)
-    h = scratch._ensure(env, per_env * env.max_actions)
-    m, s = C.c_double(0), C.c_double(0)
-    call("ppo_average_returns", policy._h, env._h, h, int(num_trajectories), C.byref(m), C.byref(s))
-    return m.value, s.value
+    return _mean_std("ppo_average_returns", env, policy, num_trajectories, per_env * env.max_actions)
 
 
-def _evaluator_scratch(env):
+def _evaluator_scratch(env, T=1):
     scratch = BufferRollouts()
-    return scratch, scratch._ensure(env, 1)
+    return scratch, scratch._ensure(env, T)
+
+
+def _mean_std(name, env, policy, num_trajectories, scratch_T=1):
+    """(mean, std) of the evaluator export `name` over num_trajectories trajectories, on a scratch buffer of scratch_T steps."""
+    scratch, h = _evaluator_scratch(env, scratch_T)
+    m, s = C.c_double(0), C.c_double(0)
+    call(name, policy._h, env._h, h, int(num_trajectories), C.byref(m), C.byref(s))
+    return m.value, s.value
 
 
 def average_best_returns(env, policy, num_trajectories):
     """average_best_returns(wrapper, policy, num_trajectories) (test/quad_game_utilities.jl:299-307; note the
     reference's argument order: env first) -> (mean, std) of initial_score - lowest score seen on the trajectory."""
-    scratch, h = _evaluator_scratch(env)
-    m, s = C.c_double(0), C.c_double(0)
-    call("ppo_average_best_returns", policy._h, env._h, h, int(num_trajectories), C.byref(m), C.byref(s))
-    return m.value, s.value
+    return _mean_std("ppo_average_best_returns", env, policy, num_trajectories)
 
 
 def average_normalized_returns(env, policy, num_trajectories):
     """average_normalized_returns(wrapper, policy, num_trajectories) (test/quad_game_utilities.jl:380-387) ->
     (mean, std) of best return / (initial_score - opt_score); a trajectory that starts at its optimum counts 1.0."""
-    scratch, h = _evaluator_scratch(env)
-    m, s = C.c_double(0), C.c_double(0)
-    call("ppo_average_normalized_returns", policy._h, env._h, h, int(num_trajectories), C.byref(m), C.byref(s))
-    return m.value, s.value
+    return _mean_std("ppo_average_normalized_returns", env, policy, num_trajectories)
 
 
 def evaluate_trajectories(env, policy, num_trajectories, kind):
@@ -1873,6 +1871,23 @@ def count_non_flips(env, policy, rng=None):
     return r["type_counts"][:, 2:].sum(axis=1, dtype=np.int64)
 
 
+def _search_io(env, sc, dg, act, K, clone_gaps):
+    """What both searches pass and return: (scratch, args, out, cg) -- the scratch buffer (the caller keeps it alive across the
+    call), the exports' common arguments from the env handle to clone_gaps, the result dict over freshly allocated output
+    arrays, and the clone_gaps array or None."""
+    M, V = sc.shape[0], 4 * env.Q
+    scratch, h = _evaluator_scratch(env)
+    st, bact = np.zeros((M, 2 * V), np.int8), np.zeros(M, np.uint32)
+    gap, clone, step, init = (np.zeros(M, np.int32) for _ in range(4))
+    cg = np.zeros((M, K), np.int32) if clone_gaps else None
+    args = (env._h, h, M, K, _p(sc, _lib.c_i8p), _p(dg, _lib.c_i8p), _p(act, _lib.c_u32p),
+            _p(st, _lib.c_i8p), _p(bact, _lib.c_u32p), _p(gap, _lib.c_i32p), _p(clone, _lib.c_i32p), _p(step, _lib.c_i32p),
+            _p(init, _lib.c_i32p), None if cg is None else _p(cg, _lib.c_i32p))
+    out = dict(best_state=st, best_score=st[:, :V], best_degree=st[:, V:], best_active=bact, best_gap=gap, best_clone=clone,
+               best_step=step, initial_gap=init)
+    return scratch, args, out, cg
+
+
 def search_best_states_(env, policy, score, degree, active, K, clone_gaps=False, path=False):
     """Best of K stochastic trajectories from each caller-supplied start state (score, degree [M, 4Q], active [M]):
     K resident envs are loaded with one start and, sampling being keyed on (global env id, tick), play K different
@@ -1882,23 +1897,15 @@ def search_best_states_(env, policy, score, degree, active, K, clone_gaps=False,
     the envs that played are left terminal.  path=True adds path [M, max_actions] int16: the winner's best_step 1-based
     actions from the start to best_state, 0 behind them (apply_paths_ replays them)."""
     sc, dg, act = check_internal(score, degree, active, env.Q)
-    M, V, K = sc.shape[0], 4 * env.Q, int(K)
+    K = int(K)
     if not 1 <= K <= env.N:
         raise PPOError(-1, "AssertionError: search_best_states: 1 <= K <= N")
-    scratch, h = _evaluator_scratch(env)
-    st, bact = np.zeros((M, 2 * V), np.int8), np.zeros(M, np.uint32)
-    gap, clone, step, init = (np.zeros(M, np.int32) for _ in range(4))
-    cg = np.zeros((M, K), np.int32) if clone_gaps else None
-    args = (policy._h, env._h, h, M, K, _p(sc, _lib.c_i8p), _p(dg, _lib.c_i8p), _p(act, _lib.c_u32p),
-            _p(st, _lib.c_i8p), _p(bact, _lib.c_u32p), _p(gap, _lib.c_i32p), _p(clone, _lib.c_i32p), _p(step, _lib.c_i32p),
-            _p(init, _lib.c_i32p), None if cg is None else _p(cg, _lib.c_i32p))
+    scratch, args, out, cg = _search_io(env, sc, dg, act, K, clone_gaps)
     if path:
-        pa = np.zeros((M, env.max_actions), np.int16)
-        call("ppo_search_best_states_path", *args, _p(pa, _lib.c_i16p))
+        pa = np.zeros((sc.shape[0], env.max_actions), np.int16)
+        call("ppo_search_best_states_path", policy._h, *args, _p(pa, _lib.c_i16p))
     else:
-        call("ppo_search_best_states", *args)
-    out = dict(best_state=st, best_score=st[:, :V], best_degree=st[:, V:], best_active=bact, best_gap=gap, best_clone=clone,
-               best_step=step, initial_gap=init)
+        call("ppo_search_best_states", policy._h, *args)
     if clone_gaps:
         out["clone_gaps"] = cg
     if path:
@@ -2003,18 +2010,13 @@ def search_resample_states_(env, policy, score, degree, active, K, interval, sur
     if critic is not None and not (np.isfinite(np.float32(value_weight)) and float(value_weight) >= 0.0):
         raise PPOError(-1, "AssertionError: search_resample_states: value_weight must be finite and >= 0")
     sc, dg, act = check_internal(score, degree, active, env.Q)
-    M, V = sc.shape[0], 4 * env.Q
+    M = sc.shape[0]
     K, R, m0 = check_resample(env.N, K, interval, survivors)
-    scratch, h = _evaluator_scratch(env)
-    st, bact = np.zeros((M, 2 * V), np.int8), np.zeros(M, np.uint32)
-    gap, clone, step, init = (np.zeros(M, np.int32) for _ in range(4))
-    cg = np.zeros((M, K), np.int32) if clone_gaps else None
+    scratch, args, out, cg = _search_io(env, sc, dg, act, K, clone_gaps)
+    args += (R, m0)
     dn = np.full((M, (env.max_actions - 1) // R, K), -2, np.int32) if donors else None
     ev = np.full((M, (env.max_actions - 1) // R, K), np.nan, np.float32) if values else None
     pa = np.zeros((M, env.max_actions), np.int16) if path else None
-    args = (env._h, h, M, K, _p(sc, _lib.c_i8p), _p(dg, _lib.c_i8p),
-            _p(act, _lib.c_u32p), _p(st, _lib.c_i8p), _p(bact, _lib.c_u32p), _p(gap, _lib.c_i32p), _p(clone, _lib.c_i32p),
-            _p(step, _lib.c_i32p), _p(init, _lib.c_i32p), None if cg is None else _p(cg, _lib.c_i32p), R, m0)
     dnp = None if dn is None else _p(dn, _lib.c_i32p)
     if critic is not None:
         call("ppo_search_resample_states_value", policy._h, critic._h, *args, float(value_weight), dnp,
@@ -2023,8 +2025,6 @@ def search_resample_states_(env, policy, score, degree, active, K, interval, sur
         call("ppo_search_resample_states_path", policy._h, *args, dnp, _p(pa, _lib.c_i16p))
     else:
         call("ppo_search_resample_states", policy._h, *args, dnp)
-    out = dict(best_state=st, best_score=st[:, :V], best_degree=st[:, V:], best_active=bact, best_gap=gap, best_clone=clone,
-               best_step=step, initial_gap=init)
     if donors:
         out["donors"] = dn
     if clone_gaps:

@@ -1,13 +1,13 @@
-// ppo_api.hip -- extern "C" surface of libppo_hip.so (include/ppo_hip.h): engine state, handle management and
-// the host-side orchestration of collect_rollouts! (launch order only; all math is in the kernels); training
-// and the critic are in ppo_train.hip.  There is NO CPU fallback: every entry point runs on the GPU or fails.
+// ppo_api.hip -- extern "C" surface of libppo_hip.so (include/ppo_hip.h): engine state, handle management (env, policy,
+// optimiser, rollout buffer) and the host-side orchestration of the step-mode collect_rollouts! (launch order only; all math
+// is in the kernels); the calls that play whole episodes, evaluate and search are in ppo_play.hip, training and the critic
+// in ppo_train.hip.  There is NO CPU fallback: every entry point runs on the GPU or fails.
 #include "ppo_internal.h"
 #include "ppo_device.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <mutex>
 
 
@@ -300,7 +300,7 @@ int32_t ppo_env_dims(ppo_env_t env, int64_t* N, int32_t* H, int32_t* F, int32_t*
 // observations of the requested rollout would exceed PPO_COMPACT_AUTO_BYTES -- default 32 GiB: re-deriving the rows costs
 // the train forward 3 % in fp32 and 17 % in bf16 mode, so below that the 288 GB of HBM are spent on speed -- or when a disk
 // sink is attached: the stream then carries 64 + 4 instead of 2304 + 4 state bytes per env-step for Q = 8
-static bool want_compact(const ppo_rollouts_s* ro, int64_t T) {
+bool want_compact(const ppo_rollouts_s* ro, int64_t T) {
     const PpoKnobs& k = ppo_knobs();
     if (ro->V == 0) return false;                             // created by shape: no env snapshot form
     if (k.rollout_compact >= 0) return k.rollout_compact == 1;
@@ -364,7 +364,7 @@ int32_t ppo_env_get_internal(ppo_env_t env, int8_t* score, int8_t* degree, int32
 
 // what ppo_env_set_internal and ppo_search_best_states require of caller-supplied env states ([count][V] each, [count]
 // active-quad words): a state reset! or step! could have left.  Checked on the host before anything is uploaded
-static int32_t check_internal_host(int32_t Q, int64_t count, const int8_t* score, const int8_t* degree, const uint32_t* active) {
+int32_t check_internal_host(int32_t Q, int64_t count, const int8_t* score, const int8_t* degree, const uint32_t* active) {
     const int V = 4 * Q;
     for (int64_t n = 0; n < count; ++n) {
         const uint32_t act = active[n];
@@ -540,6 +540,38 @@ int32_t ppo_policy_forward(ppo_policy_t pol, const int8_t* states, const uint32_
     PPO_TRY(h2d(s.p, states, ns)); PPO_TRY(h2d(a.p, active, (size_t)B));
     PPO_TRY(launch_policy_probs(pol, s.p, a.p, B, H, p.p));
     return d2h(probs, p.p, (size_t)B * H * 4);
+}
+
+// ---- action selection of the calls behind play_quotas (ppo_play.hip; no reference op): a property of the
+// policy handle
+int32_t ppo_policy_set_selection(ppo_policy_t pol, int32_t rule, double temperature) {
+    ARG_CHECK(rule == PPO_SELECT_SAMPLE || rule == PPO_SELECT_GREEDY, "policy_set_selection: rule must be 0 (sample) or 1 (greedy)");
+    ARG_CHECK(std::isfinite(temperature) && temperature > 0.0, "policy_set_selection: temperature must be finite and > 0");
+    ARG_CHECK(pol, "policy_set_selection: null policy");
+    pol->select_rule = rule;
+    pol->select_temperature = temperature;
+    return PPO_OK;
+}
+int32_t ppo_policy_get_selection(ppo_policy_t pol, int32_t* rule, double* temperature) {
+    ARG_CHECK(pol && rule && temperature, "policy_get_selection: null argument");
+    *rule = pol->select_rule;
+    *temperature = pol->select_temperature;
+    return PPO_OK;
+}
+// ---- truncation of the distribution the "sample" rule draws from (DESIGN.md 7n; no reference op), read where the selection is
+int32_t ppo_policy_set_truncation(ppo_policy_t pol, int32_t top_k, double top_p) {
+    ARG_CHECK(top_k >= 0, "policy_set_truncation: top_k must be >= 0 (0: no limit)");
+    ARG_CHECK(top_p > 0.0 && top_p <= 1.0, "policy_set_truncation: top_p must be in (0, 1] (1: no limit)");     // NaN fails both
+    ARG_CHECK(pol, "policy_set_truncation: null policy");
+    pol->trunc_top_k = top_k;
+    pol->trunc_top_p = top_p;
+    return PPO_OK;
+}
+int32_t ppo_policy_get_truncation(ppo_policy_t pol, int32_t* top_k, double* top_p) {
+    ARG_CHECK(pol && top_k && top_p, "policy_get_truncation: null argument");
+    *top_k = pol->trunc_top_k;
+    *top_p = pol->trunc_top_p;
+    return PPO_OK;
 }
 
 // ================================================================ optimiser
@@ -739,7 +771,7 @@ int32_t set_index_all(ppo_rollouts_s* r) {
     return PPO_OK;
 }
 
-static int32_t check_shapes(ppo_rollouts_s* ro, ppo_env_s* env, ppo_policy_s* pol) {
+int32_t check_shapes(ppo_rollouts_s* ro, ppo_env_s* env, ppo_policy_s* pol) {
     ARG_CHECK(ro && env && pol, "collect_rollouts!: null argument");
     ARG_CHECK(ro->N == env->N && ro->H == env->H && ro->F == env->F, "collect_rollouts!: rollouts were created for another env shape");
     ARG_CHECK(pol->F == env->F, "collect_rollouts!: policy input width != env feature count");
@@ -798,685 +830,12 @@ int32_t ppo_collect_rollouts(ppo_rollouts_t ro, ppo_env_t env, ppo_policy_t pol,
         PPO_TRY(disk_sink_step(ro, t));                 // out-of-core store: async D2H of step t on the copy stream
     }
     }
-    ro->T = T; ro->adv_T = -1; ro->values_T = -1; ro->boot_T = -1;
+    rollouts_filled(ro, T);
     PPO_TRY(set_index_all(ro));
     // compute_state_value!: returns overwrite the rewards column (src/rollout_buffer.jl:55-64)
     PPO_TRY(launch_returns_tn(ro->rewards.p, ro->done.p, ro->returns.p, T, N, discount, discount_is_f32));
     PPO_TRY(disk_sink_finish(ro));
     return ppo_env_check_errors(env, nullptr);
-}
-
-// episode e of the call is played by env e mod N: env n plays episodes n, n + N, n + 2N, ... below num_episodes
-__global__ void k_episode_quota(int32_t* left, int64_t N, int64_t num_episodes) {
-    const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (n < N) left[n] = n < num_episodes ? (int32_t)((num_episodes - n + N - 1) / N) : 0;
-}
-
-int32_t ppo_collect_rollouts_episodes(ppo_rollouts_t ro, ppo_env_t env, ppo_policy_t pol, int64_t num_episodes,
-                                      double discount, int32_t discount_is_f32) {
-    PPO_TRY(check_shapes(ro, env, pol));
-    ARG_CHECK(num_episodes >= 1, "collect_rollouts!: num_episodes must be >= 1");
-    const int64_t N = env->N;
-    const int64_t episodes_per_env = (num_episodes + N - 1) / N;       // the busiest env (env 0)
-    const int64_t Tmax = episodes_per_env * env->max_actions;
-    const bool compact = want_compact(ro, Tmax);
-    PPO_TRY(rollouts_reserve(ro, Tmax, compact));
-    const size_t srow = (size_t)N * env->H * env->F, crow = (size_t)N * 2 * env->V;
-    if (compact) PPO_TRY(env->obs_tmp.alloc(srow));
-    hipLaunchKernelGGL(k_episode_quota, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, g_stream, env->episodes_left.p, N,
-                       num_episodes);
-    PPO_TRY(launch_env_reset(env, 0));                                  // reset!(env) before the first episode
-    std::vector<int32_t> left((size_t)N);
-    int64_t T = 0;
-    for (int64_t t = 0; t < Tmax; ++t) {
-        int8_t* st = compact ? env->obs_tmp.p : ro->states.p + (size_t)t * srow;
-        uint32_t* am = ro->active.p + (size_t)t * N;
-        PPO_TRY(launch_env_observe(env, st, am));
-        if (compact) PPO_TRY(launch_env_snapshot(env, ro->cstate.p + (size_t)t * crow));
-        PPO_TRY(launch_policy_rollout(pol, env, st, am, ro->actions.p + t * N, ro->p_sel.p + t * N, nullptr));
-        PPO_TRY(launch_env_step(env, ro->actions.p + t * N, ro->rewards.p + t * N, ro->done.p + t * N,
-                                ro->valid.p + t * N, 0, 1));
-        T = t + 1;
-        if ((t & 7) == 7 || t + 1 == Tmax) {            // poll completion every 8 steps
-            PPO_TRY(d2h(left.data(), env->episodes_left.p, (size_t)N));
-            bool all = true;
-            for (int64_t n = 0; n < N; ++n) if (left[n] > 0) { all = false; break; }
-            if (all) break;
-        }
-    }
-    ro->T = T; ro->adv_T = -1; ro->values_T = -1; ro->boot_T = -1;
-    // dataset order = env-major concatenation of whole episodes (the reference's flat buffer)
-    std::vector<uint8_t> valid((size_t)T * N);
-    PPO_TRY(d2h(valid.data(), ro->valid.p, (size_t)T * N));
-    std::vector<int32_t> index;
-    index.reserve((size_t)T * N);
-    for (int64_t n = 0; n < N; ++n)
-        for (int64_t t = 0; t < T; ++t)
-            if (valid[(size_t)t * N + n]) index.push_back((int32_t)(t * N + n));
-    ro->len = (int64_t)index.size();
-    ro->all_valid = false;
-    PPO_TRY(h2d(ro->index.p, index.data(), index.size()));
-    PPO_TRY(launch_returns_tn(ro->rewards.p, ro->done.p, ro->returns.p, T, N, discount, discount_is_f32));
-    return ppo_env_check_errors(env, nullptr);
-}
-
-static int32_t evaluate_impl(ppo_policy_s* pol, ppo_env_s* env, ppo_rollouts_s* scratch, int64_t num_traj, int32_t kind,
-                             std::vector<double>& values);
-static void mean_std(const std::vector<double>& x, double* mean, double* std);
-
-// average_returns (src/evaluate.jl:18-25): undiscounted return of each whole episode, then Flux.mean / Flux.std
-int32_t ppo_average_returns(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_trajectories,
-                            double* mean, double* std) {
-    ARG_CHECK(pol && env && scratch && mean && std && num_trajectories >= 1, "average_returns: bad argument");
-    if (!default_selection(pol) || !default_truncation(pol)) {     // the collectors never read the selection or the truncation: kind 1 of the evaluators is the same statistic
-        std::vector<double> v;
-        PPO_TRY(evaluate_impl(pol, env, scratch, num_trajectories, 1, v));
-        mean_std(v, mean, std);
-        return PPO_OK;
-    }
-    const int64_t N = env->N;
-    const int64_t per_env = (num_trajectories + N - 1) / N;
-    PPO_TRY(ppo_collect_rollouts_episodes(scratch, env, pol, num_trajectories, 1.0, 0));   // exactly num_trajectories (:19-22)
-    const int64_t T = scratch->T;
-    std::vector<float> r((size_t)T * N);
-    std::vector<uint8_t> dn((size_t)T * N), va((size_t)T * N);
-    PPO_TRY(d2h(r.data(), scratch->rewards.p, r.size()));
-    PPO_TRY(d2h(dn.data(), scratch->done.p, dn.size()));
-    PPO_TRY(d2h(va.data(), scratch->valid.p, va.size()));
-    std::vector<double> rets;
-    rets.reserve((size_t)per_env * N);
-    for (int64_t n = 0; n < N; ++n) {
-        double acc = 0.0;
-        for (int64_t t = 0; t < T; ++t) {
-            const size_t i = (size_t)t * N + n;
-            if (!va[i]) continue;
-            acc += (double)r[i];                         // ret += reward(env)   src/evaluate.jl:13
-            if (dn[i]) { rets.push_back(acc); acc = 0.0; }
-        }
-    }
-    ARG_CHECK(!rets.empty(), "average_returns: no complete episode");
-    double m = 0.0;
-    for (double x : rets) m += x;
-    m /= (double)rets.size();
-    double v = 0.0;
-    for (double x : rets) v += (x - m) * (x - m);
-    *mean = m;
-    *std = rets.size() > 1 ? std::sqrt(v / (double)(rets.size() - 1)) : NAN;   // Flux.std: corrected (n-1)
-    return PPO_OK;
-}
-
-// Evaluator variants on the device (test/quad_game_utilities.jl:280-307,369-387; kind 1 = src/evaluate.jl:1-16): exactly
-// num_trajectories whole episodes, trajectory e on resident env e mod N like ppo_collect_rollouts_episodes; the
-// per-episode value is tracked inside the env step (k_env_step, EvalView), nothing but one value per trajectory
-// comes back.  Row 0 of `scratch` is the only rollout storage touched.  values: [num_trajectories], env-major.
-// The step loop of the evaluators and of the best-state search: observe, policy forward + sample, env step with the
-// bookkeeping of `ev` (k_env_step) or `tv` (k_env_step_track), until every env has used up its episodes_left (polled every
-// 8 steps) or Tmax steps have run.  Row 0 of `scratch` is the only rollout storage touched.
-// The action is chosen under the policy's selection (ppo_policy_set_selection; the default is the sampled rollout step).
-// after_step (optional) runs behind the env step of loop step t, before the poll (the resampling search's events).
-static int32_t play_quotas(ppo_policy_s* pol, ppo_env_s* env, ppo_rollouts_s* scratch, int64_t Tmax, const EvalView* ev,
-                           const TrackView* tv, bool* all_done, const std::function<int32_t(int64_t)>* after_step = nullptr) {
-    const int64_t N = env->N;
-    std::vector<int32_t> left((size_t)N);
-    bool all = false;
-    for (int64_t t = 0; t < Tmax && !all; ++t) {
-        PPO_TRY(launch_env_observe(env, scratch->states.p, scratch->active.p));
-        PPO_TRY(launch_policy_select(pol, env, scratch->states.p, scratch->active.p, scratch->actions.p, scratch->p_sel.p, nullptr));
-        if (tv) PPO_TRY(launch_env_step_track(env, scratch->actions.p, scratch->rewards.p, scratch->done.p, scratch->valid.p, *tv));
-        else PPO_TRY(launch_env_step(env, scratch->actions.p, scratch->rewards.p, scratch->done.p, scratch->valid.p, 0, 1, ev));
-        if (after_step) PPO_TRY((*after_step)(t));
-        if ((t & 7) == 7 || t + 1 == Tmax) {            // poll completion every 8 steps
-            PPO_TRY(d2h(left.data(), env->episodes_left.p, (size_t)N));
-            all = true;
-            for (int64_t n = 0; n < N; ++n) if (left[n] > 0) { all = false; break; }
-        }
-    }
-    *all_done = all;
-    return PPO_OK;
-}
-
-static int32_t evaluate_impl(ppo_policy_s* pol, ppo_env_s* env, ppo_rollouts_s* scratch, int64_t num_traj, int32_t kind,
-                             std::vector<double>& values) {
-    PPO_TRY(check_shapes(scratch, env, pol));
-    ARG_CHECK(num_traj >= 1, "evaluator: num_trajectories must be >= 1");
-    ARG_CHECK(kind >= 1 && kind <= 3, "evaluator: kind must be 1 (return), 2 (best return) or 3 (normalised best return)");
-    const int64_t N = env->N;
-    const int64_t per_env = (num_traj + N - 1) / N;
-    const int64_t Tmax = per_env * ((int64_t)env->max_actions + 1);      // + 1: a skipped (maxreturn == 0) episode costs one step
-    PPO_TRY(rollouts_reserve(scratch, 1, false));
-    DevBuf<double> ep_ret, out; DevBuf<int32_t> ep_i;
-    PPO_TRY(ep_ret.alloc((size_t)N)); PPO_TRY(out.alloc((size_t)num_traj)); PPO_TRY(ep_i.alloc((size_t)4 * N));
-    HIP_TRY(hipMemsetAsync(ep_ret.p, 0, (size_t)N * 8, g_stream));
-    HIP_TRY(hipMemsetAsync(ep_i.p, 0, (size_t)4 * N * 4, g_stream));
-    HIP_TRY(hipMemsetAsync(out.p, 0, (size_t)num_traj * 8, g_stream));
-    EvalView ev;
-    ev.kind = kind; ev.ep_ret = ep_ret.p; ev.ep_init = ep_i.p; ev.ep_min = ep_i.p + N; ev.ep_maxret = ep_i.p + 2 * N;
-    ev.ep_count = ep_i.p + 3 * N; ev.out = out.p; ev.num_traj = num_traj;
-    hipLaunchKernelGGL(k_episode_quota, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, g_stream, env->episodes_left.p, N,
-                       num_traj);
-    PPO_TRY(launch_env_reset(env, 0));                                  // reset!(env) before the first trajectory
-    bool all = false;
-    PPO_TRY(play_quotas(pol, env, scratch, Tmax, &ev, nullptr, &all));
-    ARG_CHECK(all, "evaluator: the episodes did not finish within max_actions steps each");
-    scratch->T = 0; scratch->len = 0; scratch->adv_T = -1; scratch->values_T = -1; scratch->boot_T = -1;
-    values.resize((size_t)num_traj);
-    PPO_TRY(d2h(values.data(), out.p, (size_t)num_traj));
-    return ppo_env_check_errors(env, nullptr);
-}
-
-static void mean_std(const std::vector<double>& x, double* mean, double* std) {
-    double m = 0.0;
-    for (double v : x) m += v;
-    m /= (double)x.size();
-    double s = 0.0;
-    for (double v : x) s += (v - m) * (v - m);
-    *mean = m;
-    *std = x.size() > 1 ? std::sqrt(s / (double)(x.size() - 1)) : NAN;   // Flux.std: corrected (n-1)
-}
-
-// ---- action selection of the calls behind play_quotas (no reference op): a property of the policy handle
-int32_t ppo_policy_set_selection(ppo_policy_t pol, int32_t rule, double temperature) {
-    ARG_CHECK(rule == PPO_SELECT_SAMPLE || rule == PPO_SELECT_GREEDY, "policy_set_selection: rule must be 0 (sample) or 1 (greedy)");
-    ARG_CHECK(std::isfinite(temperature) && temperature > 0.0, "policy_set_selection: temperature must be finite and > 0");
-    ARG_CHECK(pol, "policy_set_selection: null policy");
-    pol->select_rule = rule;
-    pol->select_temperature = temperature;
-    return PPO_OK;
-}
-int32_t ppo_policy_get_selection(ppo_policy_t pol, int32_t* rule, double* temperature) {
-    ARG_CHECK(pol && rule && temperature, "policy_get_selection: null argument");
-    *rule = pol->select_rule;
-    *temperature = pol->select_temperature;
-    return PPO_OK;
-}
-// ---- truncation of the distribution the "sample" rule draws from (DESIGN.md 7n; no reference op), read where the selection is
-int32_t ppo_policy_set_truncation(ppo_policy_t pol, int32_t top_k, double top_p) {
-    ARG_CHECK(top_k >= 0, "policy_set_truncation: top_k must be >= 0 (0: no limit)");
-    ARG_CHECK(top_p > 0.0 && top_p <= 1.0, "policy_set_truncation: top_p must be in (0, 1] (1: no limit)");     // NaN fails both
-    ARG_CHECK(pol, "policy_set_truncation: null policy");
-    pol->trunc_top_k = top_k;
-    pol->trunc_top_p = top_p;
-    return PPO_OK;
-}
-int32_t ppo_policy_get_truncation(ppo_policy_t pol, int32_t* top_k, double* top_p) {
-    ARG_CHECK(pol && top_k && top_p, "policy_get_truncation: null argument");
-    *top_k = pol->trunc_top_k;
-    *top_p = pol->trunc_top_p;
-    return PPO_OK;
-}
-// diagnostic for the tests (not part of include/ppo_hip.h), like ppo_debug_train_ratios: what one step of play_quotas would
-// choose for every env from the state and tick it holds -- observe, launch_policy_select -- WITHOUT the env step: actions [N]
-// (0-based) and p_sel [N], which no call behind play_quotas returns.  The envs keep state, tick and counters; their flag word
-// takes the tail's bits
-extern "C" int32_t ppo_debug_select_step(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int32_t* actions, float* p_sel) {
-    ARG_CHECK(pol && env && scratch && actions && p_sel, "ppo_debug_select_step: null argument");
-    PPO_TRY(check_shapes(scratch, env, pol));
-    PPO_TRY(rollouts_reserve(scratch, 1, false));
-    PPO_TRY(launch_env_observe(env, scratch->states.p, scratch->active.p));
-    PPO_TRY(launch_policy_select(pol, env, scratch->states.p, scratch->active.p, scratch->actions.p, scratch->p_sel.p, nullptr));
-    scratch->T = 0; scratch->len = 0; scratch->adv_T = -1; scratch->values_T = -1; scratch->boot_T = -1;
-    PPO_TRY(d2h(actions, scratch->actions.p, (size_t)env->N));
-    return d2h(p_sel, scratch->p_sel.p, (size_t)env->N);
-}
-
-int32_t ppo_evaluate_trajectories(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_trajectories,
-                                  int32_t kind, double* values) {
-    ARG_CHECK(pol && env && scratch && values, "evaluator: null argument");
-    std::vector<double> v;
-    PPO_TRY(evaluate_impl(pol, env, scratch, num_trajectories, kind, v));
-    std::memcpy(values, v.data(), v.size() * sizeof(double));
-    return PPO_OK;
-}
-
-// average_best_returns(wrapper, policy, num_trajectories)         test/quad_game_utilities.jl:299-307
-int32_t ppo_average_best_returns(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_trajectories,
-                                 double* mean, double* std) {
-    ARG_CHECK(pol && env && scratch && mean && std, "average_best_returns: null argument");
-    std::vector<double> v;
-    PPO_TRY(evaluate_impl(pol, env, scratch, num_trajectories, 2, v));
-    mean_std(v, mean, std);
-    return PPO_OK;
-}
-
-// average_normalized_returns(wrapper, policy, num_trajectories)   test/quad_game_utilities.jl:380-387
-int32_t ppo_average_normalized_returns(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_trajectories,
-                                       double* mean, double* std) {
-    ARG_CHECK(pol && env && scratch && mean && std, "average_normalized_returns: null argument");
-    std::vector<double> v;
-    PPO_TRY(evaluate_impl(pol, env, scratch, num_trajectories, 3, v));
-    mean_std(v, mean, std);
-    return PPO_OK;
-}
-
-// ---------------------------------------------------------------- best state of a rollout, best-of-K search
-// device storage of TrackView records: `slots` output records and the per-env running values
-struct TrackBufs {
-    DevBuf<int32_t> per_env, ints, trace, types; DevBuf<int8_t> state; DevBuf<uint32_t> active; DevBuf<int16_t> acts;
-    TrackView tv;
-    int32_t alloc(int64_t N, int64_t slots, int32_t V, int32_t max_actions, bool want_trace, bool want_types,
-                  bool want_actions = false) {
-        const size_t S = (size_t)slots;
-        PPO_TRY(per_env.alloc((size_t)3 * N)); PPO_TRY(ints.alloc(4 * S)); PPO_TRY(state.alloc(S * 2 * V)); PPO_TRY(active.alloc(S));
-        HIP_TRY(hipMemsetAsync(per_env.p, 0, (size_t)3 * N * 4, g_stream));
-        HIP_TRY(hipMemsetAsync(ints.p, 0, 4 * S * 4, g_stream));
-        HIP_TRY(hipMemsetAsync(state.p, 0, S * 2 * V, g_stream));
-        HIP_TRY(hipMemsetAsync(active.p, 0, S * 4, g_stream));
-        tv.t_in = per_env.p; tv.ep_init = per_env.p + N; tv.ep_count = per_env.p + 2 * N;
-        tv.best_state = state.p; tv.best_active = active.p;
-        tv.best_gap = ints.p; tv.best_step = ints.p + S; tv.length = ints.p + 2 * S; tv.initial_gap = ints.p + 3 * S;
-        tv.num_traj = slots;
-        if (want_trace) {
-            PPO_TRY(trace.alloc(S * max_actions));
-            HIP_TRY(hipMemsetAsync(trace.p, 0, S * max_actions * 4, g_stream));
-            tv.trace = trace.p;
-        }
-        if (want_types) {
-            PPO_TRY(types.alloc(S * 4));
-            HIP_TRY(hipMemsetAsync(types.p, 0, S * 4 * 4, g_stream));
-            tv.type_counts = types.p;
-        }
-        if (want_actions) {                                               // -1 everywhere: what stays behind a trajectory's end
-            PPO_TRY(acts.alloc(S * max_actions));
-            HIP_TRY(hipMemsetAsync(acts.p, 0xFF, S * max_actions * sizeof(int16_t), g_stream));
-            tv.actions = acts.p;
-        }
-        return PPO_OK;
-    }
-};
-
-// best_state_in_rollout (test/quad_game_utilities.jl:341-358) for num_trajectories trajectories, with
-// single_trajectory_scores (:309-323) and the action-type counts behind count_non_flips (test/random_quad.jl:9-27)
-static int32_t best_states_impl(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_trajectories,
-                                int32_t reset_first, int8_t* best_state, uint32_t* best_active, int32_t* best_gap,
-                                int32_t* best_step, int32_t* length, int32_t* initial_gap, int32_t* trace_or_null,
-                                int32_t* type_counts_or_null, int16_t* actions_or_null) {
-    ARG_CHECK(best_state && best_active && best_gap && best_step && length && initial_gap, "best_states: null argument");
-    PPO_TRY(check_shapes(scratch, env, pol));
-    const int64_t N = env->N, nt = num_trajectories;
-    ARG_CHECK(nt >= 1, "best_states: num_trajectories must be >= 1");
-    if (!reset_first) {
-        ARG_CHECK(nt <= N, "best_states: without reset! every env plays at most one trajectory (num_trajectories <= N)");
-        std::vector<uint8_t> dn((size_t)N);
-        PPO_TRY(d2h(dn.data(), env->done.p, (size_t)N));
-        for (int64_t n = 0; n < nt; ++n) ARG_CHECK(!dn[n], "best_states: an env that is to play is already terminal");
-    }
-    const int64_t per_env = (nt + N - 1) / N;
-    const int32_t M = env->max_actions, V = env->V;
-    PPO_TRY(rollouts_reserve(scratch, 1, false));
-    TrackBufs b;
-    PPO_TRY(b.alloc(N, nt, V, M, trace_or_null != nullptr, type_counts_or_null != nullptr, actions_or_null != nullptr));
-    hipLaunchKernelGGL(k_episode_quota, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, g_stream, env->episodes_left.p, N, nt);
-    if (reset_first) PPO_TRY(launch_env_reset(env, 0));                 // reset!(env) before the first trajectory
-    bool all = false;
-    PPO_TRY(play_quotas(pol, env, scratch, per_env * M, nullptr, &b.tv, &all));
-    ARG_CHECK(all, "best_states: the trajectories did not finish within max_actions steps each");
-    scratch->T = 0; scratch->len = 0; scratch->adv_T = -1; scratch->values_T = -1; scratch->boot_T = -1;
-    const size_t S = (size_t)nt;
-    PPO_TRY(d2h(best_state, b.state.p, S * 2 * V)); PPO_TRY(d2h(best_active, b.active.p, S));
-    PPO_TRY(d2h(best_gap, b.tv.best_gap, S)); PPO_TRY(d2h(best_step, b.tv.best_step, S));
-    PPO_TRY(d2h(length, b.tv.length, S)); PPO_TRY(d2h(initial_gap, b.tv.initial_gap, S));
-    if (trace_or_null) {
-        PPO_TRY(d2h(trace_or_null, b.trace.p, S * M));
-        for (size_t s = 0; s < S; ++s)                                    // entries behind the trajectory's end
-            for (int32_t t = std::max(length[s], 0); t < M; ++t) trace_or_null[s * M + t] = INT32_MIN;
-    }
-    if (type_counts_or_null) PPO_TRY(d2h(type_counts_or_null, b.types.p, S * 4));
-    if (actions_or_null) PPO_TRY(d2h(actions_or_null, b.acts.p, S * M));
-    return ppo_env_check_errors(env, nullptr);
-}
-
-int32_t ppo_best_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_trajectories,
-                        int32_t reset_first, int8_t* best_state, uint32_t* best_active, int32_t* best_gap,
-                        int32_t* best_step, int32_t* length, int32_t* initial_gap, int32_t* trace_or_null,
-                        int32_t* type_counts_or_null) {
-    return best_states_impl(pol, env, scratch, num_trajectories, reset_first, best_state, best_active, best_gap, best_step,
-                            length, initial_gap, trace_or_null, type_counts_or_null, nullptr);
-}
-
-// ... with every trajectory's 0-based actions: row [max_actions], -1 behind `length`; its first best_step
-// entries are the path to the best state
-int32_t ppo_best_states_actions(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_trajectories,
-                                int32_t reset_first, int8_t* best_state, uint32_t* best_active, int32_t* best_gap,
-                                int32_t* best_step, int32_t* length, int32_t* initial_gap, int32_t* trace_or_null,
-                                int32_t* type_counts_or_null, int16_t* actions) {
-    ARG_CHECK(actions, "best_states_actions: null argument");
-    return best_states_impl(pol, env, scratch, num_trajectories, reset_first, best_state, best_active, best_gap, best_step,
-                            length, initial_gap, trace_or_null, type_counts_or_null, actions);
-}
-
-// Best-of-K search from caller-supplied start states.  Sampling is keyed on (global env id, tick), so K resident envs loaded
-// with one state play K different trajectories: rounds of S = N / K starts, each a load (k_env_load_starts), the tracked
-// step loop and one reduction (k_search_argmin).  No reset! runs: the episode counters stay, ticks advance by the steps played.
-static int32_t search_best_states_impl(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
-                                       const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
-                                       uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
-                                       int32_t* initial_gap, int32_t* clone_gaps_or_null, int16_t* path_or_null) {
-    ARG_CHECK(score && degree && active && best_state && best_active && best_gap && best_clone && best_step && initial_gap,
-              "search_best_states: null argument");
-    PPO_TRY(check_shapes(scratch, env, pol));
-    const int64_t N = env->N, Mst = num_starts;
-    ARG_CHECK(Mst >= 1 && K >= 1 && K <= N, "search_best_states: need num_starts >= 1 and 1 <= K <= N");
-    PPO_TRY(check_internal_host(env->Q, Mst, score, degree, active));
-    const int32_t V = env->V;
-    const int64_t S = N / K;
-    PPO_TRY(rollouts_reserve(scratch, 1, false));
-    std::vector<int8_t> snap((size_t)Mst * 2 * V);                       // k_env_snapshot's layout: score[V] then degree[V]
-    for (int64_t m = 0; m < Mst; ++m) {
-        std::memcpy(&snap[(size_t)m * 2 * V], score + m * V, (size_t)V);
-        std::memcpy(&snap[(size_t)m * 2 * V + V], degree + m * V, (size_t)V);
-    }
-    DevBuf<int8_t> d_start; DevBuf<uint32_t> d_act; DevBuf<int32_t> d_clone, d_gaps;
-    PPO_TRY(d_start.alloc(snap.size())); PPO_TRY(d_act.alloc((size_t)Mst)); PPO_TRY(d_clone.alloc((size_t)Mst));
-    PPO_TRY(h2d(d_start.p, snap.data(), snap.size())); PPO_TRY(h2d(d_act.p, active, (size_t)Mst));
-    if (clone_gaps_or_null) PPO_TRY(d_gaps.alloc((size_t)Mst * K));
-    TrackBufs rec, out;                                                  // per-env records of a round (slot = env); the winners
-    PPO_TRY(rec.alloc(N, N, V, env->max_actions, false, false, path_or_null != nullptr));
-    PPO_TRY(out.alloc(1, Mst, V, env->max_actions, false, false, path_or_null != nullptr));
-    for (int64_t base = 0; base < Mst; base += S) {
-        const int64_t Sr = std::min(S, Mst - base);
-        HIP_TRY(hipMemsetAsync(rec.tv.ep_count, 0, (size_t)N * 4, g_stream));
-        PPO_TRY(launch_env_load_starts(env, d_start.p + (size_t)base * 2 * V, d_act.p + base, Sr * K, K, rec.tv.t_in));
-        bool all = false;
-        PPO_TRY(play_quotas(pol, env, scratch, env->max_actions, nullptr, &rec.tv, &all));
-        ARG_CHECK(all, "search_best_states: the trajectories did not finish within max_actions steps");
-        PPO_TRY(launch_search_argmin(rec.tv, V, Sr, K, out.tv, d_clone.p, clone_gaps_or_null ? d_gaps.p : nullptr, base,
-                                     env->max_actions));
-    }
-    scratch->T = 0; scratch->len = 0; scratch->adv_T = -1; scratch->values_T = -1; scratch->boot_T = -1;
-    const size_t Ms = (size_t)Mst;
-    PPO_TRY(d2h(best_state, out.state.p, Ms * 2 * V)); PPO_TRY(d2h(best_active, out.active.p, Ms));
-    PPO_TRY(d2h(best_gap, out.tv.best_gap, Ms)); PPO_TRY(d2h(best_step, out.tv.best_step, Ms));
-    PPO_TRY(d2h(initial_gap, out.tv.initial_gap, Ms)); PPO_TRY(d2h(best_clone, d_clone.p, Ms));
-    if (clone_gaps_or_null) PPO_TRY(d2h(clone_gaps_or_null, d_gaps.p, Ms * (size_t)K));
-    if (path_or_null) PPO_TRY(d2h(path_or_null, out.acts.p, Ms * (size_t)env->max_actions));
-    return ppo_env_check_errors(env, nullptr);
-}
-
-int32_t ppo_search_best_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
-                               const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
-                               uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
-                               int32_t* initial_gap, int32_t* clone_gaps_or_null) {
-    return search_best_states_impl(pol, env, scratch, num_starts, K, score, degree, active, best_state, best_active, best_gap,
-                                   best_clone, best_step, initial_gap, clone_gaps_or_null, nullptr);
-}
-
-// ... with the path to every start's result: the winner's first best_step 0-based actions, -1 behind them
-int32_t ppo_search_best_states_path(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
-                                    const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
-                                    uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
-                                    int32_t* initial_gap, int32_t* clone_gaps_or_null, int16_t* path) {
-    ARG_CHECK(path, "search_best_states_path: null argument");
-    return search_best_states_impl(pol, env, scratch, num_starts, K, score, degree, active, best_state, best_active, best_gap,
-                                   best_clone, best_step, initial_gap, clone_gaps_or_null, path);
-}
-
-// Resampling search: ppo_search_best_states' schedule with a resample event (k_search_resample: fold, rank,
-// copy) behind every interval-th step of a round, and one more fold behind the round's last step.  The events ride in
-// play_quotas' loop, which polls completion every 8 steps as for every other caller: an event costs a launch, no copy.
-// critic (optional): an event ranks the live clones by cur_gap - value_weight * V(state held now) instead of
-// cur_gap.  In front of the event the envs are observed into row 0 of `scratch` (the next loop step overwrites it anyway)
-// and the critic's forward turns the rows into one value per env, all on the device.  The last fold ranks nothing and
-// needs neither.  event_values (optional): [num_starts][E][K] log of the values the events read.
-static int32_t search_resample_states_impl(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts,
-                                           int64_t K, const int8_t* score, const int8_t* degree, const uint32_t* active,
-                                           int8_t* best_state, uint32_t* best_active, int32_t* best_gap, int32_t* best_clone,
-                                           int32_t* best_step, int32_t* initial_gap, int32_t* clone_gaps_or_null,
-                                           int64_t interval, int64_t survivors, int32_t* donors_or_null,
-                                           int16_t* path_or_null, ppo_policy_t critic = nullptr, double value_weight = 0.0,
-                                           float* event_values_or_null = nullptr) {
-    ARG_CHECK(score && degree && active && best_state && best_active && best_gap && best_clone && best_step && initial_gap,
-              "search_resample_states: null argument");
-    PPO_TRY(check_shapes(scratch, env, pol));
-    const int64_t N = env->N, Mst = num_starts;
-    ARG_CHECK(Mst >= 1 && K >= 1 && K <= N, "search_resample_states: need num_starts >= 1 and 1 <= K <= N");
-    ARG_CHECK(interval >= 1, "search_resample_states: interval must be >= 1");
-    ARG_CHECK(survivors >= 1 && survivors <= K, "search_resample_states: need 1 <= survivors <= K");
-    ARG_CHECK(critic || !event_values_or_null, "search_resample_states: a log of values needs a critic");
-    if (critic) {
-        PPO_TRY(value_checks("search_resample_states", critic, env->F));
-        if (env->H != 32 && env->H != 128) {
-            ppo_set_error("search_resample_states: the critic needs H = 32 (Q=8) or 128 (Q=32) half-edges in this build");
-            return PPO_ERR_UNSUPPORTED;
-        }
-        ARG_CHECK(std::isfinite(value_weight) && value_weight >= 0.0 && std::isfinite((float)value_weight),
-                  "search_resample_states: value_weight must be finite and >= 0");
-    }
-    PPO_TRY(check_internal_host(env->Q, Mst, score, degree, active));
-    if (K > PPO_RESAMPLE_MAX_K) {
-        ppo_set_error("search_resample_states: K above 4096 clones is not supported (the rank keys are staged in LDS)");
-        return PPO_ERR_UNSUPPORTED;
-    }
-    const int32_t V = env->V, M = env->max_actions;
-    const int64_t S = N / K, E = (M - 1) / interval;
-    PPO_TRY(rollouts_reserve(scratch, 1, false));
-    std::vector<int8_t> snap((size_t)Mst * 2 * V);                       // k_env_snapshot's layout: score[V] then degree[V]
-    for (int64_t m = 0; m < Mst; ++m) {
-        std::memcpy(&snap[(size_t)m * 2 * V], score + m * V, (size_t)V);
-        std::memcpy(&snap[(size_t)m * 2 * V + V], degree + m * V, (size_t)V);
-    }
-    DevBuf<int8_t> d_start; DevBuf<uint32_t> d_act; DevBuf<int32_t> d_clone, d_gaps, d_donors;
-    PPO_TRY(d_start.alloc(snap.size())); PPO_TRY(d_act.alloc((size_t)Mst)); PPO_TRY(d_clone.alloc((size_t)Mst));
-    PPO_TRY(h2d(d_start.p, snap.data(), snap.size())); PPO_TRY(h2d(d_act.p, active, (size_t)Mst));
-    if (clone_gaps_or_null) PPO_TRY(d_gaps.alloc((size_t)Mst * K));
-    const size_t log_len = (size_t)Mst * (size_t)E * (size_t)K;
-    const bool want_log = donors_or_null && log_len > 0;
-    if (want_log) {                                                      // an event that never runs: every clone had terminated
-        std::fill(donors_or_null, donors_or_null + log_len, -2);
-        PPO_TRY(d_donors.alloc(log_len));
-        PPO_TRY(h2d(d_donors.p, donors_or_null, log_len));
-    }
-    DevBuf<float> d_values, d_vlog;                                      // the critic's value of every env; the log of them
-    const bool want_vlog = event_values_or_null && log_len > 0;
-    if (critic) PPO_TRY(d_values.alloc((size_t)N));
-    if (want_vlog) {                                                     // an event that never runs leaves NaN
-        std::fill(event_values_or_null, event_values_or_null + log_len, std::numeric_limits<float>::quiet_NaN());
-        PPO_TRY(d_vlog.alloc(log_len));
-        PPO_TRY(h2d(d_vlog.p, event_values_or_null, log_len));
-    }
-    TrackBufs rec, out;                                                  // per-env records of a round (slot = env); the results
-    PPO_TRY(rec.alloc(N, N, V, M, false, false, path_or_null != nullptr));
-    PPO_TRY(out.alloc(1, Mst, V, M, false, false, path_or_null != nullptr));
-    for (int64_t base = 0; base < Mst; base += S) {
-        const int64_t Sr = std::min(S, Mst - base);
-        HIP_TRY(hipMemsetAsync(rec.tv.ep_count, 0, (size_t)N * 4, g_stream));
-        PPO_TRY(launch_env_load_starts(env, d_start.p + (size_t)base * 2 * V, d_act.p + base, Sr * K, K, rec.tv.t_in));
-        int first = 1;
-        const std::function<int32_t(int64_t)> event = [&](int64_t t) -> int32_t {
-            const int64_t played = t + 1;                                // loop steps since the round's load
-            if (played % interval != 0 || played >= M) return PPO_OK;
-            if (critic) {                                                // V of the state every env holds behind the step
-                PPO_TRY(launch_env_observe(env, scratch->states.p, scratch->active.p));
-                PPO_TRY(launch_value_predict(critic, scratch->states.p, nullptr, scratch->active.p, nullptr, 0, N, env->H,
-                                             d_values.p));
-            }
-            PPO_TRY(launch_search_resample(env, rec.tv, Sr, K, survivors, first, out.tv, d_clone.p, base,
-                                           want_log ? d_donors.p : nullptr, E, played / interval - 1, nullptr, played,
-                                           critic ? d_values.p : nullptr, want_vlog ? d_vlog.p : nullptr, (float)value_weight));
-            first = 0;
-            return PPO_OK;
-        };
-        bool all = false;
-        PPO_TRY(play_quotas(pol, env, scratch, M, nullptr, &rec.tv, &all, &event));
-        ARG_CHECK(all, "search_resample_states: the trajectories did not finish within max_actions steps");
-        PPO_TRY(launch_search_resample(env, rec.tv, Sr, K, survivors, first | 2, out.tv, d_clone.p, base, nullptr, E, 0,
-                                       clone_gaps_or_null ? d_gaps.p : nullptr, 0));
-    }
-    scratch->T = 0; scratch->len = 0; scratch->adv_T = -1; scratch->values_T = -1; scratch->boot_T = -1;
-    const size_t Ms = (size_t)Mst;
-    PPO_TRY(d2h(best_state, out.state.p, Ms * 2 * V)); PPO_TRY(d2h(best_active, out.active.p, Ms));
-    PPO_TRY(d2h(best_gap, out.tv.best_gap, Ms)); PPO_TRY(d2h(best_step, out.tv.best_step, Ms));
-    PPO_TRY(d2h(initial_gap, out.tv.initial_gap, Ms)); PPO_TRY(d2h(best_clone, d_clone.p, Ms));
-    if (clone_gaps_or_null) PPO_TRY(d2h(clone_gaps_or_null, d_gaps.p, Ms * (size_t)K));
-    if (want_log) PPO_TRY(d2h(donors_or_null, d_donors.p, log_len));
-    if (want_vlog) PPO_TRY(d2h(event_values_or_null, d_vlog.p, log_len));
-    if (path_or_null) PPO_TRY(d2h(path_or_null, out.acts.p, Ms * (size_t)M));
-    return ppo_env_check_errors(env, nullptr);
-}
-
-int32_t ppo_search_resample_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
-                                   const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
-                                   uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
-                                   int32_t* initial_gap, int32_t* clone_gaps_or_null, int64_t interval, int64_t survivors,
-                                   int32_t* donors_or_null) {
-    return search_resample_states_impl(pol, env, scratch, num_starts, K, score, degree, active, best_state, best_active,
-                                       best_gap, best_clone, best_step, initial_gap, clone_gaps_or_null, interval, survivors,
-                                       donors_or_null, nullptr);
-}
-
-// ... with the path to every start's result.  The action history belongs to the lineage: a copy carries the
-// donor's played prefix with its record, and every fold that takes a winner's record takes the first best_step entries of
-// that winner's history with it -- before the event's copies can overwrite them
-int32_t ppo_search_resample_states_path(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
-                                        const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
-                                        uint32_t* best_active, int32_t* best_gap, int32_t* best_clone, int32_t* best_step,
-                                        int32_t* initial_gap, int32_t* clone_gaps_or_null, int64_t interval, int64_t survivors,
-                                        int32_t* donors_or_null, int16_t* path) {
-    ARG_CHECK(path, "search_resample_states_path: null argument");
-    return search_resample_states_impl(pol, env, scratch, num_starts, K, score, degree, active, best_state, best_active,
-                                       best_gap, best_clone, best_step, initial_gap, clone_gaps_or_null, interval, survivors,
-                                       donors_or_null, path);
-}
-
-// ... ranking a start's live clones by where the critic expects them to end: cur_gap - value_weight * V(s)
-// in place of cur_gap.  The fold, the ranks, the copy and the path are the plain call's
-int32_t ppo_search_resample_states_value(ppo_policy_t pol, ppo_policy_t critic, ppo_env_t env, ppo_rollouts_t scratch,
-                                         int64_t num_starts, int64_t K, const int8_t* score, const int8_t* degree,
-                                         const uint32_t* active, int8_t* best_state, uint32_t* best_active, int32_t* best_gap,
-                                         int32_t* best_clone, int32_t* best_step, int32_t* initial_gap,
-                                         int32_t* clone_gaps_or_null, int64_t interval, int64_t survivors, double value_weight,
-                                         int32_t* donors_or_null, float* event_values_or_null, int16_t* path_or_null) {
-    ARG_CHECK(critic, "search_resample_states_value: null argument");
-    return search_resample_states_impl(pol, env, scratch, num_starts, K, score, degree, active, best_state, best_active,
-                                       best_gap, best_clone, best_step, initial_gap, clone_gaps_or_null, interval, survivors,
-                                       donors_or_null, path_or_null, critic, value_weight, event_values_or_null);
-}
-
-// Teacher-forced replay of action paths on caller-supplied states, without a policy: what checks a returned
-// path on the device.  The env handle supplies Q, max_actions and no_action_reward only: the resident envs, their ticks,
-// episode counters and error flag are untouched.  Everything is validated on the host before anything is uploaded
-int32_t ppo_env_apply_paths(ppo_env_t env, int64_t M, const int8_t* score, const int8_t* degree, const uint32_t* active,
-                            const int16_t* paths, int64_t stride, int8_t* out_state, uint32_t* out_active, int32_t* out_gap,
-                            int32_t* applied, int32_t* trace_or_null) {
-    ARG_CHECK(env && score && degree && active && paths && out_state && out_active && out_gap && applied,
-              "env_apply_paths: null argument");
-    ARG_CHECK(M >= 1, "env_apply_paths: need at least one path");
-    ARG_CHECK(stride >= 1 && stride <= INT32_MAX, "env_apply_paths: stride must be >= 1");
-    PPO_TRY(check_internal_host(env->Q, M, score, degree, active));
-    const int32_t V = env->V, A = 16 * env->Q;
-    const size_t Ms = (size_t)M, cells = Ms * (size_t)stride;
-    for (size_t i = 0; i < cells; ++i) ARG_CHECK(paths[i] < A, "env_apply_paths: action index out of range");
-    std::vector<int8_t> snap(Ms * 2 * V);                                // k_env_snapshot's layout: score[V] then degree[V]
-    for (size_t m = 0; m < Ms; ++m) {
-        std::memcpy(&snap[m * 2 * V], score + m * V, (size_t)V);
-        std::memcpy(&snap[m * 2 * V + V], degree + m * V, (size_t)V);
-    }
-    DevBuf<int8_t> d_start, d_state; DevBuf<uint32_t> d_act, d_oact; DevBuf<int16_t> d_paths; DevBuf<int32_t> d_ints, d_trace;
-    PPO_TRY(d_start.alloc(snap.size())); PPO_TRY(d_state.alloc(snap.size())); PPO_TRY(d_act.alloc(Ms)); PPO_TRY(d_oact.alloc(Ms));
-    PPO_TRY(d_paths.alloc(cells)); PPO_TRY(d_ints.alloc(6 * Ms + 1));     // gap, applied, work [4][M], the flag word
-    if (trace_or_null) PPO_TRY(d_trace.alloc(cells));
-    PPO_TRY(h2d(d_start.p, snap.data(), snap.size())); PPO_TRY(h2d(d_act.p, active, Ms)); PPO_TRY(h2d(d_paths.p, paths, cells));
-    HIP_TRY(hipMemsetAsync(d_ints.p, 0, (6 * Ms + 1) * 4, g_stream));
-    int32_t* d_err = d_ints.p + 6 * Ms;
-    PPO_TRY(launch_env_apply_paths(env, M, d_start.p, d_act.p, d_paths.p, (int32_t)stride, d_state.p, d_oact.p, d_ints.p,
-                                   d_ints.p + Ms, trace_or_null ? d_trace.p : nullptr, d_ints.p + 2 * Ms, d_err));
-    PPO_TRY(d2h(out_state, d_state.p, snap.size())); PPO_TRY(d2h(out_active, d_oact.p, Ms));
-    PPO_TRY(d2h(out_gap, d_ints.p, Ms)); PPO_TRY(d2h(applied, d_ints.p + Ms, Ms));
-    if (trace_or_null) PPO_TRY(d2h(trace_or_null, d_trace.p, cells));
-    int32_t f = 0;
-    PPO_TRY(d2h(&f, d_err, 1));
-    if (f) {
-        ppo_set_error("AssertionError (device flag): env_apply_paths: a path holds an action on an inactive quad");
-        return PPO_ERR_DEVICE_FLAG;
-    }
-    return PPO_OK;
-}
-
-// Teacher-forced collection: envs 0 .. M - 1 are loaded with the starts and play the given paths instead of
-// sampled actions, and what they pass through is left in `ro` as an ordinary rollout buffer.  The loop is the episodes
-// mode's -- observe, snapshot when compact, forward, step -- with the forced forward and the forced step; the host knows every
-// path's declared length, so T is known in front of the loop and nothing is polled.  The flag word is the call's own: a
-// path with an action on an inactive quad does not leave the env handle flagged
-int32_t ppo_collect_paths(ppo_rollouts_t ro, ppo_env_t env, ppo_policy_t pol, int64_t M, const int8_t* score, const int8_t* degree,
-                          const uint32_t* active, const int16_t* paths, int64_t stride, double discount, int32_t discount_is_f32,
-                          int32_t record_probs) {
-    PPO_TRY(check_shapes(ro, env, pol));
-    ARG_CHECK(score && degree && active && paths, "collect_paths!: null argument");
-    const int64_t N = env->N;
-    ARG_CHECK(M >= 1 && M <= N, "collect_paths!: need 1 <= M <= N paths (one resident env plays one path)");
-    ARG_CHECK(stride >= 1 && stride <= INT32_MAX, "collect_paths!: stride must be >= 1");
-    PPO_TRY(check_internal_host(env->Q, M, score, degree, active));
-    const int32_t V = env->V, A = 16 * env->Q;
-    const size_t Ms = (size_t)M, cells = Ms * (size_t)stride;
-    std::vector<int32_t> lens(Ms);                                       // declared length: the index of the first negative entry
-    int64_t T = 1;
-    for (size_t m = 0; m < Ms; ++m) {
-        int64_t len = stride;
-        for (int64_t i = 0; i < stride; ++i) {
-            const int16_t a = paths[m * (size_t)stride + i];
-            ARG_CHECK(a < A, "collect_paths!: action index out of range");
-            if (a < 0 && i < len) len = i;
-        }
-        lens[m] = (int32_t)len;
-        T = std::max(T, len);
-    }
-    if (pol->dtype != PPO_DTYPE_F32) {
-        ppo_set_error("collect_paths!: a bf16-dtype policy is not supported (the teacher-forced mode exists in the fp32-MFMA forward only)");
-        return PPO_ERR_UNSUPPORTED;
-    }
-    if (ro->sink) {
-        ppo_set_error("collect_paths!: a buffer with a disk sink attached is not supported");
-        return PPO_ERR_UNSUPPORTED;
-    }
-    const bool compact = want_compact(ro, T);
-    PPO_TRY(rollouts_reserve(ro, T, compact));
-    const size_t srow = (size_t)N * env->H * env->F, crow = (size_t)N * 2 * V;
-    if (compact) PPO_TRY(env->obs_tmp.alloc(srow));
-    if (record_probs) PPO_TRY(ro->full_probs.alloc((size_t)T * N * env->A));
-    std::vector<int8_t> snap(Ms * 2 * V);                                // k_env_snapshot's layout: score[V] then degree[V]
-    for (size_t m = 0; m < Ms; ++m) {
-        std::memcpy(&snap[m * 2 * V], score + m * V, (size_t)V);
-        std::memcpy(&snap[m * 2 * V + V], degree + m * V, (size_t)V);
-    }
-    DevBuf<int8_t> d_start; DevBuf<uint32_t> d_act; DevBuf<int16_t> d_paths; DevBuf<int32_t> d_ints;
-    PPO_TRY(d_start.alloc(snap.size())); PPO_TRY(d_act.alloc(Ms)); PPO_TRY(d_paths.alloc(cells));
-    PPO_TRY(d_ints.alloc(Ms + (size_t)N + 1));                           // lens [M], the load's step counters [N], the flag word
-    PPO_TRY(h2d(d_start.p, snap.data(), snap.size())); PPO_TRY(h2d(d_act.p, active, Ms)); PPO_TRY(h2d(d_paths.p, paths, cells));
-    PPO_TRY(h2d(d_ints.p, lens.data(), Ms));
-    int32_t* d_err = d_ints.p + Ms + N;
-    HIP_TRY(hipMemsetAsync(d_err, 0, 4, g_stream));
-    // envs 0 .. M - 1 as reset! leaves an env, one start each; the envs behind them keep what they hold and idle
-    PPO_TRY(launch_env_load_starts(env, d_start.p, d_act.p, M, 1, d_ints.p + Ms));
-    for (int64_t t = 0; t < T; ++t) {
-        int8_t* st = compact ? env->obs_tmp.p : ro->states.p + (size_t)t * srow;
-        uint32_t* am = ro->active.p + (size_t)t * N;
-        int32_t* ac = ro->actions.p + t * N;
-        PPO_TRY(launch_env_observe(env, st, am));
-        if (compact) PPO_TRY(launch_env_snapshot(env, ro->cstate.p + (size_t)t * crow));
-        PPO_TRY(launch_paths_feed(env, d_paths.p, d_ints.p, M, stride, t, ac));
-        PPO_TRY(launch_policy_forced(pol, env, st, am, ac, ro->p_sel.p + t * N,
-                                     record_probs ? ro->full_probs.p + (size_t)t * N * env->A : nullptr, d_err));
-        PPO_TRY(launch_env_step_forced(env, ac, d_ints.p, t, ro->rewards.p + t * N, ro->done.p + t * N, ro->valid.p + t * N, d_err));
-    }
-    ro->T = T; ro->adv_T = -1; ro->values_T = -1; ro->boot_T = -1;
-    // dataset order = env-major concatenation of the paths, valid transitions only (the episodes mode's order)
-    std::vector<uint8_t> valid((size_t)T * N);
-    PPO_TRY(d2h(valid.data(), ro->valid.p, (size_t)T * N));
-    std::vector<int32_t> index;
-    index.reserve((size_t)T * N);
-    for (int64_t n = 0; n < N; ++n)
-        for (int64_t t = 0; t < T; ++t)
-            if (valid[(size_t)t * N + n]) index.push_back((int32_t)(t * N + n));
-    ro->len = (int64_t)index.size();
-    ro->all_valid = false;
-    PPO_TRY(h2d(ro->index.p, index.data(), index.size()));
-    PPO_TRY(launch_returns_tn(ro->rewards.p, ro->done.p, ro->returns.p, T, N, discount, discount_is_f32));
-    int32_t f = 0;
-    PPO_TRY(d2h(&f, d_err, 1));
-    if (f) {
-        ppo_set_error("AssertionError (device flag): collect_paths!: a path holds an action on an inactive quad (its transition is recorded with valid = 0 and probability 0)");
-        return PPO_ERR_DEVICE_FLAG;
-    }
-    return PPO_OK;
 }
 
 #define RO_GETTER(name, member, type, per)                                                     \
@@ -1529,7 +888,7 @@ int32_t ppo_rollouts_set(ppo_rollouts_t ro, int64_t T, const int8_t* states, con
     PPO_TRY(h2d(ro->actions.p, actions0, n)); PPO_TRY(h2d(ro->p_sel.p, p_sel, n)); PPO_TRY(h2d(ro->returns.p, returns, n));
     PPO_TRY(h2d(ro->rewards.p, returns, n));
     if (terminal) PPO_TRY(h2d(ro->done.p, terminal, n));
-    ro->T = T; ro->adv_T = -1; ro->values_T = -1; ro->boot_T = -1;
+    rollouts_filled(ro, T);
     return set_index_all(ro);
 }
 

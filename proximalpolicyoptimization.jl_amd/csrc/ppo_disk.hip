@@ -457,7 +457,7 @@ extern "C" int32_t ppo_rollouts_load_disk(ppo_rollouts_t ro, const char* dir) {
         PPO_TRY(ppo_rollouts_set(ro, T, st.data(), act.data(), a0.data(), ps.data(), ret.data(), dn.data()));
     } else {                                      // env snapshots go back as they are: the buffer stays in the compact form
         PPO_TRY(rollouts_reserve(ro, T, true));
-        ro->T = T; ro->adv_T = -1; ro->values_T = -1; ro->boot_T = -1;
+        rollouts_filled(ro, T);
         PPO_TRY(set_index_all(ro));                  // before the copies below: no early return while they are in flight
         const size_t n = (size_t)T * N;
         hipStream_t s = ppo_stream();

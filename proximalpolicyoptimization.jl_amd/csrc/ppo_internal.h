@@ -249,9 +249,16 @@ struct ppo_rollouts_s {
     ~ppo_rollouts_s();
 };
 
-// rollout buffer internals shared with the disk loader (ppo_api.hip)
+// rollout buffer internals and argument checks of ppo_api.hip, shared with the disk loader and ppo_play.hip
 extern "C" int32_t rollouts_reserve(ppo_rollouts_s* r, int64_t T, bool compact);
 extern "C" int32_t set_index_all(ppo_rollouts_s* r);
+extern "C" int32_t check_shapes(ppo_rollouts_s* ro, ppo_env_s* env, ppo_policy_s* pol);
+extern "C" bool want_compact(const ppo_rollouts_s* ro, int64_t T);
+extern "C" int32_t check_internal_host(int32_t Q, int64_t count, const int8_t* score, const int8_t* degree, const uint32_t* active);
+// the buffer now holds T steps, or (scratch_used) row 0 served a call as scratch and nothing is held: every column cached
+// for the previous contents is stale
+inline void rollouts_filled(ppo_rollouts_s* ro, int64_t T) { ro->T = T; ro->adv_T = -1; ro->values_T = -1; ro->boot_T = -1; }
+inline void rollouts_scratch_used(ppo_rollouts_s* ro) { rollouts_filled(ro, 0); ro->len = 0; }
 
 // out-of-core store hooks used by ppo_collect_rollouts (ppo_disk.hip)
 int32_t disk_sink_begin(ppo_rollouts_s* ro, int64_t T);
