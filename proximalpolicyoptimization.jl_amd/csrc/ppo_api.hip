@@ -792,7 +792,7 @@ int32_t ppo_collect_rollouts(ppo_rollouts_t ro, ppo_env_t env, ppo_policy_t pol,
     if (record_probs) PPO_TRY(ro->full_probs.alloc((size_t)T * N * env->A));
     // an env left terminal by a previous call starts a fresh episode (reset! before each episode)
     PPO_TRY(launch_env_reset(env, 1));
-    // One launch for the whole rollout (every wave walks its envs through all T steps: k_policy_fwd MODE 3).  Default: on
+    // One launch for the whole rollout (every wave walks its envs through all T steps: k_policy_fwd's FwdMode::Persistent).  Default: on
     // for Q = 8, where the env update is wavefront-parallel (312.7 vs 314.6 ms per bench iteration, same box); off for
     // Q = 32, whose update still runs on one lane.  ppo_set_rollout_persistent / PPO_ROLLOUT_PERSISTENT=0|1 override.
     // With a disk sink attached the rollout is a CHAIN of such launches, a few steps each: the finished steps of launch k

@@ -1,6 +1,6 @@
 // ppo_env_device.h -- the synthetic rand-poly-shaped env (DESIGN.md "Synthetic env") for ONE env instance, as device
 // functions on a set of pointers: the per-step kernels (ppo_env.hip) pass pointers into the [N] global arrays, the
-// persistent rollout kernel (ppo_policy_fwd.hip, MODE 3) pointers into the wave's LDS slot.  One definition of the
+// persistent rollout kernel (ppo_policy_fwd.hip, FwdMode::Persistent) pointers into the wave's LDS slot.  One definition of the
 // integer dynamics, bit for bit the oracle's orc_env_step_one / orc_env_reset_one.
 #pragma once
 #include "ppo_internal.h"

@@ -212,7 +212,7 @@ struct ppo_rollouts_s {
     // state storage, one of two forms (ppo_set_rollout_compact):
     //   expanded: the observation rows themselves, 2304 B per transition for Q = 8 (host-supplied rollouts always)
     //   compact:  the env snapshot the rows are derived from (score[V] then degree[V], int8: 64 B for Q = 8) -- the
-    //             train forward re-derives the rows like the persistent rollout does (k_policy_fwd MODE 4)
+    //             train forward re-derives the rows like the persistent rollout does (k_policy_fwd's FwdMode::TrainSnap)
     bool compact = false;
     int32_t V = 0;             // vertices per env (4Q)
     DevBuf<int8_t> states;     // [T][N][H][F]        (expanded form)
@@ -388,13 +388,13 @@ int32_t launch_policy_probs(ppo_policy_s* p, const int8_t* states_dev, const uin
                             int32_t H, float* probs_dev);
 int32_t launch_policy_rollout(ppo_policy_s* p, ppo_env_s* e, const int8_t* states_dev, const uint32_t* active_dev,
                               int32_t* actions_out, float* psel_out, float* full_probs_or_null);
-// one step under the policy's selection: launch_policy_rollout for the default ("sample", 1), otherwise k_policy_fwd MODE 14
-// (tempered sampling) / 15 (greedy) / 16 (tempered sampling from the truncated distribution: rule "sample" with a non-default
+// one step under the policy's selection: launch_policy_rollout for the default ("sample", 1), otherwise k_policy_fwd's FwdMode::Tempered
+// (tempered sampling) / Greedy / Truncated (tempered sampling from the truncated distribution: rule "sample" with a non-default
 // truncation, at any temperature), same outputs.  A bf16-dtype policy with a non-default selection or truncation:
 // PPO_ERR_UNSUPPORTED
 int32_t launch_policy_select(ppo_policy_s* p, ppo_env_s* e, const int8_t* states_dev, const uint32_t* active_dev,
                              int32_t* actions_out, float* psel_out, float* full_probs_or_null);
-// one teacher-forced step (k_policy_fwd MODE 11): actions_io[n] = env n's given action (kept; < 0 idles), psel_out[n] = its
+// one teacher-forced step (k_policy_fwd's FwdMode::Forced): actions_io[n] = env n's given action (kept; < 0 idles), psel_out[n] = its
 // probability under the policy, 0 for an idle env or an inactive quad (bit 64 of *err).  A bf16-dtype policy: PPO_ERR_UNSUPPORTED
 int32_t launch_policy_forced(ppo_policy_s* p, ppo_env_s* e, const int8_t* states_dev, const uint32_t* active_dev,
                              int32_t* actions_io, float* psel_out, float* full_probs_or_null, int32_t* err);
@@ -458,6 +458,71 @@ struct TrainRoute { TrainFwd fwd; TrainBwd bwd; const char* err; };      // err:
 // dtype: PPO_DTYPE_*; HID: kernel width (128 / 256); H: rows per state (32 / 128); states: minibatch size
 TrainRoute train_route(int32_t dtype, int F, int HID, int L, int H, bool compact, int64_t states, const PpoKnobs& k, Objective obj);
 
+// k_policy_fwd's MODE (k_policy_fwd_bf16 has the first five).  The numbers are what kernel traces, the route strings and DESIGN.md
+// print.  A mode is two independent choices, where the state comes from and what runs behind the logits: fwd_traits is the table.
+// The clipped value loss, the forced step, imitation and the selection rules are modes of their own rather than runtime tests in
+// a tail because every such test moved the register allocation of the instantiations next to it, measurably (DESIGN.md 7k .. 7n)
+enum class FwdMode : int {
+    Probs = 0, Sample = 1, Train = 2, Persistent = 3, TrainSnap = 4, ValuePredict = 5, ValueTrain = 6, ValuePredictSnap = 7,
+    ValueTrainSnap = 8, ValueTrainClip = 9, ValueTrainClipSnap = 10, Forced = 11, Imitate = 12, ImitateSnap = 13, Tempered = 14,
+    Greedy = 15, Truncated = 16
+};
+enum class FwdSource {
+    Rows,       // observation rows [B][H][F] in storage order
+    RowsIdx,    // ... gathered through idx (a minibatch)
+    EnvSlots,   // the env slots of the persistent rollout, in the wave's LDS
+    Snap,       // one env snapshot [2V] per state in storage order, the rows re-derived from it
+    SnapIdx     // ... fetched through idx, the rows left in xs_out (minibatch order) for the backward
+};
+enum class FwdTail {      // policy_tail, or value_tail for the three Value*
+    Probs, Sample, SamplePersistent, Train, Forced, Imitate, Tempered, Greedy, Truncated, ValuePredict, ValueTrain, ValueTrainClip
+};
+struct FwdTraits { FwdSource src; FwdTail tail; };
+constexpr FwdTraits fwd_traits(FwdMode m) {
+    switch (m) {
+    case FwdMode::Probs:              return {FwdSource::Rows, FwdTail::Probs};
+    case FwdMode::Sample:             return {FwdSource::Rows, FwdTail::Sample};
+    case FwdMode::Train:              return {FwdSource::RowsIdx, FwdTail::Train};
+    case FwdMode::Persistent:         return {FwdSource::EnvSlots, FwdTail::SamplePersistent};
+    case FwdMode::TrainSnap:          return {FwdSource::SnapIdx, FwdTail::Train};
+    case FwdMode::ValuePredict:       return {FwdSource::Rows, FwdTail::ValuePredict};
+    case FwdMode::ValueTrain:         return {FwdSource::RowsIdx, FwdTail::ValueTrain};
+    case FwdMode::ValuePredictSnap:   return {FwdSource::Snap, FwdTail::ValuePredict};
+    case FwdMode::ValueTrainSnap:     return {FwdSource::SnapIdx, FwdTail::ValueTrain};
+    case FwdMode::ValueTrainClip:     return {FwdSource::RowsIdx, FwdTail::ValueTrainClip};
+    case FwdMode::ValueTrainClipSnap: return {FwdSource::SnapIdx, FwdTail::ValueTrainClip};
+    case FwdMode::Forced:             return {FwdSource::Rows, FwdTail::Forced};
+    case FwdMode::Imitate:            return {FwdSource::RowsIdx, FwdTail::Imitate};
+    case FwdMode::ImitateSnap:        return {FwdSource::SnapIdx, FwdTail::Imitate};
+    case FwdMode::Tempered:           return {FwdSource::Rows, FwdTail::Tempered};
+    case FwdMode::Greedy:             return {FwdSource::Rows, FwdTail::Greedy};
+    case FwdMode::Truncated:          return {FwdSource::Rows, FwdTail::Truncated};
+    }
+    return {FwdSource::Rows, FwdTail::Probs};
+}
+constexpr bool src_snapshot(FwdSource s) { return s == FwdSource::Snap || s == FwdSource::SnapIdx; }
+constexpr bool tail_value(FwdTail t) { return t == FwdTail::ValuePredict || t == FwdTail::ValueTrain || t == FwdTail::ValueTrainClip; }
+// train forward: saves the activations, writes dY and the loss terms
+constexpr bool tail_trains(FwdTail t) { return t == FwdTail::Train || t == FwdTail::Imitate || t == FwdTail::ValueTrain || t == FwdTail::ValueTrainClip; }
+// logits times 1 / temperature in front of the softmax
+constexpr bool tail_tempers(FwdTail t) { return t == FwdTail::Tempered || t == FwdTail::Greedy || t == FwdTail::Truncated; }
+// rand(Categorical): the Philox uniform and the CDF walk
+constexpr bool tail_samples(FwdTail t) { return t == FwdTail::Sample || t == FwdTail::SamplePersistent || t == FwdTail::Tempered || t == FwdTail::Truncated; }
+// one rollout step: an action, its probability and (on request) the whole distribution go to the output columns
+constexpr bool tail_steps(FwdTail t) { return tail_samples(t) || t == FwdTail::Greedy || t == FwdTail::Forced; }
+// the train mode the launchers run for an objective (clipped: the critic's clipped value loss), and the one the route strings
+// name: the clip is chosen at launch, while a value clip is set, and the routes keep naming 6 / 8
+constexpr FwdMode fwd_train_mode(Objective obj, bool compact, bool clipped = false) {
+    switch (obj) {
+    case Objective::Value:
+        if (clipped) return compact ? FwdMode::ValueTrainClipSnap : FwdMode::ValueTrainClip;
+        return compact ? FwdMode::ValueTrainSnap : FwdMode::ValueTrain;
+    case Objective::Imitate: return compact ? FwdMode::ImitateSnap : FwdMode::Imitate;
+    default: return compact ? FwdMode::TrainSnap : FwdMode::Train;
+    }
+}
+constexpr FwdMode fwd_route_mode(Objective obj, bool compact) { return fwd_train_mode(obj, compact, false); }
+
 // train-pass launchers: each launches what train_route chose and checks nothing else
 int32_t launch_policy_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B,
                                 int64_t B_global, double eps, double entropy_weight, const float* adv_col, TrainFwd form);
@@ -469,7 +534,7 @@ int32_t launch_value_predict(ppo_policy_s* p, const int8_t* states_dev, const in
                              const int8_t* tmpl_dev, int32_t V, int64_t B, int32_t H, float* values_dev);
 int32_t launch_value_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
                                const float* target_col, const float* vold_col, float vclip, float* vdelta_dst);
-// imitation train forward (ppo_policy_fwd.hip modes 12 / 13): cross-entropy of the buffer's actions, weighted by
+// imitation train forward (k_policy_fwd's FwdMode::Imitate / ImitateSnap): cross-entropy of the buffer's actions, weighted by
 // max(weight_col[transition], 0) (nullptr: uniform weights), plus the policy's entropy term
 int32_t launch_imitate_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
                                  double entropy_weight, const float* weight_col);
@@ -483,7 +548,7 @@ int32_t launch_policy_bwd_small(ppo_policy_s* p, ppo_rollouts_s* ro, const int32
 // forward + loss + backward-data of a tile in one workgroup, then the weight-gradient kernel (ppo_policy_train_tile.hip)
 int32_t launch_policy_train_tile(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
                                  double eps, double entropy_weight, const float* adv_col);
-// bf16 compute mode (ppo_policy_bf16.hip); MODE as in k_policy_fwd: 0 probs, 1 rollout, 2 train
+// bf16 compute mode (ppo_policy_bf16.hip): k_policy_fwd's modes Probs, Sample, Train and TrainSnap
 struct FwdArgs;
 // one-launch rollout with 2 or 4 waves per env for few envs, bit-identical results (ppo_policy_rollout_split.hip)
 int32_t launch_rollout_split(ppo_policy_s* p, FwdArgs& a, int64_t N, int tps, int V, int env);
@@ -491,7 +556,7 @@ int32_t launch_rollout_split(ppo_policy_s* p, FwdArgs& a, int64_t N, int tps, in
 int32_t launch_policy_train_fwd_split(ppo_policy_s* p, FwdArgs& a, int64_t B, bool compact);
 // train forward with its Dense products as split-fp32 MFMAs (ppo_policy_fwd_x6.hip); form: X6S, X6T or X6
 int32_t launch_policy_train_fwd_x6(ppo_policy_s* p, FwdArgs& a, int64_t B, TrainFwd form, bool compact);
-int32_t launch_policy_fwd_bf16(ppo_policy_s* p, FwdArgs& args, int mode, int64_t B, int tps);
+int32_t launch_policy_fwd_bf16(ppo_policy_s* p, FwdArgs& args, FwdMode mode, int64_t B, int tps);
 int32_t launch_policy_rollout_persistent_bf16(ppo_policy_s* p, FwdArgs& args, int64_t N, int tps, int V);
 int32_t launch_policy_bwd_bf16(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B);
 static inline int bf16_ks1(int F) { return (F + 15) / 16; }     // layer-1 k-steps of 16 (zero padded)

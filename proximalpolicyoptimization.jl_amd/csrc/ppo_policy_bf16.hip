@@ -138,20 +138,25 @@ struct FwdB {
     static constexpr size_t lds_bytes = (size_t)(W2_U4 + W3_U4) * 16 + (size_t)NT * 8 * 16 * 2;
 };
 
-template <int F, int HID, int MODE, int TPS>
+template <int F, int HID, FwdMode MODE, int TPS>
 __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs a) {
     using C = FwdB<F, HID>;
     constexpr int NT = C::NT, NS = C::NS, KS1 = C::KS1;
-    constexpr bool TRAIN = (MODE == 2 || MODE == 4);    // train forward: saves activations, loss tail
-    constexpr bool OBS = (MODE == 3 || MODE == 4);      // rows re-derived from an env snapshot in LDS (MODE 4: compact rollouts)
-    constexpr int TMODE = TRAIN ? 2 : MODE;
+    constexpr FwdSource SRC = fwd_traits(MODE).src;     // (this kernel has the modes Probs, Sample, Train, Persistent and TrainSnap)
+    constexpr FwdTail TAIL = fwd_traits(MODE).tail;
+    static_assert(!tail_value(TAIL) && SRC != FwdSource::Snap, "no bf16 form of this mode");
+    constexpr bool TRAIN = tail_trains(TAIL);           // train forward: saves activations, loss tail
+    constexpr bool GATHER = SRC == FwdSource::RowsIdx;
+    constexpr bool SNAPX = SRC == FwdSource::SnapIdx;   // compact rollouts: env snapshots through idx, the rows left in xs_out
+    constexpr bool PERSIST = SRC == FwdSource::EnvSlots;
+    constexpr bool OBS = (PERSIST || SNAPX);            // rows re-derived from an env snapshot in LDS
     static_assert(F % 8 == 0 && HID % 32 == 0, "shape");
     extern __shared__ __attribute__((aligned(16))) uint4 smem_u4[];
     uint4* const sW2 = smem_u4;
     uint4* const sW3 = sW2 + C::W2_U4;
     float4* const sB1 = reinterpret_cast<float4*>(sW3 + C::W3_U4);
     float4* const sB2 = sB1 + NT * 8;
-    char* const env_lds = reinterpret_cast<char*>(sB2 + NT * 8);     // MODE 3: env slots of the 8 waves
+    char* const env_lds = reinterpret_cast<char*>(sB2 + NT * 8);     // PERSIST: env slots of the 8 waves
     const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, h = lane >> 5;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
 #ifdef PPO_BF16_STAMP
@@ -172,7 +177,7 @@ __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs 
     // layer-3 A operand: rows 0..3 of the 32-row operand tile are W3, the rest zero (lanes j >= 4 read the zero block)
     const int w3_lane = (j < 4) ? (h * 4 + j) : -1;
 
-    // ---- MODE 3: persistent rollout (see k_policy_fwd): every wave walks its envs through all T steps; W2 is staged in
+    // ---- PERSIST: persistent rollout (see k_policy_fwd): every wave walks its envs through all T steps; W2 is staged in
     // LDS once per ROLLOUT instead of once per step.  Env state lives in the wave's LDS slots.
     const int64_t wave0 = (int64_t)blockIdx.x * FWB_W + w, nwaves = (int64_t)gridDim.x * FWB_W;
     const int slot_bytes = 2 * a.envV + 32;
@@ -188,7 +193,7 @@ __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs 
         return r;
     };
     uint32_t tmpl_regs[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (MODE == 3) {
+    if (PERSIST) {
         ec.Q = a.envQ; ec.V = a.envV; ec.max_actions = a.env_max_actions; ec.no_action_reward = a.env_nar; ec.k0 = a.k0; ec.k1 = a.k1;
         int slot = 0;
         for (int64_t n = wave0; n < a.B; n += nwaves, ++slot) {
@@ -216,7 +221,7 @@ __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs 
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
-    // MODE 4: env snapshot of a transition fetched through idx one state ahead (see k_policy_fwd)
+    // SNAPX: env snapshot of a transition fetched through idx one state ahead (see k_policy_fwd)
     uint32_t cs_next = 0u, act_next = 0u;
     int32_t sid_next = 0;
     auto fetch_snapshot = [&](int64_t state) {
@@ -225,25 +230,25 @@ __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs 
         const int nd = a.envV >> 1;
         cs_next = (lane < nd) ? reinterpret_cast<const uint32_t*>(a.cstate)[(size_t)sid_next * nd + lane] : 0u;
     };
-    if (MODE == 4 && wave0 < a.B) fetch_snapshot(wave0);
-    const int64_t t_steps = (MODE == 3) ? a.T : 1;
+    if (SNAPX && wave0 < a.B) fetch_snapshot(wave0);
+    const int64_t t_steps = PERSIST ? a.T : 1;
     FBSTAMP(0);
     for (int64_t tstep = 0; tstep < t_steps; ++tstep) {
     int slot = 0;
     for (int64_t state = wave0; state < a.B; state += nwaves, ++slot) {
-        const int64_t sid = (MODE == 2) ? (int64_t)a.idx[state] : ((MODE == 4) ? (int64_t)sid_next : state);
+        const int64_t sid = GATHER ? (int64_t)a.idx[state] : (SNAPX ? (int64_t)sid_next : state);
         EnvRefLds er = {};
-        if (MODE == 3) er = slot_ref(slot);
-        if (MODE == 4) {
+        if (PERSIST) er = slot_ref(slot);
+        if (SNAPX) {
             er = slot_ref(0);
             if (lane < (a.envV >> 1)) reinterpret_cast<PPO_LDS uint32_t*>(er.sc)[lane] = cs_next;
             if (lane == 0) *er.active = act_next;
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
-        const uint32_t act = (MODE == 3) ? *er.active : ((MODE == 4) ? act_next : a.active[sid]);
-        if (MODE == 4) fetch_snapshot(state + nwaves < a.B ? state + nwaves : state);
-        const uint32_t tick_val = (MODE == 3) ? *er.tick : ((MODE == 1) ? a.tick[state] : 0u);
-        const int64_t out_index = (MODE == 3) ? tstep * a.B + state : state;
+        const uint32_t act = PERSIST ? *er.active : (SNAPX ? act_next : a.active[sid]);
+        if (SNAPX) fetch_snapshot(state + nwaves < a.B ? state + nwaves : state);
+        const uint32_t tick_val = PERSIST ? *er.tick : (tail_samples(TAIL) ? a.tick[state] : 0u);
+        const int64_t out_index = PERSIST ? tstep * a.B + state : state;
         float l[TPS][4];
 #pragma unroll
         for (int tt = 0; tt < TPS; ++tt) l[tt][0] = l[tt][1] = l[tt][2] = l[tt][3] = 0.0f;
@@ -254,7 +259,7 @@ __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs 
             const int64_t tile = state * TPS + ts;
             // ---- state rows -> layer-1 B operands: lane (row j, half h) holds features 16s + 8h .. +7 of k-step s
             const int8_t* row = OBS ? nullptr : a.states + ((size_t)sid * TPS + ts) * 32 * F + (size_t)j * F;
-            uint32_t ob[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};       // MODE 3 / 4: this lane's 36 observed features (half h of row j)
+            uint32_t ob[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};       // OBS: this lane's 36 observed features (half h of row j)
             if (OBS) {
                 static_assert(!OBS || F == 72, "the built-in env has F = 72 features");
                 uint32_t tid9[9];
@@ -272,13 +277,13 @@ __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs 
                     for (int k = 0; k < 9; ++k) tid9[k] = tp[k];
                 }
                 env_observe_lane(er, tid9, 32 * ts + j, h, ob);
-                int8_t* const rows_out = (MODE == 4) ? a.xs_out : a.states_out;
+                int8_t* const rows_out = SNAPX ? a.xs_out : a.states_out;
                 if (rows_out) {                                  // wave-uniform
-                    uint32_t* so = reinterpret_cast<uint32_t*>(rows_out + ((size_t)(MODE == 4 ? state : out_index) * TPS + ts) * 32 * F + (size_t)j * F + (size_t)h * 36);
+                    uint32_t* so = reinterpret_cast<uint32_t*>(rows_out + ((size_t)(SNAPX ? state : out_index) * TPS + ts) * 32 * F + (size_t)j * F + (size_t)h * 36);
 #pragma unroll
                     for (int k = 0; k < 9; ++k) so[k] = ob[k];
                 }
-                if (MODE == 3 && ts == 0 && a.cstate_out && lane < (a.envV >> 1))      // compact storage: the env snapshot itself
+                if (PERSIST && ts == 0 && a.cstate_out && lane < (a.envV >> 1))      // compact storage: the env snapshot itself
                     reinterpret_cast<uint32_t*>(a.cstate_out)[(size_t)out_index * (a.envV >> 1) + lane] =
                         reinterpret_cast<PPO_LDS uint32_t*>(er.sc)[lane];
             }
@@ -402,7 +407,7 @@ __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs 
             // feature tiles (left alone hipcc keeps two fragments in flight and waits for each one a single 32-clock MFMA
             // after issuing its read; sched_barrier pins the order).  The last tile's look-ahead reads the first
             // fragments of what follows W2 in LDS (W3 / bias packs: in bounds, never used).
-            constexpr int WQ = (MODE == 4 && TPS == 4) ? 2 : PPO_BF16_FWD_WQ;      // (that instantiation has no registers to spare)
+            constexpr int WQ = (SNAPX && TPS == 4) ? 2 : PPO_BF16_FWD_WQ;      // (that instantiation has no registers to spare)
             uint4 wq[WQ];
 #pragma unroll
             for (int k = 0; k < WQ; ++k) wq[k] = sW2[k * 64 + lane];
@@ -449,7 +454,7 @@ __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs 
                 }
             };
             // (one epilogue slice per k-step: the interleaved form needs 16 of each, i.e. HID = 256)
-            constexpr bool PIPE2 = PPO_BF16_FWD_PIPE && (NT % 2 == 0) && (NS == 16) && (TPS == 1 || MODE <= 1 || PPO_BF16_FWD_PIPE > 1);
+            constexpr bool PIPE2 = PPO_BF16_FWD_PIPE && (NT % 2 == 0) && (NS == 16) && (TPS == 1 || SRC == FwdSource::Rows || PPO_BF16_FWD_PIPE > 1);
             if constexpr (PIPE2) {
                 f32x16 acc0, acc1;
                 bias_init(acc0, 0);
@@ -490,10 +495,10 @@ __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs 
 #pragma unroll
                 for (int i = 0; i < 4; ++i) l[tt][i] = (tt == ts) ? lg[i] : l[tt][i];
         }
-        const int sampled = policy_tail<TMODE, TPS, true>(a, state, sid, act, l, lane, j, h, tick_val, out_index,
+        const int sampled = policy_tail<TAIL, TPS, true>(a, state, sid, act, l, lane, j, h, tick_val, out_index,
                                                           (TRAIN && PPO_BF16_STORE_LATE) ? &tpre : nullptr);
         FBSTAMP(4);
-        if (MODE == 3) {
+        if (PERSIST) {
             asm volatile("" ::: "memory");
             if (TPS == 1) {                                  // Q == 8: wavefront-parallel env update
                 float rew; uint8_t dn;
@@ -526,7 +531,7 @@ __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs 
     if (a.stamps && lane == 0 && wave0 < 2048)
         for (int i = 0; i < 6; ++i) a.stamps[wave0 * 6 + i] = st_sum[i];
 #endif
-    if (MODE == 3) {                                            // env state back to the [N] arrays
+    if (PERSIST) {                                              // env state back to the [N] arrays
         int slot2 = 0;
         for (int64_t n = wave0; n < a.B; n += nwaves, ++slot2) {
             const EnvRefLds r = slot_ref(slot2);
@@ -554,16 +559,16 @@ static void set_fwd_stamps(FwdArgs& a) {
 static void set_fwd_stamps(FwdArgs&) {}
 #endif
 
-template <int MODE>
+template <FwdMode MODE>
 static int32_t dispatch_fwd_bf16(ppo_policy_s* p, const FwdArgs& args, int64_t B, int tps) {
     set_fwd_stamps(const_cast<FwdArgs&>(args));
     const int64_t need = (B + FWB_W - 1) / FWB_W;
     const unsigned grid = (unsigned)(need < 256 ? need : 256);
 #define LAUNCHB(FF, HH, TT)                                                                                          \
     do {                                                                                                             \
-        /* MODE 4: one env-snapshot slot per wave + the template rows behind them */                               \
+        /* TrainSnap: one env-snapshot slot per wave + the template rows behind them */                               \
         /* + the W2 queue's look-ahead past the last feature tile (the persistent form's env slots cover it there) */ \
-        const size_t lds = FwdB<FF, HH>::lds_bytes + PPO_BF16_FWD_WQ * 1024 + (MODE == 4 ? (size_t)FWB_W * (2 * args.envV + 32) + 32 * PPO_TPL : 0); \
+        const size_t lds = FwdB<FF, HH>::lds_bytes + PPO_BF16_FWD_WQ * 1024 + (MODE == FwdMode::TrainSnap ? (size_t)FWB_W * (2 * args.envV + 32) + 32 * PPO_TPL : 0); \
         static thread_local size_t attr_lds = 0;                                                                                  \
         if (lds > attr_lds) {                                                                                        \
             HIP_TRY(hipFuncSetAttribute((const void*)k_policy_fwd_bf16<FF, HH, MODE, TT>,                            \
@@ -600,11 +605,11 @@ int32_t launch_policy_rollout_persistent_bf16(ppo_policy_s* p, FwdArgs& a, int64
         lds = std::max(lds, (size_t)FwdB<72, HH>::W2_U4 * 16 + PPO_BF16_FWD_WQ * 1024);                              \
         static thread_local size_t attr_lds = 0;                                                                                  \
         if (lds > attr_lds) {                                                                                        \
-            HIP_TRY(hipFuncSetAttribute((const void*)k_policy_fwd_bf16<72, HH, 3, TT>,                               \
+            HIP_TRY(hipFuncSetAttribute((const void*)k_policy_fwd_bf16<72, HH, FwdMode::Persistent, TT>,                               \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                      \
             attr_lds = lds;                                                                                          \
         }                                                                                                            \
-        hipLaunchKernelGGL((k_policy_fwd_bf16<72, HH, 3, TT>), dim3(grid), dim3(FWB_T), lds, ppo_stream(), a);       \
+        hipLaunchKernelGGL((k_policy_fwd_bf16<72, HH, FwdMode::Persistent, TT>), dim3(grid), dim3(FWB_T), lds, ppo_stream(), a);       \
     } while (0)
     if (p->HID == 256 && tps == 1) LAUNCHP(256, 1);
     else if (p->HID == 128 && tps == 1) LAUNCHP(128, 1);
@@ -614,13 +619,13 @@ int32_t launch_policy_rollout_persistent_bf16(ppo_policy_s* p, FwdArgs& a, int64
     return PPO_OK;
 }
 
-int32_t launch_policy_fwd_bf16(ppo_policy_s* p, FwdArgs& a, int mode, int64_t B, int tps) {
+int32_t launch_policy_fwd_bf16(ppo_policy_s* p, FwdArgs& a, FwdMode mode, int64_t B, int tps) {
     a.w1b = (const uint4*)p->w1b.p; a.w2b = (const uint4*)p->w2b.p; a.w3c = (const uint4*)p->w3c.p;
     a.act1b = PPO_BF16_H1_RECOMPUTE ? nullptr : (uint4*)p->act1.p; a.act2b = (uint4*)p->act2.p;
-    if (mode == 0) return dispatch_fwd_bf16<0>(p, a, B, tps);
-    if (mode == 1) return dispatch_fwd_bf16<1>(p, a, B, tps);
-    if (mode == 4) return dispatch_fwd_bf16<4>(p, a, B, tps);
-    return dispatch_fwd_bf16<2>(p, a, B, tps);
+    if (mode == FwdMode::Probs) return dispatch_fwd_bf16<FwdMode::Probs>(p, a, B, tps);
+    if (mode == FwdMode::Sample) return dispatch_fwd_bf16<FwdMode::Sample>(p, a, B, tps);
+    if (mode == FwdMode::TrainSnap) return dispatch_fwd_bf16<FwdMode::TrainSnap>(p, a, B, tps);
+    return dispatch_fwd_bf16<FwdMode::Train>(p, a, B, tps);
 }
 
 // ================================================================ backward

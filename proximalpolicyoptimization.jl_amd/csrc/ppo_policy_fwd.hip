@@ -50,27 +50,7 @@ static __device__ __forceinline__ void act_store_nt(float4* p, float4 v) {
 #ifndef PPO_FWD_PF_SMALL_TRAIN
 #define PPO_FWD_PF_SMALL_TRAIN PPO_FWD_PF   // their train-forward ring depth
 #endif
-// k_policy_fwd's MODE: 0 probabilities, 1 one rollout step, 2 train forward (rows gathered through idx), 3 persistent
-// rollout, 4 train forward from compact env snapshots (through idx); and the critic's (value_tail instead of policy_tail):
-// 5 value-predict on rows [B][H][F], 6 value-train (= 2), 7 value-predict on snapshots [B][2V], 8 value-train (= 4);
-// 9 / 10: 6 / 8 with PPO's clipped value loss (value_tail VMODE 2).  Own modes rather than a runtime test in the tail: with the
-// test, value_train_ at the headline shape measured 0.4 % more per iteration's critic part with the clip unset (the register
-// allocation of k_policy_fwd<72,256,6,1,0> moved), outside the range of the parent's own runs; 6 / 8 are now the parent's code
-// 11: one teacher-forced step: MODE 1's forward and outputs with the action read from a.actions instead of
-// sampled (policy_tail's mode 11); an own mode for the same reason, MODE 1 is the parent's code
-// 12 / 13: imitation train forward: 2 / 4 with the cross-entropy of the stored action as the loss tail
-// (policy_tail's mode 12); own modes for the same reason, 2 / 4 are the parent's code
-// 14 / 15: one rollout step under a selection rule: MODE 1's forward with the logits scaled by 1 / temperature in
-// front of the softmax; 14 samples like MODE 1, 15 plays the first maximum (policy_tail's modes 14 / 15).  Own modes again
-// 16: 14 sampling from the top-k / nucleus truncation of the tempered distribution (policy_tail's mode 16).  An
-// own mode once more: 14 is the parent's code
-constexpr bool fwd_mode_value(int m) { return m >= 5 && m <= 10; }
-constexpr bool fwd_mode_vclip(int m) { return m == 9 || m == 10; }
-constexpr bool fwd_mode_imitate(int m) { return m == 12 || m == 13; }
-constexpr bool fwd_mode_train(int m) { return m == 2 || m == 4 || m == 6 || m == 8 || fwd_mode_vclip(m) || fwd_mode_imitate(m); }   // saves activations, writes dY
-constexpr bool fwd_mode_gather(int m) { return m == 2 || m == 6 || m == 9 || m == 12; }  // expanded rows through idx
-constexpr bool fwd_mode_snap(int m) { return m == 4 || m == 7 || m == 8 || m == 10 || m == 13; }    // one env snapshot per state in LDS
-constexpr bool fwd_mode_snap_idx(int m) { return m == 4 || m == 8 || m == 10 || m == 13; }          // ... fetched through idx, rows -> xs_out
+// k_policy_fwd's MODE: FwdMode, and the table fwd_traits from a mode to its state source and its tail (ppo_internal.h)
 
 template <int F, int HID>
 struct FwdCfg { static constexpr int WPS = (HID >= 256 || F > 128) ? 1 : PPO_FWD_WPS_SMALL; };
@@ -82,9 +62,9 @@ struct FwdCfg { static constexpr int WPS = (HID >= 256 || F > 128) ? 1 : PPO_FWD
 // rows, no barrier: only the wave itself reads them back) and re-loaded as the next layer's B operands; the last one feeds
 // the layer-3 dot epilogue as before (nl2 == 0: the dot runs on the layer-1 tiles).  Every layer walks its contraction in
 // the same accumulator-register order as layer 2, so the fp32 chain order per layer is the one the oracle's device-order
-// mode mirrors.  DEEP = 0 is the num_hidden_layers == 2 kernel, unchanged.  MODE 3 (persistent rollout) has no deep form:
+// mode mirrors.  DEEP = 0 is the num_hidden_layers == 2 kernel, unchanged.  The persistent rollout has no deep form:
 // its env slots and the park would share the LDS; deep policies roll out with the per-step launches.
-template <int F, int HID, int MODE, int TPS, int DEEP = 0>
+template <int F, int HID, FwdMode MODE, int TPS, int DEEP = 0>
 __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdArgs a) {
     constexpr int NT = HID / 32;       // 32-feature tiles
     constexpr int S41 = F / 8;         // float4 groups of layer-1 k-steps
@@ -103,17 +83,20 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
     // two waves per SIMD (HID = 128, F = 72): 4 groups cover the L2 latency; the train forward, whose activation stores
     // sit in the same vmcnt queue, wants the deep ring here too (0.072 -> 0.069 ms), the rollout does not (8.3 -> 8.7 ms)
     constexpr int PFT = (PPO_FWD_PF_SMALL_TRAIN < HID / 8) ? PPO_FWD_PF_SMALL_TRAIN : HID / 8;
-    constexpr bool TRAIN = fwd_mode_train(MODE);        // train forward: saves activations, loss tail
-    constexpr bool VALUE = fwd_mode_value(MODE);        // critic: value_tail
-    constexpr bool GATHER = fwd_mode_gather(MODE);
-    constexpr bool SNAP = fwd_mode_snap(MODE), SNAPX = fwd_mode_snap_idx(MODE);
+    constexpr FwdSource SRC = fwd_traits(MODE).src;
+    constexpr FwdTail TAIL = fwd_traits(MODE).tail;
+    constexpr bool TRAIN = tail_trains(TAIL);           // train forward: saves activations, loss tail
+    constexpr bool VALUE = tail_value(TAIL);            // critic: value_tail
+    constexpr bool IMITATE = TAIL == FwdTail::Imitate;
+    constexpr bool GATHER = SRC == FwdSource::RowsIdx;
+    constexpr bool SNAP = src_snapshot(SRC), SNAPX = SRC == FwdSource::SnapIdx;
+    constexpr bool PERSIST = SRC == FwdSource::EnvSlots;    // persistent rollout: T steps of the wave's envs, their state in LDS slots
     // (value-train from snapshots keeps half the train ring at two waves per SIMD: with 16 groups next to the row
     // re-derivation it does not fit the 256 registers)
     constexpr int PFV = (PFT < 8) ? PFT : 8;
-    // (the imitation forward from snapshots likewise: with 16 groups mode 13 spills where MODE 4 does, 196 / 60 / 116 bytes per lane)
-    constexpr int PF = (FwdCfg<F, HID>::WPS == 1) ? PFW : (TRAIN ? (((VALUE || fwd_mode_imitate(MODE)) && SNAP) ? PFV : PFT) : 4);   // weight-fragment groups kept in flight per wave
-    constexpr bool OBS = (MODE == 3 || SNAP);           // the state rows are re-derived from an env snapshot in LDS
-    constexpr int TMODE = fwd_mode_imitate(MODE) ? 12 : (TRAIN ? 2 : MODE);   // policy_tail's mode
+    // (the imitation forward from snapshots likewise: with 16 groups ImitateSnap spills where TrainSnap does, 196 / 60 / 116 bytes per lane)
+    constexpr int PF = (FwdCfg<F, HID>::WPS == 1) ? PFW : (TRAIN ? (((VALUE || IMITATE) && SNAP) ? PFV : PFT) : 4);   // weight-fragment groups kept in flight per wave
+    constexpr bool OBS = (PERSIST || SNAP);             // the state rows are re-derived from an env snapshot in LDS
     static_assert(F % 8 == 0 && HID % 32 == 0, "shape");
     static_assert(PF * 64 * 4 <= PPO_PACK_PAD, "the ring reads PF groups past the end of a packed weight stream: padding must cover it");
     const int lane = threadIdx.x & 63;
@@ -128,7 +111,7 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
     __shared__ __attribute__((aligned(16))) float4 sB1[NT * 2 * 4];      // [tile][half][4]    (HID floats)
     constexpr int NB2L = DEEP ? 3 : 1;                                   // bias packs of up to three hidden->hidden layers
     __shared__ __attribute__((aligned(16))) float4 sB2[NB2L * NT * 2 * 4];
-    static_assert(!(DEEP && MODE == 3), "no deep persistent rollout");
+    static_assert(!(DEEP && PERSIST), "no deep persistent rollout");
     for (int i = threadIdx.x; i < 2 * NT * 16; i += 256) sW3[i] = a.w3p[i];
     for (int i = threadIdx.x; i < NT * 8; i += 256) sB1[i] = a.b1p[i];
     for (int i = threadIdx.x; i < NT * 8 * (DEEP ? a.nl2 : 1); i += 256) sB2[i] = a.b2p[i];
@@ -137,7 +120,7 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
     // the rows of the NEXT 32-row tile are fetched while the current one computes (the gather through idx is two
     // dependent HBM round trips that one wave per SIMD cannot hide otherwise)
     constexpr bool PFX = (FwdCfg<F, HID>::WPS == 1) && !OBS;      // with two waves per SIMD the partner wave hides it instead;
-                                                                  // MODE 3 / 4 compute the rows themselves (no fetch)
+                                                                  // OBS: the wave computes the rows itself (no fetch)
     uint32_t xw[XW];
     auto fetch_rows = [&](int64_t state, int ts) {
         const int64_t sidn = GATHER ? (int64_t)a.idx[state] : state;
@@ -154,7 +137,7 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
 #else
 #define FSTAMP(i) do {} while (0)
 #endif
-    // ---- MODE 3: persistent rollout.  Envs are independent, so every wave walks ITS envs (state = wave, wave + nwaves,
+    // ---- PERSIST: persistent rollout.  Envs are independent, so every wave walks ITS envs (state = wave, wave + nwaves,
     // ...) through all T steps without any grid-wide synchronisation: observe -> MLP -> sample -> step!, with the env
     // state (scores, degrees, counters) resident in the wave's LDS slots and written back once at the end.
     extern __shared__ __attribute__((aligned(16))) char env_lds[];
@@ -170,7 +153,7 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
         r.done = (PPO_LDS uint8_t*)(w + 3); r.episode = w + 4; r.tick = w + 5;
         return r;
     };
-    if (MODE == 3) {
+    if (PERSIST) {
         ec.Q = a.envQ; ec.V = a.envV; ec.max_actions = a.env_max_actions; ec.no_action_reward = a.env_nar; ec.k0 = a.k0; ec.k1 = a.k1;
         int slot = 0;
         for (int64_t n = wave; n < a.B; n += nwaves, ++slot) {
@@ -183,13 +166,13 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // slots are wave-private: program order + in-order LDS suffice
     }
-    uint32_t tmpl_regs[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};       // MODE 3 / 4, TPS == 1: this lane's 36 template vertex ids
+    uint32_t tmpl_regs[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};       // OBS, TPS == 1: this lane's 36 template vertex ids
     if (OBS && TPS == 1) {
         const uint32_t* tp = reinterpret_cast<const uint32_t*>(a.env_tmpl + j * PPO_TPL);
 #pragma unroll
         for (int k = 0; k < 9; ++k) tmpl_regs[k] = tp[k];
     }
-    // MODE 4: the env snapshot of a transition (2V bytes + the active-quad word) is fetched through idx one state ahead
+    // SNAP: the env snapshot of a state (2V bytes + the active-quad word) is fetched (SNAPX: through idx) one state ahead
     // (two dependent HBM round trips) into registers and parked in the wave's LDS slot at the top of its state
     // (one dword per lane: 2V/4 <= 64 dwords for V <= 128)
     uint32_t cs_next = 0u, act_next = 0u;
@@ -201,32 +184,32 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
         cs_next = (lane < nd) ? reinterpret_cast<const uint32_t*>(a.cstate)[(size_t)sid_next * nd + lane] : 0u;
     };
     if (SNAP && wave < a.B) fetch_snapshot(wave);
-    const int64_t t_steps = (MODE == 3) ? a.T : 1;
+    const int64_t t_steps = PERSIST ? a.T : 1;
     for (int64_t tt = 0; tt < t_steps; ++tt) {
     int slot = 0;
     for (int64_t state = wave; state < a.B; state += nwaves, ++slot) {
         const int64_t sid = GATHER ? (int64_t)a.idx[state] : (SNAP ? (int64_t)sid_next : state);
         EnvRefLds er = {};
-        if (MODE == 3) er = slot_ref(slot);
+        if (PERSIST) er = slot_ref(slot);
         if (SNAP) {
             er = slot_ref(0);
             if (lane < (a.envV >> 1)) reinterpret_cast<PPO_LDS uint32_t*>(er.sc)[lane] = cs_next;
             if (lane == 0) *er.active = act_next;
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // wave-private slot: program order + in-order LDS suffice
         }
-        const uint32_t act = (MODE == 3) ? *er.active : (SNAP ? act_next : a.active[sid]);
+        const uint32_t act = PERSIST ? *er.active : (SNAP ? act_next : a.active[sid]);
         // value-train: the target is fetched here, ahead of the activation stores it would otherwise queue behind (vmcnt)
         float vtarget = 0.0f, vold = 0.0f;
         if (VALUE && TRAIN) vtarget = a.vtarget[sid];
-        if (fwd_mode_vclip(MODE)) vold = a.vold[sid];                  // clipped value loss: the old value, likewise
+        if (TAIL == FwdTail::ValueTrainClip) vold = a.vold[sid];                  // clipped value loss: the old value, likewise
         if (SNAP) fetch_snapshot(state + nwaves < a.B ? state + nwaves : state);      // lands under this state's MFMAs
-        const uint32_t tick_val = (MODE == 3) ? *er.tick : ((MODE == 1 || MODE == 14 || MODE == 16) ? a.tick[state] : 0u);
-        const int64_t out_index = (MODE == 3) ? tt * a.B + state : state;
+        const uint32_t tick_val = PERSIST ? *er.tick : (tail_samples(TAIL) ? a.tick[state] : 0u);
+        const int64_t out_index = PERSIST ? tt * a.B + state : state;
         // teacher-forced step: the state's given action, fetched here like the tick so that it has landed by the tail
         [[maybe_unused]] TailPre forced = {0, 0.0f, 0.0f};
-        if constexpr (MODE == 11) forced.ab = a.actions[state];
+        if constexpr (TAIL == FwdTail::Forced) forced.ab = a.actions[state];
         // imitation: the stored action and its weight (a.adv == nullptr: uniform), ahead of the activation stores like vtarget
-        if constexpr (fwd_mode_imitate(MODE)) { forced.ab = a.actions[sid]; forced.adv = a.adv ? a.adv[sid] : 1.0f; }
+        if constexpr (IMITATE) { forced.ab = a.actions[sid]; forced.adv = a.adv ? a.adv[sid] : 1.0f; }
         float l[TPS][4];
         // multi-tile states: the tile loop stays a real loop (no 4x code blow-up, no cross-tile hoisting that
         // would spill); the 4 logits per lane of each tile are parked in LDS and re-read after the loop
@@ -242,7 +225,7 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
             // ---- state rows -> B operands of layer 1: lane half 0 holds features [0,F/2), half 1 [F/2,F)
             if (OBS) {
                 // state(env): this lane's 36 features of half-edge row 32*ts + j, recorded into the rollout buffer
-                // (MODE 3, expanded storage) or into the minibatch-ordered row scratch the backward reads (MODE 4)
+                // (PERSIST, expanded storage) or into the minibatch-ordered row scratch the backward reads (SNAPX)
                 static_assert(!OBS || XW == 9, "the built-in env has F = 72 features");
                 uint32_t ob[9], tid[9];
                 if (TPS == 1) {
@@ -256,14 +239,14 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
                 env_observe_lane(er, tid, 32 * ts + j, h, ob);
 #pragma unroll
                 for (int k = 0; k < XW; ++k) xw[k] = ob[k < 9 ? k : 0];
-                int8_t* const rows_out = SNAPX ? a.xs_out : ((MODE == 3) ? a.states_out : nullptr);
+                int8_t* const rows_out = SNAPX ? a.xs_out : (PERSIST ? a.states_out : nullptr);
                 if (rows_out) {                                  // wave-uniform
                     uint32_t* so = reinterpret_cast<uint32_t*>(rows_out + ((size_t)(SNAPX ? state : out_index) * TPS + ts) * 32 * F +
                                                                (size_t)j * F + (size_t)h * XB);
 #pragma unroll
                     for (int k = 0; k < XW; ++k) so[k] = xw[k];
                 }
-                if (MODE == 3 && ts == 0 && a.cstate_out && lane < (a.envV >> 1))      // compact storage: the env snapshot itself
+                if (PERSIST && ts == 0 && a.cstate_out && lane < (a.envV >> 1))      // compact storage: the env snapshot itself
                     reinterpret_cast<uint32_t*>(a.cstate_out)[(size_t)out_index * (a.envV >> 1) + lane] =
                         reinterpret_cast<PPO_LDS uint32_t*>(er.sc)[lane];
             } else if (!PFX) fetch_rows(state, ts);
@@ -468,11 +451,10 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
 
         FSTAMP(4);
         int sampled = 0;
-        if constexpr (VALUE) value_tail<fwd_mode_vclip(MODE) ? 2 : (TRAIN ? 1 : 0), TPS>(a, state, act, l, lane, j, h, out_index, vtarget, vold);
-        else if constexpr (MODE == 11) sampled = policy_tail<11, TPS, false>(a, state, sid, act, l, lane, j, h, 0u, out_index, &forced);
-        else if constexpr (fwd_mode_imitate(MODE)) sampled = policy_tail<12, TPS, false>(a, state, sid, act, l, lane, j, h, 0u, out_index, &forced);
-        else sampled = policy_tail<TMODE, TPS, false>(a, state, sid, act, l, lane, j, h, tick_val, out_index);
-        if (MODE == 3) {
+        if constexpr (VALUE) value_tail<TAIL, TPS>(a, state, act, l, lane, j, h, out_index, vtarget, vold);
+        else if constexpr (TAIL == FwdTail::Forced || IMITATE) sampled = policy_tail<TAIL, TPS, false>(a, state, sid, act, l, lane, j, h, 0u, out_index, &forced);
+        else sampled = policy_tail<TAIL, TPS, false>(a, state, sid, act, l, lane, j, h, tick_val, out_index);
+        if (PERSIST) {
             // update!: the observed mask, then step!(env, a), reward, is_terminal (src/collect_rollouts.jl:9-14) and the
             // reset! before the next episode (src/rollout_buffer.jl:75) -- one lane, on the LDS slot
             asm volatile("" ::: "memory");
@@ -503,7 +485,7 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
         FSTAMP(5);
     }
     }
-    if (MODE == 3) {                                            // env state back to the [N] arrays
+    if (PERSIST) {                                              // env state back to the [N] arrays
         int slot2 = 0;
         for (int64_t n = wave; n < a.B; n += nwaves, ++slot2) {
             const EnvRefLds r = slot_ref(slot2);
@@ -536,61 +518,42 @@ __global__ void k_categorical(const float* __restrict__ probs, const float* __re
     err[b] = !(p[i] > 0.0f);
 }
 
-// num_hidden_layers != 2: the layer-looped instantiations (DEEP = 1).  Dynamic LDS = [MODE 4 / 7 / 8: one env-snapshot slot per
-// wave][park: 4 waves x HID/32 tiles x 4 KiB].
-template <int MODE>
-static int32_t dispatch_fwd_deep(ppo_policy_s* p, const FwdArgs& args, int64_t B, int tps) {
+// One launch of k_policy_fwd<F, HID, MODE, tps, DEEP> on persistent waves: 256 CUs x WPS blocks of 4 waves (one per SIMD).
+// DEEP = 0 is the entry: num_hidden_layers == 2 launches here, every other depth the layer-looped instantiations (DEEP = 1).
+// Dynamic LDS = [snapshot sources: one env-snapshot slot per wave][DEEP: the park, 4 waves x HID/32 tiles x 4 KiB]
+template <FwdMode MODE, int DEEP = 0>
+static int32_t dispatch_fwd(ppo_policy_s* p, const FwdArgs& args, int64_t B, int tps) {
+    if constexpr (!DEEP) {
+        if (p->L != 2) return dispatch_fwd<MODE, 1>(p, args, B, tps);
+    }
+    constexpr bool SNAP = src_snapshot(fwd_traits(MODE).src);
     const int64_t need = (B + 3) / 4;
     FwdArgs a = args;
-    a.nl2 = p->L - 1;
-    const size_t snap = fwd_mode_snap(MODE) ? (((size_t)4 * (2 * a.envV + 32) + 15) & ~(size_t)15) : 0;
-    a.park_off = (uint32_t)snap;
-#define LAUNCHD(FF, HH, TT)                                                                              \
-    do {                                                                                                 \
-        const int64_t cap = 256 * FwdCfg<FF, HH>::WPS;                                                   \
-        const unsigned grid = (unsigned)(need < cap ? need : cap);                                       \
-        a.wg_sync = 0;                                                                                   \
-        if constexpr (fwd_mode_snap(MODE) && FF != 72) {                                                 \
-            ppo_set_error("compact rollouts need the built-in env's F = 72"); return PPO_ERR_UNSUPPORTED; \
-        } else {                                                                                         \
-            const size_t dlds = snap + (size_t)4 * (HH / 32) * 4096;                                     \
-            static thread_local size_t attr_lds = 0;                                                                  \
-            if (dlds > attr_lds) {                                                                       \
-                HIP_TRY(hipFuncSetAttribute((const void*)k_policy_fwd<FF, HH, MODE, TT, 1>,              \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds));     \
-                attr_lds = dlds;                                                                         \
-            }                                                                                            \
-            hipLaunchKernelGGL((k_policy_fwd<FF, HH, MODE, TT, 1>), dim3(grid), dim3(256), dlds, ppo_stream(), a); \
-        }                                                                                                \
-    } while (0)
-    if (p->F == 72 && p->HID == 256 && tps == 1) LAUNCHD(72, 256, 1);
-    else if (p->F == 72 && p->HID == 256 && tps == 4) LAUNCHD(72, 256, 4);
-    else if (p->F == 72 && p->HID == 128 && tps == 1) LAUNCHD(72, 128, 1);
-    else if (p->F == 72 && p->HID == 128 && tps == 4) LAUNCHD(72, 128, 4);
-    else if (p->F == 216 && p->HID == 128 && tps == 1) LAUNCHD(216, 128, 1);
-    else if (p->F == 216 && p->HID == 256 && tps == 1) LAUNCHD(216, 256, 1);
-    else { ppo_set_error("unsupported policy/state shape (F,HID,H) for the gfx950 kernels"); return PPO_ERR_UNSUPPORTED; }
-#undef LAUNCHD
-    HIP_TRY(hipGetLastError());
-    return PPO_OK;
-}
-
-template <int MODE>
-static int32_t dispatch_fwd(ppo_policy_s* p, const FwdArgs& args, int64_t B, int tps) {
-    if (p->L != 2) return dispatch_fwd_deep<MODE>(p, args, B, tps);
-    const int64_t need = (B + 3) / 4;
-    // persistent waves: 256 CUs x WPS blocks of 4 waves (one per SIMD)
+    size_t snap = SNAP ? (size_t)4 * (2 * a.envV + 32) : 0;
+    if (DEEP) {
+        snap = (snap + 15) & ~(size_t)15;
+        a.nl2 = p->L - 1;
+        a.park_off = (uint32_t)snap;
+    }
 #define LAUNCH(FF, HH, TT)                                                                               \
     do {                                                                                                 \
         const int64_t cap = 256 * FwdCfg<FF, HH>::WPS;                                                   \
         const unsigned grid = (unsigned)(need < cap ? need : cap);                                       \
-        const_cast<FwdArgs&>(args).wg_sync = (B % ((int64_t)grid * 4) == 0) ? 1 : 0;                     \
-        if constexpr (fwd_mode_snap(MODE) && FF != 72) {                                                   \
-            ppo_set_error("compact rollouts need the built-in env's F = 72"); return PPO_ERR_UNSUPPORTED;    \
-        } else {                                                                                             \
-            const size_t dlds = fwd_mode_snap(MODE) ? (size_t)4 * (2 * args.envV + 32) : 0;   /* one snapshot slot per wave */ \
-            hipLaunchKernelGGL((k_policy_fwd<FF, HH, MODE, TT>), dim3(grid), dim3(256), dlds, ppo_stream(), args); \
-        }                                                                                                    \
+        a.wg_sync = (!DEEP && B % ((int64_t)grid * 4) == 0) ? 1 : 0;                                     \
+        if constexpr (SNAP && FF != 72) {                                                                \
+            ppo_set_error("compact rollouts need the built-in env's F = 72"); return PPO_ERR_UNSUPPORTED; \
+        } else {                                                                                         \
+            const size_t dlds = snap + (DEEP ? (size_t)4 * (HH / 32) * 4096 : 0);                        \
+            if constexpr (DEEP) {                                                                        \
+                static thread_local size_t attr_lds = 0;                                                 \
+                if (dlds > attr_lds) {                                                                   \
+                    HIP_TRY(hipFuncSetAttribute((const void*)k_policy_fwd<FF, HH, MODE, TT, DEEP>,       \
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)dlds)); \
+                    attr_lds = dlds;                                                                     \
+                }                                                                                        \
+            }                                                                                            \
+            hipLaunchKernelGGL((k_policy_fwd<FF, HH, MODE, TT, DEEP>), dim3(grid), dim3(256), dlds, ppo_stream(), a); \
+        }                                                                                                \
     } while (0)
     if (p->F == 72 && p->HID == 256 && tps == 1) LAUNCH(72, 256, 1);
     else if (p->F == 72 && p->HID == 256 && tps == 4) LAUNCH(72, 256, 4);
@@ -623,6 +586,12 @@ static void fill_weights(ppo_policy_s* p, FwdArgs& a) {
     a.b2p = (const float4*)p->b2p.p; a.w3p = (const float4*)p->w3p.p; a.b3 = p->b3.p;
 }
 
+// what the rollout tails take from the env: the Philox counter words and key, and where the step's outputs and flags go
+static void fill_rollout(ppo_env_s* e, FwdArgs& a, int32_t* actions_out, float* psel_out, float* full_probs_or_null, int32_t* err) {
+    a.tick = e->tick.p; a.global_offset = e->global_offset; a.k0 = (uint32_t)e->seed; a.k1 = (uint32_t)(e->seed >> 32);
+    a.actions_out = actions_out; a.psel_out = psel_out; a.full_probs = full_probs_or_null; a.err = err;
+}
+
 int32_t launch_policy_probs(ppo_policy_s* p, const int8_t* states_dev, const uint32_t* active_dev, int64_t B,
                             int32_t H, float* probs_dev) {
     if (B <= 0) return PPO_OK;
@@ -630,8 +599,8 @@ int32_t launch_policy_probs(ppo_policy_s* p, const int8_t* states_dev, const uin
     fill_weights(p, a);
     a.states = states_dev; a.active = active_dev; a.B = B; a.probs_out = probs_dev;
     ProfScope ps("k_policy_fwd_probs");
-    if (p->dtype == PPO_DTYPE_BF16) return launch_policy_fwd_bf16(p, a, 0, B, H / 32);
-    return dispatch_fwd<0>(p, a, B, H / 32);
+    if (p->dtype == PPO_DTYPE_BF16) return launch_policy_fwd_bf16(p, a, FwdMode::Probs, B, H / 32);
+    return dispatch_fwd<FwdMode::Probs>(p, a, B, H / 32);
 }
 
 int32_t launch_policy_rollout(ppo_policy_s* p, ppo_env_s* e, const int8_t* states_dev, const uint32_t* active_dev,
@@ -639,18 +608,17 @@ int32_t launch_policy_rollout(ppo_policy_s* p, ppo_env_s* e, const int8_t* state
     FwdArgs a = {};
     fill_weights(p, a);
     a.states = states_dev; a.active = active_dev; a.B = e->N;
-    a.tick = e->tick.p; a.global_offset = e->global_offset; a.k0 = (uint32_t)e->seed; a.k1 = (uint32_t)(e->seed >> 32);
-    a.actions_out = actions_out; a.psel_out = psel_out; a.full_probs = full_probs_or_null; a.err = e->err.p;
+    fill_rollout(e, a, actions_out, psel_out, full_probs_or_null, e->err.p);
     ProfScope ps("k_policy_fwd_rollout");
-    if (p->dtype == PPO_DTYPE_BF16) return launch_policy_fwd_bf16(p, a, 1, e->N, e->H / 32);
+    if (p->dtype == PPO_DTYPE_BF16) return launch_policy_fwd_bf16(p, a, FwdMode::Sample, e->N, e->H / 32);
     if (e->N <= ppo_knobs().rollout_split_max_envs) {   // few envs: 2 or 4 waves per env, same bits
         const int32_t rs = launch_rollout_split(p, a, e->N, e->H / 32, e->V, 0);
         if (rs != PPO_ERR_UNSUPPORTED) return rs;
     }
-    return dispatch_fwd<1>(p, a, e->N, e->H / 32);
+    return dispatch_fwd<FwdMode::Sample>(p, a, e->N, e->H / 32);
 }
 
-// One teacher-forced step (MODE 11): actions_io[n] holds env n's given 0-based action (< 0: the env idles) and keeps it;
+// One teacher-forced step (FwdMode::Forced): actions_io[n] holds env n's given 0-based action (< 0: the env idles) and keeps it;
 // psel_out[n] = the policy's probability of it (0 for an idle env or an action on an inactive quad, the latter also setting
 // bit 64 of *err, a word of the caller's).  The per-step launch only: no split-rollout form, no persistent form, no bf16 mode
 int32_t launch_policy_forced(ppo_policy_s* p, ppo_env_s* e, const int8_t* states_dev, const uint32_t* active_dev,
@@ -662,16 +630,17 @@ int32_t launch_policy_forced(ppo_policy_s* p, ppo_env_s* e, const int8_t* states
     FwdArgs a = {};
     fill_weights(p, a);
     a.states = states_dev; a.active = active_dev; a.B = e->N;
-    a.actions = actions_io; a.actions_out = actions_io; a.psel_out = psel_out; a.full_probs = full_probs_or_null; a.err = err;
+    fill_rollout(e, a, actions_io, psel_out, full_probs_or_null, err);     // (the tick and the key go unread: nothing is sampled)
+    a.actions = actions_io;
     ProfScope ps("k_policy_fwd_forced");
-    return dispatch_fwd<11>(p, a, e->N, e->H / 32);
+    return dispatch_fwd<FwdMode::Forced>(p, a, e->N, e->H / 32);
 }
 
 // One rollout step under the policy's selection, for the callers that APPLY a policy (play_quotas): the default
-// ("sample", 1) is launch_policy_rollout itself, with its split and bf16 branches; any other selection launches MODE 14
-// (tempered sampling) or MODE 15 (greedy) through the per-step dispatch only: no split-rollout form, no persistent form, no bf16.
-// Rule "sample" with a non-default truncation launches MODE 16 instead, at any temperature, 1 included; greedy
-// plays the arg-max, which every truncation keeps, and stays MODE 15
+// ("sample", 1) is launch_policy_rollout itself, with its split and bf16 branches; any other selection launches FwdMode::Tempered
+// or Greedy through the per-step dispatch only: no split-rollout form, no persistent form, no bf16.
+// Rule "sample" with a non-default truncation launches Truncated instead, at any temperature, 1 included; greedy
+// plays the arg-max, which every truncation keeps, and stays Greedy
 int32_t launch_policy_select(ppo_policy_s* p, ppo_env_s* e, const int8_t* states_dev, const uint32_t* active_dev,
                              int32_t* actions_out, float* psel_out, float* full_probs_or_null) {
     const bool truncated = !default_truncation(p) && p->select_rule == PPO_SELECT_SAMPLE;
@@ -689,24 +658,23 @@ int32_t launch_policy_select(ppo_policy_s* p, ppo_env_s* e, const int8_t* states
     FwdArgs a = {};
     fill_weights(p, a);
     a.states = states_dev; a.active = active_dev; a.B = e->N;
-    a.tick = e->tick.p; a.global_offset = e->global_offset; a.k0 = (uint32_t)e->seed; a.k1 = (uint32_t)(e->seed >> 32);
-    a.actions_out = actions_out; a.psel_out = psel_out; a.full_probs = full_probs_or_null; a.err = e->err.p;
-    a.inv_B = (float)(1.0 / p->select_temperature);
+    fill_rollout(e, a, actions_out, psel_out, full_probs_or_null, e->err.p);
+    a.inv_temperature = (float)(1.0 / p->select_temperature);
     if (p->select_rule == PPO_SELECT_GREEDY) {
         ProfScope ps("k_policy_fwd_greedy");
-        return dispatch_fwd<15>(p, a, e->N, e->H / 32);
+        return dispatch_fwd<FwdMode::Greedy>(p, a, e->N, e->H / 32);
     }
     if (truncated) {
-        a.eps = (double)p->trunc_top_k;
-        a.c_over_B = (float)p->trunc_top_p;
+        a.top_k = (double)p->trunc_top_k;
+        a.top_p = (float)p->trunc_top_p;
         ProfScope ps("k_policy_fwd_truncated");
-        return dispatch_fwd<16>(p, a, e->N, e->H / 32);
+        return dispatch_fwd<FwdMode::Truncated>(p, a, e->N, e->H / 32);
     }
     ProfScope ps("k_policy_fwd_tempered");
-    return dispatch_fwd<14>(p, a, e->N, e->H / 32);
+    return dispatch_fwd<FwdMode::Tempered>(p, a, e->N, e->H / 32);
 }
 
-// Persistent rollout (MODE 3): T steps of all N envs in one launch.  Returns PPO_ERR_UNSUPPORTED (without setting an
+// Persistent rollout (FwdMode::Persistent): T steps of all N envs in one launch.  Returns PPO_ERR_UNSUPPORTED (without setting an
 // error) when the shape is not covered, so the caller falls back to the per-step launches.
 // t0: first row of the rollout columns this launch writes (streaming collects a long rollout as a chain of launches)
 int32_t launch_policy_rollout_persistent(ppo_policy_s* p, ppo_env_s* e, ppo_rollouts_s* ro, int64_t T, int record_probs,
@@ -746,11 +714,11 @@ int32_t launch_policy_rollout_persistent(ppo_policy_s* p, ppo_env_s* e, ppo_roll
     do {                                                                                                     \
         static thread_local size_t attr_lds = 0;                                                                          \
         if (lds > attr_lds) {                                                                                \
-            HIP_TRY(hipFuncSetAttribute((const void*)k_policy_fwd<72, HH, 3, TT>,                            \
+            HIP_TRY(hipFuncSetAttribute((const void*)k_policy_fwd<72, HH, FwdMode::Persistent, TT>,                            \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));              \
             attr_lds = lds;                                                                                  \
         }                                                                                                    \
-        hipLaunchKernelGGL((k_policy_fwd<72, HH, 3, TT>), dim3(grid), dim3(256), lds, ppo_stream(), a);      \
+        hipLaunchKernelGGL((k_policy_fwd<72, HH, FwdMode::Persistent, TT>), dim3(grid), dim3(256), lds, ppo_stream(), a);      \
     } while (0)
     if (p->HID == 256 && tps == 1) LAUNCH3(256, 1);
     else if (p->HID == 256 && tps == 4) LAUNCH3(256, 4);
@@ -760,6 +728,17 @@ int32_t launch_policy_rollout_persistent(ppo_policy_s* p, ppo_env_s* e, ppo_roll
 #undef LAUNCH3
     HIP_TRY(hipGetLastError());
     return PPO_OK;
+}
+
+// a mode known at run time -> its instantiation (the modes that have a caller here)
+static int32_t dispatch_fwd_mode(FwdMode mode, ppo_policy_s* p, const FwdArgs& a, int64_t B, int tps) {
+    switch (mode) {
+#define MODE_CASE(M) case FwdMode::M: return dispatch_fwd<FwdMode::M>(p, a, B, tps)
+    MODE_CASE(TrainSnap); MODE_CASE(Train); MODE_CASE(Imitate); MODE_CASE(ImitateSnap); MODE_CASE(ValuePredict);
+    MODE_CASE(ValuePredictSnap); MODE_CASE(ValueTrainClip); MODE_CASE(ValueTrainClipSnap); MODE_CASE(ValueTrain); MODE_CASE(ValueTrainSnap);
+#undef MODE_CASE
+    default: ppo_set_error("k_policy_fwd: not a mode chosen at run time"); return PPO_ERR_ARG;
+    }
 }
 
 // what both train forwards take from the workspace: the minibatch through idx, the saved activations, dL/dy and the loss terms
@@ -785,15 +764,16 @@ int32_t launch_policy_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32
     a.actions = ro->actions.p; a.p_old = ro->p_sel.p; a.adv = adv_col; a.ratio_out = p->ratio_out;
     a.eps = eps; a.c_over_B = (float)(entropy_weight / (double)B_global);
     ProfScope ps("k_policy_fwd_train");
-    switch (form) {         // compact: MODE 4 / the CS form of the split kernel
+    const FwdMode mode = fwd_train_mode(Objective::Policy, ro->compact);
+    switch (form) {         // compact: TrainSnap / the CS form of the split kernel
     case TrainFwd::Split: return launch_policy_train_fwd_split(p, a, B, ro->compact);     // ppo_policy_fwd_split.hip
-    case TrainFwd::Bf16: return launch_policy_fwd_bf16(p, a, ro->compact ? 4 : 2, B, ro->H / 32);
-    case TrainFwd::Fwd: return ro->compact ? dispatch_fwd<4>(p, a, B, ro->H / 32) : dispatch_fwd<2>(p, a, B, ro->H / 32);
+    case TrainFwd::Bf16: return launch_policy_fwd_bf16(p, a, mode, B, ro->H / 32);
+    case TrainFwd::Fwd: return dispatch_fwd_mode(mode, p, a, B, ro->H / 32);
     default: return launch_policy_train_fwd_x6(p, a, B, form, ro->compact);               // ppo_policy_fwd_x6.hip
     }
 }
 
-// imitation train forward (modes 12 / 13): the policy's train forward with the cross-entropy of the buffer's actions as the loss;
+// imitation train forward (FwdMode::Imitate / ImitateSnap): the policy's train forward with the cross-entropy of the buffer's actions as the loss;
 // weight_col: the weights' column by transition id, clamped at 0 in the tail (nullptr: uniform weights).  Only this fp32-MFMA
 // forward has the mode
 int32_t launch_imitate_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
@@ -803,10 +783,10 @@ int32_t launch_imitate_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int3
     a.actions = ro->actions.p; a.adv = weight_col;
     a.c_over_B = (float)(entropy_weight / (double)B_global);
     ProfScope ps("k_policy_fwd_imitate");
-    return !ro->compact ? dispatch_fwd<12>(p, a, B, ro->H / 32) : dispatch_fwd<13>(p, a, B, ro->H / 32);
+    return dispatch_fwd_mode(fwd_train_mode(Objective::Imitate, ro->compact), p, a, B, ro->H / 32);
 }
 
-// ---- critic (value modes 5 .. 8): only this fp32-MFMA forward has them
+// ---- critic (the Value* modes): only this fp32-MFMA forward has them
 // values_dev[b] = V(state b) for B states in storage order: observation rows [B][H][F] (cstate_dev == nullptr), or env
 // snapshots [B][2V] with the buffer's template (compact rollouts; F = 72)
 int32_t launch_value_predict(ppo_policy_s* p, const int8_t* states_dev, const int8_t* cstate_dev, const uint32_t* active_dev,
@@ -816,9 +796,9 @@ int32_t launch_value_predict(ppo_policy_s* p, const int8_t* states_dev, const in
     fill_weights(p, a);
     a.states = states_dev; a.active = active_dev; a.B = B; a.values_out = values_dev;
     ProfScope ps("k_value_fwd_predict");
-    if (!cstate_dev) return dispatch_fwd<5>(p, a, B, H / 32);
+    if (!cstate_dev) return dispatch_fwd_mode(FwdMode::ValuePredict, p, a, B, H / 32);
     a.states = nullptr; a.cstate = cstate_dev; a.env_tmpl = tmpl_dev; a.envV = V; a.envQ = V / 4; a.env_slots = 1;
-    return dispatch_fwd<7>(p, a, B, H / 32);
+    return dispatch_fwd_mode(FwdMode::ValuePredictSnap, p, a, B, H / 32);
 }
 
 // value-train forward of a minibatch: saves the activations like the policy's train forward, leaves dL/dy of
@@ -831,8 +811,7 @@ int32_t launch_value_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_
     a.vtarget = target_col;
     a.vold = vold_col; a.vclip = vclip; a.vdelta_out = vold_col ? vdelta_dst : nullptr;
     ProfScope ps("k_value_fwd_train");
-    if (vold_col) return !ro->compact ? dispatch_fwd<9>(p, a, B, ro->H / 32) : dispatch_fwd<10>(p, a, B, ro->H / 32);
-    return !ro->compact ? dispatch_fwd<6>(p, a, B, ro->H / 32) : dispatch_fwd<8>(p, a, B, ro->H / 32);
+    return dispatch_fwd_mode(fwd_train_mode(Objective::Value, ro->compact, vold_col != nullptr), p, a, B, ro->H / 32);
 }
 
 int32_t launch_categorical(const float* probs, const float* u, int64_t B, int64_t A, int32_t* actions, float* psel,

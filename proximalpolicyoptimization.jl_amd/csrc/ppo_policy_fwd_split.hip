@@ -7,7 +7,7 @@
 // (fragment order, 4 KiB each), every wave takes all of them as B operands and computes ITS output tiles of layer 2
 // and its share of the layer-3 dot products; the four partial logits per row meet in LDS again and wave 0 of the group
 // runs the softmax / loss tail.  Saved activations, dY and the loss terms are the same buffers in the same layout as
-// k_policy_fwd's MODE 2, so both backward kernels follow unchanged.
+// k_policy_fwd's FwdMode::Train, so both backward kernels follow unchanged.
 // Numerics: identical operations except the order in which the layer-3 partial sums are added (S partial chains instead
 // of one): logits agree with k_policy_fwd to fp32 rounding, which is why only the TRAIN forward (tested against a float64
 // restatement with a tolerance) has this form and the bit-exact rollout kernels do not.
@@ -19,7 +19,7 @@ static __device__ __forceinline__ void act_store_nt4(float4* p, float4 v) {
     __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(p));
 }
 
-// CS: 1 = the states are env snapshots (compact rollouts): rows re-derived in LDS like k_policy_fwd MODE 4
+// CS: 1 = the states are env snapshots (compact rollouts): rows re-derived in LDS like k_policy_fwd's FwdMode::TrainSnap
 template <int F, int HID, int S, int CS>
 __global__ __launch_bounds__(256, 1) void k_policy_fwd_train_split(FwdArgs a) {
     constexpr int NT = HID / 32, NTS = NT / S, G = 4 / S;      // tiles per wave, state groups per workgroup
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256, 1) void k_policy_fwd_train_split(FwdArgs a) {
             l[0][1] = (p1 + __shfl_xor(p1, 32)) + a.b3[1];
             l[0][2] = (p2 + __shfl_xor(p2, 32)) + a.b3[2];
             l[0][3] = (p3 + __shfl_xor(p3, 32)) + a.b3[3];
-            policy_tail<2, 1, false>(a, state, sid, act, l, lane, j, h);
+            policy_tail<FwdTail::Train, 1, false>(a, state, sid, act, l, lane, j, h);
         }
     }
 }
@@ -220,7 +220,7 @@ static int32_t launch_split(FwdArgs& a, int64_t B) {
     return PPO_OK;
 }
 
-// `a` comes filled like MODE 2 / MODE 4 of k_policy_fwd; fp32 Policy(72, h, 2, 4), H = 32 (train_route)
+// `a` comes filled like FwdMode::Train / TrainSnap of k_policy_fwd; fp32 Policy(72, h, 2, 4), H = 32 (train_route)
 int32_t launch_policy_train_fwd_split(ppo_policy_s* p, FwdArgs& a, int64_t B, bool compact) {
     if (p->HID == 256) return compact ? launch_split<72, 256, 1>(a, B) : launch_split<72, 256, 0>(a, B);
     return compact ? launch_split<72, 128, 1>(a, B) : launch_split<72, 128, 0>(a, B);

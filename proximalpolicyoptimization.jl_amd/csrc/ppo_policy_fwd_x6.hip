@@ -234,7 +234,7 @@ __global__ __launch_bounds__(HID * 2, 4) void k_policy_fwd_train_x6(FwdArgs a, c
             l[0][1] = (s.y + __shfl_xor(s.y, 32)) + a.b3[1];
             l[0][2] = (s.z + __shfl_xor(s.z, 32)) + a.b3[2];
             l[0][3] = (s.w + __shfl_xor(s.w, 32)) + a.b3[3];
-            policy_tail<2, 1, false>(a, tile, sid_cur, act, l, (int)ln, j, h);
+            policy_tail<FwdTail::Train, 1, false>(a, tile, sid_cur, act, l, (int)ln, j, h);
         }
     }
 }
@@ -424,7 +424,7 @@ __global__ __launch_bounds__((FXTCfg<HID, T>::THREADS), (FXTCfg<HID, T>::WG_PER_
                 l[0][1] = (s.y + __shfl_xor(s.y, 32)) + b3_1;
                 l[0][2] = (s.z + __shfl_xor(s.z, 32)) + b3_2;
                 l[0][3] = (s.w + __shfl_xor(s.w, 32)) + b3_3;
-                policy_tail<2, 1, false>(a, tile, cid, tact, l, (int)ln, j, h, 0u, 0, &tpre);
+                policy_tail<FwdTail::Train, 1, false>(a, tile, cid, tact, l, (int)ln, j, h, 0u, 0, &tpre);
             }
             FXSTAMP(4);
             cid = nid;
@@ -625,7 +625,7 @@ __global__ __launch_bounds__((FXTCfg<HID, T>::THREADS), (FXTCfg<HID, T>::WG_PER_
                 l[0][1] = (s.y + __shfl_xor(s.y, 32)) + b3_1;
                 l[0][2] = (s.z + __shfl_xor(s.z, 32)) + b3_2;
                 l[0][3] = (s.w + __shfl_xor(s.w, 32)) + b3_3;
-                policy_tail<2, 1, false>(a, tile, sidw, tact, l, (int)ln, j, h, 0u, 0, &tpre);
+                policy_tail<FwdTail::Train, 1, false>(a, tile, sidw, tact, l, (int)ln, j, h, 0u, 0, &tpre);
             }
             FXSTAMP(7);
             ccid[0] = cnid[0]; ccid[1] = cnid[1];
@@ -869,7 +869,7 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_fwd_train_x6s(FwdArgs a, 
                 l[ts][2] = (s.z + __shfl_xor(s.z, 32)) + a.b3[2];
                 l[ts][3] = (s.w + __shfl_xor(s.w, 32)) + a.b3[3];
             }
-            policy_tail<2, TPS, false>(a, st8, sidw, act, l, (int)ln, j, h);
+            policy_tail<FwdTail::Train, TPS, false>(a, st8, sidw, act, l, (int)ln, j, h);
         }
     }
     }

@@ -1,7 +1,7 @@
 // ppo_policy_rollout_split.hip -- the one-launch rollout (collect_step_data! looped over T steps, src/collect_rollouts.jl:
-// 1-24; k_policy_fwd MODE 3) for FEW envs: S = 2 or 4 waves of a workgroup share an env.
+// 1-24; k_policy_fwd's FwdMode::Persistent) for FEW envs: S = 2 or 4 waves of a workgroup share an env.
 //
-// MODE 3 gives every env to one wave, so 512 envs use half of the chip's 1024 SIMDs and the reference's own regime (one
+// Persistent gives every env to one wave, so 512 envs use half of the chip's 1024 SIMDs and the reference's own regime (one
 // env, BASELINE config 1) a thousandth of it, 47 us of dependent MFMAs per step (HID = 256).  Here the matrix work of a
 // step is split over the S waves exactly as in k_policy_fwd_train_split -- wave s computes feature tiles [s NT/S, (s+1)
 // NT/S) of layer 1, the tiles meet in LDS, every wave computes its output tiles of layer 2 -- but the results stay BIT
@@ -13,7 +13,7 @@
 #include "ppo_policy_tail.h"
 #include "ppo_env_device.h"
 
-// ENV = 1: the persistent rollout (env state in LDS, T steps); ENV = 0: one step of the per-step form (k_policy_fwd MODE 1:
+// ENV = 1: the persistent rollout (env state in LDS, T steps); ENV = 0: one step of the per-step form (k_policy_fwd's FwdMode::Sample:
 // rows, active-quad word and tick come from global arrays, the env is stepped by k_env_step afterwards) -- what
 // collect_rollouts!(.., num_episodes, ..) and the evaluator run, usually on few envs
 template <int F, int HID, int S, int ENV>
@@ -200,14 +200,14 @@ __global__ __launch_bounds__(256, 1) void k_rollout_split(FwdArgs a) {
                 }
                 if (s < S - 1) __syncthreads();
             }
-            // ---- tail on the last wave of the group: exactly k_policy_fwd's epilogue + MODE 3's env update
+            // ---- tail on the last wave of the group: exactly k_policy_fwd's epilogue + the persistent rollout's env update
             if (live && sw == S - 1) {
                 float l[1][4];
                 l[0][0] = (p0 + __shfl_xor(p0, 32)) + a.b3[0];
                 l[0][1] = (p1 + __shfl_xor(p1, 32)) + a.b3[1];
                 l[0][2] = (p2 + __shfl_xor(p2, 32)) + a.b3[2];
                 l[0][3] = (p3 + __shfl_xor(p3, 32)) + a.b3[3];
-                const int sampled = policy_tail<(ENV ? 3 : 1), 1, false>(a, state, state, act, l, lane, j, h, tick_val, out_index);
+                const int sampled = policy_tail<(ENV ? FwdTail::SamplePersistent : FwdTail::Sample), 1, false>(a, state, state, act, l, lane, j, h, tick_val, out_index);
                 if (ENV) {
                 asm volatile("" ::: "memory");
                 float rew; uint8_t dn;

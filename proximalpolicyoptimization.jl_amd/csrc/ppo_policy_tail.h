@@ -12,32 +12,35 @@
 
 struct FwdArgs {
     // inputs
-    const int8_t* states;      // MODE 0/1: [B][H][F]; MODE 2: rollout states base (gathered by idx)
+    const int8_t* states;      // FwdSource::Rows: [B][H][F]; RowsIdx: rollout states base (gathered by idx)
     const uint32_t* active;    // same indexing as states
-    const int32_t* idx;        // MODE 2: transition id per tile
+    const int32_t* idx;        // RowsIdx / SnapIdx: transition id per state
     int64_t B;
     unsigned long long* stamps;   // diagnostic build only (-DPPO_FWD_STAMP)
     int wg_sync;               // 1: every wave of a workgroup runs the same number of tiles -> per-chunk barriers allowed
     const float4* w1p; const float4* w2p; const float4* b1p; const float4* b2p; const float4* w3p; const float* b3;
-    // MODE 0
+    // FwdTail::Probs
     float* probs_out;
-    // MODE 1
+    // the rollout tails (Sample .. Truncated, Forced)
     const uint32_t* tick; int64_t global_offset; uint32_t k0, k1;
     int32_t* actions_out; float* psel_out; float* full_probs; int32_t* err;
-    // MODE 2
+    // the train tails
     float4* act1; float4* act2; float4* dY; double* loss_terms;
     const int32_t* actions; const float* p_old; const float* adv;
-    double eps; float c_over_B; float inv_B;      // (MODE 14 / 15 / 16, which train nothing: inv_B = 1 / selection temperature;
-                                                  //  MODE 16: eps = top_k, an integer a double holds exactly, c_over_B = top_p)
-    // MODE 3 (persistent rollout: T steps of every env in ONE launch; env state lives in the wave's LDS slots)
+    // ... and, in the same storage, what the selection tails (which train nothing) read instead: Tempered / Greedy / Truncated
+    // the factor 1 / temperature, Truncated top_k (an integer a double holds exactly) and top_p
+    union { double eps; double top_k; };
+    union { float c_over_B; float top_p; };
+    union { float inv_B; float inv_temperature; };
+    // FwdSource::EnvSlots (persistent rollout: T steps of every env in ONE launch; env state lives in the wave's LDS slots)
     int64_t T;                                                   // steps
     int8_t* env_score; int8_t* env_degree; uint32_t* env_active; int32_t* env_steps; float* env_reward;
     uint8_t* env_done; uint32_t* env_episode; uint32_t* env_tick; const int8_t* env_tmpl;
     int32_t envQ, envV, env_max_actions, env_slots; float env_nar;
     int8_t* states_out; uint32_t* active_out; float* rew_out; uint8_t* done_out;      // rollout columns [T][N]
     // compact rollout storage: an env snapshot (score[V] then degree[V], int8) per transition instead of the expanded
-    // [H][F] observation.  MODE 3 writes cstate_out (states_out may then be null); MODE 4 = MODE 2 (train forward) reading
-    // cstate through idx, re-deriving the rows like MODE 3 and leaving them in xs_out (minibatch order) for the backward
+    // [H][F] observation.  The persistent rollout writes cstate_out (states_out may then be null); Snap / SnapIdx read cstate,
+    // re-deriving the rows like the persistent rollout, SnapIdx leaving them in xs_out (minibatch order) for the backward
     int8_t* cstate_out; const int8_t* cstate; int8_t* xs_out;
     // deep form (num_hidden_layers != 2, k_policy_fwd<.., DEEP = 1>): nl2 = hidden->hidden layers (L - 1: 0, 2 or 3), w2p /
     // b2p hold them back to back; act_mid[l] = saved output of hidden->hidden layer l < nl2 - 1 (the last one goes to act2,
@@ -48,7 +51,7 @@ struct FwdArgs {
     // critic (k_policy_fwd value modes, value_tail): state values out, indexed like the states (predict); regression target per
     // transition id (train).  Appended last: the offsets of every field above are what the other kernels were built with
     float* values_out; const float* vtarget;
-    // MODE 2, optional: ratio_out[state] = p_new(a|s) / p_old(a|s) of every state of the minibatch, the quotient the
+    // FwdTail::Train, optional: ratio_out[state] = p_new(a|s) / p_old(a|s) of every state of the minibatch, the quotient the
     // surrogate forms (per-epoch KL / clip-fraction statistics, ppo_stats.hip).  Appended last, like the two above
     float* ratio_out;
     // value-train, optional (PPO's clipped value loss, value_tail): vold = the values the critic had before the update,
@@ -56,6 +59,8 @@ struct FwdArgs {
     // every state of the minibatch (per-epoch value-clip statistics, ppo_stats.hip; nullptr: not stored).  Appended last
     const float* vold; float vclip; float* vdelta_out;
 };
+// the aliases move nothing: these are the layout every kernel was built with
+static_assert(sizeof(FwdArgs) == 512 && offsetof(FwdArgs, vdelta_out) == 504, "FwdArgs layout");
 
 // value of lane (lane ^ OFF), OFF < 32.  Same lane mapping as __shfl_xor (which hipcc lowers to ds_bpermute_b32: an
 // LDS round trip of ~100+ cycles per step, fully exposed in the one-or-two-waves-per-SIMD kernels here), but as DPP
@@ -98,34 +103,48 @@ __device__ __forceinline__ float dy_round(float x) {
     return (float)(__bf16)x;
 }
 
-// MODE 2 inputs of one transition, when the caller fetched them ahead of its own stores (vmcnt counts loads and stores
+// FwdTail::Train inputs of one transition, when the caller fetched them ahead of its own stores (vmcnt counts loads and stores
 // in one in-order queue on gfx9: a load issued behind a store cannot be waited for without waiting for the store)
 struct TailPre { int ab; float po; float adv; };
 
+// the entropy term of ppo_loss_with_entropy on the smoothed probabilities sp = p + smooth / A (src/train.jl:22):
+// lg = log(sp) per entry; returns sum(sp * lg) over the state
+template <int TPS>
+__device__ __forceinline__ float smoothed_entropy(const float (&p)[TPS][4], float (&lg)[TPS][4]) {
+    const float sA = 1e-8f / (float)(128 * TPS);
+    float hl = 0.0f;
+#pragma unroll
+    for (int ts = 0; ts < TPS; ++ts)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { const float sp = p[ts][i] + sA; lg[ts][i] = logf(sp); hl += sp * lg[ts][i]; }
+    return wave32_sum(hl);
+}
+
 // l[ts][i]: logit of action 128*ts + 4*j + i of the state, present in both lane halves (j = lane & 31).
-// MODE 2 also serves the train forward from compact states (kernel MODE 4).
-// MODE 1 / 3 (rollout): tick_val = the env's tick (Philox counter word), out_index = position of the transition in
+// Sample / SamplePersistent (rollout): tick_val = the env's tick (Philox counter word), out_index = position of the transition in
 // the output columns (state for one step, t*N + state for the persistent rollout); returns the sampled action.
-// MODE 11 (teacher-forced step): the MODE 1 outputs for the action in pre->ab instead of a sampled one; returns it.
-// MODE 12 (imitation train forward, kernel MODES 12 / 13): MODE 2's outputs for the cross-entropy of the action in pre->ab,
-// weighted by max(pre->adv, 0); pre is required.
-// MODE 14 / 15 (selection rules): MODE 1 on the logits times a.inv_B (= 1 / temperature); 14 samples like MODE 1,
-// 15 takes the first maximum of p instead (tick_val unused).  l is scaled in place.
-// MODE 16 (truncated sampling): MODE 14 on the top-k / nucleus truncation of the tempered p, renormalised;
-// a.eps = top_k (0: all), a.c_over_B = top_p (1: all).
-// dy_copy (MODE 2, TPS == 1, optional): a second destination for the state's 32 dL/dlogits rows, e.g. an LDS tile of the
+// Forced (teacher-forced step): Sample's outputs for the action in pre->ab instead of a sampled one; returns it.
+// Train: the loss and dL/dlogits of ppo_loss_with_entropy, whatever the source of the state.
+// Imitate: Train's outputs for the cross-entropy of the action in pre->ab, weighted by max(pre->adv, 0); pre is required.
+// Tempered / Greedy (selection rules): Sample on the logits times a.inv_temperature; Tempered samples like Sample,
+// Greedy takes the first maximum of p instead (tick_val unused).  l is scaled in place.
+// Truncated: Tempered on the top-k / nucleus truncation of the tempered p, renormalised; a.top_k (0: all),
+// a.top_p (1: all).
+// dy_copy (Train, TPS == 1, optional): a second destination for the state's 32 dL/dlogits rows, e.g. an LDS tile of the
 // calling workgroup (k_policy_train_tile keeps the whole training pass of a tile on the CU).
-template <int MODE, int TPS, bool DYBF16>
+// (The pick of entry ab and the probs_out store are written out at each site: as helpers they compile to other code.)
+template <FwdTail TAIL, int TPS, bool DYBF16>
 __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state, const int64_t sid, const uint32_t act,
                                            float (&l)[TPS][4], const int lane, const int j, const int h,
                                            const uint32_t tick_val = 0u, const int64_t out_index = 0,
                                            const TailPre* pre = nullptr, float4* dy_copy = nullptr) {
+    static_assert(!tail_value(TAIL), "the critic's tails are value_tail's");
     int sampled = 0;
     constexpr int A = 128 * TPS;
-    if (MODE == 14 || MODE == 15 || MODE == 16) {
+    if (tail_tempers(TAIL)) {
         // selection temperature: l' = l * (float)(1 / temperature), one fp32 multiply per logit in front of the
-        // masked max (a.inv_B carries the factor: the rollout modes have no other use for that field)
-        const float inv = a.inv_B;
+        // masked max
+        const float inv = a.inv_temperature;
 #pragma unroll
         for (int ts = 0; ts < TPS; ++ts)
 #pragma unroll
@@ -155,7 +174,7 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
 #pragma unroll
         for (int i = 0; i < 4; ++i) p[ts][i] = p[ts][i] / ssum;
 
-    if (MODE == 16) {
+    if (TAIL == FwdTail::Truncated) {
         // top-k / nucleus truncation.  b precedes a iff p[b] > p[a] || (p[b] == p[a] && b < a); rank(a) counts the b
         // that precede a, mass(a) adds their p[b] in ascending b (fp32, one rounding per add).  One pass over b = 0 .. A - 1 in
         // ascending order serves every a: p[b] is broadcast by readlane like the walk below broadcasts it, and each lane updates
@@ -163,9 +182,9 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
         // rolled loop (v_readlane takes its lane from an SGPR): 32 bodies' worth less code than the full unroll, same order.
         // "b < a" for a = 128 ts + 4 j + i needs no index compare: ts != tb decides it at compile time, ts == tb leaves
         // j > jb, or j >= jb where ib < i.  A state without an active quad has p NaN everywhere: no comparison holds, rank and
-        // mass stay 0, everything is kept and NaN stays NaN -- what MODE 14 leaves for such a state.
-        const int top_k = (int)a.eps;
-        const float top_p = a.c_over_B;
+        // mass stay 0, everything is kept and NaN stays NaN -- what Tempered leaves for such a state.
+        const int top_k = (int)a.top_k;
+        const float top_p = a.top_p;
         int rk[TPS][4];
         float ms[TPS][4];
 #pragma unroll
@@ -218,7 +237,7 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
             for (int i = 0; i < 4; ++i) p[ts][i] = p[ts][i] / ksum;
     }
 
-    if (MODE == 0) {
+    if (TAIL == FwdTail::Probs) {
         if (h == 0) {
 #pragma unroll
             for (int ts = 0; ts < TPS; ++ts)
@@ -226,9 +245,9 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
                     make_float4(p[ts][0], p[ts][1], p[ts][2], p[ts][3]);
         }
     }
-    if (MODE == 1 || MODE == 3 || MODE == 14 || MODE == 16) {
-        // rand(Categorical(p)): sequential fp32 inverse-CDF walk, same uniform as the oracle (MODE 14: over the tempered p;
-        // MODE 16: over its renormalised truncation)
+    if (tail_samples(TAIL)) {
+        // rand(Categorical(p)): sequential fp32 inverse-CDF walk, same uniform as the oracle (Tempered: over the tempered p;
+        // Truncated: over its renormalised truncation)
         uint32_t rnd[4];
         philox4x32_10((uint32_t)(a.global_offset + state), tick_val, 0u, 0u, a.k0, a.k1, rnd);
         const float u = u01_from_u32(rnd[0]);
@@ -277,14 +296,8 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
             a.psel_out[out_index] = psel;
         }
         sampled = ia;
-        if (a.full_probs && h == 0) {
-#pragma unroll
-            for (int ts = 0; ts < TPS; ++ts)
-                reinterpret_cast<float4*>(a.full_probs)[((size_t)out_index * TPS + ts) * 32 + j] =
-                    make_float4(p[ts][0], p[ts][1], p[ts][2], p[ts][3]);
-        }
     }
-    if (MODE == 15) {
+    if (TAIL == FwdTail::Greedy) {
         // greedy: the lowest action index among those with the largest p, Julia's argmax.  No Philox call, no walk.
         // Per lane the first maximum in index order (tile, then i: strictly greater replaces), then a butterfly over the 32 lanes
         // of a half on the pair (p, index) in which equal p keeps the lower index -- both halves hold the same p, so every lane
@@ -317,14 +330,8 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
             a.psel_out[out_index] = psel;
         }
         sampled = bi;
-        if (a.full_probs && h == 0) {
-#pragma unroll
-            for (int ts = 0; ts < TPS; ++ts)
-                reinterpret_cast<float4*>(a.full_probs)[((size_t)out_index * TPS + ts) * 32 + j] =
-                    make_float4(p[ts][0], p[ts][1], p[ts][2], p[ts][3]);
-        }
     }
-    if (MODE == 11) {
+    if (TAIL == FwdTail::Forced) {
         // teacher-forced: the action is given -- pre->ab, the caller's early fetch of a.actions[out_index], 0-based,
         // wave-uniform -- and p[action] is picked like the training tail picks p[ab]: no Philox call, no walk.  ab < 0 (an idle
         // env): probability 0.  An action on an inactive quad: the mask left it exactly 0; it is written as 0 and reported
@@ -345,16 +352,16 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
             a.psel_out[out_index] = psel;
         }
         sampled = ab;
-        if (a.full_probs && h == 0) {
-#pragma unroll
-            for (int ts = 0; ts < TPS; ++ts)
-                reinterpret_cast<float4*>(a.full_probs)[((size_t)out_index * TPS + ts) * 32 + j] =
-                    make_float4(p[ts][0], p[ts][1], p[ts][2], p[ts][3]);
-        }
     }
-    if (MODE == 12) {
-        // behaviour cloning (kernel MODES 12 / 13): cross-entropy of the stored action, -w log pi(a|s), with MODE 2's
-        // entropy term.  pre: the caller's early fetch -- ab the 0-based action (on an active quad, MODE 2's precondition), adv
+    if (tail_steps(TAIL) && a.full_probs && h == 0) {        // every rollout step: the whole distribution, on request
+#pragma unroll
+        for (int ts = 0; ts < TPS; ++ts)
+            reinterpret_cast<float4*>(a.full_probs)[((size_t)out_index * TPS + ts) * 32 + j] =
+                make_float4(p[ts][0], p[ts][1], p[ts][2], p[ts][3]);
+    }
+    if (TAIL == FwdTail::Imitate) {
+        // behaviour cloning: cross-entropy of the stored action, -w log pi(a|s), with Train's
+        // entropy term.  pre: the caller's early fetch -- ab the 0-based action (on an active quad, Train's precondition), adv
         // the weight column's entry (1 for uniform weights); w = max(adv, 0).  log pi in the log-softmax form (l[a] - m) - log S
         // and dL/dlogit_k = (w / B_global)(p_k - [k == a]) without a division by p[a]: both stay finite where exp(l[a] - m)
         // underflows to 0, the searched action the current policy finds very unlikely.  No p_old, no clip, no ratio
@@ -367,13 +374,8 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
             for (int i = 0; i < 4; ++i) cand = ((ab >> 7) == ts && (ab & 3) == i) ? l[ts][i] : cand;
         const float la = __shfl(cand, (ab & 127) >> 2);
         const float logp = (la - m) - logf(ssum);
-        const float sA = 1e-8f / (float)A;                                   // smooth/size(probs,1)  src/train.jl:22
-        float lg[TPS][4], hl = 0.0f;
-#pragma unroll
-        for (int ts = 0; ts < TPS; ++ts)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { const float sp = p[ts][i] + sA; lg[ts][i] = logf(sp); hl += sp * lg[ts][i]; }
-        hl = wave32_sum(hl);
+        float lg[TPS][4];
+        const float hl = smoothed_entropy(p, lg);
         float dpe[TPS][4], dot = 0.0f;
 #pragma unroll
         for (int ts = 0; ts < TPS; ++ts)
@@ -395,7 +397,7 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
         }
         if (lane == 0) { a.loss_terms[state * 2] = (double)(w * logp); a.loss_terms[state * 2 + 1] = (double)(-hl); }
     }
-    if (MODE == 2) {
+    if (TAIL == FwdTail::Train) {
         const int ab = pre ? pre->ab : a.actions[sid];
         const float po = pre ? pre->po : a.p_old[sid];
         const float adv = pre ? pre->adv : a.adv[sid];
@@ -409,13 +411,8 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
         const double clip = adv >= 0.0f ? (1.0 + a.eps) * (double)adv : (1.0 - a.eps) * (double)adv;   // :1-7
         const bool unclipped = (double)gain < clip;
         const double minval = unclipped ? (double)gain : clip;
-        const float sA = 1e-8f / (float)A;                                   // smooth/size(probs,1)  :22
-        float lg[TPS][4], hl = 0.0f;
-#pragma unroll
-        for (int ts = 0; ts < TPS; ++ts)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { const float sp = p[ts][i] + sA; lg[ts][i] = logf(sp); hl += sp * lg[ts][i]; }
-        hl = wave32_sum(hl);
+        float lg[TPS][4];
+        const float hl = smoothed_entropy(p, lg);
         float dp[TPS][4], dot = 0.0f;
         const float dsel = unclipped ? -(a.inv_B * adv / po) : 0.0f;
 #pragma unroll
@@ -446,21 +443,23 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
 
 // ---- critic: the same MLP read as a state value.  V(s) = mean of the 4 outputs of every half-edge row of an ACTIVE quad
 // (the rows policy_tail's mask keeps), 0 for a state without one; loss = Flux.mse(V, target) over the global minibatch.
-// VMODE 0 (predict): values_out[out_index] = V.
-// VMODE 1 (train):   dY = dL/dy = 2 (V - target) / (B_global * n) on the n = 16 * active-quads outputs of active rows, exactly
+// ValuePredict:     values_out[out_index] = V.
+// ValueTrain:       dY = dL/dy = 2 (V - target) / (B_global * n) on the n = 16 * active-quads outputs of active rows, exactly
 //                    0.0f on the others; loss_terms[state] = (-(V - target)^2, 0) -- the slab reduction's -(sum)/B_global
 //                    then leaves the mse where the policy's ppo loss goes.  target: the caller's early fetch (TailPre rule).
-// VMODE 2 (train, clipped; k_policy_fwd modes 9 / 10, chosen by the host while a value clip is set): the loss is PPO's clipped value loss
+// ValueTrainClip (chosen by the host while a value clip is set): the loss is PPO's clipped value loss
 //                    max((V - t)^2, (Vclip - t)^2), Vclip = vold + clamp(V - vold, -c, c), c = a.vclip, vold = the caller's
 //                    early fetch of a.vold[transition]: whether V left the range is decided on delta = V - vold itself
 //                    (vold + clamp(delta) need not reproduce V in fp32), a tie of the two squares keeps the unclipped one,
 //                    and a state whose clipped square is the larger one has dY exactly 0.0f on every row.  c = +inf: every
 //                    state is inside, the plain mse bit for bit.  a.vdelta_out (optional): delta per state of the minibatch.
 // A handful of adds, one division and the DPP butterfly: no exp / log, so the tail is short serial time for the workgroup.
-template <int VMODE, int TPS>
+template <FwdTail TAIL, int TPS>
 __device__ __forceinline__ void value_tail(const FwdArgs& a, const int64_t state, const uint32_t act, const float (&l)[TPS][4],
                                            const int lane, const int j, const int h, const int64_t out_index, const float target,
                                            const float vold = 0.0f) {
+    static_assert(tail_value(TAIL), "the policy's tails are policy_tail's");
+    constexpr bool CLIP = TAIL == FwdTail::ValueTrainClip;
     bool on[TPS];
     float s = 0.0f;
 #pragma unroll
@@ -474,13 +473,13 @@ __device__ __forceinline__ void value_tail(const FwdArgs& a, const int64_t state
     const int nq = __builtin_popcount(quads);              // wave-uniform
     const float n = (float)(16 * nq);                      // 4 rows per quad x 4 outputs per row
     const float v = nq ? s / n : 0.0f;
-    if (VMODE == 0) {
+    if (TAIL == FwdTail::ValuePredict) {
         if (lane == 0) a.values_out[out_index] = v;
     } else {
         const float d = v - target;
         float term = d, delta = 0.0f;
         bool keep = true;
-        if (VMODE == 2) {
+        if (CLIP) {
             const float c = a.vclip;
             delta = v - vold;
             const bool inside = fabsf(delta) <= c;
@@ -499,7 +498,7 @@ __device__ __forceinline__ void value_tail(const FwdArgs& a, const int64_t state
         }
         if (lane == 0) {
             a.loss_terms[state * 2] = -((double)term * (double)term); a.loss_terms[state * 2 + 1] = 0.0;
-            if (VMODE == 2 && a.vdelta_out) a.vdelta_out[state] = delta;
+            if (CLIP && a.vdelta_out) a.vdelta_out[state] = delta;
         }
     }
 }

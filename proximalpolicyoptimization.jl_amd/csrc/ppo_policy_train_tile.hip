@@ -168,7 +168,7 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_train_tile(TrainTileArgs 
             l[0][1] = (s.y + __shfl_xor(s.y, 32)) + a.b3[1];
             l[0][2] = (s.z + __shfl_xor(s.z, 32)) + a.b3[2];
             l[0][3] = (s.w + __shfl_xor(s.w, 32)) + a.b3[3];
-            policy_tail<2, 1, false>(a, tile, sid, act, l, lane, j, h, 0u, 0, nullptr, reinterpret_cast<float4*>(sDY));
+            policy_tail<FwdTail::Train, 1, false>(a, tile, sid, act, l, lane, j, h, 0u, 0, nullptr, reinterpret_cast<float4*>(sDY));
         }
         __syncthreads();                                                // (3) dY of the tile is in LDS
         // ================= backward, phase A: dZ2 tile w = (W3^T dY) . lrelu'(H2)

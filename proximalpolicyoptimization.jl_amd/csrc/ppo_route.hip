@@ -95,8 +95,7 @@ static int32_t debug_route(const char* who, Objective obj, int32_t dtype, int32_
               std::string(who) + ": shape");
     ARG_CHECK(fwd && bwd && cap >= 64, std::string(who) + ": output buffers");
     const TrainRoute r = train_route(dtype, F, hid, L, H, compact != 0, states, ppo_knobs(), obj);
-    // k_policy_fwd's train modes: 2 rows / 4 snapshots through idx; the value-train modes 6 / 8 and the imitation modes 12 / 13 likewise
-    const int tps = H / 32, mode = obj == Objective::Imitate ? (compact ? 13 : 12) : (obj == Objective::Value ? 6 : 2) + (compact ? 2 : 0);
+    const int tps = H / 32, mode = (int)fwd_route_mode(obj, compact != 0);      // the kernels' names print the mode's number
     switch (r.fwd) {
     case TrainFwd::None: snprintf(fwd, cap, "none"); break;
     case TrainFwd::TrainTile: snprintf(fwd, cap, "k_policy_train_tile<72,%d>", hid); break;
