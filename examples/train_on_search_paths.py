@@ -34,6 +34,10 @@ the k likeliest actions, or the likeliest set that reaches probability mass top_
 that keeps the clones apart without moving probability onto the long tail of moves the policy has learnt to be useless.  Like
 the temperature it is the search step's alone.
 
+--search beam replaces the best-of-K search by beam_search_states_: the result comes from the K = --clones action
+sequences the policy finds likeliest, so the paths depend on the policy and the start alone, not on Philox ticks or on the
+resident env a start landed in; --temperature, --top-k and --top-p are then not read.
+
 This script shows the calls and prints what it measures each round (the mean gap the search reaches, the transitions
 collected, the losses, the mean return of the plain stochastic policy).  Whether the loop learns faster or better than
 ppo_iterate_ on sampled rollouts, and which --loss serves it best, has not been measured; the script makes no such claim.
@@ -53,6 +57,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--starts", type=int, default=256, help="start states per round (one resident env replays one path)")
     ap.add_argument("--clones", type=int, default=16, help="K: trajectories the search plays from every start")
+    ap.add_argument("--search", choices=("best_of_k", "beam"), default="best_of_k",
+                    help="best_of_k: the best of K sampled trajectories; beam: the K likeliest action sequences (K <= %d)" % PPO.BEAM_MAX_K)
     ap.add_argument("--critic", action="store_true", help="GAE advantage from a device critic, bootstrapped where a path was cut")
     ap.add_argument("--loss", choices=("ppo", "clone", "sil"), default="clone",
                     help="clone: cross-entropy on the paths' actions; sil: weighted by max(advantage, 0); ppo: the clipped surrogate")
@@ -77,8 +83,11 @@ def main():
         fresh = PPO.HipVecEnv(num_envs=args.starts, Q=8, max_actions=max_actions, seed=1000 + r)   # this round's reset states
         st = fresh.internal()
         starts = (st["score"], st["degree"], fresh.active_quads())
-        with PPO.selecting(policy, "sample", args.temperature, top_k=args.top_k, top_p=args.top_p):   # the search alone; restored behind it
-            found = PPO.search_best_states_(search_env, policy, *starts, args.clones, path=True)
+        if args.search == "beam":                             # deterministic: the selection and the truncation are not read
+            found = PPO.beam_search_states_(search_env, policy, *starts, args.clones, path=True)
+        else:
+            with PPO.selecting(policy, "sample", args.temperature, top_k=args.top_k, top_p=args.top_p):   # the search alone; restored behind it
+                found = PPO.search_best_states_(search_env, policy, *starts, args.clones, path=True)
         PPO.collect_paths_(rollouts, env, policy, *starts, found["path"], discount)
         dataset = PPO.construct_dataset(rollouts)
         n = len(dataset)

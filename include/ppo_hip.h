@@ -679,6 +679,40 @@ int32_t ppo_search_resample_states_value(ppo_policy_t pol, ppo_policy_t critic, 
                                          int32_t* best_clone, int32_t* best_step, int32_t* initial_gap,
                                          int32_t* clone_gaps_or_null, int64_t interval, int64_t survivors, double value_weight,
                                          int32_t* donors_or_null, float* event_values_or_null, int16_t* path_or_null);
+/* Beam search (no reference op): the K action sequences from each start to which the policy gives the highest
+ * probability, deterministic and seed-free; K = 1 is the greedy trajectory.  Starts as for ppo_search_best_states, 1 <= K <= N,
+ * rounds of S = N / K starts; start s of a round owns resident envs s*K .. s*K + K - 1, its slots.  A slot carries a live flag
+ * and a weight (m, e), m an fp64 in [0.5, 1), e an int32, standing for the path probability m * 2^e.  Load: all K envs hold the
+ * start's state, slot 0 is live with (0.5, 1), the others are dead.  Step t = 0 .. max_actions - 1 of an unfinished start:
+ *   probabilities  p[slot][a], fp32: ppo_policy_forward's launcher on the states the envs hold (selection and truncation of
+ *                  the handle are not read);
+ *   candidates     every (k, a) with slot k live and p[k][a] > 0; x = m_k * (double)p[k][a], ONE IEEE fp64 multiply;
+ *                  (m', d) = frexp(x), e' = e_k + d.  Nothing else rounds;
+ *   select         candidates ordered by e' descending, then m' descending, then k*A + a ascending; the first
+ *                  n = min(K, #candidates): rank j becomes slot j with parent k, action a, weight (m', e'); slots n .. K-1 die;
+ *   expand         slot j takes score, degree, active and steps its parent held in front of the step, then plays its action
+ *                  with the env's own step (a no-op action included);
+ *   fold           the start's result (gap, state, step, slot) is the load state with step 0, slot 0, until some live slot's
+ *                  gap = current_score - opt_score is STRICTLY below it: then the lowest (gap, slot) of the step, with
+ *                  best_step = t + 1, best_beam = slot;
+ *   finish         the result's gap is 0, or t + 1 == max_actions.  The start's slots then idle.
+ * Per start: best_state [2V], best_active, best_gap, best_beam, best_step, initial_gap, and best_mant / best_exp, the weight
+ * of the slot the result was taken from ((0.5, 1) for step 0).  Optional: path [num_starts][max_actions] int16, the best_step
+ * 0-based actions to best_state and -1 behind them, walked on the host from the back-pointer log; log_parent, log_action
+ * [num_starts][max_actions][K] int16, per step and slot, -1 for a dead slot and for a step that did not run; log_mant (fp64)
+ * and log_exp (int32), the slots' weights, 0 where the others hold -1.  A log is kept on the device only where an output is
+ * made of it: path, log_parent or log_action cost 4 * num_starts * max_actions * K bytes there (and as much on the host while
+ * the path is walked), log_mant 8 and log_exp 4 bytes per entry; with all five null no log exists.  ppo_env_apply_paths(start, path) gives best_state,
+ * best_active and best_gap with applied == best_step.  No reset! runs and no random number is drawn: tick and episode counters
+ * of every env are unchanged; the slots' envs are left terminal; envs at and beyond S*K are untouched.
+ * PPO_ERR_ARG: K < 1, K > N, a bad start.  PPO_ERR_UNSUPPORTED: a bf16-dtype policy, H other than 32 / 128, K > 256 (the
+ * chosen keys and the weights are staged in LDS, one thread per slot). */
+int32_t ppo_beam_search_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
+                               const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
+                               uint32_t* best_active, int32_t* best_gap, int32_t* best_beam, int32_t* best_step,
+                               int32_t* initial_gap, double* best_mant, int32_t* best_exp, int16_t* path_or_null,
+                               int16_t* log_parent_or_null, int16_t* log_action_or_null, double* log_mant_or_null,
+                               int32_t* log_exp_or_null);
 /* Teacher-forced replay without a policy: path m of paths [M][stride] (0-based actions; an entry < 0 ends a path) is
  * applied to start m (score, degree [M][V], active [M], checked like ppo_env_set_internal), which begins as reset! leaves an
  * env (steps = 0, not terminal).  A path ends at its first entry < 0, after stride entries, or once the state is terminal

@@ -415,6 +415,36 @@ function search_resample_states_value(env::HipVecEnv, p::HipPolicy, critic::HipP
     (best_state = st, best_active = act, best_gap = gap, best_clone = clone, best_step = step, initial_gap = init,
      clone_gaps = gaps, donors = donors, event_values = event_values, path = path .+ Int16(1))
 end
+# beam search: the K likeliest action sequences from every start, deterministic and seed-free (K = 1 is the greedy trajectory).
+# A slot's weight (mant, exp) stands for the path probability mant * 2^exp; log_prob = log(best_mant) + best_exp * log(2).
+# path = true adds path [max_actions, M]; log = true adds parents / actions / mant / exp [K, max_actions, M], the back-pointer
+# log, 1-based with 0 for a dead slot or a step that did not run.  What is not asked for is neither allocated nor kept on the device
+function beam_search_states(env::HipVecEnv, p::HipPolicy, score::Matrix{Int8}, degree::Matrix{Int8}, active::Vector{UInt32}, K;
+                            path::Bool = true, log::Bool = false)
+    scratch = HipRollouts()
+    h = ensure!(scratch, env, 1)
+    M, V, T = length(active), 4 * env.Q, env.max_actions
+    st, act = zeros(Int8, 2V, M), zeros(UInt32, M)
+    gap, beam, step, init = zeros(Int32, M), zeros(Int32, M), zeros(Int32, M), zeros(Int32, M)
+    bmant, bexp = zeros(Float64, M), zeros(Int32, M)
+    pa = path ? zeros(Int16, T, M) : nothing
+    lp, la = log ? (zeros(Int16, Int(K), T, M), zeros(Int16, Int(K), T, M)) : (nothing, nothing)
+    lm, le = log ? (zeros(Float64, Int(K), T, M), zeros(Int32, Int(K), T, M)) : (nothing, nothing)
+    ornull(a) = a === nothing ? C_NULL : pointer(a)
+    GC.@preserve pa lp la lm le begin
+        check(ccall((:ppo_beam_search_states, LIB), Int32,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Int8}, Ptr{Int8}, Ptr{UInt32}, Ptr{Int8}, Ptr{UInt32},
+                     Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+                     Ptr{Cvoid}, Ptr{Cvoid}),
+                    p.h, env.h, h, M, Int64(K), score, degree, active, st, act, gap, beam, step, init, bmant, bexp, ornull(pa),
+                    ornull(lp), ornull(la), ornull(lm), ornull(le)))
+    end
+    out = (best_state = st, best_active = act, best_gap = gap, best_beam = beam, best_step = step, initial_gap = init,
+           log_prob = Base.log.(bmant) .+ bexp .* Base.log(2.0))
+    path && (out = merge(out, (path = pa .+ Int16(1),)))
+    log && (out = merge(out, (parents = lp .+ Int16(1), actions = la .+ Int16(1), mant = lm, exp = le)))
+    out
+end
 # teacher-forced replay without a policy: paths [stride, M] column-major == [M][stride], 1-based, anything <= 0 ends a path;
 # start i (score, degree [V, M], active [M]) begins as reset! leaves an env.  env supplies Q, max_actions and no_action_reward
 # only.  apply_paths(env, starts..., r.path) of a search result r gives r.best_state, r.best_active, r.best_gap, applied == r.best_step

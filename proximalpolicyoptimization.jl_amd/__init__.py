@@ -60,7 +60,7 @@ __all__ = [
     "value_train_", "pooled_state_value", "value_loss", "value_loss_clipped",
     "kl_stats", "explained_variance_", "explained_variance_from_sums",
     "check_internal", "best_states_", "best_state_in_rollout", "single_trajectory_scores", "count_non_flips",
-    "search_best_states_", "search_resample_states_", "check_resample", "apply_paths_", "check_paths",
+    "search_best_states_", "search_resample_states_", "check_resample", "apply_paths_", "check_paths", "beam_search_states_",
     "collect_paths_",
     "imitate_forward_backward", "imitate_train_", "imitation_loss",
     "check_selection", "selecting", "SELECT_RULES",
@@ -2033,6 +2033,59 @@ def search_resample_states_(env, policy, score, degree, active, K, interval, sur
         out["path"] = _paths_out(pa)
     if values:
         out["event_values"] = ev
+    return out
+
+
+BEAM_MAX_K = 256             # k_beam_select stages the chosen keys and the weights in LDS, one thread per slot
+
+
+def beam_search_states_(env, policy, score, degree, active, K, path=False, log=False):
+    """Beam search: the K action sequences from each caller-supplied start (score, degree [M, 4Q], active [M])
+    to which the policy gives the highest probability -- deterministic, seed-free, the greedy trajectory at K = 1.  K resident
+    envs, the start's slots, are loaded with one start; N // K starts run at a time.  A slot carries a weight (mant, exp), an
+    fp64 in [0.5, 1) and an int32 standing for the path probability mant * 2^exp; slot 0 starts live with (0.5, 1), the others
+    dead.  Every step scores the candidates (live slot k, action a with p[k][a] > 0) by ONE fp64 multiply mant_k * p[k][a],
+    re-normalised by frexp; the first min(K, #candidates) in the order (exp descending, mant descending, k * A + a ascending)
+    become slots 0, 1, ..., each taking its parent's state and playing its action.  A start's result is its load state (step
+    0) until a live slot's gap is strictly below it, then the lowest (gap, slot) of that step; it finishes at gap 0 or after
+    max_actions steps.  policy.selection and policy.truncation are not read.
+    Returns a dict of arrays, one row per start: best_state [2V] (best_score / best_degree), best_active, best_gap, best_step,
+    initial_gap, best_beam (the slot the result was taken from) and log_prob, float64: log(best_mant) + best_exp * log(2),
+    the log of the policy's probability of the path (0.0 at step 0).  path=True adds path [M, max_actions] int16: the
+    best_step 1-based actions from the start to best_state, 0 behind them (apply_paths_ replays them).  log=True adds the
+    back-pointer log, [M, max_actions, K]: parents and actions (int16, 1-based, 0 for a dead slot or a step that did not run),
+    mant (float64) and exp (int32), 0 there.  No reset! runs and nothing is sampled: ticks and episode counters stay, the
+    slots' envs are left terminal, envs at and beyond (N // K) * K are untouched.  HipVecEnv and fp32 policies only; K above
+    BEAM_MAX_K is PPOError(PPO_ERR_UNSUPPORTED)."""
+    if not isinstance(env, HipVecEnv):
+        raise PPOError(-4, "beam_search_states_ needs a HipVecEnv")
+    sc, dg, act = check_internal(score, degree, active, env.Q)
+    K = int(K)
+    if not 1 <= K <= env.N:
+        raise PPOError(-1, "AssertionError: beam_search_states: 1 <= K <= N")
+    if K > BEAM_MAX_K:
+        raise PPOError(-4, "beam_search_states: K above %d slots is not supported" % BEAM_MAX_K)
+    M, V, T = sc.shape[0], 4 * env.Q, env.max_actions
+    scratch, h = _evaluator_scratch(env)
+    st, bact = np.zeros((M, 2 * V), np.int8), np.zeros(M, np.uint32)
+    gap, beam, step, init, bexp = (np.zeros(M, np.int32) for _ in range(5))
+    bmant = np.zeros(M, np.float64)
+    pa = np.zeros((M, T), np.int16) if path else None
+    lp, la = (np.zeros((M, T, K), np.int16) for _ in range(2)) if log else (None, None)
+    lm = np.zeros((M, T, K), np.float64) if log else None
+    le = np.zeros((M, T, K), np.int32) if log else None
+    call("ppo_beam_search_states", policy._h, env._h, h, M, K, _p(sc, _lib.c_i8p), _p(dg, _lib.c_i8p), _p(act, _lib.c_u32p),
+         _p(st, _lib.c_i8p), _p(bact, _lib.c_u32p), _p(gap, _lib.c_i32p), _p(beam, _lib.c_i32p), _p(step, _lib.c_i32p),
+         _p(init, _lib.c_i32p), _p(bmant, _lib.c_f64p), _p(bexp, _lib.c_i32p),
+         None if pa is None else _p(pa, _lib.c_i16p), None if lp is None else _p(lp, _lib.c_i16p),
+         None if la is None else _p(la, _lib.c_i16p), None if lm is None else _p(lm, _lib.c_f64p),
+         None if le is None else _p(le, _lib.c_i32p))
+    out = dict(best_state=st, best_score=st[:, :V], best_degree=st[:, V:], best_active=bact, best_gap=gap, best_step=step,
+               initial_gap=init, best_beam=beam, log_prob=np.log(bmant) + bexp.astype(np.float64) * np.log(2.0))
+    if path:
+        out["path"] = _paths_out(pa)
+    if log:
+        out.update(parents=_paths_out(lp), actions=_paths_out(la), mant=lm, exp=le)
     return out
 
 

@@ -399,6 +399,291 @@ __global__ __launch_bounds__(256) void k_search_resample(EnvView e, TrackView tv
     }
 }
 
+// ================================================================ beam search
+// The candidate key of the rule, in two words.  x = m * (double)p is ONE fp64 multiply (the file is compiled without
+// contraction); p >= 2^-149 and m >= 0.5 make x a normal double, so frexp is a read of its fields: mantissa m' = 0.5 + the
+// 52 fraction bits / 2^53, exponent d = biased exponent - 1022, e' = e + d.  The order "e' descending, m' descending, index
+// ascending" is the descending order of the 108-bit number
+//     [e' ^ 0x80000000 : 32][fraction : 52][0xFFFFFF - index : 24]
+// (m' has a fixed exponent field, so its fraction orders it), held as w0 = its top 64 bits and w1 = the other 44, shifted up
+// to 48 so that both words split into whole 8-bit digits: 8 digits of w0, then 6 of w1.  Keys of one start are distinct
+__device__ __forceinline__ void beam_key(float p, double m, int e, uint32_t idx, unsigned long long& w0, unsigned long long& w1) {
+    const double x = m * (double)p;
+    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    const int d = (int)((b >> 52) & 0x7FFull) - 1022;
+    const unsigned long long frac = b & 0xFFFFFFFFFFFFFull;
+    const uint32_t eb = (uint32_t)(e + d) ^ 0x80000000u;
+    w0 = ((unsigned long long)eb << 32) | (frac >> 20);
+    w1 = (((frac & 0xFFFFFull) << 24) | (unsigned long long)(0xFFFFFFu - idx)) << 4;
+}
+constexpr int BEAM_DIGITS = 14;
+__device__ __forceinline__ uint32_t beam_digit(unsigned long long w0, unsigned long long w1, int d) {
+    return d < 8 ? (uint32_t)(w0 >> (56 - 8 * d)) & 0xFFu : (uint32_t)(w1 >> (40 - 8 * (d - 8))) & 0xFFu;
+}
+// do the first d digits of (w0, w1) equal those of (t0, t1)?
+__device__ __forceinline__ bool beam_prefix_eq(unsigned long long w0, unsigned long long w1, unsigned long long t0,
+                                               unsigned long long t1, int d) {
+    if (d == 0) return true;
+    if (d <= 8) return ((w0 ^ t0) >> (64 - 8 * d)) == 0;
+    return w0 == t0 && ((w1 ^ t1) >> (48 - 8 * (d - 8))) == 0;
+}
+
+// One pass of an NT-thread workgroup over the candidates of a start: f(p, m, e, index) for every (k, a) with slot k live (m != 0)
+// and p[k][a] > 0, index = k*A + a.  A thread takes four float4 of probabilities per round, all four loads issued before the
+// first is used: the pass is bound by the latency of its loads, not by their bytes (one workgroup per start is few waves per
+// CU).  A = 16 Q, so a float4 never straddles two slots and the rows start 16-byte aligned
+template <int NT, typename Fn>
+__device__ __forceinline__ void beam_for_each(const float* __restrict__ p0, int total_c, int A, const double* s_m, const int* s_e,
+                                              int tid, Fn&& f) {
+    const float4* __restrict__ p4 = reinterpret_cast<const float4*>(p0);
+    const int nv = total_c / 4;
+    for (int v0 = tid; v0 < nv; v0 += 4 * NT) {
+        float4 q[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int v = v0 + u * NT;
+            q[u] = v < nv ? p4[v] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = 4 * (v0 + u * NT);
+            if (c >= total_c) continue;
+            const int k = c / A;
+            const double m = s_m[k];
+            if (m == 0.0) continue;
+            const int e = s_e[k];
+            if (q[u].x > 0.0f) f(q[u].x, m, e, (uint32_t)c);
+            if (q[u].y > 0.0f) f(q[u].y, m, e, (uint32_t)c + 1u);
+            if (q[u].z > 0.0f) f(q[u].z, m, e, (uint32_t)c + 2u);
+            if (q[u].w > 0.0f) f(q[u].w, m, e, (uint32_t)c + 3u);
+        }
+    }
+}
+
+// load: the weights and the result of every start of a round, behind k_env_load_starts.  Slot 0 live with (0.5, 1), the
+// others dead; the result is the load state at step 0, slot 0
+__global__ __launch_bounds__(256) void k_beam_init(EnvView e, BeamView bv, int K, const uint32_t* __restrict__ start_state,
+                                                   const uint32_t* __restrict__ start_active, int64_t out_base) {
+    const int tid = threadIdx.x, V = e.V, dv = V / 4;
+    const int64_t s = blockIdx.x, o = out_base + s, env0 = s * K;
+    for (int k = tid; k < K; k += 256) {
+        bv.wm[env0 + k] = 0.5; bv.we[env0 + k] = 1; bv.live[env0 + k] = k == 0 ? 1 : 0;
+        bv.sel_parent[env0 + k] = -1; bv.sel_action[env0 + k] = -1;
+    }
+    uint32_t* dst = reinterpret_cast<uint32_t*>(bv.best_state + o * 2 * V);
+    for (int d = tid; d < 2 * dv; d += 256) dst[d] = start_state[o * 2 * dv + d];
+    if (tid == 0) {
+        const uint32_t act = start_active[o];
+        const int8_t* sc = reinterpret_cast<const int8_t*>(start_state + o * 2 * dv);
+        const int cur = env_total_abs(sc, act, e.Q), sum = env_total_sum(sc, act, e.Q);
+        const int gap = cur - (sum < 0 ? -sum : sum);
+        bv.best_active[o] = act; bv.best_gap[o] = gap; bv.initial_gap[o] = gap; bv.best_step[o] = 0; bv.best_beam[o] = 0;
+        bv.best_mant[o] = 0.5; bv.best_exp[o] = 1;
+        bv.fin[s] = 0;
+    }
+}
+
+// select, one workgroup of 1024 threads per start: the exact top n = min(K, #candidates) of the keys above, by a most-significant-digit radix
+// select.  A pass streams the K * A probabilities of the start (a dead slot's row is skipped), forms every candidate's key
+// again -- one multiply and a few shifts, cheaper than keeping 131,072 keys -- and counts digit d of the keys that share the d
+// digits found so far in a 256-bin LDS histogram; the bin in which the count from the top reaches `need` is digit d of the
+// n-th key T, and `need` drops by what lies above it.  Keys are distinct, so some pass ends with exactly `need` keys in T's
+// bin: every key >= (T's digits, zeros behind) is chosen, and that is n keys.  Index ties need no case of their own: the
+// index is the key's last 24 bits.  A thread counts runs of equal digits in registers and adds a run at once: in the
+// first passes every key has the same digit, and one LDS atomic per key would serialise the wave on one bin.
+// The chosen keys (n <= 256) go to LDS in any order; thread i then ranks key i by counting the keys above it (every lane reads
+// the same LDS word: a broadcast) and writes slot `rank`: parent, action, weight, and the log row of step t.  The weights of
+// the step are read into LDS behind the first barrier and written from the keys behind the last one, so no slot's new weight
+// is read as an old one
+constexpr int BEAM_SELECT_THREADS = 1024;
+__global__ __launch_bounds__(BEAM_SELECT_THREADS) void k_beam_select(const float* __restrict__ probs, BeamView bv, int K, int A, int64_t out_base,
+                                                     int M, int t) {
+    __shared__ double s_m[PPO_BEAM_MAX_K];
+    __shared__ int s_e[PPO_BEAM_MAX_K];
+    __shared__ unsigned long long s_k0[PPO_BEAM_MAX_K], s_k1[PPO_BEAM_MAX_K];
+    __shared__ uint32_t hist[256], wave_tot[4], ctrl[3], nsel;
+    const int tid = threadIdx.x;
+    const int64_t s = blockIdx.x, o = out_base + s, env0 = s * K;
+    if (bv.fin[s]) return;                                               // the start has finished: its slots idle
+    if (tid < K) {
+        const bool lv = bv.live[env0 + tid] != 0;
+        s_m[tid] = lv ? bv.wm[env0 + tid] : 0.0;                         // 0: dead (a live mantissa is >= 0.5)
+        s_e[tid] = bv.we[env0 + tid];
+    }
+    if (tid == 0) nsel = 0;
+    const float* p0 = probs + env0 * A;
+    const int total_c = K * A;
+    unsigned long long t0 = 0, t1 = 0;                                   // the digits of T found so far, zeros behind them
+    uint32_t need = (uint32_t)K;
+    int n = 0;
+    for (int d = 0; d < BEAM_DIGITS; ++d) {
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();                                                 // (first pass: the weights are staged)
+        uint32_t run_digit = 0, run = 0;
+        beam_for_each<BEAM_SELECT_THREADS>(p0, total_c, A, s_m, s_e, tid, [&](float p, double m, int e, uint32_t c) {
+            unsigned long long w0, w1;
+            beam_key(p, m, e, c, w0, w1);
+            if (!beam_prefix_eq(w0, w1, t0, t1, d)) return;
+            const uint32_t g = beam_digit(w0, w1, d);
+            if (g != run_digit) {
+                if (run) atomicAdd(&hist[run_digit], run);
+                run_digit = g; run = 0;
+            }
+            ++run;
+        });
+        if (run) atomicAdd(&hist[run_digit], run);
+        __syncthreads();
+        // keys in the bins above this thread's (threads 0 .. 255 hold a bin each): a suffix sum across the wave by shuffles,
+        // across the four waves through LDS
+        const uint32_t h = tid < 256 ? hist[tid] : 0u;
+        uint32_t inc = h;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t up = __shfl_down(inc, off);
+            if ((tid & 63) + off < 64) inc += up;
+        }
+        if ((tid & 63) == 0 && tid < 256) wave_tot[tid >> 6] = inc;
+        __syncthreads();
+        uint32_t above = inc - h, all = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const uint32_t wt = wave_tot[w];
+            all += wt;
+            if (w > (tid >> 6)) above += wt;
+        }
+        if (d == 0) {
+            n = (int)(all < (uint32_t)K ? all : (uint32_t)K);
+            need = (uint32_t)n;
+            if (n == 0) break;                                           // no candidate: every slot dies
+        }
+        if (tid < 256 && above < need && above + h >= need) { ctrl[0] = (uint32_t)tid; ctrl[1] = need - above; ctrl[2] = h; }
+        __syncthreads();
+        const unsigned long long g = ctrl[0];
+        need = ctrl[1];
+        if (d < 8) t0 |= g << (56 - 8 * d);
+        else t1 |= g << (40 - 8 * (d - 8));
+        if (ctrl[2] == need) break;                                      // T's bin holds exactly what is still to choose
+    }
+    if (n > 0) {
+        beam_for_each<BEAM_SELECT_THREADS>(p0, total_c, A, s_m, s_e, tid, [&](float p, double m, int e, uint32_t c) {
+            unsigned long long w0, w1;
+            beam_key(p, m, e, c, w0, w1);
+            if (w0 > t0 || (w0 == t0 && w1 >= t1)) {
+                const uint32_t pos = atomicAdd(&nsel, 1u);
+                if (pos < (uint32_t)PPO_BEAM_MAX_K) { s_k0[pos] = w0; s_k1[pos] = w1; }
+            }
+        });
+    }
+    __syncthreads();
+    if (tid < n) {
+        const unsigned long long w0 = s_k0[tid], w1 = s_k1[tid];
+        int r = 0;
+        for (int j = 0; j < n; ++j) {
+            const unsigned long long u0 = s_k0[j], u1 = s_k1[j];
+            r += (u0 > w0 || (u0 == w0 && u1 > w1)) ? 1 : 0;
+        }
+        const uint32_t idx = 0xFFFFFFu - (uint32_t)((w1 >> 4) & 0xFFFFFFull);
+        const int parent = (int)(idx / (uint32_t)A), action = (int)(idx % (uint32_t)A);
+        const unsigned long long frac = ((w0 & 0xFFFFFFFFull) << 20) | (w1 >> 28);
+        const double mant = __longlong_as_double((long long)(0x3FE0000000000000ull | frac));
+        const int ex = (int)((uint32_t)(w0 >> 32) ^ 0x80000000u);
+        bv.wm[env0 + r] = mant; bv.we[env0 + r] = ex; bv.live[env0 + r] = 1;
+        bv.sel_parent[env0 + r] = parent; bv.sel_action[env0 + r] = action;
+        const int64_t li = (o * M + t) * K + r;
+        if (bv.log_parent) { bv.log_parent[li] = (int16_t)parent; bv.log_action[li] = (int16_t)action; }
+        if (bv.log_mant) bv.log_mant[li] = mant;
+        if (bv.log_exp) bv.log_exp[li] = ex;
+    } else if (tid < K) {
+        bv.live[env0 + tid] = 0; bv.sel_parent[env0 + tid] = -1; bv.sel_action[env0 + tid] = -1;
+    }
+}
+
+// expand, one workgroup per start: gather -> step -> fold -> finish.
+//   gather  slot j takes score, degree, active and steps of its parent.  Every slot is a receiver and most parents are read
+//           several times, so nothing can be copied in place: the whole workgroup first stages the K states of the start in LDS
+//           (dynamic, K * (2V + 8) bytes), a barrier, and every write of a child reads LDS only.  One workgroup owns the K
+//           envs of a start and no other touches them, so that barrier is all the ordering there is to keep.
+//   step    one thread per live slot plays its action with env_step_ref (behind a second barrier: the thread reads bytes
+//           other threads gathered).  The tick the step bumps is a scratch word: the envs' own ticks stay.
+//   fold    the lowest (gap, slot) of the live slots, k_search_argmin's reduction; the start's result takes it on a STRICTLY
+//           lower gap, with step t + 1 and the slot's weight.
+//   finish  result gap 0, or t + 1 == max_actions: the start's flag is set and its K envs are left terminal.
+extern __shared__ __attribute__((aligned(16))) unsigned char beam_lds[];
+__global__ __launch_bounds__(256) void k_beam_expand(EnvView e, BeamView bv, int K, int64_t out_base, int t) {
+    __shared__ unsigned long long wave_min[4];
+    const int tid = threadIdx.x, V = e.V, dv = V / 4, row = 2 * dv;
+    const int64_t s = blockIdx.x, o = out_base + s, env0 = s * K;
+    if (bv.fin[s]) return;
+    uint32_t* st = reinterpret_cast<uint32_t*>(beam_lds);                // [K][row]
+    uint32_t* l_act = st + K * row;                                      // [K]
+    int32_t* l_steps = reinterpret_cast<int32_t*>(l_act + K);            // [K]
+    // ---- gather
+    for (int i = tid; i < K * row; i += 256) {
+        const int k = i / row, d = i - k * row;
+        st[i] = d < dv ? reinterpret_cast<const uint32_t*>(e.score + (env0 + k) * V)[d]
+                       : reinterpret_cast<const uint32_t*>(e.degree + (env0 + k) * V)[d - dv];
+    }
+    if (tid < K) { l_act[tid] = e.active[env0 + tid]; l_steps[tid] = e.steps[env0 + tid]; }
+    const int best_gap = bv.best_gap[o];                                 // read by everyone before the barriers below
+    __syncthreads();
+    for (int i = tid; i < K * row; i += 256) {
+        const int j = i / row, d = i - j * row;
+        const int par = bv.sel_parent[env0 + j];
+        if (par < 0) continue;
+        const uint32_t w = st[par * row + d];
+        if (d < dv) reinterpret_cast<uint32_t*>(e.score + (env0 + j) * V)[d] = w;
+        else reinterpret_cast<uint32_t*>(e.degree + (env0 + j) * V)[d - dv] = w;
+    }
+    const int my_par = tid < K ? bv.sel_parent[env0 + tid] : -1;
+    if (my_par >= 0) { e.active[env0 + tid] = l_act[my_par]; e.steps[env0 + tid] = l_steps[my_par]; }
+    __syncthreads();
+    // ---- step
+    unsigned long long best = ~0ull;
+    if (my_par >= 0) {
+        const int64_t nn = env0 + tid;
+        EnvRef er = ref_of(e, nn);
+        er.tick = bv.tick_scratch + nn;
+        float rew; uint8_t dn;
+        int score_after = 0;
+        const int errf = env_step_ref(const_of(e), er, bv.sel_action[nn], rew, dn, &score_after);
+        if (errf) atomicOr(e.err, errf);
+        const int sum = env_total_sum(er.sc, *er.active, e.Q);
+        const int gap = score_after - (sum < 0 ? -sum : sum);
+        best = ((unsigned long long)(uint32_t)gap << 32) | (unsigned long long)(uint32_t)tid;
+    }
+    // ---- fold
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const uint32_t hi = __shfl_xor((uint32_t)(best >> 32), off), lo = __shfl_xor((uint32_t)best, off);
+        const unsigned long long other = ((unsigned long long)hi << 32) | lo;
+        best = other < best ? other : best;
+    }
+    if ((tid & 63) == 0) wave_min[tid >> 6] = best;
+    __syncthreads();                                                     // ... and the stepped states are written
+    best = wave_min[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) best = wave_min[w] < best ? wave_min[w] : best;
+    int result_gap = best_gap;
+    if (best != ~0ull && (int)(uint32_t)(best >> 32) < best_gap) {
+        const int slot = (int)(uint32_t)best;
+        const int64_t wenv = env0 + slot;
+        result_gap = (int)(uint32_t)(best >> 32);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(bv.best_state + o * 2 * V);
+        for (int d = tid; d < row; d += 256)
+            dst[d] = d < dv ? reinterpret_cast<const uint32_t*>(e.score + wenv * V)[d]
+                            : reinterpret_cast<const uint32_t*>(e.degree + wenv * V)[d - dv];
+        if (tid == 0) {
+            bv.best_active[o] = e.active[wenv]; bv.best_gap[o] = result_gap; bv.best_step[o] = t + 1; bv.best_beam[o] = slot;
+            bv.best_mant[o] = bv.wm[wenv]; bv.best_exp[o] = bv.we[wenv];
+        }
+    }
+    // ---- finish
+    if (result_gap == 0 || t + 1 >= e.max_actions) {
+        if (tid < K) { e.done[env0 + tid] = 1; e.episodes_left[env0 + tid] = 0; }
+        if (tid == 0) bv.fin[s] = 1;
+    }
+}
+
 // Teacher-forced replay of action paths: one thread per path, no policy, no resident env.  Path m starts
 // from snapshot m (score[V] then degree[V], k_env_snapshot's layout) as reset! leaves an env -- steps 0, not terminal -- and
 // plays paths[m][0 ..] with env_step_ref until an entry < 0, `stride` entries, or a terminal state.  The thread's env IS
@@ -640,6 +925,56 @@ int32_t launch_search_resample(ppo_env_s* e, const TrackView& tv, int64_t S, int
     else if (value) LAUNCH_EVENT(false, true);
     else LAUNCH_EVENT(false, false);
 #undef LAUNCH_EVENT
+    HIP_TRY(hipGetLastError());
+    return PPO_OK;
+}
+
+int32_t launch_beam_init(ppo_env_s* e, const BeamView& bv, int64_t S, int64_t K, const int8_t* start_state,
+                         const uint32_t* start_active, int64_t out_base) {
+    hipLaunchKernelGGL(k_beam_init, dim3((unsigned)S), dim3(256), 0, ppo_stream(), view_of(e), bv, (int)K,
+                       reinterpret_cast<const uint32_t*>(start_state), start_active, out_base);
+    HIP_TRY(hipGetLastError());
+    return PPO_OK;
+}
+
+// k_beam_expand's dynamic LDS: the K parent states (score, degree: 2V bytes), active words and step counts of a start.  V = 4 Q
+// is at most 128 (Q = 32): 256 * (2 * 128 + 8) = 67,584 bytes is the most a call can ask for
+constexpr int BEAM_EXPAND_MAX_V = 128;
+static constexpr size_t beam_expand_lds(int64_t K, int64_t V) { return (size_t)K * (2 * (size_t)V + 8); }
+
+static int32_t beam_shape_ok(ppo_env_s* e, int64_t S, int64_t K) {
+    if (K < 1 || K > PPO_BEAM_MAX_K || S < 1 || S * K > e->N || e->V % 4 != 0 || K * (int64_t)e->A > 0xFFFFFF) {
+        ppo_set_error("beam_search: unsupported shape");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    return PPO_OK;
+}
+
+int32_t launch_beam_select(ppo_env_s* e, const float* probs, const BeamView& bv, int64_t S, int64_t K, int64_t out_base, int64_t t) {
+    PPO_TRY(beam_shape_ok(e, S, K));
+    ProfScope ps("k_beam_select");
+    hipLaunchKernelGGL(k_beam_select, dim3((unsigned)S), dim3(BEAM_SELECT_THREADS), 0, ppo_stream(), probs, bv, (int)K, (int)e->A, out_base,
+                       (int)e->max_actions, (int)t);
+    HIP_TRY(hipGetLastError());
+    return PPO_OK;
+}
+
+int32_t launch_beam_expand(ppo_env_s* e, const BeamView& bv, int64_t S, int64_t K, int64_t out_base, int64_t t) {
+    PPO_TRY(beam_shape_ok(e, S, K));
+    if (e->V > BEAM_EXPAND_MAX_V) {
+        ppo_set_error("beam_search: unsupported shape");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    const size_t lds = beam_expand_lds(K, e->V);
+    // per engine: an engine is one host thread with its own device
+    static thread_local bool attr_set = false;
+    if (!attr_set) {
+        HIP_TRY(hipFuncSetAttribute((const void*)k_beam_expand, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)beam_expand_lds(PPO_BEAM_MAX_K, BEAM_EXPAND_MAX_V)));
+        attr_set = true;
+    }
+    ProfScope ps("k_beam_expand");
+    hipLaunchKernelGGL(k_beam_expand, dim3((unsigned)S), dim3(256), lds, ppo_stream(), view_of(e), bv, (int)K, out_base, (int)t);
     HIP_TRY(hipGetLastError());
     return PPO_OK;
 }

@@ -358,6 +358,32 @@ int32_t launch_search_resample(ppo_env_s* e, const TrackView& tv, int64_t S, int
                                const TrackView& out, int32_t* best_clone, int64_t out_base, int32_t* donors, int64_t E,
                                int64_t event, int32_t* clone_gaps, int64_t played, const float* values = nullptr,
                                float* event_values = nullptr, float value_weight = 0.0f);
+// beam search: what its kernels share.  Start s of a round owns envs s*K .. s*K + K - 1, its slots
+constexpr int PPO_BEAM_MAX_K = 256;    // one thread per slot in k_beam_select's rank and k_beam_expand's step; the chosen keys
+                                       // (16 B each) and the weights (12 B each) are staged in static LDS
+struct BeamView {
+    double* wm = nullptr;              // [N] a slot's weight: mantissa in [0.5, 1)
+    int32_t* we = nullptr;             // [N] ... and exponent
+    uint8_t* live = nullptr;           // [N]
+    int32_t* sel_parent = nullptr;     // [N] what k_beam_select chose for slot j of the step: its parent slot (-1: dead)
+    int32_t* sel_action = nullptr;     // [N] ... and 0-based action
+    uint32_t* tick_scratch = nullptr;  // [N] the tick env_step_ref bumps in place of the env's own
+    int32_t* fin = nullptr;            // [S] the start of the round has finished
+    // results, one record per start of the call
+    int8_t* best_state = nullptr; uint32_t* best_active = nullptr;
+    int32_t* best_gap = nullptr; int32_t* best_beam = nullptr; int32_t* best_step = nullptr; int32_t* initial_gap = nullptr;
+    double* best_mant = nullptr; int32_t* best_exp = nullptr;
+    // back-pointer log [num_starts][max_actions][K], each on request: parent and action (both or neither), the weights
+    int16_t* log_parent = nullptr; int16_t* log_action = nullptr; double* log_mant = nullptr; int32_t* log_exp = nullptr;
+};
+// load (behind launch_env_load_starts): slot 0 of every start live with weight (0.5, 1), the others dead; record out_base + s
+// = the start's state at step 0
+int32_t launch_beam_init(ppo_env_s* e, const BeamView& bv, int64_t S, int64_t K, const int8_t* start_state,
+                         const uint32_t* start_active, int64_t out_base);
+// step t of the S starts of a round: the exact top min(K, #candidates) of the scored candidates (probs: [N][A] of the states
+// the envs hold) into sel_*, the weights and row t of the log; then gather of the parents' states, env step, fold, finish
+int32_t launch_beam_select(ppo_env_s* e, const float* probs, const BeamView& bv, int64_t S, int64_t K, int64_t out_base, int64_t t);
+int32_t launch_beam_expand(ppo_env_s* e, const BeamView& bv, int64_t S, int64_t K, int64_t out_base, int64_t t);
 // the refusals every value entry point shares: a bf16-dtype critic, an input width other than F (ppo_train.hip)
 extern "C" int32_t value_checks(const char* who, ppo_policy_s* critic, int32_t F);
 // teacher-forced replay: path m ([count][stride] 0-based actions, < 0 ends a path) from snapshot m (score[V]

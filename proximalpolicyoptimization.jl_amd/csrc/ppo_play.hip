@@ -1,6 +1,6 @@
 // ppo_play.hip -- the calls that play the resident envs step by step from the host (launch order only; all math is in the
-// kernels): the episodes-mode collector, the evaluators, best-state tracking, the best-of-K and resampling searches, the
-// teacher-forced replay and collection, and the host helpers they share.  The step-mode collector (ppo_collect_rollouts) and
+// kernels): the episodes-mode collector, the evaluators, best-state tracking, the best-of-K and resampling searches, beam
+// search, the teacher-forced replay and collection, and the host helpers they share.  The step-mode collector (ppo_collect_rollouts) and
 // the handles these calls work on are in ppo_api.hip.
 #include "ppo_internal.h"
 #include <algorithm>
@@ -511,6 +511,123 @@ int32_t ppo_search_resample_states_value(ppo_policy_t pol, ppo_policy_t critic, 
     const ResampleArgs rs = {interval, survivors, donors_or_null, critic, value_weight, event_values_or_null};
     return search_impl("search_resample_states", pol, env, scratch, {num_starts, K, score, degree, active, best_state,
                        best_active, best_gap, best_clone, best_step, initial_gap, clone_gaps_or_null, path_or_null}, &rs);
+}
+
+// ================================================================ beam search
+// Beam search: the K likeliest action sequences from every start, deterministic and seed-free.  search_impl's
+// rounds of S = N / K starts; a step is observe, the probabilities forward (ppo_policy_forward's launcher over the N envs),
+// k_beam_select and k_beam_expand.  A finished start's workgroups return at once; the host reads the round's finish flags
+// every 8 steps, play_quotas' poll, and nothing else crosses in the loop.  No reset! runs, nothing is sampled, the envs' ticks
+// and episode counters stay (the step bumps a scratch tick).  The path is walked on the host from the back-pointer log, which
+// comes back in one copy behind the last round
+int32_t ppo_beam_search_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
+                               const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
+                               uint32_t* best_active, int32_t* best_gap, int32_t* best_beam, int32_t* best_step,
+                               int32_t* initial_gap, double* best_mant, int32_t* best_exp, int16_t* path_or_null,
+                               int16_t* log_parent_or_null, int16_t* log_action_or_null, double* log_mant_or_null,
+                               int32_t* log_exp_or_null) {
+    const std::string who = "beam_search_states";
+    ARG_CHECK(score && degree && active && best_state && best_active && best_gap && best_beam && best_step && initial_gap &&
+              best_mant && best_exp, who + ": null argument");
+    PPO_TRY(check_shapes(scratch, env, pol));
+    const int64_t N = env->N, Mst = num_starts;
+    ARG_CHECK(Mst >= 1 && K >= 1 && K <= N, who + ": need num_starts >= 1 and 1 <= K <= N");
+    if (pol->dtype != PPO_DTYPE_F32) {
+        ppo_set_error(who + ": a bf16-dtype policy is not supported (the weights are defined on the fp32-MFMA forward's probabilities)");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    if (env->H != 32 && env->H != 128) {
+        ppo_set_error(who + ": H must be 32 (Q=8) or 128 (Q=32) half-edges in this build");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    PPO_TRY(check_internal_host(env->Q, Mst, score, degree, active));
+    if (K > PPO_BEAM_MAX_K) {
+        ppo_set_error(who + ": K above 256 slots is not supported (the chosen keys and the weights are staged in LDS, one thread per slot)");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    const int32_t V = env->V, M = env->max_actions, A = env->A;
+    const int64_t S = N / K;
+    const size_t Ms = (size_t)Mst, log_len = Ms * (size_t)M * (size_t)K;
+    PPO_TRY(rollouts_reserve(scratch, 1, false));
+    StartBufs start;
+    PPO_TRY(start.upload(V, Mst, score, degree, active));
+    DevBuf<float> d_probs; DevBuf<double> d_wm, d_bmant, d_lmant; DevBuf<int32_t> d_ints, d_res, d_lexp; DevBuf<uint8_t> d_live;
+    DevBuf<uint32_t> d_tick, d_bact; DevBuf<int8_t> d_state; DevBuf<int16_t> d_log;
+    PPO_TRY(d_probs.alloc((size_t)N * A)); PPO_TRY(d_wm.alloc((size_t)N)); PPO_TRY(d_live.alloc((size_t)N));
+    PPO_TRY(d_ints.alloc((size_t)4 * N + S));                            // we, sel_parent, sel_action, the load's step counters [N]; fin [S]
+    PPO_TRY(d_tick.alloc((size_t)N));
+    PPO_TRY(d_state.alloc(Ms * 2 * V)); PPO_TRY(d_bact.alloc(Ms)); PPO_TRY(d_bmant.alloc(Ms));
+    PPO_TRY(d_res.alloc(5 * Ms));                                        // gap, beam, step, initial_gap, exp
+    // the back-pointer log (parent, action: -1 = a dead slot, a step that did not run) is kept only where an output is made of it
+    const bool want_log = path_or_null || log_parent_or_null || log_action_or_null;
+    hipStream_t stream = ppo_stream();
+    if (want_log) {
+        PPO_TRY(d_log.alloc(2 * log_len));
+        HIP_TRY(hipMemsetAsync(d_log.p, 0xFF, 2 * log_len * sizeof(int16_t), stream));
+    }
+    HIP_TRY(hipMemsetAsync(d_tick.p, 0, (size_t)N * 4, stream));
+    BeamView bv;
+    bv.wm = d_wm.p; bv.we = d_ints.p; bv.sel_parent = d_ints.p + N; bv.sel_action = d_ints.p + 2 * N; bv.fin = d_ints.p + 4 * N;
+    int32_t* const load_t_in = d_ints.p + 3 * N;                         // k_env_load_starts zeroes a step counter per env; unread here
+    bv.live = d_live.p; bv.tick_scratch = d_tick.p;
+    bv.best_state = d_state.p; bv.best_active = d_bact.p; bv.best_mant = d_bmant.p;
+    bv.best_gap = d_res.p; bv.best_beam = d_res.p + Ms; bv.best_step = d_res.p + 2 * Ms; bv.initial_gap = d_res.p + 3 * Ms;
+    bv.best_exp = d_res.p + 4 * Ms;
+    if (want_log) { bv.log_parent = d_log.p; bv.log_action = d_log.p + log_len; }
+    if (log_mant_or_null) {                                              // weights of a dead slot or of a step that did not run: 0
+        PPO_TRY(d_lmant.alloc(log_len));
+        HIP_TRY(hipMemsetAsync(d_lmant.p, 0, log_len * 8, stream));
+        bv.log_mant = d_lmant.p;
+    }
+    if (log_exp_or_null) {
+        PPO_TRY(d_lexp.alloc(log_len));
+        HIP_TRY(hipMemsetAsync(d_lexp.p, 0, log_len * 4, stream));
+        bv.log_exp = d_lexp.p;
+    }
+    std::vector<int32_t> fin;
+    for (int64_t base = 0; base < Mst; base += S) {
+        const int64_t Sr = std::min(S, Mst - base);
+        PPO_TRY(launch_env_load_starts(env, start.d_start.p + (size_t)base * 2 * V, start.d_act.p + base, Sr * K, K, load_t_in));
+        PPO_TRY(launch_beam_init(env, bv, Sr, K, start.d_start.p, start.d_act.p, base));
+        bool all = false;
+        for (int64_t t = 0; t < M && !all; ++t) {
+            PPO_TRY(launch_env_observe(env, scratch->states.p, scratch->active.p));
+            PPO_TRY(launch_policy_probs(pol, scratch->states.p, scratch->active.p, N, env->H, d_probs.p));
+            PPO_TRY(launch_beam_select(env, d_probs.p, bv, Sr, K, base, t));
+            PPO_TRY(launch_beam_expand(env, bv, Sr, K, base, t));
+            if (poll_due(t, M)) {
+                fin.resize((size_t)Sr);
+                PPO_TRY(d2h(fin.data(), bv.fin, (size_t)Sr));
+                all = std::all_of(fin.begin(), fin.end(), [](int32_t f) { return f != 0; });
+            }
+        }
+        ARG_CHECK(all, who + ": the starts did not finish within max_actions steps");
+    }
+    rollouts_scratch_used(scratch);
+    PPO_TRY(d2h(best_state, d_state.p, Ms * 2 * V)); PPO_TRY(d2h(best_active, d_bact.p, Ms));
+    PPO_TRY(d2h(best_gap, bv.best_gap, Ms)); PPO_TRY(d2h(best_beam, bv.best_beam, Ms)); PPO_TRY(d2h(best_step, bv.best_step, Ms));
+    PPO_TRY(d2h(initial_gap, bv.initial_gap, Ms)); PPO_TRY(d2h(best_mant, d_bmant.p, Ms)); PPO_TRY(d2h(best_exp, bv.best_exp, Ms));
+    if (log_mant_or_null) PPO_TRY(d2h(log_mant_or_null, d_lmant.p, log_len));
+    if (log_exp_or_null) PPO_TRY(d2h(log_exp_or_null, d_lexp.p, log_len));
+    if (path_or_null || log_parent_or_null || log_action_or_null) {
+        std::vector<int16_t> log(2 * log_len);
+        PPO_TRY(d2h(log.data(), d_log.p, 2 * log_len));
+        if (log_parent_or_null) std::memcpy(log_parent_or_null, log.data(), log_len * sizeof(int16_t));
+        if (log_action_or_null) std::memcpy(log_action_or_null, log.data() + log_len, log_len * sizeof(int16_t));
+        if (path_or_null) {                                              // walk the back-pointers from (best_step, best_beam)
+            std::fill(path_or_null, path_or_null + Ms * (size_t)M, (int16_t)-1);
+            for (size_t m = 0; m < Ms; ++m) {
+                int slot = best_beam[m];
+                for (int t = best_step[m] - 1; t >= 0; --t) {
+                    const size_t li = (m * (size_t)M + (size_t)t) * (size_t)K + (size_t)slot;
+                    ARG_CHECK(slot >= 0 && slot < K && log[li] >= 0, who + ": the back-pointer log does not lead to the result");
+                    path_or_null[m * (size_t)M + (size_t)t] = log[log_len + li];
+                    slot = log[li];
+                }
+            }
+        }
+    }
+    return ppo_env_check_errors(env, nullptr);
 }
 
 // ================================================================ teacher-forced replay and collection
