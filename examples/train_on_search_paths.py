@@ -36,7 +36,9 @@ the temperature it is the search step's alone.
 
 --search beam replaces the best-of-K search by beam_search_states_: the result comes from the K = --clones action
 sequences the policy finds likeliest, so the paths depend on the policy and the start alone, not on Philox ticks or on the
-resident env a start landed in; --temperature, --top-k and --top-p are then not read.
+resident env a start landed in; --temperature, --top-k and --top-p are then not read.  --distinct children|parents makes it
+the distinct beam (DESIGN.md 7p): K different states per step instead of K spellings of a few, so that the round's paths differ;
+--beam-rounds is its budget, 256 candidates examined per step and round (--rounds is taken: the training rounds).
 
 This script shows the calls and prints what it measures each round (the mean gap the search reaches, the transitions
 collected, the losses, the mean return of the plain stochastic policy).  Whether the loop learns faster or better than
@@ -59,6 +61,10 @@ def main():
     ap.add_argument("--clones", type=int, default=16, help="K: trajectories the search plays from every start")
     ap.add_argument("--search", choices=("best_of_k", "beam"), default="best_of_k",
                     help="best_of_k: the best of K sampled trajectories; beam: the K likeliest action sequences (K <= %d)" % PPO.BEAM_MAX_K)
+    ap.add_argument("--distinct", choices=("children", "parents"), default=None,
+                    help="--search beam: keep K different states per step; parents: also different from the step's parents")
+    ap.add_argument("--beam-rounds", type=int, default=4,
+                    help="--distinct: windows of 256 candidates a step may examine (1 .. %d)" % PPO.BEAM_MAX_ROUNDS)
     ap.add_argument("--critic", action="store_true", help="GAE advantage from a device critic, bootstrapped where a path was cut")
     ap.add_argument("--loss", choices=("ppo", "clone", "sil"), default="clone",
                     help="clone: cross-entropy on the paths' actions; sil: weighted by max(advantage, 0); ppo: the clipped surrogate")
@@ -84,7 +90,8 @@ def main():
         st = fresh.internal()
         starts = (st["score"], st["degree"], fresh.active_quads())
         if args.search == "beam":                             # deterministic: the selection and the truncation are not read
-            found = PPO.beam_search_states_(search_env, policy, *starts, args.clones, path=True)
+            found = PPO.beam_search_states_distinct_(search_env, policy, *starts, args.clones, path=True,
+                                                     distinct=args.distinct, rounds=args.beam_rounds)
         else:
             with PPO.selecting(policy, "sample", args.temperature, top_k=args.top_k, top_p=args.top_p):   # the search alone; restored behind it
                 found = PPO.search_best_states_(search_env, policy, *starts, args.clones, path=True)

@@ -713,6 +713,28 @@ int32_t ppo_beam_search_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t s
                                int32_t* initial_gap, double* best_mant, int32_t* best_exp, int16_t* path_or_null,
                                int16_t* log_parent_or_null, int16_t* log_action_or_null, double* log_mant_or_null,
                                int32_t* log_exp_or_null);
+/* The distinct beam: ppo_beam_search_states with its select and expand replaced by a walk that keeps K
+ * DIFFERENT states per step.  distinct_mode 0 is ppo_beam_search_states itself (rounds is not read, log_rank and examined must
+ * be null); 1 "children", 2 "parents".  A state's identity is the bytes of score[V], degree[V] and the active word.  The seen
+ * set of a step is empty in mode 1 and holds the states of the live slots in front of the step in mode 2.  The candidates
+ * are taken in ppo_beam_search_states' order, at most B = 256 * rounds of them; examining (k, a) forms the child (slot k's
+ * state in front of the step after the env's own step with a, a no-op included); a child whose state is in the seen set is
+ * rejected, any other becomes slot j = the number accepted so far with parent k, action a and its own weight (m', e') -- the
+ * probabilities of rejected paths are not added to it -- and joins the seen set.  The walk stops at K accepted, at the end of
+ * the candidates or at B examined; slots n .. K-1 are dead.  Fold and finish as in ppo_beam_search_states, the finish also
+ * when nothing was accepted (the result stands as it is).  Outputs as there; additionally log_rank [num_starts][max_actions][K]
+ * int32, the 0-based position of the slot's candidate in the step's order (-1: a dead slot, a step that did not run), and
+ * examined [num_starts][max_actions] int32, the candidates the walk looked at: the last accepted rank + 1 if it stopped at K,
+ * otherwise min(#candidates, B); -1 for a step that did not run.
+ * PPO_ERR_ARG: distinct_mode outside 0 .. 2, rounds outside 1 .. 16 in modes 1 and 2, a rank or examined output in mode 0;
+ * everything else as ppo_beam_search_states. */
+int32_t ppo_beam_search_states_distinct(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
+                                        const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
+                                        uint32_t* best_active, int32_t* best_gap, int32_t* best_beam, int32_t* best_step,
+                                        int32_t* initial_gap, double* best_mant, int32_t* best_exp, int16_t* path_or_null,
+                                        int16_t* log_parent_or_null, int16_t* log_action_or_null, double* log_mant_or_null,
+                                        int32_t* log_exp_or_null, int32_t distinct_mode, int32_t rounds,
+                                        int32_t* log_rank_or_null, int32_t* examined_or_null);
 /* Teacher-forced replay without a policy: path m of paths [M][stride] (0-based actions; an entry < 0 ends a path) is
  * applied to start m (score, degree [M][V], active [M], checked like ppo_env_set_internal), which begins as reset! leaves an
  * env (steps = 0, not terminal).  A path ends at its first entry < 0, after stride entries, or once the state is terminal

@@ -419,8 +419,13 @@ end
 # A slot's weight (mant, exp) stands for the path probability mant * 2^exp; log_prob = log(best_mant) + best_exp * log(2).
 # path = true adds path [max_actions, M]; log = true adds parents / actions / mant / exp [K, max_actions, M], the back-pointer
 # log, 1-based with 0 for a dead slot or a step that did not run.  What is not asked for is neither allocated nor kept on the device
+# distinct = :children or :parents keeps K DIFFERENT states per step (DESIGN.md 7p): the candidates are walked in the same order,
+# at most 256 * rounds of them, and a child whose state equals one accepted before it (:parents: or a live slot's in front of the
+# step) is rejected.  log = true then adds rank [K, max_actions, M] (0-based, -1 dead) and examined [max_actions, M]
 function beam_search_states(env::HipVecEnv, p::HipPolicy, score::Matrix{Int8}, degree::Matrix{Int8}, active::Vector{UInt32}, K;
-                            path::Bool = true, log::Bool = false)
+                            path::Bool = true, log::Bool = false, distinct::Union{Nothing, Symbol} = nothing, rounds::Integer = 4)
+    mode = distinct === nothing ? Int32(0) : distinct === :children ? Int32(1) : distinct === :parents ? Int32(2) :
+           throw(ArgumentError("beam_search_states: distinct must be nothing, :children or :parents"))
     scratch = HipRollouts()
     h = ensure!(scratch, env, 1)
     M, V, T = length(active), 4 * env.Q, env.max_actions
@@ -431,18 +436,30 @@ function beam_search_states(env::HipVecEnv, p::HipPolicy, score::Matrix{Int8}, d
     lp, la = log ? (zeros(Int16, Int(K), T, M), zeros(Int16, Int(K), T, M)) : (nothing, nothing)
     lm, le = log ? (zeros(Float64, Int(K), T, M), zeros(Int32, Int(K), T, M)) : (nothing, nothing)
     ornull(a) = a === nothing ? C_NULL : pointer(a)
-    GC.@preserve pa lp la lm le begin
-        check(ccall((:ppo_beam_search_states, LIB), Int32,
-                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Int8}, Ptr{Int8}, Ptr{UInt32}, Ptr{Int8}, Ptr{UInt32},
-                     Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
-                     Ptr{Cvoid}, Ptr{Cvoid}),
-                    p.h, env.h, h, M, Int64(K), score, degree, active, st, act, gap, beam, step, init, bmant, bexp, ornull(pa),
-                    ornull(lp), ornull(la), ornull(lm), ornull(le)))
+    lr = log && mode != 0 ? zeros(Int32, Int(K), T, M) : nothing
+    lx = log && mode != 0 ? zeros(Int32, T, M) : nothing
+    GC.@preserve pa lp la lm le lr lx begin
+        if mode == 0
+            check(ccall((:ppo_beam_search_states, LIB), Int32,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Int8}, Ptr{Int8}, Ptr{UInt32}, Ptr{Int8}, Ptr{UInt32},
+                         Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+                         Ptr{Cvoid}, Ptr{Cvoid}),
+                        p.h, env.h, h, M, Int64(K), score, degree, active, st, act, gap, beam, step, init, bmant, bexp, ornull(pa),
+                        ornull(lp), ornull(la), ornull(lm), ornull(le)))
+        else
+            check(ccall((:ppo_beam_search_states_distinct, LIB), Int32,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Ptr{Int8}, Ptr{Int8}, Ptr{UInt32}, Ptr{Int8}, Ptr{UInt32},
+                         Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+                         Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}),
+                        p.h, env.h, h, M, Int64(K), score, degree, active, st, act, gap, beam, step, init, bmant, bexp, ornull(pa),
+                        ornull(lp), ornull(la), ornull(lm), ornull(le), mode, Int32(rounds), ornull(lr), ornull(lx)))
+        end
     end
     out = (best_state = st, best_active = act, best_gap = gap, best_beam = beam, best_step = step, initial_gap = init,
            log_prob = Base.log.(bmant) .+ bexp .* Base.log(2.0))
     path && (out = merge(out, (path = pa .+ Int16(1),)))
     log && (out = merge(out, (parents = lp .+ Int16(1), actions = la .+ Int16(1), mant = lm, exp = le)))
+    log && mode != 0 && (out = merge(out, (rank = lr, examined = lx)))
     out
 end
 # teacher-forced replay without a policy: paths [stride, M] column-major == [M][stride], 1-based, anything <= 0 ends a path;

@@ -61,6 +61,7 @@ __all__ = [
     "kl_stats", "explained_variance_", "explained_variance_from_sums",
     "check_internal", "best_states_", "best_state_in_rollout", "single_trajectory_scores", "count_non_flips",
     "search_best_states_", "search_resample_states_", "check_resample", "apply_paths_", "check_paths", "beam_search_states_",
+    "beam_search_states_distinct_",
     "collect_paths_",
     "imitate_forward_backward", "imitate_train_", "imitation_loss",
     "check_selection", "selecting", "SELECT_RULES",
@@ -2039,6 +2040,10 @@ def search_resample_states_(env, policy, score, degree, active, K, interval, sur
 BEAM_MAX_K = 256             # k_beam_select stages the chosen keys and the weights in LDS, one thread per slot
 
 
+BEAM_DISTINCT_MODES = {None: 0, "children": 1, "parents": 2}
+BEAM_MAX_ROUNDS = 16         # windows of 256 candidates a step of the distinct beam may examine
+
+
 def beam_search_states_(env, policy, score, degree, active, K, path=False, log=False):
     """Beam search: the K action sequences from each caller-supplied start (score, degree [M, 4Q], active [M])
     to which the policy gives the highest probability -- deterministic, seed-free, the greedy trajectory at K = 1.  K resident
@@ -2057,8 +2062,25 @@ def beam_search_states_(env, policy, score, degree, active, K, path=False, log=F
     mant (float64) and exp (int32), 0 there.  No reset! runs and nothing is sampled: ticks and episode counters stay, the
     slots' envs are left terminal, envs at and beyond (N // K) * K are untouched.  HipVecEnv and fp32 policies only; K above
     BEAM_MAX_K is PPOError(PPO_ERR_UNSUPPORTED)."""
+    return beam_search_states_distinct_(env, policy, score, degree, active, K, path=path, log=log, distinct=None)
+
+
+def beam_search_states_distinct_(env, policy, score, degree, active, K, path=False, log=False, distinct=None, rounds=4):
+    """beam_search_states_ with two more keywords; everything said there holds.
+    distinct="children" or "parents"  keeps K DIFFERENT states per step: the candidates are taken in the same
+    order, at most 256 * rounds of them (1 <= rounds <= 16); each is played, and a child whose state (score, degree, active)
+    equals that of a child accepted before it -- under "parents" also that of a slot live in front of the step -- is rejected;
+    the others become slots 0, 1, ... until K are accepted, each with its own weight.  A start also finishes when a step
+    accepts nothing.  log=True then adds rank [M, max_actions, K] int32 (the 0-based position of the slot's candidate in the
+    step's order, -1 for a dead slot or a step that did not run) and examined [M, max_actions] int32 (the candidates the step
+    looked at, -1 for a step that did not run).  distinct=None is the plain beam: rounds is not read."""
     if not isinstance(env, HipVecEnv):
         raise PPOError(-4, "beam_search_states_ needs a HipVecEnv")
+    if not (distinct is None or isinstance(distinct, str)) or distinct not in BEAM_DISTINCT_MODES:
+        raise PPOError(-1, "AssertionError: beam_search_states: distinct must be None, \"children\" or \"parents\"")
+    mode = BEAM_DISTINCT_MODES[distinct]
+    if mode and not (isinstance(rounds, (int, np.integer)) and 1 <= int(rounds) <= BEAM_MAX_ROUNDS):
+        raise PPOError(-1, "AssertionError: beam_search_states: need 1 <= rounds <= %d" % BEAM_MAX_ROUNDS)
     sc, dg, act = check_internal(score, degree, active, env.Q)
     K = int(K)
     if not 1 <= K <= env.N:
@@ -2074,18 +2096,27 @@ def beam_search_states_(env, policy, score, degree, active, K, path=False, log=F
     lp, la = (np.zeros((M, T, K), np.int16) for _ in range(2)) if log else (None, None)
     lm = np.zeros((M, T, K), np.float64) if log else None
     le = np.zeros((M, T, K), np.int32) if log else None
-    call("ppo_beam_search_states", policy._h, env._h, h, M, K, _p(sc, _lib.c_i8p), _p(dg, _lib.c_i8p), _p(act, _lib.c_u32p),
-         _p(st, _lib.c_i8p), _p(bact, _lib.c_u32p), _p(gap, _lib.c_i32p), _p(beam, _lib.c_i32p), _p(step, _lib.c_i32p),
-         _p(init, _lib.c_i32p), _p(bmant, _lib.c_f64p), _p(bexp, _lib.c_i32p),
-         None if pa is None else _p(pa, _lib.c_i16p), None if lp is None else _p(lp, _lib.c_i16p),
-         None if la is None else _p(la, _lib.c_i16p), None if lm is None else _p(lm, _lib.c_f64p),
-         None if le is None else _p(le, _lib.c_i32p))
+    args = (policy._h, env._h, h, M, K, _p(sc, _lib.c_i8p), _p(dg, _lib.c_i8p), _p(act, _lib.c_u32p),
+            _p(st, _lib.c_i8p), _p(bact, _lib.c_u32p), _p(gap, _lib.c_i32p), _p(beam, _lib.c_i32p), _p(step, _lib.c_i32p),
+            _p(init, _lib.c_i32p), _p(bmant, _lib.c_f64p), _p(bexp, _lib.c_i32p),
+            None if pa is None else _p(pa, _lib.c_i16p), None if lp is None else _p(lp, _lib.c_i16p),
+            None if la is None else _p(la, _lib.c_i16p), None if lm is None else _p(lm, _lib.c_f64p),
+            None if le is None else _p(le, _lib.c_i32p))
+    lr = np.zeros((M, T, K), np.int32) if log and mode else None
+    lx = np.zeros((M, T), np.int32) if log and mode else None
+    if mode:
+        call("ppo_beam_search_states_distinct", *args, mode, int(rounds), None if lr is None else _p(lr, _lib.c_i32p),
+             None if lx is None else _p(lx, _lib.c_i32p))
+    else:
+        call("ppo_beam_search_states", *args)
     out = dict(best_state=st, best_score=st[:, :V], best_degree=st[:, V:], best_active=bact, best_gap=gap, best_step=step,
                initial_gap=init, best_beam=beam, log_prob=np.log(bmant) + bexp.astype(np.float64) * np.log(2.0))
     if path:
         out["path"] = _paths_out(pa)
     if log:
         out.update(parents=_paths_out(lp), actions=_paths_out(la), mant=lm, exp=le)
+        if mode:
+            out.update(rank=lr, examined=lx)
     return out
 
 

@@ -64,6 +64,9 @@ SIGNATURES = {
                                          c_i32p, c_i32p, c_i32p, C.c_int64, C.c_int64, C.c_double, c_i32p, c_f32p, c_i16p],
     "ppo_beam_search_states": [H, H, H, C.c_int64, C.c_int64, c_i8p, c_i8p, c_u32p, c_i8p, c_u32p, c_i32p, c_i32p, c_i32p,
                                c_i32p, c_f64p, c_i32p, c_i16p, c_i16p, c_i16p, c_f64p, c_i32p],
+    "ppo_beam_search_states_distinct": [H, H, H, C.c_int64, C.c_int64, c_i8p, c_i8p, c_u32p, c_i8p, c_u32p, c_i32p, c_i32p,
+                                        c_i32p, c_i32p, c_f64p, c_i32p, c_i16p, c_i16p, c_i16p, c_f64p, c_i32p, C.c_int32,
+                                        C.c_int32, c_i32p, c_i32p],
     "ppo_env_apply_paths": [H, C.c_int64, c_i8p, c_i8p, c_u32p, c_i16p, C.c_int64, c_i8p, c_u32p, c_i32p, c_i32p, c_i32p],
     "ppo_collect_paths": [H, H, H, C.c_int64, c_i8p, c_i8p, c_u32p, c_i16p, C.c_int64, C.c_double, C.c_int32, C.c_int32],
     "ppo_policy_set_selection": [H, C.c_int32, C.c_double],

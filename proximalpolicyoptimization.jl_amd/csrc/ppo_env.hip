@@ -495,9 +495,13 @@ __global__ __launch_bounds__(256) void k_beam_init(EnvView e, BeamView bv, int K
 // the same LDS word: a broadcast) and writes slot `rank`: parent, action, weight, and the log row of step t.  The weights of
 // the step are read into LDS behind the first barrier and written from the keys behind the last one, so no slot's new weight
 // is read as an old one
+// WINDOW is the same select over the keys STRICTLY BELOW the start's ceiling: the top min(256, remaining) of
+// them go, in rank order, into the start's window instead of the slots, and the lowest chosen key becomes the new ceiling.
+// Keys are distinct, so the ceiling is exact: no candidate enters two windows and none is skipped
 constexpr int BEAM_SELECT_THREADS = 1024;
-__global__ __launch_bounds__(BEAM_SELECT_THREADS) void k_beam_select(const float* __restrict__ probs, BeamView bv, int K, int A, int64_t out_base,
-                                                     int M, int t) {
+template <bool WINDOW>
+__device__ __forceinline__ void beam_select_body(const float* __restrict__ probs, const BeamView& bv, const BeamChildView& cv, int K, int A,
+                                                 int64_t out_base, int M, int t) {
     __shared__ double s_m[PPO_BEAM_MAX_K];
     __shared__ int s_e[PPO_BEAM_MAX_K];
     __shared__ unsigned long long s_k0[PPO_BEAM_MAX_K], s_k1[PPO_BEAM_MAX_K];
@@ -505,6 +509,12 @@ __global__ __launch_bounds__(BEAM_SELECT_THREADS) void k_beam_select(const float
     const int tid = threadIdx.x;
     const int64_t s = blockIdx.x, o = out_base + s, env0 = s * K;
     if (bv.fin[s]) return;                                               // the start has finished: its slots idle
+    unsigned long long c0 = 0, c1 = 0;
+    if (WINDOW) {
+        if (cv.n[s] >= K || cv.exhausted[s]) return;                     // the step's beam is full, or no candidate is left
+        c0 = cv.ceil[2 * s]; c1 = cv.ceil[2 * s + 1];
+    }
+    const int limit = WINDOW ? PPO_BEAM_WINDOW : K;
     if (tid < K) {
         const bool lv = bv.live[env0 + tid] != 0;
         s_m[tid] = lv ? bv.wm[env0 + tid] : 0.0;                         // 0: dead (a live mantissa is >= 0.5)
@@ -514,7 +524,7 @@ __global__ __launch_bounds__(BEAM_SELECT_THREADS) void k_beam_select(const float
     const float* p0 = probs + env0 * A;
     const int total_c = K * A;
     unsigned long long t0 = 0, t1 = 0;                                   // the digits of T found so far, zeros behind them
-    uint32_t need = (uint32_t)K;
+    uint32_t need = (uint32_t)limit;
     int n = 0;
     for (int d = 0; d < BEAM_DIGITS; ++d) {
         if (tid < 256) hist[tid] = 0;
@@ -523,6 +533,7 @@ __global__ __launch_bounds__(BEAM_SELECT_THREADS) void k_beam_select(const float
         beam_for_each<BEAM_SELECT_THREADS>(p0, total_c, A, s_m, s_e, tid, [&](float p, double m, int e, uint32_t c) {
             unsigned long long w0, w1;
             beam_key(p, m, e, c, w0, w1);
+            if (WINDOW && !(w0 < c0 || (w0 == c0 && w1 < c1))) return;
             if (!beam_prefix_eq(w0, w1, t0, t1, d)) return;
             const uint32_t g = beam_digit(w0, w1, d);
             if (g != run_digit) {
@@ -552,7 +563,7 @@ __global__ __launch_bounds__(BEAM_SELECT_THREADS) void k_beam_select(const float
             if (w > (tid >> 6)) above += wt;
         }
         if (d == 0) {
-            n = (int)(all < (uint32_t)K ? all : (uint32_t)K);
+            n = (int)(all < (uint32_t)limit ? all : (uint32_t)limit);
             need = (uint32_t)n;
             if (n == 0) break;                                           // no candidate: every slot dies
         }
@@ -568,6 +579,7 @@ __global__ __launch_bounds__(BEAM_SELECT_THREADS) void k_beam_select(const float
         beam_for_each<BEAM_SELECT_THREADS>(p0, total_c, A, s_m, s_e, tid, [&](float p, double m, int e, uint32_t c) {
             unsigned long long w0, w1;
             beam_key(p, m, e, c, w0, w1);
+            if (WINDOW && !(w0 < c0 || (w0 == c0 && w1 < c1))) return;
             if (w0 > t0 || (w0 == t0 && w1 >= t1)) {
                 const uint32_t pos = atomicAdd(&nsel, 1u);
                 if (pos < (uint32_t)PPO_BEAM_MAX_K) { s_k0[pos] = w0; s_k1[pos] = w1; }
@@ -575,6 +587,10 @@ __global__ __launch_bounds__(BEAM_SELECT_THREADS) void k_beam_select(const float
         });
     }
     __syncthreads();
+    if (WINDOW && tid == 0) {
+        cv.win_count[s] = n;
+        if (n < PPO_BEAM_WINDOW) cv.exhausted[s] = 1;
+    }
     if (tid < n) {
         const unsigned long long w0 = s_k0[tid], w1 = s_k1[tid];
         int r = 0;
@@ -587,15 +603,29 @@ __global__ __launch_bounds__(BEAM_SELECT_THREADS) void k_beam_select(const float
         const unsigned long long frac = ((w0 & 0xFFFFFFFFull) << 20) | (w1 >> 28);
         const double mant = __longlong_as_double((long long)(0x3FE0000000000000ull | frac));
         const int ex = (int)((uint32_t)(w0 >> 32) ^ 0x80000000u);
+        if (WINDOW) {                                                    // the slots keep the parents' weights until the commit
+            const int64_t wi = s * PPO_BEAM_WINDOW + r;
+            cv.win_idx[wi] = idx; cv.win_m[wi] = mant; cv.win_e[wi] = ex;
+            if (r == n - 1) { cv.ceil[2 * s] = w0; cv.ceil[2 * s + 1] = w1; }
+            return;
+        }
         bv.wm[env0 + r] = mant; bv.we[env0 + r] = ex; bv.live[env0 + r] = 1;
         bv.sel_parent[env0 + r] = parent; bv.sel_action[env0 + r] = action;
         const int64_t li = (o * M + t) * K + r;
         if (bv.log_parent) { bv.log_parent[li] = (int16_t)parent; bv.log_action[li] = (int16_t)action; }
         if (bv.log_mant) bv.log_mant[li] = mant;
         if (bv.log_exp) bv.log_exp[li] = ex;
-    } else if (tid < K) {
+    } else if (!WINDOW && tid < K) {
         bv.live[env0 + tid] = 0; bv.sel_parent[env0 + tid] = -1; bv.sel_action[env0 + tid] = -1;
     }
+}
+__global__ __launch_bounds__(BEAM_SELECT_THREADS) void k_beam_select(const float* __restrict__ probs, BeamView bv, int K, int A, int64_t out_base,
+                                                     int M, int t) {
+    beam_select_body<false>(probs, bv, BeamChildView(), K, A, out_base, M, t);
+}
+__global__ __launch_bounds__(BEAM_SELECT_THREADS) void k_beam_select_window(const float* __restrict__ probs, BeamView bv, BeamChildView cv,
+                                                                            int K, int A) {
+    beam_select_body<true>(probs, bv, cv, K, A, 0, 0, 0);
 }
 
 // expand, one workgroup per start: gather -> step -> fold -> finish.
@@ -681,6 +711,206 @@ __global__ __launch_bounds__(256) void k_beam_expand(EnvView e, BeamView bv, int
     if (result_gap == 0 || t + 1 >= e.max_actions) {
         if (tid < K) { e.done[env0 + tid] = 1; e.episodes_left[env0 + tid] = 0; }
         if (tid == 0) bv.fin[s] = 1;
+    }
+}
+
+// ================================================================ the distinct beam
+// A 64-bit hash of a state's identity: `words` dwords (score, degree, then the active word).  It only filters: equal states
+// hash equally, and a full compare decides whether equal hashes are equal states
+__device__ __forceinline__ unsigned long long beam_hash_step(unsigned long long h, uint32_t w) {
+    h = (h ^ w) * 0x9E3779B97F4A7C15ull;
+    return h ^ (h >> 29);
+}
+
+// children, one workgroup of 256 threads per start: thread i forms the child of window entry i and decides whether the
+// sequential walk would accept it.
+//   gather   the window's parents (score, degree, active, steps) from the env arrays into row i of dynamic LDS,
+//            256 * (2V + 8) bytes.  The env arrays are only read: the parents stay there until the commit
+//   step     env_step_ref on the row (reward, done and tick are LDS scratch words), then the hash of the row's identity
+//   compare  behind a barrier, entry i is new iff no window entry j < i, no child accepted in an earlier round and -- mode 2
+//            -- no live parent holds the same state.  Comparing against EVERY earlier entry, accepted or not, is the
+//            sequential walk without its dependency chain: equality is transitive, so an entry that equals a rejected one
+//            equals whatever that one was rejected for.  Everything compared is written in front of the barrier or by an
+//            earlier launch, and nothing of it is written behind the barrier
+//   place    slot = accepted before the round + new entries before i (ballot and popcount in the wave, wave totals through
+//            LDS); slots < K go to the child buffer
+extern __shared__ __attribute__((aligned(16))) unsigned char beam_child_lds[];
+__global__ __launch_bounds__(256) void k_beam_children(EnvView e, BeamView bv, BeamChildView cv, int K, int mode) {
+    __shared__ unsigned long long s_hw[PPO_BEAM_WINDOW], s_ha[PPO_BEAM_MAX_K], s_hp[PPO_BEAM_MAX_K];
+    __shared__ uint32_t s_idx[PPO_BEAM_WINDOW], s_tick[PPO_BEAM_WINDOW], s_wt[4];
+    __shared__ float s_rew[PPO_BEAM_WINDOW];
+    __shared__ uint8_t s_done[PPO_BEAM_WINDOW], s_pl[PPO_BEAM_MAX_K];
+    const int tid = threadIdx.x, V = e.V, dv = V / 4, row = 2 * dv + 2, A = 16 * e.Q;
+    const int64_t s = blockIdx.x, env0 = s * K;
+    if (bv.fin[s]) return;
+    const int n_prev = cv.n[s], cnt = cv.win_count[s], ex_prev = cv.examined[s];
+    if (n_prev >= K || cnt <= 0) return;                                 // full, or no window that has not been read
+    uint32_t* rows = reinterpret_cast<uint32_t*>(beam_child_lds);        // [256][row]: score dv, degree dv, active, steps
+    if (tid < cnt) s_idx[tid] = cv.win_idx[s * PPO_BEAM_WINDOW + tid];
+    if (tid < n_prev) s_ha[tid] = cv.hash[env0 + tid];
+    if (tid < K) {
+        const bool lv = mode == 2 && bv.live[env0 + tid] != 0;
+        s_pl[tid] = lv ? 1 : 0;
+        if (lv) {
+            unsigned long long h = 0;
+            for (int d = 0; d < dv; ++d) h = beam_hash_step(h, reinterpret_cast<const uint32_t*>(e.score + (env0 + tid) * V)[d]);
+            for (int d = 0; d < dv; ++d) h = beam_hash_step(h, reinterpret_cast<const uint32_t*>(e.degree + (env0 + tid) * V)[d]);
+            s_hp[tid] = beam_hash_step(h, e.active[env0 + tid]);
+        }
+    }
+    __syncthreads();
+    // ---- gather
+    for (int i = tid; i < cnt * row; i += 256) {
+        const int c = i / row, d = i - c * row;
+        const int64_t pn = env0 + (int)(s_idx[c] / (uint32_t)A);
+        rows[i] = d < dv ? reinterpret_cast<const uint32_t*>(e.score + pn * V)[d]
+                : d < 2 * dv ? reinterpret_cast<const uint32_t*>(e.degree + pn * V)[d - dv]
+                : d == 2 * dv ? e.active[pn] : (uint32_t)e.steps[pn];
+    }
+    __syncthreads();
+    // ---- step
+    uint32_t* mine = rows + tid * row;
+    unsigned long long h = 0;
+    int gap = 0;
+    if (tid < cnt) {
+        s_rew[tid] = 0.0f; s_done[tid] = 0; s_tick[tid] = 0;
+        EnvRefLds er;
+        er.sc = (PPO_LDS int8_t*)mine; er.dg = (PPO_LDS int8_t*)(mine + dv);
+        er.active = (PPO_LDS uint32_t*)(mine + 2 * dv); er.steps = (PPO_LDS int32_t*)(mine + 2 * dv + 1);
+        er.reward = (PPO_LDS float*)&s_rew[tid]; er.done = (PPO_LDS uint8_t*)&s_done[tid];
+        er.episode = (PPO_LDS uint32_t*)&s_tick[tid]; er.tick = (PPO_LDS uint32_t*)&s_tick[tid];
+        float rew; uint8_t dn;
+        int score_after = 0;
+        const int errf = env_step_ref(const_of(e), er, (int)(s_idx[tid] % (uint32_t)A), rew, dn, &score_after);
+        if (errf) atomicOr(e.err, errf);
+        const int sum = env_total_sum(er.sc, *er.active, e.Q);
+        gap = score_after - (sum < 0 ? -sum : sum);
+        for (int d = 0; d <= 2 * dv; ++d) h = beam_hash_step(h, mine[d]);
+        s_hw[tid] = h;
+    }
+    __syncthreads();
+    // ---- compare: the hash filters, the bytes decide
+    bool is_new = tid < cnt;
+    if (is_new) {
+        for (int j = 0; j < tid && is_new; ++j) {
+            if (s_hw[j] != h) continue;
+            const uint32_t* other = rows + j * row;
+            bool eq = true;
+            for (int d = 0; d <= 2 * dv && eq; ++d) eq = other[d] == mine[d];
+            if (eq) is_new = false;
+        }
+        for (int j = 0; j < n_prev && is_new; ++j) {
+            if (s_ha[j] != h) continue;
+            const uint32_t* other = reinterpret_cast<const uint32_t*>(cv.state + (env0 + j) * 2 * V);
+            bool eq = cv.active[env0 + j] == mine[2 * dv];
+            for (int d = 0; d < 2 * dv && eq; ++d) eq = other[d] == mine[d];
+            if (eq) is_new = false;
+        }
+        for (int k = 0; k < K && is_new; ++k) {
+            if (!s_pl[k] || s_hp[k] != h) continue;
+            const uint32_t* osc = reinterpret_cast<const uint32_t*>(e.score + (env0 + k) * V);
+            const uint32_t* odg = reinterpret_cast<const uint32_t*>(e.degree + (env0 + k) * V);
+            bool eq = e.active[env0 + k] == mine[2 * dv];
+            for (int d = 0; d < dv && eq; ++d) eq = osc[d] == mine[d] && odg[d] == mine[dv + d];
+            if (eq) is_new = false;
+        }
+    }
+    // ---- place
+    const unsigned long long ballot = __ballot(is_new);
+    const int lane = tid & 63, wave = tid >> 6;
+    if (lane == 0) s_wt[wave] = (uint32_t)__popcll(ballot);
+    __syncthreads();
+    int before = __popcll(ballot & ((1ull << lane) - 1ull)), total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const int wt = (int)s_wt[w];
+        total += wt;
+        if (w < wave) before += wt;
+    }
+    const int slot = n_prev + before;
+    if (is_new && slot < K) {
+        const int64_t cn = env0 + slot;
+        uint32_t* dst = reinterpret_cast<uint32_t*>(cv.state + cn * 2 * V);
+        for (int d = 0; d < 2 * dv; ++d) dst[d] = mine[d];
+        cv.active[cn] = mine[2 * dv]; cv.steps[cn] = (int32_t)mine[2 * dv + 1]; cv.gap[cn] = gap; cv.hash[cn] = h;
+        cv.wm[cn] = cv.win_m[s * PPO_BEAM_WINDOW + tid]; cv.we[cn] = cv.win_e[s * PPO_BEAM_WINDOW + tid];
+        cv.parent[cn] = (int32_t)(s_idx[tid] / (uint32_t)A); cv.action[cn] = (int32_t)(s_idx[tid] % (uint32_t)A);
+        cv.rank[cn] = ex_prev + tid;
+        if (slot == K - 1) cv.examined[s] = ex_prev + tid + 1;           // the walk stops at K accepted
+    }
+    if (tid == 0) {
+        const int n_now = n_prev + total;
+        cv.n[s] = n_now < K ? n_now : K;
+        if (n_now < K) cv.examined[s] = ex_prev + cnt;
+        cv.win_count[s] = 0;
+    }
+}
+
+// commit, one workgroup per start, behind the last round of a step: the n accepted children become slots 0 .. n-1 (state,
+// active, steps, weight, live), slots n .. K-1 die, row t of the logs is written, then k_beam_expand's fold and finish -- the
+// finish also when nothing was accepted.  Last, the start's walk state is cleared for the next step.  The child buffer is
+// only read here and the env arrays are only written, so the copy needs no staging
+__global__ __launch_bounds__(256) void k_beam_commit(EnvView e, BeamView bv, BeamChildView cv, int K, int64_t out_base, int M, int t) {
+    __shared__ unsigned long long wave_min[4];
+    const int tid = threadIdx.x, V = e.V, dv = V / 4, row = 2 * dv;
+    const int64_t s = blockIdx.x, o = out_base + s, env0 = s * K;
+    if (bv.fin[s]) return;
+    const int n = cv.n[s], examined = cv.examined[s];
+    const int best_gap = bv.best_gap[o];                                 // read by everyone before the barrier below
+    for (int i = tid; i < n * row; i += 256) {
+        const int j = i / row, d = i - j * row;
+        const uint32_t w = reinterpret_cast<const uint32_t*>(cv.state + (env0 + j) * 2 * V)[d];
+        if (d < dv) reinterpret_cast<uint32_t*>(e.score + (env0 + j) * V)[d] = w;
+        else reinterpret_cast<uint32_t*>(e.degree + (env0 + j) * V)[d - dv] = w;
+    }
+    unsigned long long best = ~0ull;
+    if (tid < n) {
+        const int64_t nn = env0 + tid;
+        e.active[nn] = cv.active[nn]; e.steps[nn] = cv.steps[nn];
+        bv.wm[nn] = cv.wm[nn]; bv.we[nn] = cv.we[nn]; bv.live[nn] = 1;
+        const int64_t li = (o * M + t) * K + tid;
+        if (bv.log_parent) { bv.log_parent[li] = (int16_t)cv.parent[nn]; bv.log_action[li] = (int16_t)cv.action[nn]; }
+        if (bv.log_mant) bv.log_mant[li] = cv.wm[nn];
+        if (bv.log_exp) bv.log_exp[li] = cv.we[nn];
+        if (cv.log_rank) cv.log_rank[li] = cv.rank[nn];
+        best = ((unsigned long long)(uint32_t)cv.gap[nn] << 32) | (unsigned long long)(uint32_t)tid;
+    } else if (tid < K) {
+        bv.live[env0 + tid] = 0;
+    }
+    if (tid == 0 && cv.log_examined) cv.log_examined[o * M + t] = examined;
+    // ---- fold
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const uint32_t hi = __shfl_xor((uint32_t)(best >> 32), off), lo = __shfl_xor((uint32_t)best, off);
+        const unsigned long long other = ((unsigned long long)hi << 32) | lo;
+        best = other < best ? other : best;
+    }
+    if ((tid & 63) == 0) wave_min[tid >> 6] = best;
+    __syncthreads();
+    best = wave_min[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) best = wave_min[w] < best ? wave_min[w] : best;
+    int result_gap = best_gap;
+    if (best != ~0ull && (int)(uint32_t)(best >> 32) < best_gap) {
+        const int slot = (int)(uint32_t)best;
+        const int64_t wenv = env0 + slot;
+        result_gap = (int)(uint32_t)(best >> 32);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(bv.best_state + o * 2 * V);
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(cv.state + wenv * 2 * V);
+        for (int d = tid; d < row; d += 256) dst[d] = src[d];
+        if (tid == 0) {
+            bv.best_active[o] = cv.active[wenv]; bv.best_gap[o] = result_gap; bv.best_step[o] = t + 1; bv.best_beam[o] = slot;
+            bv.best_mant[o] = cv.wm[wenv]; bv.best_exp[o] = cv.we[wenv];
+        }
+    }
+    // ---- finish
+    if (result_gap == 0 || t + 1 >= e.max_actions || n == 0) {
+        if (tid < K) { e.done[env0 + tid] = 1; e.episodes_left[env0 + tid] = 0; }
+        if (tid == 0) bv.fin[s] = 1;
+    }
+    if (tid == 0) {
+        cv.n[s] = 0; cv.examined[s] = 0; cv.exhausted[s] = 0; cv.win_count[s] = 0;
+        cv.ceil[2 * s] = ~0ull; cv.ceil[2 * s + 1] = ~0ull;
     }
 }
 
@@ -975,6 +1205,44 @@ int32_t launch_beam_expand(ppo_env_s* e, const BeamView& bv, int64_t S, int64_t 
     }
     ProfScope ps("k_beam_expand");
     hipLaunchKernelGGL(k_beam_expand, dim3((unsigned)S), dim3(256), lds, ppo_stream(), view_of(e), bv, (int)K, out_base, (int)t);
+    HIP_TRY(hipGetLastError());
+    return PPO_OK;
+}
+
+int32_t launch_beam_select_window(ppo_env_s* e, const float* probs, const BeamView& bv, const BeamChildView& cv, int64_t S, int64_t K) {
+    PPO_TRY(beam_shape_ok(e, S, K));
+    ProfScope ps("k_beam_select_window");
+    hipLaunchKernelGGL(k_beam_select_window, dim3((unsigned)S), dim3(BEAM_SELECT_THREADS), 0, ppo_stream(), probs, bv, cv, (int)K,
+                       (int)e->A);
+    HIP_TRY(hipGetLastError());
+    return PPO_OK;
+}
+
+int32_t launch_beam_children(ppo_env_s* e, const BeamView& bv, const BeamChildView& cv, int64_t S, int64_t K, int32_t mode) {
+    PPO_TRY(beam_shape_ok(e, S, K));
+    if (e->V > BEAM_EXPAND_MAX_V || (mode != 1 && mode != 2)) {
+        ppo_set_error("beam_search: unsupported shape");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    // a row per window entry, whatever K is: k_beam_expand's budget at K = 256
+    const size_t lds = beam_expand_lds(PPO_BEAM_WINDOW, e->V);
+    static thread_local bool attr_set = false;
+    if (!attr_set) {
+        HIP_TRY(hipFuncSetAttribute((const void*)k_beam_children, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)beam_expand_lds(PPO_BEAM_WINDOW, BEAM_EXPAND_MAX_V)));
+        attr_set = true;
+    }
+    ProfScope ps("k_beam_children");
+    hipLaunchKernelGGL(k_beam_children, dim3((unsigned)S), dim3(256), lds, ppo_stream(), view_of(e), bv, cv, (int)K, (int)mode);
+    HIP_TRY(hipGetLastError());
+    return PPO_OK;
+}
+
+int32_t launch_beam_commit(ppo_env_s* e, const BeamView& bv, const BeamChildView& cv, int64_t S, int64_t K, int64_t out_base, int64_t t) {
+    PPO_TRY(beam_shape_ok(e, S, K));
+    ProfScope ps("k_beam_commit");
+    hipLaunchKernelGGL(k_beam_commit, dim3((unsigned)S), dim3(256), 0, ppo_stream(), view_of(e), bv, cv, (int)K, out_base,
+                       (int)e->max_actions, (int)t);
     HIP_TRY(hipGetLastError());
     return PPO_OK;
 }

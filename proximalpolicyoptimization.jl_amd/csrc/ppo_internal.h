@@ -384,6 +384,32 @@ int32_t launch_beam_init(ppo_env_s* e, const BeamView& bv, int64_t S, int64_t K,
 // the envs hold) into sel_*, the weights and row t of the log; then gather of the parents' states, env step, fold, finish
 int32_t launch_beam_select(ppo_env_s* e, const float* probs, const BeamView& bv, int64_t S, int64_t K, int64_t out_base, int64_t t);
 int32_t launch_beam_expand(ppo_env_s* e, const BeamView& bv, int64_t S, int64_t K, int64_t out_base, int64_t t);
+// the distinct beam: the parents stay in the env arrays through a step and the accepted children collect here
+constexpr int PPO_BEAM_WINDOW = 256;   // candidates per round: k_beam_children runs one thread per window entry
+constexpr int PPO_BEAM_MAX_ROUNDS = 16;
+struct BeamChildView {
+    // per slot [N]: the accepted children of the step
+    int8_t* state = nullptr;           // [N][2V] score, then degree
+    uint32_t* active = nullptr; int32_t* steps = nullptr; int32_t* gap = nullptr;
+    double* wm = nullptr; int32_t* we = nullptr;
+    int32_t* parent = nullptr; int32_t* action = nullptr; int32_t* rank = nullptr;
+    unsigned long long* hash = nullptr;
+    // per start [S]
+    int32_t* n = nullptr;              // accepted so far in this step
+    int32_t* examined = nullptr;       // candidates the walk has looked at
+    int32_t* exhausted = nullptr;      // the select found fewer than a full window: no candidate is left below the ceiling
+    int32_t* win_count = nullptr;      // entries of the window k_beam_children has not yet read
+    unsigned long long* ceil = nullptr;  // [S][2] beam_key's two words: the window takes keys strictly below it
+    // the window [S][PPO_BEAM_WINDOW], in rank order
+    uint32_t* win_idx = nullptr;       // parent * A + action
+    double* win_m = nullptr; int32_t* win_e = nullptr;
+    // logs [num_starts][max_actions][K] and [num_starts][max_actions], each on request
+    int32_t* log_rank = nullptr; int32_t* log_examined = nullptr;
+};
+// step t of the distinct beam: up to `rounds` times window + children, then one commit.  mode 1: "children", 2: "parents"
+int32_t launch_beam_select_window(ppo_env_s* e, const float* probs, const BeamView& bv, const BeamChildView& cv, int64_t S, int64_t K);
+int32_t launch_beam_children(ppo_env_s* e, const BeamView& bv, const BeamChildView& cv, int64_t S, int64_t K, int32_t mode);
+int32_t launch_beam_commit(ppo_env_s* e, const BeamView& bv, const BeamChildView& cv, int64_t S, int64_t K, int64_t out_base, int64_t t);
 // the refusals every value entry point shares: a bf16-dtype critic, an input width other than F (ppo_train.hip)
 extern "C" int32_t value_checks(const char* who, ppo_policy_s* critic, int32_t F);
 // teacher-forced replay: path m ([count][stride] 0-based actions, < 0 ends a path) from snapshot m (score[V]

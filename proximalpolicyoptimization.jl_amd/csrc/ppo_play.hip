@@ -520,15 +520,24 @@ int32_t ppo_search_resample_states_value(ppo_policy_t pol, ppo_policy_t critic, 
 // every 8 steps, play_quotas' poll, and nothing else crosses in the loop.  No reset! runs, nothing is sampled, the envs' ticks
 // and episode counters stay (the step bumps a scratch tick).  The path is walked on the host from the back-pointer log, which
 // comes back in one copy behind the last round
-int32_t ppo_beam_search_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
-                               const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
-                               uint32_t* best_active, int32_t* best_gap, int32_t* best_beam, int32_t* best_step,
-                               int32_t* initial_gap, double* best_mant, int32_t* best_exp, int16_t* path_or_null,
-                               int16_t* log_parent_or_null, int16_t* log_action_or_null, double* log_mant_or_null,
-                               int32_t* log_exp_or_null) {
+//
+// The distinct beam (distinct_mode 1 "children", 2 "parents") replaces select and expand by up to `rounds` rounds
+// of k_beam_select_window + k_beam_children and one k_beam_commit: the parents stay in the env arrays through the step and the
+// accepted children collect in a child buffer of the call.  The rounds of a step are enqueued without a look at the device: a
+// start that is full or has run out of candidates costs workgroups that return at once
+static int32_t beam_impl(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
+                         const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
+                         uint32_t* best_active, int32_t* best_gap, int32_t* best_beam, int32_t* best_step,
+                         int32_t* initial_gap, double* best_mant, int32_t* best_exp, int16_t* path_or_null,
+                         int16_t* log_parent_or_null, int16_t* log_action_or_null, double* log_mant_or_null,
+                         int32_t* log_exp_or_null, int32_t distinct_mode, int32_t rounds, int32_t* log_rank_or_null,
+                         int32_t* examined_or_null) {
     const std::string who = "beam_search_states";
     ARG_CHECK(score && degree && active && best_state && best_active && best_gap && best_beam && best_step && initial_gap &&
               best_mant && best_exp, who + ": null argument");
+    ARG_CHECK(distinct_mode >= 0 && distinct_mode <= 2, who + ": distinct must be 0 (off), 1 (children) or 2 (parents)");
+    ARG_CHECK(distinct_mode == 0 || (rounds >= 1 && rounds <= PPO_BEAM_MAX_ROUNDS), who + ": need 1 <= rounds <= 16");
+    ARG_CHECK(distinct_mode != 0 || (!log_rank_or_null && !examined_or_null), who + ": rank and examined are logs of a distinct call");
     PPO_TRY(check_shapes(scratch, env, pol));
     const int64_t N = env->N, Mst = num_starts;
     ARG_CHECK(Mst >= 1 && K >= 1 && K <= N, who + ": need num_starts >= 1 and 1 <= K <= N");
@@ -584,17 +593,54 @@ int32_t ppo_beam_search_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t s
         HIP_TRY(hipMemsetAsync(d_lexp.p, 0, log_len * 4, stream));
         bv.log_exp = d_lexp.p;
     }
+    // the distinct beam's child buffer, walk state and window
+    BeamChildView cv;
+    DevBuf<int8_t> c_state; DevBuf<double> c_dbl; DevBuf<int32_t> c_ints, c_lrank, c_lex; DevBuf<uint32_t> c_u32;
+    DevBuf<unsigned long long> c_u64;
+    const size_t Ns = (size_t)N, Ss = (size_t)S, Ws = Ss * PPO_BEAM_WINDOW;
+    if (distinct_mode) {
+        PPO_TRY(c_state.alloc(Ns * 2 * V)); PPO_TRY(c_dbl.alloc(Ns + Ws)); PPO_TRY(c_u32.alloc(Ns + Ws));
+        PPO_TRY(c_ints.alloc(6 * Ns + 4 * Ss + Ws)); PPO_TRY(c_u64.alloc(Ns + 2 * Ss));
+        cv.state = c_state.p; cv.wm = c_dbl.p; cv.win_m = c_dbl.p + Ns; cv.active = c_u32.p; cv.win_idx = c_u32.p + Ns;
+        cv.steps = c_ints.p; cv.gap = c_ints.p + Ns; cv.we = c_ints.p + 2 * Ns; cv.parent = c_ints.p + 3 * Ns;
+        cv.action = c_ints.p + 4 * Ns; cv.rank = c_ints.p + 5 * Ns;
+        cv.n = c_ints.p + 6 * Ns; cv.examined = cv.n + Ss; cv.exhausted = cv.n + 2 * Ss; cv.win_count = cv.n + 3 * Ss;
+        cv.win_e = cv.n + 4 * Ss;
+        cv.hash = c_u64.p; cv.ceil = c_u64.p + Ns;
+        if (log_rank_or_null) {                                          // -1: a dead slot, a step that did not run
+            PPO_TRY(c_lrank.alloc(log_len));
+            HIP_TRY(hipMemsetAsync(c_lrank.p, 0xFF, log_len * 4, stream));
+            cv.log_rank = c_lrank.p;
+        }
+        if (examined_or_null) {
+            PPO_TRY(c_lex.alloc(Ms * (size_t)M));
+            HIP_TRY(hipMemsetAsync(c_lex.p, 0xFF, Ms * (size_t)M * 4, stream));
+            cv.log_examined = c_lex.p;
+        }
+    }
     std::vector<int32_t> fin;
     for (int64_t base = 0; base < Mst; base += S) {
         const int64_t Sr = std::min(S, Mst - base);
         PPO_TRY(launch_env_load_starts(env, start.d_start.p + (size_t)base * 2 * V, start.d_act.p + base, Sr * K, K, load_t_in));
         PPO_TRY(launch_beam_init(env, bv, Sr, K, start.d_start.p, start.d_act.p, base));
+        if (distinct_mode) {                                             // an empty walk and the highest ceiling; the commit restores them
+            HIP_TRY(hipMemsetAsync(cv.n, 0, 4 * Ss * sizeof(int32_t), stream));
+            HIP_TRY(hipMemsetAsync(cv.ceil, 0xFF, 2 * Ss * sizeof(unsigned long long), stream));
+        }
         bool all = false;
         for (int64_t t = 0; t < M && !all; ++t) {
             PPO_TRY(launch_env_observe(env, scratch->states.p, scratch->active.p));
             PPO_TRY(launch_policy_probs(pol, scratch->states.p, scratch->active.p, N, env->H, d_probs.p));
-            PPO_TRY(launch_beam_select(env, d_probs.p, bv, Sr, K, base, t));
-            PPO_TRY(launch_beam_expand(env, bv, Sr, K, base, t));
+            if (distinct_mode) {
+                for (int32_t r = 0; r < rounds; ++r) {
+                    PPO_TRY(launch_beam_select_window(env, d_probs.p, bv, cv, Sr, K));
+                    PPO_TRY(launch_beam_children(env, bv, cv, Sr, K, distinct_mode));
+                }
+                PPO_TRY(launch_beam_commit(env, bv, cv, Sr, K, base, t));
+            } else {
+                PPO_TRY(launch_beam_select(env, d_probs.p, bv, Sr, K, base, t));
+                PPO_TRY(launch_beam_expand(env, bv, Sr, K, base, t));
+            }
             if (poll_due(t, M)) {
                 fin.resize((size_t)Sr);
                 PPO_TRY(d2h(fin.data(), bv.fin, (size_t)Sr));
@@ -609,6 +655,8 @@ int32_t ppo_beam_search_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t s
     PPO_TRY(d2h(initial_gap, bv.initial_gap, Ms)); PPO_TRY(d2h(best_mant, d_bmant.p, Ms)); PPO_TRY(d2h(best_exp, bv.best_exp, Ms));
     if (log_mant_or_null) PPO_TRY(d2h(log_mant_or_null, d_lmant.p, log_len));
     if (log_exp_or_null) PPO_TRY(d2h(log_exp_or_null, d_lexp.p, log_len));
+    if (log_rank_or_null) PPO_TRY(d2h(log_rank_or_null, c_lrank.p, log_len));
+    if (examined_or_null) PPO_TRY(d2h(examined_or_null, c_lex.p, Ms * (size_t)M));
     if (path_or_null || log_parent_or_null || log_action_or_null) {
         std::vector<int16_t> log(2 * log_len);
         PPO_TRY(d2h(log.data(), d_log.p, 2 * log_len));
@@ -628,6 +676,29 @@ int32_t ppo_beam_search_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t s
         }
     }
     return ppo_env_check_errors(env, nullptr);
+}
+
+int32_t ppo_beam_search_states(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
+                               const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
+                               uint32_t* best_active, int32_t* best_gap, int32_t* best_beam, int32_t* best_step,
+                               int32_t* initial_gap, double* best_mant, int32_t* best_exp, int16_t* path_or_null,
+                               int16_t* log_parent_or_null, int16_t* log_action_or_null, double* log_mant_or_null,
+                               int32_t* log_exp_or_null) {
+    return beam_impl(pol, env, scratch, num_starts, K, score, degree, active, best_state, best_active, best_gap, best_beam,
+                     best_step, initial_gap, best_mant, best_exp, path_or_null, log_parent_or_null, log_action_or_null,
+                     log_mant_or_null, log_exp_or_null, 0, 0, nullptr, nullptr);
+}
+
+int32_t ppo_beam_search_states_distinct(ppo_policy_t pol, ppo_env_t env, ppo_rollouts_t scratch, int64_t num_starts, int64_t K,
+                                        const int8_t* score, const int8_t* degree, const uint32_t* active, int8_t* best_state,
+                                        uint32_t* best_active, int32_t* best_gap, int32_t* best_beam, int32_t* best_step,
+                                        int32_t* initial_gap, double* best_mant, int32_t* best_exp, int16_t* path_or_null,
+                                        int16_t* log_parent_or_null, int16_t* log_action_or_null, double* log_mant_or_null,
+                                        int32_t* log_exp_or_null, int32_t distinct_mode, int32_t rounds,
+                                        int32_t* log_rank_or_null, int32_t* examined_or_null) {
+    return beam_impl(pol, env, scratch, num_starts, K, score, degree, active, best_state, best_active, best_gap, best_beam,
+                     best_step, initial_gap, best_mant, best_exp, path_or_null, log_parent_or_null, log_action_or_null,
+                     log_mant_or_null, log_exp_or_null, distinct_mode, rounds, log_rank_or_null, examined_or_null);
 }
 
 // ================================================================ teacher-forced replay and collection
