@@ -100,12 +100,9 @@ struct ppo_env_s {
 // row-major dZ2 tile; else feature 8g + 2e + hh against a feature-major tile, one ds_read_b32 per MFMA (round-1 form).
 // Measured (gpurun_out/r2x, alternating): HID = 128 backward 0.1170 -> 0.1156 ms with the row form; at HID = 256 it is
 // 0.3 % SLOWER (0.3423 -> 0.3432: LDS instructions beside an fp32 MFMA are not what that kernel waits for, and phase C
-// then needs four 4-byte reads per A operand), so the row form is used up to this width only.  Shared by ppo_optim.hip
-// (packing), ppo_policy_bwd.hip and ppo_policy_bwd_small.hip.
-#ifndef PPO_BWD_Z2ROW_MAX_HID
-#define PPO_BWD_Z2ROW_MAX_HID 128
-#endif
-#define PPO_BWD_Z2ROW_AT(HID) ((HID) <= PPO_BWD_Z2ROW_MAX_HID)
+// then needs four 4-byte reads per A operand), so the row form is used up to HID = 128 only.  Shared by ppo_optim.hip
+// (packing), ppo_policy_bwd.hip, ppo_policy_bwd_small.hip and ppo_policy_train_tile.hip.
+#define PPO_BWD_Z2ROW_AT(HID) ((HID) <= 128)
 
 struct ppo_policy_s {
     int32_t F, HID, L, OUT;            // HID: the width the kernels run (128 or 256); L = hidden layers (test/policy.jl:9-19):

@@ -25,56 +25,10 @@
 #include "ppo_policy_tail.h"
 #include "ppo_env_device.h"
 
-#ifndef PPO_BF16_ACT_NT
-#define PPO_BF16_ACT_NT 1
-#endif
-#ifndef PPO_BF16_TMPL_LDS
-#define PPO_BF16_TMPL_LDS 1
-#endif
-#ifndef PPO_BF16_RING_SPREAD
-#define PPO_BF16_RING_SPREAD 1
-#endif
-#ifndef PPO_BF16_STORE_LATE
-#define PPO_BF16_STORE_LATE 1
-#endif
-#ifndef PPO_BF16_ACT_NT_LOAD
-#define PPO_BF16_ACT_NT_LOAD 1
-#endif
-// dW1 += dZ1^T X inside k_policy_bwd_bf16 (NI more accumulator tiles per feature tile of the wave; the dZ1 / X operand
-// fragments never leave the CU) where the registers allow it: HID = 128 (168 + 112 registers, no scratch).  At HID = 256
-// the wave already holds 256 dW2 accumulator registers and a 236-register working set: with the 96 dW1 registers hipcc
-// spills 67 (268 B of scratch per lane), so that width keeps the round-1 form: fragments to HBM + k_policy_dw1_bf16.
-#ifndef PPO_BF16_DW1_FUSED_MAX_HID
-#define PPO_BF16_DW1_FUSED_MAX_HID 128
-#endif
-#define PPO_BF16_DW1_FUSED (HID <= PPO_BF16_DW1_FUSED_MAX_HID)
 // The backward kernel recomputes H1 = lrelu(W1 X + b1) of its feature tiles (KS1 MFMAs per tile from the 2.3 KB of
 // state rows + L2-resident W1 fragments) instead of reading what the train forward saved: 16 KB per tile less written
 // by the forward and 16 KB less read here -- a third of the training step's HBM bytes.  Same operand order as the
 // forward, so the recomputed tile is bit-identical to the one that was saved.
-#ifndef PPO_BF16_H1_RECOMPUTE
-#define PPO_BF16_H1_RECOMPUTE 1
-#endif
-// Where dW1 is NOT accumulated in the backward kernel (HID = 256), the two wave-private transposes -- H2 for the dW3 sums,
-// dZ1 for the fragments handed to k_policy_dw1_bf16 -- run as identity MFMAs on the (70 % idle) matrix pipe instead of an LDS
-// image write + transposed read: D = P * I puts the rows of the lane-is-row fragment P on the accumulator registers of
-// the lane that owns the feature.  No H2 / dZ1 image: 18 KB of LDS back (two more resident W2^T k-steps).
-#ifndef PPO_BF16_MFMA_TRANSPOSE
-#define PPO_BF16_MFMA_TRANSPOSE 1
-#endif
-// identity-MFMA form: the dH1 epilogue in front of phase C (0) or inside it, two accumulator registers behind the dW2 MFMAs
-// of each k-tile (1).  Measured 2 % SLOWER (0.940 -> 0.958 ms at 65,536 states, gpurun_out/r2b14, r2b15; with and without
-// scheduling pins): unlike the forward's chains, phase C already overlaps its transposed reads with its MFMAs, and
-// carrying the dH1 accumulator through it costs more than the vector work it hides.  Kept as an A/B switch.
-#ifndef PPO_BF16_BWD_EPI_IN_C
-#define PPO_BF16_BWD_EPI_IN_C 0
-#endif
-#ifndef PPO_BF16_BWD_DL8
-#define PPO_BF16_BWD_DL8 2            // LDS operand queue depth of the dH1 chain in the 8-wave form (the partner wave covers the rest)
-#endif
-#ifndef PPO_BF16_BWD_WAVES
-#define PPO_BF16_BWD_WAVES 8          // waves per backward workgroup at HID = 256 (4 = one per SIMD, the round-1 form)
-#endif
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -104,32 +58,16 @@ __device__ __forceinline__ float slope_hi(uint32_t d) { return (int32_t)d >= 0x1
 // churning the L2 (same as the fp32 forward kernel)
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void act_store_nt_u4(uint4* p, const uint4& v) {
-#if PPO_BF16_ACT_NT
     const u32x4 t = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(t, reinterpret_cast<u32x4*>(p));
-#else
-    *p = v;
-#endif
 }
 __device__ __forceinline__ uint32_t dw(const uint4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
 
 // ================================================================ forward
-// waves per forward workgroup (one workgroup per CU: W2 takes 128 KiB of its LDS): 8 = two per SIMD with 256 registers,
-// 12 = three per SIMD with 168
-#ifndef PPO_BF16_FWD_WQ
-#define PPO_BF16_FWD_WQ 4             // W2 fragments in flight (LDS -> registers) ahead of the layer-2 MFMAs
-#endif
-// layer-2 epilogues software-pipelined into the next feature tile's MFMA chain: 1 = where the second accumulator costs at
-// most 4 registers of scratch (every H = 32 instantiation -- the persistent rollout and the compact-source forward spill
-// 16 bytes and still gain 4-6 % -- and the H = 128 ones without a loss tail), 2 = everywhere (A/B), 0 = off
-#ifndef PPO_BF16_FWD_PIPE
-#define PPO_BF16_FWD_PIPE 1
-#endif
-#ifndef PPO_BF16_FWD_WAVES
-#define PPO_BF16_FWD_WAVES 8
-#endif
-#define FWB_W PPO_BF16_FWD_WAVES
-#define FWB_T (PPO_BF16_FWD_WAVES * 64)
+// waves per forward workgroup (one workgroup per CU: W2 takes 128 KiB of its LDS): 8 = two per SIMD with 256 registers
+// (12 would be three per SIMD with 168)
+constexpr int FWB_W = 8, FWB_T = FWB_W * 64;
+constexpr int FWB_WQ = 4;             // W2 fragments in flight (LDS -> registers) ahead of the layer-2 MFMAs
 template <int F, int HID>
 struct FwdB {
     static constexpr int NT = HID / 32, NS = HID / 16, KS1 = (F + 15) / 16;
@@ -192,7 +130,6 @@ __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs 
         r.done = (PPO_LDS uint8_t*)(ww + 3); r.episode = ww + 4; r.tick = ww + 5;
         return r;
     };
-    uint32_t tmpl_regs[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (PERSIST) {
         ec.Q = a.envQ; ec.V = a.envV; ec.max_actions = a.env_max_actions; ec.no_action_reward = a.env_nar; ec.k0 = a.k0; ec.k1 = a.k1;
         int slot = 0;
@@ -207,17 +144,11 @@ __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs 
     }
     if (OBS) {
         if (TPS == 1) {
-#if PPO_BF16_TMPL_LDS
             // the 32 template rows (36 ids each) sit behind the env slots in LDS: nine registers less to carry through
             // the tile loop (they spilled, and every scratch reload waits on vmcnt behind the rollout-column stores)
             uint32_t* tl = reinterpret_cast<uint32_t*>(env_lds + (size_t)FWB_W * a.env_slots * slot_bytes);
             for (int i = tid; i < 32 * PPO_TPL / 4; i += FWB_T) tl[i] = reinterpret_cast<const uint32_t*>(a.env_tmpl)[i];
             __syncthreads();
-#else
-            const uint32_t* tp = reinterpret_cast<const uint32_t*>(a.env_tmpl + j * PPO_TPL);
-#pragma unroll
-            for (int k = 0; k < 9; ++k) tmpl_regs[k] = tp[k];
-#endif
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
@@ -253,7 +184,7 @@ __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs 
 #pragma unroll
         for (int tt = 0; tt < TPS; ++tt) l[tt][0] = l[tt][1] = l[tt][2] = l[tt][3] = 0.0f;
         TailPre tpre = {0, 0.0f, 0.0f};
-        if (TRAIN && PPO_BF16_STORE_LATE) { tpre.ab = a.actions[sid]; tpre.po = a.p_old[sid]; tpre.adv = a.adv[sid]; }
+        if (TRAIN) { tpre.ab = a.actions[sid]; tpre.po = a.p_old[sid]; tpre.adv = a.adv[sid]; }
 #pragma unroll 1
         for (int ts = 0; ts < TPS; ++ts) {
             const int64_t tile = state * TPS + ts;
@@ -264,13 +195,9 @@ __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs 
                 static_assert(!OBS || F == 72, "the built-in env has F = 72 features");
                 uint32_t tid9[9];
                 if (TPS == 1) {
-#pragma unroll
-                    for (int k = 0; k < 9; ++k) tid9[k] = tmpl_regs[k];
-#if PPO_BF16_TMPL_LDS
                     const uint32_t* tl = reinterpret_cast<const uint32_t*>(env_lds + (size_t)FWB_W * a.env_slots * slot_bytes) + j * (PPO_TPL / 4);
 #pragma unroll
                     for (int k = 0; k < 9; ++k) tid9[k] = tl[k];
-#endif
                 } else {
                     const uint32_t* tp = reinterpret_cast<const uint32_t*>(a.env_tmpl + (32 * ts + j) * PPO_TPL);
 #pragma unroll
@@ -353,8 +280,8 @@ __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs 
                     if (p4 & 1) { h1p[o][p4 >> 1].z = d0; h1p[o][p4 >> 1].w = d1; }
                     else        { h1p[o][p4 >> 1].x = d0; h1p[o][p4 >> 1].y = d1; }
                 };
-                static_assert(PPO_BF16_STORE_LATE, "the layer-1 stores leave behind the loop");
-                if constexpr (PPO_BF16_FWD_PIPE && KS1 >= 4) {
+                static_assert(KS1 >= 4, "a tile's chain covers the four epilogue pieces of the tile before it");
+                {
                     // the epilogue of tile o in four pieces behind the first four MFMAs of tile o + 1 (a bf16 MFMA leaves the
                     // vector ALU free for the 32 clocks it occupies the matrix pipe)
                     f32x16 accs[2];
@@ -375,22 +302,11 @@ __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs 
 #pragma unroll
                     for (int p4 = 0; p4 < 4; ++p4) epi1(accs[(NT - 1) & 1], NT - 1, p4);
                     __builtin_amdgcn_sched_barrier(0);
-                } else {
-#pragma unroll
-                for (int o = 0; o < NT; ++o) {
-                    f32x16 acc;
-                    bias1(acc, o);
-#pragma unroll
-                    for (int s = 0; s < KS1; ++s) step1(acc, o, s);
-#pragma unroll
-                    for (int p4 = 0; p4 < 4; ++p4) epi1(acc, o, p4);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
                 }
                 // saved layer-1 activations leave AFTER the last W1 fragment has been waited for: loads and stores share
                 // the in-order vmcnt queue, so a store between two ring loads puts its HBM round trip on the MFMA chain
                 // (layer 2 takes its operands from LDS and never waits on vmcnt)
-                if (TRAIN && PPO_BF16_STORE_LATE && a.act1b) {        // (null: the backward kernel recomputes H1)
+                if (TRAIN && a.act1b) {                               // (null, as launch_policy_fwd_bf16 passes it: the backward kernel recomputes H1)
 #pragma unroll
                     for (int o = 0; o < NT; ++o) {
                         act_store_nt_u4(a.act1b + ((size_t)tile * NT + o) * 128 + lane, h1p[o][0]);
@@ -407,7 +323,7 @@ __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs 
             // feature tiles (left alone hipcc keeps two fragments in flight and waits for each one a single 32-clock MFMA
             // after issuing its read; sched_barrier pins the order).  The last tile's look-ahead reads the first
             // fragments of what follows W2 in LDS (W3 / bias packs: in bounds, never used).
-            constexpr int WQ = (SNAPX && TPS == 4) ? 2 : PPO_BF16_FWD_WQ;      // (that instantiation has no registers to spare)
+            constexpr int WQ = (SNAPX && TPS == 4) ? 2 : FWB_WQ;               // (that instantiation has no registers to spare)
             uint4 wq[WQ];
 #pragma unroll
             for (int k = 0; k < WQ; ++k) wq[k] = sW2[k * 64 + lane];
@@ -454,7 +370,9 @@ __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs 
                 }
             };
             // (one epilogue slice per k-step: the interleaved form needs 16 of each, i.e. HID = 256)
-            constexpr bool PIPE2 = PPO_BF16_FWD_PIPE && (NT % 2 == 0) && (NS == 16) && (TPS == 1 || SRC == FwdSource::Rows || PPO_BF16_FWD_PIPE > 1);
+            // and only where the second accumulator costs at most 4 registers of scratch: every H = 32 instantiation (the persistent
+            // rollout and the compact-source forward spill 16 bytes and still gain 4-6 %) and the H = 128 ones without a loss tail
+            constexpr bool PIPE2 = (NT % 2 == 0) && (NS == 16) && (TPS == 1 || SRC == FwdSource::Rows);
             if constexpr (PIPE2) {
                 f32x16 acc0, acc1;
                 bias_init(acc0, 0);
@@ -496,7 +414,7 @@ __global__ __launch_bounds__(FWB_T, (FWB_W / 4)) void k_policy_fwd_bf16(FwdArgs 
                 for (int i = 0; i < 4; ++i) l[tt][i] = (tt == ts) ? lg[i] : l[tt][i];
         }
         const int sampled = policy_tail<TAIL, TPS, true>(a, state, sid, act, l, lane, j, h, tick_val, out_index,
-                                                          (TRAIN && PPO_BF16_STORE_LATE) ? &tpre : nullptr);
+                                                          TRAIN ? &tpre : nullptr);
         FBSTAMP(4);
         if (PERSIST) {
             asm volatile("" ::: "memory");
@@ -568,7 +486,7 @@ static int32_t dispatch_fwd_bf16(ppo_policy_s* p, const FwdArgs& args, int64_t B
     do {                                                                                                             \
         /* TrainSnap: one env-snapshot slot per wave + the template rows behind them */                               \
         /* + the W2 queue's look-ahead past the last feature tile (the persistent form's env slots cover it there) */ \
-        const size_t lds = FwdB<FF, HH>::lds_bytes + PPO_BF16_FWD_WQ * 1024 + (MODE == FwdMode::TrainSnap ? (size_t)FWB_W * (2 * args.envV + 32) + 32 * PPO_TPL : 0); \
+        const size_t lds = FwdB<FF, HH>::lds_bytes + FWB_WQ * 1024 + (MODE == FwdMode::TrainSnap ? (size_t)FWB_W * (2 * args.envV + 32) + 32 * PPO_TPL : 0); \
         static thread_local size_t attr_lds = 0;                                                                                  \
         if (lds > attr_lds) {                                                                                        \
             HIP_TRY(hipFuncSetAttribute((const void*)k_policy_fwd_bf16<FF, HH, MODE, TT>,                            \
@@ -598,11 +516,11 @@ int32_t launch_policy_rollout_persistent_bf16(ppo_policy_s* p, FwdArgs& a, int64
     const size_t env_bytes = (size_t)FWB_W * slots * (2 * V + 32) + 32 * PPO_TPL;  // env slots + the template rows
 #define LAUNCHP(HH, TT)                                                                                              \
     do {                                                                                                             \
-        /* the W2 queue's look-ahead past the last feature tile needs PPO_BF16_FWD_WQ KiB behind W2: env slots cover it, */ \
+        /* the W2 queue's look-ahead past the last feature tile needs FWB_WQ KiB behind W2: env slots cover it, */ \
         /* few of them are topped up */                                                                              \
         size_t lds = FwdB<72, HH>::lds_bytes + env_bytes;                                                            \
         if (lds > 160 * 1024) return PPO_ERR_UNSUPPORTED;                                                            \
-        lds = std::max(lds, (size_t)FwdB<72, HH>::W2_U4 * 16 + PPO_BF16_FWD_WQ * 1024);                              \
+        lds = std::max(lds, (size_t)FwdB<72, HH>::W2_U4 * 16 + FWB_WQ * 1024);                              \
         static thread_local size_t attr_lds = 0;                                                                                  \
         if (lds > attr_lds) {                                                                                        \
             HIP_TRY(hipFuncSetAttribute((const void*)k_policy_fwd_bf16<72, HH, FwdMode::Persistent, TT>,                               \
@@ -621,7 +539,7 @@ int32_t launch_policy_rollout_persistent_bf16(ppo_policy_s* p, FwdArgs& a, int64
 
 int32_t launch_policy_fwd_bf16(ppo_policy_s* p, FwdArgs& a, FwdMode mode, int64_t B, int tps) {
     a.w1b = (const uint4*)p->w1b.p; a.w2b = (const uint4*)p->w2b.p; a.w3c = (const uint4*)p->w3c.p;
-    a.act1b = PPO_BF16_H1_RECOMPUTE ? nullptr : (uint4*)p->act1.p; a.act2b = (uint4*)p->act2.p;
+    a.act1b = nullptr; a.act2b = (uint4*)p->act2.p;      // no saved H1: the backward kernel recomputes it
     if (mode == FwdMode::Probs) return dispatch_fwd_bf16<FwdMode::Probs>(p, a, B, tps);
     if (mode == FwdMode::Sample) return dispatch_fwd_bf16<FwdMode::Sample>(p, a, B, tps);
     if (mode == FwdMode::TrainSnap) return dispatch_fwd_bf16<FwdMode::TrainSnap>(p, a, B, tps);
@@ -634,10 +552,12 @@ struct BwdBArgs {
     int tps_shift;                                          // tiles per state = 1 << tps_shift (H = 32 or 128)
     int x_by_tile;                                          // 1: `states` is the forward's row scratch in minibatch order (compact rollouts)
     int nwg;                                                // == gridDim.x (as an argument: no dispatch-packet reload in the loop)
-    const uint4* act1b; const uint4* act2b; const float4* dY;
+    const uint4* act2b; const float4* dY;
     const uint4* w2tb; const uint2* w3tb;
     const uint4* w1b; const float4* b1p;                    // layer-1 fragments / bias pack (H1 recomputed here)
-    uint4* z1f; uint4* xf;                                  // operand fragments handed to k_policy_dw1_bf16
+    uint4* z1f;                                             // dZ1^T operand fragments handed to k_policy_dw1_bf16
+    uint4* unused_xf;                                       // no kernel reads it and nothing fills it (the dW1 kernel builds its X operands from
+                                                            // the state rows): it keeps the offsets below, see profiles/build_knobs_code_identity.txt
     float* slabs; size_t slab_stride;
     unsigned long long* stamps;                             // diagnostic build only (-DPPO_BF16_STAMP)
 };
@@ -660,8 +580,9 @@ struct BwdB {
     static constexpr int NT = HID / 32, NS = HID / 16, FP = ((F + 31) / 32) * 32, NI = FP / 32;
     // waves per workgroup and feature tiles per wave.  HID = 256: 8 waves, two per SIMD, one feature tile each (128 dW2
     // accumulator registers + a working set that fits the other 128 now that only 4 k-steps of W2^T stream through
-    // registers): the partner wave covers the LDS / L2 round trips a single wave per SIMD sat through
-    static constexpr int NW = (HID >= 256) ? PPO_BF16_BWD_WAVES : 4, FT = NT / NW;
+    // registers): the partner wave covers the LDS / L2 round trips a single wave per SIMD sat through (round 1 ran 4 waves,
+    // one per SIMD, with two feature tiles each)
+    static constexpr int NW = (HID >= 256) ? 8 : 4, FT = NT / NW;
     static_assert(NT % NW == 0, "feature tiles per wave");
     static constexpr int ST = 2 * HID + 64;               // image row stride (bytes): 16 dwords mod 64 -> the 4 rows of a
     static constexpr int STX = 2 * FP;                    //   transposed-read block sit on different bank quarters
@@ -669,10 +590,18 @@ struct BwdB {
     static_assert((STX / 4) % 64 == 16 || (STX / 4) % 64 == 48, "X image stride");
     static constexpr int IMG = 32 * ST;
     // k-steps of W2^T resident in LDS for the whole launch (the rest streams from L2 once per tile into a register ring):
-    // three images (dZ1 reuses the H2 image, see phase B) + the X image leave room for 12 of the 16 at HID = 256
-    static constexpr bool FUSE = (HID <= PPO_BF16_DW1_FUSED_MAX_HID);
-    static constexpr bool TRN = PPO_BF16_MFMA_TRANSPOSE && !FUSE;       // identity-MFMA transposes, no H2 / dZ1 image
-    static constexpr int NSL = (HID >= 256) ? (TRN ? 14 : 12) : NS, NSR = NS - NSL;
+    // two images and the layer-1 operands in the X image's place leave room for 14 of the 16 at HID = 256
+    // dW1 += dZ1^T X inside k_policy_bwd_bf16 (NI more accumulator tiles per feature tile of the wave; the dZ1 / X operand
+    // fragments never leave the CU) where the registers allow it: HID = 128 (168 + 112 registers, no scratch).  At HID = 256
+    // the wave already holds 256 dW2 accumulator registers and a 236-register working set: with the 96 dW1 registers hipcc
+    // spills 67 (268 B of scratch per lane), so that width keeps the round-1 form: fragments to HBM + k_policy_dw1_bf16.
+    static constexpr bool FUSE = (HID <= 128);
+    // Where dW1 is NOT accumulated in the backward kernel (HID = 256), the two wave-private transposes -- H2 for the dW3 sums,
+    // dZ1 for the fragments handed to k_policy_dw1_bf16 -- run as identity MFMAs on the (70 % idle) matrix pipe instead of an LDS
+    // image write + transposed read: D = P * I puts the rows of the lane-is-row fragment P on the accumulator registers of
+    // the lane that owns the feature.  No H2 / dZ1 image: 18 KB of LDS back (two more resident W2^T k-steps).
+    static constexpr bool TRN = !FUSE;
+    static constexpr int NSL = (HID >= 256) ? 14 : NS, NSR = NS - NSL;
     static constexpr int oZ2 = 0, oH1 = IMG, oH2 = 2 * IMG, oX = TRN ? 2 * IMG : 3 * IMG,
                          oDY = oX + 32 * STX, oDB3 = oDY + 512, oB1 = oDB3 + 512, oID = oB1 + NT * 128,
                          oW = oID + (TRN ? 2048 : 0), wEnd = oW + NT * NSL * 1024;
@@ -692,13 +621,9 @@ __device__ __forceinline__ uint4 ldg16(const void* sbase, unsigned voff) {
 // read-once streams (the saved activations in the backward pass): non-temporal, so they do not evict the W2^T
 // fragments and the dW1 operand fragments that ARE re-read
 __device__ __forceinline__ uint4 ldg16_nt(const void* sbase, unsigned voff) {
-#if PPO_BF16_ACT_NT_LOAD
     typedef uint32_t u32x4l __attribute__((ext_vector_type(4)));
     const u32x4l t = __builtin_nontemporal_load(reinterpret_cast<const u32x4l*>(reinterpret_cast<const char*>(sbase) + voff));
     return make_uint4(t.x, t.y, t.z, t.w);
-#else
-    return ldg16(sbase, voff);
-#endif
 }
 __device__ __forceinline__ float4 ldg16f(const void* sbase, unsigned voff) {
     return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(sbase) + voff);
@@ -737,11 +662,10 @@ __global__ __launch_bounds__((BwdB<F, HID>::NW * 64), 1) void k_policy_bwd_bf16(
     uint4* const sW = reinterpret_cast<uint4*>(smem_c + C::oW);
     float4* const sB1 = reinterpret_cast<float4*>(smem_c + C::oB1);
     u32x4* const sXF = reinterpret_cast<u32x4*>(smem_c + C::oXF);
-    constexpr bool RC1 = PPO_BF16_H1_RECOMPUTE;
     constexpr int KS1 = C::KS1;
     const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, h = lane >> 5;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    if (RC1) for (int i = tid; i < NT * 8; i += C::NW * 64) sB1[i] = a.b1p[i];
+    for (int i = tid; i < NT * 8; i += C::NW * 64) sB1[i] = a.b1p[i];
     constexpr bool TRN = C::TRN;
     // identity B operands of the transposing MFMAs: k-slot (step s, lane half hB, element e) carries feature
     // 16s + 8(e>>2) + 4hB + (e&3) of the packed fragment, so lane (n, hB) holds a single 1.0 -- in step n>>4, element
@@ -770,7 +694,7 @@ __global__ __launch_bounds__((BwdB<F, HID>::NW * 64), 1) void k_policy_bwd_bf16(
         for (int s = 0; s < NSL; ++s)
             sW[((w * FT + i) * NSL + s) * 64 + lane] = a.w2tb[((size_t)(w * FT + i) * NS + s) * 64 + lane];
 
-    constexpr bool FUSE1 = PPO_BF16_DW1_FUSED;
+    constexpr bool FUSE1 = C::FUSE;
     // the state rows are needed here only when dW1 is accumulated in this kernel (k_policy_dw1_bf16 stages its own)
     // zero the padded X image once (columns >= F are never written afterwards)
     if (FUSE1) for (int i = tid; i < 32 * STX / 4; i += NTHR) reinterpret_cast<uint32_t*>(imgX)[i] = 0u;
@@ -828,10 +752,10 @@ __global__ __launch_bounds__((BwdB<F, HID>::NW * 64), 1) void k_policy_bwd_bf16(
     }
 
     // next tile's inputs, fetched one tile ahead
-    uint4 nh2[FT][2], nh1[RC1 ? 1 : FT][2];
+    uint4 nh2[FT][2];
     float4 ndy;
     constexpr int KPW = (KS1 + C::NW - 1) / C::NW;          // layer-1 k-steps a wave converts: w, w + NW, ...
-    uint2 nxr[KPW];                                         // RC1: this lane's 8 state bytes of those k-steps
+    uint2 nxr[KPW];                                         // this lane's 8 state bytes of those k-steps
 #pragma unroll
     for (int q = 0; q < KPW; ++q) nxr[q] = make_uint2(0u, 0u);
     uint32_t nx[XPD];
@@ -881,7 +805,6 @@ __global__ __launch_bounds__((BwdB<F, HID>::NW * 64), 1) void k_policy_bwd_bf16(
         for (int i = 0; i < FT; ++i) {
             const size_t base = ((size_t)t * NT + (w * FT + i)) * 128;          // wave-uniform
             nh2[i][0] = ldg16_nt(a.act2b + base, lo16); nh2[i][1] = ldg16_nt(a.act2b + base + 64, lo16);
-            if constexpr (!RC1) { nh1[i][0] = ldg16_nt(a.act1b + base, lo16); nh1[i][1] = ldg16_nt(a.act1b + base + 64, lo16); }
         }
         ndy = ldg16f(a.dY + (size_t)t * 32, lo16 & 0x1F0u);                     // row j: (lane & 31) * 16 bytes
         if constexpr (FUSE1) {
@@ -895,17 +818,16 @@ __global__ __launch_bounds__((BwdB<F, HID>::NW * 64), 1) void k_policy_bwd_bf16(
     };
     // the same loads one at a time, to be spread between the MFMAs of phase B: issued in one burst they stall the wave
     // for ~1200 cycles (the CU's miss queue back-pressures the issue), and nothing overlaps.  Piece 0 is the state
-    // bytes (the first thing consumed: converted at the end of this tile's phase C), then H2 (and H1), dY, X image
-    constexpr int NPA = RC1 ? 2 * FT : 4 * FT;              // activation pieces
+    // bytes (the first thing consumed: converted at the end of this tile's phase C), then H2, dY, X image
+    constexpr int NPA = 2 * FT;                             // activation pieces
     constexpr int NPIECE = 1 + NPA + 2;
     auto prefetch_piece = [&](int k0, int t, int sidx) {
-        if (k0 == 0) { if constexpr (RC1) load_xraw(t, sidx); return; }
+        if (k0 == 0) { load_xraw(t, sidx); return; }
         const int k = k0 - 1;
         if (k < NPA) {
-            const int i = RC1 ? (k >> 1) : (k >> 2);
+            const int i = k >> 1;
             const size_t base = ((size_t)t * NT + (w * FT + i)) * 128 + ((k & 1) ? 64 : 0);
-            if (!RC1 && (k & 2)) nh1[RC1 ? 0 : i][k & 1] = ldg16_nt(a.act1b + base, lo16);
-            else                 nh2[i][k & 1] = ldg16_nt(a.act2b + base, lo16);
+            nh2[i][k & 1] = ldg16_nt(a.act2b + base, lo16);
         } else if (k == NPA) {
             ndy = ldg16f(a.dY + (size_t)t * 32, lo16 & 0x1F0u);                     // row j: (lane & 31) * 16 bytes
         } else if (FUSE1 && k == NPA + 1) {
@@ -917,24 +839,24 @@ __global__ __launch_bounds__((BwdB<F, HID>::NW * 64), 1) void k_policy_bwd_bf16(
             }
         }
     };
-    // RC1: this wave's W1 fragments (the same KS1 KiB every tile, L2-resident).  Fetched at the end of the previous tile --
+    // This wave's W1 fragments (the same KS1 KiB every tile, L2-resident).  Fetched at the end of the previous tile --
     // register pressure is lowest there -- so that the layer-1 chain at the top of phase A does not start with an L2
     // round trip (measured: +0.1 ms per 65,536 tiles when it did)
-    uint4 w1f[RC1 ? FT : 1][RC1 ? KS1 : 1];
+    uint4 w1f[FT][KS1];
     auto load_w1 = [&]() {
 #pragma unroll
         for (int i = 0; i < FT; ++i)
 #pragma unroll
-            for (int s1 = 0; s1 < KS1; ++s1) w1f[RC1 ? i : 0][RC1 ? s1 : 0] = ldg16(a.w1b + ((size_t)(w * FT + i) * KS1 + s1) * 64, lo16);
+            for (int s1 = 0; s1 < KS1; ++s1) w1f[i][s1] = ldg16(a.w1b + ((size_t)(w * FT + i) * KS1 + s1) * 64, lo16);
     };
-    if constexpr (RC1) load_w1();
+    load_w1();
     auto tile_or_last = [&](int t) { return t < a.B ? t : a.B - 1; };
     int idx_next = 0;
     if ((int)blockIdx.x < a.B) {
-        const int sidx0 = (FUSE1 || RC1) && !a.x_by_tile ? a.idx[(int)blockIdx.x >> a.tps_shift] : 0;
+        const int sidx0 = !a.x_by_tile ? a.idx[(int)blockIdx.x >> a.tps_shift] : 0;
         prefetch((int)blockIdx.x, sidx0);
-        if ((FUSE1 || RC1) && !a.x_by_tile) idx_next = a.idx[tile_or_last((int)blockIdx.x + a.nwg) >> a.tps_shift];
-        if constexpr (RC1) { load_xraw((int)blockIdx.x, __builtin_amdgcn_readfirstlane(sidx0)); store_xfrag(); }   // first tile: latency exposed once
+        if (!a.x_by_tile) idx_next = a.idx[tile_or_last((int)blockIdx.x + a.nwg) >> a.tps_shift];
+        load_xraw((int)blockIdx.x, __builtin_amdgcn_readfirstlane(sidx0)); store_xfrag();      // first tile: latency exposed once
     }
     __syncthreads();
 
@@ -965,16 +887,16 @@ __global__ __launch_bounds__((BwdB<F, HID>::NW * 64), 1) void k_policy_bwd_bf16(
         // for the prefetched inputs, so they land under phase A (sched_barrier: hipcc otherwise sinks them to the barrier)
         uint4 ring[NSR > 0 ? NSR : 1][FT];
         const uint4* wt = a.w2tb + (size_t)(w * FT) * NS * 64;       // wave-uniform base of this wave's W2^T tiles
-        // (k-step order = the order the chain consumes them in: vmcnt retires in order).  PPO_BF16_RING_SPREAD: not in
+        // (k-step order = the order the chain consumes them in: vmcnt retires in order).  Where they are few enough, not in
         // one burst -- 8 KiB per wave through a 64 B/clk L1 stalls the issuing wave ~500 cycles -- but a few at a
         // time between the pieces of phase A's VALU/LDS work (2 here, then 3 per feature tile)
         constexpr int NRL = NSR * FT;
         auto ring_load = [&](int q) { if (q < NRL) ring[q / FT][q % FT] = ldg16(wt + (size_t)((q % FT) * NS + NSL + q / FT) * 64, lo16); };
-        constexpr bool SPREAD = PPO_BF16_RING_SPREAD && (NRL <= 2 + 3 * FT);
+        constexpr bool SPREAD = NRL <= 2 + 3 * FT;
 #pragma unroll
         for (int q = 0; q < (SPREAD ? 2 : NRL); ++q) ring_load(q);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (RC1) {
+        {
             // H1 of this wave's feature tiles, recomputed exactly as the forward kernel computes it (bias in the accumulator,
             // KS1 k-steps in order, leakyrelu, RNE pack) and laid into the H1 image.  Its own segment in front of the dZ2
             // work: the W1 fragments (L2-resident; the partner wave covers their round trip) and the accumulator are dead
@@ -1037,7 +959,6 @@ __global__ __launch_bounds__((BwdB<F, HID>::NW * 64), 1) void k_policy_bwd_bf16(
                 const int off = wrow + 64 * ft + 8 * ((2 * g + h) ^ wsw);
                 *reinterpret_cast<uint2*>(imgZ2 + off) = make_uint2(dw(zf[g >> 1], 2 * (g & 1)), dw(zf[g >> 1], 2 * (g & 1) + 1));
                 if constexpr (!TRN) *reinterpret_cast<uint2*>(imgH2 + off) = make_uint2(dw(nh2[i][g >> 1], 2 * (g & 1)), dw(nh2[i][g >> 1], 2 * (g & 1) + 1));
-                if constexpr (!RC1) *reinterpret_cast<uint2*>(imgH1 + off) = make_uint2(dw(nh1[RC1 ? 0 : i][g >> 1], 2 * (g & 1)), dw(nh1[RC1 ? 0 : i][g >> 1], 2 * (g & 1) + 1));
                 if constexpr (SPREAD) {
                     if (g < 2) {
                         __builtin_amdgcn_sched_barrier(0);
@@ -1051,8 +972,11 @@ __global__ __launch_bounds__((BwdB<F, HID>::NW * 64), 1) void k_policy_bwd_bf16(
         __syncthreads();
         BSTAMP(2);
         // ================= phase B: dH1^T[k-tiles of this wave] = W2^T dZ2^T, dZ1 = dH1 . lrelu'(H1) -> image
-        f32x16 accH[FT];                // dH1 of this wave's feature tiles (EPI_C: its epilogue runs inside phase C)
-        constexpr bool EPI_C = TRN && PPO_BF16_BWD_EPI_IN_C && (16 % NT == 0);
+        // The epilogue of dH1 runs here, in front of phase C.  Inside phase C, two accumulator registers behind the dW2 MFMAs of
+        // each k-tile, the identity-MFMA form measured 2 % SLOWER (0.940 -> 0.958 ms at 65,536 states, with and without
+        // scheduling pins): unlike the forward's chains, phase C already overlaps its transposed reads with its MFMAs, and
+        // carrying the dH1 accumulator through it costs more than the vector work it hides.
+        f32x16 accH[FT];                // dH1 of this wave's feature tiles
         {
             // the next tile's inputs start their HBM round trip here (their registers were consumed in phase A).  They
             // are issued BEHIND the streamed W2^T half: vmcnt retires in order, so the chain below waits only for
@@ -1060,7 +984,7 @@ __global__ __launch_bounds__((BwdB<F, HID>::NW * 64), 1) void k_policy_bwd_bf16(
             static_assert(NPIECE <= NS, "one prefetch piece per k-step");
             constexpr int PF_T0 = 0;
             const int pf_tile = tile_or_last(tile + a.nwg), pf_sidx = __builtin_amdgcn_readfirstlane(idx_next);
-            if ((FUSE1 || RC1) && !a.x_by_tile) idx_next = a.idx[tile_or_last(tile + 2 * a.nwg) >> a.tps_shift];
+            if (!a.x_by_tile) idx_next = a.idx[tile_or_last(tile + 2 * a.nwg) >> a.tps_shift];
             auto& acc = accH;
 #pragma unroll
             for (int i = 0; i < FT; ++i)
@@ -1113,7 +1037,7 @@ __global__ __launch_bounds__((BwdB<F, HID>::NW * 64), 1) void k_policy_bwd_bf16(
             // B operand of k-step s: dZ2[row j][features 16s + 8h .. +7] straight from the row-major image -- chunks
             // 4(s&1) + 2h and the next one of feature tile s>>1, each where the row's swizzle put it (two 8-byte reads;
             // W2^T is packed in this natural contraction order)
-            constexpr int DL = DIET ? PPO_BF16_BWD_DL8 : 3;
+            constexpr int DL = DIET ? 2 : 3;                 // (two waves per SIMD: the partner wave covers the rest)
             // this wave's resident W2^T fragments behind ONE opaque per-lane base: the k-step offsets then fit the ds_read
             // immediate (with the array base folded in they pass 64 KiB, and hipcc hoists one address register per k-step
             // out of the tile loop -- which spill, and every scratch reload waits vmcnt(0), i.e. for the whole prefetch)
@@ -1155,7 +1079,7 @@ __global__ __launch_bounds__((BwdB<F, HID>::NW * 64), 1) void k_policy_bwd_bf16(
             }
             BSTAMP(3);
 #pragma unroll
-            for (int i = 0; i < (EPI_C ? 0 : FT); ++i) {
+            for (int i = 0; i < FT; ++i) {
                 const int ft = w * FT + i;
                 BF16_SWZ();          // (shadows the chain's copies: those die with the chain)
                 uint2 hc[4];         // H1 of this feature tile, back from the image written in phase A (lane = row again)
@@ -1208,20 +1132,6 @@ __global__ __launch_bounds__((BwdB<F, HID>::NW * 64), 1) void k_policy_bwd_bf16(
             // (interleaving these MFMAs with the dH1 chain to hide its W2^T refills was measured slower: the chain's
             // two working accumulators then compete with the 256 resident ones for the AGPR half and hipcc parks two
             // dW2 tiles in scratch)
-            auto emit_z = [&](int i, int s) {
-                const uint4 z = tr_frag(imgZ1 + tro[0] + 16 * s * ST + 64 * (w * FT + i), imgZ1 + tro[1] + 16 * s * ST + 64 * (w * FT + i));
-                db1[i] += sum_frag(z);
-                stg16(a.z1f + (((size_t)tile * NT + (w * FT + i)) * 2 + s) * 64, lo16, z);
-            };
-            auto emit_x = [&](int i) {
-                const int it = w * FT + i;                     // wave-uniform
-                if (it < NI) {
-#pragma unroll
-                    for (int s = 0; s < 2; ++s)
-                        stg16(a.xf + (((size_t)tile * NI + it) * 2 + s) * 64, lo16,
-                              tr_frag(imgX + trx[0] + 16 * s * STX + 64 * it, imgX + trx[1] + 16 * s * STX + 64 * it));
-                }
-            };
             uint4 az[FT][2];
 #pragma unroll
             for (int i = 0; i < FT; ++i)
@@ -1230,17 +1140,6 @@ __global__ __launch_bounds__((BwdB<F, HID>::NW * 64), 1) void k_policy_bwd_bf16(
                     az[i][s] = tr_frag(imgZ2 + tro[0] + 16 * s * ST + 64 * (w * FT + i), imgZ2 + tro[1] + 16 * s * ST + 64 * (w * FT + i));
                     db2[i] += sum_frag(az[i][s]);
                 }
-            // EPI_C: the dH1 epilogue (dZ1 = dH1 . lrelu'(H1), two accumulator registers per step) issues behind the dW2 MFMAs
-            // of each k-tile -- the chain that produced dH1 is done, the two are independent, and a bf16 MFMA leaves the
-            // vector ALU free for the 32 clocks it holds the matrix pipe
-            uint2 hcq[FT][4];
-            if constexpr (EPI_C) {
-                BF16_SWZ();
-#pragma unroll
-                for (int i = 0; i < FT; ++i)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) hcq[i][g] = *reinterpret_cast<const uint2*>(imgH1 + wrow + 64 * (w * FT + i) + 8 * ((2 * g + h) ^ wsw));
-            }
 #pragma unroll
             for (int kt = 0; kt < NT; ++kt) {
                 uint4 b[2];
@@ -1250,49 +1149,13 @@ __global__ __launch_bounds__((BwdB<F, HID>::NW * 64), 1) void k_policy_bwd_bf16(
                 for (int i = 0; i < FT; ++i)
 #pragma unroll
                     for (int s = 0; s < 2; ++s) accW2[i][kt] = mfma_bf16(az[i][s], b[s], accW2[i][kt]);
-                if constexpr (EPI_C) {
-                    constexpr int RPS = 16 / NT;
-#pragma unroll
-                    for (int i = 0; i < FT; ++i)
-#pragma unroll
-                        for (int rr = 0; rr < RPS; ++rr) {
-                            const int r = RPS * kt + rr;
-                            const uint32_t d = (r & 2) ? hcq[i][r >> 2].y : hcq[i][r >> 2].x;
-                            accH[i][r] = accH[i][r] * ((r & 1) ? slope_hi(d) : slope_lo(d));
-                        }
-                }
-            }
-            if constexpr (EPI_C) {
-                // the rest of the epilogue: RNE pack, the identity-MFMA transpose, db1, the fragments for the dW1 kernel
-                const unsigned lds0 = (unsigned)(size_t)(PPO_LDS void*)smem_c;
-                const PPO_LDS u32x4* const idl = (const PPO_LDS u32x4*)(size_t)(lds0 + (unsigned)C::oID + lo16);
-                const u32x4 i0 = idl[0], i1 = idl[64];
-#pragma unroll
-                for (int i = 0; i < FT; ++i) {
-                    const int ft = w * FT + i;
-                    uint4 z1[2];
-                    pack_tile(accH[i], z1);
-                    f32x16 d;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) d[r] = 0.0f;
-                    d = mfma_bf16(z1[0], make_uint4(i0.x, i0.y, i0.z, i0.w), d);
-                    d = mfma_bf16(z1[1], make_uint4(i1.x, i1.y, i1.z, i1.w), d);
-                    float sd = 0.0f;
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) sd += d[r];
-                    db1[i] += sd;
-                    uint4 zt[2];
-                    pack_tile(d, zt);
-                    stg16(a.z1f + (((size_t)tile * NT + ft) * 2 + 0) * 64, lo16, zt[0]);
-                    stg16(a.z1f + (((size_t)tile * NT + ft) * 2 + 1) * 64, lo16, zt[1]);
-                }
             }
             BSTAMP(5);
             BSTAMP(6);
             if constexpr (FUSE1) {
             // dW1[k][i] += sum_rows dZ1[k][row] X[row][i]: both operands come back transposed from their LDS images (the
-            // fragments the HID = 256 form sends through HBM to a second kernel), NI x 2 MFMAs per feature tile
-            (void)emit_z; (void)emit_x;
+            // fragments the HID = 256 form sends through HBM to a second kernel: dZ1^T from phase B's identity MFMAs, while the
+            // dW1 kernel builds its X operands from the state rows itself), NI x 2 MFMAs per feature tile
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 uint4 xb[NI];
@@ -1306,21 +1169,11 @@ __global__ __launch_bounds__((BwdB<F, HID>::NW * 64), 1) void k_policy_bwd_bf16(
                     for (int it = 0; it < NI; ++it) accW1[FUSE1 ? i : 0][FUSE1 ? it : 0] = mfma_bf16(z, xb[it], accW1[FUSE1 ? i : 0][FUSE1 ? it : 0]);
                 }
             }
-            } else {
-            // dZ1^T of this wave's feature tiles and (first NI slots) the X column tiles, as MFMA operand fragments
-            // for k_policy_dw1_bf16
-            if constexpr (!TRN) {
-#pragma unroll
-            for (int i = 0; i < FT; ++i)
-#pragma unroll
-                for (int s = 0; s < 2; ++s) emit_z(i, s);
-            }
-            (void)emit_x;                                      // the dW1 kernel builds its X operands from the state rows itself
             }
         }
         // layer-1 B operands of the NEXT tile (its state bytes were the first piece fetched during phase B) into sXF: read
         // by everybody in that tile's phase A, behind the barrier below; this tile's readers are all past barrier 1
-        if constexpr (RC1) { store_xfrag(); load_w1(); }
+        store_xfrag(); load_w1();
         __syncthreads();
         BSTAMP(7);
     }
@@ -1483,13 +1336,12 @@ int32_t launch_policy_bwd_bf16(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_
     a.tps_shift = (tps == 4) ? 2 : 0;
     a.states = ro->compact ? p->xs.p : ro->states.p; a.x_by_tile = ro->compact ? 1 : 0;
     a.idx = idx_dev; a.B = (int32_t)(B * tps);
-    a.act1b = (const uint4*)p->act1.p; a.act2b = (const uint4*)p->act2.p; a.dY = (const float4*)p->dY.p;
+    a.act2b = (const uint4*)p->act2.p; a.dY = (const float4*)p->dY.p;
     a.w2tb = (const uint4*)p->w2tb.p; a.w3tb = (const uint2*)p->w3tb.p;
     a.w1b = (const uint4*)p->w1b.p; a.b1p = (const float4*)p->b1p.p;
-    // the fp32 mode's activation buffers are twice the size the bf16 activations need: the operand fragments for the
-    // dW1 kernel live in their upper halves (z1f behind act1b, xf behind act2b; NI <= NT)
+    // the fp32 mode's activation buffers are twice the size the bf16 activations need: the dZ1 operand fragments for the
+    // dW1 kernel live in the upper half of act1 (whose lower half, H1, nobody writes or reads: the backward recomputes it)
     a.z1f = (uint4*)p->act1.p + (size_t)a.B * (p->HID / 32) * 128;
-    a.xf = (uint4*)p->act2.p + (size_t)a.B * (p->HID / 32) * 128;
     ARG_CHECK(p->act1.n >= (size_t)a.B * (p->HID / 32) * 1024 && p->act2.n >= (size_t)a.B * (p->HID / 32) * 1024,
               "bf16 backward: activation workspace smaller than the minibatch (train_reserve)");
     a.slabs = p->slabs.p; a.slab_stride = slab_floats(p->F, p->HID);
@@ -1503,7 +1355,6 @@ int32_t launch_policy_bwd_bf16(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_
     a.nwg = nwg;
 #define LAUNCHB(FF, HH)                                                                                           \
     do {                                                                                                          \
-        static_assert(BwdB<FF, HH>::NI <= BwdB<FF, HH>::NT, "X fragments are emitted by waves 0..NI-1");          \
         const size_t lds = BwdB<FF, HH>::total;                                                                   \
         static thread_local bool attr_set = false;                                                                             \
         if (!attr_set) {                                                                                          \
@@ -1515,7 +1366,7 @@ int32_t launch_policy_bwd_bf16(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_
             ProfScope ps("k_policy_bwd");                                                                         \
             hipLaunchKernelGGL((k_policy_bwd_bf16<FF, HH>), dim3(nwg), dim3(BwdB<FF, HH>::NW * 64), lds, ppo_stream(), a); \
         }                                                                                                         \
-        if (HH > PPO_BF16_DW1_FUSED_MAX_HID) {                                                                    \
+        if (!BwdB<FF, HH>::FUSE) {                                                               \
             ProfScope ps("k_policy_dw1");                                                                         \
             hipLaunchKernelGGL((k_policy_dw1_bf16<FF, HH>), dim3(nwg), dim3(HH * 2), 0, ppo_stream(), a);         \
         }                                                                                                         \

@@ -22,20 +22,8 @@
 #include "ppo_device.h"
 #include <cstdlib>
 
-#ifndef PPO_BWD_LD
-#define PPO_BWD_LD 36
-#endif
-#ifndef PPO_BWD_ACT_NT
-#define PPO_BWD_ACT_NT 1          // read-once saved activations: non-temporal loads
-#endif
-#if PPO_BWD_ACT_NT
-#define PPO_BWD_NT_SFX " nt"
-#else
-#define PPO_BWD_NT_SFX ""
-#endif
-#ifndef PPO_BWD_KG
-#define PPO_BWD_KG 2
-#endif
+// leading dimension (rows) of the LDS tiles, see k_policy_bwd
+constexpr int BWD_LD = 36;
 
 // two fp32 FMAs per vector instruction (v_pk_fma_f32; each element is the same IEEE fma as fmaf)
 typedef float pk2 __attribute__((ext_vector_type(2)));
@@ -57,52 +45,28 @@ struct BwdArgs {
 // unless a SECOND workgroup shares the CU.  Registers allow it (~220 per wave); LDS did not (86.5 KB).  So in this
 // shape X^T is staged as int8 (2.3 KB instead of 9.2 KB as floats; the B operands of phase D are converted on the way
 // in, 8 VALU per 16-byte read), which brings the workgroup to 79.6 KB: two per CU, 512 workgroups per launch.
-// How the state rows X reach phase D's B operands (F = 72 only; the 8 tail columns always go through sXt as floats):
-//   0  X^T as floats [feature][36 rows]: 288 cvt pairs + 288 ds_write_b32 per wave and tile, 8 ds_read_b128 in phase D
-//   1  X^T as int8   [feature][36 rows]: 288 ds_write_b8, 8 ds_read_b32 + 32 cvt in phase D
-//   2  X   as int8   [row][68 B] (the rows as they come): 64 ds_write_b32, 32 ds_read_i8 + 32 cvt in phase D
+// How the state rows X reach phase D's B operands (the 8 tail columns of F = 72 always go through sXt as floats):
+//   X^T as floats [feature][36 rows]: 288 cvt pairs + 288 ds_write_b32 per wave and tile, 8 ds_read_b128 in phase D
+//   X^T as int8   [feature][36 rows]: 288 ds_write_b8, 8 ds_read_b32 + 32 cvt in phase D  (XI8: HID = 128, F = 72)
 // Every vector instruction beside an fp32 MFMA costs MFMA time on gfx950, so the forms differ by
 // what they issue, not by what they compute.
-// Measured (gpurun_out/r2i, same box, alternating): form 0 is the fastest at HID = 256 (0.3523 vs 0.3555-0.3560 ms:
-// the byte / dword reads of forms 1-2 put their LDS latency in front of phase D's MFMAs, which costs more than the
-// 500 vector instructions they save); at HID = 128 the three are level (0.1211-0.1221 ms) and form 0 does not fit.
-#ifndef PPO_BWD_XMODE
-#define PPO_BWD_XMODE 0
-#endif
-// which state dword a thread stages: 1 = lane -> tile row, so the 32 lanes of a transposing LDS write land in 32 banks
-// (the global load is then a 72-byte-stride gather inside a 2.3 KB, cache-resident tile); 0 = linear (coalesced load,
-// 4.5-way bank conflicts on the writes: the 6 % SQ_LDS_BANK_CONFLICT of round 1)
-#ifndef PPO_BWD_XROWLANE
-#define PPO_BWD_XROWLANE 1
-#endif
-// dH2 = W3^T dY of the wave's feature tile: 1 = two MFMAs (k = the 4 outputs) whose accumulator IS the lane-is-row
-// fragment the phase needs; 0 = 64 FMAs + 16 LDS reads of W3 per lane (round-1 form).  Only where the 16 extra live
-// registers fit: at HID = 256 the kernel sits at 256 VGPRs and the MFMA form spills 10 of them.
-#ifndef PPO_BWD_DH2_MFMA
-#define PPO_BWD_DH2_MFMA 1
-#endif
-#ifndef PPO_BWD_DH2_MFMA_MAX_HID
-#define PPO_BWD_DH2_MFMA_MAX_HID 256
-#endif
-// workgroup barrier between phases B and C/D (round-1 form; no data flow needs it, see the loop) for hidden widths below
-// this one.  Measured (gpurun_out/r2v): HID = 256 0.3430 -> 0.3420 ms without it, HID = 128 0.1165 -> 0.1178 ms (two
-// workgroups share a CU there and the barrier keeps their MFMA phases apart).
-#ifndef PPO_BWD_BAR2_BELOW_HID
-#define PPO_BWD_BAR2_BELOW_HID 256
-#endif
+// Measured (same box, alternating), with a third form, X as int8 [row][68 B] as the rows come (64 ds_write_b32, 32
+// ds_read_i8 + 32 cvt in phase D): floats are the fastest at HID = 256 (0.3523 vs 0.3555-0.3560 ms: the byte / dword
+// reads of the int8 forms put their LDS latency in front of phase D's MFMAs, which costs more than the 500 vector
+// instructions they save); at HID = 128 the three are level (0.1211-0.1221 ms) and floats do not fit.
+// Which state dword a thread stages: lane -> tile row, so the 32 lanes of a transposing LDS write land in 32 banks (the
+// global load is then a 72-byte-stride gather inside a 2.3 KB, cache-resident tile).  Staged linearly (coalesced load)
+// the writes had 4.5-way bank conflicts: the 6 % SQ_LDS_BANK_CONFLICT of round 1.
 template <int F, int HID>
 struct BwdCfg {
-    static constexpr int XMODE = (F == 72) ? ((HID == 128 && PPO_BWD_XMODE == 0) ? 1 : PPO_BWD_XMODE) : 0;   // HID = 128 needs an int8 form (LDS)
-    static constexpr bool XI8 = XMODE == 1, XN8 = XMODE == 2;
-    static constexpr int XS = 68;                                        // XN8 row stride in bytes (17 dwords: rows 16 apart sit 16 banks apart)
+    static constexpr bool XI8 = F == 72 && HID == 128;
     static constexpr int WG_PER_CU = (HID == 128 && F == 72) ? 2 : 1;
     static constexpr int MIN_WAVES = (HID >= 256 || WG_PER_CU == 2) ? 2 : 1;   // per SIMD (caps the register budget at 256)
 };
 
 template <int F, int HID>
 __global__ __launch_bounds__(HID * 2, (BwdCfg<F, HID>::MIN_WAVES)) void k_policy_bwd(BwdArgs a) {
-    constexpr bool XI8 = BwdCfg<F, HID>::XI8, XN8 = BwdCfg<F, HID>::XN8;
-    constexpr int XS = BwdCfg<F, HID>::XS;
+    constexpr bool XI8 = BwdCfg<F, HID>::XI8;
     constexpr int NT = HID / 32;                // feature tiles == waves per workgroup (wave w owns tile w)
     constexpr int NTHR = NT * 64;
     constexpr int FP = ((F + 31) / 32) * 32;
@@ -116,7 +80,7 @@ __global__ __launch_bounds__(HID * 2, (BwdCfg<F, HID>::MIN_WAVES)) void k_policy
     // order of an MFMA contraction is free as long as A and B agree).  Beside the fp32 MFMA an LDS read costs the same
     // ~6 ns whether it returns 4 or 16 bytes per lane (tools/microbench/mfma_f32_lds_overlap.hip), and these kernels
     // issued one ds_read_b32 per MFMA.
-    constexpr int LD = PPO_BWD_LD;
+    constexpr int LD = BWD_LD;
     static_assert(F % 8 == 0, "state rows are staged in 8-byte units");
     constexpr int XQW = 32 * F / 8;             // 8-byte units of one state (F = 72, 512 threads: ONE pass, 288 threads busy;
     constexpr int XPD = (XQW + NTHR - 1) / NTHR;  //   as dwords it was a full pass plus a 64-thread one with its own addresses)
@@ -133,7 +97,7 @@ __global__ __launch_bounds__(HID * 2, (BwdCfg<F, HID>::MIN_WAVES)) void k_policy
     float* sZ1 = sH2 + HID * LD;                // [HID][33]  dZ1^T
     float* sX = sZ1 + HID * LD;                 // [NIM*32][33]  X^T (float), MFMA part  (XI8: int8 [NIM*32][LD bytes])
     int8_t* const sXb = reinterpret_cast<int8_t*>(sX);
-    float* sXt = XN8 ? sX + 32 * XS / 4 : (XI8 ? sX + NIM * 32 * LD / 4 : sX + NIM * 32 * LD);   // [32][FT]  X tail columns, row-major per tile row
+    float* sXt = XI8 ? sX + NIM * 32 * LD / 4 : sX + NIM * 32 * LD;   // [32][FT]  X tail columns, row-major per tile row
     float* sDY = sXt + 32 * (FT > 0 ? FT : 4);  // [32][4]
     float* sW3 = sDY + 32 * 4;                  // [HID][4]   W3[:,f] per feature (staged once)
 
@@ -165,8 +129,6 @@ __global__ __launch_bounds__(HID * 2, (BwdCfg<F, HID>::MIN_WAVES)) void k_policy
     }
     __syncthreads();
 
-    constexpr bool DH2M = PPO_BWD_DH2_MFMA && HID <= PPO_BWD_DH2_MFMA_MAX_HID;
-
     const char* const w2t = reinterpret_cast<const char*>(a.w2tp + (size_t)w * S4 * 64);   // this wave's W2^T tile (scalar base)
     const unsigned lo16 = (unsigned)lane * 16u;
     const unsigned fb = (unsigned)(32 * w + 4 * h);
@@ -189,7 +151,7 @@ __global__ __launch_bounds__(HID * 2, (BwdCfg<F, HID>::MIN_WAVES)) void k_policy
             unsigned keep;
             const float4* gsrc = src + q * 64;
             const unsigned dst = h2slice_lds + (unsigned)q * 1024u;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" PPO_BWD_NT_SFX "\n\ts_mov_b32 m0, %0"
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
                          : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
         }
     };
@@ -202,24 +164,16 @@ __global__ __launch_bounds__(HID * 2, (BwdCfg<F, HID>::MIN_WAVES)) void k_policy
         const char* s1 = reinterpret_cast<const char*>(a.act1 + ((size_t)t * NT + w) * 4 * 64);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-#if PPO_BWD_ACT_NT
-            typedef float f32x4l __attribute__((ext_vector_type(4)));
+            typedef float f32x4l __attribute__((ext_vector_type(4)));                // read-once saved activations: non-temporal loads
             const f32x4l t4 = __builtin_nontemporal_load(reinterpret_cast<const f32x4l*>(s1 + (lo16 + (unsigned)q * 1024u)));
             v1[q] = make_float4(t4.x, t4.y, t4.z, t4.w);
-#else
-            v1[q] = *reinterpret_cast<const float4*>(s1 + (lo16 + (unsigned)q * 1024u));
-#endif
         }
         dy = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(a.dY + (size_t)t * 32) + (unsigned)j * 16u);
         const char* xs = reinterpret_cast<const char*>(a.states + (a.x_by_tile ? (size_t)t : ((size_t)sidx * a.tps + (size_t)(t % a.tps))) * 32 * F);
 #pragma unroll
         for (int i = 0; i < XPD; ++i) {
             const unsigned u = (unsigned)tid + (unsigned)i * NTHR;
-#if PPO_BWD_XROWLANE
             const unsigned d = (u & 31u) * (unsigned)(F / 8) + (u >> 5);      // lane -> row, 32-lane group -> one 8-feature unit
-#else
-            const unsigned d = u;
-#endif
             xd[i] = u < (unsigned)XQW ? *reinterpret_cast<const uint2*>(xs + d * 8u) : make_uint2(0u, 0u);
         }
     };
@@ -245,7 +199,6 @@ __global__ __launch_bounds__(HID * 2, (BwdCfg<F, HID>::MIN_WAVES)) void k_policy
         float* const h1b = sH1 + lb;
         float* const h2b = sH2 + lb;
         float* const z1b = sZ1 + lb;
-        const float* const w3b = sW3 + fb * 4;
         // ================= phase A: stage the tile (transposes through LDS)
         // Nothing is fetched here any more: the layer-1 fragments, dY and the state dwords were issued into
         // registers at the top of phase D of the previous tile (v1/dy/xd), the layer-2 fragments came by LDS-DMA.
@@ -253,17 +206,15 @@ __global__ __launch_bounds__(HID * 2, (BwdCfg<F, HID>::MIN_WAVES)) void k_policy
         {
             // wait for everything this wave has in flight (its DMA is the oldest)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if constexpr (DH2M) {
-                // the layer-1 fragments go to their transposed places FIRST: their 16 registers are free again before the
-                // dH2 accumulator and the layer-2 fragments come alive (the kernel sits at the 256-register budget)
+            // the layer-1 fragments go to their transposed places FIRST: their 16 registers are free again before the
+            // dH2 accumulator and the layer-2 fragments come alive (the kernel sits at the 256-register budget)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float h1v[4] = {v1[q].x, v1[q].y, v1[q].z, v1[q].w};
+            for (int q = 0; q < 4; ++q) {
+                const float h1v[4] = {v1[q].x, v1[q].y, v1[q].z, v1[q].w};
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) h1b[(e + 8 * q) * LD] = h1v[e];
-                }
-                __builtin_amdgcn_sched_barrier(0);
+                for (int e = 0; e < 4; ++e) h1b[(e + 8 * q) * LD] = h1v[e];
             }
+            __builtin_amdgcn_sched_barrier(0);
             // read the raw 4 KiB of layer-2 fragments out of the slice, and only then overwrite the slice with the
             // transposed tile below
 #pragma unroll
@@ -275,10 +226,12 @@ __global__ __launch_bounds__(HID * 2, (BwdCfg<F, HID>::MIN_WAVES)) void k_policy
         STAMP(6);
 #endif
         if (w == 0 && h == 0) *reinterpret_cast<float4*>(&sDY[j * 4]) = dy;
-        // feature of register r: 32w + 4h + (r&3) + 8(r>>2)  ->  one base per array + compile-time offsets
-        // (the offsets fold into the ds_* immediate field; no per-element address registers)
+        // dH2 = W3^T dY of the wave's feature tile: two MFMAs (k = the 4 outputs) whose accumulator IS the lane-is-row fragment
+        // the phase needs (round 1 spent 64 FMAs + 16 LDS reads of W3 per lane on it).  Its 16 live registers were fitted to
+        // the 256-register budget at these widths only
+        static_assert(HID <= 256, "dH2 on the MFMA pipe: register budget checked up to HID = 256");
         f32x16 dh2;
-        if constexpr (DH2M) {
+        {
 #pragma unroll
             for (int r = 0; r < 16; ++r) dh2[r] = 0.0f;
             // A operand of dH2^T[f, row] = sum_o W3[o, f] dY[row, o] for feature f = 32w + j: k-step s, lane half h -> output
@@ -287,25 +240,19 @@ __global__ __launch_bounds__(HID * 2, (BwdCfg<F, HID>::MIN_WAVES)) void k_policy
             dh2 = __builtin_amdgcn_mfma_f32_32x32x2f32(w3a0, h ? dy.y : dy.x, dh2, 0, 0, 0);     // register r = 4q + e <-> feature e + 8q (+ 4h)
             dh2 = __builtin_amdgcn_mfma_f32_32x32x2f32(w3a1, h ? dy.w : dy.z, dh2, 0, 0, 0);
         }
-        float* const z2r = sZ2 + j * RS + fb;                      // Z2R: this lane's row, features 32w + 4h + 8q .. +3
+        // feature of register r: 32w + 4h + (r&3) + 8(r>>2)  ->  one base per array + compile-time offsets
+        // (the offsets fold into the ds_* immediate field; no per-element address registers)
+        float* const z2r = sZ2 + j * RS + fb;                     // Z2R: this lane's row, features 32w + 4h + 8q .. +3
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const float h2v[4] = {v2[q].x, v2[q].y, v2[q].z, v2[q].w};
-            const float h1v[4] = {v1[q].x, v1[q].y, v1[q].z, v1[q].w};
             float z[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int fo = e + 8 * q;                          // feature offset inside the tile
-                float dh;
-                if constexpr (DH2M) dh = dh2[4 * q + e];
-                else {
-                    const float4 ww = *reinterpret_cast<const float4*>(w3b + fo * 4);
-                    dh = fmaf(ww.w, dy.w, fmaf(ww.z, dy.z, fmaf(ww.y, dy.y, ww.x * dy.x)));
-                }
-                z[e] = dh * (h2v[e] > 0.0f ? 1.0f : 0.01f);
+                z[e] = dh2[4 * q + e] * (h2v[e] > 0.0f ? 1.0f : 0.01f);
                 if constexpr (!Z2R) z2b[fo * LD] = z[e];
                 h2b[fo * LD] = h2v[e];
-                if constexpr (!DH2M) h1b[fo * LD] = h1v[e];
             }
             if constexpr (Z2R) *reinterpret_cast<float4*>(z2r + 8 * q) = make_float4(z[0], z[1], z[2], z[3]);
         }
@@ -313,14 +260,10 @@ __global__ __launch_bounds__(HID * 2, (BwdCfg<F, HID>::MIN_WAVES)) void k_policy
         for (int i = 0; i < XPD; ++i) {
             const int d = tid + i * NTHR;                         // unit row*(F/8) + c : features 8c..8c+7 of a row
             if (d < XQW) {
-#if PPO_BWD_XROWLANE
                 const int row = d & 31, c = d >> 5;               // the 32 lanes of an LDS write hold 32 rows of ONE feature:
-#else                                                             // banks (LD*f + row) mod 64 are all different
-                const int row = d / (F / 8), c = d % (F / 8);     // consecutive lanes = consecutive c: bank conflicts on the writes
-#endif
+                                                                  // banks (LD*f + row) mod 64 are all different
                 const uint32_t xw[2] = {xd[i].x, xd[i].y};
                 if (8 * c < NIM * 32) {
-                    if (XN8) { *reinterpret_cast<uint2*>(sXb + row * XS + 8 * c) = xd[i]; continue; }
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
                         if (XI8) sXb[(8 * c + e) * LD + row] = (int8_t)(xw[e >> 2] >> (8 * (e & 3)));
@@ -438,7 +381,9 @@ __global__ __launch_bounds__(HID * 2, (BwdCfg<F, HID>::MIN_WAVES)) void k_policy
         // (complete since the barrier behind phase A), phase D this wave's own dZ1 rows (written by itself above) and
         // X^T (phase A), and nothing in C/D writes LDS.  A wave that finishes its dH1 chain early goes straight on, so
         // the two waves of a SIMD keep the skew grads_first gives them instead of being re-aligned here.
-        if constexpr (HID < PPO_BWD_BAR2_BELOW_HID) __syncthreads();
+        // HID = 128 keeps the barrier of round 1 all the same: two workgroups share a CU there and it keeps their MFMA phases
+        // apart.  Measured: HID = 256 0.3430 -> 0.3420 ms without it, HID = 128 0.1165 -> 0.1178 ms.
+        if constexpr (HID < 256) __syncthreads();
         else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's dZ1 writes have landed
         STAMP(3);
         // LDS-DMA of the next tile's layer-2 fragments into this wave's (now idle) sH2 slice.  Issued here, after
@@ -485,7 +430,7 @@ __global__ __launch_bounds__(HID * 2, (BwdCfg<F, HID>::MIN_WAVES)) void k_policy
         };
         if (grads_first) tail_grads();
         {
-            constexpr int KG = PPO_BWD_KG;                           // k-tiles whose B operands are in flight together
+            constexpr int KG = 2;                                    // k-tiles whose B operands are in flight together
             // rows 16h .. 16h+15 of this lane's feature (Z2R: four 4-byte reads per step, and db2 is their sum)
             const float* pa = Z2R ? sZ2 + (16 * h) * RS + 32 * w + j : sZ2 + (32 * w + j) * LD + 16 * h;
             const float* pb = sH1 + j * LD + 16 * h;
@@ -538,10 +483,7 @@ __global__ __launch_bounds__(HID * 2, (BwdCfg<F, HID>::MIN_WAVES)) void k_policy
 #pragma unroll
                 for (int it = 0; it < NIM; ++it) {
                     float4 b4;
-                    if (XN8) {                                   // feature 32 it + j of rows 16h + 4q .. +3: four sign-extending byte reads
-                        const int8_t* xb = sXb + (16 * h + 4 * q) * XS + 32 * it + j;
-                        b4 = make_float4((float)(int)xb[0], (float)(int)xb[XS], (float)(int)xb[2 * XS], (float)(int)xb[3 * XS]);
-                    } else if (XI8) {                            // four rows of feature 32 it + j as one dword of int8
+                    if (XI8) {                            // four rows of feature 32 it + j as one dword of int8
                         const uint32_t d = *reinterpret_cast<const uint32_t*>(sXb + (32 * it + j) * LD + 16 * h + 4 * q);
                         b4 = make_float4((float)(int)(int8_t)(d), (float)(int)(int8_t)(d >> 8), (float)(int)(int8_t)(d >> 16), (float)(int)(int8_t)(d >> 24));
                     } else b4 = *reinterpret_cast<const float4*>(pb + 32 * it * LD + 4 * q);
@@ -619,10 +561,10 @@ extern "C" int32_t ppo_debug_bwd_stamps(unsigned long long* out) {
 
 template <int F, int HID>
 static size_t bwd_lds_bytes() {
-    const size_t xt = (size_t)(F / 32) * 32 * PPO_BWD_LD;      // X^T elements: floats, or bytes in the int8 forms
-    const size_t xfl = BwdCfg<F, HID>::XN8 ? (size_t)32 * BwdCfg<F, HID>::XS / 4 : (BwdCfg<F, HID>::XI8 ? xt / 4 : xt);
-    const size_t z2 = PPO_BWD_Z2ROW_AT(HID) ? (size_t)32 * (HID + 4) : (size_t)HID * PPO_BWD_LD;
-    return sizeof(float) * (z2 + (size_t)3 * HID * PPO_BWD_LD + xfl + (size_t)32 * ((F % 32) ? (F % 32) : 4) + 32 * 4 + (size_t)HID * 4);
+    const size_t xt = (size_t)(F / 32) * 32 * BWD_LD;          // X^T elements: floats, or bytes in the int8 form
+    const size_t xfl = BwdCfg<F, HID>::XI8 ? xt / 4 : xt;
+    const size_t z2 = PPO_BWD_Z2ROW_AT(HID) ? (size_t)32 * (HID + 4) : (size_t)HID * BWD_LD;
+    return sizeof(float) * (z2 + (size_t)3 * HID * BWD_LD + xfl + (size_t)32 * ((F % 32) ? (F % 32) : 4) + 32 * 4 + (size_t)HID * 4);
 }
 
 int32_t launch_policy_bwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B) {

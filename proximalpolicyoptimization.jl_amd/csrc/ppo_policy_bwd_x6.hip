@@ -74,29 +74,17 @@ struct XCfg {
 // VALU ops, instead of living in ~30 loop-invariant registers that hipcc hoists out of the tile loop and spills
 #define X6_LANE() unsigned ln = (unsigned)lane; asm volatile("" : "+v"(ln)); const int j = (int)(ln & 31u), h = (int)(ln >> 5); (void)j; (void)h
 
-#ifndef PPO_X6_DMA_SPREAD
-// next-tile LDS-DMA loads spread through phase C's MFMA loop (bit 0: layer 2, bit 1: layer 1) or issued together in front of
-// it (0).  Off: the loads have to land before the barrier that ends the tile (see the loop), and the pieces issued last
-// would make that barrier wait for them.
-#define PPO_X6_DMA_SPREAD 0
-#endif
-#ifndef PPO_X6_RING
-#define PPO_X6_RING 6
-#endif
-// W2 pieces in flight per wave in the dH1 chain (3 per k-step).  At HID = 256 the kernel runs at the 256-register budget: 4
-// fit, 6 spill 72 B inside the chain loop.  Depth is not what the chain waits for: with the third dW1 accumulator tile parked
-// in LDS across the chain (its 9 live columns; 253 VGPRs, no scratch) rings of 6 and 8 measured 1-2 % SLOWER than 4, with
-// and without the scalar-base loads (profiles/r05_w2_ring_ab.txt), so the parking was not kept.  3 -> 4 was worth 1.8 %.
-#ifndef PPO_X6_RING_256
-#define PPO_X6_RING_256 4
-#endif
-
 template <int F, int HID>
 __global__ __launch_bounds__(HID * 2, 2) void k_policy_bwd_x6(BwdXArgs a) {
     using C = XCfg<F, HID>;
     constexpr int NT = C::NT, KS = C::KS, NTHR = NT * 64, LD = C::LD, NIX = C::NIX, XROW = C::XROW;
     constexpr int XQW = 32 * F / 8, XPD = (XQW + NTHR - 1) / NTHR;
-    constexpr int RD = HID >= 256 ? PPO_X6_RING_256 : PPO_X6_RING;
+    // W2 pieces in flight per wave in the dH1 chain (3 per k-step): 6 at HID = 128, 4 at HID = 256.  At HID = 256 the kernel runs
+    // at the 256-register budget: 4 fit, 6 spill 72 B inside the chain loop.  Depth is not what the chain waits for: with the
+    // third dW1 accumulator tile parked in LDS across the chain (its 9 live columns; 253 VGPRs, no scratch) rings of 6 and 8
+    // measured 1-2 % SLOWER than 4, with and without the scalar-base loads (profiles/r05_w2_ring_ab.txt), so the parking was
+    // not kept.  3 -> 4 was worth 1.8 %.
+    constexpr int RD = HID >= 256 ? 4 : 6;
     static_assert(NTHR >= 256 && NTHR >= HID, "shape");
     extern __shared__ __attribute__((aligned(16))) char smem_c[];
     char* const fragZ2 = smem_c + C::oZ2;
@@ -173,16 +161,6 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_bwd_x6(BwdXArgs a) {
                          : "=&s"(keep) : "v"(voff), "s"(dst), "s"(gsrc) : "memory");
         }
     };
-    // one of the four 1 KiB pieces of such a load (phase C issues them one per fragment set, between the MFMAs: eight loads
-    // issued back to back hold the wave at the issue stage for ~1200 clocks)
-    auto dma_one = [&](const float4* base, int64_t t, unsigned dst_lds, int q, unsigned ln) {
-        unsigned keep;
-        const float4* gsrc = base + ((size_t)t * NT + w) * 4 * 64 + ln + q * 64;
-        const unsigned dst = dst_lds + (unsigned)q * 1024u;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-    };
-    (void)dma_one;
     float4 dy;
     uint2 xd[XPD];
     auto issue_tile_loads = [&](int64_t t, int sidx, unsigned ln) {
@@ -469,12 +447,11 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_bwd_x6(BwdXArgs a) {
             }
             // the next tile's inputs: fragments by LDS-DMA into the (now idle) regions, dY and the state dwords into registers
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // this wave's reads of its H2^T rows have returned
-#if !(PPO_X6_DMA_SPREAD & 1)
+            // Both issued together here, in front of phase C's MFMA loop: the loads have to land before the barrier that ends
+            // the tile, and spread through that loop, one 1 KiB piece per fragment set, the pieces issued last made that
+            // barrier wait for them.
             dma_frag(a.act2, ntile, h2slice_lds, ln);
-#endif
-#if !(PPO_X6_DMA_SPREAD & 2)
             dma_frag(a.act1, ntile, z2own_lds, ln);
-#endif
             {
                 int nidx = 0;
                 if (!a.x_by_tile) {
@@ -522,13 +499,6 @@ __global__ __launch_bounds__(HID * 2, 2) void k_policy_bwd_x6(BwdXArgs a) {
                 accW2[kt] = x_mfma(ah[s], bc[1], accW2[kt]);
                 accW2[kt] = x_mfma(ah[s], bc[0], accW2[kt]);
                 __builtin_amdgcn_sched_barrier(0);
-#if PPO_X6_DMA_SPREAD
-                // the next tile's saved activations, one 1 KiB piece per fragment set (this wave's regions are idle since the
-                // lgkmcnt(0) above): layer 2 into the H2^T rows, layer 1 into the dZ2 fragment images
-                if ((PPO_X6_DMA_SPREAD & 1) && g < 4) dma_one(a.act2, ntile, h2slice_lds, g, ln);
-                else if ((PPO_X6_DMA_SPREAD & 2) && g >= 4 && g < 8) dma_one(a.act1, ntile, z2own_lds, g - 4, ln);
-                __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
                 for (int p = 0; p < 3; ++p) bc[p] = bn[p];
             }

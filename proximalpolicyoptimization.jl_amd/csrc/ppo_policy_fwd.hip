@@ -20,40 +20,22 @@
 #include "ppo_env_device.h"
 #include <cstdlib>
 
-// activation stores of the train forward: tuning knobs for A/B builds (defaults are the shipped configuration)
-#ifndef PPO_FWD_STORE
-#define PPO_FWD_STORE 1          // 0: timing-only build without activation stores (results are wrong)
-#endif
-// Non-temporal stores for the 268 MB of saved activations: they are written once and read once by the backward
-// kernel much later, so they should not churn the L2; measured -4 % on the train forward (A/B in one process).
-#ifndef PPO_FWD_NT
-#define PPO_FWD_NT 1
-#endif
-#if PPO_FWD_NT
+// Non-temporal stores for the 268 MB of activations the train forward saves: they are written once and read once by the
+// backward kernel much later, so they should not churn the L2; measured -4 % on the train forward (A/B in one process).
 static __device__ __forceinline__ void act_store_nt(float4* p, float4 v) {
     f32x4 t = {v.x, v.y, v.z, v.w};
     __builtin_nontemporal_store(t, reinterpret_cast<f32x4*>(p));
 }
-#define ACT_STORE(ptr, val) act_store_nt((ptr), (val))
-#else
-#define ACT_STORE(ptr, val) (*(ptr) = (val))
-#endif
 
 // waves per SIMD: the HID=256 / F=216 instantiations need more than 256 VGPRs (128 for the layer-1
 // accumulators + operands in flight), so they run one wave per SIMD with the whole 512-entry file.
 // HID = 128, F = 72: two waves per SIMD with the deep (16-group) ring in the train forward.  Re-measured in round 2
-// (gpurun_out/r2l, train forward / 128-step rollout): 2 waves + 16 groups 0.0685 ms / 8.34 ms; 2 + 8: 0.0817 / 8.37;
+// (train forward / 128-step rollout): 2 waves + 16 groups 0.0685 ms / 8.34 ms; 2 + 8: 0.0817 / 8.37;
 // 3 waves + 4 groups: 0.0717 / 8.87 (the rollout instantiation spills at 168 registers); 3 + 8: 0.0889 / 8.88.
-#ifndef PPO_FWD_WPS_SMALL
-#define PPO_FWD_WPS_SMALL 2          // waves per SIMD of the HID = 128, F = 72 instantiations (A/B knob)
-#endif
-#ifndef PPO_FWD_PF_SMALL_TRAIN
-#define PPO_FWD_PF_SMALL_TRAIN PPO_FWD_PF   // their train-forward ring depth
-#endif
 // k_policy_fwd's MODE: FwdMode, and the table fwd_traits from a mode to its state source and its tail (ppo_internal.h)
 
 template <int F, int HID>
-struct FwdCfg { static constexpr int WPS = (HID >= 256 || F > 128) ? 1 : PPO_FWD_WPS_SMALL; };
+struct FwdCfg { static constexpr int WPS = (HID >= 256 || F > 128) ? 1 : 2; };
 
 // TPS = 32-row tiles per state (H = 32*TPS half-edges, A = 128*TPS actions): the wave walks the tiles of its
 // state one after the other, keeps the 4*TPS logits per lane, and runs softmax / sampling / loss once per state.
@@ -70,19 +52,8 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
     constexpr int S41 = F / 8;         // float4 groups of layer-1 k-steps
     constexpr int XB = F / 2;          // bytes of the state row held by one lane
     constexpr int XW = XB / 4;
-#ifndef PPO_FWD_PF
-#define PPO_FWD_PF 16
-#endif
-#ifndef PPO_FWD_WGSYNC
-#define PPO_FWD_WGSYNC 0
-#endif
-#ifndef PPO_FWD_OUNROLL
-#define PPO_FWD_OUNROLL 1
-#endif
-    constexpr int PFW = (PPO_FWD_PF < HID / 8) ? PPO_FWD_PF : HID / 8;     // at most the groups of one output tile
-    // two waves per SIMD (HID = 128, F = 72): 4 groups cover the L2 latency; the train forward, whose activation stores
-    // sit in the same vmcnt queue, wants the deep ring here too (0.072 -> 0.069 ms), the rollout does not (8.3 -> 8.7 ms)
-    constexpr int PFT = (PPO_FWD_PF_SMALL_TRAIN < HID / 8) ? PPO_FWD_PF_SMALL_TRAIN : HID / 8;
+    constexpr int PFW = 16;            // the deep ring of weight-fragment groups: at most the groups of one output tile
+    static_assert(PFW <= HID / 8, "the deep ring is one output tile's groups at the most");
     constexpr FwdSource SRC = fwd_traits(MODE).src;
     constexpr FwdTail TAIL = fwd_traits(MODE).tail;
     constexpr bool TRAIN = tail_trains(TAIL);           // train forward: saves activations, loss tail
@@ -91,11 +62,13 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
     constexpr bool GATHER = SRC == FwdSource::RowsIdx;
     constexpr bool SNAP = src_snapshot(SRC), SNAPX = SRC == FwdSource::SnapIdx;
     constexpr bool PERSIST = SRC == FwdSource::EnvSlots;    // persistent rollout: T steps of the wave's envs, their state in LDS slots
+    // two waves per SIMD (HID = 128, F = 72): 4 groups cover the L2 latency; the train forward, whose activation stores
+    // sit in the same vmcnt queue, wants the deep ring here too (0.072 -> 0.069 ms), the rollout does not (8.3 -> 8.7 ms)
     // (value-train from snapshots keeps half the train ring at two waves per SIMD: with 16 groups next to the row
     // re-derivation it does not fit the 256 registers)
-    constexpr int PFV = (PFT < 8) ? PFT : 8;
+    constexpr int PFV = PFW / 2;
     // (the imitation forward from snapshots likewise: with 16 groups ImitateSnap spills where TrainSnap does, 196 / 60 / 116 bytes per lane)
-    constexpr int PF = (FwdCfg<F, HID>::WPS == 1) ? PFW : (TRAIN ? (((VALUE || IMITATE) && SNAP) ? PFV : PFT) : 4);   // weight-fragment groups kept in flight per wave
+    constexpr int PF = (FwdCfg<F, HID>::WPS == 1) ? PFW : (TRAIN ? (((VALUE || IMITATE) && SNAP) ? PFV : PFW) : 4);   // weight-fragment groups kept in flight per wave
     constexpr bool OBS = (PERSIST || SNAP);             // the state rows are re-derived from an env snapshot in LDS
     static_assert(F % 8 == 0 && HID % 32 == 0, "shape");
     static_assert(PF * 64 * 4 <= PPO_PACK_PAD, "the ring reads PF groups past the end of a packed weight stream: padding must cover it");
@@ -294,11 +267,11 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
                     asm volatile("" : "+v"(acc));
                     lrelu16(acc);
                     h1[o] = acc;
-                    if (TRAIN && PPO_FWD_STORE) {
+                    if (TRAIN) {
                         float4* dst = a.act1 + ((size_t)tile * NT + o) * 4 * 64;
 #pragma unroll
                         for (int q = 0; q < 4; ++q)
-                            ACT_STORE(dst + q * 64 + lane, make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]));
+                            act_store_nt(dst + q * 64 + lane, make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]));
                     }
                 }
             }
@@ -353,11 +326,11 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
                         }
                         asm volatile("" : "+v"(acc));
                         lrelu16(acc);
-                        if (TRAIN && PPO_FWD_STORE) {
+                        if (TRAIN) {
                             float4* dst = act_out + ((size_t)tile * NT + o) * 4 * 64;
 #pragma unroll
                             for (int q = 0; q < 4; ++q)
-                                ACT_STORE(dst + q * 64 + lane, make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]));
+                                act_store_nt(dst + q * 64 + lane, make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]));
                         }
                         if (last) dot3(o, acc);
                         else {
@@ -389,11 +362,8 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
                 float4 ring[PF];
 #pragma unroll
                 for (int g = 0; g < PF; ++g) ring[g] = wp[(size_t)g * 64];
-#pragma unroll PPO_FWD_OUNROLL
+#pragma unroll 1
                 for (int o = 0; o < NT; ++o) {
-                    // keep the 4 waves of the workgroup on the same 32 KiB weight chunk: their 1 KiB fragment loads then
-                    // hit in the CU's L1 for three of the four waves (speed only; skipped when trip counts differ)
-                    if (PPO_FWD_WGSYNC && a.wg_sync) __builtin_amdgcn_s_barrier();
                     f32x16 acc;
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
@@ -418,11 +388,11 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
                     FSTAMP(2);
                     asm volatile("" : "+v"(acc));
                     lrelu16(acc);
-                    if (TRAIN && PPO_FWD_STORE) {
+                    if (TRAIN) {
                         float4* dst = a.act2 + ((size_t)tile * NT + o) * 4 * 64;
 #pragma unroll
                         for (int q = 0; q < 4; ++q)
-                            ACT_STORE(dst + q * 64 + lane, make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]));
+                            act_store_nt(dst + q * 64 + lane, make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]));
                     }
                     const float4* w3 = sW3 + (half_o * NT + o) * 16;
 #pragma unroll
@@ -539,7 +509,6 @@ static int32_t dispatch_fwd(ppo_policy_s* p, const FwdArgs& args, int64_t B, int
     do {                                                                                                 \
         const int64_t cap = 256 * FwdCfg<FF, HH>::WPS;                                                   \
         const unsigned grid = (unsigned)(need < cap ? need : cap);                                       \
-        a.wg_sync = (!DEEP && B % ((int64_t)grid * 4) == 0) ? 1 : 0;                                     \
         if constexpr (SNAP && FF != 72) {                                                                \
             ppo_set_error("compact rollouts need the built-in env's F = 72"); return PPO_ERR_UNSUPPORTED; \
         } else {                                                                                         \
@@ -683,7 +652,7 @@ int32_t launch_policy_rollout_persistent(ppo_policy_s* p, ppo_env_s* e, ppo_roll
     const int tps = e->H / 32;
     const int64_t N = e->N;
     const int64_t need = (N + 3) / 4;
-    const int wps = (p->HID >= 256) ? 1 : PPO_FWD_WPS_SMALL;     // FwdCfg<72, HID>::WPS
+    const int wps = (p->HID >= 256) ? 1 : 2;                     // FwdCfg<72, HID>::WPS
     const int64_t cap = 256 * wps;
     const unsigned grid = (unsigned)(need < cap ? need : cap);
     const int slots = (int)((N + (int64_t)grid * 4 - 1) / ((int64_t)grid * 4));

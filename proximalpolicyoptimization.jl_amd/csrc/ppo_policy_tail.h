@@ -6,10 +6,6 @@
 #include "ppo_internal.h"
 #include "ppo_device.h"
 
-#ifndef PPO_DPP_REDUCE
-#define PPO_DPP_REDUCE 1
-#endif
-
 struct FwdArgs {
     // inputs
     const int8_t* states;      // FwdSource::Rows: [B][H][F]; RowsIdx: rollout states base (gathered by idx)
@@ -17,7 +13,8 @@ struct FwdArgs {
     const int32_t* idx;        // RowsIdx / SnapIdx: transition id per state
     int64_t B;
     unsigned long long* stamps;   // diagnostic build only (-DPPO_FWD_STAMP)
-    int wg_sync;               // 1: every wave of a workgroup runs the same number of tiles -> per-chunk barriers allowed
+    int unused_wg_sync;        // no kernel reads it (it allowed per-chunk barriers in a build that is gone) and nothing fills it: it
+                               // keeps the offsets below, see profiles/build_knobs_code_identity.txt
     const float4* w1p; const float4* w2p; const float4* b1p; const float4* b2p; const float4* w3p; const float* b3;
     // FwdTail::Probs
     float* probs_out;
@@ -68,7 +65,7 @@ static_assert(sizeof(FwdArgs) == 512 && offsetof(FwdArgs, vdelta_out) == 504, "F
 // and ds_swizzle (no address VGPR) for 16.  Bit-identical results: only the transport changes.
 template <int OFF>
 __device__ __forceinline__ float xor_lane(float v) {
-#if PPO_DPP_REDUCE
+    static_assert(OFF == 1 || OFF == 2 || OFF == 4 || OFF == 8 || OFF == 16, "the steps of a 32-lane butterfly");
     const int x = __float_as_int(v);
     if (OFF == 1) return __int_as_float(__builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false));          // quad_perm:[1,0,3,2]
     if (OFF == 2) return __int_as_float(__builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false));          // quad_perm:[2,3,0,1]
@@ -77,9 +74,7 @@ __device__ __forceinline__ float xor_lane(float v) {
         return __int_as_float(__builtin_amdgcn_update_dpp(t, x, 0x114, 0xF, 0xA, false));                   // row_shr:4 -> banks 1, 3
     }
     if (OFF == 8) return __int_as_float(__builtin_amdgcn_update_dpp(x, x, 0x128, 0xF, 0xF, false));         // row_ror:8
-    if (OFF == 16) return __int_as_float(__builtin_amdgcn_ds_swizzle(x, 0x401F));                            // bitmode: xor 16
-#endif
-    return __shfl_xor(v, OFF);
+    return __int_as_float(__builtin_amdgcn_ds_swizzle(x, 0x401F));                                           // OFF == 16, bitmode: xor 16
 }
 __device__ __forceinline__ float wave32_max(float v) {
     v = fmaxf(v, xor_lane<16>(v)); v = fmaxf(v, xor_lane<8>(v)); v = fmaxf(v, xor_lane<4>(v));

@@ -55,6 +55,27 @@ def test_product_never_imports_oracle():
                 assert "oracle" not in txt.lower().replace("the oracle", "").replace("cpu oracle", ""), (dp, f)
 
 
+def test_every_build_switch_has_a_build():
+    """A build switch exists only while something in the tree can build it: every PPO_<NAME> that the kernel sources test
+    with #ifndef (an override hook: -DPPO_<NAME>=value replaces a default) or #ifdef / #if defined (a diagnostic build)
+    is named in csrc/Makefile or in a file under tools/.  The settled A/B knobs of rounds 1-3 had no such user."""
+    csrc = os.path.join(ROOT, "proximalpolicyoptimization.jl_amd", "csrc")
+    switches = {}
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h")):
+            txt = open(os.path.join(csrc, f), errors="replace").read()
+            for m in re.finditer(r"^[ \t]*#[ \t]*(?:ifndef|ifdef|if[ \t]+!?[ \t]*defined[ \t]*\(?)[ \t]*(PPO_\w+)", txt, flags=re.M):
+                switches.setdefault(m.group(1), f)
+    users = open(os.path.join(csrc, "Makefile")).read()
+    tools = os.path.join(ROOT, "tools")
+    for dp, _, files in os.walk(tools):
+        for f in files:
+            users += open(os.path.join(dp, f), errors="replace").read()
+    names = set(re.findall(r"PPO_\w+", users))
+    orphans = {n: f for n, f in switches.items() if n not in names}
+    assert not orphans, "build switches that nothing in the tree builds: %r" % orphans
+
+
 # ---------------------------------------------------------------- Julia shim: every ccall against the header
 def _split_top(s):
     """split on commas that are not nested in () or {}"""
