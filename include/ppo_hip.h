@@ -402,6 +402,42 @@ int32_t ppo_imitate_train(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, i
                           int32_t rank, int32_t world, ppo_allreduce_fn allreduce, void* allreduce_ctx, double* ce_hist,
                           double* entropy_hist, double* lr_hist);
 
+/* ---------------------------------------------------------------- policy distillation (soft targets) on a rollout buffer
+ * No reference op.  Training towards a DISTRIBUTION over actions per stored state -- a wider or deeper teacher's, the behaviour
+ * policy's recorded one, or rows made on the host (label smoothing): the policy minimises
+ *     -(1 / B_global) sum_i w_i sum_k q'_ik log pi(k | s_i)  +  entropy_weight * (the entropy term of ppo_loss_with_entropy)
+ * q' = the state's target row q on the actions of active quads and 0 elsewhere (mass on an inactive quad is ignored, never an
+ * error), log pi the log-softmax of imitation above, a term with q'_k == 0 contributing exactly 0.  The gradient per logit is
+ * (w / B_global)(p_k Qs - q'_k) with Qs = sum_k q'_k used as it is: rows need not sum to 1, an all-zero row leaves the entropy
+ * term alone, a one-hot row is ppo_imitate_forward_backward.  Nothing divides by a probability.  The loss is the cross-entropy,
+ * not the KL divergence: its floor is the targets' entropy, which the device does not compute.
+ * The target column: [T][N][A] floats in ppo_rollouts_get_full_probs' layout, indexed by transition id, allocated on first use;
+ * every call that writes new transitions into the buffer (the collectors, ppo_rollouts_set, a disk load) marks it not filled.
+ * ppo_rollouts_fill_targets: the teacher's action probabilities (ppo_policy_forward's bits) of all T*N stored states, on the
+ *   device.  Any teacher ppo_policy_forward takes on the buffer's states, bf16 dtype included; on a compact buffer (env
+ *   snapshots) fp32 teachers only (a bf16 one: PPO_ERR_UNSUPPORTED).  teacher F != the buffer's F: PPO_ERR_ARG.
+ * ppo_rollouts_set_targets / _get_targets: upload (every entry finite and >= 0, else PPO_ERR_ARG) and read back.
+ * A buffer with a disk sink attached: PPO_ERR_UNSUPPORTED from every call of this section. */
+int32_t ppo_rollouts_fill_targets(ppo_policy_t teacher, ppo_rollouts_t ro);
+int32_t ppo_rollouts_set_targets(ppo_rollouts_t ro, const float* targets);
+int32_t ppo_rollouts_get_targets(ppo_rollouts_t ro, float* targets_out);
+/* target_source: PPO_TARGETS_COLUMN, the column above; PPO_TARGETS_RECORDED, the behaviour policy's distributions a collector
+ * recorded (record_probs).  A source that is not filled / not recorded for these rollouts: PPO_ERR_ARG; an unknown one:
+ * PPO_ERR_UNSUPPORTED.  weight_mode / adv_mode: as for ppo_imitate_forward_backward.  fp32 students only (a bf16-dtype policy:
+ * PPO_ERR_UNSUPPORTED). */
+#define PPO_TARGETS_COLUMN 0
+#define PPO_TARGETS_RECORDED 1
+/* gradient only, like ppo_imitate_forward_backward; the two loss columns through ppo_last_losses */
+int32_t ppo_distill_forward_backward(ppo_policy_t pol, ppo_rollouts_t ro, const int64_t* sample_idx, int64_t B,
+                                     int64_t B_global, double entropy_weight, int32_t weight_mode, int32_t adv_mode,
+                                     int32_t target_source);
+/* ppo_imitate_train's epoch loop on that objective, same permutation, rank and hook arguments and histories; never stops
+ * early, stores no ratios, leaves ppo_policy_last_train_stats and ppo_policy_last_value_stats alone */
+int32_t ppo_distill_train(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, int64_t batch_size, int32_t num_epochs,
+                          double entropy_weight, int32_t weight_mode, int32_t adv_mode, int32_t target_source,
+                          const int64_t* perm, uint64_t seed, int32_t rank, int32_t world, ppo_allreduce_fn allreduce,
+                          void* allreduce_ctx, double* ce_hist, double* entropy_hist, double* lr_hist);
+
 /* ---------------------------------------------------------------- update statistics and target-KL early stopping
  * No reference op: the reference reports the two losses and the learning rate.  While a target_kl is set on the policy
  * handle (below; +inf = record only), every train forward stores the probability ratio r = p_new(a|s) / p_old(a|s) of

@@ -573,6 +573,38 @@ function imitate_train!(p::HipPolicy, optimizer, r::HipRollouts, batch_size, num
     check(status)
     ch, eh, lh
 end
+# ---- policy distillation (include/ppo_hip.h "policy distillation"; no reference op): training towards a distribution over
+# actions per stored state.  fill_targets!(r, teacher) leaves the teacher's action probabilities of every stored state in the
+# buffer's target column, on the device; targets = :column reads that column, :recorded the distributions a collection with
+# record_probs kept.  The loss is -mean(w sum_k q_k log pi(k|s)) plus the entropy term; weights / advantage as for imitation
+const DISTILL_TARGETS = Dict(:column => Int32(0), :recorded => Int32(1))
+function fill_targets!(r::HipRollouts, teacher::HipPolicy)
+    check(ccall((:ppo_rollouts_fill_targets, LIB), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), teacher.h, r.h))
+end
+function distill_forward_backward(p::HipPolicy, r::HipRollouts, idx::Vector{Int64}; entropy_weight = 0.0, weights = :uniform,
+                                  advantage = :returns, targets = :column, B_global = length(idx))
+    check(ccall((:ppo_distill_forward_backward, LIB), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}, Int64, Int64, Float64, Int32, Int32, Int32),
+                p.h, r.h, idx .- 1, length(idx), B_global, Float64(entropy_weight), IMITATE_WEIGHTS[weights], IMITATE_ADV[advantage],
+                DISTILL_TARGETS[targets]))
+    ce, el = Ref{Float64}(), Ref{Float64}()
+    check(ccall((:ppo_last_losses, LIB), Int32, (Ptr{Cvoid}, Ref{Float64}, Ref{Float64}), p.h, ce, el))
+    ce[], el[]
+end
+# the epoch loop of imitate_train! on that loss -> (ce_history, entropy_history, lr_history); never stops early
+function distill_train!(p::HipPolicy, optimizer, r::HipRollouts, batch_size, num_epochs; entropy_weight = 0.0, weights = :uniform,
+                        advantage = :returns, targets = :column, rank = 0, world = 1, hook = C_NULL)
+    oh = opt_handle(optimizer)
+    ch, eh, lh = zeros(num_epochs), zeros(num_epochs), zeros(num_epochs)
+    status = ccall((:ppo_distill_train, LIB), Int32,
+                   (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Float64, Int32, Int32, Int32, Ptr{Int64}, UInt64, Int32, Int32,
+                    Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                   p.h, oh, r.h, batch_size, num_epochs, Float64(entropy_weight), IMITATE_WEIGHTS[weights], IMITATE_ADV[advantage],
+                   DISTILL_TARGETS[targets], C_NULL, SEED[], rank, world, hook, C_NULL, ch, eh, lh)
+    opt_done!(optimizer)
+    check(status)
+    ch, eh, lh
+end
 # ---- update statistics (include/ppo_hip.h "update statistics"; no reference op): approx_kl = mean((r - 1) - log r),
 # old_approx_kl = mean(-log r) and clip_fraction = mean(|r - 1| > epsilon) of every epoch of the latest ppo_train!, and the
 # target-KL stop: ppo_train! ends after the first epoch whose approx_kl exceeds target_kl (nothing / 0 = off, Inf = record only)

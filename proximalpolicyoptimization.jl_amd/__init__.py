@@ -64,6 +64,7 @@ __all__ = [
     "beam_search_states_distinct_",
     "collect_paths_",
     "imitate_forward_backward", "imitate_train_", "imitation_loss",
+    "fill_targets_", "distill_forward_backward", "distill_train_", "distillation_loss",
     "check_selection", "selecting", "SELECT_RULES",
     "check_truncation", "DEFAULT_TRUNCATION",
 ]
@@ -612,6 +613,45 @@ def imitation_loss(logits, mask, actions, weights=None):
     return float(-np.mean(w * logp, dtype=np.float32))
 
 
+def _bool_mask(mask, A):
+    m = np.asarray(mask)
+    if m.ndim == 1:
+        bits = m.astype(np.uint32)
+        m = ((bits[:, None] >> (np.arange(A) // 16).astype(np.uint32)[None, :]) & 1).astype(bool)
+    return m.astype(bool)
+
+
+def distillation_loss(logits, mask, targets, weights=None, floor=False):
+    """The distillation (soft-target cross-entropy) loss column 0 on given logits, in float32 arithmetic as the device forms it
+    (plain numpy host mirror) -> float: -mean_i(w_i sum_k q'_ik log pi(k | s_i)), q' the target row on the allowed actions and
+    0 elsewhere (mass on a masked action is ignored), log pi the log-softmax over the allowed actions, (l - max l) -
+    log sum exp(l - max l); a term with q'_k == 0 is exactly 0, so the loss is finite where exp underflows.  logits, targets
+    [B, A] (targets finite and >= 0, not necessarily normalised); mask and weights as in imitation_loss.  floor=True: returns
+    (loss, floor) with floor = mean_i(w_i * -sum_k q'_ik log q'_ik), the weighted entropy of the kept targets: the value the
+    cross-entropy of normalised rows cannot go below (loss - floor is then the weighted KL(q' || pi)); the device does not
+    compute it."""
+    l = np.asarray(logits, np.float32)
+    B, A = l.shape
+    m = _bool_mask(mask, A)
+    q = np.asarray(targets, np.float32)
+    if q.shape != l.shape:
+        raise PPOError(-1, "AssertionError: distillation_loss: targets must have the logits' shape")
+    if not np.all(np.isfinite(q)) or (q < 0).any():
+        raise PPOError(-1, "AssertionError: distillation_loss: every target entry must be finite and >= 0")
+    w = np.ones(B, np.float32) if weights is None else np.maximum(np.asarray(weights, np.float32), np.float32(0))
+    q = np.where(m, q, np.float32(0))
+    mx = np.where(m, l, np.float32(-np.inf)).max(axis=1)
+    S = np.where(m, np.exp(np.where(m, l - mx[:, None], np.float32(0)), dtype=np.float32), np.float32(0)).sum(axis=1, dtype=np.float32)
+    logp = (l - mx[:, None]) - np.log(S, dtype=np.float32)[:, None]
+    ce = np.where(q == 0, np.float32(0), q * np.where(q == 0, np.float32(0), logp)).sum(axis=1, dtype=np.float32)
+    loss = float(-np.mean(w * ce, dtype=np.float32))
+    if not floor:
+        return loss
+    with np.errstate(divide="ignore", invalid="ignore"):
+        h = -np.where(q == 0, 0.0, q.astype(np.float64) * np.log(q.astype(np.float64))).sum(axis=1)
+    return loss, float(np.mean(w.astype(np.float64) * h))
+
+
 # ------------------------------------------------------------------ optimiser
 class Adam:
     """Flux legacy Adam(eta, beta, epsilon)."""
@@ -1090,6 +1130,30 @@ class BufferRollouts:
         out = np.empty((T, N, self._env.A), np.float32)
         call("ppo_rollouts_get_full_probs", self._h, _p(out, _lib.c_f32p))
         return out
+
+    @property
+    def action_targets(self):
+        """The distillation target column [T,N,A] (fill_targets_ / set_action_targets), in full_probs' layout."""
+        T, N = self.dims()
+        out = np.empty((T, N, self._env.A), np.float32)
+        call("ppo_rollouts_get_targets", self._h, _p(out, _lib.c_f32p))
+        return out
+
+    def set_action_targets(self, q):
+        """Upload distillation targets q [T,N,A]: one row per stored transition (valid or not), every entry finite and >= 0.
+        Rows need not be normalised; mass on the actions of inactive quads is ignored by the loss."""
+        if self._h is None:
+            raise PPOError(-1, "AssertionError: set_action_targets: empty rollout buffer")
+        T, N = self.dims()
+        q = np.asarray(q)
+        if q.shape != (T, N, self._env.A):
+            raise PPOError(-1, "AssertionError: set_action_targets: targets must have shape [T,N,A] = %r, got %r" % ((T, N, self._env.A), q.shape))
+        q = np.ascontiguousarray(q, np.float32)
+        if not np.all(np.isfinite(q)):
+            raise PPOError(-1, "AssertionError: set_action_targets: every target entry must be finite")
+        if (q < 0).any():
+            raise PPOError(-1, "AssertionError: set_action_targets: every target entry must be >= 0")
+        call("ppo_rollouts_set_targets", self._h, _p(q, _lib.c_f32p))
 
     def index(self):
         """Dataset order: flat transition ids t*N+n of the valid transitions."""
@@ -1587,6 +1651,78 @@ def imitate_train_(policy, optimizer, dataset, batch_size, num_epochs, entropy_w
     try:
         call("ppo_imitate_train", policy._h, oh, dataset.rollouts._h, int(batch_size), int(num_epochs), float(entropy_weight),
              wm, am, _p(pp, _lib.c_i64p) if pp is not None else None, int(seed), int(rank), int(world), fn, None,
+             _p(ch, _lib.c_f64p), _p(eh, _lib.c_f64p), _p(lh, _lib.c_f64p))
+    finally:
+        optimizer._pull()
+    if verbose:
+        for e in range(num_epochs):
+            print("EPOCH : %d \t CE LOSS : %1.4f\t ENTROPY LOSS : %1.4f \t LR : %1.1e" % (e + 1, ch[e], eh[e], lh[e]))
+    return list(ch), list(eh), list(lh)
+
+
+DISTILL_TARGETS = {"column": 0, "recorded": 1}
+
+
+def _distill_modes(weights, advantage, targets):
+    """(weight_mode, adv_mode, target_source) of the distillation entry points, refused like the library refuses them."""
+    if weights not in IMITATION_WEIGHTS:
+        raise PPOError(-4, "distill weights must be one of %s" % sorted(IMITATION_WEIGHTS))
+    a = _adv_mode(advantage)
+    if advantage.endswith("_normalised"):
+        raise PPOError(-4, "distill: the normalised advantage modes are not supported")
+    if targets not in DISTILL_TARGETS:
+        raise PPOError(-4, "distill targets must be one of %s" % sorted(DISTILL_TARGETS))
+    return IMITATION_WEIGHTS[weights], a, DISTILL_TARGETS[targets]
+
+
+def fill_targets_(rollouts, teacher):
+    """Fills the rollouts' distillation target column with `teacher`'s action probabilities of every stored state, on the
+    device (no host trip): what batch_action_probabilities(teacher, ...) gives for those states, bit for bit.  Any HipPolicy
+    that can read the buffer's states (same F, 4 outputs; any width, depth, dtype) -- on compact storage fp32 teachers only.
+    A later collection into the buffer, or set_columns, marks the column not filled.  Returns nothing."""
+    if not isinstance(rollouts, BufferRollouts) or rollouts._h is None:
+        raise PPOError(-4, "fill_targets_ needs a filled BufferRollouts")
+    if not isinstance(teacher, HipPolicy):
+        _not_implemented("action_probabilities")
+    call("ppo_rollouts_fill_targets", teacher._h, rollouts._h)
+
+
+def distill_forward_backward(policy, dataset, batch_indices, entropy_weight=0.0, weights="uniform", advantage="returns",
+                             targets="column", B_global=None):
+    """Gradient (no update) of the distillation loss on dataset[batch_indices] (1-based): the cross-entropy
+    -(1 / B_global) sum w sum_k q'_k log pi(k | s) against each state's target row plus the entropy term of
+    ppo_loss_with_entropy; leaves it in policy.grad() and returns (cross_entropy, entropy_weight * entropy loss).  targets:
+    "column" (fill_targets_ / set_action_targets) or "recorded" (the distributions a collector recorded with
+    record_probs=True).  weights and advantage as in imitate_forward_backward."""
+    wm, am, ts = _distill_modes(weights, advantage, targets)
+    ii = np.ascontiguousarray(np.asarray(batch_indices, np.int64) - 1)
+    call("ppo_distill_forward_backward", policy._h, dataset.rollouts._h, _p(ii, _lib.c_i64p), ii.size,
+         int(B_global or ii.size), float(entropy_weight), wm, am, ts)
+    a, b = C.c_double(0), C.c_double(0)
+    call("ppo_last_losses", policy._h, C.byref(a), C.byref(b))
+    return a.value, b.value
+
+
+def distill_train_(policy, optimizer, dataset, batch_size, num_epochs, entropy_weight=0.0, weights="uniform",
+                   advantage="returns", targets="column", perm=None, seed=0, parallel=None, verbose=True):
+    """imitate_train_'s epoch loop on the distillation loss (distill_forward_backward) -> (ce_history, entropy_history,
+    lr_history), num_epochs entries each: never stops early, leaves policy.last_train_stats() and last_value_stats() alone.
+    The history is the cross-entropy, whose floor is the targets' entropy (distillation_loss(..., floor=True)), not the KL."""
+    wm, am, ts = _distill_modes(weights, advantage, targets)
+    oh = optimizer._handle(policy)
+    n = len(dataset)
+    pp = _perm0(perm, num_epochs, n)
+    ch, eh, lh = (np.zeros(num_epochs, np.float64) for _ in range(3))
+    rank, world, fn, keep = 0, 1, _lib.ALLREDUCE_FN(0), None
+    if parallel is not None and (parallel.world > 1 or parallel.force_hook):
+        rank, world = parallel.rank, parallel.world
+        keep = parallel.make_hook(policy)
+        fn = keep
+    if world == 1:                                         # else inside the library, on the shortest shard (see ppo_train_)
+        _check_batch_size(batch_size, n)
+    try:
+        call("ppo_distill_train", policy._h, oh, dataset.rollouts._h, int(batch_size), int(num_epochs), float(entropy_weight),
+             wm, am, ts, _p(pp, _lib.c_i64p) if pp is not None else None, int(seed), int(rank), int(world), fn, None,
              _p(ch, _lib.c_f64p), _p(eh, _lib.c_f64p), _p(lh, _lib.c_f64p))
     finally:
         optimizer._pull()

@@ -134,6 +134,12 @@ SIGNATURES = {
     "ppo_imitate_forward_backward": [H, H, c_i64p, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_int32],
     "ppo_imitate_train": [H, H, H, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_int32, c_i64p, C.c_uint64, C.c_int32,
                           C.c_int32, ALLREDUCE_FN, C.c_void_p, c_f64p, c_f64p, c_f64p],
+    "ppo_rollouts_fill_targets": [H, H],
+    "ppo_rollouts_set_targets": [H, c_f32p],
+    "ppo_rollouts_get_targets": [H, c_f32p],
+    "ppo_distill_forward_backward": [H, H, c_i64p, C.c_int64, C.c_int64, C.c_double, C.c_int32, C.c_int32, C.c_int32],
+    "ppo_distill_train": [H, H, H, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, c_i64p, C.c_uint64,
+                          C.c_int32, C.c_int32, ALLREDUCE_FN, C.c_void_p, c_f64p, c_f64p, c_f64p],
     "ppo_rollouts_attach_disk": [H, C.c_char_p, C.c_int32],
     "ppo_rollouts_detach_disk": [H],
     "ppo_set_disk_async": [C.c_int32],

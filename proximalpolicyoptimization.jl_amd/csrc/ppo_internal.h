@@ -241,6 +241,10 @@ struct ppo_rollouts_s {
     DevBuf<float> boot;        // [T][N] boot_vals scattered to their transitions (or host-supplied), 0 elsewhere
     int64_t boot_T = -1;       // T the boot column was computed for (-1: none)
     DevBuf<double> stats_part; // workspace and result of k_value_moments (ppo_stats.hip)
+    // policy distillation: a target distribution per transition, in full_probs' layout; allocated on first use
+    DevBuf<float> targets;     // [T][N][A] filled by ppo_rollouts_fill_targets (a teacher's probabilities) or ppo_rollouts_set_targets
+    int64_t targets_T = -1;    // T the targets were filled for (-1: none)
+    int64_t probs_T = -1;      // T full_probs was recorded for (-1: the buffer's contents were collected without record_probs)
     bool all_valid = true;
     DiskSink* sink = nullptr;  // optional out-of-core store (ppo_rollouts_attach_disk)
     ~ppo_rollouts_s();
@@ -254,7 +258,10 @@ extern "C" bool want_compact(const ppo_rollouts_s* ro, int64_t T);
 extern "C" int32_t check_internal_host(int32_t Q, int64_t count, const int8_t* score, const int8_t* degree, const uint32_t* active);
 // the buffer now holds T steps, or (scratch_used) row 0 served a call as scratch and nothing is held: every column cached
 // for the previous contents is stale
-inline void rollouts_filled(ppo_rollouts_s* ro, int64_t T) { ro->T = T; ro->adv_T = -1; ro->values_T = -1; ro->boot_T = -1; }
+// (a collector that recorded the whole distributions sets probs_T behind this call)
+inline void rollouts_filled(ppo_rollouts_s* ro, int64_t T) {
+    ro->T = T; ro->adv_T = -1; ro->values_T = -1; ro->boot_T = -1; ro->targets_T = -1; ro->probs_T = -1;
+}
 inline void rollouts_scratch_used(ppo_rollouts_s* ro) { rollouts_filled(ro, 0); ro->len = 0; }
 
 // out-of-core store hooks used by ppo_collect_rollouts (ppo_disk.hip)
@@ -477,8 +484,9 @@ const PpoKnobs& ppo_knobs();
 
 // What one training pass minimises: the policy's clipped PPO loss with its entropy bonus, or a critic's (a ppo_policy_t
 // read as a state value) Flux.mse against a target column, or the policy's cross-entropy on the buffer's actions (behaviour
-// cloning).  TrainObjective: the loss inputs of one pass
-enum class Objective { Policy, Value, Imitate };
+// cloning), or its cross-entropy against a target distribution per state (policy distillation).
+// TrainObjective: the loss inputs of one pass
+enum class Objective { Policy, Value, Imitate, Distill };
 struct TrainObjective {
     Objective kind;
     // Policy
@@ -494,13 +502,15 @@ struct TrainObjective {
     float* vdelta_dst = nullptr;       // where the pass stores V - vold per state while the clip is set (nullptr: nowhere)
     // Imitate (entropy_weight and adv_mode as for Policy; adv_mode names the weights' column, read in the weighted form only)
     int32_t weight_mode = PPO_IMITATE_UNIFORM;
+    // Distill (entropy_weight, adv_mode and weight_mode as for Imitate): the target rows [T*N][A] by transition id
+    const float* distill_targets = nullptr;
 };
 
 // The kernels that run one training minibatch.  TrainTile runs forward, loss and backward-data in one launch and is
 // always followed by Wgrad (k_policy_wgrad<TR = true>).  Objective::Value: the forward is always Fwd -- k_policy_fwd in a
 // value-train mode, the only forward with one -- followed by the backward the policy would take at that shape and size; where
 // that is the one-tile pass, whose weight-gradient kernel only runs from inside it, the three-product Small backward.
-// Objective::Imitate: likewise, k_policy_fwd in an imitation mode (12 / 13).
+// Objective::Imitate: likewise, k_policy_fwd in an imitation mode (12 / 13).  Objective::Distill: likewise, modes 17 / 18.
 enum class TrainFwd { None, TrainTile, X6S, X6T, X6, Split, Fwd, Bf16 };
 enum class TrainBwd { None, Wgrad, Small, X6, Fused, Bf16 };
 struct TrainRoute { TrainFwd fwd; TrainBwd bwd; const char* err; };      // err: why fwd is None
@@ -509,12 +519,13 @@ TrainRoute train_route(int32_t dtype, int F, int HID, int L, int H, bool compact
 
 // k_policy_fwd's MODE (k_policy_fwd_bf16 has the first five).  The numbers are what kernel traces, the route strings and DESIGN.md
 // print.  A mode is two independent choices, where the state comes from and what runs behind the logits: fwd_traits is the table.
-// The clipped value loss, the forced step, imitation and the selection rules are modes of their own rather than runtime tests in
-// a tail because every such test moved the register allocation of the instantiations next to it, measurably (DESIGN.md 7k .. 7n)
+// The clipped value loss, the forced step, imitation, distillation and the selection rules are modes of their own rather than
+// runtime tests in a tail because every such test moved the register allocation of the instantiations next to it, measurably
+// (DESIGN.md 7k .. 7n, 7q)
 enum class FwdMode : int {
     Probs = 0, Sample = 1, Train = 2, Persistent = 3, TrainSnap = 4, ValuePredict = 5, ValueTrain = 6, ValuePredictSnap = 7,
     ValueTrainSnap = 8, ValueTrainClip = 9, ValueTrainClipSnap = 10, Forced = 11, Imitate = 12, ImitateSnap = 13, Tempered = 14,
-    Greedy = 15, Truncated = 16
+    Greedy = 15, Truncated = 16, Distill = 17, DistillSnap = 18, ProbsSnap = 19
 };
 enum class FwdSource {
     Rows,       // observation rows [B][H][F] in storage order
@@ -524,7 +535,8 @@ enum class FwdSource {
     SnapIdx     // ... fetched through idx, the rows left in xs_out (minibatch order) for the backward
 };
 enum class FwdTail {      // policy_tail, or value_tail for the three Value*
-    Probs, Sample, SamplePersistent, Train, Forced, Imitate, Tempered, Greedy, Truncated, ValuePredict, ValueTrain, ValueTrainClip
+    Probs, Sample, SamplePersistent, Train, Forced, Imitate, Tempered, Greedy, Truncated, ValuePredict, ValueTrain, ValueTrainClip,
+    Distill
 };
 struct FwdTraits { FwdSource src; FwdTail tail; };
 constexpr FwdTraits fwd_traits(FwdMode m) {
@@ -546,13 +558,18 @@ constexpr FwdTraits fwd_traits(FwdMode m) {
     case FwdMode::Tempered:           return {FwdSource::Rows, FwdTail::Tempered};
     case FwdMode::Greedy:             return {FwdSource::Rows, FwdTail::Greedy};
     case FwdMode::Truncated:          return {FwdSource::Rows, FwdTail::Truncated};
+    case FwdMode::Distill:            return {FwdSource::RowsIdx, FwdTail::Distill};
+    case FwdMode::DistillSnap:        return {FwdSource::SnapIdx, FwdTail::Distill};
+    case FwdMode::ProbsSnap:          return {FwdSource::Snap, FwdTail::Probs};
     }
     return {FwdSource::Rows, FwdTail::Probs};
 }
 constexpr bool src_snapshot(FwdSource s) { return s == FwdSource::Snap || s == FwdSource::SnapIdx; }
 constexpr bool tail_value(FwdTail t) { return t == FwdTail::ValuePredict || t == FwdTail::ValueTrain || t == FwdTail::ValueTrainClip; }
 // train forward: saves the activations, writes dY and the loss terms
-constexpr bool tail_trains(FwdTail t) { return t == FwdTail::Train || t == FwdTail::Imitate || t == FwdTail::ValueTrain || t == FwdTail::ValueTrainClip; }
+constexpr bool tail_trains(FwdTail t) {
+    return t == FwdTail::Train || t == FwdTail::Imitate || t == FwdTail::Distill || t == FwdTail::ValueTrain || t == FwdTail::ValueTrainClip;
+}
 // logits times 1 / temperature in front of the softmax
 constexpr bool tail_tempers(FwdTail t) { return t == FwdTail::Tempered || t == FwdTail::Greedy || t == FwdTail::Truncated; }
 // rand(Categorical): the Philox uniform and the CDF walk
@@ -567,6 +584,7 @@ constexpr FwdMode fwd_train_mode(Objective obj, bool compact, bool clipped = fal
         if (clipped) return compact ? FwdMode::ValueTrainClipSnap : FwdMode::ValueTrainClip;
         return compact ? FwdMode::ValueTrainSnap : FwdMode::ValueTrain;
     case Objective::Imitate: return compact ? FwdMode::ImitateSnap : FwdMode::Imitate;
+    case Objective::Distill: return compact ? FwdMode::DistillSnap : FwdMode::Distill;
     default: return compact ? FwdMode::TrainSnap : FwdMode::Train;
     }
 }
@@ -587,6 +605,13 @@ int32_t launch_value_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_
 // max(weight_col[transition], 0) (nullptr: uniform weights), plus the policy's entropy term
 int32_t launch_imitate_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
                                  double entropy_weight, const float* weight_col);
+// distillation train forward (k_policy_fwd's FwdMode::Distill / DistillSnap): cross-entropy against the target row
+// target_ptr[transition][A] (full_probs' layout), weighted like imitation's, plus the policy's entropy term
+int32_t launch_distill_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
+                                 double entropy_weight, const float* weight_col, const float* target_ptr);
+// launch_policy_probs from env snapshots [B][2V] in storage order (k_policy_fwd's FwdMode::ProbsSnap; fp32 policies, F = 72)
+int32_t launch_policy_probs_snap(ppo_policy_s* p, const int8_t* cstate_dev, const uint32_t* active_dev, const int8_t* tmpl_dev,
+                                 int32_t V, int64_t B, int32_t H, float* probs_dev);
 // the same fused backward with its row contractions (dW2, dW1) as split-fp32 products on the bf16 matrix pipe
 // (ppo_policy_bwd_x6.hip)
 int32_t launch_policy_bwd_x6(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B);

@@ -803,6 +803,7 @@ int32_t ppo_collect_paths(ppo_rollouts_t ro, ppo_env_t env, ppo_policy_t pol, in
         PPO_TRY(launch_env_step_forced(env, ac, d_ints.p, t, ro->rewards.p + t * N, ro->done.p + t * N, ro->valid.p + t * N, d_err));
     }
     rollouts_filled(ro, T);
+    if (record_probs) ro->probs_T = T;
     PPO_TRY(set_index_env_major(ro, T));          // env-major concatenation of the paths: the episodes mode's order
     PPO_TRY(launch_returns_tn(ro->rewards.p, ro->done.p, ro->returns.p, T, N, discount, discount_is_f32));
     int32_t f = 0;

@@ -37,6 +37,13 @@ static __device__ __forceinline__ void act_store_nt(float4* p, float4 v) {
 template <int F, int HID>
 struct FwdCfg { static constexpr int WPS = (HID >= 256 || F > 128) ? 1 : 2; };
 
+// FwdTail::Distill: whether an instantiation holds the state's target row (4 * TPS registers) across the tile loop.  Every one
+// does without scratch but the deep HID = 128 forward of Q = 32 rows at two waves per SIMD with the 16-group ring (24 bytes per
+// lane with the early fetch): that one fetches the row behind the loop.  (Its snapshot sibling runs the 8-group ring and fits.)
+constexpr bool distill_row_early(int F, int HID, int TPS, int DEEP, bool SNAP) {
+    return !(F == 72 && HID == 128 && TPS == 4 && DEEP && !SNAP);
+}
+
 // TPS = 32-row tiles per state (H = 32*TPS half-edges, A = 128*TPS actions): the wave walks the tiles of its
 // state one after the other, keeps the 4*TPS logits per lane, and runs softmax / sampling / loss once per state.
 // DEEP = 1: Policy(F, HID, num_hidden_layers != 2, 4) (test/policy.jl:9-19).  The hidden->hidden block becomes a loop over
@@ -59,6 +66,7 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
     constexpr bool TRAIN = tail_trains(TAIL);           // train forward: saves activations, loss tail
     constexpr bool VALUE = tail_value(TAIL);            // critic: value_tail
     constexpr bool IMITATE = TAIL == FwdTail::Imitate;
+    constexpr bool DISTILL = TAIL == FwdTail::Distill;
     constexpr bool GATHER = SRC == FwdSource::RowsIdx;
     constexpr bool SNAP = src_snapshot(SRC), SNAPX = SRC == FwdSource::SnapIdx;
     constexpr bool PERSIST = SRC == FwdSource::EnvSlots;    // persistent rollout: T steps of the wave's envs, their state in LDS slots
@@ -68,7 +76,12 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
     // re-derivation it does not fit the 256 registers)
     constexpr int PFV = PFW / 2;
     // (the imitation forward from snapshots likewise: with 16 groups ImitateSnap spills where TrainSnap does, 196 / 60 / 116 bytes per lane)
-    constexpr int PF = (FwdCfg<F, HID>::WPS == 1) ? PFW : (TRAIN ? (((VALUE || IMITATE) && SNAP) ? PFV : PFW) : 4);   // weight-fragment groups kept in flight per wave
+    // (the distillation forward from snapshots takes the same ring: ImitateSnap's registers plus the target row)
+    constexpr int PF = (FwdCfg<F, HID>::WPS == 1) ? PFW : (TRAIN ? (((VALUE || IMITATE || DISTILL) && SNAP) ? PFV : PFW) : 4);   // weight-fragment groups kept in flight per wave
+    // distillation: the state's target row (TPS float4 per lane) is fetched in front of the tile loop, ahead of the activation
+    // stores like TailPre, where holding it across the loop costs no scratch; else behind the loop, paying the wait for the
+    // stores queued in front of it (vmcnt is one in-order queue).  DESIGN.md 7q lists which instantiation got which
+    constexpr bool QPRE = DISTILL && distill_row_early(F, HID, TPS, DEEP, SNAP);
     constexpr bool OBS = (PERSIST || SNAP);             // the state rows are re-derived from an env snapshot in LDS
     static_assert(F % 8 == 0 && HID % 32 == 0, "shape");
     static_assert(PF * 64 * 4 <= PPO_PACK_PAD, "the ring reads PF groups past the end of a packed weight stream: padding must cover it");
@@ -183,6 +196,18 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
         if constexpr (TAIL == FwdTail::Forced) forced.ab = a.actions[state];
         // imitation: the stored action and its weight (a.adv == nullptr: uniform), ahead of the activation stores like vtarget
         if constexpr (IMITATE) { forced.ab = a.actions[sid]; forced.adv = a.adv ? a.adv[sid] : 1.0f; }
+        // distillation: the weight likewise, and the target row: TPS coalesced float4 loads per lane (both lane halves read the
+        // same 512 B of a tile, as both hold the same logits)
+        [[maybe_unused]] float4 qrow[DISTILL ? TPS : 1];
+        [[maybe_unused]] const float4* qsrc = nullptr;
+        if constexpr (DISTILL) {
+            forced.adv = a.adv ? a.adv[sid] : 1.0f;
+            qsrc = reinterpret_cast<const float4*>(a.targets) + (size_t)sid * (32 * TPS) + j;
+            if constexpr (QPRE) {
+#pragma unroll
+                for (int ts = 0; ts < TPS; ++ts) qrow[ts] = qsrc[ts * 32];
+            }
+        }
         float l[TPS][4];
         // multi-tile states: the tile loop stays a real loop (no 4x code blow-up, no cross-tile hoisting that
         // would spill); the 4 logits per lane of each tile are parked in LDS and re-read after the loop
@@ -422,6 +447,13 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
         FSTAMP(4);
         int sampled = 0;
         if constexpr (VALUE) value_tail<TAIL, TPS>(a, state, act, l, lane, j, h, out_index, vtarget, vold);
+        else if constexpr (DISTILL) {
+            if constexpr (!QPRE) {
+#pragma unroll
+                for (int ts = 0; ts < TPS; ++ts) qrow[ts] = qsrc[ts * 32];
+            }
+            sampled = policy_tail<TAIL, TPS, false>(a, state, sid, act, l, lane, j, h, 0u, out_index, &forced, nullptr, qrow);
+        }
         else if constexpr (TAIL == FwdTail::Forced || IMITATE) sampled = policy_tail<TAIL, TPS, false>(a, state, sid, act, l, lane, j, h, 0u, out_index, &forced);
         else sampled = policy_tail<TAIL, TPS, false>(a, state, sid, act, l, lane, j, h, tick_val, out_index);
         if (PERSIST) {
@@ -705,6 +737,7 @@ static int32_t dispatch_fwd_mode(FwdMode mode, ppo_policy_s* p, const FwdArgs& a
 #define MODE_CASE(M) case FwdMode::M: return dispatch_fwd<FwdMode::M>(p, a, B, tps)
     MODE_CASE(TrainSnap); MODE_CASE(Train); MODE_CASE(Imitate); MODE_CASE(ImitateSnap); MODE_CASE(ValuePredict);
     MODE_CASE(ValuePredictSnap); MODE_CASE(ValueTrainClip); MODE_CASE(ValueTrainClipSnap); MODE_CASE(ValueTrain); MODE_CASE(ValueTrainSnap);
+    MODE_CASE(Distill); MODE_CASE(DistillSnap); MODE_CASE(ProbsSnap);
 #undef MODE_CASE
     default: ppo_set_error("k_policy_fwd: not a mode chosen at run time"); return PPO_ERR_ARG;
     }
@@ -753,6 +786,31 @@ int32_t launch_imitate_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int3
     a.c_over_B = (float)(entropy_weight / (double)B_global);
     ProfScope ps("k_policy_fwd_imitate");
     return dispatch_fwd_mode(fwd_train_mode(Objective::Imitate, ro->compact), p, a, B, ro->H / 32);
+}
+
+// distillation train forward (FwdMode::Distill / DistillSnap): the imitation forward with a target row per state,
+// target_ptr[transition][A], in place of the stored action.  Only this fp32-MFMA forward has the mode
+int32_t launch_distill_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
+                                 double entropy_weight, const float* weight_col, const float* target_ptr) {
+    FwdArgs a = {};
+    fill_train(p, ro, idx_dev, B, B_global, a);
+    a.adv = weight_col; a.targets = target_ptr;
+    a.c_over_B = (float)(entropy_weight / (double)B_global);
+    ProfScope ps("k_policy_fwd_distill");
+    return dispatch_fwd_mode(fwd_train_mode(Objective::Distill, ro->compact), p, a, B, ro->H / 32);
+}
+
+// probs_dev[b][A] of B states held as env snapshots [B][2V] in storage order (FwdMode::ProbsSnap: what ValuePredictSnap is to
+// ValuePredict): launch_policy_probs' bits for the rows the snapshots expand to.  fp32 policies, F = 72
+int32_t launch_policy_probs_snap(ppo_policy_s* p, const int8_t* cstate_dev, const uint32_t* active_dev, const int8_t* tmpl_dev,
+                                 int32_t V, int64_t B, int32_t H, float* probs_dev) {
+    if (B <= 0) return PPO_OK;
+    FwdArgs a = {};
+    fill_weights(p, a);
+    a.active = active_dev; a.B = B; a.probs_out = probs_dev;
+    a.cstate = cstate_dev; a.env_tmpl = tmpl_dev; a.envV = V; a.envQ = V / 4; a.env_slots = 1;
+    ProfScope ps("k_policy_fwd_probs_snap");
+    return dispatch_fwd_mode(FwdMode::ProbsSnap, p, a, B, H / 32);
 }
 
 // ---- critic (the Value* modes): only this fp32-MFMA forward has them

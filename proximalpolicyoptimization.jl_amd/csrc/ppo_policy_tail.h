@@ -55,9 +55,12 @@ struct FwdArgs {
     // indexed by transition id like vtarget (nullptr: plain mse); vclip = the clip range; vdelta_out[state] = V - vold of
     // every state of the minibatch (per-epoch value-clip statistics, ppo_stats.hip; nullptr: not stored).  Appended last
     const float* vold; float vclip; float* vdelta_out;
+    // FwdTail::Distill: the target distributions [T*N][A] by transition id, entry 128 ts + 4 j + i of a row as probs_out and
+    // full_probs hold it.  Appended last
+    const float* targets;
 };
 // the aliases move nothing: these are the layout every kernel was built with
-static_assert(sizeof(FwdArgs) == 512 && offsetof(FwdArgs, vdelta_out) == 504, "FwdArgs layout");
+static_assert(sizeof(FwdArgs) == 520 && offsetof(FwdArgs, vdelta_out) == 504 && offsetof(FwdArgs, targets) == 512, "FwdArgs layout");
 
 // value of lane (lane ^ OFF), OFF < 32.  Same lane mapping as __shfl_xor (which hipcc lowers to ds_bpermute_b32: an
 // LDS round trip of ~100+ cycles per step, fully exposed in the one-or-two-waves-per-SIMD kernels here), but as DPP
@@ -121,6 +124,8 @@ __device__ __forceinline__ float smoothed_entropy(const float (&p)[TPS][4], floa
 // Forced (teacher-forced step): Sample's outputs for the action in pre->ab instead of a sampled one; returns it.
 // Train: the loss and dL/dlogits of ppo_loss_with_entropy, whatever the source of the state.
 // Imitate: Train's outputs for the cross-entropy of the action in pre->ab, weighted by max(pre->adv, 0); pre is required.
+// Distill: Train's outputs for the cross-entropy against the state's target row, weighted like Imitate; pre (adv)
+// and qrow are required: qrow[ts] = entries 128 ts + 4 j .. + 3 of a.targets' row sid, the caller's fetch (registers).
 // Tempered / Greedy (selection rules): Sample on the logits times a.inv_temperature; Tempered samples like Sample,
 // Greedy takes the first maximum of p instead (tick_val unused).  l is scaled in place.
 // Truncated: Tempered on the top-k / nucleus truncation of the tempered p, renormalised; a.top_k (0: all),
@@ -132,7 +137,8 @@ template <FwdTail TAIL, int TPS, bool DYBF16>
 __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state, const int64_t sid, const uint32_t act,
                                            float (&l)[TPS][4], const int lane, const int j, const int h,
                                            const uint32_t tick_val = 0u, const int64_t out_index = 0,
-                                           const TailPre* pre = nullptr, float4* dy_copy = nullptr) {
+                                           const TailPre* pre = nullptr, float4* dy_copy = nullptr,
+                                           const float4* qrow = nullptr) {
     static_assert(!tail_value(TAIL), "the critic's tails are value_tail's");
     int sampled = 0;
     constexpr int A = 128 * TPS;
@@ -391,6 +397,58 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
             }
         }
         if (lane == 0) { a.loss_terms[state * 2] = (double)(w * logp); a.loss_terms[state * 2 + 1] = (double)(-hl); }
+    }
+    if (TAIL == FwdTail::Distill) {
+        // policy distillation: cross-entropy against a target distribution q over the state's actions,
+        // -w sum_k q'_k log pi(k|s), with Train's entropy term.  q' = q on the rows of active quads and 0 elsewhere (mass on an
+        // inactive row is ignored); Qs = sum q' in the softmax's own reduction order, used as it is: an unnormalised row, or one
+        // that lost mass to the mask, gets the exact gradient of the loss as stated.  log pi in the log-softmax form
+        // (l_k - m) - log S, a term with q'_k == 0 contributing exactly 0 (selected, not multiplied), and
+        // dL/dlogit_k = (w / B_global)(p_k Qs - q'_k): nothing divides by a probability, so a target on an action whose
+        // exp(l - m) underflows keeps a finite loss and gradient.  A one-hot row is Imitate term for term (Qs == 1)
+        const float w = fmaxf(pre->adv, 0.0f);
+        float q[TPS][4];
+        float qs = 0.0f;
+#pragma unroll
+        for (int ts = 0; ts < TPS; ++ts) {
+            const float4 v = qrow[ts];
+            q[ts][0] = on[ts] ? v.x : 0.0f; q[ts][1] = on[ts] ? v.y : 0.0f;
+            q[ts][2] = on[ts] ? v.z : 0.0f; q[ts][3] = on[ts] ? v.w : 0.0f;
+            const float st = ((q[ts][0] + q[ts][1]) + q[ts][2]) + q[ts][3];
+            qs = (ts == 0) ? st : qs + st;                   // tile partials in tile order, then the butterfly
+        }
+        qs = wave32_sum(qs);
+        const float ls = logf(ssum);
+        float ce = 0.0f;
+#pragma unroll
+        for (int ts = 0; ts < TPS; ++ts) {
+            float t[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) t[i] = (q[ts][i] == 0.0f) ? 0.0f : q[ts][i] * ((l[ts][i] - m) - ls);
+            const float st = ((t[0] + t[1]) + t[2]) + t[3];
+            ce = (ts == 0) ? st : ce + st;
+        }
+        ce = wave32_sum(ce);
+        float lg[TPS][4];
+        const float hl = smoothed_entropy(p, lg);
+        float dpe[TPS][4], dot = 0.0f;
+#pragma unroll
+        for (int ts = 0; ts < TPS; ++ts)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { dpe[ts][i] = a.c_over_B * (lg[ts][i] + 1.0f); dot += p[ts][i] * dpe[ts][i]; }
+        dot = wave32_sum(dot);
+        const float wB = w * a.inv_B;
+        if (h == 0) {
+#pragma unroll
+            for (int ts = 0; ts < TPS; ++ts) {
+                float dy[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    dy[i] = dy_round<DYBF16>(wB * (p[ts][i] * qs - q[ts][i]) + p[ts][i] * (dpe[ts][i] - dot));   // p_k Qs - q'_k
+                a.dY[((size_t)state * TPS + ts) * 32 + j] = make_float4(dy[0], dy[1], dy[2], dy[3]);
+            }
+        }
+        if (lane == 0) { a.loss_terms[state * 2] = (double)(w * ce); a.loss_terms[state * 2 + 1] = (double)(-hl); }
     }
     if (TAIL == FwdTail::Train) {
         const int ab = pre ? pre->ab : a.actions[sid];

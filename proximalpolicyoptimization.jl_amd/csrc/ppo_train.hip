@@ -1,6 +1,7 @@
 // ppo_train.hip -- the training half of the extern "C" surface (include/ppo_hip.h): one minibatch pass and one epoch loop,
 // driven for the policy (step_batch! / ppo_train!), for a critic (value_forward_backward / value_train) and for the policy's
-// imitation objective (imitate_forward_backward / imitate_train), and the critic's state values and GAE.  Host orchestration only: launch order, all math is in the kernels.
+// imitation objective (imitate_forward_backward / imitate_train) and its distillation objective (distill_forward_backward /
+// distill_train, with the target column's fill, upload and getter), and the critic's state values and GAE.  Host orchestration only: launch order, all math is in the kernels.
 #include "ppo_internal.h"
 #include <algorithm>
 #include <cmath>
@@ -48,9 +49,9 @@ static int32_t advantage_column(ppo_policy_s* net, ppo_rollouts_s* ro, const int
 static int32_t train_pass_dev(ppo_policy_s* net, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
                               const TrainObjective& obj, ppo_adam_s* fuse_opt = nullptr, float* fuse_hist2 = nullptr) {
     PPO_TRY(train_reserve(net, B * (ro->H / 32), ro->compact));
-    const bool policy = obj.kind == Objective::Policy, imitate = obj.kind == Objective::Imitate;
-    const float* adv = nullptr;                             // imitation with uniform weights: no column
-    if (policy || (imitate && obj.weight_mode == PPO_IMITATE_POSITIVE_ADVANTAGE))
+    const bool policy = obj.kind == Objective::Policy, imitate = obj.kind == Objective::Imitate, distill = obj.kind == Objective::Distill;
+    const float* adv = nullptr;                             // imitation / distillation with uniform weights: no column
+    if (policy || ((imitate || distill) && obj.weight_mode == PPO_IMITATE_POSITIVE_ADVANTAGE))
         PPO_TRY(advantage_column(net, ro, idx_dev, B, obj.adv_mode, &adv));
     if (policy) {
         // the tail's probability ratios, stored while a target_kl is set only (measured: the store costs the train forward
@@ -69,6 +70,7 @@ static int32_t train_pass_dev(ppo_policy_s* net, ppo_rollouts_s* ro, const int32
         if (net->L > 2) PPO_TRY(net->dzm.alloc((size_t)(net->L - 2) * frag));
     }
     if (imitate) PPO_TRY(launch_imitate_train_fwd(net, ro, idx_dev, B, B_global, obj.entropy_weight, adv));
+    else if (distill) PPO_TRY(launch_distill_train_fwd(net, ro, idx_dev, B, B_global, obj.entropy_weight, adv, obj.distill_targets));
     else if (!policy) {
         // PPO's clipped value loss while the critic handle has a clip range: against the buffer's values of before the update
         // (the callers have checked that they are there), V - vold going to the caller's slice of an epoch column if any
@@ -240,7 +242,7 @@ static int32_t sum_rank_sums(double* st, int k, DevBuf<float>& sx, int32_t rank,
 // the two per-batch loss columns (ppo and entropy loss; a critic's mse is column 0).  world > 1: data-parallel, through the
 // all-reduce hook.  Objective::Policy adds the per-epoch ratio statistics and the target_kl stop, Objective::Value the per-epoch
 // value-clip statistics while the critic handle has a value clip; with world > 1 either kind is summed over the ranks.
-// Objective::Imitate keeps no statistics of either kind, leaves the handle's as they are and never stops early
+// Objective::Imitate and Objective::Distill keep no statistics of either kind, leave the handle's as they are and never stop early
 static int32_t train_epochs(ppo_policy_s* net, ppo_adam_s* opt, ppo_rollouts_s* ro, const TrainObjective& obj, int64_t batch_size,
                             int32_t num_epochs, const int64_t* perm, uint64_t seed, int32_t rank, int32_t world,
                             ppo_allreduce_fn allreduce, void* allreduce_ctx, double* hist0, double* hist1, double* lr_hist) {
@@ -410,6 +412,109 @@ int32_t ppo_imitate_train(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, i
     ARG_CHECK(batch_size >= 1, "1 <= batch_size <= num_data (src/train.jl:88)");
     PPO_TRY(imitate_modes(weight_mode, adv_mode));
     TrainObjective obj = {Objective::Imitate};
+    obj.entropy_weight = entropy_weight; obj.adv_mode = adv_mode; obj.weight_mode = weight_mode;
+    return train_epochs(pol, opt, ro, obj, batch_size, num_epochs, perm, seed, rank, world, allreduce, allreduce_ctx, ce_hist,
+                        entropy_hist, lr_hist);
+}
+
+// ---- policy distillation (no reference op): the policy's cross-entropy against a target distribution per state
+// The target column [T*N][A], full_probs' layout, by transition id; every call that writes new transitions into the buffer
+// marks it not filled (rollouts_filled)
+static int32_t targets_checks(const char* who, const ppo_rollouts_s* ro) {
+    ARG_CHECK(ro->T >= 1, std::string(who) + ": empty rollout buffer");
+    if (ro->sink) {
+        ppo_set_error(std::string(who) + ": a buffer with a disk sink attached is not supported");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    return PPO_OK;
+}
+
+int32_t ppo_rollouts_fill_targets(ppo_policy_t teacher, ppo_rollouts_t ro) {
+    ARG_CHECK(teacher && ro, "fill_targets: null argument");
+    PPO_TRY(targets_checks("fill_targets", ro));
+    ARG_CHECK(ro->H == 32 || ro->H == 128, "fill_targets: shape mismatch");
+    ARG_CHECK(teacher->F == ro->F, "fill_targets: the teacher's input width F differs from the buffer's");
+    ARG_CHECK(teacher->OUT == PPO_OUT && ro->A == PPO_OUT * ro->H, "fill_targets: the teacher must have 4 outputs per half-edge row");
+    if (ro->compact && teacher->dtype != PPO_DTYPE_F32) {
+        ppo_set_error("fill_targets: a bf16-dtype teacher on a compact buffer is not supported (the probabilities forward from env "
+                      "snapshots exists in the fp32-MFMA forward only); collect with expanded storage");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    const int64_t n = ro->T * ro->N;
+    PPO_TRY(ro->targets.alloc((size_t)ro->capT * ro->N * ro->A));
+    ro->targets_T = -1;
+    if (ro->compact) PPO_TRY(launch_policy_probs_snap(teacher, ro->cstate.p, ro->active.p, ro->tmpl.p, ro->V, n, ro->H, ro->targets.p));
+    else PPO_TRY(launch_policy_probs(teacher, ro->states.p, ro->active.p, n, ro->H, ro->targets.p));
+    HIP_TRY(hipStreamSynchronize(ppo_stream()));
+    ro->targets_T = ro->T;
+    return PPO_OK;
+}
+
+int32_t ppo_rollouts_set_targets(ppo_rollouts_t ro, const float* targets) {
+    ARG_CHECK(ro && targets, "set_targets: null argument");
+    PPO_TRY(targets_checks("set_targets", ro));
+    const size_t n = (size_t)ro->T * ro->N * ro->A;
+    for (size_t i = 0; i < n; ++i) ARG_CHECK(std::isfinite(targets[i]) && targets[i] >= 0.0f, "set_targets: every target entry must be finite and >= 0");
+    PPO_TRY(ro->targets.alloc((size_t)ro->capT * ro->N * ro->A));
+    ro->targets_T = -1;
+    PPO_TRY(h2d(ro->targets.p, targets, n));
+    ro->targets_T = ro->T;
+    return PPO_OK;
+}
+
+int32_t ppo_rollouts_get_targets(ppo_rollouts_t ro, float* targets_out) {
+    ARG_CHECK(ro && targets_out, "get_targets: null argument");
+    ARG_CHECK(ro->targets.p && ro->targets_T == ro->T && ro->T >= 1, "get_targets: the target column is not filled for these rollouts (ppo_rollouts_fill_targets or ppo_rollouts_set_targets first)");
+    return d2h(targets_out, ro->targets.p, (size_t)ro->T * ro->N * ro->A);
+}
+
+// what both entry points check of the buffer and their mode arguments -> the target rows
+static int32_t distill_targets(ppo_rollouts_s* ro, int32_t weight_mode, int32_t adv_mode, int32_t target_source, const float** col) {
+    if (weight_mode != PPO_IMITATE_UNIFORM && weight_mode != PPO_IMITATE_POSITIVE_ADVANTAGE) { ppo_set_error("distill: unknown weight mode"); return PPO_ERR_UNSUPPORTED; }
+    if (adv_mode < PPO_ADV_RETURNS || adv_mode > PPO_ADV_GAE_NORMALISED) { ppo_set_error("batch_advantage: unknown advantage mode"); return PPO_ERR_UNSUPPORTED; }
+    if (adv_mode == PPO_ADV_RETURNS_NORMALISED || adv_mode == PPO_ADV_GAE_NORMALISED) {
+        ppo_set_error("distill: the weights are max(advantage, 0) of the returns or the GAE column; the normalised advantage modes are not supported");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    if (target_source != PPO_TARGETS_COLUMN && target_source != PPO_TARGETS_RECORDED) { ppo_set_error("distill: unknown target source"); return PPO_ERR_UNSUPPORTED; }
+    PPO_TRY(targets_checks("distill", ro));
+    if (target_source == PPO_TARGETS_COLUMN) {
+        ARG_CHECK(ro->targets.p && ro->targets_T == ro->T, "distill: the target column is not filled for these rollouts (ppo_rollouts_fill_targets or ppo_rollouts_set_targets first)");
+        *col = ro->targets.p;
+    } else {
+        ARG_CHECK(ro->full_probs.p && ro->probs_T == ro->T, "distill: no recorded distributions for these rollouts (collect them with record_probs)");
+        *col = ro->full_probs.p;
+    }
+    return PPO_OK;
+}
+
+int32_t ppo_distill_forward_backward(ppo_policy_t pol, ppo_rollouts_t ro, const int64_t* sample_idx, int64_t B, int64_t B_global,
+                                     double entropy_weight, int32_t weight_mode, int32_t adv_mode, int32_t target_source) {
+    ARG_CHECK(pol && ro && sample_idx, "distill_forward_backward: null argument");
+    ARG_CHECK(B >= 1 && B <= ro->len, "distill_forward_backward: 1 <= batch_size <= num_data (src/train.jl:88)");
+    ARG_CHECK(B_global >= B, "distill_forward_backward: B_global < B");
+    ARG_CHECK(pol->F == ro->F && (ro->H == 32 || ro->H == 128), "distill_forward_backward: shape mismatch");
+    TrainObjective obj = {Objective::Distill};
+    PPO_TRY(distill_targets(ro, weight_mode, adv_mode, target_source, &obj.distill_targets));
+    DevBuf<int64_t> pos;
+    PPO_TRY(gather_minibatch(pol, ro, sample_idx, B, pos));
+    obj.entropy_weight = entropy_weight; obj.adv_mode = adv_mode; obj.weight_mode = weight_mode;
+    PPO_TRY(train_pass_dev(pol, ro, pol->idx.p, B, B_global, obj));
+    HIP_TRY(hipStreamSynchronize(ppo_stream()));
+    return PPO_OK;
+}
+
+int32_t ppo_distill_train(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, int64_t batch_size, int32_t num_epochs,
+                          double entropy_weight, int32_t weight_mode, int32_t adv_mode, int32_t target_source, const int64_t* perm,
+                          uint64_t seed, int32_t rank, int32_t world, ppo_allreduce_fn allreduce, void* allreduce_ctx,
+                          double* ce_hist, double* entropy_hist, double* lr_hist) {
+    ARG_CHECK(pol && opt && ro && opt->pol == pol, "distill_train!: null/mismatched argument");
+    ARG_CHECK(num_epochs >= 0 && world >= 1 && rank >= 0 && rank < world, "distill_train!: bad epochs/rank/world");
+    ARG_CHECK(world == 1 || allreduce, "distill_train!: world > 1 needs an all-reduce hook");
+    ARG_CHECK(pol->F == ro->F && (ro->H == 32 || ro->H == 128), "distill_train!: shape mismatch");
+    ARG_CHECK(batch_size >= 1, "1 <= batch_size <= num_data (src/train.jl:88)");
+    TrainObjective obj = {Objective::Distill};
+    PPO_TRY(distill_targets(ro, weight_mode, adv_mode, target_source, &obj.distill_targets));
     obj.entropy_weight = entropy_weight; obj.adv_mode = adv_mode; obj.weight_mode = weight_mode;
     return train_epochs(pol, opt, ro, obj, batch_size, num_epochs, perm, seed, rank, world, allreduce, allreduce_ctx, ce_hist,
                         entropy_hist, lr_hist);
