@@ -40,6 +40,13 @@ resident env a start landed in; --temperature, --top-k and --top-p are then not 
 the distinct beam (DESIGN.md 7p): K different states per step instead of K spellings of a few, so that the round's paths differ;
 --beam-rounds is its budget, 256 candidates examined per step and round (--rounds is taken: the training rounds).
 
+--anchor COEF adds the step this loop ends in: fine-tuning the cloned policy with PPO on its OWN sampled rollouts without losing
+it.  Behind the rounds a frozen copy of the policy becomes the anchor; every PPO iteration collects with the current policy,
+fill_targets_(rollouts, frozen) leaves the frozen copy's distribution of every visited state in the buffer, and ppo_train_
+minimises the PPO loss plus COEF * KL(frozen || policy) (policy.kl_anchor = (COEF, "column", --anchor-target)).
+With --anchor-target d > 0 the coefficient doubles behind an epoch whose mean anchor KL exceeds 1.5 d and halves below d / 1.5.
+COEF = 0 records the divergence of plain PPO from the cloned policy.
+
 This script shows the calls and prints what it measures each round (the mean gap the search reaches, the transitions
 collected, the losses, the mean return of the plain stochastic policy).  Whether the loop learns faster or better than
 ppo_iterate_ on sampled rollouts, and which --loss serves it best, has not been measured; the script makes no such claim.
@@ -73,6 +80,10 @@ def main():
     ap.add_argument("--top-k", type=int, default=0, help="the search step samples from the k likeliest actions only (0: all)")
     ap.add_argument("--top-p", type=float, default=1.0,
                     help="the search step samples from the likeliest actions that reach this probability mass only (1: all)")
+    ap.add_argument("--anchor", type=float, default=None, metavar="COEF",
+                    help="behind the rounds: PPO on sampled rollouts with the penalty COEF * KL(frozen cloned policy || policy)")
+    ap.add_argument("--anchor-target", type=float, default=0.0, help="--anchor: adapt COEF towards this mean KL (0: fixed)")
+    ap.add_argument("--ppo-iterations", type=int, default=5, help="--anchor: PPO iterations behind the rounds")
     args = ap.parse_args()
 
     discount, epsilon, entropy_weight, max_actions = 1.0, 0.05, 0.01, 32
@@ -121,6 +132,22 @@ def main():
         with PPO.selecting(policy, "greedy"):
             gret, _ = PPO.average_returns(policy, eval_env, 1024)
         print(line + "; stochastic policy: mean return %.3f (std %.3f), greedy %.3f" % (ret, dev, gret))
+    if args.anchor is not None:
+        frozen = PPO.HipPolicy(72, 128, 2, 4, seed=0)
+        frozen.params = policy.params                         # the cloned policy, from here on the anchor
+        policy.kl_anchor = (args.anchor, "column", args.anchor_target)
+        sampled = PPO.BufferRollouts()
+        for it in range(args.ppo_iterations):
+            PPO.collect_rollouts_steps_(sampled, env, policy, max_actions, discount)
+            PPO.fill_targets_(sampled, frozen)                # the anchor's distribution of every visited state, on the device
+            dataset = PPO.construct_dataset(sampled)
+            ph, eh, _ = PPO.ppo_train_(policy, optimizer, dataset, epsilon, min(1024, len(dataset)), 2, entropy_weight, seed=it,
+                                       verbose=False)
+            stats = policy.last_anchor_stats()
+            ret, dev = PPO.average_returns(policy, eval_env, 1024)
+            print("anchored PPO %d: loss %.4f (surrogate + coef * cross-entropy), anchor KL %s at coef %s, next coef %.4g; "
+                  "mean return %.3f (std %.3f)" % (it, ph[-1], ["%.5f" % k for k in stats["anchor_kl"]],
+                                                   ["%.4g" % c for c in stats["anchor_coef"]], policy.kl_anchor[0], ret, dev))
     return policy
 
 

@@ -466,6 +466,37 @@ int32_t ppo_policy_get_target_kl(ppo_policy_t pol, double* target_kl);
 int32_t ppo_policy_last_train_stats(ppo_policy_t pol, int32_t cap, int32_t* epochs_run, int32_t* stopped_early,
                                     double* approx_kl, double* old_approx_kl, double* clip_fraction);
 
+/* ---------------------------------------------------------------- KL-anchored PPO: a penalty towards target distributions
+ * No reference op.  While a KL anchor is set on the policy handle, ppo_train, ppo_forward_backward and ppo_step_batch
+ * (signatures unchanged) minimise
+ *     ppo_loss_with_entropy  +  coef * -(1 / B_global) sum_i sum_k q'_ik log pi(k | s_i)
+ * the clipped surrogate and entropy term as they are plus coef times the soft-target cross-entropy of the distillation section
+ * above (q', log pi, Qs and the gradient (coef / B_global)(p_k Qs - q'_k) as stated there): the gradient of
+ * coef * KL(q' || pi), whose value differs from the cross-entropy by the targets' entropy only.  q: the frozen cloned or
+ * teacher policy (kickstarting / RL from a prior; source PPO_TARGETS_COLUMN, filled by ppo_rollouts_fill_targets), or the
+ * behaviour policy's whole distribution at collection time (PPO's penalty form, Schulman et al. 2017, section 4; source
+ * PPO_TARGETS_RECORDED).  Loss column 0 (ppo_last_losses, ppo_train's ppo_hist) is then the minimised sum, surrogate plus
+ * coef * cross-entropy.  The per-state divergence kl_i = sum over q'_ik > 0 of q'_ik (log q'_ik - log pi(k | s_i)) is formed in
+ * fp32 beside it; ppo_train reduces an epoch's column once (fp64, fixed order) to the mean anchor KL, every state with the
+ * parameters its own minibatch saw.  coef == 0 records the divergence and leaves the gradient alone.
+ * target == 0: the coefficient is fixed.  target = d > 0: behind every epoch of ppo_train whose mean anchor KL exceeds 1.5 d
+ * coef doubles, below d / 1.5 it halves; the adapted value stays on the handle across calls (ppo_policy_get_kl_anchor).
+ * Data parallel: the sums behind the mean are exchanged through the hook once per epoch (6 * world floats), so every rank
+ * holds the global mean and the same coefficient; the anchor must be the same on every rank.
+ * Errors, before anything is launched: a source not filled / not recorded for these rollouts PPO_ERR_ARG; a bf16-dtype
+ * policy or a buffer with a disk sink attached PPO_ERR_UNSUPPORTED.  The fp32-MFMA train forward alone has the anchored tail:
+ * while an anchor is set every minibatch size takes it.  The target_kl statistics and stop work as without an anchor. */
+#define PPO_ANCHOR_OFF (-1)
+/* source: PPO_ANCHOR_OFF (the default; coef and target are then ignored and read back 0), PPO_TARGETS_COLUMN or
+ * PPO_TARGETS_RECORDED (another value: PPO_ERR_UNSUPPORTED); coef >= 0 and finite, target >= 0 and finite, else PPO_ERR_ARG */
+int32_t ppo_policy_set_kl_anchor(ppo_policy_t pol, double coef, int32_t source, double target);
+/* every output may be NULL */
+int32_t ppo_policy_get_kl_anchor(ppo_policy_t pol, double* coef, int32_t* source, double* target);
+/* Of the latest ppo_train on this policy that ran with an anchor: n = its epochs that ran, and the first min(cap, n) entries
+ * of kl (mean anchor KL of the epoch) and coef (the coefficient the epoch ran with); every output may be NULL.  A ppo_train
+ * without an anchor leaves n = 0 */
+int32_t ppo_policy_last_anchor_stats(ppo_policy_t pol, int32_t cap, int32_t* n, double* kl, double* coef);
+
 /* ---------------------------------------------------------------- critic (device state values)
  * A critic is an ordinary ppo_policy_t made by ppo_policy_create(F, hidden, L, 4) and read as a state value: the mean of
  * the 4 outputs of every half-edge row that belongs to an ACTIVE quad,

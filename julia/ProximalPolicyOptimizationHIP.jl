@@ -627,6 +627,31 @@ function last_train_stats(p::HipPolicy)
                 p.h, n[], n, stopped, kl, okl, cf))
     (epochs_run = Int(n[]), stopped_early = stopped[] != 0, approx_kl = kl, old_approx_kl = okl, clip_fraction = cf)
 end
+# ---- KL-anchored PPO (include/ppo_hip.h "KL-anchored PPO"; no reference op): while an anchor is set, ppo_train! and step_batch!
+# minimise the PPO loss plus coef * the cross-entropy against the rollouts' target rows (the gradient of coef * KL(q || pi)).
+# source = :column (fill_targets!: a frozen cloned or teacher policy) or :recorded (record_probs: PPO's penalty form); target = 0
+# keeps coef fixed, d > 0 doubles it behind an epoch whose mean anchor KL exceeds 1.5 d and halves it below d / 1.5
+function set_kl_anchor!(p::HipPolicy, coef, source::Symbol = :column, target = 0.0)
+    check(ccall((:ppo_policy_set_kl_anchor, LIB), Int32, (Ptr{Cvoid}, Float64, Int32, Float64),
+                p.h, Float64(coef), DISTILL_TARGETS[source], Float64(target)))
+end
+function clear_kl_anchor!(p::HipPolicy)
+    check(ccall((:ppo_policy_set_kl_anchor, LIB), Int32, (Ptr{Cvoid}, Float64, Int32, Float64), p.h, 0.0, Int32(-1), 0.0))
+end
+function kl_anchor(p::HipPolicy)
+    c, s, t = Ref{Float64}(), Ref{Int32}(), Ref{Float64}()
+    check(ccall((:ppo_policy_get_kl_anchor, LIB), Int32, (Ptr{Cvoid}, Ref{Float64}, Ref{Int32}, Ref{Float64}), p.h, c, s, t))
+    s[] < 0 ? nothing : (coef = c[], source = s[] == 0 ? :column : :recorded, target = t[])
+end
+function last_anchor_stats(p::HipPolicy)
+    n = Ref{Int32}()
+    check(ccall((:ppo_policy_last_anchor_stats, LIB), Int32, (Ptr{Cvoid}, Int32, Ref{Int32}, Ptr{Float64}, Ptr{Float64}),
+                p.h, Int32(0), n, C_NULL, C_NULL))
+    kl, co = zeros(n[]), zeros(n[])
+    check(ccall((:ppo_policy_last_anchor_stats, LIB), Int32, (Ptr{Cvoid}, Int32, Ref{Int32}, Ptr{Float64}, Ptr{Float64}),
+                p.h, n[], n, kl, co))
+    (anchor_kl = kl, anchor_coef = co)
+end
 # ---- action selection (include/ppo_hip.h "Action selection"; no reference op): how the evaluators, best_states! and the searches
 # choose an action -- :sample draws rand(Categorical(p)), :greedy plays argmax(p), p = softmax(logits / temperature).  The
 # default (:sample, 1.0) is the reference's rule.  collect_rollouts!, collect_paths!, action_probabilities and train! never read it

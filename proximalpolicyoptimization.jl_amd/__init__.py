@@ -414,6 +414,40 @@ class HipPolicy:
                 "old_approx_kl": list(okl), "clip_fraction": list(cf)}
 
     @property
+    def kl_anchor(self):
+        """None (off, the default), or (coef, source, target): while set, ppo_train_, forward_backward and step_batch_ on this
+        policy minimise the PPO loss plus coef * the soft-target cross-entropy against the rollouts' target rows -- the gradient
+        of coef * KL(q || pi).  source: "column" (fill_targets_ / set_action_targets: a frozen cloned or teacher policy) or
+        "recorded" (the behaviour policy's distributions of a collection with record_probs=True: PPO's penalty form).  target:
+        0.0 for a fixed coefficient, or d > 0 for PPO's rule: behind every epoch of ppo_train_ whose mean anchor KL exceeds 1.5 d
+        coef doubles, below d / 1.5 it halves; the adapted coef is what this property then reads.  Set it from (coef, source)
+        or (coef, source, target); coef = 0 records the divergence and leaves the gradient alone.  fp32 policies, in-memory
+        rollouts."""
+        c, s, t = C.c_double(0), C.c_int32(0), C.c_double(0)
+        call("ppo_policy_get_kl_anchor", self._h, C.byref(c), C.byref(s), C.byref(t))
+        if s.value == ANCHOR_OFF:
+            return None
+        return (c.value, ANCHOR_SOURCES[s.value], t.value)
+
+    @kl_anchor.setter
+    def kl_anchor(self, value):
+        if value is None:
+            call("ppo_policy_set_kl_anchor", self._h, 0.0, ANCHOR_OFF, 0.0)
+            return
+        call("ppo_policy_set_kl_anchor", self._h, *check_kl_anchor(value))
+
+    def last_anchor_stats(self):
+        """Of the latest ppo_train_ on this policy that ran with kl_anchor set: {"anchor_kl", "anchor_coef"}, one entry per epoch
+        that ran: the mean over the dataset of KL(q' || pi), each state with the parameters its own minibatch saw, and the
+        coefficient that epoch ran with.  Empty lists after a ppo_train_ without an anchor.  After ppo_train_(..., parallel=):
+        over the states of all ranks, the same on every rank."""
+        n = C.c_int32(0)
+        call("ppo_policy_last_anchor_stats", self._h, 0, C.byref(n), None, None)
+        kl, co = np.zeros(n.value, np.float64), np.zeros(n.value, np.float64)
+        call("ppo_policy_last_anchor_stats", self._h, n.value, C.byref(n), _p(kl, _lib.c_f64p), _p(co, _lib.c_f64p))
+        return {"anchor_kl": list(kl), "anchor_coef": list(co)}
+
+    @property
     def value_clip(self):
         """For a handle that serves as a critic: None (off, the default: Flux.mse), or the range c of PPO's clipped value loss
         max((V - t)^2, (V_old + clamp(V - V_old, -c, c) - t)^2) that value_forward_backward / value_train_ then minimise,
@@ -650,6 +684,73 @@ def distillation_loss(logits, mask, targets, weights=None, floor=False):
     with np.errstate(divide="ignore", invalid="ignore"):
         h = -np.where(q == 0, 0.0, q.astype(np.float64) * np.log(q.astype(np.float64))).sum(axis=1)
     return loss, float(np.mean(w.astype(np.float64) * h))
+
+
+ANCHOR_OFF = -1              # PPO_ANCHOR_OFF
+ANCHOR_SOURCES = ("column", "recorded")        # PPO_TARGETS_COLUMN, PPO_TARGETS_RECORDED
+
+
+def check_kl_anchor(value):
+    """A HipPolicy.kl_anchor value -> (coef, source number, target), refused like the library refuses it (no device call)."""
+    if not isinstance(value, (tuple, list)) or len(value) not in (2, 3):
+        raise PPOError(-1, "AssertionError: kl_anchor must be None, (coef, source) or (coef, source, target)")
+    coef, source = float(value[0]), value[1]
+    target = float(value[2]) if len(value) == 3 else 0.0
+    if source not in ANCHOR_SOURCES:
+        raise PPOError(-4, "kl_anchor source must be one of %s" % sorted(ANCHOR_SOURCES))
+    if not (coef >= 0.0 and np.isfinite(coef)):                           # NaN fails it too
+        raise PPOError(-1, "AssertionError: kl_anchor: the coefficient must be finite and >= 0")
+    if not (target >= 0.0 and np.isfinite(target)):
+        raise PPOError(-1, "AssertionError: kl_anchor: the target must be 0 (fixed coefficient) or positive and finite")
+    return coef, ANCHOR_SOURCES.index(source), target
+
+
+def adapt_kl_coef(coef, mean_kl, target):
+    """The coefficient rule ppo_train_ applies behind every epoch (PPO's penalty form, Schulman et al. 2017, section 4; plain
+    host mirror): target 0 keeps coef; a mean anchor KL above 1.5 target doubles it, one below target / 1.5 halves it.  On a
+    data-parallel run mean_kl is the mean over the states of ALL ranks, so every rank makes the same move."""
+    if target > 0:
+        if mean_kl > 1.5 * target and np.isfinite(coef * 2.0):
+            return coef * 2.0
+        if mean_kl < target / 1.5:
+            return coef / 2.0
+    return coef
+
+
+def anchored_ppo_loss(logits, mask, actions, p_old, adv, eps, targets, coef, kl=False):
+    """The KL-anchored PPO loss column 0 on given logits, in float32 arithmetic as the device forms it (plain numpy host mirror)
+    -> float: -mean_i(min(pi(a_i | s_i) / p_old_i * adv_i, clip_i) + coef * sum_k q'_ik log pi(k | s_i)), the clipped surrogate
+    of ppo_loss_with_entropy (clip = (1 + eps) adv for adv >= 0, (1 - eps) adv below) plus coef times distillation_loss's
+    cross-entropy.  logits, targets [B, A]; mask as in imitation_loss; actions [B] 0-based, each allowed; p_old, adv [B].
+    kl=True: returns (loss, mean_i KL(q'_i || pi_i)), KL_i = sum over q'_ik > 0 of q'_ik (log q'_ik - log pi(k | s_i)), the
+    figure last_anchor_stats reports per epoch."""
+    l = np.asarray(logits, np.float32)
+    B, A = l.shape
+    m = _bool_mask(mask, A)
+    q = np.asarray(targets, np.float32)
+    if q.shape != l.shape:
+        raise PPOError(-1, "AssertionError: anchored_ppo_loss: targets must have the logits' shape")
+    if not np.all(np.isfinite(q)) or (q < 0).any():
+        raise PPOError(-1, "AssertionError: anchored_ppo_loss: every target entry must be finite and >= 0")
+    a = np.asarray(actions, np.int64)
+    po, ad = np.asarray(p_old, np.float32), np.asarray(adv, np.float32)
+    q = np.where(m, q, np.float32(0))
+    mx = np.where(m, l, np.float32(-np.inf)).max(axis=1)
+    e = np.where(m, np.exp(np.where(m, l - mx[:, None], np.float32(0)), dtype=np.float32), np.float32(0))
+    S = e.sum(axis=1, dtype=np.float32)
+    ps = (e / S[:, None])[np.arange(B), a]
+    gain = (ps / po * ad).astype(np.float64)
+    clip = np.where(ad >= 0, (1.0 + float(eps)) * ad.astype(np.float64), (1.0 - float(eps)) * ad.astype(np.float64))
+    minval = np.where(gain < clip, gain, clip)
+    logp = (l - mx[:, None]) - np.log(S, dtype=np.float32)[:, None]
+    ce = np.where(q == 0, np.float32(0), q * np.where(q == 0, np.float32(0), logp)).sum(axis=1, dtype=np.float32)
+    loss = float(np.float32(-np.mean(minval + (np.float32(coef) * ce).astype(np.float64))))
+    if not kl:
+        return loss
+    pos = q > 0
+    lq = np.log(np.where(pos, q, np.float32(1)), dtype=np.float32)
+    d = np.where(pos, q * (lq - np.where(pos, logp, np.float32(0))), np.float32(0)).sum(axis=1, dtype=np.float32)
+    return loss, float(np.mean(d, dtype=np.float64))
 
 
 # ------------------------------------------------------------------ optimiser
@@ -1808,12 +1909,27 @@ def ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size,
     were cut in
     (compute_gae_critic_(..., bootstrap_truncated=True)), per rank like the GAE itself; loss gains "truncated", the number of
     truncated transitions per iteration (this rank's).  value_train_'s lambda-returns and "explained_variance" are then the
-    bootstrapped ones."""
+    bootstrapped ones.
+    anchor (keyword only, the third name **options takes): a frozen HipPolicy -- a cloned or teacher policy -- that PPO stays
+    anchored to.  policy.kl_anchor must be set with source "column" (PPOError otherwise, before anything runs; "recorded" is
+    not taken here); every iteration runs fill_targets_(rollouts, anchor) behind its collection, ppo_train_ then minimises the
+    PPO loss plus coef * KL(anchor || policy), and loss gains "anchor_kl" and "anchor_coef", one entry per epoch that ran.
+    In-memory rollouts only."""
     parallel = options.pop("parallel", None)
     bootstrap = bool(options.pop("bootstrap_truncated", False))
+    anchor = options.pop("anchor", None)
     if options:
         raise TypeError("ppo_iterate_() got an unexpected keyword argument %r" % sorted(options)[0])
     loss = {"ppo": [], "entropy": [], "lr": []}
+    if anchor is not None:
+        set_anchor = getattr(policy, "kl_anchor", None)
+        if set_anchor is None:
+            raise PPOError(-1, "AssertionError: ppo_iterate_(anchor=...) needs policy.kl_anchor = (coef, \"column\"[, target]) set")
+        if set_anchor[1] != "column":
+            raise PPOError(-4, "ppo_iterate_(anchor=...) fills the target column: policy.kl_anchor's source must be \"column\"")
+        if state_data_path is not None:
+            raise PPOError(-4, "an anchor with disk-backed rollouts is not supported")
+        loss["anchor_kl"], loss["anchor_coef"] = [], []
     stats = getattr(policy, "target_kl", None) is not None
     if stats:
         loss["approx_kl"], loss["clip_fraction"] = [], []
@@ -1836,6 +1952,8 @@ def ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size,
         rollouts = BufferRollouts() if state_data_path is None else DiskRollouts(state_data_path)   # :185,230
         collect_rollouts_(rollouts, env, policy, episodes_per_iteration, discount)
         dataset = construct_dataset(rollouts)
+        if anchor is not None:
+            fill_targets_(dataset.rollouts, anchor)
         if critic is None:
             p, e, lr = ppo_train_(policy, optimizer, dataset, epsilon, minibatch_size, epochs_per_iteration,
                                   entropy_weight, parallel=parallel, verbose=verbose)
@@ -1862,6 +1980,10 @@ def ppo_iterate_(policy, env, optimizer, episodes_per_iteration, minibatch_size,
             st = policy.last_train_stats()
             loss["approx_kl"] += st["approx_kl"]
             loss["clip_fraction"] += st["clip_fraction"]
+        if anchor is not None:
+            ast = policy.last_anchor_stats()
+            loss["anchor_kl"] += ast["anchor_kl"]
+            loss["anchor_coef"] += ast["anchor_coef"]
         save_loss(evaluator, loss)       # :196,247 -- like the reference, an evaluator without a save_loss method throws
     if state_data_path is not None and os.path.isdir(state_data_path):
         if verbose:

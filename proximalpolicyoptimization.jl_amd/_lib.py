@@ -167,6 +167,9 @@ SIGNATURES = {
     "ppo_policy_set_target_kl": [H, C.c_double],
     "ppo_policy_get_target_kl": [H, c_f64p],
     "ppo_policy_last_train_stats": [H, C.c_int32, c_i32p, c_i32p, c_f64p, c_f64p, c_f64p],
+    "ppo_policy_set_kl_anchor": [H, C.c_double, C.c_int32, C.c_double],
+    "ppo_policy_get_kl_anchor": [H, c_f64p, c_i32p, c_f64p],
+    "ppo_policy_last_anchor_stats": [H, C.c_int32, c_i32p, c_f64p, c_f64p],
     "ppo_rollouts_value_moments": [H, C.c_int32, c_f64p],
     "ppo_rollouts_value_moments_shifts": [H, C.c_int32, c_f64p, c_f64p],
     "ppo_policy_set_value_clip": [H, C.c_double],

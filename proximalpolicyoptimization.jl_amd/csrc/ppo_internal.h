@@ -153,6 +153,15 @@ struct ppo_policy_s {
     double target_kl = 0.0;            // ppo_policy_set_target_kl: 0 off
     int32_t stats_stopped = 0;         // the latest ppo_train: ended by target_kl before num_epochs
     std::vector<double> stats_kl, stats_old_kl, stats_clip;   // ... and its per-epoch statistics (epochs that ran)
+    // KL anchor (ppo_policy_set_kl_anchor): a penalty anchor_coef * KL(q || pi) in the policy's PPO objective, q
+    // the rollout buffer's target rows of anchor_source (PPO_TARGETS_COLUMN / PPO_TARGETS_RECORDED; PPO_ANCHOR_OFF: none)
+    double anchor_coef = 0.0;          // >= 0, finite; adapted by ppo_train's epoch loop while anchor_target > 0
+    int32_t anchor_source = PPO_ANCHOR_OFF;
+    double anchor_target = 0.0;        // 0: fixed coefficient; d > 0: PPO's adaptive rule around d
+    DevBuf<float> anchor;              // [cap_tiles] the divergence per state of one minibatch (ppo_forward_backward / ppo_step_batch)
+    DevBuf<float> anchor_col;          // [len] one epoch of ppo_train, like ratio_col
+    const float* anchor_last = nullptr; int64_t anchor_last_n = 0;   // what ppo_debug_anchor_kl reads, like ratio_last
+    std::vector<double> astats_kl, astats_coef;   // the latest ppo_train, per epoch: mean anchor KL, the coefficient it ran with
     // critic: PPO's clipped value loss (ppo_policy_set_value_clip) and what ppo_value_train makes of V - vold
     double value_clip = 0.0;           // 0 off; > 0 on; +inf: record the statistics, never clip
     DevBuf<float> vdelta_col;          // [len] one epoch of ppo_value_train: the minibatch at dataset position `start` writes at start
@@ -486,7 +495,8 @@ const PpoKnobs& ppo_knobs();
 // read as a state value) Flux.mse against a target column, or the policy's cross-entropy on the buffer's actions (behaviour
 // cloning), or its cross-entropy against a target distribution per state (policy distillation).
 // TrainObjective: the loss inputs of one pass
-enum class Objective { Policy, Value, Imitate, Distill };
+// PolicyAnchored: Policy plus a coefficient times Distill's cross-entropy, while the handle has a KL anchor.
+enum class Objective { Policy, Value, Imitate, Distill, PolicyAnchored };
 struct TrainObjective {
     Objective kind;
     // Policy
@@ -504,6 +514,11 @@ struct TrainObjective {
     int32_t weight_mode = PPO_IMITATE_UNIFORM;
     // Distill (entropy_weight, adv_mode and weight_mode as for Imitate): the target rows [T*N][A] by transition id
     const float* distill_targets = nullptr;
+    // PolicyAnchored (eps, entropy_weight, adv_mode and ratio_dst as for Policy): the target rows, the coefficient of this pass
+    // and where it stores the divergence per state (nullptr: the policy's minibatch buffer)
+    const float* anchor_targets = nullptr;
+    double anchor_coef = 0.0;
+    float* anchor_dst = nullptr;
 };
 
 // The kernels that run one training minibatch.  TrainTile runs forward, loss and backward-data in one launch and is
@@ -511,6 +526,7 @@ struct TrainObjective {
 // value-train mode, the only forward with one -- followed by the backward the policy would take at that shape and size; where
 // that is the one-tile pass, whose weight-gradient kernel only runs from inside it, the three-product Small backward.
 // Objective::Imitate: likewise, k_policy_fwd in an imitation mode (12 / 13).  Objective::Distill: likewise, modes 17 / 18.
+// Objective::PolicyAnchored: likewise, modes 20 / 21.
 enum class TrainFwd { None, TrainTile, X6S, X6T, X6, Split, Fwd, Bf16 };
 enum class TrainBwd { None, Wgrad, Small, X6, Fused, Bf16 };
 struct TrainRoute { TrainFwd fwd; TrainBwd bwd; const char* err; };      // err: why fwd is None
@@ -525,7 +541,7 @@ TrainRoute train_route(int32_t dtype, int F, int HID, int L, int H, bool compact
 enum class FwdMode : int {
     Probs = 0, Sample = 1, Train = 2, Persistent = 3, TrainSnap = 4, ValuePredict = 5, ValueTrain = 6, ValuePredictSnap = 7,
     ValueTrainSnap = 8, ValueTrainClip = 9, ValueTrainClipSnap = 10, Forced = 11, Imitate = 12, ImitateSnap = 13, Tempered = 14,
-    Greedy = 15, Truncated = 16, Distill = 17, DistillSnap = 18, ProbsSnap = 19
+    Greedy = 15, Truncated = 16, Distill = 17, DistillSnap = 18, ProbsSnap = 19, TrainAnchored = 20, TrainAnchoredSnap = 21
 };
 enum class FwdSource {
     Rows,       // observation rows [B][H][F] in storage order
@@ -536,7 +552,7 @@ enum class FwdSource {
 };
 enum class FwdTail {      // policy_tail, or value_tail for the three Value*
     Probs, Sample, SamplePersistent, Train, Forced, Imitate, Tempered, Greedy, Truncated, ValuePredict, ValueTrain, ValueTrainClip,
-    Distill
+    Distill, TrainAnchored
 };
 struct FwdTraits { FwdSource src; FwdTail tail; };
 constexpr FwdTraits fwd_traits(FwdMode m) {
@@ -561,6 +577,8 @@ constexpr FwdTraits fwd_traits(FwdMode m) {
     case FwdMode::Distill:            return {FwdSource::RowsIdx, FwdTail::Distill};
     case FwdMode::DistillSnap:        return {FwdSource::SnapIdx, FwdTail::Distill};
     case FwdMode::ProbsSnap:          return {FwdSource::Snap, FwdTail::Probs};
+    case FwdMode::TrainAnchored:      return {FwdSource::RowsIdx, FwdTail::TrainAnchored};
+    case FwdMode::TrainAnchoredSnap:  return {FwdSource::SnapIdx, FwdTail::TrainAnchored};
     }
     return {FwdSource::Rows, FwdTail::Probs};
 }
@@ -568,7 +586,8 @@ constexpr bool src_snapshot(FwdSource s) { return s == FwdSource::Snap || s == F
 constexpr bool tail_value(FwdTail t) { return t == FwdTail::ValuePredict || t == FwdTail::ValueTrain || t == FwdTail::ValueTrainClip; }
 // train forward: saves the activations, writes dY and the loss terms
 constexpr bool tail_trains(FwdTail t) {
-    return t == FwdTail::Train || t == FwdTail::Imitate || t == FwdTail::Distill || t == FwdTail::ValueTrain || t == FwdTail::ValueTrainClip;
+    return t == FwdTail::Train || t == FwdTail::Imitate || t == FwdTail::Distill || t == FwdTail::TrainAnchored || t == FwdTail::ValueTrain ||
+           t == FwdTail::ValueTrainClip;
 }
 // logits times 1 / temperature in front of the softmax
 constexpr bool tail_tempers(FwdTail t) { return t == FwdTail::Tempered || t == FwdTail::Greedy || t == FwdTail::Truncated; }
@@ -585,6 +604,7 @@ constexpr FwdMode fwd_train_mode(Objective obj, bool compact, bool clipped = fal
         return compact ? FwdMode::ValueTrainSnap : FwdMode::ValueTrain;
     case Objective::Imitate: return compact ? FwdMode::ImitateSnap : FwdMode::Imitate;
     case Objective::Distill: return compact ? FwdMode::DistillSnap : FwdMode::Distill;
+    case Objective::PolicyAnchored: return compact ? FwdMode::TrainAnchoredSnap : FwdMode::TrainAnchored;
     default: return compact ? FwdMode::TrainSnap : FwdMode::Train;
     }
 }
@@ -609,6 +629,12 @@ int32_t launch_imitate_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int3
 // target_ptr[transition][A] (full_probs' layout), weighted like imitation's, plus the policy's entropy term
 int32_t launch_distill_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
                                  double entropy_weight, const float* weight_col, const float* target_ptr);
+// KL-anchored train forward (k_policy_fwd's FwdMode::TrainAnchored / TrainAnchoredSnap): launch_policy_train_fwd's
+// surrogate and entropy term plus beta times the cross-entropy against target_ptr[transition][A]; the ratios go where
+// p->ratio_out points, the divergence per state to anchor_dst (minibatch order)
+int32_t launch_anchored_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
+                                  double eps, double entropy_weight, const float* adv_col, const float* target_ptr, double beta,
+                                  float* anchor_dst);
 // launch_policy_probs from env snapshots [B][2V] in storage order (k_policy_fwd's FwdMode::ProbsSnap; fp32 policies, F = 72)
 int32_t launch_policy_probs_snap(ppo_policy_s* p, const int8_t* cstate_dev, const uint32_t* active_dev, const int8_t* tmpl_dev,
                                  int32_t V, int64_t B, int32_t H, float* probs_dev);
@@ -644,6 +670,8 @@ int32_t launch_categorical(const float* probs, const float* u, int64_t B, int64_
 // first 4 (ratio statistics: sum(-log r), sum((r - 1) - log r), count(|r - 1| > eps), n) resp. 5 (value moments) doubles
 size_t stats_part_doubles();
 int32_t launch_ratio_stats(const float* ratio, int64_t n, double eps, double* part);
+// (sum x, n) of a column of n floats in the first 2 doubles
+int32_t launch_sum_stats(const float* col, int64_t n, double* part);
 // value-clip statistics over n deltas V - vold: count(|delta| > c), sum delta^2, n in the first 3 doubles
 int32_t launch_value_clip_stats(const float* delta, int64_t n, float c, double* part);
 // over the transitions with valid[i] != 0 of [0, n): n, sum x, sum x^2, sum y, sum y^2 with x = t - t[i0], y = (t - v) - (t - v)[i0],

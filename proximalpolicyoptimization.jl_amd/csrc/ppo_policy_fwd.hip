@@ -44,6 +44,14 @@ constexpr bool distill_row_early(int F, int HID, int TPS, int DEEP, bool SNAP) {
     return !(F == 72 && HID == 128 && TPS == 4 && DEEP && !SNAP);
 }
 
+// FwdTail::TrainAnchored: the same question for the anchored train forward, which holds TailPre's three inputs
+// beside the row.  DESIGN.md 7r lists which instantiation got which
+constexpr bool anchor_row_early(int F, int HID, int TPS, int DEEP, bool SNAP) {
+    return distill_row_early(F, HID, TPS, DEEP, SNAP);      // the same one instantiation: 20 bytes per lane with the early fetch
+}
+// ... and whether TailPre's three inputs are fetched ahead of the activation stores too (else behind the loop, like the row)
+constexpr bool anchor_pre_early(int F, int HID, int TPS, int DEEP, bool SNAP) { return anchor_row_early(F, HID, TPS, DEEP, SNAP); }
+
 // TPS = 32-row tiles per state (H = 32*TPS half-edges, A = 128*TPS actions): the wave walks the tiles of its
 // state one after the other, keeps the 4*TPS logits per lane, and runs softmax / sampling / loss once per state.
 // DEEP = 1: Policy(F, HID, num_hidden_layers != 2, 4) (test/policy.jl:9-19).  The hidden->hidden block becomes a loop over
@@ -67,6 +75,8 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
     constexpr bool VALUE = tail_value(TAIL);            // critic: value_tail
     constexpr bool IMITATE = TAIL == FwdTail::Imitate;
     constexpr bool DISTILL = TAIL == FwdTail::Distill;
+    constexpr bool ANCHOR = TAIL == FwdTail::TrainAnchored;
+    constexpr bool QROW = DISTILL || ANCHOR;                // the tails that read a target row per state
     constexpr bool GATHER = SRC == FwdSource::RowsIdx;
     constexpr bool SNAP = src_snapshot(SRC), SNAPX = SRC == FwdSource::SnapIdx;
     constexpr bool PERSIST = SRC == FwdSource::EnvSlots;    // persistent rollout: T steps of the wave's envs, their state in LDS slots
@@ -77,11 +87,12 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
     constexpr int PFV = PFW / 2;
     // (the imitation forward from snapshots likewise: with 16 groups ImitateSnap spills where TrainSnap does, 196 / 60 / 116 bytes per lane)
     // (the distillation forward from snapshots takes the same ring: ImitateSnap's registers plus the target row)
-    constexpr int PF = (FwdCfg<F, HID>::WPS == 1) ? PFW : (TRAIN ? (((VALUE || IMITATE || DISTILL) && SNAP) ? PFV : PFW) : 4);   // weight-fragment groups kept in flight per wave
+    // (the anchored forward from snapshots likewise: DistillSnap's registers plus TailPre's)
+    constexpr int PF = (FwdCfg<F, HID>::WPS == 1) ? PFW : (TRAIN ? (((VALUE || IMITATE || QROW) && SNAP) ? PFV : PFW) : 4);   // weight-fragment groups kept in flight per wave
     // distillation: the state's target row (TPS float4 per lane) is fetched in front of the tile loop, ahead of the activation
     // stores like TailPre, where holding it across the loop costs no scratch; else behind the loop, paying the wait for the
     // stores queued in front of it (vmcnt is one in-order queue).  DESIGN.md 7q lists which instantiation got which
-    constexpr bool QPRE = DISTILL && distill_row_early(F, HID, TPS, DEEP, SNAP);
+    constexpr bool QPRE = (DISTILL && distill_row_early(F, HID, TPS, DEEP, SNAP)) || (ANCHOR && anchor_row_early(F, HID, TPS, DEEP, SNAP));
     constexpr bool OBS = (PERSIST || SNAP);             // the state rows are re-derived from an env snapshot in LDS
     static_assert(F % 8 == 0 && HID % 32 == 0, "shape");
     static_assert(PF * 64 * 4 <= PPO_PACK_PAD, "the ring reads PF groups past the end of a packed weight stream: padding must cover it");
@@ -198,10 +209,13 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
         if constexpr (IMITATE) { forced.ab = a.actions[sid]; forced.adv = a.adv ? a.adv[sid] : 1.0f; }
         // distillation: the weight likewise, and the target row: TPS coalesced float4 loads per lane (both lane halves read the
         // same 512 B of a tile, as both hold the same logits)
-        [[maybe_unused]] float4 qrow[DISTILL ? TPS : 1];
+        // the anchored train forward: Train's three inputs ahead of the activation stores (TailPre), and the target row likewise
+        [[maybe_unused]] float4 qrow[QROW ? TPS : 1];
         [[maybe_unused]] const float4* qsrc = nullptr;
-        if constexpr (DISTILL) {
-            forced.adv = a.adv ? a.adv[sid] : 1.0f;
+        constexpr bool APRE = ANCHOR && anchor_pre_early(F, HID, TPS, DEEP, SNAP);
+        if constexpr (APRE) { forced.ab = a.actions[sid]; forced.po = a.p_old[sid]; forced.adv = a.adv[sid]; }
+        if constexpr (DISTILL) forced.adv = a.adv ? a.adv[sid] : 1.0f;
+        if constexpr (QROW) {
             qsrc = reinterpret_cast<const float4*>(a.targets) + (size_t)sid * (32 * TPS) + j;
             if constexpr (QPRE) {
 #pragma unroll
@@ -447,7 +461,8 @@ __global__ __launch_bounds__(256, (FwdCfg<F, HID>::WPS)) void k_policy_fwd(FwdAr
         FSTAMP(4);
         int sampled = 0;
         if constexpr (VALUE) value_tail<TAIL, TPS>(a, state, act, l, lane, j, h, out_index, vtarget, vold);
-        else if constexpr (DISTILL) {
+        else if constexpr (QROW) {
+            if constexpr (ANCHOR && !APRE) { forced.ab = a.actions[sid]; forced.po = a.p_old[sid]; forced.adv = a.adv[sid]; }
             if constexpr (!QPRE) {
 #pragma unroll
                 for (int ts = 0; ts < TPS; ++ts) qrow[ts] = qsrc[ts * 32];
@@ -737,7 +752,7 @@ static int32_t dispatch_fwd_mode(FwdMode mode, ppo_policy_s* p, const FwdArgs& a
 #define MODE_CASE(M) case FwdMode::M: return dispatch_fwd<FwdMode::M>(p, a, B, tps)
     MODE_CASE(TrainSnap); MODE_CASE(Train); MODE_CASE(Imitate); MODE_CASE(ImitateSnap); MODE_CASE(ValuePredict);
     MODE_CASE(ValuePredictSnap); MODE_CASE(ValueTrainClip); MODE_CASE(ValueTrainClipSnap); MODE_CASE(ValueTrain); MODE_CASE(ValueTrainSnap);
-    MODE_CASE(Distill); MODE_CASE(DistillSnap); MODE_CASE(ProbsSnap);
+    MODE_CASE(Distill); MODE_CASE(DistillSnap); MODE_CASE(ProbsSnap); MODE_CASE(TrainAnchored); MODE_CASE(TrainAnchoredSnap);
 #undef MODE_CASE
     default: ppo_set_error("k_policy_fwd: not a mode chosen at run time"); return PPO_ERR_ARG;
     }
@@ -798,6 +813,21 @@ int32_t launch_distill_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int3
     a.c_over_B = (float)(entropy_weight / (double)B_global);
     ProfScope ps("k_policy_fwd_distill");
     return dispatch_fwd_mode(fwd_train_mode(Objective::Distill, ro->compact), p, a, B, ro->H / 32);
+}
+
+// KL-anchored train forward (FwdMode::TrainAnchored / TrainAnchoredSnap): the policy's train forward with beta
+// times the cross-entropy against target_ptr[transition][A] added to the surrogate; the divergence per state goes to
+// anchor_dst.  Only this fp32-MFMA forward has the mode
+int32_t launch_anchored_train_fwd(ppo_policy_s* p, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
+                                  double eps, double entropy_weight, const float* adv_col, const float* target_ptr, double beta,
+                                  float* anchor_dst) {
+    FwdArgs a = {};
+    fill_train(p, ro, idx_dev, B, B_global, a);
+    a.actions = ro->actions.p; a.p_old = ro->p_sel.p; a.adv = adv_col; a.ratio_out = p->ratio_out;
+    a.eps = eps; a.c_over_B = (float)(entropy_weight / (double)B_global);
+    a.targets = target_ptr; a.beta = beta; a.anchor_out = anchor_dst;
+    ProfScope ps("k_policy_fwd_train_anchored");
+    return dispatch_fwd_mode(fwd_train_mode(Objective::PolicyAnchored, ro->compact), p, a, B, ro->H / 32);
 }
 
 // probs_dev[b][A] of B states held as env snapshots [B][2V] in storage order (FwdMode::ProbsSnap: what ValuePredictSnap is to

@@ -58,9 +58,13 @@ struct FwdArgs {
     // FwdTail::Distill: the target distributions [T*N][A] by transition id, entry 128 ts + 4 j + i of a row as probs_out and
     // full_probs hold it.  Appended last
     const float* targets;
+    // FwdTail::TrainAnchored: the coefficient beta of the penalty towards the target rows (a.targets), and,
+    // optional, anchor_out[state] = the divergence KL(q' || pi) of every state of the minibatch.  Appended last
+    double beta; float* anchor_out;
 };
 // the aliases move nothing: these are the layout every kernel was built with
-static_assert(sizeof(FwdArgs) == 520 && offsetof(FwdArgs, vdelta_out) == 504 && offsetof(FwdArgs, targets) == 512, "FwdArgs layout");
+static_assert(sizeof(FwdArgs) == 536 && offsetof(FwdArgs, vdelta_out) == 504 && offsetof(FwdArgs, targets) == 512 &&
+              offsetof(FwdArgs, beta) == 520, "FwdArgs layout");
 
 // value of lane (lane ^ OFF), OFF < 32.  Same lane mapping as __shfl_xor (which hipcc lowers to ds_bpermute_b32: an
 // LDS round trip of ~100+ cycles per step, fully exposed in the one-or-two-waves-per-SIMD kernels here), but as DPP
@@ -126,6 +130,8 @@ __device__ __forceinline__ float smoothed_entropy(const float (&p)[TPS][4], floa
 // Imitate: Train's outputs for the cross-entropy of the action in pre->ab, weighted by max(pre->adv, 0); pre is required.
 // Distill: Train's outputs for the cross-entropy against the state's target row, weighted like Imitate; pre (adv)
 // and qrow are required: qrow[ts] = entries 128 ts + 4 j .. + 3 of a.targets' row sid, the caller's fetch (registers).
+// TrainAnchored: Train's surrogate plus a.beta times Distill's cross-entropy against the target row; pre (ab, po,
+// adv) and qrow are required.
 // Tempered / Greedy (selection rules): Sample on the logits times a.inv_temperature; Tempered samples like Sample,
 // Greedy takes the first maximum of p instead (tick_val unused).  l is scaled in place.
 // Truncated: Tempered on the top-k / nucleus truncation of the tempered p, renormalised; a.top_k (0: all),
@@ -449,6 +455,94 @@ __device__ __forceinline__ int policy_tail(const FwdArgs& a, const int64_t state
             }
         }
         if (lane == 0) { a.loss_terms[state * 2] = (double)(w * ce); a.loss_terms[state * 2 + 1] = (double)(-hl); }
+    }
+    if (TAIL == FwdTail::TrainAnchored) {
+        // KL-anchored PPO: the clipped surrogate and the entropy term of Train plus beta times Distill's
+        // cross-entropy against the state's target row q -- a penalty beta KL(q' || pi) up to the targets' entropy, which has no
+        // gradient.  The surrogate (gain, fp64 clip, unclipped, minval, dsel, ratio_out) is Train's term for term; q', Qs and ce
+        // are Distill's with its weight w replaced by beta: betaB = (float)beta * inv_B.  Order of dL/dlogit_k:
+        //     dy_k = dy_round(betaB * (p_k * Qs - q'_k) + p_k * (dp_k - dot))
+        // Distill's expression with Train's second summand (dp carries dsel at k == a, dot is formed from that dp).  With an
+        // advantage of 0 dsel is -0 and the line is Distill's at w = beta; with beta == 0 the first summand is a zero and the
+        // line is Train's value (an exact -0 of Train's on a row of an inactive quad, where p == 0, comes out as +0).
+        // kl = sum over q'_k > 0 of q'_k (log q'_k - ((l_k - m) - log S)) in fp32, the softmax's reduction order.  Nothing
+        // divides by a probability: a target on an action whose exp(l - m) underflows keeps loss, gradient and kl finite
+        const int ab = pre->ab;
+        const float po = pre->po;
+        const float adv = pre->adv;
+        float cand = 0.0f;
+#pragma unroll
+        for (int ts = 0; ts < TPS; ++ts)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) cand = ((ab >> 7) == ts && (ab & 3) == i) ? p[ts][i] : cand;
+        const float ps = __shfl(cand, (ab & 127) >> 2);
+        const float gain = ps / po * adv;
+        // (opaque per-state copies of the two scalar arguments: 1 + eps, 1 - eps, (float)beta and beta / B are then formed here,
+        // a handful of operations per state, instead of being hoisted out of the state loop into registers that the tile loop
+        // spills -- 36 bytes of scratch per lane in the deep snapshot instantiations, as FwdMode::TrainSnap has them)
+        double eps = a.eps, beta = a.beta;
+        asm volatile("" : "+s"(eps), "+s"(beta));
+        const double clip = adv >= 0.0f ? (1.0 + eps) * (double)adv : (1.0 - eps) * (double)adv;
+        const bool unclipped = (double)gain < clip;
+        const double minval = unclipped ? (double)gain : clip;
+        float q[TPS][4];
+        float qs = 0.0f;
+#pragma unroll
+        for (int ts = 0; ts < TPS; ++ts) {
+            const float4 v = qrow[ts];
+            q[ts][0] = on[ts] ? v.x : 0.0f; q[ts][1] = on[ts] ? v.y : 0.0f;
+            q[ts][2] = on[ts] ? v.z : 0.0f; q[ts][3] = on[ts] ? v.w : 0.0f;
+            const float st = ((q[ts][0] + q[ts][1]) + q[ts][2]) + q[ts][3];
+            qs = (ts == 0) ? st : qs + st;                   // tile partials in tile order, then the butterfly
+        }
+        qs = wave32_sum(qs);
+        const float ls = logf(ssum);
+        float ce = 0.0f, kl = 0.0f;
+#pragma unroll
+        for (int ts = 0; ts < TPS; ++ts) {
+            float t[4], u[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float lp = (l[ts][i] - m) - ls;
+                t[i] = (q[ts][i] == 0.0f) ? 0.0f : q[ts][i] * lp;
+                u[i] = (q[ts][i] > 0.0f) ? q[ts][i] * (logf(q[ts][i]) - lp) : 0.0f;
+            }
+            const float st = ((t[0] + t[1]) + t[2]) + t[3];
+            const float su = ((u[0] + u[1]) + u[2]) + u[3];
+            ce = (ts == 0) ? st : ce + st;
+            kl = (ts == 0) ? su : kl + su;
+        }
+        ce = wave32_sum(ce);
+        kl = wave32_sum(kl);
+        float lg[TPS][4];
+        const float hl = smoothed_entropy(p, lg);
+        float dp[TPS][4], dot = 0.0f;
+        const float dsel = unclipped ? -(a.inv_B * adv / po) : 0.0f;
+#pragma unroll
+        for (int ts = 0; ts < TPS; ++ts)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                dp[ts][i] = a.c_over_B * (lg[ts][i] + 1.0f) + ((128 * ts + 4 * j + i == ab) ? dsel : 0.0f);
+                dot += p[ts][i] * dp[ts][i];
+            }
+        dot = wave32_sum(dot);
+        const float beta_f = (float)beta;
+        const float betaB = beta_f * a.inv_B;
+        if (h == 0) {
+#pragma unroll
+            for (int ts = 0; ts < TPS; ++ts) {
+                float dy[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    dy[i] = dy_round<DYBF16>(betaB * (p[ts][i] * qs - q[ts][i]) + p[ts][i] * (dp[ts][i] - dot));
+                a.dY[((size_t)state * TPS + ts) * 32 + j] = make_float4(dy[0], dy[1], dy[2], dy[3]);
+            }
+        }
+        if (lane == 0) {
+            a.loss_terms[state * 2] = minval + (double)(beta_f * ce); a.loss_terms[state * 2 + 1] = (double)(-hl);
+            if (a.ratio_out) a.ratio_out[state] = ps / po;
+            if (a.anchor_out) a.anchor_out[state] = kl;
+        }
     }
     if (TAIL == FwdTail::Train) {
         const int ab = pre ? pre->ab : a.actions[sid];

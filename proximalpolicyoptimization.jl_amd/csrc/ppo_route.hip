@@ -44,7 +44,7 @@ int32_t ppo_set_rollout_split_max_envs(int64_t envs) { g_knobs.rollout_split_max
 
 TrainRoute train_route(int32_t dtype, int F, int HID, int L, int H, bool compact, int64_t states, const PpoKnobs& k, Objective obj) {
     // (value: the objectives only the fp32-MFMA forward has a tail for -- a critic's mse, the imitation cross-entropy and the
-    // distillation cross-entropy)
+    // distillation cross-entropy -- and the policy's KL-anchored objective, which takes the same branch)
     const bool f32 = dtype == PPO_DTYPE_F32, value = obj != Objective::Policy;
     const int tps = H / 32;
     const int64_t tiles = states * tps;
@@ -52,6 +52,7 @@ TrainRoute train_route(int32_t dtype, int F, int HID, int L, int H, bool compact
     if (value) {                                        // what the fp32-MFMA forward refuses, before anything else
         if (!f32 && obj == Objective::Imitate) return {TrainFwd::None, TrainBwd::None, "imitation training of a bf16-dtype policy is not supported: the imitation modes exist in the fp32-MFMA forward only"};
         if (!f32 && obj == Objective::Distill) return {TrainFwd::None, TrainBwd::None, "distillation into a bf16-dtype student is not supported: the distillation modes exist in the fp32-MFMA forward only"};
+        if (!f32 && obj == Objective::PolicyAnchored) return {TrainFwd::None, TrainBwd::None, "KL-anchored training of a bf16-dtype policy is not supported: the anchored modes exist in the fp32-MFMA forward only"};
         if (!f32) return {TrainFwd::None, TrainBwd::None, "a bf16-dtype critic is not supported: the value modes exist in the fp32-MFMA forward only"};
         if (F != 72 && tps != 1) return {TrainFwd::None, TrainBwd::None, "unsupported policy/state shape (F,HID,H) for the gfx950 kernels"};
         if (F != 72 && compact) return {TrainFwd::None, TrainBwd::None, "compact rollouts need the built-in env's F = 72"};
@@ -136,4 +137,8 @@ extern "C" int32_t ppo_debug_imitate_route(int32_t dtype, int32_t F, int32_t hid
 extern "C" int32_t ppo_debug_distill_route(int32_t dtype, int32_t F, int32_t hid, int32_t L, int32_t H, int32_t compact,
                                            int64_t states, char* fwd, char* bwd, int64_t cap) {
     return debug_route("ppo_debug_distill_route", Objective::Distill, dtype, F, hid, L, H, compact, states, fwd, bwd, cap);
+}
+extern "C" int32_t ppo_debug_anchor_route(int32_t dtype, int32_t F, int32_t hid, int32_t L, int32_t H, int32_t compact,
+                                          int64_t states, char* fwd, char* bwd, int64_t cap) {
+    return debug_route("ppo_debug_anchor_route", Objective::PolicyAnchored, dtype, F, hid, L, H, compact, states, fwd, bwd, cap);
 }

@@ -4,6 +4,7 @@
 //                    sum(-log r), sum((r - 1) - log r), count(|r - 1| > eps), n  ->  old_approx_kl, approx_kl, clip_fraction
 //   k_value_clip_stats over the changes delta = V - V_old the critic's loss tail stored while a value clip is set:
 //                    count(|delta| > c), sum(delta^2), n  ->  clip_fraction, mean_sq_change
+//   k_sum_stats      over a column of floats, e.g. the per-state anchor divergences the anchored loss tail stored: sum x, n
 //   k_value_moments  over the valid transitions of a rollout buffer: the five shifted sums behind the critic's explained
 //                    variance 1 - Var(t - V) / Var(t)
 // All in fp64 with a FIXED summation order that depends on the element count only: every thread walks its 16-byte groups
@@ -109,6 +110,21 @@ __global__ __launch_bounds__(STATS_THREADS) void k_value_clip_stats(const float*
     block_sum_store<3>(acc, partials + (size_t)blockIdx.x * 3);
 }
 
+// x: 16-byte aligned
+__global__ __launch_bounds__(STATS_THREADS) void k_sum_stats(const float* __restrict__ x, int64_t n, double* __restrict__ partials) {
+    double acc[2] = {0.0, 0.0};
+    const int64_t n4 = n >> 2, total = (int64_t)gridDim.x * STATS_THREADS;
+    const int64_t g = (int64_t)blockIdx.x * STATS_THREADS + threadIdx.x;
+    for (int64_t q = g; q < n4; q += total) {
+        const float4 v = reinterpret_cast<const float4*>(x)[q];
+        acc[0] = (((acc[0] + (double)v.x) + (double)v.y) + (double)v.z) + (double)v.w;
+        acc[1] = acc[1] + 4.0;
+    }
+    const int64_t i = (n4 << 2) + g;                       // the n & 3 elements behind the last whole group
+    if (i < n) { acc[0] = acc[0] + (double)x[i]; acc[1] = acc[1] + 1.0; }
+    block_sum_store<2>(acc, partials + (size_t)blockIdx.x * 2);
+}
+
 __device__ __forceinline__ void moment_term(const float t, const float v, const uint8_t on, const double st, const double sd,
                                             double (&acc)[5]) {
     if (!on) return;
@@ -159,6 +175,15 @@ int32_t launch_value_clip_stats(const float* delta, int64_t n, float c, double* 
     return PPO_OK;
 }
 
+int32_t launch_sum_stats(const float* col, int64_t n, double* part) {
+    const int blocks = stats_blocks(n);
+    ProfScope ps("k_sum_stats");
+    hipLaunchKernelGGL(k_sum_stats, dim3(blocks), dim3(STATS_THREADS), 0, ppo_stream(), col, n, part + STATS_RESULT);
+    hipLaunchKernelGGL(k_stats_finish<2>, dim3(1), dim3(64), 0, ppo_stream(), part + STATS_RESULT, blocks, part);
+    HIP_TRY(hipGetLastError());
+    return PPO_OK;
+}
+
 int32_t launch_value_moments(const float* target, const float* values, const uint8_t* valid, const int32_t* first_id,
                              int64_t n, double* part) {
     const int blocks = stats_blocks(n);
@@ -192,6 +217,14 @@ extern "C" int32_t ppo_debug_value_clip_stats(const float* delta, int64_t n, flo
     PPO_TRY(col.alloc((size_t)n)); PPO_TRY(h2d(col.p, delta, (size_t)n));
     PPO_TRY(launch_value_clip_stats(col.p, n, c, part.p));
     return d2h(out3, part.p, 3);
+}
+
+extern "C" int32_t ppo_debug_sum_stats(const float* x, int64_t n, double* out2) {
+    DevBuf<double> part; DevBuf<float> col;
+    PPO_TRY(debug_stats_begin("ppo_debug_sum_stats", x, out2, n, part));
+    PPO_TRY(col.alloc((size_t)n)); PPO_TRY(h2d(col.p, x, (size_t)n));
+    PPO_TRY(launch_sum_stats(col.p, n, part.p));
+    return d2h(out2, part.p, 2);
 }
 
 extern "C" int32_t ppo_debug_value_moments(const float* t, const float* v, const uint8_t* valid, int64_t first_id, int64_t n,

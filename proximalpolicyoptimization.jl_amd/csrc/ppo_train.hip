@@ -49,8 +49,10 @@ static int32_t advantage_column(ppo_policy_s* net, ppo_rollouts_s* ro, const int
 static int32_t train_pass_dev(ppo_policy_s* net, ppo_rollouts_s* ro, const int32_t* idx_dev, int64_t B, int64_t B_global,
                               const TrainObjective& obj, ppo_adam_s* fuse_opt = nullptr, float* fuse_hist2 = nullptr) {
     PPO_TRY(train_reserve(net, B * (ro->H / 32), ro->compact));
-    const bool policy = obj.kind == Objective::Policy, imitate = obj.kind == Objective::Imitate, distill = obj.kind == Objective::Distill;
-    const float* adv = nullptr;                             // imitation / distillation with uniform weights: no column
+    // (the KL-anchored objective is the policy's: advantages and ratios as for Objective::Policy, a forward of its own)
+    const bool anchored = obj.kind == Objective::PolicyAnchored;
+    const bool policy = obj.kind == Objective::Policy || anchored, imitate = obj.kind == Objective::Imitate, distill = obj.kind == Objective::Distill;
+    const float* adv = nullptr;                            // imitation / distillation with uniform weights: no column
     if (policy || ((imitate || distill) && obj.weight_mode == PPO_IMITATE_POSITIVE_ADVANTAGE))
         PPO_TRY(advantage_column(net, ro, idx_dev, B, obj.adv_mode, &adv));
     if (policy) {
@@ -71,6 +73,16 @@ static int32_t train_pass_dev(ppo_policy_s* net, ppo_rollouts_s* ro, const int32
     }
     if (imitate) PPO_TRY(launch_imitate_train_fwd(net, ro, idx_dev, B, B_global, obj.entropy_weight, adv));
     else if (distill) PPO_TRY(launch_distill_train_fwd(net, ro, idx_dev, B, B_global, obj.entropy_weight, adv, obj.distill_targets));
+    else if (anchored) {
+        // the divergence per state: the caller's slice of an epoch column (train_epochs), else the policy's minibatch buffer
+        float* kl_dst = obj.anchor_dst;
+        if (!kl_dst) {
+            PPO_TRY(net->anchor.alloc((size_t)net->cap_tiles));
+            kl_dst = net->anchor.p; net->anchor_last = kl_dst; net->anchor_last_n = (int64_t)net->anchor.n;
+        }
+        PPO_TRY(launch_anchored_train_fwd(net, ro, idx_dev, B, B_global, obj.eps, obj.entropy_weight, adv, obj.anchor_targets,
+                                          obj.anchor_coef, kl_dst));
+    }
     else if (!policy) {
         // PPO's clipped value loss while the critic handle has a clip range: against the buffer's values of before the update
         // (the callers have checked that they are there), V - vold going to the caller's slice of an epoch column if any
@@ -120,6 +132,31 @@ static int32_t gather_minibatch(ppo_policy_s* net, ppo_rollouts_s* ro, const int
     return launch_gather_index(ro, pos.p, B, net->idx.p, net->err.p);
 }
 
+// KL anchor: while the policy handle has one, the policy's pass runs Objective::PolicyAnchored with the handle's
+// coefficient against the buffer's rows of the handle's source.  What the distillation entry points refuse is refused here,
+// before anything is launched: a source not filled / not recorded for these rollouts, a disk sink, a bf16-dtype policy
+static int32_t anchor_objective(const char* who, ppo_policy_s* pol, ppo_rollouts_s* ro, TrainObjective& obj) {
+    if (pol->anchor_source == PPO_ANCHOR_OFF) return PPO_OK;
+    if (pol->dtype != PPO_DTYPE_F32) {
+        ppo_set_error(std::string(who) + ": KL-anchored training of a bf16-dtype policy is not supported: the anchored modes exist in the fp32-MFMA forward only");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    if (ro->sink) {
+        ppo_set_error(std::string(who) + ": a KL anchor on a buffer with a disk sink attached is not supported");
+        return PPO_ERR_UNSUPPORTED;
+    }
+    if (pol->anchor_source == PPO_TARGETS_COLUMN) {
+        ARG_CHECK(ro->targets.p && ro->targets_T == ro->T && ro->T >= 1, std::string(who) + ": KL anchor: the target column is not filled for these rollouts (ppo_rollouts_fill_targets or ppo_rollouts_set_targets first)");
+        obj.anchor_targets = ro->targets.p;
+    } else {
+        ARG_CHECK(ro->full_probs.p && ro->probs_T == ro->T && ro->T >= 1, std::string(who) + ": KL anchor: no recorded distributions for these rollouts (collect them with record_probs)");
+        obj.anchor_targets = ro->full_probs.p;
+    }
+    obj.kind = Objective::PolicyAnchored;
+    obj.anchor_coef = pol->anchor_coef;
+    return PPO_OK;
+}
+
 int32_t ppo_forward_backward(ppo_policy_t pol, ppo_rollouts_t ro, const int64_t* sample_idx, int64_t B,
                              int64_t B_global, double epsilon, double entropy_weight, int32_t adv_mode) {
     ARG_CHECK(pol && ro && sample_idx, "step_batch!: null argument");
@@ -127,10 +164,11 @@ int32_t ppo_forward_backward(ppo_policy_t pol, ppo_rollouts_t ro, const int64_t*
     ARG_CHECK(B_global >= B, "step_batch!: B_global < B");
     ARG_CHECK(pol->F == ro->F && (ro->H == 32 || ro->H == 128), "step_batch!: shape mismatch");
     if (adv_mode < PPO_ADV_RETURNS || adv_mode > PPO_ADV_GAE_NORMALISED) { ppo_set_error("batch_advantage: unknown advantage mode"); return PPO_ERR_UNSUPPORTED; }
-    DevBuf<int64_t> pos;
-    PPO_TRY(gather_minibatch(pol, ro, sample_idx, B, pos));
     TrainObjective obj = {Objective::Policy};
     obj.eps = epsilon; obj.entropy_weight = entropy_weight; obj.adv_mode = adv_mode;
+    PPO_TRY(anchor_objective("step_batch!", pol, ro, obj));
+    DevBuf<int64_t> pos;
+    PPO_TRY(gather_minibatch(pol, ro, sample_idx, B, pos));
     PPO_TRY(train_pass_dev(pol, ro, pol->idx.p, B, B_global, obj));
     HIP_TRY(hipStreamSynchronize(ppo_stream()));
     return PPO_OK;
@@ -242,7 +280,12 @@ static int32_t sum_rank_sums(double* st, int k, DevBuf<float>& sx, int32_t rank,
 // the two per-batch loss columns (ppo and entropy loss; a critic's mse is column 0).  world > 1: data-parallel, through the
 // all-reduce hook.  Objective::Policy adds the per-epoch ratio statistics and the target_kl stop, Objective::Value the per-epoch
 // value-clip statistics while the critic handle has a value clip; with world > 1 either kind is summed over the ranks.
-// Objective::Imitate and Objective::Distill keep no statistics of either kind, leave the handle's as they are and never stop early
+// Objective::Imitate and Objective::Distill keep no statistics of either kind, leave the handle's as they are and never stop early.
+// Objective::PolicyAnchored is Objective::Policy in all of this and adds the per-epoch mean anchor KL and PPO's coefficient rule
+// (DESIGN.md 7r): every minibatch's forward stores its divergences in its slice of one column, one reduction per epoch reads it;
+// the coefficient starts from the handle's, is adapted on the host behind every epoch while the handle has an anchor target, and
+// the adapted value goes back to the handle.  With world > 1 the rule reads the sums of all ranks, so every rank keeps the same
+// coefficient
 static int32_t train_epochs(ppo_policy_s* net, ppo_adam_s* opt, ppo_rollouts_s* ro, const TrainObjective& obj, int64_t batch_size,
                             int32_t num_epochs, const int64_t* perm, uint64_t seed, int32_t rank, int32_t world,
                             ppo_allreduce_fn allreduce, void* allreduce_ctx, double* hist0, double* hist1, double* lr_hist) {
@@ -264,7 +307,8 @@ static int32_t train_epochs(ppo_policy_s* net, ppo_adam_s* opt, ppo_rollouts_s* 
     // per-epoch statistics of the policy's probability ratios (ppo_stats.hip), while a target_kl is set: every minibatch's
     // train forward stores its ratios in its slice of one column, one reduction per epoch reads the column, its four sums come
     // back with the loss history.  target_kl == 0: nothing is stored, launched or copied, the statistics are NaN
-    const bool policy = obj.kind == Objective::Policy;
+    const bool anchored = obj.kind == Objective::PolicyAnchored;
+    const bool policy = obj.kind == Objective::Policy || anchored;
     // likewise for a critic while a value clip is set: V - vold of every minibatch in its slice of one column, one reduction per
     // epoch (count(|delta| > c), sum delta^2, n).  value_clip == 0: nothing is allocated, stored, launched or copied
     const bool value = obj.kind == Objective::Value;
@@ -289,6 +333,14 @@ static int32_t train_epochs(ppo_policy_s* net, ppo_adam_s* opt, ppo_rollouts_s* 
         }
         net->stats_kl.clear(); net->stats_old_kl.clear(); net->stats_clip.clear(); net->stats_stopped = 0;
         if (world > 1 && target_kl > 0) PPO_TRY(sx.alloc((size_t)12 * world));
+        net->astats_kl.clear(); net->astats_coef.clear();
+    }
+    double coef = obj.anchor_coef;                                     // the coefficient of the epoch at hand
+    if (anchored) {
+        if (net->anchor_col.n < (size_t)len) { net->anchor_last = nullptr; net->anchor_last_n = 0; }
+        PPO_TRY(net->anchor_col.alloc((size_t)len));
+        PPO_TRY(net->stats_part.alloc(stats_part_doubles()));
+        if (world > 1) PPO_TRY(sx.alloc((size_t)std::max(6, target_kl > 0 ? 12 : 6) * world));
     }
     for (int32_t ep = 0; ep < num_epochs; ++ep) {
         if (perm) {                                                    // randperm(num_data)  src/train.jl:93
@@ -309,6 +361,7 @@ static int32_t train_epochs(ppo_policy_s* net, ppo_adam_s* opt, ppo_rollouts_s* 
             TrainObjective o = obj;
             o.ratio_dst = stats ? net->ratio_col.p + start : nullptr;
             o.vdelta_dst = vstats ? net->vdelta_col.p + start : nullptr;
+            if (anchored) { o.anchor_dst = net->anchor_col.p + start; o.anchor_coef = coef; }
             if (B > 0) PPO_TRY(train_pass_dev(net, ro, order.p + start, B, Bg, o, fused ? opt : nullptr, hist.p + 2 * b));
             else HIP_TRY(hipMemsetAsync(net->grad.p, 0, (size_t)(net->np + 2) * sizeof(float), ppo_stream()));   // shard exhausted
             if (allreduce) {                     // every rank of a data-parallel run; a world of 1 may pass it too
@@ -331,6 +384,12 @@ static int32_t train_epochs(ppo_policy_s* net, ppo_adam_s* opt, ppo_rollouts_s* 
             net->vdelta_n = len;
             HIP_TRY(hipMemcpyAsync(vst, net->stats_part.p, sizeof(vst), hipMemcpyDeviceToHost, ppo_stream()));  // waited for just below
         }
+        double ast[2] = {NAN, 1.0};                                                  // sum of the anchor divergences, n
+        if (anchored) {
+            PPO_TRY(launch_sum_stats(net->anchor_col.p, len, net->stats_part.p));    // behind the copy above, in stream order
+            net->anchor_last = net->anchor_col.p; net->anchor_last_n = len;
+            HIP_TRY(hipMemcpyAsync(ast, net->stats_part.p, sizeof(ast), hipMemcpyDeviceToHost, ppo_stream()));  // waited for just below
+        }
         PPO_TRY(d2h(hh.data(), hist.p, (size_t)nb * 2));
         double s0 = 0.0, s1 = 0.0;
         for (int64_t i = 0; i < nb; ++i) { s0 += hh[2 * i]; s1 += hh[2 * i + 1]; }
@@ -342,6 +401,19 @@ static int32_t train_epochs(ppo_policy_s* net, ppo_adam_s* opt, ppo_rollouts_s* 
             net->vstats_clip.push_back(vst[0] / vst[2]); net->vstats_msq.push_back(vst[1] / vst[2]);
         }
         if (!policy) continue;
+        if (anchored) {
+            if (world > 1) PPO_TRY(sum_rank_sums(ast, 2, sx, rank, world, allreduce, allreduce_ctx, "anchor statistics"));
+            const double akl = ast[0] / ast[1];
+            net->astats_kl.push_back(akl); net->astats_coef.push_back(coef);
+            // PPO's rule (Schulman et al. 2017, section 4) around the handle's target d: above 1.5 d the coefficient doubles,
+            // below d / 1.5 it halves (a NaN mean compares false twice and leaves it)
+            const double d = net->anchor_target;
+            if (d > 0.0) {
+                if (akl > 1.5 * d && std::isfinite(coef * 2.0)) coef *= 2.0;
+                else if (akl < d / 1.5) coef /= 2.0;
+                net->anchor_coef = coef;
+            }
+        }
         if (world > 1 && target_kl > 0) PPO_TRY(sum_rank_sums(st, 4, sx, rank, world, allreduce, allreduce_ctx, "ratio statistics"));
         const double kl = st[1] / st[3];
         net->stats_kl.push_back(kl); net->stats_old_kl.push_back(st[0] / st[3]); net->stats_clip.push_back(st[2] / st[3]);
@@ -368,6 +440,7 @@ int32_t ppo_train(ppo_policy_t pol, ppo_adam_t opt, ppo_rollouts_t ro, double ep
     if (adv_mode < PPO_ADV_RETURNS || adv_mode > PPO_ADV_GAE_NORMALISED) { ppo_set_error("batch_advantage: unknown advantage mode"); return PPO_ERR_UNSUPPORTED; }
     TrainObjective obj = {Objective::Policy};
     obj.eps = epsilon; obj.entropy_weight = entropy_weight; obj.adv_mode = adv_mode;
+    PPO_TRY(anchor_objective("ppo_train!", pol, ro, obj));
     return train_epochs(pol, opt, ro, obj, batch_size, num_epochs, perm, seed, rank, world, allreduce, allreduce_ctx, ppo_hist,
                         entropy_hist, lr_hist);
 }
@@ -544,6 +617,46 @@ int32_t ppo_policy_last_train_stats(ppo_policy_t pol, int32_t cap, int32_t* epoc
         if (clip_fraction) clip_fraction[i] = pol->stats_clip[i];
     }
     return PPO_OK;
+}
+
+// ---- KL anchor (no reference op): a property of the policy handle
+int32_t ppo_policy_set_kl_anchor(ppo_policy_t pol, double coef, int32_t source, double target) {
+    // (the arguments are judged before the handle, like ppo_policy_set_target_kl's)
+    if (source != PPO_ANCHOR_OFF && source != PPO_TARGETS_COLUMN && source != PPO_TARGETS_RECORDED) { ppo_set_error("policy_set_kl_anchor: unknown target source"); return PPO_ERR_UNSUPPORTED; }
+    if (source != PPO_ANCHOR_OFF) {
+        ARG_CHECK(coef >= 0.0 && std::isfinite(coef), "policy_set_kl_anchor: the coefficient must be finite and >= 0");      // NaN fails it too
+        ARG_CHECK(target >= 0.0 && std::isfinite(target), "policy_set_kl_anchor: the target must be 0 (fixed coefficient) or positive and finite");
+    }
+    ARG_CHECK(pol, "policy_set_kl_anchor: null policy");
+    if (source == PPO_ANCHOR_OFF) { pol->anchor_source = PPO_ANCHOR_OFF; pol->anchor_coef = 0.0; pol->anchor_target = 0.0; return PPO_OK; }
+    pol->anchor_coef = coef; pol->anchor_source = source; pol->anchor_target = target;
+    return PPO_OK;
+}
+int32_t ppo_policy_get_kl_anchor(ppo_policy_t pol, double* coef, int32_t* source, double* target) {
+    ARG_CHECK(pol, "policy_get_kl_anchor: null policy");
+    if (coef) *coef = pol->anchor_coef;
+    if (source) *source = pol->anchor_source;
+    if (target) *target = pol->anchor_target;
+    return PPO_OK;
+}
+int32_t ppo_policy_last_anchor_stats(ppo_policy_t pol, int32_t cap, int32_t* n, double* kl, double* coef) {
+    ARG_CHECK(pol && cap >= 0, "policy_last_anchor_stats: null policy or negative capacity");
+    const size_t k = pol->astats_kl.size(), m = std::min(k, (size_t)cap);
+    if (n) *n = (int32_t)k;
+    for (size_t i = 0; i < m; ++i) {
+        if (kl) kl[i] = pol->astats_kl[i];
+        if (coef) coef[i] = pol->astats_coef[i];
+    }
+    return PPO_OK;
+}
+
+// diagnostic for the tests (not part of include/ppo_hip.h), like ppo_debug_train_ratios: the anchor divergence per state the
+// anchored loss tail stored -- of the latest forward in minibatch order, or, after ppo_train, of its latest epoch in the order
+// of that epoch's permutation
+int32_t ppo_debug_anchor_kl(ppo_policy_t pol, int64_t n, float* out) {
+    ARG_CHECK(pol && out, "ppo_debug_anchor_kl: null argument");
+    ARG_CHECK(pol->anchor_last && n >= 1 && n <= pol->anchor_last_n, "ppo_debug_anchor_kl: no divergences stored, or n out of range");
+    return d2h(out, pol->anchor_last, (size_t)n);
 }
 
 // ---- PPO's clipped value loss for a critic (no reference op): the clip range is a property of the handle
